@@ -9,13 +9,18 @@ around exactly K steps, max over ranks, ONE JSON line from rank 0) is kept; torc
 used only as rendezvous/barrier plumbing when launched with N > 1, the product path is ctypes ->
 libmsim.so.
 
-    python bench.py                      # 1 GPU, K=3, W=1
+    python bench.py                      # 1 GPU, K=20, W=5: the headline workload only
+    python bench.py --full               # + everything else the line can carry (below)
+    python bench.py --dump-outputs DIR   # + what the last timed step computed, as DIR/<name>.npy
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Extra keys in the JSON line: "roofline" (rewrite kernel vs HBM peak, measured live with HIP events
-on the library's stream) and "cpu_baseline" (the CPU oracle timed on a bounded sample, rank 0; its
-"matches_gpu" says whether that sample genome, pushed through `one_step` -- the timed function, in the
-timed call order -- on the GPU, gives the oracle's bytes).
+A plain run sets up, warms up, times the K steps of the headline workload and prints the line; its
+"roofline" (rewrite kernel vs HBM peak, measured live with HIP events on the library's stream) takes its
+traffic from the last recorded profile.  With --full the line also carries the live rocprofv3 traffic,
+"cpu_baseline" (the CPU oracle timed on a bounded sample, rank 0; its "matches_gpu" says whether that
+sample genome, pushed through `one_step` -- the timed function, in the timed call order -- on the GPU,
+gives the oracle's bytes), "secondary" (the other workloads, fast mode, the CLI end to end),
+"amdahl_ceiling", "predicted_one_genome_scaling" and, for N > 1, the other scaling mode and the gather.
 
 What N > 1 means here.  The reference draws from two global generators contig after contig
 (mutator.py:111-141), so in this bit-identical mode ONE genome over N GPUs is Amdahl-bound: every rank
@@ -178,6 +183,56 @@ def one_step(eng, sim, cids, my_contigs, seed=42, plan_descriptors=None, lengths
     eng.seed(seed, seed)
     run_sharded_pass(eng, sim, cids, my_contigs, plan_descriptors or mm.plan_descriptors, lengths=lengths)
     eng.sync()
+
+
+DUMP_WINDOWS, DUMP_WINDOW = 8, 8192            # mutated-sequence sample: windows per contig x bases per window
+DUMP_RECORDS = 16384                           # record-table sample per contig
+DUMP_POOL = 16384                              # insert-pool bytes per contig (its head)
+DUMP_LIMIT = 64 << 20
+
+
+def dump_outputs(eng, cids, owned, out_dir, seed=20240607):
+    """What the last timed step left in HBM for this rank's contigs, as float32 / float64 .npy files in `out_dir`: the sizes
+    and the device checksum of every mutated contig (its whole stream), fixed seeded samples of the mutated sequences and of
+    the record tables, the head of each insert pool and both MT19937 streams' final states.  The sample positions depend only
+    on `seed`, the contig index and the sizes, so two builds that computed the same step write the same files."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    owned = sorted(owned)
+    sizes = np.zeros((len(owned), 4), dtype=np.float64)          # contig index, mutated length, records, insert-pool bytes
+    checksum = np.zeros((len(owned), 2), dtype=np.float64)       # device checksum of the whole mutated stream: high, low 32 bits
+    seq = np.full((len(owned) * DUMP_WINDOWS, DUMP_WINDOW + 2), -1.0, dtype=np.float32)   # contig, offset, bases (-1: past the end)
+    pool = np.full((len(owned), DUMP_POOL), -1.0, dtype=np.float32)
+    recs = []
+    for j, i in enumerate(owned):
+        cid = cids[i]
+        out_len, n_rec, n_pool = eng.result_sizes(cid)
+        sizes[j] = (i, out_len, n_rec, n_pool)
+        s = eng.result_checksum(cid)
+        checksum[j] = (s >> 32, s & 0xFFFFFFFF)
+        rng = np.random.default_rng([seed, i])
+        w = min(DUMP_WINDOW, out_len)
+        for k, off in enumerate(np.sort(rng.integers(0, out_len - w + 1, DUMP_WINDOWS))):
+            row = seq[j * DUMP_WINDOWS + k]
+            row[0], row[1] = i, off
+            row[2:2 + w] = eng.fetch_sequence(cid, int(off), w)
+        r, p = eng.fetch_records(cid)
+        pick = np.sort(rng.choice(n_rec, min(DUMP_RECORDS, n_rec), replace=False)) if n_rec else np.zeros(0, dtype=np.int64)
+        r = r[pick]
+        recs.append(np.stack([np.full(len(pick), i), pick, r["pos"], r["stop"], r["extra"], r["type"], r["aux"]],
+                             axis=1).astype(np.float64))
+        pool[j, :min(n_pool, DUMP_POOL)] = p[:DUMP_POOL]
+    streams = np.zeros((2, 625), dtype=np.float64)               # 624 state words + position, per stream (0 = random, 1 = numpy)
+    for stream in (0, 1):
+        mt, pos = eng.get_mt_state(stream)
+        streams[stream, :624], streams[stream, 624] = mt, pos
+    arrays = {"contig_sizes": sizes, "sequence_checksum": checksum, "sequence_sample": seq,
+              "records_sample": np.concatenate(recs) if recs else np.zeros((0, 7)), "insert_pool_head": pool,
+              "mt_states": streams}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT, f"outputs to dump: {total} bytes > {DUMP_LIMIT}"
+    for name, v in arrays.items():
+        np.save(out_dir / f"{name}.npy", v)
 
 
 C3_FLAGS = ["-in", "0.001", "-inmin", "1", "-inmax", "50", "-de", "0.001", "-demin", "1", "-demax", "50",
@@ -714,6 +769,12 @@ def main():
                          "linearly).  The other mode is measured too and reported in the same line")
     ap.add_argument("--gather", action="store_true", help="(kept for compatibility: the gather is always measured for N > 1, strong)")
     ap.add_argument("--fast-only", action="store_true", help="(child of the N = 1 run) only the `--rng fast` secondary numbers, as one JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: live rocprofv3 traffic, secondary workloads, fast mode, "
+                         "CLI end to end, Amdahl ceiling, predicted scaling, CPU baseline, the other scaling mode and the gather")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rank 0's contigs: seeded samples of the "
+                         "mutated sequences and record tables, sizes, checksums, final stream states) as DIR/<name>.npy")
     a = ap.parse_args()
     if a.fast_only:
         from mutation_simulator_amd import _ffi
@@ -833,8 +894,10 @@ def main():
         return dt, eng.stats()
 
     dt, st = measure(a.workload, a.steps, a.warmup)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(eng, cids, mine, a.dump_outputs)
     line = None
-    LIVE_PMC[0] = world == 1 and not a.no_secondary and not os.environ.get("MSIM_BENCH_NO_PMC")
+    LIVE_PMC[0] = a.full and world == 1 and not a.no_secondary and not os.environ.get("MSIM_BENCH_NO_PMC")
     if rank == 0:
         total = sum(lengths) * (1 if strong else world)      # weak: every rank mutated a whole genome
         W = WORKLOADS[a.workload]
@@ -885,7 +948,7 @@ def main():
         gather_jobs.append((workload, out))
         return out
 
-    if strong:
+    if strong and a.full:
         sh = sharded_numbers(dt)
         if rank == 0:
             line["with_gather"] = sh["with_gather"]          # (replaced by the gather phase at the end)
@@ -911,7 +974,7 @@ def main():
                 fr = {"error": f"{type(e).__name__}: {e}"}
             if rank == 0:
                 line["one_genome_sharded_fast_rng"] = fr
-    elif world > 1:
+    elif world > 1 and a.full:
         dts_, _ = measure(a.workload, a.steps, 1, owned=parts[rank], step_seed=42)
         sh = sharded_numbers(dts_)
         if rank == 0:
@@ -927,17 +990,18 @@ def main():
     # What N GPUs can give ONE genome (strong scaling): the chain of both MT19937 streams runs over every contig on every
     # rank whatever N is; only emission + APPLY of the owned contigs shrink.  Measured, not modelled: a step that owns
     # nothing (msim_plan_chain for all 24 contigs) against the full step.
-    dtc, _ = measure(a.workload, a.steps, 1, owned=[], step_seed=42)
     dtf = dt
-    if strong:
-        dtf, _ = measure(a.workload, a.steps, 1, owned=everything, step_seed=42)
-    if rank == 0:
+    if a.full:
+        dtc, _ = measure(a.workload, a.steps, 1, owned=[], step_seed=42)
+        if strong:
+            dtf, _ = measure(a.workload, a.steps, 1, owned=everything, step_seed=42)
+    if rank == 0 and a.full:
         line["amdahl_ceiling"] = {"value": round(dtf / dtc, 3), "chain_only_ms_per_step": round(dtc / a.steps * 1e3, 3),
                                   "full_step_ms": round(dtf / a.steps * 1e3, 3),
                                   "what": "upper bound of the strong-scaling speed-up of one genome over N GPUs: full 1-GPU step / "
                                           "step of a rank that owns no contig (stream chain only); N independent genomes "
                                           "(weak_replicas / --scaling weak) scale linearly instead"}
-    if world == 1 and not a.no_secondary and a.workload == "c2":
+    if a.full and world == 1 and not a.no_secondary and a.workload == "c2":
         # BASELINE configs[2] and [3] on the same resident genome: 8 steps each after 2 warm-up steps (the first steps of a
         # workload still grow scratch buffers), same definition of a step
         sec = {}
@@ -970,7 +1034,7 @@ def main():
             except Exception as e:  # noqa: BLE001  (no tmpfs / disk space: the kernels' numbers above still stand)
                 sec[key] = {"error": f"{type(e).__name__}: {e}"}
         line["secondary"] = sec
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(a.cpu_sample, a.workload, device=device)      # bounded sample: ~6-10 s of CPU work
     printed = [False]
 

@@ -9,7 +9,7 @@ for w in c2 c3 c4 c4sv; do
   [ $w = c3 ] && python3 profiles/summarize_rocprof.py timeline $O/kf_$w/ks_results.db -6 120 2 k_fsplit_top > $O/timeline_fast_c3.txt 2>&1
   rm -rf $O/kf_$w
 done
-python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python3 - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r4ev/bench_default.json").read().strip().splitlines()[-1])

@@ -7,7 +7,7 @@ O=gpurun_out/r5ev; mkdir -p $O
 T="timeout -s KILL 240"
 # ---- 1. kernel traces: compatible mode (bench workloads) and the counter-based engine (tools/fast_steps.py)
 for w in c2 c3 c4 c4sv; do
-  $T rocprofv3 --kernel-trace --stats -d $O/ks_$w -o ks -- python3 bench.py --workload $w --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > $O/ks_$w.log 2>&1
+  $T rocprofv3 --kernel-trace --stats -d $O/ks_$w -o ks -- python3 bench.py --full --workload $w --steps 3 --warmup 1 --no-cpu-baseline --no-secondary > $O/ks_$w.log 2>&1
   python3 profiles/summarize_rocprof.py stats $O/ks_$w/ks_results.db > $O/kernel_stats_$w.txt 2>&1
   [ $w = c2 ] && python3 profiles/summarize_rocprof.py timeline $O/ks_$w/ks_results.db -4 330 2 > $O/timeline_c2.txt 2>&1
   rm -rf $O/ks_$w
@@ -20,7 +20,7 @@ done
 for w in c2 c3 c4 c4sv; do
   for ctr in FETCH_SIZE WRITE_SIZE; do
     n=$(echo $ctr | tr A-Z a-z | sed 's/_size//')
-    MSIM_BENCH_NO_PMC=1 $T rocprofv3 --pmc $ctr -d $O/pmc_${n}_$w -o f -- python3 bench.py --workload $w --steps 1 --warmup 1 --no-cpu-baseline --no-secondary > $O/pmc_${n}_$w.log 2>&1
+    MSIM_BENCH_NO_PMC=1 $T rocprofv3 --pmc $ctr -d $O/pmc_${n}_$w -o f -- python3 bench.py --full --workload $w --steps 1 --warmup 1 --no-cpu-baseline --no-secondary > $O/pmc_${n}_$w.log 2>&1
     python3 profiles/summarize_rocprof.py pmc $O/pmc_${n}_$w/f_results.db > $O/pmc_${n}_$w.txt 2>&1
     rm -rf $O/pmc_${n}_$w
   done
@@ -43,7 +43,7 @@ for tag in c2 c3 readme; do
   rm -rf $O/kc_$tag
 done
 # ---- 5. the driver's command, CLI profiles (no profiler attached), micro-benchmarks
-$T python3 bench.py > $O/bench_default.json 2> $O/bench_default.err
+$T python3 bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 $T python3 mutation-simulator_amd/tools/cli_profile.py --mb 1200 --contigs 6 --top 12 > $O/cli_profile.txt 2>&1
 $T python3 mutation-simulator_amd/tools/cli_profile.py --mb 1200 --contigs 6 --top 6 -- args -sn 0.005 -in 0.001 -inmin 1 -inmax 50 -de 0.001 -demin 1 -demax 50 -du 0.0005 -dumin 50 -dumax 500 -iv 0.0005 -ivmin 50 -ivmax 500 >> $O/cli_profile.txt 2>&1
 $T python3 mutation-simulator_amd/tools/cli_profile.py --mb 1200 --contigs 6 --top 6 -- args -sn 0.01 -in 0.01 -de 0.01 -du 0.01 -iv 0.01 -tl 0.01 >> $O/cli_profile.txt 2>&1

@@ -17,7 +17,7 @@ for v in ahead chain; do
   rm -rf $O/ks_$v
 done
 unset MSIM_NO_AHEAD
-$T python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+$T python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
 python3 - <<'PY'
 import json
 d=json.loads(open("gpurun_out/r5ev/bench_default.json").read().strip().splitlines()[-1])
