@@ -300,6 +300,22 @@ int msim_fetch_sequence_framed(msim_ctx *ctx, int contig, uint32_t bpl, uint8_t 
 int msim_render_vcf_device_file(msim_ctx *ctx, int contig, const char *seq_name, int fd, uint64_t offset, uint64_t *written);
 int msim_fetch_sequence_framed_file(msim_ctx *ctx, int contig, uint32_t bpl, int fd, uint64_t offset, uint64_t *written);
 int msim_file_wait(msim_ctx *ctx);
+/* BGZF output (SAM/BAM specification 4.1; compressed on the device, bgzf.hip).  msim_bgzf_open puts the output channel
+ * `channel` (0 the FASTA, 1 the VCF) into BGZF mode on `fd` (a regular file, written from offset 0).  From then on every
+ * transfer queued on that channel -- msim_fetch_sequence_framed_file / msim_render_vcf_device_file / msim_batch_fetch_file
+ * and msim_bgzf_append -- is appended, in queue order, to ONE uncompressed stream that is cut into 65 280-byte blocks and
+ * written as BGZF members; the `fd` those calls get is not used and their `offset` must equal the stream's current length
+ * (MSIM_ERR_ARG otherwise).  msim_bgzf_append copies `n` host bytes (the caller may reuse them at once).  msim_bgzf_close
+ * compresses the tail, appends the 28-byte EOF marker, waits for the channel and reports the compressed and uncompressed
+ * byte counts; the channel is a plain one again.  The compressed bytes are a function of the uncompressed stream only.
+ * msim_bgzf_compress: host bytes -> a whole BGZF file (members + EOF marker) in `out`, cap >= msim_bgzf_bound(n);
+ * *device_ms (optional): the compression kernels' time on the device (events), copies excluded.                      */
+int msim_bgzf_open(msim_ctx *ctx, int channel, int fd);
+int msim_bgzf_append(msim_ctx *ctx, int channel, const uint8_t *bytes, uint64_t n);
+int msim_bgzf_close(msim_ctx *ctx, int channel, uint64_t *compressed, uint64_t *uncompressed);
+uint64_t msim_bgzf_bound(uint64_t n);
+int msim_bgzf_compress(msim_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *written,
+                       float *device_ms);
 /* Ingest one FASTA record straight from file text: `body` = the bytes after the header line, n_bases bases
  * in lines of `lenc` bases every `lenb` bytes (the .fai columns; uniform line width is what pyfaidx
  * requires, util.py:77-91).  Line terminators are skipped and a-z upper-cased on the device

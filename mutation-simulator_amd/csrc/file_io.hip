@@ -20,6 +20,7 @@
 #include <condition_variable>
 #include <cstring>
 #include <deque>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -29,6 +30,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include "bgzf.h"
 #include "ctx.h"
 
 namespace msim {
@@ -45,6 +47,9 @@ struct FileJob {
     uint64_t n;
     int fd;                                // a dup() of the caller's descriptor: closed when the job is done
     uint64_t offset;
+    bool bgzf = false;                     // BGZF mode: the bytes are appended to the channel's uncompressed stream
+    bool bgzf_close = false;               //   ... or the stream is finished: tail, EOF marker
+    std::shared_ptr<std::vector<uint8_t>> owned;   // host bytes the channel holds itself (msim_bgzf_append)
 };
 
 struct FileChannel {
@@ -65,6 +70,15 @@ struct FileChannel {
     size_t cap[2] = {0, 0};
     bool in_flight[2] = {false, false};
     hipEvent_t ready[2] = {nullptr, nullptr};
+    // BGZF mode (bgzf.hip).  The calling thread's view: on, the file, the uncompressed bytes queued so far.
+    bool bz = false;
+    int bz_fd = -1;
+    uint64_t bz_queued = 0;
+    // the channel thread's: device staging of the uncompressed stream (whole blocks are compressed once it is full), the
+    // bytes compressed so far and the compressed bytes written
+    uint8_t *bz_stage = nullptr;
+    uint64_t bz_fill = 0, bz_ulen = 0, bz_clen = 0;
+    BgzfWork bz_w;
 };
 
 }  // namespace
@@ -91,7 +105,95 @@ bool pwrite_all(int fd, const uint8_t *p, size_t n, uint64_t off, std::string &w
     return true;
 }
 
+hipError_t channel_stream(FileChannel &ch) {
+    hipError_t e = hipSuccess;
+    if (!ch.st) {
+        e = hipSetDevice(ch.device);
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&ch.st, hipStreamNonBlocking);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&ch.pin, FILE_CHUNK * FILE_SLOTS, hipHostMallocDefault);
+        for (int i = 0; i < FILE_SLOTS && e == hipSuccess; i++) e = hipEventCreateWithFlags(&ch.ev[i], hipEventDisableTiming);
+    }
+    return e;
+}
+
+constexpr uint64_t BZ_STAGE = BGZF_PIECE_BLOCKS * BGZF_BLOCK;
+
+// Compress staging bytes [0, n) (whole blocks, or everything at the end of the stream), write the members at the channel's
+// compressed offset through the pinned ring, move what is left of the staging to its front.
+bool bz_flush(FileChannel &ch, uint64_t n, hipError_t &e, std::string &why) {
+    uint64_t out = 0;
+    e = bgzf_compress_device(ch.bz_stage, n, ch.bz_w, ch.st, &out);
+    if (e != hipSuccess) return false;
+    const uint64_t pieces = (out + FILE_CHUNK - 1) / FILE_CHUNK;
+    auto issue = [&](uint64_t k) {
+        const uint64_t off = k * FILE_CHUNK, len = out - off < FILE_CHUNK ? out - off : FILE_CHUNK;
+        const int slot = (int)(k % FILE_SLOTS);
+        hipError_t r = hipMemcpyAsync(ch.pin + (size_t)slot * FILE_CHUNK, ch.bz_w.d_out + off, len, hipMemcpyDeviceToHost, ch.st);
+        if (r == hipSuccess) r = hipEventRecord(ch.ev[slot], ch.st);
+        return r;
+    };
+    for (uint64_t k = 0; k < pieces && k < (uint64_t)FILE_SLOTS && e == hipSuccess; k++) e = issue(k);
+    for (uint64_t k = 0; k < pieces && e == hipSuccess; k++) {
+        const int slot = (int)(k % FILE_SLOTS);
+        e = wait_event(ch.ev[slot]);
+        if (e != hipSuccess) break;
+        const uint64_t off = k * FILE_CHUNK, len = out - off < FILE_CHUNK ? out - off : FILE_CHUNK;
+        if (!pwrite_all(ch.bz_fd, ch.pin + (size_t)slot * FILE_CHUNK, len, ch.bz_clen + off, why)) {
+            (void)wait_stream(ch.st);
+            return false;
+        }
+        if (k + FILE_SLOTS < pieces) e = issue(k + FILE_SLOTS);
+    }
+    if (e != hipSuccess) return false;
+    ch.bz_clen += out;
+    ch.bz_ulen += n;
+    const uint64_t tail = ch.bz_fill - n;                  // (< one block, and n >= one block: no overlap)
+    if (tail) e = hipMemcpyAsync(ch.bz_stage, ch.bz_stage + n, tail, hipMemcpyDeviceToDevice, ch.st);
+    ch.bz_fill = tail;
+    return e == hipSuccess;
+}
+
+// A job of a channel in BGZF mode: its bytes are appended to the staging (full staging: compressed and written), or the
+// stream is closed (the tail, then the EOF marker).
+void run_bgzf_job(FileChannel &ch, const FileJob &job) {
+    {
+        std::lock_guard<std::mutex> lk(ch.mu);
+        if (ch.err) return;
+    }
+    std::string why;
+    hipError_t e = channel_stream(ch);
+    if (e == hipSuccess && !ch.bz_stage) e = hipMalloc((void **)&ch.bz_stage, BZ_STAGE + PAD);
+    bool ok = e == hipSuccess;
+    if (ok && job.bgzf_close) {
+        if (ch.bz_fill) ok = bz_flush(ch, ch.bz_fill, e, why);
+        if (ok) ok = pwrite_all(ch.bz_fd, BGZF_EOF, sizeof BGZF_EOF, ch.bz_clen, why);
+        if (ok) ch.bz_clen += sizeof BGZF_EOF;
+    } else if (ok) {
+        const uint8_t *src = job.owned ? job.owned->data() : job.h_src ? job.h_src : job.d_src;
+        const hipMemcpyKind kind = job.d_src && !job.owned && !job.h_src ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+        if (kind == hipMemcpyDeviceToDevice) e = hipStreamWaitEvent(ch.st, ch.ready[job.buf], 0);   // the text is complete
+        uint64_t left = job.n;
+        while (ok && left && e == hipSuccess) {
+            const uint64_t take = left < BZ_STAGE - ch.bz_fill ? left : BZ_STAGE - ch.bz_fill;
+            e = hipMemcpyAsync(ch.bz_stage + ch.bz_fill, src, take, kind, ch.st);
+            ch.bz_fill += take;
+            src += take;
+            left -= take;
+            if (e == hipSuccess && ch.bz_fill == BZ_STAGE) ok = bz_flush(ch, BZ_STAGE, e, why);
+        }
+        if (ok && e == hipSuccess) e = wait_stream(ch.st);      // (the source may be reused once the channel is idle)
+        ok = ok && e == hipSuccess;
+    }
+    if (e != hipSuccess) {
+        set_err(ch, MSIM_ERR_HIP, std::string("output channel (BGZF): ") + hipGetErrorString(e));
+        if (ch.st) (void)wait_stream(ch.st);
+    } else if (!ok) {
+        set_err(ch, MSIM_ERR_IO, why);
+    }
+}
+
 void run_job(FileChannel &ch, const FileJob &job) {
+    if (job.bgzf) { run_bgzf_job(ch, job); return; }
     static const bool prof = getenv("MSIM_IO_PROF") != nullptr;
     const auto t0 = std::chrono::steady_clock::now();
     double wait_ms = 0, write_ms = 0;
@@ -220,6 +322,7 @@ void channel_main(FileChannel *chp) {
             ch.running = true;
         }
         run_job(ch, job);
+        job.owned.reset();
         {
             std::lock_guard<std::mutex> lk(ch.mu);
             ch.running = false;
@@ -229,6 +332,9 @@ void channel_main(FileChannel *chp) {
     }
     if (ch.st) {
         (void)wait_stream(ch.st);
+        bgzf_work_free(ch.bz_w);
+        if (ch.bz_stage) (void)hipFree(ch.bz_stage);
+        ch.bz_stage = nullptr;
         for (auto &e : ch.ev) if (e) (void)hipEventDestroy(e);
         if (ch.pin) (void)hipHostFree(ch.pin);
         (void)hipStreamDestroy(ch.st);
@@ -244,7 +350,118 @@ FileIo *io_get(Ctx *c) {
     return c->file_io;
 }
 
+// queue a BGZF job (the calling thread): starts the channel's thread on first use, counts the uncompressed bytes
+int bz_push(Ctx *c, FileChannel &ch, FileJob job) {
+    {
+        std::lock_guard<std::mutex> lk(ch.mu);
+        if (!ch.started) {
+            try {
+                ch.th = std::thread(channel_main, &ch);
+            } catch (const std::system_error &e) {
+                return fail(c, MSIM_ERR_NOMEM, std::string("output channel thread: ") + e.what());
+            }
+            ch.started = true;
+        }
+        if (job.buf >= 0) ch.in_flight[job.buf] = true;
+        if (!job.bgzf_close) ch.bz_queued += job.n;
+        ch.q.push_back(std::move(job));
+    }
+    ch.cv_job.notify_one();
+    return MSIM_OK;
+}
+
 }  // namespace
+
+// BGZF mode of channel `ch_id` on `fd` (a regular file, written from offset 0): until file_bgzf_close, every job queued on
+// the channel -- device text, host text, file_bgzf_append -- is appended to one uncompressed stream in queue order, and
+// the offsets the *_file entry points are given must be that stream's length.
+int file_bgzf_open(Ctx *c, int ch_id, int fd) {
+    int rc = file_check(c, fd);
+    if (rc) return rc;
+    FileChannel &ch = io_get(c)->ch[ch_id];
+    file_channel_idle(c, ch_id);
+    if (ch.bz) return fail(c, MSIM_ERR_ARG, "output channel is in BGZF mode already");
+    const int own = dup(fd);
+    if (own < 0) return fail(c, MSIM_ERR_IO, std::string("dup: ") + strerror(errno));
+    std::lock_guard<std::mutex> lk(ch.mu);
+    ch.bz = true;
+    ch.bz_fd = own;
+    ch.bz_queued = 0;
+    ch.bz_fill = ch.bz_ulen = ch.bz_clen = 0;
+    return MSIM_OK;
+}
+
+int file_bgzf_append(Ctx *c, int ch_id, const uint8_t *src, uint64_t n) {
+    FileChannel &ch = io_get(c)->ch[ch_id];
+    if (!ch.bz) return fail(c, MSIM_ERR_ARG, "output channel is not in BGZF mode");
+    if (!n) return MSIM_OK;
+    FileJob job{nullptr, nullptr, -1, n, -1, ch.bz_queued, false, false, nullptr};
+    job.bgzf = true;
+    try {
+        job.owned = std::make_shared<std::vector<uint8_t>>(src, src + n);
+    } catch (const std::bad_alloc &) {
+        return fail(c, MSIM_ERR_NOMEM, "BGZF append");
+    }
+    return bz_push(c, ch, std::move(job));
+}
+
+// The tail and the EOF marker go out; waits for the channel; the mode ends (the descriptor is the caller's again).
+int file_bgzf_close(Ctx *c, int ch_id, uint64_t *compressed, uint64_t *uncompressed) {
+    FileChannel &ch = io_get(c)->ch[ch_id];
+    if (!ch.bz) return fail(c, MSIM_ERR_ARG, "output channel is not in BGZF mode");
+    FileJob job{nullptr, nullptr, -1, 0, -1, ch.bz_queued, false, false, nullptr};
+    job.bgzf = true;
+    job.bgzf_close = true;
+    int rc = bz_push(c, ch, std::move(job));
+    file_channel_idle(c, ch_id);
+    std::lock_guard<std::mutex> lk(ch.mu);
+    if (compressed) *compressed = ch.bz_clen;
+    if (uncompressed) *uncompressed = ch.bz_ulen;
+    (void)close(ch.bz_fd);
+    ch.bz = false;
+    ch.bz_fd = -1;
+    if (rc == MSIM_OK && ch.err) {
+        rc = ch.err;
+        fail(c, ch.err, ch.err_msg);
+        ch.err = 0;
+        ch.err_msg.clear();
+    }
+    return rc;
+}
+
+// One-shot: host bytes -> BGZF bytes (members + EOF marker) in `out` (cap >= bgzf_bound(n)), on the context's stream.
+uint64_t bgzf_bound(uint64_t n) { return (n + BGZF_BLOCK - 1) / BGZF_BLOCK * (BGZF_BLOCK + 5 + 26) + sizeof BGZF_EOF; }
+
+int bgzf_compress_host(Ctx *c, const uint8_t *src, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *written, float *device_ms) {
+    if (cap < bgzf_bound(n)) return fail(c, MSIM_ERR_ARG, "BGZF output buffer smaller than msim_bgzf_bound");
+    BgzfWork w;
+    uint8_t *d_in = nullptr;
+    uint64_t done = 0, pos = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    float total_ms = 0;
+    hipError_t e = hipMalloc((void **)&d_in, BZ_STAGE + PAD);
+    for (int i = 0; i < 2 && e == hipSuccess && device_ms; i++) e = hipEventCreate(&ev[i]);
+    while (e == hipSuccess && pos < n) {
+        const uint64_t take = n - pos < BZ_STAGE ? n - pos : BZ_STAGE;
+        uint64_t got = 0;
+        e = hipMemcpyAsync(d_in, src + pos, take, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = bgzf_compress_device(d_in, take, w, c->stream, &got, ev[0], ev[1]);
+        float ms = 0;
+        if (e == hipSuccess && device_ms && hipEventElapsedTime(&ms, ev[0], ev[1]) == hipSuccess) total_ms += ms;
+        if (e == hipSuccess) e = hipMemcpyAsync(out + done, w.d_out, got, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = wait_stream(c->stream);
+        done += got;
+        pos += take;
+    }
+    bgzf_work_free(w);
+    if (d_in) (void)hipFree(d_in);
+    for (auto x : ev) if (x) (void)hipEventDestroy(x);
+    if (device_ms) *device_ms = total_ms;
+    if (e != hipSuccess) return fail(c, MSIM_ERR_HIP, std::string("BGZF compression: ") + hipGetErrorString(e));
+    memcpy(out + done, BGZF_EOF, sizeof BGZF_EOF);
+    *written = done + sizeof BGZF_EOF;
+    return MSIM_OK;
+}
 
 void device_host_cpus(int device, char *buf, size_t cap) { gpu_node_cpulist(device, buf, cap); }
 
@@ -276,6 +493,13 @@ int file_enqueue(Ctx *c, int ch_id, int slot, uint64_t n, int fd, uint64_t offse
     if (!n) return MSIM_OK;
     FileChannel &ch = io_get(c)->ch[ch_id];
     if (!ch.ready[slot]) MSIM_HIP(c, hipEventCreateWithFlags(&ch.ready[slot], hipEventDisableTiming));
+    if (ch.bz) {                                            // BGZF mode: `offset` is the uncompressed stream's length
+        if (offset != ch.bz_queued) return fail(c, MSIM_ERR_ARG, "BGZF channel: offset is not the end of the stream");
+        MSIM_HIP(c, hipEventRecord(ch.ready[slot], c->stream));
+        FileJob job{ch.d_buf[slot], nullptr, slot, n, -1, offset, false, false, nullptr};
+        job.bgzf = true;
+        return bz_push(c, ch, job);
+    }
     MSIM_HIP(c, hipEventRecord(ch.ready[slot], c->stream));
     const int own = dup(fd);
     if (own < 0) return fail(c, MSIM_ERR_IO, std::string("dup: ") + strerror(errno));
@@ -291,7 +515,7 @@ int file_enqueue(Ctx *c, int ch_id, int slot, uint64_t n, int fd, uint64_t offse
             ch.started = true;
         }
         ch.in_flight[slot] = true;
-        ch.q.push_back(FileJob{ch.d_buf[slot], nullptr, slot, n, own, offset});
+        ch.q.push_back(FileJob{ch.d_buf[slot], nullptr, slot, n, own, offset, false, false, nullptr});
     }
     ch.cv_job.notify_one();
     return MSIM_OK;
@@ -302,6 +526,12 @@ int file_enqueue(Ctx *c, int ch_id, int slot, uint64_t n, int fd, uint64_t offse
 int file_enqueue_host(Ctx *c, int ch_id, const uint8_t *src, uint64_t n, int fd, uint64_t offset) {
     if (!n) return MSIM_OK;
     FileChannel &ch = io_get(c)->ch[ch_id];
+    if (ch.bz) {
+        if (offset != ch.bz_queued) return fail(c, MSIM_ERR_ARG, "BGZF channel: offset is not the end of the stream");
+        FileJob job{nullptr, src, -1, n, -1, offset, false, false, nullptr};
+        job.bgzf = true;
+        return bz_push(c, ch, job);
+    }
     const int own = dup(fd);
     if (own < 0) return fail(c, MSIM_ERR_IO, std::string("dup: ") + strerror(errno));
     {
@@ -315,7 +545,7 @@ int file_enqueue_host(Ctx *c, int ch_id, const uint8_t *src, uint64_t n, int fd,
             }
             ch.started = true;
         }
-        ch.q.push_back(FileJob{nullptr, src, -1, n, own, offset});
+        ch.q.push_back(FileJob{nullptr, src, -1, n, own, offset, false, false, nullptr});
     }
     ch.cv_job.notify_one();
     return MSIM_OK;
@@ -356,6 +586,7 @@ void file_io_destroy(Ctx *c) {
         }
         ch.cv_job.notify_all();
         if (ch.th.joinable()) ch.th.join();
+        if (ch.bz_fd >= 0) (void)close(ch.bz_fd);
         for (int s = 0; s < 2; s++) {
             if (ch.ready[s]) (void)hipEventDestroy(ch.ready[s]);
             if (ch.d_buf[s]) (void)hipFree(ch.d_buf[s]);

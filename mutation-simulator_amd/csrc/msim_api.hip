@@ -953,6 +953,39 @@ int msim_file_wait(msim_ctx *p) {
     return file_wait(c);
 }
 
+// BGZF output (bgzf.hip, file_io.hip): the output channels compress what they write.
+int msim_bgzf_open(msim_ctx *p, int channel, int fd) {
+    Ctx *c = C(p);
+    if (!c || channel < 0 || channel > 1 || fd < 0) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    return file_bgzf_open(c, channel, fd);
+}
+
+int msim_bgzf_append(msim_ctx *p, int channel, const uint8_t *bytes, uint64_t n) {
+    Ctx *c = C(p);
+    if (!c || channel < 0 || channel > 1 || (!bytes && n)) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    return file_bgzf_append(c, channel, bytes, n);
+}
+
+int msim_bgzf_close(msim_ctx *p, int channel, uint64_t *compressed, uint64_t *uncompressed) {
+    Ctx *c = C(p);
+    if (!c || channel < 0 || channel > 1) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    return file_bgzf_close(c, channel, compressed, uncompressed);
+}
+
+uint64_t msim_bgzf_bound(uint64_t n) { return bgzf_bound(n); }
+
+int msim_bgzf_compress(msim_ctx *p, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *written,
+                       float *device_ms) {
+    Ctx *c = C(p);
+    if (!c || (!in && n) || !out || !written) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    TraceRange tr("msim bgzf: one-shot");
+    return bgzf_compress_host(c, in, n, out, cap, written, device_ms);
+}
+
 int msim_add_contig_text(msim_ctx *p, const uint8_t *body, uint64_t body_bytes, uint64_t n_bases, uint32_t lenc,
                          uint32_t lenb, int *contig) {
     CTX_FLUSHED(c, p)

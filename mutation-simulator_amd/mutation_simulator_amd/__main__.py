@@ -19,16 +19,31 @@ _INIT_ERRORS = (FileNotFoundError, ITNotEnoughAvailChromsError, RatesTooHighErro
 STAGES: dict = {}          # wall seconds of the last run's stages (--bench-json: cli_s)
 
 
+class BgzipUnsupportedError(Exception):
+    """--bgzip together with what it does not cover (the IT pass, a sharded run)."""
+
+
+def _warm_up(args):
+    try:
+        from ._ffi import warm_up_async
+        warm_up_async(args.device or 0, pin=True)
+    except Exception:  # noqa: BLE001  (no library: Mutator reports it properly)
+        pass
+
+
 def initialize(argv=None):
     t0 = timer()
     args = get_args(argv)
     STAGES["parse_args"] = timer() - t0
-    if (args.gpus or 1) <= 1:
-        try:                       # the GPU comes up while the FASTA is read and indexed (never in the parent of --gpus N)
-            from ._ffi import warm_up_async
-            warm_up_async(args.device or 0, pin=True)
-        except Exception:  # noqa: BLE001  (no library: Mutator reports it properly)
-            pass
+    if args.bgzip and args.mode == "it":
+        exit_with_error(BgzipUnsupportedError("--bgzip does not apply to the interchromosomal pass (it)"), args.no_color)
+    if args.bgzip and (args.gpus or 1) > 1:
+        exit_with_error(BgzipUnsupportedError("--bgzip needs a single-GPU run (--gpus 1)"), args.no_color)
+    # the GPU comes up while the FASTA is read and indexed (never in the parent of --gpus N; with --bgzip and an RMT only
+    # once the RMT is known to hold no it lines)
+    early = (args.gpus or 1) <= 1 and not (args.bgzip and args.mode == "rmt")
+    if early:
+        _warm_up(args)
     try:
         t0 = timer()
         fasta = load_fasta(args.infile)
@@ -41,6 +56,11 @@ def initialize(argv=None):
             sim = SimulationSettings.from_rmt(args.rmtfile, fasta, args.ignore_warnings)
     except _INIT_ERRORS as e:
         exit_with_error(e, args.no_color)
+    if args.bgzip and sim.has_it:
+        exit_with_error(BgzipUnsupportedError("--bgzip does not apply to the interchromosomal pass (it lines in the RMT)"),
+                        args.no_color)
+    if not early and (args.gpus or 1) <= 1:
+        _warm_up(args)
     if not args.ignore_warnings:
         warn_user(args, sim)
     return args, fasta, sim

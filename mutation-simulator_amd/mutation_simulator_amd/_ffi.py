@@ -124,6 +124,11 @@ SYMBOLS = [
     ("msim_render_vcf_device_file", C.c_int, [_VP, C.c_int, C.c_char_p, C.c_int, C.c_uint64, _U64P]),
     ("msim_fetch_sequence_framed_file", C.c_int, [_VP, C.c_int, C.c_uint32, C.c_int, C.c_uint64, _U64P]),
     ("msim_file_wait", C.c_int, [_VP]),
+    ("msim_bgzf_open", C.c_int, [_VP, C.c_int, C.c_int]),
+    ("msim_bgzf_append", C.c_int, [_VP, C.c_int, _VP, C.c_uint64]),
+    ("msim_bgzf_close", C.c_int, [_VP, C.c_int, _U64P, _U64P]),
+    ("msim_bgzf_bound", C.c_uint64, [C.c_uint64]),
+    ("msim_bgzf_compress", C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint64, _U64P, C.POINTER(C.c_float)]),
     ("msim_device_host_cpus", C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     ("msim_batch_fetch_file", C.c_int, [_VP, C.c_int, C.c_uint64, C.c_int, C.c_uint64]),
     ("msim_add_contig_text", C.c_int, [_VP, _VP, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _IP]),
@@ -488,6 +493,36 @@ class Engine:
     def file_wait(self):
         """Everything queued by the ``..._to_file`` calls is in its file (raises the first failure of a queued write)."""
         self._check(self.lib.msim_file_wait(self.h))
+
+    # ------------------------------------------------------------------ BGZF output (msim.h: msim_bgzf_*)
+    def bgzf_open(self, channel: int, fd: int):
+        """Output channel ``channel`` (0 FASTA, 1 VCF) writes BGZF into the regular file ``fd`` from now on; the ``offset``
+        of the ``..._to_file`` calls on it is the uncompressed stream's length."""
+        self._check(self.lib.msim_bgzf_open(self.h, int(channel), int(fd)))
+
+    def bgzf_append(self, channel: int, data) -> None:
+        """Host bytes appended to the channel's uncompressed stream (copied: ``data`` may be reused at once)."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        if buf.shape[0]:
+            self._check(self.lib.msim_bgzf_append(self.h, int(channel), C.c_void_p(buf.ctypes.data), buf.shape[0]))
+
+    def bgzf_close(self, channel: int):
+        """Tail + EOF marker out, channel joined; returns (compressed bytes, uncompressed bytes)."""
+        c, u = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.msim_bgzf_close(self.h, int(channel), C.byref(c), C.byref(u)))
+        return c.value, u.value
+
+    def bgzf_compress(self, data, timed: bool = False):
+        """``data`` (bytes-like) as a whole BGZF file, compressed on the device; ``timed``: (bytes, kernel ms)."""
+        buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+        n = int(buf.shape[0])
+        cap = int(self.lib.msim_bgzf_bound(n))
+        out = np.empty(cap, dtype=np.uint8)
+        got, ms = C.c_uint64(), C.c_float()
+        self._check(self.lib.msim_bgzf_compress(self.h, C.c_void_p(buf.ctypes.data) if n else None, n,
+                                                C.c_void_p(out.ctypes.data), cap, C.byref(got), C.byref(ms) if timed else None))
+        res = out[:got.value].tobytes()
+        return (res, ms.value) if timed else res
 
     def fetch_sequence_framed_to_file(self, contig: int, bpl: int, fd: int, offset: int) -> int:
         """The framed body QUEUED for bytes [offset, offset + n) of the open regular file ``fd`` (libmsim's output channel

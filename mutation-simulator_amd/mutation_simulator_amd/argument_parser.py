@@ -1,6 +1,6 @@
 """Command line of ``mutation-simulator`` -- flag-for-flag the reference's ``args`` and ``rmt``
 sub-commands (reference argument_parser.py:31-240) plus a few additions of ours that never change
-a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bench-json``.
+a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bgzip``, ``--bench-json``.
 
 The ``it`` sub-command (inter-chromosomal translocations, reference it_mutator.py: a second pass over
 the Fasta) runs through ``ITMutator`` / ``BedpeWriter``.  ``--rng fast`` applies to the mutation pass
@@ -29,6 +29,9 @@ def add_outfile_names(args: Namespace) -> Namespace:
     args.outfastait = args.outfasta.with_stem(args.outfasta.stem + "_it")
     args.outvcf = args.outfasta.with_suffix(".vcf")
     args.outbedpe = args.outfastait.with_suffix(".bedpe")
+    if getattr(args, "bgzip", False):             # BGZF-compressed mutation-pass outputs: <name>.gz
+        args.outfasta = args.outfasta.with_name(args.outfasta.name + ".gz")
+        args.outvcf = args.outvcf.with_name(args.outvcf.name + ".gz")
     return args
 
 
@@ -73,6 +76,9 @@ def build_parser() -> ArgumentParser:
                         help="compat (default): the reference's two MT19937 streams, output bit-identical to the reference "
                              "under the same seeds. fast: a counter-based generator (Philox) -- same distributions, NOT the "
                              "reference's numbers; no sequential chain in the draw; SNP-only settings")
+    parser.add_argument("--bgzip", action="store_true", default=False,
+                        help="Write the mutated Fasta and the VCF BGZF-compressed (<name>.gz, compressed on the GPU); "
+                             "they decompress to exactly the files written without it. Not with it / --gpus N > 1")
     parser.add_argument("--bench-json", type=Path, default=None,
                         help="Write per-stage timings of the mutation pass to this JSON file")
 

@@ -81,13 +81,30 @@ class FastaWriterError(Exception):
 
 
 class FastaWriter:
-    def __init__(self, fname):
+    def __init__(self, fname, bgzip: bool = False, device: int = 0):
         try:
-            self._out = open(fname, "w+b")         # (readable too: map_region maps spans of it)
+            if bgzip:                              # a BGZF stream compressed on the device (bgzf.py): same bytes, inflated
+                from .bgzf import FASTA_CHANNEL, BgzfSink
+                self._out = BgzfSink(fname, FASTA_CHANNEL, device)
+            else:
+                self._out = open(fname, "w+b")     # (readable too: map_region maps spans of it)
         except IOError as e:
             raise FastaWriterError(f"Cannot write to Fasta file {fname} {e}")
+        self._bgzip = bgzip
         self._written = 0      # bases on the current (partial) line
         self._bpl = 60
+
+    def attach(self, engine):
+        """BGZF output: the engine whose output channel compresses and writes the stream (what was written before goes
+        first)."""
+        if self._bgzip:
+            self._out.attach(engine)
+
+    def _region(self, nbytes: int):
+        if self._bgzip:
+            from .bgzf import HostRegion
+            return HostRegion(nbytes)
+        return MappedRegion(self._out, nbytes)
 
     def __del__(self):
         self.close()
@@ -128,7 +145,7 @@ class FastaWriter:
         start a line).  ``commit_region(region, n_bases)`` finishes it."""
         if self._written != 0:
             raise FastaWriterError("map_region needs to start at the beginning of a line")
-        return MappedRegion(self._out, nbytes)
+        return self._region(nbytes)
 
     def commit_region(self, region: MappedRegion, n_bases: int):
         region.close(self._out)
@@ -181,7 +198,7 @@ class FastaWriter:
         if nbytes and self._written != 0:
             self._out.write(b"\n")
             self._written = 0
-        return MappedRegion(self._out, nbytes)
+        return self._region(nbytes)
 
     def commit_records(self, region: MappedRegion, bpl: int, last_line_bases: int):
         region.close(self._out)

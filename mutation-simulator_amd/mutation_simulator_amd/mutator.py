@@ -314,12 +314,16 @@ BATCH_MAX_CONTIGS = 16384
 class Mutator:
     """Runs the mutation pass of one genome on the GPU and writes ``*_ms.fa`` / ``*_ms.vcf``."""
 
+    _bgzip = False                                     # --bgzip: BGZF writers (subclasses that open writers of their own: plain)
+
     def __init__(self, args, fasta, sim, engine: Optional["_ffi.Engine"] = None):
         self._args = args
         self._fasta = fasta
         self._sim = sim
-        self._fasta_writer = FastaWriter(args.outfasta)
-        self._vcf_writer = VcfWriter(args.outvcf)
+        self._bgzip = bool(getattr(args, "bgzip", False))
+        dev = getattr(args, "device", 0) or 0
+        self._fasta_writer = FastaWriter(args.outfasta, bgzip=self._bgzip, device=dev)
+        self._vcf_writer = VcfWriter(args.outvcf, bgzip=self._bgzip, device=dev)
         self._vcf_writer.write_header(args.infile.name, fasta, sim.assembly_name, sim.species_name,
                                       sim.sample_name)
         self._engine = engine
@@ -335,6 +339,11 @@ class Mutator:
                 self._engine.file_wait()
             except _ffi.MsimError as e:
                 pending = e
+        if self._bgzip:                                # BGZF: the streams' tails and EOF markers go out through the engine
+            try:
+                self._fasta_writer.close()
+            finally:
+                self._vcf_writer.close()
         eng, self._engine = (self._engine if self._own_engine else None), None
         side = None
         if eng is not None and os.environ.get("MSIM_SERIAL_CLOSE") != "1":
@@ -641,6 +650,8 @@ class Mutator:
         else:
             self._seed_engine(self._engine)
         eng = self._engine
+        self._fasta_writer.attach(eng)                 # (BGZF output: the engine's output channels compress the streams)
+        self._vcf_writer.attach(eng)
         eng.set_params(params_descriptor(self._sim))
         eng.reset_stats()
         try:

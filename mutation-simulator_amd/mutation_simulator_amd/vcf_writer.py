@@ -47,11 +47,21 @@ _HEADER_TAIL = (
 
 
 class VcfWriter:
-    def __init__(self, fname):
+    def __init__(self, fname, bgzip: bool = False, device: int = 0):
         try:
-            self._out = open(fname, "w+b")         # (readable too: map_region maps spans of it)
+            if bgzip:                              # a BGZF stream compressed on the device (bgzf.py): same bytes, inflated
+                from .bgzf import VCF_CHANNEL, BgzfSink
+                self._out = BgzfSink(fname, VCF_CHANNEL, device)
+            else:
+                self._out = open(fname, "w+b")     # (readable too: map_region maps spans of it)
         except IOError as e:
             raise VcfWriterError(f"Cannot write to VCF file {fname} {e}")
+        self._bgzip = bgzip
+
+    def attach(self, engine):
+        """BGZF output: the engine whose output channel compresses and writes the stream (the header goes first)."""
+        if self._bgzip:
+            self._out.attach(engine)
 
     def __del__(self):
         self.close()
@@ -59,6 +69,9 @@ class VcfWriter:
     def close(self):
         out = getattr(self, "_out", None)
         if out is not None and not out.closed:
+            if getattr(self, "_bgzip", False):
+                out.close()
+                return
             out.flush()
             if os.fstat(out.fileno()).st_size > out.tell():     # (a mapped region that was cut short)
                 os.ftruncate(out.fileno(), out.tell())
@@ -92,6 +105,9 @@ class VcfWriter:
 
     def map_region(self, nbytes: int):
         """The next ``nbytes`` of the file mapped for writing (record lines rendered elsewhere land there directly)."""
+        if self._bgzip:
+            from .bgzf import HostRegion
+            return HostRegion(nbytes)
         from .fasta_writer import MappedRegion
         return MappedRegion(self._out, nbytes)
 
