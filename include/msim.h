@@ -316,6 +316,24 @@ int msim_bgzf_close(msim_ctx *ctx, int channel, uint64_t *compressed, uint64_t *
 uint64_t msim_bgzf_bound(uint64_t n);
 int msim_bgzf_compress(msim_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *written,
                        float *device_ms);
+/* BGZF input (what msim_bgzf_* above and bgzip write).  msim_bgzf_probe is a host pass over the member chain (no context, no
+ * device): *uncompressed = the sum of the members' ISIZE, *members = the members of the chain, empty ones (ISIZE 0: the EOF
+ * marker, also in the middle of concatenated files) included; either may be NULL.  MSIM_ERR_VALUE (text: msim_last_error(NULL))
+ * for bytes that are not gzip, gzip without BGZF framing (no extra field / no 'BC' subfield), a BSIZE that runs past the
+ * end, a truncated last member and an ISIZE above 65 536; a missing EOF marker is accepted.
+ * msim_bgzf_inflate: a whole BGZF file (host bytes) -> its uncompressed bytes in `out`, cap >= *uncompressed of the probe
+ * (MSIM_ERR_ARG otherwise), *written = that count.  One RFC 1951 decoder per member on the device (stored, fixed and dynamic
+ * blocks, any number of them per member), 1024 members per launch, uploads, kernels and downloads of neighbouring pieces
+ * overlapped; empty members are skipped.  Every member's length and CRC32 are checked on the device against its trailer.
+ * MSIM_ERR_VALUE for what the probe refuses and for a member that does not decode: "... member at offset <file offset of
+ * the first such member>: <bad block type | invalid code lengths | invalid code | distance too far back | data past ISIZE |
+ * truncated | invalid stored block lengths | CRC32 mismatch | ISIZE mismatch>"; `out` is then undefined, the context stays
+ * usable.  Nothing is in flight into `out` or out of `in` when the call returns, whatever it returns (a wait that ran into
+ * MSIM_WAIT_TIMEOUT_S is followed by an unbounded one).  `out` is best page-locked (msim_host_alloc).
+ * *device_ms (optional): the inflate kernels' time on the device (events), copies excluded.                             */
+int msim_bgzf_probe(const uint8_t *in, uint64_t n, uint64_t *uncompressed, uint64_t *members);
+int msim_bgzf_inflate(msim_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *written,
+                      float *device_ms);
 /* Ingest one FASTA record straight from file text: `body` = the bytes after the header line, n_bases bases
  * in lines of `lenc` bases every `lenb` bytes (the .fai columns; uniform line width is what pyfaidx
  * requires, util.py:77-91).  Line terminators are skipped and a-z upper-cased on the device

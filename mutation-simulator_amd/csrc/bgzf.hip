@@ -19,6 +19,8 @@
 // k_bgzf_scan + k_bgzf_pack then lay the members out back to back (header, deflate data, CRC32, ISIZE) in one buffer.
 // Everything is a function of the uncompressed bytes only: no timing, no "last writer wins".
 #include <cstring>
+#include <string>
+#include <vector>
 
 #include "ctx.h"
 #include "bgzf.h"
@@ -558,6 +560,339 @@ __global__ void __launch_bounds__(256) k_bgzf_pack(const uint8_t *__restrict__ s
     for (uint32_t i = threadIdx.x; i < csize; i += 256) o[18 + i] = s[i];
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------- inflate
+// k_bgzf_inflate: RFC 1951 decoder, one member per workgroup of ONE wavefront; the member's output is built in LDS (back-
+// references never leave the CU) and written out coalesced once its length and CRC32 have been checked.
+//   symbol loop    every lane runs the same bit reader and the same table look-ups (the wave executes them once): the state
+//                  is wave-uniform, so no lane has to tell the others what it decoded.  A literal is stored by lane 0; a
+//                  match is copied by the wave, lane i taking bytes i, i + 64, ... from out[pos - dist + i mod dist] --
+//                  sources lie before `pos` whatever the overlap, so a distance-1 run of 258 is five LDS stores.
+//   bit reader     a 64-bit buffer topped up 32 bits at a time from the member's deflate data in global memory; the word
+//                  after the one being consumed is always in flight (its latency hides behind ~16 symbols of ACGT text).
+//                  Reads past the member's data yield zeros and are found out by the bit count at the end of each block.
+//   tables         canonical code lengths -> count / sorted-symbol arrays (lane 0, as zlib's checks want them: over-
+//                  subscribed and incomplete sets are refused); a 10-bit (lit/len) and an 8-bit (distance) direct table
+//                  are filled by the wave, each lane decoding its indices through the canonical arrays; longer codes take
+//                  the canonical walk (at most 15 steps).
+//   CRC32          as the encoder: raw CRC per lane span, shifted by x^(8 k) mod P, XOR-combined.
+// Bounds: input reads by in_len, output writes by ISIZE <= 65 536, distances by the bytes produced, every loop by a
+// constant (symbols by ISIZE + blocks, blocks by the member's bits, IZ_MAX_STEPS over all).  A member that fails a check
+// leaves (index << 4 | reason) in the error word (atomicMin: the first one wins) and writes nothing.
+constexpr int IZ_THREADS = 64;
+constexpr int IZ_LBITS = 10, IZ_DBITS = 8;
+constexpr uint32_t IZ_MAX_STEPS = 1u << 20;    // symbols + blocks of one member: 65 536 bytes and 8 * 65 536 / 3 blocks at most
+
+struct IzSmem {
+    uint32_t out[BGZF_MAX_ISIZE / 4 + 1];      // (+1: the write-out reads one word past the last byte)
+    uint32_t crc_table[256];
+    uint32_t x2n[32];
+    uint16_t ltab[1 << IZ_LBITS], dtab[1 << IZ_DBITS];   // symbol << 4 | code length; 0: longer than the table / no code
+    uint16_t lsym[288], dsym[32], csym[20];    // symbols ordered by (code length, symbol)
+    uint16_t lcnt[16], dcnt[16], ccnt[16];     // codes per length
+    uint16_t offs[16];
+    uint8_t lens[320];                         // lit/len code lengths, then the distance code lengths
+    uint8_t cl_lens[20];
+    uint32_t flag;
+    uint32_t crc_acc;
+};
+
+__device__ inline void wave_fence() { __builtin_amdgcn_wave_barrier(); }
+
+// Wave-uniform LSB-first bit reader over in[0, n).
+struct IzBits {
+    const uint8_t *in;
+    uint32_t n;
+    uint64_t buf;
+    uint32_t cnt;                              // valid bits in buf
+    uint32_t pos;                              // bytes taken into buf (may pass n: zeros)
+    uint32_t nxt;                              // the word at pos, already loaded
+    __device__ inline uint32_t word(uint32_t p) const {
+        if (p + 4 <= n) {
+            uint32_t w;
+            __builtin_memcpy(&w, in + p, 4);
+            return w;
+        }
+        uint32_t w = 0;
+        for (uint32_t k = 0; k < 4; k++)
+            if (p + k < n) w |= (uint32_t)in[p + k] << (8 * k);
+        return w;
+    }
+    __device__ inline void start(uint32_t at) { pos = at; buf = 0; cnt = 0; nxt = word(at); }
+    __device__ inline void refill() {          // at least 32 bits afterwards
+        if (cnt <= 32) {
+            buf |= (uint64_t)nxt << cnt;
+            cnt += 32;
+            pos += 4;
+            nxt = word(pos);
+        }
+    }
+    __device__ inline uint32_t peek() const { return (uint32_t)buf; }
+    __device__ inline void drop(uint32_t k) { buf >>= k; cnt -= k; }
+    __device__ inline uint32_t take(uint32_t k) {
+        const uint32_t v = (uint32_t)buf & ((1u << k) - 1u);
+        drop(k);
+        return v;
+    }
+    __device__ inline uint32_t used_bits() const { return pos * 8u - cnt; }
+    __device__ inline bool overrun() const { return used_bits() > n * 8u; }
+};
+
+// the symbol whose canonical code starts the LSB-first bits v; len = its length, 0 if no code of <= maxbits bits matches
+__device__ inline uint32_t canon_decode(uint32_t v, const uint16_t *cnt, const uint16_t *sym, int maxbits, uint32_t &len) {
+    int code = 0, first = 0, index = 0;
+    for (int l = 1; l <= maxbits; l++) {
+        code |= (int)(v & 1u);
+        v >>= 1;
+        const int count = cnt[l];
+        if (code - count < first) { len = (uint32_t)l; return sym[index + (code - first)]; }
+        index += count;
+        first += count;
+        first <<= 1;
+        code <<= 1;
+    }
+    len = 0;
+    return 0;
+}
+
+// Code lengths lens[0, n) -> cnt / sym (lane 0) and, if tab, the direct table (the wave).  zlib's rules: an over-subscribed
+// set is refused, an incomplete one too unless it is a single 1-bit code of a lit/len or distance set (strict: never).
+// Returns false (wave-uniform) for a refused set.
+__device__ bool iz_build(IzSmem &S, const uint8_t *lens, int n, uint16_t *cnt, uint16_t *sym, uint16_t *tab, int tbits,
+                         bool strict) {
+    const int lane = threadIdx.x;
+    __syncthreads();                           // the lengths are written
+    if (lane == 0) {
+        for (int l = 0; l < 16; l++) cnt[l] = 0;
+        for (int s = 0; s < n; s++) cnt[lens[s]]++;
+        int left = 1, maxl = 0;
+        bool ok = true;
+        for (int l = 1; l < 16; l++) {
+            left = (left << 1) - (int)cnt[l];
+            if (left < 0) { ok = false; break; }
+            if (cnt[l]) maxl = l;
+        }
+        if (ok && left > 0 && maxl != 0 && (strict || maxl != 1)) ok = false;
+        if (ok) {
+            uint32_t o = 0;
+            for (int l = 1; l < 16; l++) { S.offs[l] = (uint16_t)o; o += cnt[l]; }
+            for (int s = 0; s < n; s++)
+                if (lens[s]) sym[S.offs[lens[s]]++] = (uint16_t)s;
+        }
+        cnt[0] = 0;
+        S.flag = ok ? 1u : 0u;
+    }
+    __syncthreads();
+    if (!S.flag) return false;
+    if (tab) {
+        for (uint32_t i = lane; i < (1u << tbits); i += IZ_THREADS) {
+            uint32_t len;
+            const uint32_t s = canon_decode(i, cnt, sym, tbits, len);
+            tab[i] = len ? (uint16_t)((s << 4) | len) : (uint16_t)0;
+        }
+        __syncthreads();
+    }
+    return true;
+}
+
+__global__ void __launch_bounds__(IZ_THREADS) k_bgzf_inflate(const uint8_t *__restrict__ src, uint32_t src_len,
+                                                             const BgzfMember *__restrict__ meta, uint8_t *__restrict__ dst,
+                                                             uint32_t *__restrict__ err) {
+    __shared__ IzSmem S;
+    const uint32_t lane = threadIdx.x;
+    const uint32_t m = blockIdx.x;
+    const BgzfMember M = meta[m];
+    uint8_t *outb = reinterpret_cast<uint8_t *>(S.out);
+    uint32_t fail = 0;
+    // (the host pass made these true; a launch with other values must still stay inside its buffers)
+    if (M.isize > BGZF_MAX_ISIZE || (uint64_t)M.in_off + M.in_len > src_len) fail = BGZF_E_TRUNC;
+    const uint32_t isize = M.isize;
+
+    for (uint32_t i = lane; i < 256; i += IZ_THREADS) {
+        uint32_t c = i;
+        for (int k = 0; k < 8; k++) c = (c & 1) ? (c >> 1) ^ 0xedb88320u : c >> 1;
+        S.crc_table[i] = c;
+    }
+    if (lane == 0) {
+        uint32_t p = 1u << 30;                 // x^1
+        for (int k = 0; k < 32; k++) { S.x2n[k] = p; p = multmodp(p, p); }
+        S.crc_acc = 0;
+        S.out[isize / 4] = 0;                  // (the last word's unused bytes and the one past it: defined)
+        if (isize / 4 + 1 <= BGZF_MAX_ISIZE / 4) S.out[isize / 4 + 1] = 0;
+    }
+    __syncthreads();
+
+    IzBits br;
+    br.in = src + M.in_off;
+    br.n = fail ? 0u : M.in_len;
+    br.start(0);
+    uint32_t pos = 0, steps = 0;
+    bool last = false;
+    while (!fail && !last) {
+        if (++steps > IZ_MAX_STEPS) { fail = BGZF_E_STEPS; break; }
+        br.refill();
+        last = br.take(1) != 0;
+        const uint32_t btype = br.take(2);
+        if (btype == 3) { fail = BGZF_E_BTYPE; break; }
+        if (btype == 0) {
+            br.drop(br.cnt & 7u);
+            br.refill();
+            const uint32_t len = br.take(16), nlen = br.take(16);
+            if (br.overrun()) { fail = BGZF_E_TRUNC; break; }
+            if ((len ^ nlen) != 0xffffu) { fail = BGZF_E_STORED; break; }
+            const uint32_t at = br.pos - br.cnt / 8u;      // the byte after NLEN
+            if (at + len > br.n) { fail = BGZF_E_TRUNC; break; }
+            if (pos + len > isize) { fail = BGZF_E_PAST; break; }
+            for (uint32_t i = lane; i < len; i += IZ_THREADS) outb[pos + i] = br.in[at + i];
+            pos += len;
+            br.start(at + len);
+            continue;
+        }
+        if (btype == 1) {
+            for (uint32_t i = lane; i < 288; i += IZ_THREADS) S.lens[i] = i < 144 ? 8 : i < 256 ? 9 : i < 280 ? 7 : 8;
+            if (lane < 32) S.lens[288 + lane] = 5;
+            if (!iz_build(S, S.lens, 288, S.lcnt, S.lsym, S.ltab, IZ_LBITS, false) ||
+                !iz_build(S, S.lens + 288, 32, S.dcnt, S.dsym, S.dtab, IZ_DBITS, false)) { fail = BGZF_E_LENS; break; }
+        } else {
+            const uint32_t hlit = br.take(5) + 257, hdist = br.take(5) + 1, hclen = br.take(4) + 4;
+            if (hlit > 286 || hdist > 30) { fail = BGZF_E_LENS; break; }
+            for (uint32_t i = 0; i < 19; i++) {
+                br.refill();
+                const uint32_t v = i < hclen ? br.take(3) : 0u;
+                if (lane == 0) S.cl_lens[kClOrder[i]] = (uint8_t)v;
+            }
+            if (!iz_build(S, S.cl_lens, 19, S.ccnt, S.csym, nullptr, 0, true)) { fail = BGZF_E_LENS; break; }
+            const uint32_t total = hlit + hdist;
+            uint32_t idx = 0, prev = 0;
+            while (idx < total) {              // (every round adds at least one length: at most 316 rounds)
+                br.refill();
+                uint32_t l;
+                const uint32_t s = canon_decode(br.peek(), S.ccnt, S.csym, 7, l);
+                if (!l) { fail = BGZF_E_LENS; break; }
+                br.drop(l);
+                uint32_t rep = 1, val = s;
+                if (s == 16) {
+                    if (idx == 0) { fail = BGZF_E_LENS; break; }
+                    rep = 3 + br.take(2);
+                    val = prev;
+                } else if (s == 17) {
+                    rep = 3 + br.take(3);
+                    val = 0;
+                } else if (s == 18) {
+                    rep = 11 + br.take(7);
+                    val = 0;
+                }
+                if (idx + rep > total) { fail = BGZF_E_LENS; break; }
+                for (uint32_t i = lane; i < rep; i += IZ_THREADS) S.lens[idx + i] = (uint8_t)val;
+                idx += rep;
+                prev = val;
+            }
+            if (fail) break;
+            if (br.overrun()) { fail = BGZF_E_TRUNC; break; }
+            __syncthreads();
+            if (S.lens[256] == 0) { fail = BGZF_E_LENS; break; }          // no end-of-block code
+            if (!iz_build(S, S.lens, (int)hlit, S.lcnt, S.lsym, S.ltab, IZ_LBITS, false) ||
+                !iz_build(S, S.lens + hlit, (int)hdist, S.dcnt, S.dsym, S.dtab, IZ_DBITS, false)) { fail = BGZF_E_LENS; break; }
+        }
+        // ---- the symbols of this block
+        for (;;) {
+            if (++steps > IZ_MAX_STEPS) { fail = BGZF_E_STEPS; break; }
+            br.refill();
+            uint32_t v = br.peek(), l, sym;
+            const uint32_t e = S.ltab[v & ((1u << IZ_LBITS) - 1u)];
+            if (e) {
+                sym = e >> 4;
+                l = e & 15u;
+            } else {
+                sym = canon_decode(v, S.lcnt, S.lsym, 15, l);
+                if (!l) { fail = BGZF_E_CODE; break; }
+            }
+            br.drop(l);
+            if (sym < 256) {
+                if (pos >= isize) { fail = BGZF_E_PAST; break; }
+                if (lane == 0) outb[pos] = (uint8_t)sym;
+                pos++;
+                wave_fence();
+                continue;
+            }
+            if (sym == 256) break;
+            sym -= 257;
+            if (sym >= 29) { fail = BGZF_E_CODE; break; }
+            uint32_t len;
+            if (sym < 8) len = 3 + sym;
+            else if (sym == 28) len = 258;
+            else {
+                const uint32_t eb = (sym >> 2) - 1;
+                len = 3 + ((4 + (sym & 3u)) << eb) + br.take(eb);
+            }
+            br.refill();
+            v = br.peek();
+            uint32_t ds;
+            const uint32_t de = S.dtab[v & ((1u << IZ_DBITS) - 1u)];
+            if (de) {
+                ds = de >> 4;
+                l = de & 15u;
+            } else {
+                ds = canon_decode(v, S.dcnt, S.dsym, 15, l);
+                if (!l) { fail = BGZF_E_CODE; break; }
+            }
+            br.drop(l);
+            if (ds >= 30) { fail = BGZF_E_CODE; break; }
+            uint32_t dist;
+            if (ds < 4) dist = 1 + ds;
+            else {
+                const uint32_t eb = (ds >> 1) - 1;
+                dist = 1 + ((2 + (ds & 1u)) << eb) + br.take(eb);
+            }
+            if (dist > pos) { fail = BGZF_E_DIST; break; }
+            if (pos + len > isize) { fail = BGZF_E_PAST; break; }
+            const uint32_t from = pos - dist;
+            if (dist >= len || dist >= IZ_THREADS * 5) {     // (258 <= 64 * 5: i < dist for every i)
+                for (uint32_t i = lane; i < len; i += IZ_THREADS) outb[pos + i] = outb[from + i];
+            } else {
+                for (uint32_t i = lane; i < len; i += IZ_THREADS) outb[pos + i] = outb[from + i % dist];
+            }
+            pos += len;
+            wave_fence();
+        }
+        if (!fail && br.overrun()) fail = BGZF_E_TRUNC;
+    }
+    if (fail && fail != BGZF_E_STEPS && br.overrun()) fail = BGZF_E_TRUNC;    // (whatever the zeros past the end decoded to)
+    if (!fail && pos != isize) fail = BGZF_E_ISIZE;
+    __syncthreads();
+
+    // ---- CRC32 of the produced bytes
+    if (!fail) {
+        const uint32_t span = (isize + IZ_THREADS - 1) / IZ_THREADS;
+        const uint32_t a = lane * span < isize ? lane * span : isize, b = a + span < isize ? a + span : isize;
+        uint32_t c = 0;
+        for (uint32_t i = a; i < b; i++) c = S.crc_table[(c ^ outb[i]) & 0xff] ^ (c >> 8);
+        uint32_t x = a < b ? multmodp(x8nmodp(S.x2n, isize - b), c) : 0;
+        if (lane == 0) x ^= multmodp(x8nmodp(S.x2n, isize), 0xffffffffu);
+        atomicXor(&S.crc_acc, x);
+        __syncthreads();
+        if ((S.crc_acc ^ 0xffffffffu) != M.crc) fail = BGZF_E_CRC;
+    }
+    if (fail) {
+        if (lane == 0) atomicMin(err, (m << 4) | fail);
+        return;
+    }
+
+    // ---- write-out: bytes up to the first 4-byte boundary of the destination, whole words, the tail
+    uint8_t *o = dst + M.out_off;
+    uint32_t head = (uint32_t)((4u - ((uintptr_t)o & 3u)) & 3u);
+    if (head > isize) head = isize;
+    if (lane < head) o[lane] = outb[lane];
+    const uint32_t nw = (isize - head) / 4;
+    uint32_t *o32 = reinterpret_cast<uint32_t *>(o + head);
+    for (uint32_t w = lane; w < nw; w += IZ_THREADS) {
+        const uint32_t s = head + 4 * w;
+        o32[w] = __builtin_amdgcn_alignbyte(S.out[(s >> 2) + 1], S.out[s >> 2], s & 3u);
+    }
+    const uint32_t done = head + 4 * nw;
+    if (lane < isize - done) o[done + lane] = outb[done + lane];
+}
+
 }  // namespace
 
 const uint8_t BGZF_EOF[28] = {0x1f, 0x8b, 8, 4, 0, 0, 0, 0, 0, 0xff, 6, 0, 0x42, 0x43, 2, 0, 0x1b, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -598,6 +933,73 @@ hipError_t bgzf_compress_device(const uint8_t *d_src, uint64_t n, BgzfWork &w, h
     if (e == hipSuccess) e = wait_stream(st);
     if (e == hipSuccess) *out_bytes = *w.h_total;
     return e;
+}
+
+const char *bgzf_inflate_reason(uint32_t code) {
+    switch (code) {
+    case BGZF_E_BTYPE: return "bad block type";
+    case BGZF_E_LENS: return "invalid code lengths";
+    case BGZF_E_CODE: return "invalid code";
+    case BGZF_E_DIST: return "distance too far back";
+    case BGZF_E_PAST: return "data past ISIZE";
+    case BGZF_E_TRUNC: return "truncated";
+    case BGZF_E_STORED: return "invalid stored block lengths";
+    case BGZF_E_CRC: return "CRC32 mismatch";
+    case BGZF_E_ISIZE: return "ISIZE mismatch";
+    case BGZF_E_STEPS: return "too many symbols";
+    default: return "unknown";
+    }
+}
+
+bool bgzf_walk(const uint8_t *in, uint64_t n, uint64_t *uncompressed, uint64_t *n_members, std::vector<BgzfMemberHost> *members,
+               std::string *why) {
+    auto bad = [&](uint64_t at, const char *what) {
+        if (why) *why = "offset " + std::to_string(at) + ": " + what;
+        return false;
+    };
+    auto le16 = [&](uint64_t p) { return (uint32_t)in[p] | ((uint32_t)in[p + 1] << 8); };
+    auto le32 = [&](uint64_t p) { return le16(p) | (le16(p + 2) << 16); };
+    uint64_t pos = 0, total = 0, count = 0;
+    if (n < 2 || in[0] != 0x1f || in[1] != 0x8b) return bad(0, "not gzip data");
+    while (pos < n) {
+        if (n - pos < 18) {
+            if (in[pos] == 0x1f && (n - pos < 2 || in[pos + 1] == 0x8b)) return bad(pos, "truncated BGZF member");
+            return bad(pos, "not a gzip member");
+        }
+        if (in[pos] != 0x1f || in[pos + 1] != 0x8b) return bad(pos, "not a gzip member");
+        if (in[pos + 2] != 8 || in[pos + 3] != 4) return bad(pos, "gzip without BGZF framing (no extra field)");
+        const uint64_t xlen = le16(pos + 10), x0 = pos + 12, x1 = x0 + xlen;
+        if (x1 > n) return bad(pos, "truncated BGZF member");
+        int64_t bsize = -1;
+        for (uint64_t x = x0; x + 4 <= x1;) {
+            const uint64_t slen = le16(x + 2);
+            if (in[x] == 'B' && in[x + 1] == 'C' && slen == 2 && x + 6 <= x1) bsize = le16(x + 4);
+            x += 4 + slen;
+        }
+        if (bsize < 0) return bad(pos, "gzip without BGZF framing (no BC subfield)");
+        const uint64_t end = pos + (uint64_t)bsize + 1;
+        if (end > n) return bad(pos, "BSIZE runs past the end of the file (truncated BGZF member)");
+        if (end < x1 + 8) return bad(pos, "BSIZE smaller than the member's header and trailer");
+        const uint32_t crc = le32(end - 8), isize = le32(end - 4);
+        if (isize > BGZF_MAX_ISIZE) return bad(pos, "ISIZE above 65536: not BGZF");
+        count++;
+        if (isize) {
+            if (members) members->push_back(BgzfMemberHost{pos, x1, (uint32_t)(end - 8 - x1), isize, crc});
+            total += isize;
+        }
+        pos = end;
+    }
+    if (uncompressed) *uncompressed = total;
+    if (n_members) *n_members = count;
+    return true;
+}
+
+hipError_t bgzf_inflate_device(const uint8_t *d_in, uint32_t in_len, const BgzfMember *d_meta, uint32_t n, uint8_t *d_out,
+                               uint32_t *d_err, hipStream_t st) {
+    hipError_t e = hipMemsetAsync(d_err, 0xff, sizeof(uint32_t), st);
+    if (e != hipSuccess || !n) return e;
+    k_bgzf_inflate<<<dim3(n), dim3(IZ_THREADS), 0, st>>>(d_in, in_len, d_meta, d_out, d_err);
+    return hipGetLastError();
 }
 
 }  // namespace msim

@@ -305,6 +305,8 @@ int file_bgzf_append(Ctx *c, int ch, const uint8_t *src, uint64_t n);
 int file_bgzf_close(Ctx *c, int ch, uint64_t *compressed, uint64_t *uncompressed);
 uint64_t bgzf_bound(uint64_t n);
 int bgzf_compress_host(Ctx *c, const uint8_t *src, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *written, float *device_ms);
+int bgzf_probe_host(const uint8_t *src, uint64_t n, uint64_t *uncompressed, uint64_t *members);
+int bgzf_inflate_host(Ctx *c, const uint8_t *src, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *written, float *device_ms);
 void device_host_cpus(int device, char *buf, size_t cap);   // cpulist of the device's NUMA node ("" if unknown)
 
 // render.cpp

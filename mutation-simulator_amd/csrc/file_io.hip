@@ -463,6 +463,113 @@ int bgzf_compress_host(Ctx *c, const uint8_t *src, uint64_t n, uint8_t *out, uin
     return MSIM_OK;
 }
 
+// One-shot: a whole BGZF file (host bytes) -> its uncompressed bytes in `out`.  Pieces of at most BGZF_PIECE_BLOCKS members
+// alternate between two slots, each with a stream of its own (upload -> k_bgzf_inflate -> download), so that a piece's
+// copies overlap its neighbour's kernel.  `src` and `out` belong to the caller: whatever ends the call -- a member that
+// fails a check, a HIP error, a wait that ran into its deadline -- both streams are drained before it returns, so no copy
+// is left in flight into memory the caller may free.
+int bgzf_probe_host(const uint8_t *src, uint64_t n, uint64_t *uncompressed, uint64_t *members) {
+    std::string why;
+    if (!bgzf_walk(src, n, uncompressed, members, nullptr, &why)) return fail(nullptr, MSIM_ERR_VALUE, "BGZF input, " + why);
+    return MSIM_OK;
+}
+
+int bgzf_inflate_host(Ctx *c, const uint8_t *src, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *written, float *device_ms) {
+    std::vector<BgzfMemberHost> mem;
+    std::string why;
+    uint64_t total = 0;
+    if (!bgzf_walk(src, n, &total, nullptr, &mem, &why)) return fail(c, MSIM_ERR_VALUE, "BGZF input, " + why);
+    if (cap < total) return fail(c, MSIM_ERR_ARG, "BGZF output buffer smaller than the uncompressed size msim_bgzf_probe reports");
+    *written = 0;
+    if (device_ms) *device_ms = 0;
+    constexpr size_t P = BGZF_PIECE_BLOCKS;
+    constexpr size_t IN_CAP = P * 65536, OUT_CAP = P * (size_t)BGZF_MAX_ISIZE;
+    struct Slot {
+        hipStream_t st = nullptr;
+        hipEvent_t ev[2] = {nullptr, nullptr};
+        uint8_t *d_in = nullptr, *d_out = nullptr;
+        BgzfMember *d_meta = nullptr, *h_meta = nullptr;
+        uint32_t *d_err = nullptr, *h_err = nullptr;
+        bool busy = false;
+        size_t first = 0;                      // index of the piece's first member in `mem`
+    } slot[2];
+    hipError_t e = hipSuccess;
+    for (auto &s : slot) {
+        if (e == hipSuccess) e = hipStreamCreateWithFlags(&s.st, hipStreamNonBlocking);
+        for (int i = 0; i < 2 && e == hipSuccess; i++) e = hipEventCreate(&s.ev[i]);
+        if (e == hipSuccess) e = hipMalloc((void **)&s.d_in, IN_CAP);
+        if (e == hipSuccess) e = hipMalloc((void **)&s.d_out, OUT_CAP);
+        if (e == hipSuccess) e = hipMalloc((void **)&s.d_meta, P * sizeof(BgzfMember));
+        if (e == hipSuccess) e = hipMalloc((void **)&s.d_err, sizeof(uint32_t));
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_meta, P * sizeof(BgzfMember), hipHostMallocDefault);
+        if (e == hipSuccess) e = hipHostMalloc((void **)&s.h_err, sizeof(uint32_t), hipHostMallocDefault);
+    }
+    float total_ms = 0;
+    int rc = MSIM_OK;
+    // the piece in `s` has finished: its time, its error word
+    auto collect = [&](Slot &s) {
+        if (!s.busy) return;
+        e = wait_stream(s.st);
+        if (e != hipSuccess) return;
+        s.busy = false;
+        float ms = 0;
+        if (device_ms && hipEventElapsedTime(&ms, s.ev[0], s.ev[1]) == hipSuccess) total_ms += ms;
+        const uint32_t w = *s.h_err;
+        if (w != 0xffffffffu && rc == MSIM_OK) {
+            const BgzfMemberHost &m = mem[s.first + (w >> 4)];
+            rc = fail(c, MSIM_ERR_VALUE, "BGZF input, member at offset " + std::to_string(m.start) + ": " + bgzf_inflate_reason(w & 15u));
+        }
+    };
+    uint64_t out_pos = 0;
+    size_t k = 0;
+    int turn = 0;
+    while (e == hipSuccess && rc == MSIM_OK && k < mem.size()) {
+        Slot &s = slot[turn];
+        collect(s);                            // (the slot's previous piece: its buffers are free again)
+        if (e != hipSuccess || rc != MSIM_OK) break;
+        const size_t k1 = std::min(mem.size(), k + P);
+        const uint64_t in0 = mem[k].start, in1 = (uint64_t)mem[k1 - 1].payload + mem[k1 - 1].payload_len;
+        if (in1 - in0 > IN_CAP) {              // (cannot happen: a member is at most 65 536 bytes and empty ones hold 28)
+            size_t q = k + 1;
+            while (q < k1 && (uint64_t)mem[q].payload + mem[q].payload_len - in0 <= IN_CAP) q++;
+            rc = fail(c, MSIM_ERR_VALUE, "BGZF input, member at offset " + std::to_string(mem[q - 1].start) + ": too many empty members around it");
+            break;
+        }
+        uint32_t o = 0;
+        for (size_t q = k; q < k1; q++) {
+            s.h_meta[q - k] = BgzfMember{(uint32_t)(mem[q].payload - in0), mem[q].payload_len, o, mem[q].isize, mem[q].crc};
+            o += mem[q].isize;
+        }
+        s.first = k;
+        s.busy = true;
+        e = hipMemcpyAsync(s.d_in, src + in0, in1 - in0, hipMemcpyHostToDevice, s.st);
+        if (e == hipSuccess) e = hipMemcpyAsync(s.d_meta, s.h_meta, (k1 - k) * sizeof(BgzfMember), hipMemcpyHostToDevice, s.st);
+        if (e == hipSuccess) e = hipEventRecord(s.ev[0], s.st);
+        if (e == hipSuccess) e = bgzf_inflate_device(s.d_in, (uint32_t)(in1 - in0), s.d_meta, (uint32_t)(k1 - k), s.d_out, s.d_err, s.st);
+        if (e == hipSuccess) e = hipEventRecord(s.ev[1], s.st);
+        if (e == hipSuccess) e = hipMemcpyAsync(s.h_err, s.d_err, sizeof(uint32_t), hipMemcpyDeviceToHost, s.st);
+        if (e == hipSuccess) e = hipMemcpyAsync(out + out_pos, s.d_out, o, hipMemcpyDeviceToHost, s.st);
+        out_pos += o;
+        k = k1;
+        turn ^= 1;
+    }
+    for (int i = 0; i < 2 && e == hipSuccess; i++) collect(slot[turn ^ i]);   // (oldest first: the first failing member is reported)
+    // nothing may stay in flight into `out` / out of `src`: after an error or a deadline this wait has no limit
+    for (auto &s : slot) if (s.st) (void)hipStreamSynchronize(s.st);
+    for (auto &s : slot) {
+        for (void *p : {(void *)s.d_in, (void *)s.d_out, (void *)s.d_meta, (void *)s.d_err}) if (p) (void)hipFree(p);
+        if (s.h_meta) (void)hipHostFree(s.h_meta);
+        if (s.h_err) (void)hipHostFree(s.h_err);
+        for (auto x : s.ev) if (x) (void)hipEventDestroy(x);
+        if (s.st) (void)hipStreamDestroy(s.st);
+    }
+    if (device_ms) *device_ms = total_ms;
+    if (rc != MSIM_OK) return rc;
+    if (e != hipSuccess) return hip_fail(c, e, "BGZF inflate");
+    *written = total;
+    return MSIM_OK;
+}
+
 void device_host_cpus(int device, char *buf, size_t cap) { gpu_node_cpulist(device, buf, cap); }
 
 // `fd` must be something pwrite() can address: a regular file.  MSIM_ERR_UNSUPPORTED otherwise (a pipe, a terminal): the

@@ -986,6 +986,21 @@ int msim_bgzf_compress(msim_ctx *p, const uint8_t *in, uint64_t n, uint8_t *out,
     return bgzf_compress_host(c, in, n, out, cap, written, device_ms);
 }
 
+// BGZF input: the member chain on the host, the members' deflate data on the device (bgzf.hip: k_bgzf_inflate).
+int msim_bgzf_probe(const uint8_t *in, uint64_t n, uint64_t *uncompressed, uint64_t *members) {
+    if (!in && n) return MSIM_ERR_ARG;
+    return bgzf_probe_host(in, n, uncompressed, members);
+}
+
+int msim_bgzf_inflate(msim_ctx *p, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *written,
+                      float *device_ms) {
+    Ctx *c = C(p);
+    if (!c || (!in && n) || (!out && cap) || !written) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    TraceRange tr("msim bgzf: inflate");
+    return bgzf_inflate_host(c, in, n, out, cap, written, device_ms);
+}
+
 int msim_add_contig_text(msim_ctx *p, const uint8_t *body, uint64_t body_bytes, uint64_t n_bases, uint32_t lenc,
                          uint32_t lenb, int *contig) {
     CTX_FLUSHED(c, p)

@@ -7,7 +7,7 @@ from ._version import __version__
 from .argument_parser import get_args
 from .bedpe_writer import BedpeWriter, BedpeWriterError
 from .colors import Colors
-from .fasta_io import FastaIndexingError, FastaNotFoundError
+from .fasta_io import FastaIndexingError, FastaNotFoundError, UnsupportedCompressionFormat
 from .fasta_writer import FastaWriter, FastaWriterError
 from .it_mutator import ITMutator
 from .mut_types import MutType

@@ -8,12 +8,13 @@ from timeit import default_timer as timer
 
 from . import *  # noqa: F401,F403  (same style of namespace as the reference entry point)
 from ._ffi import MsimError, MsimUnsupported
+from .fasta_io import is_gzip
 
 _INIT_ERRORS = (FileNotFoundError, ITNotEnoughAvailChromsError, RatesTooHighError, RatesTooLowError,
                 FastaIndexingError, FastaNotFoundError, ItRateTooHighError, ItRateTooLowError,
                 RMTParseError, MissingLengthError, MinimumLengthTooLowError, TitvTooLowError,
                 ChromNotExistError, RangeDefinitionOutOfBoundsError, FastaDuplicateHeaderError,
-                MinimumLengthHigherThanMaximumError)
+                MinimumLengthHigherThanMaximumError, UnsupportedCompressionFormat)
 
 
 STAGES: dict = {}          # wall seconds of the last run's stages (--bench-json: cli_s)
@@ -21,6 +22,10 @@ STAGES: dict = {}          # wall seconds of the last run's stages (--bench-json
 
 class BgzipUnsupportedError(Exception):
     """--bgzip together with what it does not cover (the IT pass, a sharded run)."""
+
+
+class CompressedInputUnsupportedError(Exception):
+    """A gzip-compressed input together with what does not cover it (a sharded run)."""
 
 
 def _warm_up(args):
@@ -39,6 +44,11 @@ def initialize(argv=None):
         exit_with_error(BgzipUnsupportedError("--bgzip does not apply to the interchromosomal pass (it)"), args.no_color)
     if args.bgzip and (args.gpus or 1) > 1:
         exit_with_error(BgzipUnsupportedError("--bgzip needs a single-GPU run (--gpus 1)"), args.no_color)
+    if (args.gpus or 1) > 1 and is_gzip(args.infile):
+        # (the parent of a sharded run never opens a GPU, and parent and workers would each inflate the whole file)
+        exit_with_error(CompressedInputUnsupportedError(
+            f"compressed input ({args.infile.name}) needs a single-GPU run (--gpus 1); inflate it first (bgzip -d) for --gpus N"),
+            args.no_color)
     # the GPU comes up while the FASTA is read and indexed (never in the parent of --gpus N; with --bgzip and an RMT only
     # once the RMT is known to hold no it lines)
     early = (args.gpus or 1) <= 1 and not (args.bgzip and args.mode == "rmt")
@@ -46,8 +56,12 @@ def initialize(argv=None):
         _warm_up(args)
     try:
         t0 = timer()
-        fasta = load_fasta(args.infile)
+        fasta = load_fasta(args.infile, args.device or 0)
         STAGES["load_index"] = timer() - t0
+        # the genome's own name: what the VCF header and an RMT's `fasta` line call it (genome.fa for a BGZF genome.fa.gz)
+        args.genome_name = args.infile.name
+        if fasta.compressed and args.infile.suffix.lower() in (".gz", ".bgz") and args.infile.stem:
+            args.genome_name = args.infile.stem
         if args.mode == "args":
             sim = SimulationSettings.from_args(args, fasta, args.ignore_warnings)
         elif args.mode == "it":
@@ -67,7 +81,7 @@ def initialize(argv=None):
 
 
 def warn_user(args, sim):
-    if sim.fasta and args.infile.name != sim.fasta:
+    if sim.fasta and sim.fasta not in (args.infile.name, getattr(args, "genome_name", args.infile.name)):
         print_warning("Fasta filename does not match RMT", args.no_color)
     if sim.md5 and get_md5(args.infile) != sim.md5:
         print_warning("Fasta md5 hash does not match RMT", args.no_color)
@@ -105,8 +119,8 @@ def main(argv=None):
     if sim.has_it:                         # the second pass reads what the first one wrote (reference __main__.py:88-102)
         if sim.has_mutations:
             try:
-                fasta = load_fasta(args.outfasta)
-            except (FastaDuplicateHeaderError, FastaIndexingError, FastaNotFoundError) as e:
+                fasta = load_fasta(args.outfasta, args.device or 0)
+            except (FastaDuplicateHeaderError, FastaIndexingError, FastaNotFoundError, UnsupportedCompressionFormat) as e:
                 exit_with_error(e, args.no_color)
         try:
             it_mutator = ITMutator(args, fasta, sim)

@@ -129,6 +129,8 @@ SYMBOLS = [
     ("msim_bgzf_close", C.c_int, [_VP, C.c_int, _U64P, _U64P]),
     ("msim_bgzf_bound", C.c_uint64, [C.c_uint64]),
     ("msim_bgzf_compress", C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint64, _U64P, C.POINTER(C.c_float)]),
+    ("msim_bgzf_probe", C.c_int, [_VP, C.c_uint64, _U64P, _U64P]),
+    ("msim_bgzf_inflate", C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint64, _U64P, C.POINTER(C.c_float)]),
     ("msim_device_host_cpus", C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     ("msim_batch_fetch_file", C.c_int, [_VP, C.c_int, C.c_uint64, C.c_int, C.c_uint64]),
     ("msim_add_contig_text", C.c_int, [_VP, _VP, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _IP]),
@@ -524,6 +526,28 @@ class Engine:
         res = out[:got.value].tobytes()
         return (res, ms.value) if timed else res
 
+    # ------------------------------------------------------------------ BGZF input (msim.h: msim_bgzf_probe / _inflate)
+    def bgzf_inflate(self, data, out: np.ndarray | None = None, timed: bool = False):
+        """A whole BGZF file (bytes-like) inflated on the device.  ``out`` (uint8, at least the probe's byte count; best a
+        ``host_buffer``): filled, and the view ``out[:n]`` is returned; without it the result is a ``bytes`` object.
+        ``timed``: (result, kernel ms).  ``MsimError`` with ``code == ERR_VALUE`` for bytes that are not BGZF and for a
+        member that does not decode (the message names the member's file offset and the reason)."""
+        buf = _as_u8(data)
+        n = int(buf.shape[0])
+        total, _ = bgzf_probe(buf)
+        dst = np.empty(total, dtype=np.uint8) if out is None else out
+        if dst.dtype != np.uint8 or dst.ndim != 1 or not dst.flags.c_contiguous or not dst.flags.writeable:
+            raise ValueError("out must be a writable contiguous uint8 array")
+        got, ms = C.c_uint64(), C.c_float()
+        rc = self.lib.msim_bgzf_inflate(self.h, C.c_void_p(buf.ctypes.data) if n else None, n,
+                                        C.c_void_p(dst.ctypes.data) if dst.shape[0] else None, int(dst.shape[0]),
+                                        C.byref(got), C.byref(ms) if timed else None)
+        if rc == ERR_VALUE:
+            raise _bgzf_error(rc, self.lib.msim_last_error(self.h).decode())
+        self._check(rc)
+        res = dst[:got.value].tobytes() if out is None else dst[:got.value]
+        return (res, ms.value) if timed else res
+
     def fetch_sequence_framed_to_file(self, contig: int, bpl: int, fd: int, offset: int) -> int:
         """The framed body QUEUED for bytes [offset, offset + n) of the open regular file ``fd`` (libmsim's output channel
         writes it while the caller goes on; ``file_wait`` / ``sync`` / ``close`` join); returns n.  ``MsimUnsupported``:
@@ -732,6 +756,32 @@ def render_vcf(recs: np.ndarray, pool: np.ndarray, bases: np.ndarray, seq_name: 
 FASTA_RECORD_DTYPE = np.dtype([("h0", "<u8"), ("h1", "<u8"), ("b0", "<u8"), ("b1", "<u8"), ("n_bases", "<u8"),
                                ("lenc", "<u4"), ("lenb", "<u4"), ("flags", "<u4"), ("rsv", "<u4")])   # msim_fasta_record
 FASTA_HAS_BODY, FASTA_BAD_LINES, FASTA_NONUNIFORM = 1, 2, 4
+
+
+def _as_u8(data) -> np.ndarray:
+    if isinstance(data, np.ndarray):
+        return np.ascontiguousarray(data).view(np.uint8).reshape(-1)
+    return np.frombuffer(data, dtype=np.uint8)
+
+
+def _bgzf_error(rc: int, msg: str) -> MsimError:
+    e = MsimError(f"libmsim error {rc}: {msg}")
+    e.code = rc
+    return e
+
+
+def bgzf_probe(data):
+    """(uncompressed bytes, members) of a BGZF file given as bytes-like, from a host pass over its member chain (no
+    device, no context); empty members count.  ``MsimError`` with ``code == ERR_VALUE``: not gzip, gzip without BGZF
+    framing, a BSIZE past the end, a truncated member."""
+    lib = load()
+    buf = _as_u8(data)
+    n = int(buf.shape[0])
+    total, members = C.c_uint64(), C.c_uint64()
+    rc = lib.msim_bgzf_probe(C.c_void_p(buf.ctypes.data) if n else None, n, C.byref(total), C.byref(members))
+    if rc != OK:
+        raise _bgzf_error(rc, lib.msim_last_error(None).decode())
+    return total.value, members.value
 
 
 def fasta_index(text: np.ndarray):

@@ -13,6 +13,7 @@ from pathlib import Path
 
 from ._version import __version__
 from .defaults import Defaults as D
+from .fasta_io import is_gzip
 
 
 def add_outfile_names(args: Namespace) -> Namespace:
@@ -20,12 +21,19 @@ def add_outfile_names(args: Namespace) -> Namespace:
 
     ``-o`` may be a basename or a directory-like path with an empty stem (".", "dir/.."): then the
     input's stem is used inside that directory.
+
+    For an input that IS gzip-compressed (by content: it exists and starts with the gzip magic) a trailing ``.gz`` /
+    ``.bgz`` of its name is dropped before the names are derived: ``genome.fa.gz`` gives ``genome_ms.fa`` +
+    ``genome_ms.vcf``.  Every other input -- a text Fasta whatever its name -- keeps the reference's names.
     """
+    infile = args.infile
+    if infile.suffix.lower() in (".gz", ".bgz") and infile.stem and is_gzip(infile):
+        infile = infile.with_suffix("")
     try:
         args.outbase = args.outbase.with_stem(args.outbase.stem + "_ms")
     except ValueError:
-        args.outbase = args.outbase / (args.infile.stem + "_ms")
-    args.outfasta = args.outbase.with_suffix(args.infile.suffix)
+        args.outbase = args.outbase / (infile.stem + "_ms")
+    args.outfasta = args.outbase.with_suffix(infile.suffix)
     args.outfastait = args.outfasta.with_stem(args.outfasta.stem + "_it")
     args.outvcf = args.outfasta.with_suffix(".vcf")
     args.outbedpe = args.outfastait.with_suffix(".bedpe")

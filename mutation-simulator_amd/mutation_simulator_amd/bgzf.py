@@ -1,4 +1,6 @@
-"""BGZF output (``--bgzip``): the writers' bytes go to one of libmsim's output channels in BGZF mode, which compresses
+"""BGZF input is read through ``fasta_io`` (``Engine.bgzf_inflate``); this module is the output side and the checkers.
+
+BGZF output (``--bgzip``): the writers' bytes go to one of libmsim's output channels in BGZF mode, which compresses
 them on the device (csrc/bgzf.hip) and writes the members (csrc/file_io.hip).  Also a pure-Python reader of the BGZF
 structure (SAM/BAM specification section 4.1) and a zlib-made reference file, for checks and measurements."""
 from __future__ import annotations
@@ -156,14 +158,19 @@ def check_file(data: bytes) -> bytes:
     return b"".join(inflate_members(data))
 
 
-def zlib_bgzf(data: bytes, level: int = 1) -> bytes:
-    """``data`` as BGZF made by Python's zlib at ``level`` (same 65 280-byte blocking): the yardstick for sizes."""
+def make_member(blk: bytes, payload: bytes) -> bytes:
+    """One BGZF member around the raw deflate data ``payload`` of ``blk``."""
+    return (b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00"
+            + struct.pack("<H", len(payload) + 25) + payload + struct.pack("<II", zlib.crc32(blk), len(blk)))
+
+
+def zlib_bgzf(data: bytes, level: int = 1, strategy: int = zlib.Z_DEFAULT_STRATEGY, block: int = BGZF_BLOCK) -> bytes:
+    """``data`` as BGZF made by Python's zlib at ``level`` (same 65 280-byte blocking): the yardstick for sizes, and with
+    ``strategy`` (``zlib.Z_FIXED`` ...) the source of members of every deflate block type for the inflate tests."""
     out = []
-    for a in range(0, len(data), BGZF_BLOCK):
-        blk = data[a:a + BGZF_BLOCK]
-        c = zlib.compressobj(level, zlib.DEFLATED, -15)
-        payload = c.compress(blk) + c.flush()
-        out.append(b"\x1f\x8b\x08\x04\x00\x00\x00\x00\x00\xff\x06\x00BC\x02\x00"
-                   + struct.pack("<H", len(payload) + 25) + payload + struct.pack("<II", zlib.crc32(blk), len(blk)))
+    for a in range(0, len(data), block):
+        blk = data[a:a + block]
+        c = zlib.compressobj(level, zlib.DEFLATED, -15, 8, strategy)
+        out.append(make_member(blk, c.compress(blk) + c.flush()))
     out.append(EOF_BLOCK)
     return b"".join(out)

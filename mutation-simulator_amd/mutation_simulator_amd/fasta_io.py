@@ -16,6 +16,12 @@ libmsim: ``msim_fasta_index``) and exposes the small part of the pyfaidx surface
 plus ``record.body`` (the record's file text, for ingest on the device: the HIP gather kernel skips the
 line terminators and upper-cases) and ``record.bases`` (np.uint8, materialised lazily on the host).  Like
 pyfaidx it leaves a samtools-style ``<infile>.fai`` next to the input when it can.
+
+Like pyfaidx it also reads BGZF-compressed Fasta (``bgzip genome.fa``, or this tool's own ``--bgzip`` output).  The format is
+recognised by content, not by name: a file that starts with the gzip magic and carries BGZF framing is inflated on the
+device (``Engine.bgzf_inflate``: csrc/bgzf.hip, one member per workgroup) into page-locked host memory, and that text takes
+the place of the mapped file for everything above.  Plain (single-stream) gzip is refused with
+``UnsupportedCompressionFormat``; no ``.fai`` is written for a compressed input (its offsets would need a ``.gzi``).
 """
 from __future__ import annotations
 
@@ -33,6 +39,67 @@ class FastaIndexingError(Exception):
 
 class FastaNotFoundError(Exception):
     """Input FASTA does not exist / is unreadable."""
+
+
+class UnsupportedCompressionFormat(Exception):
+    """The input is gzip-compressed but not BGZF (pyfaidx's name for the same case)."""
+
+
+def is_gzip(filename) -> bool:
+    """The file starts with the gzip magic (1f 8b)."""
+    try:
+        with open(filename, "rb") as fh:
+            return fh.read(2) == b"\x1f\x8b"
+    except OSError:
+        return False
+
+
+class _PinnedText:
+    """Owner of the inflated text: a page-locked buffer of a short-lived engine.  Arrays made from it (``np.asarray``) keep
+    it -- and with it the buffer -- alive; the engine goes when the last of them does."""
+
+    def __init__(self, engine, view: np.ndarray):
+        self._engine = engine
+        self.__array_interface__ = dict(view.__array_interface__)
+
+    def __del__(self):
+        eng, self._engine = self._engine, None
+        if eng is not None:
+            eng.close()
+
+
+def _inflate_bgzf(raw: np.ndarray, filename: str, device: int, engine=None) -> np.ndarray:
+    """The uncompressed text of the BGZF file ``raw``, inflated on ``device`` (or by ``engine``, whose buffer it then is)."""
+    from . import _ffi
+    try:
+        total, _ = _ffi.bgzf_probe(raw)
+    except _ffi.MsimError as e:
+        if getattr(e, "code", None) != _ffi.ERR_VALUE:
+            raise
+        raise UnsupportedCompressionFormat(
+            f"Compressed FASTA is only supported in BGZF format. Use the samtools bgzip utility (instead of gzip) to "
+            f"compress {filename} ({str(e).split(': ', 1)[-1]})") from None
+    if total == 0:
+        return np.zeros(0, np.uint8)
+    own = engine is None
+    eng = _ffi.Engine(int(device)) if own else engine
+    try:
+        buf = eng.host_buffer(total)
+        try:
+            text = eng.bgzf_inflate(raw, out=buf)
+        except _ffi.MsimError as e:
+            if getattr(e, "code", None) != _ffi.ERR_VALUE:
+                raise
+            raise FastaIndexingError(f"Compressed FASTA {filename} is damaged: {str(e).split(': ', 1)[-1]}") from None
+    except BaseException:
+        if own:
+            eng.close()
+        raise
+    if not own:
+        return text
+    out = np.asarray(_PinnedText(eng, text))
+    out.flags.writeable = False
+    return out
 
 
 class FastaRecord:
@@ -100,7 +167,7 @@ class _FaidxIndex(Mapping):
 
 
 class Fasta:
-    def __init__(self, filename, write_index: bool = True, **_pyfaidx_compat):
+    def __init__(self, filename, write_index: bool = True, device: int = 0, engine=None, **_pyfaidx_compat):
         filename = str(filename)
         if not os.path.isfile(filename):
             raise FastaNotFoundError(f"Cannot read FASTA from file {filename}")
@@ -116,6 +183,12 @@ class Fasta:
         else:
             self._map = None
             raw = np.zeros(0, np.uint8)
+        self.compressed = size >= 2 and raw[0] == 0x1F and raw[1] == 0x8B
+        if self.compressed:                            # BGZF (by content, whatever the name): the text comes from the device
+            raw = _inflate_bgzf(raw, filename, device, engine)
+            self._map = None
+            size = int(raw.shape[0])
+            write_index = False                        # (a .fai of the uncompressed offsets is of no use next to a .gz)
         self.text = raw                                # the whole file text (the batch path hands spans of it to libmsim)
         self.text_bytes = size
         self.index_table = _ffi_empty_index()          # msim_fasta_record per record, file order (numpy structured array)

@@ -324,7 +324,7 @@ class Mutator:
         dev = getattr(args, "device", 0) or 0
         self._fasta_writer = FastaWriter(args.outfasta, bgzip=self._bgzip, device=dev)
         self._vcf_writer = VcfWriter(args.outvcf, bgzip=self._bgzip, device=dev)
-        self._vcf_writer.write_header(args.infile.name, fasta, sim.assembly_name, sim.species_name,
+        self._vcf_writer.write_header(getattr(args, "genome_name", args.infile.name), fasta, sim.assembly_name, sim.species_name,
                                       sim.sample_name)
         self._engine = engine
         self._own_engine = engine is None

@@ -46,9 +46,10 @@ def get_md5(fname: Path) -> str:
     return digest.hexdigest()
 
 
-def load_fasta(fname: Path) -> Fasta:
-    """Load the input genome (replaces the reference's pyfaidx call, util.py:77-91)."""
+def load_fasta(fname: Path, device: int = 0) -> Fasta:
+    """Load the input genome (replaces the reference's pyfaidx call, util.py:77-91).  ``device``: where a BGZF-compressed
+    input is inflated."""
     try:
-        return Fasta(str(Path(fname).resolve()))
+        return Fasta(str(Path(fname).resolve()), device=device)
     except ValueError:
         raise FastaDuplicateHeaderError(f"Fasta {fname} contains duplicate header")

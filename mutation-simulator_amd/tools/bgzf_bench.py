@@ -1,17 +1,25 @@
 """BGZF on the device (csrc/bgzf.hip): kernel throughput, compressed size against zlib level 1 at the same 65 280-byte
 blocking, and the CLI end to end with and without --bgzip.  Prints one JSON line.
 
-    python tools/bgzf_bench.py [--gb 1.0] [--cli-gb 1.2] [--no-cli]
+The inflate leg (``--inflate``, input side: k_bgzf_inflate) adds to the same line: kernel GB/s of uncompressed output for
+zlib-level-6 members of Fasta text, for our own encoder's members of the same text and for VCF text; the one-shot call end
+to end (upload + kernel + download into page-locked memory); ``zlib.decompress`` of the same members on one host core and
+over a 16-thread pool (device and pool alternate, min / median / max); and the CLI end to end on a genome given as ``.fa``,
+as ``.fa.gz`` and as ``.fa`` after a timed host inflate to a file.
+
+    python tools/bgzf_bench.py [--gb 1.0] [--cli-gb 1.2] [--no-cli] [--inflate] [--no-compress]
 """
 from __future__ import annotations
 
 import argparse
+import concurrent.futures
 import json
 import os
 import subprocess
 import sys
 import tempfile
 import time
+import zlib
 from pathlib import Path
 
 import numpy as np
@@ -89,18 +97,97 @@ def cli(tmp: Path, inp: Path, extra):
     return time.perf_counter() - t0
 
 
+def _mmm(xs):
+    xs = sorted(xs)
+    return {"min": round(xs[0], 4), "median": round(xs[len(xs) // 2], 4), "max": round(xs[-1], 4)}
+
+
+def _host_inflate(payloads, pool):
+    def one(p):
+        return len(zlib.decompress(p, -15))                # (zlib releases the GIL while it inflates)
+    t0 = time.perf_counter()
+    n = sum(pool.map(one, payloads, chunksize=64)) if pool else sum(map(one, payloads))
+    return time.perf_counter() - t0, n
+
+
+def inflate_kernel(eng, gz: bytes, n: int, reps: int = 3):
+    out = eng.host_buffer(n)
+    eng.bgzf_inflate(gz, out=out)                          # (warm-up: code objects, first touch of the buffer)
+    ms = [eng.bgzf_inflate(gz, out=out, timed=True)[1] for _ in range(reps)]
+    return {"bytes": n, "compressed": len(gz), "kernel_ms": _mmm(ms), "gbps": round(n / min(ms) / 1e6, 2)}, out
+
+
+def inflate_leg(eng, n: int, reps: int = 5):
+    text = fasta_text(n)
+    res = {}
+    z6 = bgzf.zlib_bgzf(text[: min(n, 256_000_000)], 6)    # (level 6 on a host core is slow: a quarter GB of it)
+    res["fasta_zlib6"], _ = inflate_kernel(eng, z6, min(n, 256_000_000))
+    own = eng.bgzf_compress(text)
+    res["fasta_own"], out = inflate_kernel(eng, own, len(text))
+    vcf = vcf_text(min(n, 200_000_000))
+    res["vcf_zlib6"], _ = inflate_kernel(eng, bgzf.zlib_bgzf(vcf, 6), len(vcf))
+    # the one-shot call end to end against the host, same members, alternated in one process
+    payloads = [m[4] for m in bgzf.parse_members(own) if m[2]]
+    dev, pool16, one = [], [], []
+    with concurrent.futures.ThreadPoolExecutor(16) as pool:
+        _host_inflate(payloads[:2000], pool)
+        for k in range(reps):
+            t0 = time.perf_counter()
+            eng.bgzf_inflate(own, out=out)
+            dev.append(time.perf_counter() - t0)
+            pool16.append(_host_inflate(payloads, pool)[0])
+            if k == 0:
+                one.append(_host_inflate(payloads, None)[0])
+    res["one_shot"] = {"bytes": len(text), "device_s": _mmm(dev), "zlib_16_threads_s": _mmm(pool16),
+                       "zlib_1_core_s": round(one[0], 4), "device_gbps": round(len(text) / min(dev) / 1e9, 2),
+                       "pool_gbps": round(len(text) / min(pool16) / 1e9, 2),
+                       "device_faster_outside_spread": max(dev) < min(pool16)}
+    return res
+
+
+def inflate_cli(td: Path, total: int, reps: int = 3):
+    inp, gz = td / "g.fa", td / "g.fa.gz"
+    write_genome(inp, total)
+    with open(inp, "rb") as f, open(gz, "wb") as g:
+        while True:
+            chunk = f.read(512 * bgzf.BGZF_BLOCK)
+            if not chunk:
+                break
+            g.write(bgzf.zlib_bgzf(chunk, 1)[:-28])
+        g.write(bgzf.EOF_BLOCK)
+    cli(td, inp, [])                                       # (warm: page cache, code objects)
+    plain, comp, host = [], [], []
+    for _ in range(reps):
+        plain.append(cli(td, inp, []))
+        comp.append(cli(td, gz, []))
+        t0 = time.perf_counter()
+        subprocess.run(f"gzip -dc {gz} > {td / 'h.fa'}", shell=True, check=True)
+        t1 = time.perf_counter()
+        host.append((t1 - t0) + cli(td, td / "h.fa", []))
+    return {"bases": total, "fa_s": _mmm(plain), "fa_gz_s": _mmm(comp), "gzip_d_then_fa_s": _mmm(host),
+            "gz_bytes": gz.stat().st_size}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gb", type=float, default=1.0)
     ap.add_argument("--cli-gb", type=float, default=1.2)
     ap.add_argument("--no-cli", action="store_true")
+    ap.add_argument("--inflate", action="store_true", help="add the inflate (compressed input) leg")
+    ap.add_argument("--no-compress", action="store_true", help="skip the compression legs")
     a = ap.parse_args()
     n = int(a.gb * 1e9)
     res = {}
     with _ffi.Engine(0) as eng:
-        res["fasta"] = kernel(eng, fasta_text(n))
-        res["vcf"] = kernel(eng, vcf_text(min(n, 200_000_000)))
-    if not a.no_cli:
+        if not a.no_compress:
+            res["fasta"] = kernel(eng, fasta_text(n))
+            res["vcf"] = kernel(eng, vcf_text(min(n, 200_000_000)))
+        if a.inflate:
+            res["inflate"] = inflate_leg(eng, n)
+    if a.inflate and not a.no_cli:
+        with tempfile.TemporaryDirectory() as td:
+            res["inflate_cli"] = inflate_cli(Path(td), int(a.cli_gb * 1e9))
+    if not a.no_cli and not a.no_compress:
         with tempfile.TemporaryDirectory() as td:
             td = Path(td)
             inp = td / "g.fa"
