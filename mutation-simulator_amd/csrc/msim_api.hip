@@ -521,6 +521,38 @@ int msim_set_plan_mode(msim_ctx *p, uint32_t mode) {
     return MSIM_OK;
 }
 
+// A record table and insert pool made on the host become the contig's plan (the host planner's result; msim_dbg_set_records):
+// kept on the host in a host-only context, uploaded otherwise.  APPLY then computes the output offsets on the device.
+static int install_host_table(Ctx *c, Contig *g, std::vector<msim_record> &recs, std::vector<uint8_t> &pool, bool empty) {
+    const auto t0 = std::chrono::steady_clock::now();
+    g->n_rec = recs.size();
+    g->pool_len = pool.size();
+    g->plan_empty = empty;
+    g->all_snp = true;
+    for (const msim_record &r : recs)
+        if (r.type != MSIM_SN) { g->all_snp = false; break; }
+    if (c->host_only) {
+        g->h_recs.swap(recs);
+        g->h_pool.swap(pool);
+        g->planned = true;
+        return MSIM_OK;
+    }
+    int rc = MSIM_OK;
+    if (g->n_rec) {
+        rc = dev_reserve(c, (void **)&g->d_recs, &g->cap_recs, g->n_rec * sizeof(msim_record));
+        if (rc) return rc;
+        MSIM_HIP(c, hipMemcpyAsync(g->d_recs, recs.data(), g->n_rec * sizeof(msim_record), hipMemcpyHostToDevice, c->stream));
+    }
+    rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, g->pool_len + 2 * PAD);
+    if (rc) return rc;
+    if (g->pool_len)
+        MSIM_HIP(c, hipMemcpyAsync(g->d_pool + PAD, pool.data(), g->pool_len, hipMemcpyHostToDevice, c->stream));
+    MSIM_HIP(c, wait_stream(c->stream));
+    c->t.upload_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    g->planned = true;
+    return MSIM_OK;
+}
+
 // One iteration of mutate()'s contig loop up to the rewrite, for contig `g` (id `contig`; chain only: a length-only stand-in,
 // id -1): picks the PLAN engine, keeps the streams chained.
 static int plan_dispatch(Ctx *c, Contig *g, int contig, const msim_range *ranges, int n_ranges) {
@@ -602,32 +634,7 @@ static int plan_dispatch(Ctx *c, Contig *g, int contig, const msim_range *ranges
     c->t.np_words += c->np.words - w_np;
     if (c->chain_only) return MSIM_OK;                     // the streams have advanced: that is all
     c->t.contigs_host++;
-    const auto t0 = std::chrono::steady_clock::now();
-    g->n_rec = hp.recs.size();
-    g->pool_len = hp.pool.size();
-    g->plan_empty = hp.empty;
-    g->all_snp = true;
-    for (const msim_record &r : hp.recs)
-        if (r.type != MSIM_SN) { g->all_snp = false; break; }
-    if (c->host_only) {
-        g->h_recs.swap(hp.recs);
-        g->h_pool.swap(hp.pool);
-        g->planned = true;
-        return MSIM_OK;
-    }
-    if (g->n_rec) {
-        rc = dev_reserve(c, (void **)&g->d_recs, &g->cap_recs, g->n_rec * sizeof(msim_record));
-        if (rc) return rc;
-        MSIM_HIP(c, hipMemcpyAsync(g->d_recs, hp.recs.data(), g->n_rec * sizeof(msim_record), hipMemcpyHostToDevice, c->stream));
-    }
-    rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, g->pool_len + 2 * PAD);
-    if (rc) return rc;
-    if (g->pool_len)
-        MSIM_HIP(c, hipMemcpyAsync(g->d_pool + PAD, hp.pool.data(), g->pool_len, hipMemcpyHostToDevice, c->stream));
-    MSIM_HIP(c, wait_stream(c->stream));
-    c->t.upload_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    g->planned = true;
-    return MSIM_OK;
+    return install_host_table(c, g, hp.recs, hp.pool, hp.empty);
 }
 
 int msim_plan_contig(msim_ctx *p, int contig, const msim_range *ranges, int n_ranges) {
@@ -1196,6 +1203,118 @@ int msim_dbg_fast_plan(msim_ctx *p, uint64_t L, const msim_range *ranges, int n_
         if (!hp.pool.empty() && pool) memcpy(pool, hp.pool.data(), hp.pool.size());
     }
     return MSIM_OK;
+}
+
+// test support (tests/test_apply_ref_host.py, tests/test_gpu_apply_tables.py): is this a table the rewrite kernels are written
+// for (apply.hip: rec_lengths / rec_view)?  What every planner guarantees, checked: known types, records strictly increasing in
+// pos and consuming disjoint input (SN / IN / TLI their own base, DE / DU / IV / TL pos..stop), every span inside the contig,
+// every insert inside the pool, an SNP's aux a LUT column, every output offset and the mutated length in [0, 2^32).
+// A TLI whose span is empty (extra > stop: __link_tls found no TL, plan_host.cpp) is a planner's table and passes.
+// off (optional): the output offset of every record; *delta: mutated length - length.
+static int check_record_table(Ctx *c, uint64_t L, const msim_record *recs, uint64_t n, uint64_t pool_len, std::vector<uint32_t> *off,
+                              long long *delta) {
+    auto bad = [&](uint64_t i, const char *what) { return fail(c, MSIM_ERR_ARG, "record " + std::to_string(i) + ": " + what); };
+    if (n >= (1ull << 31)) return fail(c, MSIM_ERR_ARG, "more than 2^31 records");
+    long long run = 0;                                     // length change of the records so far
+    uint64_t next_free = 0;                                // first input position no earlier record consumed
+    if (off) off->resize((size_t)n);
+    for (uint64_t i = 0; i < n; i++) {
+        const msim_record &r = recs[i];
+        if (r.type < MSIM_SN || r.type > MSIM_TLI) return bad(i, "unknown type");
+        if (r.pos >= L) return bad(i, "position beyond the contig");
+        if (i && r.pos < next_free) return bad(i, "not behind the input its predecessor consumed (positions strictly increasing, no overlap)");
+        const long long len = (long long)r.stop - (long long)r.pos + 1;
+        uint64_t last = r.pos;                             // last input position this record consumes
+        long long d = 0;
+        switch (r.type) {
+            case MSIM_SN:
+                if (r.stop != r.pos) return bad(i, "SNP with stop != pos");
+                if (r.aux > 2) return bad(i, "SNP outcome (aux) outside 0..2");
+                break;
+            case MSIM_IN:
+                if (len < 1) return bad(i, "stop < pos");
+                if (r.extra > pool_len || (uint64_t)len > pool_len - r.extra) return bad(i, "insert outside the insert pool");
+                d = len;
+                break;
+            case MSIM_DE: case MSIM_TL: case MSIM_DU: case MSIM_IV:
+                if (len < 1) return bad(i, "stop < pos");
+                if (r.stop >= L) return bad(i, "stop beyond the contig");
+                last = r.stop;
+                d = (r.type == MSIM_DU) ? len : (r.type == MSIM_IV) ? 0 : -len;
+                break;
+            default:                                       // MSIM_TLI: copy of in[extra .. stop]
+                if (r.extra <= r.stop) {
+                    if (r.stop >= L) return bad(i, "linked span beyond the contig");
+                    d = (long long)r.stop + 1 - (long long)r.extra;
+                }
+                break;
+        }
+        const long long o = (long long)r.pos + run;
+        if (o < 0 || o >= (1ll << 32)) return bad(i, "output offset outside [0, 2^32)");
+        if (off) (*off)[(size_t)i] = (uint32_t)o;
+        run += d;
+        next_free = last + 1;
+    }
+    const long long out_len = (long long)L + run;
+    if (out_len < 0 || out_len >= (1ll << 32)) return fail(c, MSIM_ERR_ARG, "mutated length outside [0, 2^32)");
+    *delta = run;
+    return MSIM_OK;
+}
+
+// Installs the caller's record table and insert pool on an existing contig, as the host planner installs its own
+// (install_host_table); msim_apply_contig then takes the device-scan route.  Nothing reaches a kernel unless
+// check_record_table passes: MSIM_ERR_ARG otherwise, nothing launched, the contig as it was.
+// flags & 1: the output offsets and the length change are computed here and left in d_off / known_delta as the host-chain
+// engines leave theirs (off_ready, delta_known): APPLY skips the device scan, and the contig may go through msim_dbg_apply_batch.
+int msim_dbg_set_records(msim_ctx *p, int contig, const msim_record *recs, uint64_t n_records, const uint8_t *insert_pool,
+                         uint64_t pool_len, uint32_t flags) {
+    CTX_FLUSHED(c, p)
+    if (!c || (n_records && !recs) || (pool_len && !insert_pool) || (flags & ~1u)) return MSIM_ERR_ARG;
+    Contig *g = get_contig(c, contig);
+    if (!g) return MSIM_ERR_ARG;
+    const bool with_offsets = flags & 1u;
+    std::vector<uint32_t> off;
+    long long delta = 0;
+    int rc = check_record_table(c, g->len, recs, n_records, pool_len, with_offsets ? &off : nullptr, &delta);
+    if (rc) return rc;
+    if ((rc = drain(c))) return rc;                        // this contig's buffers may still be read by its last APPLY
+    reset_contig(*g);
+    c->text_kind = 0;
+    g->apply_stream = nullptr;
+    std::vector<msim_record> rv(recs, recs + n_records);
+    std::vector<uint8_t> pv(insert_pool, insert_pool + pool_len);
+    if ((rc = install_host_table(c, g, rv, pv, n_records == 0))) return rc;
+    if (!with_offsets) return MSIM_OK;
+    g->delta_known = true;
+    g->known_delta = delta;
+    if (c->host_only || g->all_snp || !n_records) return MSIM_OK;      // (SNP-only: offset == position, no table)
+    rc = dev_reserve(c, (void **)&g->d_off, &g->cap_off, (size_t)n_records * sizeof(uint32_t));
+    if (rc) return rc;
+    MSIM_HIP(c, hipMemcpyAsync(g->d_off, off.data(), (size_t)n_records * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    MSIM_HIP(c, wait_stream(c->stream));
+    g->off_ready = true;
+    return MSIM_OK;
+}
+
+// What flush_deferred_apply does for a group of host-chain contigs: one tile-index launch for all of them, their rewrites as
+// one launch per kernel variant (apply_batch_device).  Every contig must hold a table installed with offsets (or an SNP-only one).
+int msim_dbg_apply_batch(msim_ctx *p, const int *contigs, int n) {
+    CTX_FLUSHED(c, p)
+    if (!c || !contigs || n < 1) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    std::vector<int> ids(contigs, contigs + n);
+    for (int i = 0; i < n; i++) {
+        Contig *g = get_contig(c, ids[(size_t)i]);
+        if (!g) return MSIM_ERR_ARG;
+        if (!g->planned || g->d_dyn || !(g->all_snp || (g->off_ready && g->delta_known)))
+            return fail(c, MSIM_ERR_ARG, "msim_dbg_apply_batch: a contig without a table installed with its offsets");
+        for (int q = 0; q < i; q++) if (ids[(size_t)q] == ids[(size_t)i]) return fail(c, MSIM_ERR_ARG, "msim_dbg_apply_batch: contig listed twice");
+    }
+    int rc = drain(c);                                     // nothing of these contigs in flight
+    if (rc) return rc;
+    c->text_kind = 0;
+    for (int id : ids) c->contigs[(size_t)id].apply_stream = c->emit_stream;
+    return apply_batch_device(c, ids, true);
 }
 
 // test support (tests/test_ahead_moments.py, CPU tier): the moments the anchored windows are laid out from; needs no context

@@ -447,6 +447,35 @@ class Engine:
         self._check(self.lib.msim_fetch_records(self.h, contig, _ptr(recs), _ptr(pool)))
         return recs, pool
 
+    # test hooks (msim_dbg_*: exported, not part of include/msim.h)
+    def set_records(self, contig: int, recs: np.ndarray, pool: np.ndarray, with_offsets: bool = False):
+        """Install a hand-built record table (RECORD_DTYPE) and insert pool on a contig, as the host planner installs its
+        own.  The library checks the table first and raises MsimError (ERR_ARG) for one the kernels are not written for.
+        ``with_offsets``: the output offsets come with the table (APPLY skips the device scan; needed for apply_batch)."""
+        fn = self.lib.msim_dbg_set_records
+        fn.restype, fn.argtypes = C.c_int, [_VP, C.c_int, _VP, C.c_uint64, _VP, C.c_uint64, C.c_uint32]
+        recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+        pool = np.ascontiguousarray(pool, dtype=np.uint8)
+        self._check(fn(self.h, contig, _ptr(recs), len(recs), _ptr(pool), len(pool), 1 if with_offsets else 0), contig)
+
+    def apply_batch(self, contigs):
+        """APPLY of several contigs whose tables came with their offsets as ONE batch (one tile-index launch, one rewrite
+        launch per kernel variant), as the host-chain engines' deferred groups go out."""
+        fn = self.lib.msim_dbg_apply_batch
+        fn.restype, fn.argtypes = C.c_int, [_VP, _IP, C.c_int]
+        ids = (C.c_int * len(contigs))(*[int(i) for i in contigs])
+        self._check(fn(self.h, ids, len(contigs)))
+
+    def key_error(self, contig: int):
+        """(base, position) of the KeyError the contig's APPLY recorded, or None."""
+        base, pos = C.c_uint8(), C.c_uint64()
+        rc = self.lib.msim_sync(self.h)                    # collects asynchronous APPLYs (their KeyError words)
+        if rc not in (OK, ERR_KEY):
+            self._check(rc, contig)
+        if self.lib.msim_key_error(self.h, contig, C.byref(base), C.byref(pos)) != OK:
+            return None
+        return chr(base.value), pos.value
+
     def render_vcf_device(self, contig: int, seq_name: str, guess: int = 0) -> np.ndarray:
         """VCF record lines of the contig rendered on the device (uint8 array of text).  With a size ``guess`` the
         text comes back in ONE synchronising call when it fits (the library keeps the rendered text, so a second

@@ -21,6 +21,7 @@ from __future__ import annotations
 import numpy as np
 import pytest
 
+import apply_ref
 import fast_twin as ft
 from inputs import random_bases
 from mutation_simulator_amd import _ffi
@@ -232,35 +233,11 @@ def test_distributions_match_the_oracle_on_config3_settings():
 
 # ---------------------------------------------------------------------------------------------- APPLY + text behind fast records
 def _apply_records(bases, recs, pool):
-    """__mutate_sequence (mutator.py:318-426) over a finished record table: SNP outcomes and insert bases come with the
-    records (aux / pool) instead of from the generators.  Plain A/C/G/T input."""
-    ti = {65: 71, 71: 65, 84: 67, 67: 84}
-    tv = {65: b"TC", 71: b"CT", 84: b"GA", 67: b"AG"}
-    comp = {65: 84, 84: 65, 67: 71, 71: 67}
-    out = []
-    at = 0
-    for r in recs:
-        p, s, t = int(r["pos"]), int(r["stop"]), int(r["type"])
-        out.append(bases[at:p])
-        if t == 1:
-            b = int(bases[p])
-            out.append(np.array([ti[b] if r["aux"] == 0 else tv[b][int(r["aux"]) - 1]], dtype=np.uint8))
-            at = p + 1
-        elif t == 2:
-            out.append(pool[int(r["extra"]):int(r["extra"]) + s - p + 1])
-            out.append(bases[p:p + 1])
-            at = p + 1
-        elif t == 3:
-            at = s + 1
-        elif t == 5:
-            out.append(np.array([comp[int(x)] for x in bases[p:s + 1][::-1]], dtype=np.uint8))
-            at = s + 1
-        elif t == 4:
-            out.append(bases[p:s + 1])
-            out.append(bases[p:s + 1])
-            at = s + 1
-    out.append(bases[at:])
-    return np.concatenate(out)
+    """__mutate_sequence (mutator.py:318-426) over a finished record table: tests/apply_ref.py, the restatement that
+    tests/test_apply_ref_host.py holds against the real reference's bytes."""
+    res = apply_ref.apply(bases, recs, pool)
+    assert res.key_error is None
+    return res.seq
 
 
 @pytest.mark.parametrize("kind", ["snp", "svmix", "rmt"])
