@@ -334,6 +334,46 @@ int msim_bgzf_compress(msim_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *ou
 int msim_bgzf_probe(const uint8_t *in, uint64_t n, uint64_t *uncompressed, uint64_t *members);
 int msim_bgzf_inflate(msim_ctx *ctx, const uint8_t *in, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *written,
                       float *device_ms);
+/* ---- VCF replay: the mutated genome again from the reference and the VCF (csrc/vcf_parse.hip) ------------------------------ */
+/* The inverse of the rendering above: every data line of a VCF this library (or Mutation-Simulator 3.0.2, vcf_writer.py:118-126)
+ * wrote becomes one msim_record of the contig its CHROM names -- SN for a line whose INFO is ".", IN for SVTYPE=INS / INS:ME (the
+ * inserted bytes go into the insert pool as they stand), DE for DEL / DEL:ME (length from REF), IV for INV, DU for DUP -- after
+ * REF has been compared with the contig's resident bases and ALT with what the record type produces.  The one base an INS / DEL
+ * line shares between REF and ALT (leading: ALT[0] == REF / ALT == REF[0], preferred; else trailing) stays as the genome has it.
+ *   msim_vcf_load         uploads the whole text once and finds its lines, its header lines ('#...' in front of the first data
+ *                         line) and its groups: the runs of data lines with the same CHROM.  On a host-only context: kept on the host.
+ *   msim_vcf_groups       the groups (at most 65 537 are kept: more runs than a context has contigs cannot all be matched);
+ *                         *n_groups = how many `out` could hold.  name_off: where the group's first line -- its CHROM -- starts
+ *                         in the text.  The caller matches names to contigs.
+ *   msim_vcf_plan_contig  parses group `group` (-1: the contig has no lines) against contig `contig` and leaves the contig PLANNED,
+ *                         exactly as msim_plan_contig's host planner leaves one: msim_apply_contig and everything behind it go on
+ *                         unchanged.  No generator is touched.  MSIM_ERR_VALUE, before anything is installed or launched on the
+ *                         contig, for what the rewrite is not written for: "VCF line <1-based line>: <reason>", the first offending
+ *                         line -- other than 10 fields; POS no number, 0 or beyond the contig; positions not increasing or inside
+ *                         the input an earlier line consumed; REF not the genome's; ALT not what the type produces; multi-allelic,
+ *                         symbolic or breakend alleles; another SVTYPE; FORMAT / sample other than GT / 1; an SNP ALT no
+ *                         transition or transversion gives; an insert byte that is no letter; a mutated length of 2^32 or more
+ *                         (decided from length + inserted + duplicated bytes, deletions not counted).  The context stays usable; the contig
+ *                         is left UNPLANNED after a refusal (either parser), whatever it held before.
+ *   msim_vcf_timing       device time (HIP events) of the load's and of all plans' kernels since msim_vcf_load
+ *   msim_vcf_release      drops the text.
+ * A host-only context runs a sequential parser behind the same calls; it keeps no bases of its own (msim_add_contig reads none
+ * there), so msim_vcf_host_bases hands it the contig's `len` upper-cased bases first (copied; a no-op on a device context).
+ * msim_fetch_records reads either parser's table.                                                                             */
+typedef struct msim_vcf_group {
+    uint64_t name_off;     /* offset of the group's first line in the text                                                     */
+    uint64_t first_line;   /* 0-based index of that line among ALL lines of the text (line number - 1)                         */
+    uint64_t n_lines;
+    uint32_t name_len;     /* bytes of CHROM (256: longer than a contig name this mode takes)                                  */
+    uint32_t rsv;
+} msim_vcf_group;
+int msim_vcf_load(msim_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *n_lines, uint64_t *n_groups);
+int msim_vcf_groups(msim_ctx *ctx, msim_vcf_group *out, uint64_t cap, uint64_t *n_groups);
+int msim_vcf_plan_contig(msim_ctx *ctx, int contig, int64_t group);
+int msim_vcf_host_bases(msim_ctx *ctx, int contig, const uint8_t *bases);
+int msim_vcf_timing(msim_ctx *ctx, double *load_kernel_ms, double *plan_kernel_ms);
+int msim_vcf_release(msim_ctx *ctx);
+
 /* Ingest one FASTA record straight from file text: `body` = the bytes after the header line, n_bases bases
  * in lines of `lenc` bases every `lenb` bytes (the .fai columns; uniform line width is what pyfaidx
  * requires, util.py:77-91).  Line terminators are skipped and a-z upper-cased on the device

@@ -58,6 +58,7 @@ struct Contig {
     // host-only context (device_id -1): the record table stays here
     std::vector<msim_record> h_recs;
     std::vector<uint8_t> h_pool;
+    std::vector<uint8_t> h_in;        // ... and the bases, once msim_vcf_host_bases gave them (the VCF replay's host parser reads them)
 };
 
 constexpr uint64_t PAD = 64;          // slack after every byte buffer so 16-B vector accesses stay in bounds
@@ -67,6 +68,7 @@ struct FastPlan;                      // plan_fast.hip: the counter-based PLAN e
 struct Comm;                          // comm.cpp: RCCL communicator + receive buffers of the gather
 struct Batch;                         // msim_api.hip: state of msim_batch_run
 struct FileIo;                        // file_io.hip: the output channels (thread + stream + pinned ring per output file)
+struct VcfState;                      // vcf_parse.hip: the VCF text of a replay, its line starts and groups
 
 struct Ctx {
     int device = 0;
@@ -84,6 +86,7 @@ struct Ctx {
     void *rw_collect = nullptr;       // apply.hip: where apply_contig_device hands rewrite launches over while apply_batch_device runs
     Batch *batch = nullptr;           // last batch of small contigs (host buffers)
     FileIo *file_io = nullptr;        // file_io.hip (made on first use)
+    VcfState *vcf = nullptr;          // vcf_parse.hip (msim_vcf_load .. msim_vcf_release)
     msim_params params{};
     bool have_params = false;
     std::vector<Contig> contigs;
@@ -147,6 +150,14 @@ double wait_limit_seconds();
 // their chain starts)
 int flush_deferred_apply(Ctx *c, bool only_groups = false);
 bool deferred_apply_holds(const Ctx *c, int contig);
+
+// msim_api.hip: what the VCF replay (vcf_parse.hip) shares with the planners' installation path
+int ctx_drain(Ctx *c);                // everything enqueued has completed, deferred results collected
+void contig_reset(Contig &g);         // forget a contig's plan / apply results (buffers stay allocated)
+int table_install(Ctx *c, Contig *g, std::vector<msim_record> &recs, std::vector<uint8_t> &pool, bool empty);   // install_host_table
+int table_check(Ctx *c, uint64_t L, const msim_record *recs, uint64_t n, uint64_t pool_len, long long *delta, uint64_t *bad_index,
+                const char **bad_what);                                                                       // check_record_table
+void vcf_state_destroy(Ctx *c);       // vcf_parse.hip
 
 // plan_host.cpp
 struct HostPlan {

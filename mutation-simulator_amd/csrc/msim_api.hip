@@ -94,6 +94,8 @@ uint8_t *ctx_lut(Ctx *c) { return dev_of(c)->d_lut; }
 
 // Everything enqueued has completed and its deferred results are collected: sampler flags + exact
 // stream position, APPLY timings + KeyError words.  Returns the sampler's error, if any.
+static int drain(Ctx *c);
+int ctx_drain(Ctx *c) { return drain(c); }
 static int drain(Ctx *c) {
     if (c->host_only) return MSIM_OK;
     TraceRange tr("msim drain (collect deferred results)");
@@ -173,6 +175,8 @@ static void build_lut(uint8_t *lut) {
 }
 
 // forget a contig's plan/apply results; device buffers stay allocated for the next plan of this contig
+static void reset_contig(Contig &g);
+void contig_reset(Contig &g) { reset_contig(g); }
 static void reset_contig(Contig &g) {   // (callers also drop the context's text cache: see text_kind)
     g.planned = g.applied = false;
     g.defer_apply = false;
@@ -332,6 +336,7 @@ void msim_destroy(msim_ctx *p) {
     CtxFull *c = static_cast<CtxFull *>(C(p));
     c->deferred_apply = -1;                                // nobody will ask for their results
     c->n_deferred_more = 0;
+    vcf_state_destroy(c);
     if (c->host_only) { file_io_destroy(c); batch_free(c); delete c; return; }
     static const bool prof = getenv("MSIM_BATCH_PROF") != nullptr;
     auto tp = std::chrono::steady_clock::now();
@@ -1211,9 +1216,14 @@ int msim_dbg_fast_plan(msim_ctx *p, uint64_t L, const msim_range *ranges, int n_
 // every insert inside the pool, an SNP's aux a LUT column, every output offset and the mutated length in [0, 2^32).
 // A TLI whose span is empty (extra > stop: __link_tls found no TL, plan_host.cpp) is a planner's table and passes.
 // off (optional): the output offset of every record; *delta: mutated length - length.
+// bad_index / bad_what (optional): which record was refused and why, for callers that word the refusal themselves (vcf_parse.hip).
 static int check_record_table(Ctx *c, uint64_t L, const msim_record *recs, uint64_t n, uint64_t pool_len, std::vector<uint32_t> *off,
-                              long long *delta) {
-    auto bad = [&](uint64_t i, const char *what) { return fail(c, MSIM_ERR_ARG, "record " + std::to_string(i) + ": " + what); };
+                              long long *delta, uint64_t *bad_index = nullptr, const char **bad_what = nullptr) {
+    auto bad = [&](uint64_t i, const char *what) {
+        if (bad_index) *bad_index = i;
+        if (bad_what) *bad_what = what;
+        return fail(c, MSIM_ERR_ARG, "record " + std::to_string(i) + ": " + what);
+    };
     if (n >= (1ull << 31)) return fail(c, MSIM_ERR_ARG, "more than 2^31 records");
     long long run = 0;                                     // length change of the records so far
     uint64_t next_free = 0;                                // first input position no earlier record consumed
@@ -1418,6 +1428,16 @@ int msim_reset_stats(msim_ctx *p) {
 // threshold anyway), the record tables are concatenated with their positions shifted to the contig's place in ONE
 // super-contig, the GPU runs ONE APPLY over it (records never cross a contig border, so the rewrite kernels need no
 // change), and the host frames the mutated stream per contig and renders the VCF lines (msim_render_vcf).
+namespace msim {
+int table_install(Ctx *c, Contig *g, std::vector<msim_record> &recs, std::vector<uint8_t> &pool, bool empty) {
+    return ::install_host_table(c, g, recs, pool, empty);
+}
+int table_check(Ctx *c, uint64_t L, const msim_record *recs, uint64_t n, uint64_t pool_len, long long *delta, uint64_t *bad_index,
+                const char **bad_what) {
+    return ::check_record_table(c, L, recs, n, pool_len, nullptr, delta, bad_index, bad_what);
+}
+}  // namespace msim
+
 namespace msim {
 
 struct Batch {

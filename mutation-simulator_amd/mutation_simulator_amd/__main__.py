@@ -1,4 +1,4 @@
-"""``mutation-simulator file {args,rmt}`` (reference __main__.py:34-111) on an MI355X."""
+"""``mutation-simulator file {args,rmt,it}`` (reference __main__.py:34-111) on an MI355X, plus ``file vcf truth.vcf``."""
 from __future__ import annotations
 
 import json
@@ -24,6 +24,10 @@ class BgzipUnsupportedError(Exception):
     """--bgzip together with what it does not cover (the IT pass, a sharded run)."""
 
 
+class VcfModeUnsupportedError(Exception):
+    """The vcf mode together with what it does not cover (a sharded run)."""
+
+
 class CompressedInputUnsupportedError(Exception):
     """A gzip-compressed input together with what does not cover it (a sharded run)."""
 
@@ -40,6 +44,8 @@ def initialize(argv=None):
     t0 = timer()
     args = get_args(argv)
     STAGES["parse_args"] = timer() - t0
+    if args.mode == "vcf" and (args.gpus or 1) > 1:
+        exit_with_error(VcfModeUnsupportedError("the vcf mode needs a single-GPU run (--gpus 1)"), args.no_color)
     if args.bgzip and args.mode == "it":
         exit_with_error(BgzipUnsupportedError("--bgzip does not apply to the interchromosomal pass (it)"), args.no_color)
     if args.bgzip and (args.gpus or 1) > 1:
@@ -62,6 +68,8 @@ def initialize(argv=None):
         args.genome_name = args.infile.name
         if fasta.compressed and args.infile.suffix.lower() in (".gz", ".bgz") and args.infile.stem:
             args.genome_name = args.infile.stem
+        if args.mode == "vcf":                         # a replay has no settings and draws nothing
+            return args, fasta, None
         if args.mode == "args":
             sim = SimulationSettings.from_args(args, fasta, args.ignore_warnings)
         elif args.mode == "it":
@@ -91,6 +99,24 @@ def main(argv=None):
     start = timer()
     args, fasta, sim = initialize(argv)
     loaded = timer()
+    if args.mode == "vcf":                             # (--seed / --rng have no effect: no generator is touched)
+        from .vcf_replay import VcfReplay, VcfReplayError
+        try:
+            replay = VcfReplay(args, fasta)
+            try:
+                replay.run()
+            finally:
+                replay.close()
+            fasta.close()
+            if args.bench_json:
+                stats = dict(replay.stats)
+                stats["cli_s"] = {"load_index": round(STAGES.get("load_index", 0.0), 4), "replay": round(timer() - loaded, 4)}
+                args.bench_json.write_text(json.dumps(stats, indent=1) + "\n")
+        except (FastaWriterError, VcfReplayError, MsimError, FileNotFoundError, UnsupportedCompressionFormat, ValueError) as e:
+            exit_with_error(e, args.no_color)
+        if not args.quiet:
+            print_success(f"Mutation-Simulator finished in: {round(timer() - start, 4)}s", args.no_color)
+        return
     if args.seed is not None:
         import numpy
         random.seed(args.seed)

@@ -131,6 +131,12 @@ SYMBOLS = [
     ("msim_bgzf_compress", C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint64, _U64P, C.POINTER(C.c_float)]),
     ("msim_bgzf_probe", C.c_int, [_VP, C.c_uint64, _U64P, _U64P]),
     ("msim_bgzf_inflate", C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint64, _U64P, C.POINTER(C.c_float)]),
+    ("msim_vcf_load", C.c_int, [_VP, _VP, C.c_uint64, _U64P, _U64P]),
+    ("msim_vcf_groups", C.c_int, [_VP, _VP, C.c_uint64, _U64P]),
+    ("msim_vcf_plan_contig", C.c_int, [_VP, C.c_int, C.c_int64]),
+    ("msim_vcf_host_bases", C.c_int, [_VP, C.c_int, _VP]),
+    ("msim_vcf_timing", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("msim_vcf_release", C.c_int, [_VP]),
     ("msim_device_host_cpus", C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     ("msim_batch_fetch_file", C.c_int, [_VP, C.c_int, C.c_uint64, C.c_int, C.c_uint64]),
     ("msim_add_contig_text", C.c_int, [_VP, _VP, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _IP]),
@@ -446,6 +452,46 @@ class Engine:
         pool = np.zeros(n_pool, dtype=np.uint8)
         self._check(self.lib.msim_fetch_records(self.h, contig, _ptr(recs), _ptr(pool)))
         return recs, pool
+
+    # ------------------------------------------------------------------ VCF replay (msim.h: msim_vcf_*)
+    def vcf_load(self, text) -> tuple:
+        """The whole VCF text (bytes-like / uint8 array) into the context, parsed into lines and groups once; returns
+        (lines, groups).  The caller's buffer is free again when this returns."""
+        buf = _as_u8(text)
+        n = int(buf.shape[0])
+        lines, groups = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.msim_vcf_load(self.h, C.c_void_p(buf.ctypes.data) if n else None, n, C.byref(lines), C.byref(groups)))
+        return lines.value, groups.value
+
+    def vcf_groups(self) -> np.ndarray:
+        """The runs of data lines with one CHROM, in file order (``VCF_GROUP_DTYPE``)."""
+        n = C.c_uint64()
+        self._check(self.lib.msim_vcf_groups(self.h, None, 0, C.byref(n)))
+        out = np.zeros(n.value, dtype=VCF_GROUP_DTYPE)
+        if n.value:
+            self._check(self.lib.msim_vcf_groups(self.h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def vcf_plan_contig(self, contig: int, group: int = -1):
+        """Group ``group`` (-1: no lines) becomes the contig's record table and insert pool, validated against its bases;
+        ``ValueError`` ("VCF line N: reason") for a line the rewrite is not written for.  ``apply_contig`` follows."""
+        self._check(self.lib.msim_vcf_plan_contig(self.h, int(contig), int(group)), contig)
+
+    def vcf_host_bases(self, contig: int, bases: np.ndarray):
+        """Host-only contexts keep no bases: the contig's (upper-cased, its whole length) for the host parser.  A no-op on a
+        device context."""
+        bases = np.ascontiguousarray(bases, dtype=np.uint8)
+        assert bases.shape[0] == self.contig_length(contig)
+        self._check(self.lib.msim_vcf_host_bases(self.h, int(contig), _ptr(bases)), contig)
+
+    def vcf_timing(self) -> tuple:
+        """(load, plan) kernel milliseconds since ``vcf_load`` (HIP events)."""
+        a, b = C.c_double(), C.c_double()
+        self._check(self.lib.msim_vcf_timing(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def vcf_release(self):
+        self._check(self.lib.msim_vcf_release(self.h))
 
     # test hooks (msim_dbg_*: exported, not part of include/msim.h)
     def set_records(self, contig: int, recs: np.ndarray, pool: np.ndarray, with_offsets: bool = False):
@@ -782,6 +828,7 @@ def render_vcf(recs: np.ndarray, pool: np.ndarray, bases: np.ndarray, seq_name: 
     return out.tobytes()
 
 
+VCF_GROUP_DTYPE = np.dtype([("name_off", "<u8"), ("first_line", "<u8"), ("n_lines", "<u8"), ("name_len", "<u4"), ("rsv", "<u4")])   # msim_vcf_group
 FASTA_RECORD_DTYPE = np.dtype([("h0", "<u8"), ("h1", "<u8"), ("b0", "<u8"), ("b1", "<u8"), ("n_bases", "<u8"),
                                ("lenc", "<u4"), ("lenb", "<u4"), ("flags", "<u4"), ("rsv", "<u4")])   # msim_fasta_record
 FASTA_HAS_BODY, FASTA_BAD_LINES, FASTA_NONUNIFORM = 1, 2, 4

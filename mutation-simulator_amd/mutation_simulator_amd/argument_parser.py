@@ -1,6 +1,7 @@
 """Command line of ``mutation-simulator`` -- flag-for-flag the reference's ``args`` and ``rmt``
 sub-commands (reference argument_parser.py:31-240) plus a few additions of ours that never change
-a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bgzip``, ``--bench-json``.
+a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bgzip``, ``--bench-json``, and the ``vcf`` sub-command
+(``vcf_replay.py``: the mutated Fasta again from the reference and a run's VCF; it writes ``<outbase>_ms.fa`` only).
 
 The ``it`` sub-command (inter-chromosomal translocations, reference it_mutator.py: a second pass over
 the Fasta) runs through ``ITMutator`` / ``BedpeWriter``.  ``--rng fast`` applies to the mutation pass
@@ -122,6 +123,9 @@ def build_parser() -> ArgumentParser:
 
     p_rmt = sub.add_parser("rmt", help="Use random mutation table instead of arguments")
     p_rmt.add_argument("rmtfile", type=Path, help="Path to the RMT file")
+
+    p_vcf = sub.add_parser("vcf", help="Rebuild the mutated Fasta from the reference Fasta and the VCF of a run")
+    p_vcf.add_argument("vcffile", type=Path, help="Path to the VCF file (text or BGZF-compressed)")
     return parser
 
 

@@ -1,0 +1,154 @@
+"""``mutation-simulator genome.fa vcf truth.vcf``: the mutated Fasta again, from the reference and the VCF of a run.
+
+Every data line replaces REF at POS by ALT; libmsim parses the text into the record tables the mutation pass would have
+planned (``msim_vcf_*``, csrc/vcf_parse.hip), the unchanged rewrite produces the bytes, and ``FastaWriter`` with the
+output channels writes them -- ``--bgzip`` included.  No generator is touched: there is nothing random about a replay.
+
+The whole genome is resident while the VCF is checked, because nothing is rewritten before every line has been accepted.
+"""
+from __future__ import annotations
+
+from pathlib import Path
+
+import numpy as np
+
+from . import _ffi
+from .fasta_io import UnsupportedCompressionFormat
+from .fasta_writer import FastaWriter
+
+MAX_CONTIGS = 65536          # contigs one context holds (csrc/ctx.h)
+
+
+class VcfReplayError(Exception):
+    """The VCF cannot be replayed onto this Fasta (the message names the line)."""
+
+
+def load_vcf_text(path, engine) -> np.ndarray:
+    """The VCF's text as a uint8 array; a BGZF ``.vcf.gz`` (by content) is inflated on the device, plain gzip refused as
+    the Fasta loader refuses it."""
+    path = Path(path)
+    if not path.is_file():
+        raise FileNotFoundError(f"Cannot read VCF from file {path}")
+    raw = np.fromfile(path, dtype=np.uint8)
+    if raw.shape[0] >= 2 and raw[0] == 0x1F and raw[1] == 0x8B:
+        try:
+            total, _ = _ffi.bgzf_probe(raw)
+        except _ffi.MsimError as e:
+            if getattr(e, "code", None) != _ffi.ERR_VALUE:
+                raise
+            raise UnsupportedCompressionFormat(
+                f"Compressed VCF is only supported in BGZF format. Use the samtools bgzip utility (instead of gzip) to "
+                f"compress {path} ({str(e).split(': ', 1)[-1]})") from None
+        if total == 0:
+            return np.zeros(0, np.uint8)
+        try:
+            return engine.bgzf_inflate(raw, out=np.empty(total, dtype=np.uint8))
+        except _ffi.MsimError as e:
+            if getattr(e, "code", None) != _ffi.ERR_VALUE:
+                raise
+            raise VcfReplayError(f"Compressed VCF {path} is damaged: {str(e).split(': ', 1)[-1]}") from None
+    return raw
+
+
+def plan_all(engine, text: np.ndarray, names, contig_ids) -> None:
+    """Load ``text`` and plan every contig (``contig_ids[i]`` is the context's id of the contig called ``names[i]``) from the
+    lines that name it, in FILE order, so that the first offending line of the file is the one reported (ValueError /
+    VcfReplayError, "VCF line N: ...").  Contigs without lines get an empty table.  Nothing has been rewritten when this raises."""
+    engine.vcf_load(text)
+    groups = engine.vcf_groups()
+    by_name = {}
+    for i, name in enumerate(names):
+        by_name.setdefault(name.encode("utf-8", "replace"), i)
+    seen = set()
+    for k in range(len(groups)):
+        off, nlen, line = int(groups["name_off"][k]), int(groups["name_len"][k]), int(groups["first_line"][k]) + 1
+        chrom = text[off:off + nlen].tobytes()
+        i = by_name.get(chrom) if nlen <= 255 else None
+        if i is None:
+            raise VcfReplayError(f"VCF line {line}: CHROM {chrom[:64].decode('utf-8', 'replace')!r} is no contig of the Fasta")
+        if i in seen:
+            raise VcfReplayError(f"VCF line {line}: the lines of contig {names[i]!r} are not contiguous in the file")
+        seen.add(i)
+        try:
+            engine.vcf_plan_contig(contig_ids[i], k)
+        except ValueError as e:
+            raise VcfReplayError(str(e)) from None
+    for i, cid in enumerate(contig_ids):
+        if i not in seen:
+            engine.vcf_plan_contig(cid, -1)
+
+
+class VcfReplay:
+    """Runs the replay of one genome on the GPU and writes ``*_ms.fa``."""
+
+    def __init__(self, args, fasta, engine=None):
+        self._args = args
+        self._fasta = fasta
+        self._bgzip = bool(getattr(args, "bgzip", False))
+        self._device = getattr(args, "device", 0) or 0
+        self._engine = engine
+        self._own_engine = engine is None
+        self._writer = None
+        self.stats: dict = {}
+
+    def run(self):
+        fa = self._fasta
+        if len(fa) > MAX_CONTIGS:
+            raise _ffi.MsimUnsupported(f"vcf mode keeps the genome resident: more than {MAX_CONTIGS} contigs")
+        if self._engine is None:
+            self._engine = _ffi.Engine(self._device)
+        eng = self._engine
+        text = load_vcf_text(self._args.vcffile, eng)
+        recs = [fa[i] for i in range(len(fa))]
+        cids = []
+        for rec in recs:
+            if getattr(rec, "uniform", False):         # file text -> HBM: strip + upper-case on the device
+                cids.append(eng.add_contig_text(rec.body, len(rec), rec.lenc, rec.lenb))
+            else:
+                cids.append(eng.add_contig(rec.bases))
+        plan_all(eng, text, [r.name for r in recs], cids)
+        # every line is accepted: rewrite and write, contig by contig
+        self._writer = FastaWriter(self._args.outfasta, bgzip=self._bgzip, device=self._device)
+        self._writer.attach(eng)
+        for rec, cid in zip(recs, cids):
+            bpl = fa.faidx.index[rec.name].lenc
+            self._writer.set_bpl(bpl)
+            self._writer.write_header(rec.long_name)
+            eng.apply_contig(cid)
+            if bpl > 0:
+                out_len = eng.result_sizes(cid)[0]
+                try:
+                    fd, pos = self._writer.native_span()
+                    n_done = eng.fetch_sequence_framed_to_file(cid, bpl, fd, pos)
+                    self._writer.commit_native(pos, n_done, out_len)
+                except _ffi.MsimUnsupported:           # no regular file: through a mapping made here
+                    region = self._writer.map_region(out_len + out_len // bpl)
+                    try:
+                        eng.fetch_sequence_framed_into(cid, bpl, region.view)
+                    finally:
+                        self._writer.commit_region(region, out_len)
+            else:
+                self._writer.write_array(eng.fetch_sequence(cid))
+            eng.release_result(cid)
+        eng.file_wait()
+        load_ms, plan_ms = eng.vcf_timing()
+        self.stats = {"vcf_bytes": int(text.shape[0]), "vcf_load_kernel_ms": load_ms, "vcf_plan_kernel_ms": plan_ms}
+        eng.vcf_release()
+
+    def close(self):
+        pending = None
+        eng = self._engine
+        if getattr(eng, "h", None):
+            try:
+                eng.file_wait()
+            except _ffi.MsimError as e:
+                pending = e
+        try:
+            if self._writer is not None:
+                self._writer.close()                   # (BGZF: tail and EOF marker go out through the engine)
+        finally:
+            self._engine = None
+            if eng is not None and self._own_engine:
+                eng.close()
+        if pending is not None:
+            raise pending
