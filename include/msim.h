@@ -276,6 +276,25 @@ int msim_render_vcf(const msim_record *recs, uint64_t n_records, const uint8_t *
                     const uint8_t *bases, uint64_t len, const char *seq_name,
                     char *out, uint64_t cap, uint64_t *needed);
 
+/* ---- liftover chain: the record table as a coordinate map (UCSC chain format; liftOver, CrossMap, bcftools consensus -c) ---- */
+/* One chain per contig, reference = target, mutated = query, both on the + strand:
+ *   chain <score> <tName> <tSize> + <tStart> <tEnd> <qName> <qSize> + <qStart> <qEnd> <id>\n
+ *   <size>\t<dt>\t<dq>\n   per aligned block but the last,   <size>\n   for the last one,   \n
+ * SNPs are substitutions inside blocks.  Every other record is one gap in the walk of __mutate_sequence (mutator.py:318-426):
+ * IN / TLI insert dq bases in front of base pos; DE / TL skip dt = stop - pos + 1 reference bases; IV leaves its span unmapped
+ * on both sides (dt = dq: one chain has one strand); DU keeps its first copy aligned and inserts the second behind it.  Gaps
+ * with no aligned base between them share one line (dt / dq summed); in front of the first block they become tStart / qStart,
+ * behind the last one they shorten tEnd / qEnd.  score = the aligned bases, tSize = len, qSize = the mutated length.  A contig
+ * without an aligned base (length 0, wholly deleted) has no chain: *needed = 0.
+ * Stateless host helper, the twin of msim_render_vcf (reads no bases): out == NULL reports the size, cap < *needed is
+ * MSIM_ERR_ARG.                                                                                                          */
+int msim_render_chain(const msim_record *recs, uint64_t n_records, uint64_t len, const char *t_name,
+                      const char *q_name, uint64_t id, char *out, uint64_t cap, uint64_t *needed);
+/* The same bytes rendered by HIP kernels from the record table in HBM.  The contig must be planned (msim_plan_contig,
+ * msim_vcf_plan_contig); applied it need not be.  Two-call protocol of msim_render_vcf_device.                           */
+int msim_render_chain_device(msim_ctx *ctx, int contig, const char *t_name, const char *q_name,
+                             uint64_t id, char *out, uint64_t cap, uint64_t *needed);
+
 /* ---- text on the device ------------------------------------------------ */
 /* The same record lines as msim_render_vcf, rendered by HIP kernels from the record table, insert pool and
  * input contig already in HBM (mutator.py:334-421 + vcf_writer.py:44-52,118-126).  Two-call protocol:

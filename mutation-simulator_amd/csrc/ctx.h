@@ -110,8 +110,11 @@ struct Ctx {
     uint8_t *d_text = nullptr;
     size_t cap_text = 0;
     uint64_t text_len = 0;
-    int text_contig = -1, text_kind = 0;  // what d_text currently holds: 1 VCF lines, 2 framed FASTA body
+    int text_contig = -1, text_kind = 0;  // what d_text currently holds: 1 VCF lines, 2 framed FASTA body, 3 liftover chain
     uint32_t text_bpl = 0;
+    uint64_t text_chain_id = 0;           // kind 3: the chain id and the names (tName '\n' qName) the text was rendered with
+    std::string text_chain_names;
+    double chain_kernel_ms = -1.0;        // >= 0: msim_dbg_chain_ms asked for the chain kernels' time; that of the last rendering
     uint8_t *d_text_scratch = nullptr;
     size_t cap_text_scratch = 0;
 };
@@ -297,6 +300,9 @@ int fast_plan_emulated(Ctx *c, uint64_t L, const msim_range *ranges, int n_range
 // text_gpu.hip
 // (buf / cap: render there instead of into the context's text buffer -- an output channel's; text_len is then left alone)
 int vcf_render_device(Ctx *c, Contig &g, const char *seq_name, uint64_t *bytes, uint8_t **buf = nullptr, size_t *cap = nullptr);
+// liftover chain of one planned contig into c->d_text / c->text_len (kernel_ms: optional, the kernels' time by HIP events)
+int chain_render_device(Ctx *c, Contig &g, const char *t_name, const char *q_name, uint64_t id, double *kernel_ms = nullptr);
+uint32_t chain_tile();                 // records / gaps of a workgroup of the chain kernels (CH_TILE), for the tests' edge cases
 int fasta_frame_device(Ctx *c, Contig &g, uint32_t bpl, uint64_t *bytes, uint8_t **buf = nullptr, size_t *cap = nullptr);
 int splice_device(Ctx *c, const Contig &a, const Contig *b, const uint32_t *seg_out, const uint32_t *seg_src, uint32_t n_seg,
                   Contig &dst);
@@ -323,6 +329,10 @@ void device_host_cpus(int device, char *buf, size_t cap);   // cpulist of the de
 // render.cpp
 uint64_t render_vcf_unchecked(const msim_record *recs, uint64_t n_records, const uint8_t *insert_pool, const uint8_t *bases,
                               uint64_t len, const char *seq_name, char *out);
+// "chain <score> <tName> <tSize> + <tStart> <tEnd> <qName> <qSize> + <qStart> <qEnd> <id>\n" at out + *n (out == nullptr:
+// counted only); score = the aligned bases = length - sum of dt.  Shared by msim_render_chain and chain_render_device.
+void chain_header(char *out, uint64_t *n, uint64_t L, uint64_t sum_dt, uint64_t sum_dq, uint64_t t_start, uint64_t q_start,
+                  uint64_t t_trail, uint64_t q_trail, const char *t_name, const char *q_name, uint64_t id);
 
 // comm.cpp
 void comm_destroy(Ctx *c);

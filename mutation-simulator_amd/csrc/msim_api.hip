@@ -898,6 +898,45 @@ int msim_render_vcf_device(msim_ctx *p, int contig, const char *seq_name, char *
     return text_copy_out(c, reinterpret_cast<uint8_t *>(out), cap, needed);
 }
 
+// The contig's liftover chain, rendered from its record table (text_gpu.hip: chain_render_device).  Planned is enough: the
+// table is the whole input.  Names are part of the text, so a copy call whose names or id differ renders again.
+int msim_render_chain_device(msim_ctx *p, int contig, const char *t_name, const char *q_name, uint64_t id, char *out, uint64_t cap,
+                             uint64_t *needed) {
+    CTX_FLUSHED(c, p)
+    if (!c || !t_name || !q_name || !needed) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    TraceRange tr("msim text: liftover chain");
+    Contig *g = get_contig(c, contig);
+    if (!g) return MSIM_ERR_ARG;
+    if (!g->planned) return fail(c, MSIM_ERR_ARG, "contig has not been planned");
+    const std::string names = std::string(t_name) + '\n' + q_name;
+    if (!(out && c->text_kind == 3 && c->text_contig == contig && c->text_chain_id == id && c->text_chain_names == names)) {
+        int rc = drain(c);                                               // the table's last bytes come from the emit stream
+        if (rc) return rc;
+        c->text_kind = 0;
+        rc = chain_render_device(c, *g, t_name, q_name, id, c->chain_kernel_ms >= 0 ? &c->chain_kernel_ms : nullptr);
+        if (rc) return rc;
+        c->text_kind = 3;
+        c->text_contig = contig;
+        c->text_chain_id = id;
+        c->text_chain_names = names;
+    }
+    return text_copy_out(c, reinterpret_cast<uint8_t *>(out), cap, needed);
+}
+
+// test / measurement support: the chain kernels' device time (HIP events around every run of launches) of the last
+// msim_render_chain_device rendering; the first call switches the measurement on (*ms = 0 then).
+int msim_dbg_chain_ms(msim_ctx *p, double *ms) {
+    CTX_FLUSHED(c, p)
+    if (!c || !ms) return MSIM_ERR_ARG;
+    if (c->chain_kernel_ms < 0) c->chain_kernel_ms = 0;
+    *ms = c->chain_kernel_ms;
+    return MSIM_OK;
+}
+
+// test support: the chain kernels' tile (records / gaps of a workgroup), where their edge cases lie
+uint32_t msim_dbg_chain_tile(void) { return chain_tile(); }
+
 int msim_fetch_sequence_framed(msim_ctx *p, int contig, uint32_t bpl, uint8_t *out, uint64_t cap, uint64_t *needed) {
     CTX_FLUSHED(c, p)
     if (!c || !needed || bpl == 0) return MSIM_ERR_ARG;

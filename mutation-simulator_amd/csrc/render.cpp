@@ -7,7 +7,7 @@
 #include <cstring>
 #include <string>
 
-#include "../../include/msim.h"
+#include "ctx.h"
 
 namespace {
 
@@ -143,6 +143,72 @@ uint64_t render(const msim_record *recs, uint64_t n, const uint8_t *pool, const 
     return s.n;
 }
 
+// ---- liftover chain (UCSC chain format): the record table as a coordinate map, reference = target, mutated = query ----------
+// Every record other than an SNP is one gap (t0: where alignment stops, t1: where it resumes, dt / dq: reference / mutated
+// bases skipped), read off the rewrite's walk (mutator.py:318-426):
+//   IN   the insert lands in front of base pos                      t0 = t1 = pos            dq = insert length
+//   TLI  like IN, the linked span's copy                            t0 = t1 = pos            dq = stop - extra + 1 (0: no gap)
+//   DE / TL  pos..stop are skipped                                  t0 = pos, t1 = stop + 1  dt = span
+//   IV   the span comes out reverse-complemented: one chain has one strand, so it is unmapped on both sides
+//                                                                   t0 = pos, t1 = stop + 1  dt = dq = span
+//   DU   the first copy stays aligned, the second one is inserted   t0 = t1 = stop + 1       dq = span
+// The aligned block between two gaps has t0_j - t1_i bases; a block of none is not written, the gaps around it merge (their
+// dt / dq add up), in front of the first block they become tStart / qStart, behind the last one they shorten tEnd / qEnd.
+struct ChainGap { uint64_t t0, t1, dt, dq; };
+
+inline bool chain_gap(const msim_record &r, ChainGap &g) {
+    const uint64_t pos = r.pos, stop = r.stop, span = stop - pos + 1;
+    switch (r.type) {
+        case MSIM_IN:  g = {pos, pos, 0, span}; break;
+        case MSIM_TLI: g = {pos, pos, 0, r.extra <= r.stop ? stop - r.extra + 1 : 0}; break;
+        case MSIM_DE:
+        case MSIM_TL:  g = {pos, stop + 1, span, 0}; break;
+        case MSIM_IV:  g = {pos, stop + 1, span, span}; break;
+        case MSIM_DU:  g = {stop + 1, stop + 1, 0, span}; break;
+        default: return false;
+    }
+    return (g.dt | g.dq) != 0;
+}
+
+struct ChainEnds { uint64_t t_start = 0, q_start = 0, t_trail = 0, q_trail = 0, sum_dt = 0, sum_dq = 0; bool any = false; };
+
+// the lines of every block but the last, then "<size>\n\n" of the last one; nothing when no base is aligned
+ChainEnds chain_body(const msim_record *recs, uint64_t n, uint64_t L, Sink &s) {
+    ChainEnds e;
+    uint64_t prev_t1 = 0, block = 0, dt = 0, dq = 0;       // block: the last block seen; dt / dq: the gaps behind it so far
+    auto step = [&](uint64_t size) {                        // a block of `size` bases follows the gaps gathered so far
+        if (!size) return;
+        if (e.any) { s.num(block); s.put('\t'); s.num(dt); s.put('\t'); s.num(dq); s.put('\n'); }
+        else { e.t_start = dt; e.q_start = dq; }
+        e.any = true;
+        block = size; dt = dq = 0;
+    };
+    for (uint64_t i = 0; i < n; i++) {
+        ChainGap g;
+        if (!chain_gap(recs[i], g)) continue;
+        step(g.t0 - prev_t1);
+        dt += g.dt; dq += g.dq;
+        e.sum_dt += g.dt; e.sum_dq += g.dq;
+        prev_t1 = g.t1;
+    }
+    step(L - prev_t1);
+    if (e.any) { s.num(block); s.lit("\n\n"); e.t_trail = dt; e.q_trail = dq; }
+    return e;
+}
+
+uint64_t render_chain(const msim_record *recs, uint64_t n, uint64_t L, const char *t_name, const char *q_name, uint64_t id,
+                      char *out) {
+    Sink count(nullptr);
+    const ChainEnds e = chain_body(recs, n, L, count);
+    if (!e.any) return 0;
+    Sink s(out);
+    msim::chain_header(s.p, &s.n, L, e.sum_dt, e.sum_dq, e.t_start, e.q_start, e.t_trail, e.q_trail, t_name, q_name, id);
+    if (!out) return s.n + count.n;
+    Sink body(out + s.n);
+    chain_body(recs, n, L, body);
+    return s.n + body.n;
+}
+
 }  // namespace
 
 // single pass, no size check: the caller guarantees room (msim_batch_run sizes its buffer by an upper bound)
@@ -152,6 +218,31 @@ uint64_t render_vcf_unchecked(const msim_record *recs, uint64_t n_records, const
     return render(recs, n_records, insert_pool, bases, len, seq_name, out);
 }
 }  // namespace msim
+
+namespace msim {
+void chain_header(char *out, uint64_t *n, uint64_t L, uint64_t sum_dt, uint64_t sum_dq, uint64_t t_start, uint64_t q_start,
+                  uint64_t t_trail, uint64_t q_trail, const char *t_name, const char *q_name, uint64_t id) {
+    const uint64_t q_size = L + sum_dq - sum_dt;
+    Sink s(out);
+    s.n = *n;
+    s.lit("chain "); s.num(L - sum_dt); s.put(' ');
+    s.lit(t_name); s.put(' '); s.num(L); s.lit(" + "); s.num(t_start); s.put(' '); s.num(L - t_trail); s.put(' ');
+    s.lit(q_name); s.put(' '); s.num(q_size); s.lit(" + "); s.num(q_start); s.put(' '); s.num(q_size - q_trail); s.put(' ');
+    s.num(id); s.put('\n');
+    *n = s.n;
+}
+}  // namespace msim
+
+extern "C" int msim_render_chain(const msim_record *recs, uint64_t n_records, uint64_t len, const char *t_name,
+                                 const char *q_name, uint64_t id, char *out, uint64_t cap, uint64_t *needed) {
+    if ((n_records && !recs) || !t_name || !q_name || !needed) return MSIM_ERR_ARG;
+    const uint64_t want = render_chain(recs, n_records, len, t_name, q_name, id, nullptr);
+    *needed = want;
+    if (!out) return MSIM_OK;
+    if (cap < want) return MSIM_ERR_ARG;
+    render_chain(recs, n_records, len, t_name, q_name, id, out);
+    return MSIM_OK;
+}
 
 extern "C" int msim_render_vcf(const msim_record *recs, uint64_t n_records, const uint8_t *insert_pool,
                                const uint8_t *bases, uint64_t len, const char *seq_name, char *out,

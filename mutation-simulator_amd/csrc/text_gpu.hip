@@ -26,6 +26,7 @@
 // Byte/integer work, HBM-bound; no MFMA.
 #include <cstdlib>
 #include <cstring>
+#include <string>
 
 #include "ctx.h"
 
@@ -734,6 +735,171 @@ __global__ __launch_bounds__(TX_THREADS) void k_len_offsets(const uint32_t *__re
     }
 }
 
+// ---- liftover chain (render.cpp: the gap table and the merge rule; msim_render_chain is the host twin) -------------------------
+// The record table as a UCSC chain: every record other than an SNP is one gap (t0, t1, dt, dq), consecutive gaps with no
+// aligned base between them share a line.  Five small kernels around the scans above:
+//   k_chain_count / k_chain_compact  a lane per record classifies it; ballot + popcount give every gap its place among the
+//                                    gaps (striped: lane l of a workgroup takes records l, l + 256, ... of its tile, so a
+//                                    ballot's bits are consecutive records) -> uint4 (t0, t1, dt, dq) per gap
+//   k_chain_tiles / k_chain_heads    a gap is the HEAD of a line if the block in front of it has a base (t0 > t1 of the gap
+//                                    before).  Exclusive 64-bit prefix sums of dt and dq and a count of the heads, over the
+//                                    gaps: head number j notes the block's size and the two prefixes at ITS position, so
+//                                    line j's dt / dq are prefix[j + 1] - prefix[j] -- a difference, not a walk over the
+//                                    merged run, however long that is
+//   k_chain_lines<false / true>      a lane per line: its length (three numbers), then -- behind k_len_* / k_scan_u64 -- its text
+// The header line and the last block's "<size>\n\n" need the totals: the host writes them (chain_render_device).
+constexpr int CH_ITEMS = 4;
+constexpr int CH_TILE = TX_THREADS * CH_ITEMS;                           // records / gaps of a workgroup: the scans' tile
+
+__device__ __forceinline__ bool chain_gap(const msim_record &r, uint4 &g) {
+    const uint32_t pos = r.pos, stop = r.stop, span = stop - pos + 1;
+    switch (r.type) {
+        case MSIM_IN:  g = uint4{pos, pos, 0u, span}; break;
+        case MSIM_TLI: g = uint4{pos, pos, 0u, r.extra <= stop ? stop - r.extra + 1 : 0u}; break;
+        case MSIM_DE:
+        case MSIM_TL:  g = uint4{pos, stop + 1, span, 0u}; break;
+        case MSIM_IV:  g = uint4{pos, stop + 1, span, span}; break;
+        case MSIM_DU:  g = uint4{stop + 1, stop + 1, 0u, span}; break;
+        default: g = uint4{0u, 0u, 0u, 0u}; break;
+    }
+    return (g.z | g.w) != 0;
+}
+
+__global__ __launch_bounds__(TX_THREADS) void k_chain_count(const msim_record *__restrict__ recs, uint32_t n,
+                                                            unsigned long long *__restrict__ sums) {
+    __shared__ uint32_t red[TX_WAVES];
+    const uint32_t base = blockIdx.x * CH_TILE + threadIdx.x;
+    uint32_t cnt = 0;
+#pragma unroll
+    for (int q = 0; q < CH_ITEMS; q++) {
+        const uint32_t i = base + q * TX_THREADS;
+        uint4 g;
+        const bool s = i < n && chain_gap(recs[i], g);
+        cnt += (uint32_t)__popcll(__ballot(s));
+    }
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) sums[blockIdx.x] = (unsigned long long)red[0] + red[1] + red[2] + red[3];
+}
+
+// tile_off: the exclusive scan of k_chain_count's sums
+__global__ __launch_bounds__(TX_THREADS) void k_chain_compact(const msim_record *__restrict__ recs, uint32_t n,
+                                                              const unsigned long long *__restrict__ tile_off,
+                                                              uint4 *__restrict__ gaps) {
+    __shared__ uint32_t cnt[CH_ITEMS * TX_WAVES];                        // gaps per (row q, wave): record order
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t base = blockIdx.x * CH_TILE + threadIdx.x;
+    uint4 g[CH_ITEMS];
+    unsigned long long b[CH_ITEMS];
+#pragma unroll
+    for (int q = 0; q < CH_ITEMS; q++) {
+        const uint32_t i = base + q * TX_THREADS;
+        const bool s = i < n && chain_gap(recs[i], g[q]);
+        b[q] = __ballot(s);
+        if (lane == 0) cnt[q * TX_WAVES + wave] = (uint32_t)__popcll(b[q]);
+    }
+    __syncthreads();
+    unsigned long long run = tile_off[blockIdx.x];
+    const unsigned long long below = (1ull << lane) - 1;
+#pragma unroll
+    for (int q = 0; q < CH_ITEMS; q++) {
+#pragma unroll
+        for (int w = 0; w < TX_WAVES; w++) {
+            if ((uint32_t)w == wave && ((b[q] >> lane) & 1)) gaps[run + (uint32_t)__popcll(b[q] & below)] = g[q];
+            run += cnt[q * TX_WAVES + w];
+        }
+    }
+}
+
+// A thread's CH_ITEMS consecutive gaps: its sums of dt and dq, its heads (bit q of `heads`: gap i0 + q opens a line) and,
+// per gap, the size of the block in front of it.
+struct ChainLocal { unsigned long long dt, dq; uint32_t heads, n_heads; uint4 g[CH_ITEMS]; uint32_t size[CH_ITEMS]; };
+
+__device__ __forceinline__ ChainLocal chain_local(const uint4 *__restrict__ gaps, uint32_t m, uint32_t i0) {
+    ChainLocal c;
+    c.dt = c.dq = 0; c.heads = c.n_heads = 0;
+    uint32_t prev_t1 = (i0 > 0 && i0 <= m) ? gaps[i0 - 1].y : 0u;         // (in front of the first gap: the contig's start)
+#pragma unroll
+    for (int q = 0; q < CH_ITEMS; q++) {
+        c.g[q] = uint4{0u, 0u, 0u, 0u};
+        c.size[q] = 0;
+        if (i0 + q < m) {
+            c.g[q] = gaps[i0 + q];
+            c.size[q] = c.g[q].x - prev_t1;                              // >= 0: the table rule (check_record_table)
+            if (c.size[q]) { c.heads |= 1u << q; c.n_heads++; }
+            c.dt += c.g[q].z; c.dq += c.g[q].w;
+            prev_t1 = c.g[q].y;
+        }
+    }
+    return c;
+}
+
+// per tile of gaps: sum of dt, sum of dq, heads (three arrays of `stride` entries, scanned by k_scan_u64 afterwards)
+__global__ __launch_bounds__(TX_THREADS) void k_chain_tiles(const uint4 *__restrict__ gaps, uint32_t m, uint32_t stride,
+                                                            unsigned long long *__restrict__ tiles) {
+    __shared__ unsigned long long red[3][TX_WAVES];
+    const ChainLocal c = chain_local(gaps, m, blockIdx.x * CH_TILE + threadIdx.x * CH_ITEMS);
+    unsigned long long a = c.dt, b = c.dq, h = c.n_heads;
+    for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o, 64); b += __shfl_down(b, o, 64); h += __shfl_down(h, o, 64); }
+    if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = a; red[1][threadIdx.x >> 6] = b; red[2][threadIdx.x >> 6] = h; }
+    __syncthreads();
+    if (threadIdx.x < 3) tiles[(size_t)threadIdx.x * stride + blockIdx.x] = red[threadIdx.x][0] + red[threadIdx.x][1] +
+                                                                           red[threadIdx.x][2] + red[threadIdx.x][3];
+}
+
+// tiles: the three scanned arrays.  Head number j -> hsize[j], hp_dt[j], hp_dq[j]; the last gap closes the tables
+// (hp_*[H] = the totals) and leaves tot = {H, t1 of the last gap, sum dt, sum dq}.
+__global__ __launch_bounds__(TX_THREADS) void k_chain_heads(const uint4 *__restrict__ gaps, uint32_t m, uint32_t stride,
+                                                            const unsigned long long *__restrict__ tiles,
+                                                            uint32_t *__restrict__ hsize, unsigned long long *__restrict__ hp_dt,
+                                                            unsigned long long *__restrict__ hp_dq,
+                                                            unsigned long long *__restrict__ tot) {
+    __shared__ unsigned long long wsum[3][TX_WAVES];
+    const uint32_t i0 = blockIdx.x * CH_TILE + threadIdx.x * CH_ITEMS;
+    const ChainLocal c = chain_local(gaps, m, i0);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long a = c.dt, b = c.dq, h = c.n_heads;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long ta = __shfl_up(a, o, 64), tb = __shfl_up(b, o, 64), th = __shfl_up(h, o, 64);
+        if (lane >= o) { a += ta; b += tb; h += th; }
+    }
+    if (lane == 63) { wsum[0][wave] = a; wsum[1][wave] = b; wsum[2][wave] = h; }
+    __syncthreads();
+    unsigned long long pa = tiles[blockIdx.x] + a - c.dt, pb = tiles[(size_t)stride + blockIdx.x] + b - c.dq,
+                       ph = tiles[2 * (size_t)stride + blockIdx.x] + h - c.n_heads;
+    for (int w = 0; w < wave; w++) { pa += wsum[0][w]; pb += wsum[1][w]; ph += wsum[2][w]; }
+#pragma unroll
+    for (int q = 0; q < CH_ITEMS; q++) {
+        if (i0 + q >= m) break;
+        if ((c.heads >> q) & 1) { hsize[ph] = c.size[q]; hp_dt[ph] = pa; hp_dq[ph] = pb; ph++; }
+        pa += c.g[q].z; pb += c.g[q].w;
+        if (i0 + q == m - 1) {
+            hp_dt[ph] = pa; hp_dq[ph] = pb;
+            tot[0] = ph; tot[1] = c.g[q].y; tot[2] = pa; tot[3] = pb;
+        }
+    }
+}
+
+// line j: "<hsize[j]>\t<hp_dt[j + 1] - hp_dt[j]>\t<hp_dq[j + 1] - hp_dq[j]>\n"
+template <bool WRITE>
+__global__ __launch_bounds__(TX_THREADS) void k_chain_lines(const uint32_t *__restrict__ hsize,
+                                                            const unsigned long long *__restrict__ hp_dt,
+                                                            const unsigned long long *__restrict__ hp_dq, uint32_t n_lines,
+                                                            uint32_t *__restrict__ len, const unsigned long long *__restrict__ off,
+                                                            char *__restrict__ text) {
+    const uint32_t j = blockIdx.x * TX_THREADS + threadIdx.x;
+    if (j >= n_lines) return;
+    const unsigned long long size = hsize[j], dt = hp_dt[j + 1] - hp_dt[j], dq = hp_dq[j + 1] - hp_dq[j];
+    if (!WRITE) {
+        len[j] = (uint32_t)(ndigits(size) + ndigits(dt) + ndigits(dq) + 3);
+    } else {
+        DSink s;
+        s.text = text; s.n = off[j];
+        s.num(size); s.put('\t'); s.num(dt); s.put('\t'); s.num(dq); s.put('\n');
+    }
+}
+
 // ---- FASTA egress: '\n' after every bpl bases (no newline after a partial last line)
 __global__ __launch_bounds__(TX_THREADS) void k_frame(const uint8_t *__restrict__ seq, unsigned long long L,
                                                       uint32_t bpl, unsigned long long text_len,
@@ -928,6 +1094,157 @@ int vcf_render_device(Ctx *c, Contig &g, const char *seq_name, uint64_t *bytes, 
     }
     if (own) c->text_len = total;
     *bytes = total;
+    return MSIM_OK;
+}
+
+// msim_render_chain's bytes for one planned contig into the context's text buffer (render.cpp has the format).
+uint32_t chain_tile() { return CH_TILE; }
+
+int chain_render_device(Ctx *c, Contig &g, const char *t_name, const char *q_name, uint64_t id, double *kernel_ms) {
+    const uint32_t n = (uint32_t)g.n_rec;
+    const uint64_t L = g.len;
+    hipStream_t st = c->stream;
+    c->text_len = 0;
+    // kernel time on request (msim_dbg_chain_ms): an event pair around every run of launches between two host waits
+    // (four runs: gaps | heads and prefixes | line lengths | text.  A fifth one has to make room here: it is an error, not a
+    // run left out of the sum.)
+    constexpr int CH_MARKS = 2 * 4;
+    hipEvent_t ev[CH_MARKS] = {};
+    int n_ev = 0;
+    auto mark = [&]() -> hipError_t {
+        if (!kernel_ms) return hipSuccess;
+        if (n_ev >= CH_MARKS) return hipErrorInvalidValue;
+        hipError_t e = hipEventCreate(&ev[n_ev]);
+        if (e != hipSuccess) return e;
+        return hipEventRecord(ev[n_ev++], st);
+    };
+    auto drop_events = [&]() { for (int q = 0; q < n_ev; q++) (void)hipEventDestroy(ev[q]); n_ev = 0; };
+    struct Guard { decltype(drop_events) &f; ~Guard() { f(); } } guard{drop_events};
+    auto sum_events = [&]() -> hipError_t {                              // (behind a host wait: every event has happened)
+        if (!kernel_ms) return hipSuccess;
+        *kernel_ms = 0;
+        for (int q = 0; q + 1 < n_ev; q += 2) {
+            float ms = 0;
+            hipError_t e = hipEventElapsedTime(&ms, ev[q], ev[q + 1]);
+            if (e != hipSuccess) return e;
+            *kernel_ms += ms;
+        }
+        return hipSuccess;
+    };
+    // ---- the gaps: count, place, compact.  The tile counts live in the text buffer until the text itself is written.
+    uint64_t m = 0;
+    const uint32_t nb = (n + CH_TILE - 1) / CH_TILE;
+    if (n && !g.all_snp) {
+        int rc = dev_reserve(c, (void **)&c->d_text, &c->cap_text, ((size_t)nb + 1) * 8 + 64);
+        if (rc) return rc;
+        unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->d_text);
+        MSIM_HIP(c, mark());
+        hipLaunchKernelGGL(k_chain_count, dim3(nb), dim3(TX_THREADS), 0, st, g.d_recs, n, d_cnt);
+        hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, d_cnt, nb, c->h_mail);
+        MSIM_HIP(c, hipGetLastError());
+        MSIM_HIP(c, mark());
+        MSIM_HIP(c, wait_stream(st));
+        m = *c->h_mail;
+    }
+    uint64_t sum_dt = 0, sum_dq = 0, t_start = 0, q_start = 0, t_trail = 0, q_trail = 0, last_size = L, n_lines = 0, body = 0;
+    uint32_t *d_hsize = nullptr;
+    unsigned long long *d_hp_dt = nullptr, *d_hp_dq = nullptr, *d_off = nullptr;
+    if (m) {
+        const uint32_t mm = (uint32_t)m, nb2 = (mm + CH_TILE - 1) / CH_TILE, stride = nb2 + 1, nbl = (mm + LS_BLOCK - 1) / LS_BLOCK;
+        auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        // scratch: gaps uint4[m] | tiles u64[3][nb2 + 1] | hsize u32[m + 1] | hp_dt, hp_dq u64[m + 1] | tot u64[4] |
+        //          len u32[m] | lsums u64[nbl + 1] | off u64[m]
+        const size_t o_tiles = up((size_t)mm * 16), o_hsize = o_tiles + up((size_t)3 * stride * 8);
+        const size_t o_hpdt = o_hsize + up(((size_t)mm + 1) * 4), o_hpdq = o_hpdt + up(((size_t)mm + 1) * 8);
+        const size_t o_tot = o_hpdq + up(((size_t)mm + 1) * 8), o_len = o_tot + 256, o_lsums = o_len + up((size_t)mm * 4);
+        const size_t o_off = o_lsums + up(((size_t)nbl + 1) * 8), end = o_off + up((size_t)mm * 8);
+        int rc = dev_reserve(c, (void **)&c->d_text_scratch, &c->cap_text_scratch, end);
+        if (rc) return rc;
+        uint8_t *base = c->d_text_scratch;
+        uint4 *d_gaps = reinterpret_cast<uint4 *>(base);
+        unsigned long long *d_tiles = reinterpret_cast<unsigned long long *>(base + o_tiles);
+        d_hsize = reinterpret_cast<uint32_t *>(base + o_hsize);
+        d_hp_dt = reinterpret_cast<unsigned long long *>(base + o_hpdt);
+        d_hp_dq = reinterpret_cast<unsigned long long *>(base + o_hpdq);
+        unsigned long long *d_tot = reinterpret_cast<unsigned long long *>(base + o_tot);
+        uint32_t *d_len = reinterpret_cast<uint32_t *>(base + o_len);
+        unsigned long long *d_lsums = reinterpret_cast<unsigned long long *>(base + o_lsums);
+        d_off = reinterpret_cast<unsigned long long *>(base + o_off);
+        MSIM_HIP(c, mark());
+        hipLaunchKernelGGL(k_chain_compact, dim3(nb), dim3(TX_THREADS), 0, st, g.d_recs, n,
+                           reinterpret_cast<const unsigned long long *>(c->d_text), d_gaps);
+        hipLaunchKernelGGL(k_chain_tiles, dim3(nb2), dim3(TX_THREADS), 0, st, d_gaps, mm, stride, d_tiles);
+        for (int q = 0; q < 3; q++)
+            hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, d_tiles + (size_t)q * stride, nb2, c->h_mail);
+        hipLaunchKernelGGL(k_chain_heads, dim3(nb2), dim3(TX_THREADS), 0, st, d_gaps, mm, stride, d_tiles, d_hsize, d_hp_dt, d_hp_dq,
+                           d_tot);
+        MSIM_HIP(c, hipGetLastError());
+        MSIM_HIP(c, mark());
+        unsigned long long tot[4];
+        MSIM_HIP(c, hipMemcpyAsync(tot, d_tot, sizeof tot, hipMemcpyDeviceToHost, st));
+        MSIM_HIP(c, wait_stream(st));
+        const uint64_t heads = tot[0], final_block = L - tot[1];
+        sum_dt = tot[2]; sum_dq = tot[3];
+        if (L > sum_dt) {                                                // (else: no aligned base, no chain)
+            // gaps in front of the first head are leading ones; without a last block the last head's run is trailing
+            // and its block the last one
+            unsigned long long lead[2] = {sum_dt, sum_dq}, trail[2] = {sum_dt, sum_dq};
+            uint32_t tail_size = 0;
+            if (heads) {
+                MSIM_HIP(c, hipMemcpyAsync(&lead[0], d_hp_dt, 8, hipMemcpyDeviceToHost, st));
+                MSIM_HIP(c, hipMemcpyAsync(&lead[1], d_hp_dq, 8, hipMemcpyDeviceToHost, st));
+            }
+            if (!final_block) {                                          // (heads >= 1: some base is aligned)
+                MSIM_HIP(c, hipMemcpyAsync(&trail[0], d_hp_dt + heads - 1, 8, hipMemcpyDeviceToHost, st));
+                MSIM_HIP(c, hipMemcpyAsync(&trail[1], d_hp_dq + heads - 1, 8, hipMemcpyDeviceToHost, st));
+                MSIM_HIP(c, hipMemcpyAsync(&tail_size, d_hsize + heads - 1, 4, hipMemcpyDeviceToHost, st));
+            }
+            n_lines = final_block ? heads : heads - 1;
+            if (n_lines) {
+                const uint32_t nl = (uint32_t)n_lines, nbk = (nl + LS_BLOCK - 1) / LS_BLOCK;
+                MSIM_HIP(c, mark());
+                hipLaunchKernelGGL((k_chain_lines<false>), dim3((nl + TX_THREADS - 1) / TX_THREADS), dim3(TX_THREADS), 0, st, d_hsize,
+                                   d_hp_dt, d_hp_dq, nl, d_len, (const unsigned long long *)nullptr, (char *)nullptr);
+                hipLaunchKernelGGL(k_len_reduce, dim3(nbk), dim3(TX_THREADS), 0, st, d_len, nl, d_lsums);
+                hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, d_lsums, nbk, c->h_mail);
+                hipLaunchKernelGGL(k_len_offsets, dim3(nbk), dim3(TX_THREADS), 0, st, d_len, nl, d_lsums, d_off);
+                MSIM_HIP(c, hipGetLastError());
+                MSIM_HIP(c, mark());
+            }
+            MSIM_HIP(c, wait_stream(st));
+            if (n_lines) body = *c->h_mail;
+            t_start = lead[0]; q_start = lead[1];
+            if (final_block) last_size = final_block;
+            else { last_size = tail_size; t_trail = sum_dt - trail[0]; q_trail = sum_dq - trail[1]; }
+        }
+    }
+    if (L <= sum_dt) {                                                   // wholly deleted / empty contig: no text
+        MSIM_HIP(c, sum_events());
+        return MSIM_OK;
+    }
+    // ---- the text: header (host) | lines (device) | last block (host)
+    uint64_t hdr = 0;
+    chain_header(nullptr, &hdr, L, sum_dt, sum_dq, t_start, q_start, t_trail, q_trail, t_name, q_name, id);
+    std::string edge((size_t)hdr, '\0');
+    uint64_t at = 0;
+    chain_header(&edge[0], &at, L, sum_dt, sum_dq, t_start, q_start, t_trail, q_trail, t_name, q_name, id);
+    edge += std::to_string(last_size) + "\n\n";
+    const uint64_t total = edge.size() + body;
+    int rc = dev_reserve(c, (void **)&c->d_text, &c->cap_text, total + 64);
+    if (rc) return rc;
+    MSIM_HIP(c, hipMemcpyAsync(c->d_text, edge.data(), hdr, hipMemcpyHostToDevice, st));
+    if (n_lines) {
+        const uint32_t nl = (uint32_t)n_lines;
+        MSIM_HIP(c, mark());
+        hipLaunchKernelGGL((k_chain_lines<true>), dim3((nl + TX_THREADS - 1) / TX_THREADS), dim3(TX_THREADS), 0, st, d_hsize, d_hp_dt,
+                           d_hp_dq, nl, (uint32_t *)nullptr, d_off, reinterpret_cast<char *>(c->d_text) + hdr);
+        MSIM_HIP(c, hipGetLastError());
+        MSIM_HIP(c, mark());
+    }
+    MSIM_HIP(c, hipMemcpyAsync(c->d_text + hdr + body, edge.data() + hdr, edge.size() - hdr, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, wait_stream(st));                                        // (`edge` is read until here)
+    MSIM_HIP(c, sum_events());
+    c->text_len = total;
     return MSIM_OK;
 }
 

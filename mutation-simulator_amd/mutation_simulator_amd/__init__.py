@@ -6,6 +6,7 @@ build covers; the work behind ``Mutator`` runs as hand-written HIP kernels throu
 from ._version import __version__
 from .argument_parser import get_args
 from .bedpe_writer import BedpeWriter, BedpeWriterError
+from .chain_writer import ChainWriter, ChainWriterError
 from .colors import Colors
 from .fasta_io import FastaIndexingError, FastaNotFoundError, UnsupportedCompressionFormat
 from .fasta_writer import FastaWriter, FastaWriterError

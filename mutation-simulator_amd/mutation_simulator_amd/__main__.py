@@ -28,6 +28,10 @@ class VcfModeUnsupportedError(Exception):
     """The vcf mode together with what it does not cover (a sharded run)."""
 
 
+class ChainUnsupportedError(Exception):
+    """--chain together with what it does not cover (the IT pass, a sharded run)."""
+
+
 class CompressedInputUnsupportedError(Exception):
     """A gzip-compressed input together with what does not cover it (a sharded run)."""
 
@@ -50,6 +54,10 @@ def initialize(argv=None):
         exit_with_error(BgzipUnsupportedError("--bgzip does not apply to the interchromosomal pass (it)"), args.no_color)
     if args.bgzip and (args.gpus or 1) > 1:
         exit_with_error(BgzipUnsupportedError("--bgzip needs a single-GPU run (--gpus 1)"), args.no_color)
+    if args.chain and args.mode == "it":
+        exit_with_error(ChainUnsupportedError("--chain does not apply to the interchromosomal pass (it)"), args.no_color)
+    if args.chain and (args.gpus or 1) > 1:
+        exit_with_error(ChainUnsupportedError("--chain needs a single-GPU run (--gpus 1)"), args.no_color)
     if (args.gpus or 1) > 1 and is_gzip(args.infile):
         # (the parent of a sharded run never opens a GPU, and parent and workers would each inflate the whole file)
         exit_with_error(CompressedInputUnsupportedError(
@@ -80,6 +88,9 @@ def initialize(argv=None):
         exit_with_error(e, args.no_color)
     if args.bgzip and sim.has_it:
         exit_with_error(BgzipUnsupportedError("--bgzip does not apply to the interchromosomal pass (it lines in the RMT)"),
+                        args.no_color)
+    if args.chain and sim.has_it:
+        exit_with_error(ChainUnsupportedError("--chain does not apply to the interchromosomal pass (it lines in the RMT)"),
                         args.no_color)
     if not early and (args.gpus or 1) <= 1:
         _warm_up(args)
@@ -112,7 +123,8 @@ def main(argv=None):
                 stats = dict(replay.stats)
                 stats["cli_s"] = {"load_index": round(STAGES.get("load_index", 0.0), 4), "replay": round(timer() - loaded, 4)}
                 args.bench_json.write_text(json.dumps(stats, indent=1) + "\n")
-        except (FastaWriterError, VcfReplayError, MsimError, FileNotFoundError, UnsupportedCompressionFormat, ValueError) as e:
+        except (FastaWriterError, ChainWriterError, VcfReplayError, MsimError, FileNotFoundError, UnsupportedCompressionFormat,
+                ValueError) as e:
             exit_with_error(e, args.no_color)
         if not args.quiet:
             print_success(f"Mutation-Simulator finished in: {round(timer() - start, 4)}s", args.no_color)
@@ -140,7 +152,7 @@ def main(argv=None):
                                   "parse_args": round(STAGES.get("parse_args", 0.0), 4), "load_index": round(STAGES.get("load_index", 0.0), 4),
                                   "open_writers": round(t1 - t0, 4), "mutate": round(t2 - t1, 4), "close": round(timer() - t2, 4)}
                 args.bench_json.write_text(json.dumps(stats, indent=1) + "\n")
-        except (FastaWriterError, VcfWriterError, MsimError) as e:
+        except (FastaWriterError, VcfWriterError, ChainWriterError, MsimError) as e:
             exit_with_error(e, args.no_color)
     if sim.has_it:                         # the second pass reads what the first one wrote (reference __main__.py:88-102)
         if sim.has_mutations:

@@ -119,6 +119,8 @@ SYMBOLS = [
     ("msim_result_device_ptr", C.c_int, [_VP, C.c_int, _U64P, _U64P]),
     ("msim_render_vcf", C.c_int, [_VP, C.c_uint64, _VP, _VP, C.c_uint64, C.c_char_p, _VP,
                                   C.c_uint64, _U64P]),
+    ("msim_render_chain", C.c_int, [_VP, C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint64, _VP, C.c_uint64, _U64P]),
+    ("msim_render_chain_device", C.c_int, [_VP, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, _VP, C.c_uint64, _U64P]),
     ("msim_render_vcf_device", C.c_int, [_VP, C.c_int, C.c_char_p, _VP, C.c_uint64, _U64P]),
     ("msim_fetch_sequence_framed", C.c_int, [_VP, C.c_int, C.c_uint32, _VP, C.c_uint64, _U64P]),
     ("msim_render_vcf_device_file", C.c_int, [_VP, C.c_int, C.c_char_p, C.c_int, C.c_uint64, _U64P]),
@@ -191,6 +193,32 @@ def load():
             raise MsimError("libmsim ABI version mismatch")
         _lib = lib
     return _lib
+
+
+def render_chain(recs: np.ndarray, length: int, t_name: str, q_name: str, chain_id: int) -> bytes:
+    """``msim_render_chain``: the liftover chain of a record table (RECORD_DTYPE) over a contig of ``length`` bases.  Pure host
+    code, no context."""
+    lib = load()
+    recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+    t, q = t_name.encode("utf-8", "replace"), q_name.encode("utf-8", "replace")
+    need = C.c_uint64()
+    rc = lib.msim_render_chain(_ptr(recs), len(recs), int(length), t, q, int(chain_id), None, 0, C.byref(need))
+    if rc != OK:
+        raise MsimError(f"msim_render_chain failed ({rc})")
+    out = np.empty(need.value, dtype=np.uint8)
+    if need.value:
+        rc = lib.msim_render_chain(_ptr(recs), len(recs), int(length), t, q, int(chain_id), _ptr(out), need.value, C.byref(need))
+        if rc != OK:
+            raise MsimError(f"msim_render_chain failed ({rc})")
+    return out.tobytes()
+
+
+def chain_tile() -> int:
+    """Records / gaps a workgroup of the chain kernels takes (text_gpu.hip: CH_TILE): where the device renderer's edge cases
+    lie (msim_dbg_chain_tile: exported, not part of include/msim.h)."""
+    fn = load().msim_dbg_chain_tile
+    fn.restype, fn.argtypes = C.c_uint32, []
+    return int(fn())
 
 
 def parse_cpulist(text: str) -> set:
@@ -541,6 +569,27 @@ class Engine:
         if need.value:
             self._check(self.lib.msim_render_vcf_device(self.h, contig, name, _ptr(out), need.value, C.byref(need)), contig)
         return out
+
+    def render_chain_device(self, contig: int, t_name: str, q_name: str, chain_id: int) -> np.ndarray:
+        """The planned contig's liftover chain (msim.h: msim_render_chain_device) rendered on the device, as a uint8 array of
+        text; empty for a contig without an aligned base."""
+        need = C.c_uint64()
+        t, q = t_name.encode("utf-8", "replace"), q_name.encode("utf-8", "replace")
+        self._check(self.lib.msim_render_chain_device(self.h, contig, t, q, int(chain_id), None, 0, C.byref(need)), contig)
+        out = np.empty(need.value, dtype=np.uint8)
+        if need.value:
+            self._check(self.lib.msim_render_chain_device(self.h, contig, t, q, int(chain_id), _ptr(out), need.value,
+                                                          C.byref(need)), contig)
+        return out
+
+    def chain_kernel_ms(self) -> float:
+        """Device time (HIP events) of the chain kernels of the last ``render_chain_device`` rendering; the first call switches
+        the measurement on and returns 0 (msim_dbg_chain_ms: exported, not part of include/msim.h)."""
+        fn = self.lib.msim_dbg_chain_ms
+        fn.restype, fn.argtypes = C.c_int, [_VP, C.POINTER(C.c_double)]
+        ms = C.c_double()
+        self._check(fn(self.h, C.byref(ms)))
+        return ms.value
 
     def render_vcf_device_size(self, contig: int, seq_name: str) -> int:
         """Render the contig's VCF record lines on the device and report their size (the text stays in HBM for

@@ -1,7 +1,8 @@
 """Command line of ``mutation-simulator`` -- flag-for-flag the reference's ``args`` and ``rmt``
 sub-commands (reference argument_parser.py:31-240) plus a few additions of ours that never change
-a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bgzip``, ``--bench-json``, and the ``vcf`` sub-command
-(``vcf_replay.py``: the mutated Fasta again from the reference and a run's VCF; it writes ``<outbase>_ms.fa`` only).
+a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bgzip``, ``--chain``, ``--bench-json``, and the ``vcf`` sub-command
+(``vcf_replay.py``: the mutated Fasta again from the reference and a run's VCF; it writes ``<outbase>_ms.fa`` and, with
+``--chain``, ``<outbase>_ms.chain``).
 
 The ``it`` sub-command (inter-chromosomal translocations, reference it_mutator.py: a second pass over
 the Fasta) runs through ``ITMutator`` / ``BedpeWriter``.  ``--rng fast`` applies to the mutation pass
@@ -18,7 +19,8 @@ from .fasta_io import is_gzip
 
 
 def add_outfile_names(args: Namespace) -> Namespace:
-    """``<outbase>_ms<infile suffix>`` / ``<outbase>_ms.vcf`` (reference argument_parser.py:14-28).
+    """``<outbase>_ms<infile suffix>`` / ``<outbase>_ms.vcf`` (reference argument_parser.py:14-28), and ``<outbase>_ms.chain``
+    for ``--chain`` (plain text also under ``--bgzip``).
 
     ``-o`` may be a basename or a directory-like path with an empty stem (".", "dir/.."): then the
     input's stem is used inside that directory.
@@ -38,6 +40,7 @@ def add_outfile_names(args: Namespace) -> Namespace:
     args.outfastait = args.outfasta.with_stem(args.outfasta.stem + "_it")
     args.outvcf = args.outfasta.with_suffix(".vcf")
     args.outbedpe = args.outfastait.with_suffix(".bedpe")
+    args.outchain = args.outfasta.with_suffix(".chain")
     if getattr(args, "bgzip", False):             # BGZF-compressed mutation-pass outputs: <name>.gz
         args.outfasta = args.outfasta.with_name(args.outfasta.name + ".gz")
         args.outvcf = args.outvcf.with_name(args.outvcf.name + ".gz")
@@ -88,6 +91,12 @@ def build_parser() -> ArgumentParser:
     parser.add_argument("--bgzip", action="store_true", default=False,
                         help="Write the mutated Fasta and the VCF BGZF-compressed (<name>.gz, compressed on the GPU); "
                              "they decompress to exactly the files written without it. Not with it / --gpus N > 1")
+    parser.add_argument("--chain", action="store_true", default=False,
+                        help="Also write <outbase>_ms.chain: a UCSC liftover chain per contig from the reference's coordinates "
+                             "(target) to the mutated genome's (query), rendered on the GPU from the mutation table. Plain text "
+                             "also with --bgzip. The run goes contig by contig (an assembly of thousands of small scaffolds "
+                             "loses the speed of the batched pass; the output bytes are the same). Not with it / it lines in "
+                             "the RMT / --gpus N > 1")
     parser.add_argument("--bench-json", type=Path, default=None,
                         help="Write per-stage timings of the mutation pass to this JSON file")
 

@@ -15,6 +15,7 @@ changed is *where* the work happens:
   pyfaidx per-base reads                   -> msim_add_contig_text: file text to HBM, stripped + upper-cased there
   FastaWriter.write per base               -> msim_fetch_sequence_framed: line-wrapped on the device, one write
   VcfWriter.write per record               -> msim_render_vcf_device: record lines rendered on the device
+  (no counterpart: --chain)                -> msim_render_chain_device: the record table as a liftover chain
 
 All floating-point expressions of the path are evaluated here with the reference's own formulas
 (``plan_descriptors``); the C-ABI takes integers only.
@@ -31,6 +32,7 @@ from typing import Optional
 import numpy as np
 
 from . import _ffi
+from .chain_writer import ChainWriter
 from .fasta_writer import FastaWriter
 from .mut_types import MutType
 from .util import format_warning
@@ -315,6 +317,7 @@ class Mutator:
     """Runs the mutation pass of one genome on the GPU and writes ``*_ms.fa`` / ``*_ms.vcf``."""
 
     _bgzip = False                                     # --bgzip: BGZF writers (subclasses that open writers of their own: plain)
+    _chain_writer = None                               # --chain: the liftover chain file (subclasses without one: none)
 
     def __init__(self, args, fasta, sim, engine: Optional["_ffi.Engine"] = None):
         self._args = args
@@ -322,6 +325,9 @@ class Mutator:
         self._sim = sim
         self._bgzip = bool(getattr(args, "bgzip", False))
         dev = getattr(args, "device", 0) or 0
+        # --chain: the liftover chains, contig by contig behind the VCF lines.  Opened first: a chain path that cannot be
+        # written ends the run (ChainWriterError) before the other two files exist.
+        self._chain_writer = ChainWriter(args.outchain) if getattr(args, "chain", False) else None
         self._fasta_writer = FastaWriter(args.outfasta, bgzip=self._bgzip, device=dev)
         self._vcf_writer = VcfWriter(args.outvcf, bgzip=self._bgzip, device=dev)
         self._vcf_writer.write_header(getattr(args, "genome_name", args.infile.name), fasta, sim.assembly_name, sim.species_name,
@@ -353,6 +359,8 @@ class Mutator:
         try:
             self._fasta_writer.close()
             self._vcf_writer.close()
+            if self._chain_writer is not None:
+                self._chain_writer.close()
         finally:
             if side is not None:
                 side.join()
@@ -577,6 +585,11 @@ class Mutator:
             finally:
                 self._vcf_writer.commit_region(region)
         t["vcf_egress_s"] += time.perf_counter() - t3
+        if self._chain_writer is not None and "chain" not in done:
+            t4 = time.perf_counter()
+            self._chain_writer.write_contig(eng, cid, rec.name, chrom.number)
+            done.add("chain")
+            t["chain_egress_s"] = t.get("chain_egress_s", 0.0) + time.perf_counter() - t4
         eng.clear()
 
     def _units(self, chroms):
@@ -586,6 +599,8 @@ class Mutator:
         from .rmt import StdChromosomes
         n = len(chroms)
         if self._fast_rng:                             # no chain to amortise, and batches are planned on the host's streams
+            return [(q, q + 1) for q in range(n)]
+        if self._chain_writer is not None:             # --chain: a batch keeps no per-contig table to render a chain from
             return [(q, q + 1) for q in range(n)]
         tab = getattr(self._fasta, "index_table", None)
         if (isinstance(chroms, StdChromosomes) and tab is not None and len(tab) == n

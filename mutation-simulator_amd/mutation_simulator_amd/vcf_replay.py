@@ -2,7 +2,7 @@
 
 Every data line replaces REF at POS by ALT; libmsim parses the text into the record tables the mutation pass would have
 planned (``msim_vcf_*``, csrc/vcf_parse.hip), the unchanged rewrite produces the bytes, and ``FastaWriter`` with the
-output channels writes them -- ``--bgzip`` included.  No generator is touched: there is nothing random about a replay.
+output channels writes them -- ``--bgzip`` included; ``--chain`` adds the tables' liftover chains (``chain_writer.py``).  No generator is touched: there is nothing random about a replay.
 
 The whole genome is resident while the VCF is checked, because nothing is rewritten before every line has been accepted.
 """
@@ -13,6 +13,7 @@ from pathlib import Path
 import numpy as np
 
 from . import _ffi
+from .chain_writer import ChainWriter
 from .fasta_io import UnsupportedCompressionFormat
 from .fasta_writer import FastaWriter
 
@@ -89,6 +90,7 @@ class VcfReplay:
         self._engine = engine
         self._own_engine = engine is None
         self._writer = None
+        self._chain_writer = None
         self.stats: dict = {}
 
     def run(self):
@@ -108,9 +110,11 @@ class VcfReplay:
                 cids.append(eng.add_contig(rec.bases))
         plan_all(eng, text, [r.name for r in recs], cids)
         # every line is accepted: rewrite and write, contig by contig
+        if getattr(self._args, "chain", False):        # the one extra file of this mode: the chains of the replayed tables
+            self._chain_writer = ChainWriter(self._args.outchain)      # (first: if it cannot be written, no Fasta is left)
         self._writer = FastaWriter(self._args.outfasta, bgzip=self._bgzip, device=self._device)
         self._writer.attach(eng)
-        for rec, cid in zip(recs, cids):
+        for number, (rec, cid) in enumerate(zip(recs, cids)):
             bpl = fa.faidx.index[rec.name].lenc
             self._writer.set_bpl(bpl)
             self._writer.write_header(rec.long_name)
@@ -129,6 +133,8 @@ class VcfReplay:
                         self._writer.commit_region(region, out_len)
             else:
                 self._writer.write_array(eng.fetch_sequence(cid))
+            if self._chain_writer is not None:
+                self._chain_writer.write_contig(eng, cid, rec.name, number)
             eng.release_result(cid)
         eng.file_wait()
         load_ms, plan_ms = eng.vcf_timing()
@@ -146,6 +152,8 @@ class VcfReplay:
         try:
             if self._writer is not None:
                 self._writer.close()                   # (BGZF: tail and EOF marker go out through the engine)
+            if self._chain_writer is not None:
+                self._chain_writer.close()
         finally:
             self._engine = None
             if eng is not None and self._own_engine:
