@@ -1107,6 +1107,7 @@ int apply_finish(Ctx *c) {
 struct RwPending { RwJob job; int variant; int contig; };
 
 static_assert((TILE & (TILE - 1)) == 0, "the expansion's tile index shifts by log2(TILE)");
+uint32_t apply_tile_shift() { return (uint32_t)__builtin_ctz((unsigned)TILE); }
 int apply_prepare_tile_index(Ctx *c, Contig &g, hipStream_t st, int32_t **first, uint32_t *n_tiles, uint32_t *tile_shift,
                              unsigned long long **err) {
     const uint32_t nt = (uint32_t)((g.len + TILE - 1) / TILE);      // (SNP-only: the mutated contig is as long as the contig)

@@ -347,6 +347,7 @@ int apply_batch_device(Ctx *c, const std::vector<int> &ids, bool batch_rewrites)
 int apply_finish(Ctx *c);             // collect results of asynchronous APPLYs (timing, KeyError words)
 // SNP sampler (plan_gpu.hip: gpu_emit_flush): the expansion kernel writes an SNP-only contig's tile index itself -- room for it,
 // its geometry (tile = 1 << *tile_shift output bytes, *n_tiles of them; n_tiles + 1 entries) and the contig's KeyError word
+uint32_t apply_tile_shift();              // log2 of the rewrite kernels' tile
 int apply_prepare_tile_index(Ctx *c, Contig &g, hipStream_t st, int32_t **first, uint32_t *n_tiles, uint32_t *tile_shift,
                              unsigned long long **err);
 constexpr int MAX_CONTIGS = 1 << 16;

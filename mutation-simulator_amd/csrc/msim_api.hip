@@ -1366,6 +1366,23 @@ int msim_dbg_apply_batch(msim_ctx *p, const int *contigs, int n) {
     return apply_batch_device(c, ids, true);
 }
 
+// The SNP sampler's emission train (plan_gpu.hip: gpu_emit_flush's launches) over bitmaps the caller made: up to 8 jobs of
+// (bitmap words, start, contig length, SNP outcomes by rank) go through ONE group's launches, train = 3 or 6; each job's record
+// table comes back and, for train 3 where first[i] is given, its APPLY tile index (ceil(len / msim_dbg_apply_tile()) + 1 entries).  The kernels
+// can so be run on bitmaps the sampler never produces.  Synchronous; touches no contig.
+uint32_t msim_dbg_apply_tile(void) { return 1u << apply_tile_shift(); }
+int msim_dbg_emit_train(msim_ctx *p, int n_jobs, const uint64_t *const *bitmaps, const uint32_t *n_words, const uint32_t *start,
+                        const uint64_t *contig_len, const uint8_t *const *aux8, uint32_t d, int train, msim_record *const *recs,
+                        const uint64_t *cap_recs, uint64_t *n_recs, int32_t *const *first) {
+    CTX_FLUSHED(c, p)
+    if (!c) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    int rc = drain(c);
+    if (rc) return rc;
+    return gpu_dbg_emit_train(c, n_jobs, bitmaps, n_words, start, contig_len, aux8, d, train, apply_tile_shift(), recs, cap_recs,
+                              n_recs, first);
+}
+
 // test support (tests/test_ahead_moments.py, CPU tier): the moments the anchored windows are laid out from; needs no context
 int msim_dbg_stream_moments(uint64_t n, uint64_t k, uint64_t K, uint64_t ti_lim, double out[4]) {
     if (!out || !n || k >= n) return MSIM_ERR_ARG;

@@ -36,6 +36,10 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
 // still queued (mark_apply: its APPLY follows its group's emission -- msim_apply_contig)
 int gpu_emit_flush(Ctx *c);
 bool gpu_emit_pending(Ctx *c, int contig, bool mark_apply);
+// test support (msim_dbg_emit_train): one group's train over the caller's bitmaps and outcomes
+int gpu_dbg_emit_train(Ctx *c, int n_jobs, const uint64_t *const *bm, const uint32_t *n_words, const uint32_t *start,
+                       const uint64_t *len, const uint8_t *const *aux8, uint32_t d, int train, uint32_t tile_shift,
+                       msim_record *const *recs, const uint64_t *cap_recs, uint64_t *n_recs, int32_t *const *first);
 int gpu_plan_force_overflow(Ctx *c, GpuPlan *g);          // test support
 void gpu_plan_abandon(GpuPlan *g);                        // a device engine failed mid-contig: the session is over
 // before a contig goes to a device engine: room for its windows in the current session's jump-table span, re-basing the session

@@ -875,7 +875,7 @@ static int enqueue_sample_chain(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
     const uint32_t bmw = (uint32_t)bm_words64;
     const uint32_t bnb = (bmw + BM_THREADS - 1) / BM_THREADS;
     if ((rc = grow(c, (void **)&S.cnt, &S.cnt_cap, (size_t)(nb + 2) * sizeof(uint32_t), &grew))) return rc;
-    if ((rc = grow(c, (void **)&S.cnt2, &S.cnt2_cap, (size_t)(bnb + EMIT_SUPER + bnb / EMIT_SUPER + 4) * sizeof(uint32_t), &grew))) return rc;   // (+ whole super-blocks and their totals: k_snp_emit_count_b)
+    if ((rc = grow(c, (void **)&S.cnt2, &S.cnt2_cap, emit_cnt2_words(bmw) * sizeof(uint32_t), &grew))) return rc;   // (either train's layout: plan_kernels.h)
     if ((rc = grow(c, (void **)&S.acc, &S.acc_cap, (size_t)W * sizeof(uint32_t), &grew))) return rc;
     if ((rc = grow(c, (void **)&S.bitmap, &S.bm_cap, bm_words64 * 8, &grew))) return rc;
     if (!S.emit_done) MSIM_HIP(c, hipEventCreateWithFlags(&S.emit_done, hipEventDisableTiming));
@@ -995,7 +995,7 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
     const double mean = (double)((nbk + BIN_SUBS - 1) / BIN_SUBS) * SPL_BLOCK * p_acc * std::min(1.0, (double)BIN_VALUES / (double)n);
     const uint32_t bin_cap = (uint32_t)std::min<double>((double)K + 16.0, 1.25 * mean + 16.0 * std::sqrt(mean) + 512.0);
     if ((rc = grow(c, (void **)&S.cnt, &S.cnt_cap, (size_t)(nb + 2) * sizeof(uint32_t), &grew))) return rc;
-    if ((rc = grow(c, (void **)&S.cnt2, &S.cnt2_cap, (size_t)(bnb + EMIT_SUPER + bnb / EMIT_SUPER + 4) * sizeof(uint32_t), &grew))) return rc;   // (+ whole super-blocks and their totals: k_snp_emit_count_b)
+    if ((rc = grow(c, (void **)&S.cnt2, &S.cnt2_cap, emit_cnt2_words(bmw) * sizeof(uint32_t), &grew))) return rc;   // (either train's layout: plan_kernels.h)
     if ((rc = grow(c, (void **)&S.acc, &S.acc_cap, (size_t)W * sizeof(uint32_t), &grew))) return rc;
     if ((rc = grow(c, (void **)&S.bins, &S.bins_cap, (size_t)n_bins * BIN_SUBS * bin_cap * sizeof(uint32_t), &grew))) return rc;
     if ((rc = grow(c, (void **)&S.cursors, &S.cursors_cap, (size_t)MAX_BINS * BIN_SUBS * sizeof(uint32_t), &grew))) return rc;
@@ -1107,6 +1107,28 @@ static int enqueue_snp_stage(Ctx *c, GpuPlan *g, Contig &ct, uint64_t K, const u
     return MSIM_OK;
 }
 
+// The launches of a train in front of its rewrite, on `es` (gpu_emit_flush; gpu_dbg_emit_train on a caller's bitmaps).  J carries
+// the jobs' buffers and sizes (bmw, bnb, nb2); their places in the grids are laid out here.  Jobs without SNP draws (nb2 == 0
+// throughout: aux8 is already there) launch no outcome blocks.
+static void emit_train_launch(hipStream_t es, const SnpLane *lanes, EmitJobs &J, bool train3) {
+    uint32_t blk = 0, eblk = 0, cblk = 0, xblk = 0;
+    for (uint32_t i = 0; i < J.n; i++) {
+        EmitJob &T = J.j[i];
+        T.blk0 = blk; T.eblk0 = eblk; T.cblk0 = cblk; T.xblk0 = xblk;
+        blk += T.bnb; eblk += T.nb2; cblk += emit_supers(T.bmw); xblk += emit_blocks(T.bmw);
+    }
+    J.total_blk = blk; J.total_eblk = eblk; J.total_cblk = cblk;
+    if (train3) {
+        if (eblk + cblk) hipLaunchKernelGGL(k_snp_emit_count_b, dim3(eblk + cblk), dim3(SNP_THREADS), 0, es, lanes, J);
+        if (xblk) hipLaunchKernelGGL(k_bitmap_expand_tiles_b, dim3(xblk), dim3(BM_THREADS), 0, es, J);
+    } else {
+        if (blk) hipLaunchKernelGGL(k_bitmap_count_b, dim3(blk), dim3(BM_THREADS), 0, es, J);
+        hipLaunchKernelGGL(k_scan_u32_b, dim3(J.n), dim3(256), 0, es, J);
+        if (eblk) hipLaunchKernelGGL(k_snp_emit_abs_b, dim3(eblk), dim3(SNP_THREADS), 0, es, lanes, J);
+        if (blk) hipLaunchKernelGGL(k_bitmap_expand_b, dim3(blk), dim3(BM_THREADS), 0, es, J);
+    }
+}
+
 // The emission group: count, scan, SNP outcomes and expansion of every queued contig in one launch per stage on the emission
 // stream, behind the chain of the last one; then the APPLYs msim_apply_contig marked (one tile-index launch for all of them,
 // apply.hip: apply_batch_device), the rewrite kernels back to back.
@@ -1119,16 +1141,13 @@ int gpu_emit_flush(Ctx *c) {
     memset(&J, 0, sizeof J);
     J.n = (uint32_t)items.size();
     J.d = g->emit_d;
-    uint32_t blk = 0, eblk = 0;
     for (uint32_t i = 0; i < J.n; i++) {
         const EmitItem &it = items[i];
         EmitJob &T = J.j[i];
         T.bm = reinterpret_cast<const uint64_t *>(it.S->bitmap); T.cnt2 = it.S->cnt2; T.recs = it.recs; T.aux8 = it.T->aux8;
         T.base = it.T->base; T.win_maps = it.T->maps;
-        T.bmw = it.bmw; T.bnb = it.bnb; T.start = it.start; T.K = it.K; T.W2 = it.W2; T.nb2 = it.nb2; T.blk0 = blk; T.eblk0 = eblk;
-        blk += it.bnb; eblk += it.nb2;
+        T.bmw = it.bmw; T.bnb = it.bnb; T.start = it.start; T.K = it.K; T.W2 = it.W2; T.nb2 = it.nb2;
     }
-    J.total_blk = blk; J.total_eblk = eblk;
     hipStream_t es = c->emit_stream;
     // The train in three launches (MSIM_EMIT_TRAIN=6: the six of rounds 4-5: count, scan, outcomes, expansion, tile index,
     // rewrite): outcomes + popcounts in one grid; the expansion makes its rank base from two levels of counts and writes the
@@ -1142,12 +1161,9 @@ int gpu_emit_flush(Ctx *c) {
     const bool train3 = g->emit_train == 3 || (g->emit_train == 0 && ahead_in_use);
     std::vector<int> applies;
     if (train3) {
-        uint32_t cblk = 0;
         for (uint32_t i = 0; i < J.n; i++) {
             const EmitItem &it = items[i];
             EmitJob &T = J.j[i];
-            T.cblk0 = cblk;
-            cblk += (it.bnb + EMIT_SUPER - 1) / EMIT_SUPER;
             T.first = nullptr; T.err = nullptr; T.n_tiles = 0;
             if (it.apply && (size_t)it.contig < c->contigs.size()) {
                 Contig &ct = c->contigs[(size_t)it.contig];
@@ -1160,20 +1176,11 @@ int gpu_emit_flush(Ctx *c) {
                 applies.push_back(it.contig);
             }
         }
-        J.total_cblk = cblk;
     }
     hipEvent_t ce = next_chain_event(g);
     MSIM_HIP(c, hipEventRecord(ce, c->stream));
     MSIM_HIP(c, hipStreamWaitEvent(es, ce, 0));
-    if (train3) {
-        hipLaunchKernelGGL(k_snp_emit_count_b, dim3(eblk + J.total_cblk), dim3(SNP_THREADS), 0, es, g->s[0].d_lanes, J);
-        hipLaunchKernelGGL(k_bitmap_expand_tiles_b, dim3(blk), dim3(BM_THREADS), 0, es, J);
-    } else {
-        hipLaunchKernelGGL(k_bitmap_count_b, dim3(blk), dim3(BM_THREADS), 0, es, J);
-        hipLaunchKernelGGL(k_scan_u32_b, dim3(J.n), dim3(256), 0, es, J);
-        hipLaunchKernelGGL(k_snp_emit_abs_b, dim3(eblk), dim3(SNP_THREADS), 0, es, g->s[0].d_lanes, J);
-        hipLaunchKernelGGL(k_bitmap_expand_b, dim3(blk), dim3(BM_THREADS), 0, es, J);
-    }
+    emit_train_launch(es, g->s[0].d_lanes, J, train3);
     MSIM_HIP(c, hipGetLastError());
     for (const EmitItem &it : items) {
         if (!train3 && it.apply && (size_t)it.contig < c->contigs.size()) {
@@ -1192,6 +1199,61 @@ int gpu_emit_flush(Ctx *c) {
         it.T->wait_ev = ge; it.T->pending = true;
     }
     return arc;
+}
+
+// test support (msim_dbg_emit_train): the train of gpu_emit_flush over bitmaps and SNP outcomes the caller made, in buffers of
+// its own, synchronous.  Job i: bm[i] (n_words[i] words), start[i], the contig's length len[i], aux8[i] by rank; out: recs[i]
+// (cap_recs[i] records of room; n_recs[i] = the bitmap's set bits) and, train 3 and first[i] given, the tile index of
+// len[i] bytes (n_tiles + 1 entries, n_tiles = ceil(len / tile); tile = 1 << tile_shift as apply.hip has it).
+int gpu_dbg_emit_train(Ctx *c, int n_jobs, const uint64_t *const *bm, const uint32_t *n_words, const uint32_t *start,
+                       const uint64_t *len, const uint8_t *const *aux8, uint32_t d, int train, uint32_t tile_shift,
+                       msim_record *const *recs, const uint64_t *cap_recs, uint64_t *n_recs, int32_t *const *first) {
+    if (n_jobs < 1 || n_jobs > EMIT_G || (train != 3 && train != 6) || !bm || !n_words || !start || !len || !aux8 || !recs ||
+        !cap_recs || !n_recs || tile_shift < 4 || tile_shift > 30)
+        return fail(c, MSIM_ERR_ARG, "msim_dbg_emit_train: bad argument");
+    struct Dev { void *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; ~Dev() { for (void *q : p) if (q) (void)hipFree(q); } };
+    std::vector<Dev> dev((size_t)n_jobs);
+    std::vector<uint64_t> cnt((size_t)n_jobs, 0);
+    unsigned long long *d_err = nullptr;
+    struct ErrFree { unsigned long long *&p; ~ErrFree() { if (p) (void)hipFree(p); } } err_free{d_err};
+    MSIM_HIP(c, hipMalloc(&d_err, sizeof(unsigned long long) * EMIT_G));
+    EmitJobs J;
+    memset(&J, 0, sizeof J);
+    J.n = (uint32_t)n_jobs; J.d = d; J.tile_shift = tile_shift;
+    hipStream_t es = c->emit_stream;
+    for (int i = 0; i < n_jobs; i++) {
+        if (!bm[i] || !n_words[i] || n_words[i] > (1u << 26) || !recs[i] || !aux8[i])
+            return fail(c, MSIM_ERR_ARG, "msim_dbg_emit_train: a job without a bitmap or without room for its records");
+        for (uint32_t q = 0; q < n_words[i]; q++) cnt[(size_t)i] += (uint64_t)__builtin_popcountll(bm[i][q]);
+        n_recs[i] = cnt[(size_t)i];
+        const uint64_t last = (uint64_t)start[i] + 64ull * n_words[i] + (uint64_t)d * cnt[(size_t)i];
+        if (cnt[(size_t)i] > cap_recs[i] || last >= (1ull << 32) || len[i] >= (1ull << 32))
+            return fail(c, MSIM_ERR_ARG, "msim_dbg_emit_train: more records than room, or positions beyond 2^32");
+        const size_t n_tiles = (size_t)((len[i] + (1ull << tile_shift) - 1) >> tile_shift);
+        const size_t sz[5] = {(size_t)n_words[i] * 8, emit_cnt2_words(n_words[i]) * sizeof(uint32_t),
+                              (size_t)(cnt[(size_t)i] + 1) * sizeof(msim_record), (size_t)cnt[(size_t)i] + 1,
+                              (n_tiles + 1) * sizeof(int32_t)};
+        for (int q = 0; q < 5; q++) MSIM_HIP(c, hipMalloc(&dev[(size_t)i].p[q], sz[q]));
+        MSIM_HIP(c, hipMemcpyAsync(dev[(size_t)i].p[0], bm[i], sz[0], hipMemcpyHostToDevice, es));
+        MSIM_HIP(c, hipMemcpyAsync(dev[(size_t)i].p[3], aux8[i], (size_t)cnt[(size_t)i], hipMemcpyHostToDevice, es));
+        MSIM_HIP(c, hipMemsetAsync(dev[(size_t)i].p[4], 0xee, sz[4], es));
+        EmitJob &T = J.j[i];
+        T.bm = static_cast<const uint64_t *>(dev[(size_t)i].p[0]); T.cnt2 = static_cast<uint32_t *>(dev[(size_t)i].p[1]);
+        T.recs = static_cast<msim_record *>(dev[(size_t)i].p[2]); T.aux8 = static_cast<uint8_t *>(dev[(size_t)i].p[3]);
+        T.bmw = n_words[i]; T.bnb = (n_words[i] + BM_THREADS - 1) / BM_THREADS; T.start = start[i]; T.K = (uint32_t)cnt[(size_t)i];
+        if (train == 3 && first && first[i] && n_tiles) {
+            T.first = static_cast<int32_t *>(dev[(size_t)i].p[4]); T.n_tiles = (uint32_t)n_tiles; T.err = d_err + i;
+        }
+    }
+    emit_train_launch(es, nullptr, J, train == 3);
+    MSIM_HIP(c, hipGetLastError());
+    for (int i = 0; i < n_jobs; i++) {
+        MSIM_HIP(c, hipMemcpyAsync(recs[i], dev[(size_t)i].p[2], (size_t)cnt[(size_t)i] * sizeof(msim_record), hipMemcpyDeviceToHost, es));
+        if (J.j[i].first)
+            MSIM_HIP(c, hipMemcpyAsync(first[i], dev[(size_t)i].p[4], ((size_t)J.j[i].n_tiles + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, es));
+    }
+    MSIM_HIP(c, wait_stream(es));
+    return MSIM_OK;
 }
 
 bool gpu_emit_pending(Ctx *c, int contig, bool mark_apply) {

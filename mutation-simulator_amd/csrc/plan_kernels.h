@@ -793,6 +793,7 @@ struct EmitJob {
     // the contig is not applied with its group)
     int32_t *first; unsigned long long *err;
     uint32_t cblk0, n_tiles;
+    uint32_t xblk0;                                          // ... and its first block in the expansion grid (blocks of EX_WORDS)
 };
 struct EmitJobs { EmitJob j[EMIT_G]; uint32_t n, d, total_blk, total_eblk, total_cblk, tile_shift; };   // (tile = 1 << tile_shift bytes)
 __device__ __forceinline__ uint32_t emit_job_of(const EmitJobs &J, uint32_t blk, bool emit_grid) {
@@ -856,32 +857,68 @@ __global__ __launch_bounds__(BM_THREADS) void k_bitmap_expand_b(EmitJobs J) {
 
 // ---- the emission train in THREE launches (round 6; count, scan, outcomes, expansion, tile index, rewrite before):
 //   k_snp_emit_count_b      the SNP outcomes by rank (snp_emit_body) and, in the same grid, the bitmap's popcounts: a workgroup per
-//                           SUPER-block of 16 expansion blocks writes their 16 counts and the super-block's total -- exclusive
-//                           owners, no atomics, nothing to zero
+//                           SUPER-block of EMIT_SUPER expansion blocks, a wave per block, writes their counts and the super-block's
+//                           total -- exclusive owners, no atomics, nothing to zero
 //   k_bitmap_expand_tiles_b the expansion; a workgroup makes its own rank base from the two levels (the totals of the super-blocks in
-//                           front of its own + the counts of the blocks in front of it inside: <= 16 loads per lane for n = 2^30 --
+//                           front of its own + the counts of the blocks in front of it inside: <= 8 loads per lane for n = 2^30 --
 //                           the scan launch is gone) and writes the APPLY tile index while it is there (below)
 //   k_rewrite_snp_b         (apply.hip)
-constexpr int EMIT_SUPER = 16;                            // expansion blocks per super-block (4096 bitmap words)
+// Both kernels are streams over the bitmap and run at the rate their loads are issued at: an expansion block is EX_WORDS = 2048
+// words (16 KB of bitmap, ~1300 records at 1 %), a lane's share of it EX_WPL words in 16-byte loads that all go out before the
+// first use.  (The six-launch train keeps its own blocks of BM_THREADS words and its own layout of cnt2.)
+constexpr int EX_WPL = 8;                                 // bitmap words per lane of an expansion block
+constexpr int EX_WORDS = BM_THREADS * EX_WPL;             // ... and per block
+constexpr int EX_STAGE = 2048;                            // records a block compacts through LDS at a time (8 KB)
+constexpr int EMIT_SUPER = 4;                             // expansion blocks per super-block (8192 bitmap words): one per wave
+static_assert(EMIT_SUPER == BM_THREADS / 64, "bitmap_count_super_body: a wave per block of the super-block");
+static_assert(EX_WPL == 8 && EX_WORDS * 64 / 4 < 65536, "k_bitmap_expand_tiles_b packs two quarter-blocks' prefix sums in one word");
+// the words of scratch the count array of a bitmap of n_words needs, whichever train runs: the six-launch train's blocks of
+// BM_THREADS words (scanned in place, in rounds), or whole super-blocks of expansion blocks and behind them their totals
+__host__ __device__ constexpr size_t emit_cnt2_words(uint32_t n_words) {
+    const size_t six = (size_t)(n_words + BM_THREADS - 1) / BM_THREADS + 24;
+    const size_t n_super = ((size_t)n_words + EX_WORDS * EMIT_SUPER - 1) / (EX_WORDS * EMIT_SUPER);
+    const size_t three = n_super * EMIT_SUPER + n_super;
+    return six > three ? six : three;
+}
+__host__ __device__ constexpr uint32_t emit_blocks(uint32_t n_words) { return (n_words + EX_WORDS - 1) / EX_WORDS; }
+__host__ __device__ constexpr uint32_t emit_supers(uint32_t n_words) { return (emit_blocks(n_words) + EMIT_SUPER - 1) / EMIT_SUPER; }
+
+// N 16-byte loads of a lane: pair q * STRIDE + idx of the words behind `base` (even: the bitmap is a device allocation of its
+// own), all issued before the first use where the whole run lies inside the bitmap; words at or behind n_words read as 0
+template <int N, int STRIDE>
+__device__ __forceinline__ void bitmap_load_pairs(const uint64_t *__restrict__ bm, uint32_t n_words, uint32_t base, uint32_t idx,
+                                                  uint64_t (&w)[2 * N]) {
+    if (base + 2u * N * STRIDE <= n_words) {               // (uniform wherever base is)
+        const ulonglong2 *p = reinterpret_cast<const ulonglong2 *>(bm + base) + idx;
+#pragma unroll
+        for (int q = 0; q < N; q++) {
+            const ulonglong2 v = p[q * STRIDE];
+            w[2 * q] = v.x; w[2 * q + 1] = v.y;
+        }
+    } else {
+#pragma unroll
+        for (int q = 0; q < N; q++) {
+            const uint32_t i = base + (q * STRIDE + idx) * 2;
+            w[2 * q] = i < n_words ? bm[i] : 0ull;
+            w[2 * q + 1] = i + 1 < n_words ? bm[i + 1] : 0ull;
+        }
+    }
+}
 __device__ __forceinline__ void bitmap_count_super_body(const uint64_t *__restrict__ bm, uint32_t n_words,
                                                         uint32_t *__restrict__ block_cnt, uint32_t *__restrict__ super_cnt,
                                                         uint32_t sb, uint32_t *red) {
-    // wave w takes blocks 4q + w of the super-block (q = 0 .. 3): four 64-word loads per lane and block, a wave reduction each
+    // wave w takes block w of the super-block: 16 loads of 16 bytes per lane, 1 KB per wave and load, all issued before the first
+    // popcount; then one wave reduction
     const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t tot = 0;
+    const uint32_t blk = sb * EMIT_SUPER + wave;
+    const uint32_t base = blk * EX_WORDS;
+    uint64_t w[EX_WORDS / 64];                             // (base may lie behind the bitmap: all zero then)
+    bitmap_load_pairs<EX_WORDS / 128, 64>(bm, n_words, base, lane, w);
+    uint32_t c = 0;
 #pragma unroll
-    for (int q = 0; q < EMIT_SUPER / 4; q++) {
-        const uint32_t blk = sb * EMIT_SUPER + q * 4 + wave;
-        uint32_t c = 0;
-#pragma unroll
-        for (int r = 0; r < BM_THREADS / 64; r++) {
-            const uint32_t i = blk * BM_THREADS + r * 64 + lane;
-            c += i < n_words ? (uint32_t)__popcll(bm[i]) : 0u;
-        }
-        for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
-        if (lane == 0) { block_cnt[blk] = c; tot += c; }    // (the count array holds whole super-blocks: plan_gpu.hip sizes it so)
-    }
-    if (lane == 0) red[wave] = tot;
+    for (int r = 0; r < EX_WORDS / 64; r++) c += (uint32_t)__popcll(w[r]);
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if (lane == 0) { block_cnt[blk] = c; red[wave] = c; }   // (the count array holds whole super-blocks: emit_cnt2_words)
     __syncthreads();
     if (threadIdx.x == 0) super_cnt[sb] = red[0] + red[1] + red[2] + red[3];
 }
@@ -911,44 +948,97 @@ __device__ __forceinline__ void expand_tile_borders(uint64_t w, uint32_t i, uint
         first[t] = (int32_t)(rank + below) - 1;
     }
 }
+// A block's words are laid out for the loads: load q of lane t brings words q * 2 * BM_THREADS + 2 t and + 2 t + 1 of the block, so a
+// wave's load is 1 KB contiguous.  Ranks inside the block: the four loads' lane counts are scanned as two words of two 16-bit
+// fields each (a field sums at most 512 words' bits = 32768: no carry), one barrier.  The records then go through LDS: every lane
+// drops the block-relative value of each of its bits at that bit's rank in the block, and lane t writes records t, t + 256, ... --
+// 1 KB contiguous per wave, aux8 read the same way -- instead of one 16-byte store per bit from a loop whose trip count differs
+// from lane to lane.  The staging buffer takes EX_STAGE records; a block with more (up to 64 per word) goes round again.
 __global__ __launch_bounds__(BM_THREADS) void k_bitmap_expand_tiles_b(EmitJobs J) {
-    __shared__ uint32_t wsum[BM_THREADS / 64];
+    __shared__ uint32_t stage[EX_STAGE];
+    __shared__ uint32_t wsum[2][BM_THREADS / 64];
     __shared__ uint32_t bsum[BM_THREADS / 64];
-    const EmitJob &T = J.j[emit_job_of(J, blockIdx.x, false)];
-    const uint32_t blk = blockIdx.x - T.blk0;
-    const uint32_t sb = blk / EMIT_SUPER, n_super = (T.bnb + EMIT_SUPER - 1) / EMIT_SUPER;
+    uint32_t k = 0;
+    for (uint32_t q = 1; q < J.n; q++) if (J.j[q].xblk0 <= blockIdx.x) k = q;
+    const EmitJob &T = J.j[k];
+    const uint32_t blk = blockIdx.x - T.xblk0;
+    const uint32_t sb = blk / EMIT_SUPER, n_super = emit_supers(T.bmw);
     const uint32_t *super_cnt = T.cnt2 + (size_t)n_super * EMIT_SUPER;
+    const uint32_t word0 = blk * EX_WORDS;
+    uint64_t w[EX_WPL];
+    bitmap_load_pairs<EX_WPL / 2, BM_THREADS>(T.bm, T.bmw, word0, threadIdx.x, w);
     // the block's rank base: super-block totals in front of its super-block + block counts in front of it inside
     uint32_t v = 0;
     for (uint32_t j = threadIdx.x; j < sb; j += BM_THREADS) v += super_cnt[j];
     if (threadIdx.x < blk % EMIT_SUPER) v += T.cnt2[sb * EMIT_SUPER + threadIdx.x];
     for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
     if ((threadIdx.x & 63) == 0) bsum[threadIdx.x >> 6] = v;
-    const uint32_t i = blk * BM_THREADS + threadIdx.x;
-    uint64_t w = i < T.bmw ? T.bm[i] : 0;
-    const uint32_t c = (uint32_t)__popcll(w);
-    uint32_t incl = c;
+    uint32_t c[EX_WPL];
+#pragma unroll
+    for (int q = 0; q < EX_WPL; q++) c[q] = (uint32_t)__popcll(w[q]);
+    static_assert(EX_WPL == 8, "two packed scans of two loads each");
+    const uint32_t mine0 = (c[0] + c[1]) | ((c[2] + c[3]) << 16), mine1 = (c[4] + c[5]) | ((c[6] + c[7]) << 16);
+    uint32_t incl0 = mine0, incl1 = mine1;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t t = __shfl_up(incl, o, 64);
-        if ((threadIdx.x & 63) >= (unsigned)o) incl += t;
+        const uint32_t t0 = __shfl_up(incl0, o, 64), t1 = __shfl_up(incl1, o, 64);
+        if ((threadIdx.x & 63) >= (unsigned)o) { incl0 += t0; incl1 += t1; }
     }
-    if ((threadIdx.x & 63) == 63) wsum[threadIdx.x >> 6] = incl;
+    if ((threadIdx.x & 63) == 63) { wsum[0][threadIdx.x >> 6] = incl0; wsum[1][threadIdx.x >> 6] = incl1; }
     __syncthreads();
-    for (uint32_t q = 0; q < (threadIdx.x >> 6); q++) incl += wsum[q];
-    uint32_t rank = bsum[0] + bsum[1] + bsum[2] + bsum[3] + incl - c;
+    uint32_t tot0 = 0, tot1 = 0;
+#pragma unroll
+    for (uint32_t q = 0; q < BM_THREADS / 64; q++) {
+        if (q < (threadIdx.x >> 6)) { incl0 += wsum[0][q]; incl1 += wsum[1][q]; }
+        tot0 += wsum[0][q]; tot1 += wsum[1][q];
+    }
+    const uint32_t ex0 = incl0 - mine0, ex1 = incl1 - mine1;       // (field by field: an inclusive sum is never below its own term)
+    const uint32_t seg1 = tot0 & 0xffffu, seg2 = seg1 + (tot0 >> 16), seg3 = seg2 + (tot1 & 0xffffu), n_here = seg3 + (tot1 >> 16);
+    uint32_t lr[EX_WPL];                                   // rank inside the block of the first bit of each of the lane's words
+    lr[0] = ex0 & 0xffffu;          lr[1] = lr[0] + c[0];
+    lr[2] = seg1 + (ex0 >> 16);     lr[3] = lr[2] + c[2];
+    lr[4] = seg2 + (ex1 & 0xffffu); lr[5] = lr[4] + c[4];
+    lr[6] = seg3 + (ex1 >> 16);     lr[7] = lr[6] + c[6];
+    const uint32_t rank0 = bsum[0] + bsum[1] + bsum[2] + bsum[3];
     if (T.first) {
         if (blk == 0 && threadIdx.x == 0) *T.err = ~0ull;  // the contig's KeyError word: none so far (the rewrite kernel follows)
-        if (i < T.bmw) expand_tile_borders(w, i, T.bmw, T.start, J.d, rank, c, J.tile_shift, T.n_tiles, T.first);
+#pragma unroll
+        for (int q = 0; q < EX_WPL; q++) {
+            const uint32_t i = word0 + ((q >> 1) * BM_THREADS + threadIdx.x) * 2 + (q & 1);
+            if (i < T.bmw) expand_tile_borders(w[q], i, T.bmw, T.start, J.d, rank0 + lr[q], c[q], J.tile_shift, T.n_tiles, T.first);
+        }
     }
-    while (w) {
-        const uint32_t bit = (uint32_t)__builtin_ctzll(w);
-        w &= w - 1;
-        const uint32_t pos = T.start + (i * 64 + bit) + J.d * rank;
-        msim_record r;
-        r.pos = pos; r.stop = pos; r.extra = 0; r.type = MSIM_SN; r.aux = T.aux8[rank]; r.rsv = 0;
-        T.recs[rank] = r;
-        rank++;
+    for (uint32_t s0 = 0; s0 < n_here; s0 += EX_STAGE) {   // (uniform)
+        if (s0) __syncthreads();                           // the last round's records have left the staging buffer
+        const uint32_t n_round = min(n_here - s0, (uint32_t)EX_STAGE);
+        uint32_t aux[EX_STAGE / BM_THREADS];               // the outcomes of this lane's records of the round: on their way meanwhile
+#pragma unroll
+        for (int u = 0; u < EX_STAGE / BM_THREADS; u++) {
+            const uint32_t s = u * BM_THREADS + threadIdx.x;
+            aux[u] = (uint32_t)T.aux8[rank0 + s0 + min(s, n_round - 1)];   // (no branch: the loads go out together; n_round >= 1)
+        }
+#pragma unroll
+        for (int q = 0; q < EX_WPL; q++) {
+            if (!c[q] || lr[q] >= s0 + EX_STAGE || lr[q] + c[q] <= s0) continue;
+            const uint32_t val0 = (((q >> 1) * BM_THREADS + threadIdx.x) * 2 + (q & 1)) * 64;
+            uint64_t x = w[q];
+            for (uint32_t r = lr[q]; x && r < s0 + EX_STAGE; r++) {
+                const uint32_t bit = (uint32_t)__builtin_ctzll(x);
+                x &= x - 1;
+                if (r >= s0) stage[r - s0] = val0 + bit;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < EX_STAGE / BM_THREADS; u++) {
+            const uint32_t s = u * BM_THREADS + threadIdx.x;
+            if (s >= n_round) break;
+            const uint32_t rank = rank0 + s0 + s;
+            const uint32_t pos = T.start + (word0 * 64 + stage[s]) + J.d * rank;
+            // pos, stop, extra = 0, then type, aux, rsv = 0 in the last word: one 16-byte store (a table is a device allocation)
+            static_assert(sizeof(msim_record) == 16 && offsetof(msim_record, type) == 12 && offsetof(msim_record, aux) == 13, "");
+            *reinterpret_cast<uint4 *>(T.recs + rank) = make_uint4(pos, pos, 0u, (uint32_t)MSIM_SN | (aux[u] << 8));
+        }
     }
 }
 
@@ -1303,7 +1393,7 @@ __global__ __launch_bounds__(SNP_THREADS) void k_snp_emit_count_b(const SnpLane 
     uint32_t k = 0;
     for (uint32_t q = 1; q < J.n; q++) if (J.j[q].cblk0 <= cb) k = q;
     const EmitJob &T = J.j[k];
-    const uint32_t n_super = (T.bnb + EMIT_SUPER - 1) / EMIT_SUPER;
+    const uint32_t n_super = emit_supers(T.bmw);
     bitmap_count_super_body(T.bm, T.bmw, T.cnt2, T.cnt2 + (size_t)n_super * EMIT_SUPER, cb - T.cblk0, red);
 }
 

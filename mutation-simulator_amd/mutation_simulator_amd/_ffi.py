@@ -540,6 +540,34 @@ class Engine:
         ids = (C.c_int * len(contigs))(*[int(i) for i in contigs])
         self._check(fn(self.h, ids, len(contigs)))
 
+    def emit_train(self, jobs, d: int = 1, train: int = 3):
+        """The SNP sampler's emission train (count, expansion: one group's launches, ``train`` = 3 or 6) over the caller's
+        bitmaps.  ``jobs``: up to 8 of (bitmap as uint64 words, start, contig length, aux8 = SNP outcomes by rank, at least
+        one per set bit).  Returns (tile, [(records, first)]): each job's record table (RECORD_DTYPE) and, for train 3, its
+        APPLY tile index (int32, ceil(length / tile) + 1 entries; None for train 6)."""
+        fn = self.lib.msim_dbg_emit_train
+        fn.restype = C.c_int
+        fn.argtypes = [_VP, C.c_int, _VP, _VP, _VP, _VP, _VP, C.c_uint32, C.c_int, _VP, _VP, _VP, _VP]
+        self.lib.msim_dbg_apply_tile.restype = C.c_uint32
+        tile = int(self.lib.msim_dbg_apply_tile())
+        n = len(jobs)
+        bms = [np.ascontiguousarray(j[0], dtype=np.uint64) for j in jobs]
+        auxs = [np.ascontiguousarray(j[3], dtype=np.uint8) for j in jobs]
+        caps = [max(1, int(a.shape[0])) for a in auxs]
+        auxs = [a if a.shape[0] else np.zeros(1, dtype=np.uint8) for a in auxs]
+        recs = [np.zeros(cap, dtype=RECORD_DTYPE) for cap in caps]
+        ptrs = lambda arrs: (C.c_void_p * n)(*[a.ctypes.data for a in arrs])
+        n_words = np.array([b.shape[0] for b in bms], dtype=np.uint32)
+        start = np.array([int(j[1]) for j in jobs], dtype=np.uint32)
+        length = np.array([int(j[2]) for j in jobs], dtype=np.uint64)
+        cap_a = np.array(caps, dtype=np.uint64)
+        n_recs = np.zeros(n, dtype=np.uint64)
+        n_tiles = [(int(j[2]) + tile - 1) // tile for j in jobs]
+        firsts = [np.zeros(nt + 1, dtype=np.int32) for nt in n_tiles] if train == 3 else None
+        self._check(fn(self.h, n, ptrs(bms), _ptr(n_words), _ptr(start), _ptr(length), ptrs(auxs), int(d), int(train),
+                       ptrs(recs), _ptr(cap_a), _ptr(n_recs), ptrs(firsts) if firsts else None))
+        return tile, [(recs[i][:int(n_recs[i])], firsts[i] if firsts and n_tiles[i] else None) for i in range(n)]
+
     def key_error(self, contig: int):
         """(base, position) of the KeyError the contig's APPLY recorded, or None."""
         base, pos = C.c_uint8(), C.c_uint64()
