@@ -193,6 +193,19 @@ inline uint32_t chain_lg_rows(const ChainClasses &cc) { return cc.n <= 1 ? 0u : 
 constexpr uint32_t chain_value_bits(uint32_t lg_rows) { return lg_rows <= 2 ? 24u : 23u; }
 bool chain_classes(const msim_range &r, ChainClasses &cc);          // false: some length does not fit the table entry
 void accept_tables_host(const ChainClasses &cc, const uint32_t *words, size_t n_words, uint32_t *T);   // test support
+// test support (msim_dbg_accept_tables*): classes given as (shift, width) pairs -> cc, if they are what chain_classes can make:
+// 1..8 classes, shift == 32 - bit_length(width), 1 <= width < 2^chain_value_bits(lg_rows)
+inline bool dbg_chain_classes(const uint32_t *sh, const uint32_t *width, uint32_t n, ChainClasses &cc) {
+    cc = ChainClasses{};
+    if (!sh || !width || n < 1 || n > 8) return false;
+    cc.n = n;
+    const uint32_t vbits = chain_value_bits(chain_lg_rows(cc));
+    for (uint32_t k = 0; k < n; k++) {
+        if (width[k] < 1 || width[k] >= (1u << vbits) || sh[k] != (uint32_t)__builtin_clz(width[k])) return false;
+        cc.sh[k] = sh[k]; cc.width[k] = width[k];
+    }
+    return true;
+}
 // The walk is resumable, so that the host can start on the first piece of the table while the rest is still being
 // copied: run() walks candidates [j, n) while the next position stays below w_lim (positions [0, w_lim) are valid).
 // It writes stops only; the kept count and the length delta are summed where the stops are consumed (device:

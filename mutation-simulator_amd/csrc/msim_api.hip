@@ -1383,6 +1383,66 @@ int msim_dbg_emit_train(msim_ctx *p, int n_jobs, const uint64_t *const *bitmaps,
                               n_recs, first);
 }
 
+// The device halves of the SV-mix and host-chain engines over tables the caller made (plan_gpu.hip: gpu_dbg_*): the engines' own
+// launch helpers in buffers of the call's own.  Synchronous; no contig, no stream session.  Each refuses with MSIM_ERR_ARG,
+// before anything is launched, whatever the planners cannot produce.
+//   msim_dbg_candidates: the candidate front.  bitmap given: one range (bitmap, start, d, sets[0]) through k_bitmap_count,
+//     k_scan_u32, k_bitmap_expand_cand; bitmap NULL: K candidates over rt[n_draw] (four uint32: rec_base, clip, set_id, 0) and
+//     sets[n_sets] (80 bytes: thr[8] u64, n u32, type[8] u8) through k_types_multi.  Then k_nsn_count, k_scan_u32, k_nsn_scatter.
+//     np_words: raw (untempered) NumPy-stream words, two per candidate.
+//   msim_dbg_accept_tables: k_accept_tables at p0 and k_accept_tables_ps behind k_set_pos(p0) over raw CPython-stream words;
+//     (n + 1) << lg_rows entries each.  msim_dbg_accept_tables_host: the host's tables (accept_tables_host) over TEMPERED words,
+//     same checks, no context.
+//   msim_dbg_mixed_emit: k_stop_scatter, k_link_scatter, k_blk_reduce, k_scan_max_u32, k_keep_flags, k_scan4, k_emit_records,
+//     k_pool_fill over candidates, chain verdicts and (optionally) a range table; block[] from msim_set_params.
+int msim_dbg_candidates(msim_ctx *p, const uint64_t *bitmap, uint32_t n_words, uint32_t start, uint32_t d, uint32_t K,
+                        const void *rt, uint32_t n_draw, const void *sets, uint32_t n_sets, const uint32_t *np_words, uint64_t n_np_words,
+                        uint32_t all, uint32_t *cand_pos, uint8_t *cand_type, uint32_t *nsn_pos, uint8_t *nsn_type, uint32_t *nsn_rank,
+                        uint64_t cap, uint32_t *k_out, uint32_t *n_nsn) {
+    CTX_FLUSHED(c, p)
+    if (!c) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    int rc = drain(c);
+    if (rc) return rc;
+    return gpu_dbg_candidates(c, bitmap, n_words, start, d, K, rt, n_draw,
+                              sets, n_sets, np_words, n_np_words, all, cand_pos, cand_type, nsn_pos,
+                              nsn_type, nsn_rank, cap, k_out, n_nsn);
+}
+
+int msim_dbg_accept_tables(msim_ctx *p, const uint32_t *raw_words, uint64_t n_words, uint64_t p0, uint32_t n, const uint32_t *shift,
+                           const uint32_t *width, uint32_t n_classes, uint32_t *T, uint32_t *T_ps) {
+    CTX_FLUSHED(c, p)
+    if (!c) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    int rc = drain(c);
+    if (rc) return rc;
+    return gpu_dbg_accept_tables(c, raw_words, n_words, p0, n, shift, width, n_classes, T, T_ps);
+}
+
+int msim_dbg_accept_tables_host(const uint32_t *tempered, uint32_t n, const uint32_t *shift, const uint32_t *width, uint32_t n_classes,
+                                uint32_t *T) {
+    ChainClasses cc;
+    if (!T || (n && !tempered) || n > (1u << 26) || !dbg_chain_classes(shift, width, n_classes, cc)) return MSIM_ERR_ARG;
+    memset(T, 0, (((size_t)n + 1) << chain_lg_rows(cc)) * 4);
+    accept_tables_host(cc, tempered, n, T);
+    return MSIM_OK;
+}
+
+int msim_dbg_mixed_emit(msim_ctx *p, uint64_t L, uint32_t k, const uint32_t *cand_pos, const uint8_t *cand_type, uint32_t n_ch,
+                        const uint32_t *ch_rank, const uint32_t *ch_stop, const uint32_t *ch_extra, const uint8_t *ch_aux, uint32_t n_draw,
+                        const void *rt, const uint32_t *visit_from, uint32_t sn_chained, const uint32_t *np_words, uint64_t n_np_words,
+                        msim_record *recs, uint32_t *rec_off, uint32_t *sn_index, uint8_t *pool, uint64_t cap_pool, uint32_t *counts,
+                        int64_t *len_delta) {
+    CTX_FLUSHED(c, p)
+    if (!c) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    int rc = drain(c);
+    if (rc) return rc;
+    return gpu_dbg_mixed_emit(c, L, k, cand_pos, cand_type, n_ch, ch_rank, ch_stop, ch_extra, ch_aux, n_draw,
+                              rt, visit_from, sn_chained, np_words, n_np_words, recs, rec_off, sn_index,
+                              pool, cap_pool, counts, len_delta);
+}
+
 // test support (tests/test_ahead_moments.py, CPU tier): the moments the anchored windows are laid out from; needs no context
 int msim_dbg_stream_moments(uint64_t n, uint64_t k, uint64_t K, uint64_t ti_lim, double out[4]) {
     if (!out || !n || k >= n) return MSIM_ERR_ARG;

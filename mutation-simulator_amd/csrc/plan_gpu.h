@@ -40,6 +40,20 @@ bool gpu_emit_pending(Ctx *c, int contig, bool mark_apply);
 int gpu_dbg_emit_train(Ctx *c, int n_jobs, const uint64_t *const *bm, const uint32_t *n_words, const uint32_t *start,
                        const uint64_t *len, const uint8_t *const *aux8, uint32_t d, int train, uint32_t tile_shift,
                        msim_record *const *recs, const uint64_t *cap_recs, uint64_t *n_recs, int32_t *const *first);
+// test support (msim_dbg_candidates / msim_dbg_accept_tables / msim_dbg_mixed_emit): the device halves of the SV-mix and host-chain
+// engines -- the engines' own launch helpers -- over tables the caller made (plan_gpu.hip);
+// rt: MixRangeDev[n_draw], sets: TypeTable[n_sets] (plan_kernels.h)
+int gpu_dbg_candidates(Ctx *c, const uint64_t *bm, uint32_t n_words, uint32_t start, uint32_t d, uint32_t K, const void *rt,
+                       uint32_t n_draw, const void *sets, uint32_t n_sets, const uint32_t *np_raw, uint64_t n_np, uint32_t all,
+                       uint32_t *cand_pos, uint8_t *cand_type, uint32_t *nsn_pos, uint8_t *nsn_type, uint32_t *nsn_rank, uint64_t cap,
+                       uint32_t *k_out, uint32_t *n_nsn);
+int gpu_dbg_accept_tables(Ctx *c, const uint32_t *raw, uint64_t n_words, uint64_t p0, uint32_t n, const uint32_t *sh,
+                          const uint32_t *width, uint32_t n_classes, uint32_t *T, uint32_t *T_ps);
+int gpu_dbg_mixed_emit(Ctx *c, uint64_t L, uint32_t k, const uint32_t *cand_pos, const uint8_t *cand_type, uint32_t n_ch,
+                       const uint32_t *ch_rank, const uint32_t *ch_stop, const uint32_t *ch_extra, const uint8_t *ch_aux,
+                       uint32_t n_draw, const void *rt, const uint32_t *visit_from, uint32_t sn_chained, const uint32_t *np_raw,
+                       uint64_t n_np, msim_record *recs, uint32_t *rec_off, uint32_t *sn_index, uint8_t *pool, uint64_t cap_pool,
+                       uint32_t *counts, int64_t *len_delta);
 int gpu_plan_force_overflow(Ctx *c, GpuPlan *g);          // test support
 void gpu_plan_abandon(GpuPlan *g);                        // a device engine failed mid-contig: the session is over
 // before a contig goes to a device engine: room for its windows in the current session's jump-table span, re-basing the session

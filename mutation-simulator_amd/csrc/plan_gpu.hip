@@ -1644,6 +1644,89 @@ static int flush_deferred_apply_behind(Ctx *c, hipEvent_t last_copy) {
 static inline size_t mixed_cnt_words(uint32_t nbk) { return ((size_t)5 * (nbk + 2) + 1) & ~(size_t)1; }
 static inline size_t mixed_cnt_bytes(uint32_t nbk) { return mixed_cnt_words(nbk) * 4 + (size_t)(nbk + 2) * 8; }
 
+// ---- The launches of the SV-mix and host-chain engines' device halves, each group in one place: the engines below and the
+// test hooks (gpu_dbg_candidates, gpu_dbg_accept_tables, gpu_dbg_mixed_emit) call the same functions, so a hook runs the
+// product's grids and arguments.  Nothing here waits or checks; the caller asks hipGetLastError.
+// bitmap -> candidate positions and types of one range (cnt2: (bmw + 255) / 256 + 1 words)
+static void cand_front_launch(hipStream_t s, const uint64_t *bm, uint32_t bmw, uint32_t *cnt2, uint32_t start, uint32_t d,
+                              const uint32_t *np_raw, unsigned long long np_base, const TypeTable &tt, uint32_t *cand_pos,
+                              uint8_t *cand_type) {
+    const uint32_t bnb = (bmw + BM_THREADS - 1) / BM_THREADS;
+    hipLaunchKernelGGL(k_bitmap_count, dim3(bnb), dim3(BM_THREADS), 0, s, bm, bmw, cnt2);
+    hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, s, cnt2, bnb);
+    hipLaunchKernelGGL(k_bitmap_expand_cand, dim3(bnb), dim3(BM_THREADS), 0, s, bm, bmw, cnt2, start, d, np_raw, np_base, tt,
+                       cand_pos, cand_type);
+}
+// candidate types by ordinal alone (host-chain engine: no positions yet)
+static void types_multi_launch(hipStream_t s, const uint32_t *np_raw, unsigned long long np_base, uint32_t K, const MixRangeDev *rt,
+                               uint32_t n_draw, const TypeTable *sets, uint8_t *cand_type) {
+    const uint32_t nbk = (K + CB_BLOCK - 1) / CB_BLOCK;
+    hipLaunchKernelGGL(k_types_multi, dim3(nbk), dim3(CB_THREADS), 0, s, np_raw, np_base, K, rt, n_draw, sets, cand_type);
+}
+// the chain's candidates compacted (cnt: nbk + 1 words; cand_pos / nsn_pos may be null: k_nsn_scatter); their number -> ps->n_nsn
+static void nsn_compact_launch(hipStream_t s, const uint32_t *cand_pos, const uint8_t *cand_type, uint32_t k, uint32_t *cnt,
+                               uint32_t *nsn_pos, uint8_t *nsn_type, uint32_t *nsn_rank, PlanState *ps, bool all) {
+    const uint32_t nbk = (k + CB_BLOCK - 1) / CB_BLOCK;
+    hipLaunchKernelGGL(k_nsn_count, dim3(nbk), dim3(CB_THREADS), 0, s, cand_type, k, cnt, all ? 1u : 0u);
+    hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, s, cnt, nbk);
+    hipLaunchKernelGGL(k_nsn_scatter, dim3(nbk), dim3(CB_THREADS), 0, s, cand_pos, cand_type, k, cnt, nbk, nsn_pos, nsn_type, nsn_rank,
+                       ps, all ? 1u : 0u);
+}
+// accept tables over words [p0, p0 + n) resp. from ps->pos on: (n + 1) << lg entries
+static void accept_tables_launch(hipStream_t s, const uint32_t *raw, unsigned long long p0, uint32_t n, const ChainClasses &cc,
+                                 uint32_t lg, uint32_t *T) {
+    const size_t n_slots = (size_t)(n + 1) << lg;
+    hipLaunchKernelGGL(k_accept_tables, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, s, raw, p0, n, cc, lg, T);
+}
+static void accept_tables_ps_launch(hipStream_t s, const uint32_t *raw, const PlanState *ps, uint32_t n, const ChainClasses &cc,
+                                    uint32_t lg, uint32_t *T) {
+    const size_t n_slots = ((size_t)n + 1) << lg;
+    hipLaunchKernelGGL(k_accept_tables_ps, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, s, raw, ps, n, cc, lg, T);
+}
+// what the host chain decided, from chain order back to candidate order
+static void stop_scatter_launch(hipStream_t s, const uint32_t *nsn_rank, const uint32_t *nsn_stop, uint32_t n, uint32_t *cand_stop) {
+    hipLaunchKernelGGL(k_stop_scatter, dim3((n + 255) / 256), dim3(256), 0, s, nsn_rank, nsn_stop, n, cand_stop);
+}
+static void link_scatter_launch(hipStream_t s, const uint32_t *nsn_rank, const uint32_t *nsn_extra, const uint8_t *nsn_aux, uint32_t n,
+                                uint32_t *cand_extra, uint8_t *cand_aux) {
+    hipLaunchKernelGGL(k_link_scatter, dim3((n + 255) / 256), dim3(256), 0, s, nsn_rank, nsn_extra, nsn_aux, n, cand_extra, cand_aux);
+}
+// The candidate tables steps 3 and 4 of an SV-mix plan work on.  cnt: mixed_cnt_bytes(nbk); cand_extra / cand_aux: contigs with
+// translocations, else null; rt / visit_from: several drawing ranges, else null (k_keep_flags).
+struct MixedTables {
+    uint32_t k;
+    const uint32_t *cand_pos; uint8_t *cand_type; const uint32_t *cand_stop; const uint32_t *cand_extra; const uint8_t *cand_aux;
+    uint32_t *cnt, *sn_index;
+    const MixRangeDev *rt; uint32_t n_draw; const uint32_t *visit_from; bool sn_chained;
+    uint32_t nbk() const { return (k + CB_BLOCK - 1) / CB_BLOCK; }
+    uint32_t *bmax() const { return cnt + (nbk() + 2); }
+    uint32_t *cnt_keep() const { return cnt + 2 * (nbk() + 2); }
+    uint32_t *cnt_sn() const { return cnt + 3 * (nbk() + 2); }
+    uint32_t *cnt_ins() const { return cnt + 4 * (nbk() + 2); }
+    long long *blk_delta() const { return reinterpret_cast<long long *>(cnt + mixed_cnt_words(nbk())); }   // (8-byte aligned: see mixed_cnt_bytes)
+};
+// keep flags and counts; n_rec, n_sn, pool_len, len_delta -> *ps
+static void keep_flags_launch(hipStream_t s, const msim_params &P, const MixedTables &M, PlanState *ps) {
+    const uint32_t nbk = M.nbk();
+    BlockTable bt{};
+    for (int t = 1; t <= 7; t++) bt.p1[t] = (uint32_t)std::min<int64_t>(P.block[t] + 1, 0xffffffffll);
+    hipLaunchKernelGGL(k_blk_reduce, dim3(nbk), dim3(CB_THREADS), 0, s, M.cand_pos, M.cand_type, M.cand_stop, M.k, bt, M.bmax(),
+                       M.rt, M.n_draw);
+    hipLaunchKernelGGL(k_scan_max_u32, dim3(1), dim3(1024), 0, s, M.bmax(), nbk);
+    hipLaunchKernelGGL(k_keep_flags, dim3(nbk), dim3(CB_THREADS), 0, s, M.cand_pos, M.cand_type, M.cand_stop, M.k, bt,
+                       M.bmax(), M.cnt_keep(), M.cnt_sn(), M.cnt_ins(), M.blk_delta(), M.rt, M.n_draw, M.visit_from,
+                       M.sn_chained ? 1u : 0u, M.cand_extra, M.cand_aux);
+    hipLaunchKernelGGL(k_scan4, dim3(4), dim3(1024), 0, s, M.cnt_keep(), M.cnt_sn(), M.cnt_ins(), M.blk_delta(), nbk, ps);
+}
+// records with their output offsets, SNP ordinals, insert pool (pool: padded to whole dwords, k_pool_fill)
+static void emit_records_launch(hipStream_t s, const MixedTables &M, msim_record *recs, uint32_t *rec_off, const uint32_t *np_raw,
+                                unsigned long long np_base, uint32_t pool_len, uint8_t *pool) {
+    hipLaunchKernelGGL(k_emit_records, dim3(M.nbk()), dim3(CB_THREADS), 0, s, M.cand_pos, M.cand_type, M.cand_stop, M.k,
+                       M.cnt_keep(), M.cnt_sn(), M.cnt_ins(), M.blk_delta(), recs, M.sn_index, rec_off, M.cand_extra, M.cand_aux);
+    if (pool_len)
+        hipLaunchKernelGGL(k_pool_fill, dim3((pool_len / 4 + 256) / 256), dim3(256), 0, s, np_raw, np_base, pool_len, pool);
+}
+
 // Steps 3 and 4 of an SV-mix plan, shared by the single-range engine and the host-chain engine: the stops of the chain's
 // candidates are in M.cand_stop -> keep flags and counts -> records, insert pool, SNP draws.  p_s: where the SNP draws of
 // __mutate_sequence start in the CPython stream.  rt / visit_from / sn_chained: see k_keep_flags (nullptr for one range).
@@ -1654,21 +1737,11 @@ static int mixed_emit(Ctx *c, GpuPlan *g, Contig &ct, MixedSet &M, uint32_t k, u
     const msim_params &P = c->params;
     GpuStream &py = g->s[0], &np = g->s[1];
     int rc;
-    const uint32_t nbk = (k + CB_BLOCK - 1) / CB_BLOCK;
-    uint32_t *bmax = M.cnt + (nbk + 2), *cnt_keep = M.cnt + 2 * (nbk + 2), *cnt_sn = M.cnt + 3 * (nbk + 2),
-             *cnt_ins = M.cnt + 4 * (nbk + 2);
-    long long *blk_delta = reinterpret_cast<long long *>(M.cnt + mixed_cnt_words(nbk));   // (8-byte aligned: see mixed_cnt_bytes)
+    const MixedTables mt{k, M.cand_pos, M.cand_type, M.cand_stop, c_extra, c_aux, M.cnt, M.sn_index, rt, n_draw, visit_from, sn_chained};
     hipLaunchKernelGGL(k_set_pos, dim3(1), dim3(1), 0, c->stream, g->d_ps, (unsigned long long)p_s);
 
     // ---- 3. keep flags, counts
-    BlockTable bt{};
-    for (int t = 1; t <= 7; t++) bt.p1[t] = (uint32_t)std::min<int64_t>(P.block[t] + 1, 0xffffffffll);
-    hipLaunchKernelGGL(k_blk_reduce, dim3(nbk), dim3(CB_THREADS), 0, c->stream, M.cand_pos, M.cand_type, M.cand_stop, k, bt, bmax,
-                       rt, n_draw);
-    hipLaunchKernelGGL(k_scan_max_u32, dim3(1), dim3(1024), 0, c->stream, bmax, nbk);
-    hipLaunchKernelGGL(k_keep_flags, dim3(nbk), dim3(CB_THREADS), 0, c->stream, M.cand_pos, M.cand_type, M.cand_stop, k, bt,
-                       bmax, cnt_keep, cnt_sn, cnt_ins, blk_delta, rt, n_draw, visit_from, sn_chained ? 1u : 0u, c_extra, c_aux);
-    hipLaunchKernelGGL(k_scan4, dim3(4), dim3(1024), 0, c->stream, cnt_keep, cnt_sn, cnt_ins, blk_delta, nbk, g->d_ps);
+    keep_flags_launch(c->stream, P, mt, g->d_ps);
     MSIM_HIP(c, hipGetLastError());
     PlanState h;
     if ((rc = mixed_poll(c, g, h))) return rc;
@@ -1698,11 +1771,7 @@ static int mixed_emit(Ctx *c, GpuPlan *g, Contig &ct, MixedSet &M, uint32_t k, u
     MSIM_HIP(c, hipEventRecord(ce, c->stream));
     MSIM_HIP(c, hipStreamWaitEvent(c->emit_stream, ce, 0));
     if (!c->chain_only) {
-        hipLaunchKernelGGL(k_emit_records, dim3(nbk), dim3(CB_THREADS), 0, c->emit_stream, M.cand_pos, M.cand_type, M.cand_stop, k,
-                           cnt_keep, cnt_sn, cnt_ins, blk_delta, ct.d_recs, M.sn_index, ct.d_off, c_extra, c_aux);
-        if (pool_len)
-            hipLaunchKernelGGL(k_pool_fill, dim3((pool_len / 4 + 256) / 256), dim3(256), 0, c->emit_stream, np.d_raw,
-                               (unsigned long long)np.pos, pool_len, ct.d_pool + PAD);
+        emit_records_launch(c->emit_stream, mt, ct.d_recs, ct.d_off, np.d_raw, (unsigned long long)np.pos, pool_len, ct.d_pool + PAD);
         MSIM_HIP(c, hipGetLastError());
     }
     np.pos += pool_len;
@@ -1817,16 +1886,9 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
     TypeTable tt{};
     tt.n = (uint32_t)r.n_types;
     for (int j = 0; j < r.n_types; j++) { tt.thr[j] = r.cdf_thr[j]; tt.type[j] = (uint8_t)r.types[j]; }
-    hipLaunchKernelGGL(k_bitmap_count, dim3(sl.bnb), dim3(BM_THREADS), 0, c->stream,
-                       reinterpret_cast<const uint64_t *>(S.bitmap), sl.bmw, S.cnt2);
-    hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, S.cnt2, sl.bnb);
-    hipLaunchKernelGGL(k_bitmap_expand_cand, dim3(sl.bnb), dim3(BM_THREADS), 0, c->stream,
-                       reinterpret_cast<const uint64_t *>(S.bitmap), sl.bmw, S.cnt2, (uint32_t)r.start, (uint32_t)d,
-                       np.d_raw, (unsigned long long)np_base, tt, M.cand_pos, M.cand_type);
-    hipLaunchKernelGGL(k_nsn_count, dim3(nbk), dim3(CB_THREADS), 0, c->stream, M.cand_type, k, cnt_nsn, 0u);
-    hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, cnt_nsn, nbk);
-    hipLaunchKernelGGL(k_nsn_scatter, dim3(nbk), dim3(CB_THREADS), 0, c->stream, M.cand_pos, M.cand_type, k, cnt_nsn, nbk,
-                       M.nsn_pos, M.nsn_type, M.nsn_rank, g->d_ps, 0u);
+    cand_front_launch(c->stream, reinterpret_cast<const uint64_t *>(S.bitmap), sl.bmw, S.cnt2, (uint32_t)r.start, (uint32_t)d, np.d_raw,
+                      (unsigned long long)np_base, tt, M.cand_pos, M.cand_type);
+    nsn_compact_launch(c->stream, M.cand_pos, M.cand_type, k, cnt_nsn, M.nsn_pos, M.nsn_type, M.nsn_rank, g->d_ps, false);
     MSIM_HIP(c, hipGetLastError());
     S.pending = false;                                     // consumed on the plan stream itself
     // The host walks the non-SNP candidates.  Their copy starts at once, beside the plan stream and before their number
@@ -1887,9 +1949,7 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
     const auto tq0 = std::chrono::steady_clock::now();
     rc = mixed_poll(c, g, h, [&]() -> int {
         if (!early) return MSIM_OK;
-        const size_t n_slots = (size_t)(Wb_hi + 1) << lg;
-        hipLaunchKernelGGL(k_accept_tables_ps, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, c->stream, py.d_raw, g->d_ps, Wb_hi,
-                           cc, lg, M.words);
+        accept_tables_ps_launch(c->stream, py.d_raw, g->d_ps, Wb_hi, cc, lg, M.words);
         MSIM_HIP(c, hipGetLastError());
         // three pieces (1/8, 3/8, 1/2 of the positions): the walk starts on the first one while the others are in flight -- it
         // consumes the table at ~3 GB/s, the copies deliver 50 GB/s
@@ -1933,9 +1993,7 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
         }
         if (tables) {
             if (!early_ok) {                               // (not launched behind the mailbox: now, with the exact window)
-                const size_t n_slots = (size_t)(Wb + 1) << lg;
-                hipLaunchKernelGGL(k_accept_tables, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, c->stream, py.d_raw,
-                                   (unsigned long long)p_b, Wb, cc, lg, M.words);
+                accept_tables_launch(c->stream, py.d_raw, (unsigned long long)p_b, Wb, cc, lg, M.words);
                 MSIM_HIP(c, hipGetLastError());
                 cut[0] = 0; cut[1] = (size_t)(Wb + 1) / 8; cut[2] = (size_t)(Wb + 1) / 2; cut[3] = (size_t)Wb + 1;
                 for (int q = 0; q < 3; q++) {
@@ -2012,16 +2070,14 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
         if (rc) { g->s[0].live = g->s[1].live = false; g->unverified = false; return rc; }
         MSIM_HIP(c, hipEventRecord(g->t0, c->stream));    // the host chain is not GPU time
         MSIM_HIP(c, hipMemcpyAsync(M.nsn_stop, g->h_nstop, (size_t)n_nsn * 4, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(k_stop_scatter, dim3((n_nsn + 255) / 256), dim3(256), 0, c->stream, M.nsn_rank, M.nsn_stop, n_nsn,
-                           M.cand_stop);
+        stop_scatter_launch(c->stream, M.nsn_rank, M.nsn_stop, n_nsn, M.cand_stop);
     }
     if (has_tl) {
         MSIM_HIP(c, hipMemsetAsync(M.cand_aux, 0, (size_t)k, c->stream));
         if (n_nsn) {
             MSIM_HIP(c, hipMemcpyAsync(M.nsn_extra, g->h_nextra, (size_t)n_nsn * 4, hipMemcpyHostToDevice, c->stream));
             MSIM_HIP(c, hipMemcpyAsync(M.nsn_aux, g->h_naux, (size_t)n_nsn, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_link_scatter, dim3((n_nsn + 255) / 256), dim3(256), 0, c->stream, M.nsn_rank, M.nsn_extra, M.nsn_aux,
-                               n_nsn, M.cand_extra, M.cand_aux);
+            link_scatter_launch(c->stream, M.nsn_rank, M.nsn_extra, M.nsn_aux, n_nsn, M.cand_extra, M.cand_aux);
         }
         MSIM_HIP(c, hipGetLastError());
     }
@@ -2421,12 +2477,8 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
     if ((rc = ensure_words(c, g, 1, np_base + 2ull * K + 1))) return rc;
     if ((rc = ensure_signals(c, g))) return rc;
     MSIM_HIP(c, hipMemcpyAsync(M.mm_d, M.mm_h, off_visit, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(k_types_multi, dim3(nbk), dim3(CB_THREADS), 0, c->stream, np.d_raw, (unsigned long long)np_base, K, rt_d,
-                       n_draw, sets_d, M.cand_type);
-    hipLaunchKernelGGL(k_nsn_count, dim3(nbk), dim3(CB_THREADS), 0, c->stream, M.cand_type, K, M.cnt, ms.sn_chained ? 1u : 0u);
-    hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, M.cnt, nbk);
-    hipLaunchKernelGGL(k_nsn_scatter, dim3(nbk), dim3(CB_THREADS), 0, c->stream, (const uint32_t *)nullptr, M.cand_type, K, M.cnt, nbk,
-                       (uint32_t *)nullptr, M.nsn_type, M.nsn_rank, g->d_ps, ms.sn_chained ? 1u : 0u);
+    types_multi_launch(c->stream, np.d_raw, (unsigned long long)np_base, K, rt_d, n_draw, sets_d, M.cand_type);
+    nsn_compact_launch(c->stream, nullptr, M.cand_type, K, M.cnt, nullptr, M.nsn_type, M.nsn_rank, g->d_ps, ms.sn_chained);
     MSIM_HIP(c, hipGetLastError());
     {   // the chain's candidates go over beside the plan stream, a 16-sigma bound of their number first
         hipEvent_t se = next_chain_event(g);
@@ -2437,8 +2489,7 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
         MSIM_HIP(c, hipEventRecord(g->ev_cand, g->copy_stream));
     }
     hipLaunchKernelGGL(k_temper_window_ps, dim3((W + 255) / 256), dim3(256), 0, c->stream, py.d_raw, g->d_ps, W, M.words);
-    hipLaunchKernelGGL(k_accept_tables_ps, dim3((unsigned)((n_slots + 255) / 256)), dim3(256), 0, c->stream, py.d_raw, g->d_ps, W,
-                       ms.gcc, lg, M.tables);
+    accept_tables_ps_launch(c->stream, py.d_raw, g->d_ps, W, ms.gcc, lg, M.tables);
     MSIM_HIP(c, hipGetLastError());
     // window and tables come over in three pieces (1/8, 3/8, 1/2); the host starts on the first while the others are in flight.
     // Their copies go out behind the mailbox kernel, before the host polls: nothing of them depends on what the poll tells.
@@ -2503,14 +2554,13 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
     MSIM_HIP(c, hipMemcpyAsync(M.cand_pos, g->h_npos, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
     if (n_ch) MSIM_HIP(c, hipMemcpyAsync(M.nsn_stop, g->h_nstop, (size_t)n_ch * 4, hipMemcpyHostToDevice, c->stream));
     MSIM_HIP(c, hipMemcpyAsync(visit_d, visit_h, (size_t)n_draw * 4, hipMemcpyHostToDevice, c->stream));
-    if (n_ch) hipLaunchKernelGGL(k_stop_scatter, dim3((n_ch + 255) / 256), dim3(256), 0, c->stream, M.nsn_rank, M.nsn_stop, n_ch, M.cand_stop);
+    if (n_ch) stop_scatter_launch(c->stream, M.nsn_rank, M.nsn_stop, n_ch, M.cand_stop);
     if (ms.has_tl) {                                       // what __link_tls decided: linked spans, flags, tombstones
         MSIM_HIP(c, hipMemsetAsync(M.cand_aux, 0, (size_t)K, c->stream));
         if (n_ch) {
             MSIM_HIP(c, hipMemcpyAsync(M.nsn_extra, g->h_nextra, (size_t)n_ch * 4, hipMemcpyHostToDevice, c->stream));
             MSIM_HIP(c, hipMemcpyAsync(M.nsn_aux, g->h_naux, (size_t)n_ch, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_link_scatter, dim3((n_ch + 255) / 256), dim3(256), 0, c->stream, M.nsn_rank, M.nsn_extra, M.nsn_aux,
-                               n_ch, M.cand_extra, M.cand_aux);
+            link_scatter_launch(c->stream, M.nsn_rank, M.nsn_extra, M.nsn_aux, n_ch, M.cand_extra, M.cand_aux);
         }
     }
     MSIM_HIP(c, hipGetLastError());
@@ -2522,6 +2572,287 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
                 n_ch, W, lg, us(tp0, tp1), us(tp1, tp2), us(tp1, tp2) * 1e3 / K, us(tp2, tp3));
     }
     return rc;
+}
+
+// ====================================================================== test support: the device halves on hand-built tables
+// msim_dbg_candidates / msim_dbg_accept_tables / msim_dbg_mixed_emit: the launch helpers above over tables the caller made, in
+// device buffers of their own, synchronous, touching no contig and no stream session.  Each checks on the host what the
+// planners guarantee and refuses everything else (MSIM_ERR_ARG) before anything is allocated or launched.
+namespace {
+struct DbgDev {                                            // device blocks of one hook call
+    std::vector<void *> blocks;
+    ~DbgDev() { for (void *q : blocks) if (q) (void)hipFree(q); }
+    template <class T> hipError_t get(T **out, size_t n) {
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, std::max<size_t>(n * sizeof(T), 4) + PAD);
+        if (e == hipSuccess) blocks.push_back(q);
+        *out = static_cast<T *>(q);
+        return e;
+    }
+};
+bool dbg_type_table_ok(const TypeTable &tt) {
+    if (tt.n < 1 || tt.n > 8) return false;
+    for (uint32_t j = 0; j < tt.n; j++) {
+        if (tt.type[j] < 1 || tt.type[j] > 7) return false;
+        if (j && tt.thr[j] < tt.thr[j - 1]) return false;
+    }
+    return true;
+}
+}  // namespace
+
+// Form (a), bm given: one range's bitmap (n_words words), start, d -> cand_pos / cand_type (k_bitmap_count, k_scan_u32,
+// k_bitmap_expand_cand over sets[0]), then the compaction.  Form (b), bm null: K candidates typed by ordinal over rt[n_draw] and
+// sets[n_sets] (k_types_multi), the compaction without positions.  np_raw: RAW NumPy-stream words, at least two per candidate.
+// Outputs hold `cap` entries each (cand_pos / nsn_pos unused in form (b)); *k_out candidates, *n_nsn on the chain.
+int gpu_dbg_candidates(Ctx *c, const uint64_t *bm, uint32_t n_words, uint32_t start, uint32_t d, uint32_t K, const void *rt_v,
+                       uint32_t n_draw, const void *sets_v, uint32_t n_sets, const uint32_t *np_raw, uint64_t n_np, uint32_t all,
+                       uint32_t *cand_pos, uint8_t *cand_type, uint32_t *nsn_pos, uint8_t *nsn_type, uint32_t *nsn_rank, uint64_t cap,
+                       uint32_t *k_out, uint32_t *n_nsn) {
+    const MixRangeDev *rt = static_cast<const MixRangeDev *>(rt_v);
+    const TypeTable *sets = static_cast<const TypeTable *>(sets_v);
+    if (!sets || n_sets < 1 || n_sets > 8 || !cand_type || !nsn_type || !nsn_rank || !k_out || !n_nsn || all > 1 || (n_np && !np_raw))
+        return fail(c, MSIM_ERR_ARG, "msim_dbg_candidates: bad argument");
+    for (uint32_t q = 0; q < n_sets; q++)
+        if (!dbg_type_table_ok(sets[q])) return fail(c, MSIM_ERR_ARG, "msim_dbg_candidates: type table outside 1..8 types, types 1..7, non-decreasing thresholds");
+    uint64_t k = K;
+    if (bm) {
+        if (!n_words || n_words > (1u << 26) || n_sets != 1 || !cand_pos || !nsn_pos)
+            return fail(c, MSIM_ERR_ARG, "msim_dbg_candidates: a bitmap takes 1..2^26 words, one type table and room for positions");
+        k = 0;
+        for (uint32_t q = 0; q < n_words; q++) k += (uint64_t)__builtin_popcountll(bm[q]);
+        if ((uint64_t)start + 64ull * n_words + (uint64_t)d * k >= (1ull << 32))
+            return fail(c, MSIM_ERR_ARG, "msim_dbg_candidates: positions beyond 2^32");
+    } else {
+        if (!rt || n_draw < 1 || K < 1 || K > (1u << 28) || rt[0].rec_base != 0)
+            return fail(c, MSIM_ERR_ARG, "msim_dbg_candidates: a range table starts at candidate 0 and has 1..2^28 candidates");
+        for (uint32_t q = 0; q < n_draw; q++)
+            if (rt[q].set_id >= n_sets || rt[q].rec_base >= K || (q && rt[q].rec_base <= rt[q - 1].rec_base))
+                return fail(c, MSIM_ERR_ARG, "msim_dbg_candidates: rec_base not strictly increasing below K, or set_id out of range");
+    }
+    if (k > cap || 2 * k > n_np) return fail(c, MSIM_ERR_ARG, "msim_dbg_candidates: more candidates than room, or fewer than two words each");
+    *k_out = (uint32_t)k; *n_nsn = 0;
+    if (!k) return MSIM_OK;                                // (the engines never plan a range without candidates, and a grid of no
+                                                           //  workgroups is no launch: an empty bitmap comes back empty, unlaunched)
+    const uint32_t ku = (uint32_t)k, nbk = (ku + CB_BLOCK - 1) / CB_BLOCK;
+    DbgDev dev;
+    uint64_t *d_bm = nullptr; uint32_t *d_cnt2 = nullptr, *d_np = nullptr, *d_pos = nullptr, *d_npos = nullptr, *d_nrank = nullptr, *d_cnt = nullptr;
+    uint8_t *d_type = nullptr, *d_ntype = nullptr; MixRangeDev *d_rt = nullptr; TypeTable *d_sets = nullptr; PlanState *d_ps = nullptr;
+    hipStream_t s = c->stream;
+    MSIM_HIP(c, dev.get(&d_np, (size_t)n_np));
+    MSIM_HIP(c, dev.get(&d_type, k)); MSIM_HIP(c, dev.get(&d_ntype, k)); MSIM_HIP(c, dev.get(&d_nrank, k));
+    MSIM_HIP(c, dev.get(&d_cnt, (size_t)nbk + 2)); MSIM_HIP(c, dev.get(&d_ps, 1));
+    MSIM_HIP(c, hipMemcpyAsync(d_np, np_raw, (size_t)n_np * 4, hipMemcpyHostToDevice, s));
+    MSIM_HIP(c, hipMemsetAsync(d_ps, 0, sizeof(PlanState), s));
+    if (bm) {
+        MSIM_HIP(c, dev.get(&d_bm, n_words)); MSIM_HIP(c, dev.get(&d_cnt2, emit_cnt2_words(n_words)));
+        MSIM_HIP(c, dev.get(&d_pos, k)); MSIM_HIP(c, dev.get(&d_npos, k));
+        MSIM_HIP(c, hipMemcpyAsync(d_bm, bm, (size_t)n_words * 8, hipMemcpyHostToDevice, s));
+        cand_front_launch(s, d_bm, n_words, d_cnt2, start, d, d_np, 0ull, sets[0], d_pos, d_type);
+    } else {
+        MSIM_HIP(c, dev.get(&d_rt, n_draw)); MSIM_HIP(c, dev.get(&d_sets, n_sets));
+        MSIM_HIP(c, hipMemcpyAsync(d_rt, rt, (size_t)n_draw * sizeof(MixRangeDev), hipMemcpyHostToDevice, s));
+        MSIM_HIP(c, hipMemcpyAsync(d_sets, sets, (size_t)n_sets * sizeof(TypeTable), hipMemcpyHostToDevice, s));
+        types_multi_launch(s, d_np, 0ull, ku, d_rt, n_draw, d_sets, d_type);
+    }
+    nsn_compact_launch(s, d_pos, d_type, ku, d_cnt, d_npos, d_ntype, d_nrank, d_ps, all != 0);
+    MSIM_HIP(c, hipGetLastError());
+    PlanState h;
+    MSIM_HIP(c, hipMemcpyAsync(&h, d_ps, sizeof h, hipMemcpyDeviceToHost, s));
+    MSIM_HIP(c, wait_stream(s));
+    if (h.n_nsn > ku) return fail(c, MSIM_ERR_HIP, "msim_dbg_candidates: more chain candidates than candidates");
+    *n_nsn = h.n_nsn;
+    if (bm) MSIM_HIP(c, hipMemcpyAsync(cand_pos, d_pos, k * 4, hipMemcpyDeviceToHost, s));
+    MSIM_HIP(c, hipMemcpyAsync(cand_type, d_type, k, hipMemcpyDeviceToHost, s));
+    if (h.n_nsn) {
+        if (bm) MSIM_HIP(c, hipMemcpyAsync(nsn_pos, d_npos, (size_t)h.n_nsn * 4, hipMemcpyDeviceToHost, s));
+        MSIM_HIP(c, hipMemcpyAsync(nsn_type, d_ntype, (size_t)h.n_nsn, hipMemcpyDeviceToHost, s));
+        MSIM_HIP(c, hipMemcpyAsync(nsn_rank, d_nrank, (size_t)h.n_nsn * 4, hipMemcpyDeviceToHost, s));
+    }
+    MSIM_HIP(c, wait_stream(s));
+    return MSIM_OK;
+}
+
+// Both accept-table kernels over RAW CPython-stream words [p0, p0 + n): k_accept_tables at p0, k_accept_tables_ps behind
+// k_set_pos(p0).  T / T_ps: (n + 1) << lg_rows entries each, zero where the kernels write nothing (rows >= the class count).
+int gpu_dbg_accept_tables(Ctx *c, const uint32_t *raw, uint64_t n_words, uint64_t p0, uint32_t n, const uint32_t *sh,
+                          const uint32_t *width, uint32_t n_classes, uint32_t *T, uint32_t *T_ps) {
+    ChainClasses cc;
+    if (!T || !T_ps || (n_words && !raw) || n > (1u << 26) || p0 > n_words || n > n_words - p0 || !dbg_chain_classes(sh, width, n_classes, cc))
+        return fail(c, MSIM_ERR_ARG, "msim_dbg_accept_tables: window outside the words given, or a class that is no (32 - bit_length(width), width) pair of a table entry");
+    const uint32_t lg = chain_lg_rows(cc);
+    const size_t n_slots = ((size_t)n + 1) << lg;
+    DbgDev dev;
+    uint32_t *d_raw = nullptr, *d_T = nullptr, *d_Tps = nullptr; PlanState *d_ps = nullptr;
+    hipStream_t s = c->stream;
+    MSIM_HIP(c, dev.get(&d_raw, (size_t)n_words)); MSIM_HIP(c, dev.get(&d_T, n_slots)); MSIM_HIP(c, dev.get(&d_Tps, n_slots));
+    MSIM_HIP(c, dev.get(&d_ps, 1));
+    if (n_words) MSIM_HIP(c, hipMemcpyAsync(d_raw, raw, (size_t)n_words * 4, hipMemcpyHostToDevice, s));
+    MSIM_HIP(c, hipMemsetAsync(d_T, 0, n_slots * 4, s));
+    MSIM_HIP(c, hipMemsetAsync(d_Tps, 0, n_slots * 4, s));
+    MSIM_HIP(c, hipMemsetAsync(d_ps, 0, sizeof(PlanState), s));
+    accept_tables_launch(s, d_raw, (unsigned long long)p0, n, cc, lg, d_T);
+    hipLaunchKernelGGL(k_set_pos, dim3(1), dim3(1), 0, s, d_ps, (unsigned long long)p0);
+    accept_tables_ps_launch(s, d_raw, d_ps, n, cc, lg, d_Tps);
+    MSIM_HIP(c, hipGetLastError());
+    MSIM_HIP(c, hipMemcpyAsync(T, d_T, n_slots * 4, hipMemcpyDeviceToHost, s));
+    MSIM_HIP(c, hipMemcpyAsync(T_ps, d_Tps, n_slots * 4, hipMemcpyDeviceToHost, s));
+    MSIM_HIP(c, wait_stream(s));
+    return MSIM_OK;
+}
+
+// Steps 3 and 4 of an SV-mix plan (mixed_emit's launches) over the caller's candidates and chain verdicts: k_stop_scatter,
+// k_link_scatter (ch_extra / ch_aux given), keep_flags_launch, emit_records_launch.  L: the contig's length.  recs / rec_off /
+// sn_index hold k entries, pool cap_pool bytes; counts[0..2] = n_rec, n_sn, pool_len.
+int gpu_dbg_mixed_emit(Ctx *c, uint64_t L, uint32_t k, const uint32_t *cand_pos, const uint8_t *cand_type, uint32_t n_ch,
+                       const uint32_t *ch_rank, const uint32_t *ch_stop, const uint32_t *ch_extra, const uint8_t *ch_aux,
+                       uint32_t n_draw, const void *rt_v, const uint32_t *visit_from, uint32_t sn_chained, const uint32_t *np_raw,
+                       uint64_t n_np, msim_record *recs, uint32_t *rec_off, uint32_t *sn_index, uint8_t *pool, uint64_t cap_pool,
+                       uint32_t *counts, int64_t *len_delta) {
+    const MixRangeDev *rt = static_cast<const MixRangeDev *>(rt_v);
+    const msim_params &P = c->params;
+    const bool has_tl = ch_extra != nullptr;
+    if (!c->have_params || k < 1 || k > (1u << 28) || L < 1 || L >= (1ull << 32) || !cand_pos || !cand_type || n_ch > k ||
+        (n_ch && (!ch_rank || !ch_stop)) || (ch_extra != nullptr) != (ch_aux != nullptr) || sn_chained > 1 || (n_np && !np_raw) ||
+        (rt != nullptr) != (visit_from != nullptr) || (rt ? n_draw < 1 : n_draw != 0) || !recs || !rec_off || !sn_index || !counts ||
+        !len_delta || (cap_pool && !pool))
+        return fail(c, MSIM_ERR_ARG, "msim_dbg_mixed_emit: bad argument");
+    for (int t = 1; t <= 7; t++)
+        if (P.block[t] < 0) return fail(c, MSIM_ERR_ARG, "msim_dbg_mixed_emit: negative block");
+    // ---- what the planners guarantee
+    std::vector<uint32_t> stop(k, CHAIN_DROPPED), extra(k, 0);
+    std::vector<uint8_t> aux(k, 0);
+    {
+        uint32_t q = 0;
+        for (uint32_t j = 0; j < k; j++) {
+            const uint8_t t = cand_type[j];
+            if (t < 1 || t > 7 || cand_pos[j] >= L || (j && cand_pos[j] <= cand_pos[j - 1]))
+                return fail(c, MSIM_ERR_ARG, "msim_dbg_mixed_emit: types 1..7 at strictly increasing positions below the contig's length");
+            if ((t == MSIM_TL || t == MSIM_TLI) && !has_tl)
+                return fail(c, MSIM_ERR_ARG, "msim_dbg_mixed_emit: a translocation without ch_extra / ch_aux");
+            // off the chain an SNP must not block: sample_with_minimum_distance leaves more than block[SN] = d between positions
+            if (!sn_chained && j && cand_type[j - 1] == MSIM_SN && (int64_t)cand_pos[j] - (int64_t)cand_pos[j - 1] <= P.block[MSIM_SN])
+                return fail(c, MSIM_ERR_ARG, "msim_dbg_mixed_emit: without sn_chained an SNP could block its successor");
+            if (t == MSIM_SN && !sn_chained) continue;
+            if (q >= n_ch || ch_rank[q] != j)
+                return fail(c, MSIM_ERR_ARG, "msim_dbg_mixed_emit: ch_rank does not list exactly the chain's candidates, in order");
+            const uint32_t s = ch_stop[q];
+            if (has_tl) { extra[j] = ch_extra[q]; aux[j] = ch_aux[q]; }
+            q++;
+            stop[j] = s;
+            if ((aux[j] & ~(CHAIN_TOMBSTONE | 3u)) || ((aux[j] & CHAIN_TOMBSTONE) && t != MSIM_TL && t != MSIM_TLI) || ((aux[j] & 3u) && t != MSIM_TLI))
+                return fail(c, MSIM_ERR_ARG, "msim_dbg_mixed_emit: ch_aux flags outside what linking sets");
+            if (s == CHAIN_DROPPED) continue;
+            bool ok;
+            if (t == MSIM_TLI) ok = s < L && extra[j] < L;                       // the linked TL's span (or stop 0: unlinked)
+            else if (t == MSIM_SN) ok = s == cand_pos[j];
+            else if (t == MSIM_IN) ok = s >= cand_pos[j] && s < 0xfffffffeu;     // (an insert's stop is a length, not a place)
+            else ok = s >= cand_pos[j] && s < L;
+            if (!ok) return fail(c, MSIM_ERR_ARG, "msim_dbg_mixed_emit: a stop that is neither CHAIN_DROPPED nor in [pos, 2^32 - 1) within the contig");
+        }
+        if (q != n_ch) return fail(c, MSIM_ERR_ARG, "msim_dbg_mixed_emit: ch_rank lists candidates off the chain");
+    }
+    if (rt) {
+        if (rt[0].rec_base != 0) return fail(c, MSIM_ERR_ARG, "msim_dbg_mixed_emit: the range table starts at candidate 0");
+        for (uint32_t r = 0; r < n_draw; r++) {
+            const uint32_t a = rt[r].rec_base, b = r + 1 < n_draw ? rt[r + 1].rec_base : k;
+            if (a >= b || b > k || cand_pos[b - 1] >= rt[r].clip || (b < k && rt[r].clip > cand_pos[b]))
+                return fail(c, MSIM_ERR_ARG, "msim_dbg_mixed_emit: rec_base not strictly increasing below k, or a clip that does not part its range from the next");
+        }
+    }
+    // (visit_from is taken as given: any value is memory-safe, and only a boundary pass can say which ones are consistent --
+    //  tests/mixed_ref.py derives it from the same run as the stops)
+    // The keep rule, sequentially -- k_keep_flags' own arithmetic, NOT an independent check of it: it sizes the output buffers and
+    // bounds the kernels' 32-bit sums.
+    uint64_t n_rec = 0, n_ins = 0;
+    long long shift = 0;
+    {
+        BlockTable bt{};
+        for (int t = 1; t <= 7; t++) bt.p1[t] = (uint32_t)std::min<int64_t>(P.block[t] + 1, 0xffffffffll);
+        uint32_t run = 0, r = 0;
+        for (uint32_t j = 0; j < k; j++) {
+            uint32_t clip = 0xffffffffu;
+            bool vis = true;
+            if (rt) {
+                while (r + 1 < n_draw && rt[r + 1].rec_base <= j) r++;
+                clip = rt[r].clip;
+                vis = cand_pos[j] >= visit_from[r];
+            }
+            const uint8_t t = cand_type[j];
+            bool keep;
+            if (t == MSIM_SN) keep = (sn_chained ? stop[j] != CHAIN_DROPPED : cand_pos[j] >= run) && vis;
+            else keep = stop[j] != CHAIN_DROPPED && vis && !(aux[j] & CHAIN_TOMBSTONE);
+            run = std::max(run, std::min(clip, blocked_end(cand_pos[j], t, stop[j], bt)));
+            if (!keep) continue;
+            const long long off = (long long)cand_pos[j] + shift;
+            if (off < 0 || off >= (1ll << 32)) return fail(c, MSIM_ERR_ARG, "msim_dbg_mixed_emit: an output offset outside [0, 2^32)");
+            n_rec++;
+            if (t == MSIM_IN) n_ins += (uint64_t)stop[j] - cand_pos[j] + 1;
+            shift += record_delta(t, cand_pos[j], t == MSIM_SN ? cand_pos[j] : stop[j], extra[j]);
+        }
+        const long long out_len = (long long)L + shift;
+        if (out_len < 0 || out_len >= (1ll << 32) || n_ins >= (1ull << 32) || n_ins > n_np || n_ins > cap_pool)
+            return fail(c, MSIM_ERR_ARG, "msim_dbg_mixed_emit: mutated length or insert bases outside [0, 2^32), or fewer words / less room than insert bases");
+    }
+    // ---- device
+    const uint32_t nbk = (k + CB_BLOCK - 1) / CB_BLOCK;
+    DbgDev dev;
+    uint32_t *d_pos = nullptr, *d_stop = nullptr, *d_extra = nullptr, *d_crank = nullptr, *d_cstop = nullptr, *d_cextra = nullptr, *d_cnt = nullptr,
+             *d_snidx = nullptr, *d_visit = nullptr, *d_np = nullptr, *d_off = nullptr;
+    uint8_t *d_type = nullptr, *d_aux = nullptr, *d_caux = nullptr, *d_pool = nullptr;
+    MixRangeDev *d_rt = nullptr; PlanState *d_ps = nullptr; msim_record *d_recs = nullptr;
+    hipStream_t s = c->stream, es = c->emit_stream;
+    MSIM_HIP(c, dev.get(&d_pos, k)); MSIM_HIP(c, dev.get(&d_type, k)); MSIM_HIP(c, dev.get(&d_stop, k));
+    MSIM_HIP(c, dev.get(&d_crank, n_ch)); MSIM_HIP(c, dev.get(&d_cstop, n_ch));
+    MSIM_HIP(c, dev.get(&d_cnt, mixed_cnt_bytes(nbk) / 4)); MSIM_HIP(c, dev.get(&d_snidx, k)); MSIM_HIP(c, dev.get(&d_np, (size_t)n_np));
+    MSIM_HIP(c, dev.get(&d_ps, 1)); MSIM_HIP(c, dev.get(&d_recs, std::max<uint64_t>(n_rec, 1))); MSIM_HIP(c, dev.get(&d_off, std::max<uint64_t>(n_rec, 1)));
+    MSIM_HIP(c, dev.get(&d_pool, (size_t)n_ins + 2 * PAD));
+    MSIM_HIP(c, hipMemcpyAsync(d_pos, cand_pos, (size_t)k * 4, hipMemcpyHostToDevice, s));
+    MSIM_HIP(c, hipMemcpyAsync(d_type, cand_type, (size_t)k, hipMemcpyHostToDevice, s));
+    MSIM_HIP(c, hipMemsetAsync(d_stop, 0xee, (size_t)k * 4, s));          // (the engines leave the SNPs' entries unwritten too)
+    MSIM_HIP(c, hipMemsetAsync(d_ps, 0, sizeof(PlanState), s));
+    if (n_np) MSIM_HIP(c, hipMemcpyAsync(d_np, np_raw, (size_t)n_np * 4, hipMemcpyHostToDevice, s));
+    if (n_ch) {
+        MSIM_HIP(c, hipMemcpyAsync(d_crank, ch_rank, (size_t)n_ch * 4, hipMemcpyHostToDevice, s));
+        MSIM_HIP(c, hipMemcpyAsync(d_cstop, ch_stop, (size_t)n_ch * 4, hipMemcpyHostToDevice, s));
+        stop_scatter_launch(s, d_crank, d_cstop, n_ch, d_stop);
+    }
+    if (has_tl) {
+        MSIM_HIP(c, dev.get(&d_extra, k)); MSIM_HIP(c, dev.get(&d_aux, k)); MSIM_HIP(c, dev.get(&d_cextra, n_ch)); MSIM_HIP(c, dev.get(&d_caux, n_ch));
+        MSIM_HIP(c, hipMemsetAsync(d_extra, 0xee, (size_t)k * 4, s));
+        MSIM_HIP(c, hipMemsetAsync(d_aux, 0, (size_t)k, s));
+        if (n_ch) {
+            MSIM_HIP(c, hipMemcpyAsync(d_cextra, ch_extra, (size_t)n_ch * 4, hipMemcpyHostToDevice, s));
+            MSIM_HIP(c, hipMemcpyAsync(d_caux, ch_aux, (size_t)n_ch, hipMemcpyHostToDevice, s));
+            link_scatter_launch(s, d_crank, d_cextra, d_caux, n_ch, d_extra, d_aux);
+        }
+    }
+    if (rt) {
+        MSIM_HIP(c, dev.get(&d_rt, n_draw)); MSIM_HIP(c, dev.get(&d_visit, n_draw));
+        MSIM_HIP(c, hipMemcpyAsync(d_rt, rt, (size_t)n_draw * sizeof(MixRangeDev), hipMemcpyHostToDevice, s));
+        MSIM_HIP(c, hipMemcpyAsync(d_visit, visit_from, (size_t)n_draw * 4, hipMemcpyHostToDevice, s));
+    }
+    const MixedTables mt{k, d_pos, d_type, d_stop, d_extra, d_aux, d_cnt, d_snidx, d_rt, n_draw, d_visit, sn_chained != 0};
+    keep_flags_launch(s, P, mt, d_ps);
+    MSIM_HIP(c, hipGetLastError());
+    PlanState h;
+    MSIM_HIP(c, hipMemcpyAsync(&h, d_ps, sizeof h, hipMemcpyDeviceToHost, s));
+    MSIM_HIP(c, wait_stream(s));
+    counts[0] = h.n_rec; counts[1] = h.n_sn; counts[2] = h.pool_len; *len_delta = h.len_delta;
+    // the buffers are sized by the host's count: a device count that differs is reported, and nothing is emitted into them
+    if (h.n_rec != n_rec || h.pool_len != n_ins || h.n_sn > h.n_rec)
+        return fail(c, MSIM_ERR_HIP, "msim_dbg_mixed_emit: the device kept " + std::to_string(h.n_rec) + " records (" + std::to_string(h.n_sn) + " SNPs, " +
+                                     std::to_string(h.pool_len) + " insert bases), the keep rule on the host " + std::to_string(n_rec) + " (" +
+                                     std::to_string(n_ins) + " insert bases)");
+    emit_records_launch(es, mt, d_recs, d_off, d_np, 0ull, h.pool_len, d_pool + PAD);
+    MSIM_HIP(c, hipGetLastError());
+    if (n_rec) {
+        MSIM_HIP(c, hipMemcpyAsync(recs, d_recs, (size_t)n_rec * sizeof(msim_record), hipMemcpyDeviceToHost, es));
+        MSIM_HIP(c, hipMemcpyAsync(rec_off, d_off, (size_t)n_rec * 4, hipMemcpyDeviceToHost, es));
+    }
+    if (h.n_sn) MSIM_HIP(c, hipMemcpyAsync(sn_index, d_snidx, (size_t)h.n_sn * 4, hipMemcpyDeviceToHost, es));
+    if (n_ins) MSIM_HIP(c, hipMemcpyAsync(pool, d_pool + PAD, (size_t)n_ins, hipMemcpyDeviceToHost, es));
+    MSIM_HIP(c, wait_stream(es));
+    return MSIM_OK;
 }
 
 // test hook: which of the context's streams still have work queued (hipStreamQuery; never blocks)

@@ -1662,7 +1662,7 @@ __global__ __launch_bounds__(256) void k_link_scatter(const uint32_t *__restrict
     if (j < n_nsn) { cand_extra[nsn_rank[j]] = nsn_extra[j]; cand_aux[nsn_rank[j]] = nsn_aux[j]; }
 }
 // output length change of one kept record (apply.hip: rec_lengths): IN / DU + len, DE / TL - len, IV 0, TLI + the copied span
-__device__ __forceinline__ long long record_delta(uint8_t type, uint32_t pos, uint32_t stop, uint32_t extra) {
+__host__ __device__ __forceinline__ long long record_delta(uint8_t type, uint32_t pos, uint32_t stop, uint32_t extra) {
     const long long len = (long long)stop - (long long)pos + 1;
     switch (type) {
         case MSIM_IN: case MSIM_DU: return len;
@@ -1674,7 +1674,7 @@ __device__ __forceinline__ long long record_delta(uint8_t type, uint32_t pos, ui
 
 // end (exclusive) of the blocked range a kept non-SNP opens: [pos, stop + block] resp. [pos, pos + block]
 // for an insertion (mutator.py:204-209); 0 for everything else
-__device__ __forceinline__ uint32_t blocked_end(uint32_t pos, uint8_t type, uint32_t stop, const BlockTable &bt) {
+__host__ __device__ __forceinline__ uint32_t blocked_end(uint32_t pos, uint8_t type, uint32_t stop, const BlockTable &bt) {
     if (type == MSIM_SN || stop == CHAIN_DROPPED) return 0;
     if (type == MSIM_TLI) return bt.p1[MSIM_TLI];          // its stop is 0 in the boundary pass: range(start, 1 + block) (mutator.py:207)
     const unsigned long long e = (unsigned long long)(type == MSIM_IN ? pos : stop) + bt.p1[type & 7];

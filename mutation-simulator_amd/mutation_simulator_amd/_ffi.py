@@ -19,7 +19,8 @@ RNG_FAST = 4           # Engine flag: counter-based generator, NOT stream-compat
 
 
 class MsimError(RuntimeError):
-    """A libmsim call failed (HIP error, bad argument, unsupported input)."""
+    """A libmsim call failed (HIP error, bad argument, unsupported input).  ``code``: the MSIM_ERR_* value, where one came back."""
+    code = None
 
 
 class MsimUnsupported(MsimError):
@@ -213,6 +214,35 @@ def render_chain(recs: np.ndarray, length: int, t_name: str, q_name: str, chain_
     return out.tobytes()
 
 
+# the device tables of the SV-mix / host-chain test hooks (csrc/plan_kernels.h: TypeTable, MixRangeDev)
+TYPE_TABLE_DTYPE = np.dtype([("thr", "<u8", (8,)), ("n", "<u4"), ("type", "u1", (8,)), ("_pad", "u1", (4,))])
+MIX_RANGE_DTYPE = np.dtype([("rec_base", "<u4"), ("clip", "<u4"), ("set_id", "<u4"), ("rsv", "<u4")])
+CHAIN_DROPPED = 0xFFFFFFFF           # ctx.h: a chain candidate that is blocked / dropped
+CHAIN_TOMBSTONE = 0x80               # ctx.h: ch_aux flag of an entry __fix_tl_amount deleted
+
+
+def chain_lg_rows(n_classes: int) -> int:
+    """log2 of the accept tables' slots per word position (ctx.h: chain_lg_rows)."""
+    return 0 if n_classes <= 1 else 1 if n_classes == 2 else 2 if n_classes <= 4 else 3
+
+
+def accept_tables_host(tempered, classes) -> np.ndarray:
+    """The host's accept tables (plan_host.cpp: accept_tables_host) over TEMPERED words for ``classes`` = [(shift, width)], shape
+    (len(tempered) + 1, 1 << lg_rows).  Pure host code, no context (msim_dbg_accept_tables_host: not part of include/msim.h)."""
+    fn = load().msim_dbg_accept_tables_host
+    fn.restype, fn.argtypes = C.c_int, [_VP, C.c_uint32, _VP, _VP, C.c_uint32, _VP]
+    words = np.ascontiguousarray(tempered, dtype=np.uint32)
+    sh = np.array([c[0] for c in classes], dtype=np.uint32)
+    width = np.array([c[1] for c in classes], dtype=np.uint32)
+    T = np.full((len(words) + 1, 1 << chain_lg_rows(len(classes))), 0xdddddddd, dtype=np.uint32)
+    rc = fn(_ptr(words), len(words), _ptr(sh), _ptr(width), len(classes), _ptr(T))
+    if rc != OK:
+        err = MsimError(f"msim_dbg_accept_tables_host failed ({rc})")
+        err.code = rc
+        raise err
+    return T
+
+
 def chain_tile() -> int:
     """Records / gaps a workgroup of the chain kernels takes (text_gpu.hip: CH_TILE): where the device renderer's edge cases
     lie (msim_dbg_chain_tile: exported, not part of include/msim.h)."""
@@ -309,9 +339,9 @@ class Engine:
             self.lib.msim_key_error(self.h, -1, C.byref(base),
                                     C.byref(pos))
             raise KeyError(chr(base.value))            # mutator.py:449-455
-        if rc == ERR_UNSUPPORTED:
-            raise MsimUnsupported(msg)
-        raise MsimError(f"libmsim error {rc}: {msg}")
+        err = MsimUnsupported(msg) if rc == ERR_UNSUPPORTED else MsimError(f"libmsim error {rc}: {msg}")
+        err.code = rc
+        raise err
 
     # ------------------------------------------------------------------ device / rng
     def device_name(self) -> str:
@@ -567,6 +597,86 @@ class Engine:
         self._check(fn(self.h, n, ptrs(bms), _ptr(n_words), _ptr(start), _ptr(length), ptrs(auxs), int(d), int(train),
                        ptrs(recs), _ptr(cap_a), _ptr(n_recs), ptrs(firsts) if firsts else None))
         return tile, [(recs[i][:int(n_recs[i])], firsts[i] if firsts and n_tiles[i] else None) for i in range(n)]
+
+    def candidates(self, np_words, sets, bitmap=None, start: int = 0, d: int = 1, K: int = 0, ranges=None, all: bool = False):
+        """The candidate front of the SV-mix (``bitmap`` given: one range, ``sets`` one TYPE_TABLE_DTYPE entry) or host-chain
+        engine (``K`` candidates over ``ranges``, a MIX_RANGE_DTYPE table, and up to 8 ``sets``), then the compaction of the
+        chain's candidates (``all``: every candidate).  ``np_words``: RAW NumPy-stream words, two per candidate.  Returns a dict:
+        cand_pos (None without a bitmap), cand_type, nsn_pos (None without a bitmap), nsn_type, nsn_rank, n_nsn."""
+        fn = self.lib.msim_dbg_candidates
+        fn.restype = C.c_int
+        fn.argtypes = [_VP, _VP, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, _VP, C.c_uint32, _VP, C.c_uint32, _VP, C.c_uint64,
+                       C.c_uint32, _VP, _VP, _VP, _VP, _VP, C.c_uint64, _U32P, _U32P]
+        words = np.ascontiguousarray(np_words, dtype=np.uint32)
+        sets = np.ascontiguousarray(np.atleast_1d(sets), dtype=TYPE_TABLE_DTYPE)
+        if bitmap is not None:
+            bm = np.ascontiguousarray(bitmap, dtype=np.uint64)
+            cap = int(np.unpackbits(bm.view(np.uint8)).sum())
+            rt, n_draw = None, 0
+        else:
+            bm, cap = None, int(K)
+            rt = np.ascontiguousarray(ranges, dtype=MIX_RANGE_DTYPE)
+            n_draw = len(rt)
+        room = max(cap, 1)
+        cand_pos, nsn_pos, nsn_rank = (np.zeros(room, dtype=np.uint32) for _ in range(3))
+        cand_type, nsn_type = (np.zeros(room, dtype=np.uint8) for _ in range(2))
+        k_out, n_nsn = C.c_uint32(), C.c_uint32()
+        self._check(fn(self.h, _ptr(bm) if bm is not None else None, len(bm) if bm is not None else 0, int(start), int(d), int(K),
+                       _ptr(rt) if rt is not None else None, n_draw, _ptr(sets), len(sets), _ptr(words), len(words), 1 if all else 0,
+                       _ptr(cand_pos), _ptr(cand_type), _ptr(nsn_pos), _ptr(nsn_type), _ptr(nsn_rank), cap, C.byref(k_out),
+                       C.byref(n_nsn)))
+        k, m = k_out.value, n_nsn.value
+        return {"cand_pos": cand_pos[:k] if bm is not None else None, "cand_type": cand_type[:k],
+                "nsn_pos": nsn_pos[:m] if bm is not None else None, "nsn_type": nsn_type[:m], "nsn_rank": nsn_rank[:m], "n_nsn": m}
+
+    def accept_tables(self, raw_words, n: int, p0: int, classes):
+        """Both accept-table kernels over RAW CPython-stream words [p0, p0 + n) for ``classes`` = [(shift, width)]: returns
+        (k_accept_tables' table, k_accept_tables_ps' table), each of shape (n + 1, 1 << lg_rows); rows the kernels never write
+        (>= len(classes)) are zero."""
+        fn = self.lib.msim_dbg_accept_tables
+        fn.restype, fn.argtypes = C.c_int, [_VP, _VP, C.c_uint64, C.c_uint64, C.c_uint32, _VP, _VP, C.c_uint32, _VP, _VP]
+        words = np.ascontiguousarray(raw_words, dtype=np.uint32)
+        sh = np.array([c[0] for c in classes], dtype=np.uint32)
+        width = np.array([c[1] for c in classes], dtype=np.uint32)
+        rows = 1 << chain_lg_rows(len(classes))
+        T = np.full((int(n) + 1, rows), 0xdddddddd, dtype=np.uint32)
+        T_ps = np.full((int(n) + 1, rows), 0xdddddddd, dtype=np.uint32)
+        self._check(fn(self.h, _ptr(words), len(words), int(p0), int(n), _ptr(sh), _ptr(width), len(classes), _ptr(T), _ptr(T_ps)))
+        return T, T_ps
+
+    def mixed_emit(self, length: int, cand_pos, cand_type, ch_rank, ch_stop, np_words, ch_extra=None, ch_aux=None, ranges=None,
+                   visit_from=None, sn_chained: bool = False):
+        """Keep flags through records of the SV-mix / host-chain engines (k_stop_scatter ... k_pool_fill) over hand-built
+        candidates and chain verdicts; ``block`` comes from ``set_params``.  ``np_words``: RAW NumPy-stream words for the insert
+        pool.  Returns a dict: recs (RECORD_DTYPE), rec_off, sn_index, pool, n_rec, n_sn, pool_len, len_delta."""
+        fn = self.lib.msim_dbg_mixed_emit
+        fn.restype = C.c_int
+        fn.argtypes = [_VP, C.c_uint64, C.c_uint32, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP, C.c_uint32, _VP, _VP, C.c_uint32, _VP,
+                       C.c_uint64, _VP, _VP, _VP, _VP, C.c_uint64, _VP, C.POINTER(C.c_int64)]
+        pos = np.ascontiguousarray(cand_pos, dtype=np.uint32)
+        typ = np.ascontiguousarray(cand_type, dtype=np.uint8)
+        rank = np.ascontiguousarray(ch_rank, dtype=np.uint32)
+        stop = np.ascontiguousarray(ch_stop, dtype=np.uint32)
+        words = np.ascontiguousarray(np_words, dtype=np.uint32)
+        extra = None if ch_extra is None else np.ascontiguousarray(ch_extra, dtype=np.uint32)
+        aux = None if ch_aux is None else np.ascontiguousarray(ch_aux, dtype=np.uint8)
+        rt = None if ranges is None else np.ascontiguousarray(ranges, dtype=MIX_RANGE_DTYPE)
+        visit = None if visit_from is None else np.ascontiguousarray(visit_from, dtype=np.uint32)
+        k = len(pos)
+        assert len(typ) == k and len(stop) == len(rank)
+        opt = lambda a: _ptr(a) if a is not None else None
+        recs = np.zeros(max(k, 1), dtype=RECORD_DTYPE)
+        rec_off, sn_index = np.zeros(max(k, 1), dtype=np.uint32), np.zeros(max(k, 1), dtype=np.uint32)
+        cap_pool = len(words)
+        pool = np.zeros(max(cap_pool, 1), dtype=np.uint8)
+        counts = np.zeros(4, dtype=np.uint32)
+        delta = C.c_int64()
+        self._check(fn(self.h, int(length), k, _ptr(pos), _ptr(typ), len(rank), _ptr(rank), _ptr(stop), opt(extra), opt(aux),
+                       0 if rt is None else len(rt), opt(rt), opt(visit), 1 if sn_chained else 0, _ptr(words), len(words), _ptr(recs),
+                       _ptr(rec_off), _ptr(sn_index), _ptr(pool), cap_pool, _ptr(counts), C.byref(delta)))
+        n_rec, n_sn, pool_len = (int(x) for x in counts[:3])
+        return {"recs": recs[:n_rec], "rec_off": rec_off[:n_rec], "sn_index": sn_index[:n_sn], "pool": pool[:pool_len],
+                "n_rec": n_rec, "n_sn": n_sn, "pool_len": pool_len, "len_delta": int(delta.value)}
 
     def key_error(self, contig: int):
         """(base, position) of the KeyError the contig's APPLY recorded, or None."""
