@@ -388,6 +388,20 @@ typedef struct msim_vcf_group {
 } msim_vcf_group;
 int msim_vcf_load(msim_ctx *ctx, const uint8_t *text, uint64_t n, uint64_t *n_lines, uint64_t *n_groups);
 int msim_vcf_groups(msim_ctx *ctx, msim_vcf_group *out, uint64_t cap, uint64_t *n_groups);
+/* Which grammar msim_vcf_plan_contig reads the lines with; called between msim_vcf_load (which selects grammar 0 again) and the
+ * first msim_vcf_plan_contig.  grammar 0: the simulator's dialect described above (sample_index 0, haplotype 0 or 1).
+ * grammar 1, "consensus": any VCF, one haplotype of one sample, as `bcftools consensus -s SAMPLE -H N` applies it.  A line has 8
+ * fields or 10 and more, every data line as many as the first; ID, QUAL, FILTER and INFO are not looked at.  sample_index is the
+ * 0-based sample column (field 10 + sample_index; MSIM_ERR_ARG when the first data line has no such column), haplotype the 1-based
+ * entry of its GT (FORMAT's first key) split at '/' and '|'; a haploid GT serves every haplotype.  Entry '.' or 0, or a selected
+ * ALT '*': the line is skipped unread.  Entry k: REF -> the k-th ALT, both upper-cased, a REF byte matching the genome's base as it
+ * stands or de-ambiguated.  One base REF and ALT share (their first bytes, preferred; else their last) stays as the genome has
+ * it; what is left becomes a DE, an IN behind it, or both -- an SN record where a single base changes to what a transition or
+ * transversion gives.  Further refusals: an allele index beyond the ALTs or a multi-allelic ALT field longer than 4096 bytes,
+ * and "replacement or insertion that reaches behind the contig's last base" (reason 13), which has no record form.
+ * Overlapping lines, and a line that starts at the base directly behind a pure insertion's anchor, are refused as out of
+ * order.  On a device context the call reserves 96 bytes of parser state per line of the file's largest group.              */
+int msim_vcf_select(msim_ctx *ctx, uint32_t grammar, uint32_t sample_index, uint32_t haplotype);
 int msim_vcf_plan_contig(msim_ctx *ctx, int contig, int64_t group);
 int msim_vcf_host_bases(msim_ctx *ctx, int contig, const uint8_t *bases);
 int msim_vcf_timing(msim_ctx *ctx, double *load_kernel_ms, double *plan_kernel_ms);

@@ -33,6 +33,7 @@ enum : uint32_t {
     VCF_R_INSERT = 10,     // an inserted byte that is no letter
     VCF_R_ORDER = 11,      // not behind the input an earlier line consumed
     VCF_R_LENGTH = 12,     // the contig would grow to 2^32 bytes or more
+    VCF_R_END = 13,        // consensus grammar: a replacement or insertion that reaches behind the contig's last base
 };
 constexpr uint32_t VCF_FIELD_CAP = 255;
 
@@ -279,6 +280,167 @@ VCF_HD uint32_t vcf_long_byte(const msim_record &r, bool lead, uint64_t M, uint6
     return vcf_allele_char(ch) ? VCF_R_ALLELE : (in_ref ? VCF_R_REF : VCF_R_ALT);
 }
 
+// ---- the consensus grammar (msim_vcf_select(ctx, 1, sample, haplotype)) ----------------------------------------------------
+// Any VCF: the line's selected sample names one of the ALTs (or none: the line is skipped), and REF -> that ALT is decomposed
+// into at most a DE and an IN behind it.  Three statements, shared by the host loop and the device kernels:
+//   vcf_cons_ends   the short fields from the front, the sample columns, FORMAT, INFO, FILTER, QUAL from the back: POS, where REF
+//                   starts, where the ALT field ends, the allele the genotype selects
+//   vcf_cons_line   with the REF / ALT separator known: the selected ALT, the anchor, the records' shape
+//   vcf_cons_ref_byte / vcf_cons_alt_byte   one byte of REF / of the selected ALT
+// No statement walks more than VCF_CONS_WALK bytes of a REF or ALT.
+constexpr uint64_t VCF_CONS_WALK = 4096;                   // an ALT field longer than this is taken as one allele (a comma in it: refused)
+constexpr uint32_t VCF_C_ALT = 1u, VCF_C_REF = 2u;         // VcfCons::flags: whose bytes the per-byte pass looks at
+
+struct VcfCons {           // one line's state between the steps (the device keeps an array of them)
+    uint64_t r0, sep, a1;  // REF = [r0, sep), the ALT field = [sep + 1, a1)
+    uint64_t s0;           // the selected ALT = [s0, s0 + A)
+    uint32_t pos1, k;      // POS; the selected allele (0: the line is skipped)
+    uint32_t g0, R, A;     // genome index of REF[0], the lengths
+    uint32_t at, dlen;     // DE [at, at + dlen - 1] (dlen 0: none)
+    uint32_t ilen, ioff;   // IN of ALT[ioff, ioff + ilen) in front of base at + dlen (ilen 0: none)
+    uint32_t nrec, snp;    // records the line emits; snp: 1 + aux of its SN record (then dlen = ilen = 0)
+    uint32_t flags, poff;  // VCF_C_*; the insert's place in the pool
+};
+
+VCF_HD uint8_t vcf_upper(uint8_t b) { return (uint8_t)(b - 'a') < 26 ? (uint8_t)(b - 32) : b; }
+VCF_HD bool vcf_symbolic(uint8_t b) { return b == '<' || b == '>' || b == '[' || b == ']' || b == ','; }
+
+// nf0: fields of the file's first data line (every line must have as many); sample: 0-based sample column; hap: 1-based entry
+VCF_HD uint32_t vcf_cons_ends(const uint8_t *t, uint64_t b, uint64_t e, uint32_t tabs, uint32_t name_len, uint32_t nf0, uint32_t sample,
+                              uint32_t hap, uint64_t L, VcfCons &o) {
+    o.r0 = o.sep = o.a1 = o.s0 = 0; o.pos1 = o.k = o.g0 = o.R = o.A = o.at = o.dlen = o.ilen = o.ioff = o.nrec = o.snp = o.flags = o.poff = 0;
+    if (tabs + 1 != nf0 || !(nf0 == 8 || nf0 >= 10)) return VCF_R_FIELDS;
+    uint64_t p = b + name_len;
+    if (p >= e || t[p] != '\t') return VCF_R_FIELDS;
+    p++;
+    uint64_t pos1 = 0;
+    uint32_t nd = 0;
+    bool pos_bad = false;
+    while (p < e && t[p] != '\t') {
+        const uint8_t ch = t[p];
+        if (ch < '0' || ch > '9' || nd >= 10) pos_bad = true;
+        else { pos1 = pos1 * 10 + (ch - '0'); nd++; }
+        p++;
+    }
+    if (nd == 0 || pos1 == 0 || pos1 > L) pos_bad = true;
+    p++;
+    while (p < e && t[p] != '\t') p++;                     // ID: whatever it holds
+    const uint64_t r0 = p + 1;
+    // from the back: the sample columns, FORMAT, INFO, FILTER, QUAL -- fields nf0 - 1 down to 5
+    uint64_t q = e, gt0 = 0, gt1 = 0, fm0 = 0, fm1 = 0;
+    for (uint32_t f = nf0 - 1; f >= 5; f--) {
+        const uint64_t end = q;
+        while (q > r0 && t[q - 1] != '\t') q--;
+        if (q <= r0) return VCF_R_FIELDS;                  // (cannot happen with the tabs counted; keeps every read inside the line)
+        if (f == 9 + sample) { gt0 = q; gt1 = end; }
+        if (f == 8) { fm0 = q; fm1 = end; }
+        q--;
+    }
+    if (q < r0) return VCF_R_FIELDS;
+    uint32_t k = 1;
+    if (nf0 >= 10) {
+        if (fm1 - fm0 < 2 || t[fm0] != 'G' || t[fm0 + 1] != 'T' || (fm1 - fm0 > 2 && t[fm0 + 2] != ':')) return pos_bad ? VCF_R_POS : VCF_R_SAMPLE;
+        uint64_t g1 = gt0;
+        while (g1 < gt1 && t[g1] != ':') g1++;
+        // the hap-th entry of [gt0, g1) split at '/' and '|'; a single entry serves every hap
+        uint32_t total = 1;
+        for (uint64_t x = gt0; x < g1; x++) total += t[x] == '/' || t[x] == '|';
+        const uint32_t want = total == 1 ? 1 : hap;
+        if (want > total) return pos_bad ? VCF_R_POS : VCF_R_SAMPLE;
+        uint32_t cur = 1;
+        uint64_t e0 = gt0;
+        for (uint64_t x = gt0; x < g1 && cur < want; x++) if (t[x] == '/' || t[x] == '|') { cur++; e0 = x + 1; }
+        uint64_t e1 = e0;
+        while (e1 < g1 && t[e1] != '/' && t[e1] != '|') e1++;
+        if (e1 == e0) return pos_bad ? VCF_R_POS : VCF_R_SAMPLE;
+        if (e1 - e0 == 1 && t[e0] == '.') k = 0;
+        else {
+            if (e1 - e0 > 9) return pos_bad ? VCF_R_POS : VCF_R_SAMPLE;
+            k = 0;
+            for (uint64_t x = e0; x < e1; x++) {
+                if (t[x] < '0' || t[x] > '9') return pos_bad ? VCF_R_POS : VCF_R_SAMPLE;
+                k = k * 10 + (t[x] - '0');
+            }
+        }
+    }
+    o.k = k;
+    if (k == 0) return VCF_OK;                             // skipped: nothing else about the line is looked at
+    if (pos_bad) return VCF_R_POS;
+    o.pos1 = (uint32_t)pos1; o.r0 = r0; o.a1 = q;
+    return VCF_OK;
+}
+
+// o.sep is known.  Returns the reason the line is refused for (o.flags still says which bytes the per-byte pass checks: a smaller
+// reason found there wins), or VCF_OK with the line's records described in o.
+VCF_HD uint32_t vcf_cons_line(const uint8_t *t, const uint8_t *in, uint64_t L, VcfCons &o) {
+    if (o.k == 0) return VCF_OK;
+    const uint64_t r0 = o.r0, sep = o.sep, a1 = o.a1;
+    const uint64_t R = sep - r0, F = a1 - (sep + 1);
+    uint64_t s0 = sep + 1, s1 = a1;
+    if (F <= VCF_CONS_WALK) {
+        uint32_t cur = 1;
+        for (uint64_t x = sep + 1; x < a1; x++) {
+            if (t[x] != ',') continue;
+            if (cur == o.k) { s1 = x; break; }
+            cur++; s0 = x + 1;
+        }
+        if (cur < o.k) { o.k = 0; return VCF_R_ALLELE; }
+    } else if (o.k != 1) { o.k = 0; return VCF_R_ALLELE; }
+    const uint64_t A = s1 - s0;
+    if (A == 0) { o.k = 0; return VCF_R_ALLELE; }
+    if (A == 1 && t[s0] == '*') { o.k = 0; return VCF_OK; }       // the allele is missing because of an upstream deletion: skipped
+    o.s0 = s0;
+    o.flags = VCF_C_ALT;
+    const uint64_t g0 = (uint64_t)o.pos1 - 1;
+    o.g0 = (uint32_t)g0;
+    if (A >= (1ull << 32)) { o.A = 0; o.flags = 0; return VCF_R_LENGTH; }
+    o.A = (uint32_t)A;
+    if (R == 0 || g0 + R > L) return VCF_R_REF;
+    o.R = (uint32_t)R;
+    o.flags |= VCF_C_REF;
+    const uint8_t rf = vcf_upper(t[r0]), rl = vcf_upper(t[sep - 1]), af = vcf_upper(t[s0]), al = vcf_upper(t[s1 - 1]);
+    uint64_t at = g0, dlen = R, ilen = A;
+    uint32_t ioff = 0;
+    if (R == 1 && A == 1) {
+        const uint8_t g = in[g0], c = vcf_conv(g);
+        if (af == g) return VCF_OK;
+        const bool acgt = c == 'A' || c == 'C' || c == 'G' || c == 'T';
+        const uint32_t aux = !acgt ? 3u : af == vcf_ti(c) ? 0u : af == vcf_tv(0, c) ? 1u : af == vcf_tv(1, c) ? 2u : 3u;
+        if (aux != 3u) { o.at = (uint32_t)g0; o.snp = 1 + aux; o.nrec = 1; return VCF_OK; }
+    } else if (rf == af && !(A > 1 && g0 + R == L)) { at = g0 + 1; dlen = R - 1; ilen = A - 1; ioff = 1; }
+    else if (rl == al) { dlen = R - 1; ilen = A - 1; }
+    if (ilen && at + dlen == L) return VCF_R_END;
+    if (ilen && at + dlen + ilen - 1 >= (1ull << 32)) return VCF_R_LENGTH;
+    o.at = (uint32_t)at; o.dlen = (uint32_t)dlen; o.ilen = (uint32_t)ilen; o.ioff = ioff;
+    o.nrec = (dlen ? 1u : 0u) + (ilen ? 1u : 0u);
+    return VCF_OK;
+}
+
+// the line's records, in order, at out[0 .. o.nrec)
+VCF_HD void vcf_cons_records(const VcfCons &o, uint32_t poff, msim_record *out) {
+    uint32_t n = 0;
+    msim_record r;
+    r.extra = 0; r.aux = 0; r.rsv = 0;
+    if (o.snp) { r.pos = o.at; r.stop = o.at; r.type = MSIM_SN; r.aux = (uint8_t)(o.snp - 1); out[n++] = r; return; }
+    if (o.nrec == 0) return;
+    if (o.dlen) { r.pos = o.at; r.stop = o.at + o.dlen - 1; r.type = MSIM_DE; out[n++] = r; }
+    if (o.ilen) { r.pos = o.at + o.dlen; r.stop = r.pos + o.ilen - 1; r.extra = poff; r.type = MSIM_IN; out[n++] = r; }
+}
+
+// REF byte j: either form of the genome's base
+VCF_HD uint32_t vcf_cons_ref_byte(const VcfCons &o, uint64_t j, uint8_t ch, const uint8_t *in) {
+    const uint8_t u = vcf_upper(ch), g = in[(uint64_t)o.g0 + j];
+    return (u == g || u == vcf_conv(g)) ? VCF_OK : VCF_R_REF;
+}
+// byte j of the selected ALT; *pool_at >= 0: it belongs at that index of the line's insert, as *up
+VCF_HD uint32_t vcf_cons_alt_byte(const VcfCons &o, uint64_t j, uint8_t ch, int64_t *pool_at, uint8_t *up) {
+    *pool_at = -1;
+    if (vcf_symbolic(ch)) return VCF_R_ALLELE;
+    if (!vcf_letter(ch)) return VCF_R_INSERT;
+    if (j >= o.ioff && j - o.ioff < o.ilen) { *pool_at = (int64_t)(j - o.ioff); *up = vcf_upper(ch); }
+    return VCF_OK;
+}
+
 VCF_HD const char *vcf_reason_text(uint32_t reason) {
     switch (reason) {
         case VCF_R_FIELDS: return "other than 10 tab-separated fields";
@@ -293,7 +455,19 @@ VCF_HD const char *vcf_reason_text(uint32_t reason) {
         case VCF_R_INSERT: return "inserted byte that is no letter";
         case VCF_R_ORDER: return "not behind the input an earlier line consumed (positions increasing, no overlap)";
         case VCF_R_LENGTH: return "mutated length of 2^32 or more";
+        case VCF_R_END: return "replacement or insertion that reaches behind the contig's last base";
         default: return "unknown reason";
+    }
+}
+
+// the consensus grammar's wording where the dialect's does not describe it
+VCF_HD const char *vcf_cons_reason_text(uint32_t reason) {
+    switch (reason) {
+        case VCF_R_FIELDS: return "neither 8 nor 10 or more tab-separated fields, or not as many as the first data line";
+        case VCF_R_SAMPLE: return "FORMAT does not start with GT, or a genotype entry that is neither a number nor .";
+        case VCF_R_ALLELE: return "allele index beyond the ALTs, symbolic allele, breakend, or multi-allelic ALT longer than 4096 bytes";
+        case VCF_R_INSERT: return "ALT byte that is no letter";
+        default: return vcf_reason_text(reason);
     }
 }
 

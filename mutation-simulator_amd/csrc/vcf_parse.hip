@@ -12,6 +12,16 @@
 //           k_vcf_long: one lane per 16-byte piece of the group's text -- REF against the genome, an INV / DUP ALT against
 //           what the type produces, insert bytes into the pool -- so that no lane's work grows with a line's length
 //   The first failure travels as (line << 4 | reason) through atomicMin on one word, read back with the sizes.
+// Consensus grammar (msim_vcf_select(ctx, 1, ..): any VCF, one sample's one haplotype; the load is the same), per contig:
+//   k_cons_ends   one lane per line: POS, the start of REF from the front, the end of ALT from the back over the sample columns, the
+//                 selected genotype entry (vcf_cons_ends)
+//   k_cons_sep    one lane per 16-byte piece of the group's text: the one tab inside a line's REF / ALT span
+//   k_cons_lines  one lane per line: the selected ALT, the anchor, 0 / 1 / 2 records and the insert length (vcf_cons_line)
+//   scan          record counts and insert lengths (two packed channels); its emit writes the compacted records (ConsEmitF)
+//   k_cons_neigh  ordering / overlap between neighbours of the compacted table
+//   k_cons_long   one lane per 16-byte piece: REF against the genome in either form, the selected ALT's bytes upper-cased into
+//                 the pool
+//   No lane walks more than VCF_CONS_WALK bytes of a REF or ALT.
 // Host path (msim_create(-1)): the same grammar (vcf_parse_line is shared), the long parts as plain loops, and
 // check_record_table at the end.
 #include <algorithm>
@@ -45,6 +55,11 @@ struct VcfState {
     unsigned long long *d_mb = nullptr, *h_mb = nullptr;       // 8 words: results of a pass (h_mb pinned)
     hipEvent_t e0 = nullptr, e1 = nullptr;
     double load_ms = 0, plan_ms = 0;
+    // msim_vcf_select
+    uint32_t grammar = 0, sample = 0, hap = 1;
+    uint32_t nf0 = 0;                      // fields of the first data line
+    VcfCons *d_cons = nullptr;             // consensus grammar: one per line
+    uint32_t *d_recline = nullptr;         // the line (index within its group) of every compacted record
 };
 
 namespace {
@@ -280,10 +295,144 @@ __global__ __launch_bounds__(256) void k_vcf_long(const uint8_t *t, const uint64
     if (worst != 0xffffffffu) report(mb, worst_line, worst);
 }
 
+// ---- consensus grammar ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_cons_ends(const uint8_t *t, const uint64_t *ls, const uint32_t *tabcum, uint64_t first, uint64_t cnt,
+                                                   uint32_t name_len, uint32_t nf0, uint32_t sample, uint32_t hap, uint64_t L, VcfCons *cons,
+                                                   unsigned long long *mb) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= cnt) return;
+    const uint64_t idx = first + i;
+    VcfCons o;
+    const uint32_t reason = vcf_cons_ends(t, ls[idx], ls[idx + 1] - 1, tabcum[idx + 1] - tabcum[idx], name_len, nf0, sample, hap, L, o);
+    if (reason) { report(mb, idx + 1, reason); o.k = 0; }
+    cons[i] = o;
+}
+
+// the line that holds text byte x: the largest a in [0, cnt) with ls[first + a] <= x
+__device__ inline uint64_t line_of(const uint64_t *ls, uint64_t first, uint64_t cnt, uint64_t x) {
+    uint64_t a = 0, b = cnt - 1;
+    while (a < b) {
+        const uint64_t m = (a + b + 1) >> 1;
+        if (ls[first + m] <= x) a = m; else b = m - 1;
+    }
+    return a;
+}
+
+__global__ __launch_bounds__(256) void k_cons_sep(const uint8_t *t, const uint64_t *ls, uint64_t first, uint64_t cnt, VcfCons *cons) {
+    const uint64_t lo = ls[first], hi = ls[first + cnt];
+    const uint64_t piece = (lo & ~15ull) + 16 * ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    uint64_t x = piece > lo ? piece : lo;
+    const uint64_t x1 = piece + 16 < hi ? piece + 16 : hi;
+    if (x >= x1) return;
+    const uint4 w = *reinterpret_cast<const uint4 *>(t + piece);             // (aligned; the allocation's slack covers both ends)
+    const uint64_t w_lo = w.x | ((uint64_t)w.y << 32), w_hi = w.z | ((uint64_t)w.w << 32);
+    uint64_t a = line_of(ls, first, cnt, x);
+    while (x < x1) {
+        const uint64_t next = ls[first + a + 1];
+        if (x >= next) { a++; continue; }
+        const uint64_t lend = next < x1 ? next : x1;
+        if (cons[a].k == 0) { x = lend; continue; }
+        const uint64_t r0 = cons[a].r0, a1 = cons[a].a1;
+        if (x < r0) x = r0;
+        const uint64_t stop = a1 < lend ? a1 : lend;
+        for (; x < stop; x++) {
+            const uint32_t j = (uint32_t)(x - piece);
+            if ((uint8_t)((j < 8 ? w_lo : w_hi) >> (8 * (j & 7))) == '\t') cons[a].sep = x;
+        }
+        x = lend;
+    }
+}
+
+// mb: [0] first failure, [1] bytes the lines add to the contig, [3] bit 0: some record is no SNP
+__global__ __launch_bounds__(256) void k_cons_lines(const uint8_t *t, uint64_t first, uint64_t cnt, const uint8_t *in, uint64_t L, VcfCons *cons,
+                                                    unsigned long long *mb) {
+    const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long grow = 0;
+    bool sv = false;
+    if (i < cnt) {
+        VcfCons o = cons[i];
+        const uint32_t reason = vcf_cons_line(t, in, L, o);
+        if (reason) report(mb, first + i + 1, reason);
+        cons[i] = o;
+        grow = o.ilen;
+        sv = o.nrec && !o.snp;
+    }
+    for (int d = 32; d; d >>= 1) grow += __shfl_xor(grow, d);
+    const bool any_sv = __any(sv);
+    if ((threadIdx.x & 63) == 0) {
+        if (grow) atomicAdd(&mb[1], grow);
+        if (any_sv) atomicOr(&mb[3], 1ull);
+    }
+}
+
+// records (low) and insert bytes (high) of every line -> its slot in the compacted table and its place in the pool
+struct ConsEmitF {
+    VcfCons *cons; msim_record *recs; uint32_t *recline;
+    __device__ uint64_t count(uint64_t i) const { return (uint64_t)cons[i].nrec | ((uint64_t)cons[i].ilen << 32); }
+    __device__ void emit(uint64_t i, uint64_t slot, uint64_t poff) const {
+        const VcfCons o = cons[i];
+        if (o.nrec == 0) return;
+        cons[i].poff = (uint32_t)poff;
+        msim_record r[2];
+        vcf_cons_records(o, (uint32_t)poff, r);
+        for (uint32_t q = 0; q < o.nrec; q++) { recs[slot + q] = r[q]; recline[slot + q] = (uint32_t)i; }
+    }
+};
+
+__global__ void k_cons_neigh(const msim_record *recs, const uint32_t *recline, const unsigned long long *n_rec, uint64_t first, unsigned long long *mb) {
+    const uint64_t j = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j == 0 || j >= *n_rec) return;
+    if ((uint64_t)recs[j].pos < vcf_next_free(recs[j - 1])) report(mb, first + recline[j] + 1, VCF_R_ORDER);
+}
+
+__global__ __launch_bounds__(256) void k_cons_long(const uint8_t *t, const uint64_t *ls, uint64_t first, uint64_t cnt, const VcfCons *cons,
+                                                   const uint8_t *in, uint8_t *pool, uint64_t pool_len, unsigned long long *mb) {
+    const uint64_t lo = ls[first], hi = ls[first + cnt];
+    const uint64_t piece = (lo & ~15ull) + 16 * ((uint64_t)blockIdx.x * blockDim.x + threadIdx.x);
+    uint64_t x = piece > lo ? piece : lo;
+    const uint64_t x1 = piece + 16 < hi ? piece + 16 : hi;
+    if (x >= x1) return;
+    const uint4 w = *reinterpret_cast<const uint4 *>(t + piece);
+    const uint64_t w_lo = w.x | ((uint64_t)w.y << 32), w_hi = w.z | ((uint64_t)w.w << 32);
+    uint64_t a = line_of(ls, first, cnt, x);
+    uint32_t worst = 0xffffffffu;
+    uint64_t worst_line = 0;
+    while (x < x1) {
+        const uint64_t next = ls[first + a + 1];
+        if (x >= next) { a++; continue; }
+        const uint64_t lend = next < x1 ? next : x1;
+        const uint32_t flags = cons[a].flags;
+        if (!flags) { x = lend; continue; }
+        const VcfCons o = cons[a];
+        const uint64_t ref1 = (flags & VCF_C_REF) ? o.r0 + o.R : o.r0, alt1 = o.s0 + o.A;
+        if (x >= alt1) { x = lend; continue; }
+        if (x < o.r0) x = o.r0;
+        const uint64_t stop = alt1 < lend ? alt1 : lend;
+        for (; x < stop; x++) {
+            const uint32_t j = (uint32_t)(x - piece);
+            const uint8_t ch = (uint8_t)((j < 8 ? w_lo : w_hi) >> (8 * (j & 7)));
+            uint32_t reason = VCF_OK;
+            if (x < ref1) reason = vcf_cons_ref_byte(o, x - o.r0, ch, in);
+            else if (x >= o.s0) {
+                int64_t at;
+                uint8_t up;
+                reason = vcf_cons_alt_byte(o, x - o.s0, ch, &at, &up);
+                if (!reason && at >= 0 && (uint64_t)o.poff + (uint64_t)at < pool_len) pool[(uint64_t)o.poff + (uint64_t)at] = up;
+            }
+            if (reason && (worst == 0xffffffffu || first + a + 1 < worst_line || (first + a + 1 == worst_line && reason < worst))) {
+                worst = reason; worst_line = first + a + 1;
+            }
+        }
+        x = lend;
+    }
+    if (worst != 0xffffffffu) report(mb, worst_line, worst);
+}
+
 inline unsigned blocks_for(uint64_t n, unsigned per) { return (unsigned)((n + per - 1) / per); }
 
 int vcf_fail(Ctx *c, uint64_t line1, uint32_t reason) {
-    return fail(c, MSIM_ERR_VALUE, "VCF line " + std::to_string(line1) + ": " + vcf_reason_text(reason));
+    const bool cons = c->vcf && c->vcf->grammar;
+    return fail(c, MSIM_ERR_VALUE, "VCF line " + std::to_string(line1) + ": " + (cons ? vcf_cons_reason_text(reason) : vcf_reason_text(reason)));
 }
 
 // wait for the context's stream; a wait that gave up is followed by an unbounded one when caller memory is part of a copy
@@ -313,7 +462,7 @@ int run_scan(Ctx *c, VcfState *S, F f, uint64_t n_items, unsigned long long *d_t
 }
 
 void free_device(VcfState *S) {
-    void *bufs[] = {S->d_text, S->d_ls, S->d_tabcum, S->d_a, S->d_b, S->d_c, S->d_tile, S->d_mb};
+    void *bufs[] = {S->d_text, S->d_ls, S->d_tabcum, S->d_a, S->d_b, S->d_c, S->d_tile, S->d_mb, S->d_cons, S->d_recline};
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (S->h_mb) (void)hipHostFree(S->h_mb);
     if (S->e0) (void)hipEventDestroy(S->e0);
@@ -440,6 +589,58 @@ int plan_host(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) {
     const char *what = "";
     if (table_check(c, L, recs.data(), recs.size(), pool.size(), &delta, &bad, &what))
         return fail(c, MSIM_ERR_VALUE, "VCF line " + std::to_string((grp ? grp->first_line : 0) + bad + 1) + ": " + what);
+    return table_install(c, g, recs, pool, recs.empty());
+}
+
+// the consensus grammar, line after line (vcf_parse.h: the three statements the kernels share)
+int plan_host_cons(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) {
+    contig_reset(*g);
+    c->text_kind = 0;
+    g->apply_stream = nullptr;
+    std::vector<msim_record> recs;
+    std::vector<uint64_t> recline;
+    std::vector<uint8_t> pool, ins;
+    const uint8_t *t = S->h_text.data(), *in = g->h_in.data();
+    const uint64_t L = g->len;
+    uint64_t grow = 0;
+    const uint64_t cnt = grp ? grp->n_lines : 0;
+    for (uint64_t i = 0; i < cnt; i++) {
+        const uint64_t idx = grp->first_line + i, b = S->h_ls[idx], e = S->h_ls[idx + 1] - 1;
+        VcfCons o;
+        uint32_t worst = vcf_cons_ends(t, b, e, S->h_tabcum[idx + 1] - S->h_tabcum[idx], grp->name_len, S->nf0, S->sample, S->hap, L, o);
+        if (worst) return vcf_fail(c, idx + 1, worst);
+        if (o.k == 0) continue;
+        o.sep = o.r0;
+        while (o.sep < o.a1 && t[o.sep] != '\t') o.sep++;
+        worst = vcf_cons_line(t, in, L, o);
+        const bool shaped = worst == VCF_OK;
+        if (!worst) worst = 0xffffffffu;
+        auto note = [&](uint32_t r) { if (r && r < worst) worst = r; };
+        ins.assign(o.ilen, 0);
+        if (o.flags & VCF_C_REF) for (uint64_t j = 0; j < o.R; j++) note(vcf_cons_ref_byte(o, j, t[o.r0 + j], in));
+        if (o.flags & VCF_C_ALT)
+            for (uint64_t j = 0; j < o.A; j++) {
+                int64_t at;
+                uint8_t up;
+                note(vcf_cons_alt_byte(o, j, t[o.s0 + j], &at, &up));
+                if (at >= 0) ins[(size_t)at] = up;
+            }
+        msim_record r[2];
+        if (shaped) {
+            vcf_cons_records(o, (uint32_t)pool.size(), r);
+            if (o.nrec && !recs.empty() && (uint64_t)r[0].pos < vcf_next_free(recs.back())) note(VCF_R_ORDER);
+        }
+        if (worst != 0xffffffffu) return vcf_fail(c, idx + 1, worst);
+        for (uint32_t q = 0; q < o.nrec; q++) { recs.push_back(r[q]); recline.push_back(idx); }
+        pool.insert(pool.end(), ins.begin(), ins.end());
+        grow += o.ilen;
+    }
+    if (grp && L + grow >= (1ull << 32)) return vcf_fail(c, grp->first_line + 1, VCF_R_LENGTH);
+    long long delta = 0;
+    uint64_t bad = 0;
+    const char *what = "";
+    if (table_check(c, L, recs.data(), recs.size(), pool.size(), &delta, &bad, &what))
+        return fail(c, MSIM_ERR_VALUE, "VCF line " + std::to_string((bad < recline.size() ? recline[(size_t)bad] : (grp ? grp->first_line : 0)) + 1) + ": " + what);
     return table_install(c, g, recs, pool, recs.empty());
 }
 
@@ -597,6 +798,67 @@ int plan_device(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) {
     return MSIM_OK;
 }
 
+int plan_device_cons(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) {
+    int rc = ctx_drain(c);                                 // this contig's buffers may still be read by its last APPLY
+    if (rc) return rc;
+    contig_reset(*g);
+    c->text_kind = 0;
+    g->apply_stream = nullptr;
+    const uint64_t cnt = grp ? grp->n_lines : 0;
+    uint64_t pool_len = 0, n_rec = 0;
+    bool any_sv = false, too_long = false;
+    if (cnt) {
+        const uint8_t *t = S->d_text + PAD, *in = g->d_in + PAD;
+        const uint64_t first = grp->first_line;
+        rc = dev_reserve(c, (void **)&g->d_recs, &g->cap_recs, (size_t)cnt * 2 * sizeof(msim_record));
+        if (rc) return rc;
+        // the group's text: from its first line's start to the start of the line behind its last one, in 16-byte pieces
+        const uint64_t bytes = S->group_end[(size_t)(grp - S->groups.data())] - grp->name_off + (grp->name_off & 15);
+        const unsigned piece_blocks = blocks_for((bytes + 15) / 16, 256), line_blocks = blocks_for(cnt, 256);
+        S->h_mb[0] = ~0ull; S->h_mb[1] = S->h_mb[2] = S->h_mb[3] = 0;
+        MSIM_HIP(c, hipMemcpyAsync(S->d_mb, S->h_mb, 4 * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+        MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+        hipLaunchKernelGGL(k_cons_ends, dim3(line_blocks), dim3(256), 0, c->stream, t, S->d_ls, S->d_tabcum, first, cnt, grp->name_len, S->nf0,
+                           S->sample, S->hap, g->len, S->d_cons, S->d_mb);
+        hipLaunchKernelGGL(k_cons_sep, dim3(piece_blocks), dim3(256), 0, c->stream, t, S->d_ls, first, cnt, S->d_cons);
+        hipLaunchKernelGGL(k_cons_lines, dim3(line_blocks), dim3(256), 0, c->stream, t, first, cnt, in, g->len, S->d_cons, S->d_mb);
+        rc = run_scan(c, S, ConsEmitF{S->d_cons, g->d_recs, S->d_recline}, cnt, S->d_mb + 4);
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_cons_neigh, dim3(blocks_for(2 * cnt, 256)), dim3(256), 0, c->stream, g->d_recs, S->d_recline, S->d_mb + 4, first, S->d_mb);
+        MSIM_HIP(c, hipGetLastError());
+        MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+        if ((rc = fetch_mailbox(c, S))) return rc;
+        if ((rc = elapsed(c, S, &S->plan_ms))) return rc;
+        // as plan_device: a refusal found so far does not end the pass, and with one pending, or with sums of 2^32 or more,
+        // the per-byte pass checks only and writes no pool byte
+        too_long = g->len + S->h_mb[1] >= (1ull << 32);
+        const bool check_only = too_long || S->h_mb[0] != ~0ull;
+        n_rec = S->h_mb[4];
+        pool_len = check_only ? 0 : S->h_mb[5];
+        any_sv = S->h_mb[3] & 1;
+        rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, (size_t)pool_len + 2 * PAD);
+        if (rc) return rc;
+        MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+        hipLaunchKernelGGL(k_cons_long, dim3(piece_blocks), dim3(256), 0, c->stream, t, S->d_ls, first, cnt, S->d_cons, in, g->d_pool + PAD, pool_len,
+                           S->d_mb);
+        MSIM_HIP(c, hipGetLastError());
+        MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+        if ((rc = fetch_mailbox(c, S))) return rc;
+        if ((rc = elapsed(c, S, &S->plan_ms))) return rc;
+        if (S->h_mb[0] != ~0ull) return vcf_fail(c, S->h_mb[0] >> 4, (uint32_t)(S->h_mb[0] & 15));
+        if (too_long) return vcf_fail(c, grp->first_line + 1, VCF_R_LENGTH);
+    } else {
+        rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, 2 * PAD);
+        if (rc) return rc;
+    }
+    g->n_rec = n_rec;
+    g->pool_len = pool_len;
+    g->plan_empty = n_rec == 0;
+    g->all_snp = !any_sv;
+    g->planned = true;
+    return MSIM_OK;
+}
+
 }  // namespace
 
 void vcf_state_destroy(Ctx *c) {
@@ -666,10 +928,46 @@ int msim_vcf_plan_contig(msim_ctx *p, int contig, int64_t group) {
     const msim_vcf_group *grp = group >= 0 ? &S->groups[(size_t)group] : nullptr;
     if (c->host_only) {
         if (g->len && g->h_in.size() != g->len) return fail(c, MSIM_ERR_ARG, "host-only context: the contig's bases were not given (msim_vcf_host_bases)");
-        return plan_host(c, S, g, grp);
+        return S->grammar ? plan_host_cons(c, S, g, grp) : plan_host(c, S, g, grp);
     }
     TraceRange tr("msim VCF plan contig");
-    return plan_device(c, S, g, grp);
+    return S->grammar ? plan_device_cons(c, S, g, grp) : plan_device(c, S, g, grp);
+}
+
+int msim_vcf_select(msim_ctx *p, uint32_t grammar, uint32_t sample_index, uint32_t haplotype) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c) return MSIM_ERR_ARG;
+    int rc = flushed(c);
+    if (rc) return rc;
+    VcfState *S = c->vcf;
+    if (!S) return fail(c, MSIM_ERR_ARG, "msim_vcf_select before msim_vcf_load");
+    if (grammar > 1) return fail(c, MSIM_ERR_ARG, "msim_vcf_select: grammar is 0 (the simulator's dialect) or 1 (consensus)");
+    if (grammar == 0) {
+        if (sample_index || haplotype > 1) return fail(c, MSIM_ERR_ARG, "msim_vcf_select: the dialect has one haploid sample");
+        S->grammar = 0;
+        return MSIM_OK;
+    }
+    if (haplotype < 1) return fail(c, MSIM_ERR_ARG, "msim_vcf_select: haplotypes count from 1");
+    uint32_t nf0 = 0;
+    if (S->n_lines > S->n_header) {                        // the first data line's fields: every line must have as many
+        if (c->host_only) nf0 = S->h_tabcum[S->n_header + 1] - S->h_tabcum[S->n_header] + 1;
+        else {
+            uint32_t *two = reinterpret_cast<uint32_t *>(&S->h_mb[6]);       // (staged in the pinned mailbox)
+            MSIM_HIP(c, hipMemcpyAsync(two, S->d_tabcum + S->n_header, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            if ((rc = wait_ctx(c, false))) return rc;
+            nf0 = two[1] - two[0] + 1;
+        }
+    }
+    if (nf0 >= 10 && sample_index >= nf0 - 9)
+        return fail(c, MSIM_ERR_ARG, "msim_vcf_select: sample column " + std::to_string(sample_index) + " of " + std::to_string(nf0 - 9));
+    if (!c->host_only) {                                   // per-line state for the largest group: 88 + 8 bytes a line
+        uint64_t most = 0;
+        for (const msim_vcf_group &g : S->groups) most = std::max<uint64_t>(most, g.n_lines);
+        if (!S->d_cons) MSIM_HIP(c, hipMalloc((void **)&S->d_cons, (most + 1) * sizeof(VcfCons)));
+        if (!S->d_recline) MSIM_HIP(c, hipMalloc((void **)&S->d_recline, 2 * (most + 1) * sizeof(uint32_t)));
+    }
+    S->grammar = 1; S->sample = sample_index; S->hap = haplotype; S->nf0 = nf0;
+    return MSIM_OK;
 }
 
 int msim_vcf_host_bases(msim_ctx *p, int contig, const uint8_t *bases) {

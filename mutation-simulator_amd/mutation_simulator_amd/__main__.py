@@ -1,4 +1,5 @@
-"""``mutation-simulator file {args,rmt,it}`` (reference __main__.py:34-111) on an MI355X, plus ``file vcf truth.vcf``."""
+"""``mutation-simulator file {args,rmt,it}`` (reference __main__.py:34-111) on an MI355X, plus ``file vcf truth.vcf``
+(``--consensus``: any VCF, one haplotype of one sample)."""
 from __future__ import annotations
 
 import json

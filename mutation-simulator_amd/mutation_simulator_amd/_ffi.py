@@ -136,6 +136,7 @@ SYMBOLS = [
     ("msim_bgzf_inflate", C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint64, _U64P, C.POINTER(C.c_float)]),
     ("msim_vcf_load", C.c_int, [_VP, _VP, C.c_uint64, _U64P, _U64P]),
     ("msim_vcf_groups", C.c_int, [_VP, _VP, C.c_uint64, _U64P]),
+    ("msim_vcf_select", C.c_int, [_VP, C.c_uint32, C.c_uint32, C.c_uint32]),
     ("msim_vcf_plan_contig", C.c_int, [_VP, C.c_int, C.c_int64]),
     ("msim_vcf_host_bases", C.c_int, [_VP, C.c_int, _VP]),
     ("msim_vcf_timing", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -529,6 +530,11 @@ class Engine:
         if n.value:
             self._check(self.lib.msim_vcf_groups(self.h, _ptr(out), n.value, C.byref(n)))
         return out
+
+    def vcf_select(self, grammar: int, sample_index: int = 0, haplotype: int = 1):
+        """The grammar the following ``vcf_plan_contig`` calls read with: 0 the simulator's dialect, 1 consensus (any VCF; the
+        0-based sample column and the 1-based haplotype to follow).  ``vcf_load`` selects 0 again."""
+        self._check(self.lib.msim_vcf_select(self.h, int(grammar), int(sample_index), int(haplotype)))
 
     def vcf_plan_contig(self, contig: int, group: int = -1):
         """Group ``group`` (-1: no lines) becomes the contig's record table and insert pool, validated against its bases;

@@ -2,7 +2,7 @@
 sub-commands (reference argument_parser.py:31-240) plus a few additions of ours that never change
 a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bgzip``, ``--chain``, ``--bench-json``, and the ``vcf`` sub-command
 (``vcf_replay.py``: the mutated Fasta again from the reference and a run's VCF; it writes ``<outbase>_ms.fa`` and, with
-``--chain``, ``<outbase>_ms.chain``).
+``--chain``, ``<outbase>_ms.chain``; with ``--consensus [--sample NAME] [--haplotype N]`` the VCF may come from anywhere).
 
 The ``it`` sub-command (inter-chromosomal translocations, reference it_mutator.py: a second pass over
 the Fasta) runs through ``ITMutator`` / ``BedpeWriter``.  ``--rng fast`` applies to the mutation pass
@@ -135,11 +135,26 @@ def build_parser() -> ArgumentParser:
 
     p_vcf = sub.add_parser("vcf", help="Rebuild the mutated Fasta from the reference Fasta and the VCF of a run")
     p_vcf.add_argument("vcffile", type=Path, help="Path to the VCF file (text or BGZF-compressed)")
+    p_vcf.add_argument("--consensus", action="store_true", default=False,
+                       help="Take any VCF, not only one this program wrote: apply one haplotype of one sample, as "
+                            "bcftools consensus -s SAMPLE -H N does")
+    p_vcf.add_argument("--sample", default=None, metavar="NAME",
+                       help="With --consensus: the sample column to follow. Default = the first one")
+    p_vcf.add_argument("--haplotype", type=int, default=None, metavar="N",
+                       help="With --consensus: which allele of the genotype to apply, counted from 1. Default = 1")
     return parser
 
 
 def get_args(argv=None) -> Namespace:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.mode == "vcf":
+        if not args.consensus and (args.sample is not None or args.haplotype is not None):
+            parser.error("--sample and --haplotype need --consensus")
+        if args.haplotype is not None and args.haplotype < 1:
+            parser.error("--haplotype counts from 1")
+        if not args.consensus:                         # (the namespace of a plain replay stays as it was)
+            del args.consensus, args.sample, args.haplotype
     if args.quiet:
         args.ignore_warnings = True
         args.no_progress = True

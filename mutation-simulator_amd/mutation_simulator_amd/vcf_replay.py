@@ -1,4 +1,5 @@
-"""``mutation-simulator genome.fa vcf truth.vcf``: the mutated Fasta again, from the reference and the VCF of a run.
+"""``mutation-simulator genome.fa vcf truth.vcf``: the mutated Fasta again, from the reference and the VCF of a run; with
+``--consensus [--sample NAME] [--haplotype N]`` from any VCF, one haplotype of one sample (``msim_vcf_select``).
 
 Every data line replaces REF at POS by ALT; libmsim parses the text into the record tables the mutation pass would have
 planned (``msim_vcf_*``, csrc/vcf_parse.hip), the unchanged rewrite produces the bytes, and ``FastaWriter`` with the
@@ -51,12 +52,37 @@ def load_vcf_text(path, engine) -> np.ndarray:
     return raw
 
 
-def plan_all(engine, text: np.ndarray, names, contig_ids) -> None:
+def sample_column(text: np.ndarray, groups, sample) -> int:
+    """The 0-based sample column called ``sample`` (None: the first), from the ``#CHROM`` header line: the last line that
+    starts so among the bytes in front of the first data line."""
+    head = text[:int(groups["name_off"][0])] if len(groups) else text
+    names = None
+    for line in head.tobytes().split(b"\n"):
+        if line.startswith(b"#CHROM"):
+            names = line.rstrip(b"\r").split(b"\t")[9:]
+    if sample is None:
+        return 0
+    want = sample.encode("utf-8", "replace")
+    if names is None or want not in names:
+        raise VcfReplayError(f"the VCF has no sample column {sample!r}")
+    return names.index(want)
+
+
+def plan_all(engine, text: np.ndarray, names, contig_ids, consensus=None) -> None:
     """Load ``text`` and plan every contig (``contig_ids[i]`` is the context's id of the contig called ``names[i]``) from the
     lines that name it, in FILE order, so that the first offending line of the file is the one reported (ValueError /
-    VcfReplayError, "VCF line N: ...").  Contigs without lines get an empty table.  Nothing has been rewritten when this raises."""
+    VcfReplayError, "VCF line N: ...").  Contigs without lines get an empty table.  Nothing has been rewritten when this raises.
+    ``consensus``: None for the simulator's dialect, or (sample name or None, haplotype) for the general grammar."""
     engine.vcf_load(text)
     groups = engine.vcf_groups()
+    if consensus is not None:
+        sample, haplotype = consensus
+        try:
+            engine.vcf_select(1, sample_column(text, groups, sample), haplotype)
+        except _ffi.MsimError as e:                    # (the #CHROM line names more samples than the data lines hold)
+            if getattr(e, "code", None) != _ffi.ERR_ARG:
+                raise
+            raise VcfReplayError(str(e).split(": ", 1)[-1]) from None
     by_name = {}
     for i, name in enumerate(names):
         by_name.setdefault(name.encode("utf-8", "replace"), i)
@@ -108,7 +134,10 @@ class VcfReplay:
                 cids.append(eng.add_contig_text(rec.body, len(rec), rec.lenc, rec.lenb))
             else:
                 cids.append(eng.add_contig(rec.bases))
-        plan_all(eng, text, [r.name for r in recs], cids)
+        consensus = None
+        if getattr(self._args, "consensus", False):
+            consensus = (getattr(self._args, "sample", None), getattr(self._args, "haplotype", None) or 1)
+        plan_all(eng, text, [r.name for r in recs], cids, consensus)
         # every line is accepted: rewrite and write, contig by contig
         if getattr(self._args, "chain", False):        # the one extra file of this mode: the chains of the replayed tables
             self._chain_writer = ChainWriter(self._args.outchain)      # (first: if it cannot be written, no Fasta is left)

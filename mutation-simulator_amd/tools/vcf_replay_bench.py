@@ -2,9 +2,12 @@
 """Measure the ``vcf`` mode: parser kernels (GB/s of VCF text, HIP events), the command line end to end beside the ``args``
 run that produced its input (same box, same call), and one host core running the host parser on the same text.
 
-    python tools/vcf_replay_bench.py [--mbases 1200] [--contigs 8] [--repeats 3] [--flags sn|readme] [--dir /dev/shm]
+    python tools/vcf_replay_bench.py [--mbases 1200] [--contigs 8] [--repeats 3] [--flags sn|readme] [--dir /dev/shm] [--consensus]
 
-Prints one JSON line per flag set.  Every command-line run is a child process with a time limit.
+``--consensus``: the same run's VCF is also replayed with ``vcf --consensus`` (the general grammar), and its figures stand beside
+the dialect's.  The consensus grammar refuses what it has no record form for -- the simulator's own inversion or duplication line
+that ends on a contig's last base without a trailing anchor, say; such a draw is reported as ``consensus_refused`` in the JSON
+line and the dialect's figures stand alone.  Prints one JSON line per flag set.  Every command-line run is a child process with a time limit.
 """
 from __future__ import annotations
 
@@ -43,13 +46,19 @@ def gen_genome(path: Path, lengths, seed: int):
                     f.write(b[full * 60:].tobytes() + b"\n")
 
 
-def cli(argv, limit):
+class Refused(Exception):
+    """A child ended with a "VCF line N: reason" refusal."""
+
+
+def cli(argv, limit, may_refuse=False):
     env = dict(os.environ, PYTHONPATH=str(ROOT))
     t0 = time.perf_counter()
     p = subprocess.run([sys.executable, "-m", "mutation_simulator_amd", "-q", "-c"] + [str(a) for a in argv], env=env,
                        capture_output=True, text=True, timeout=limit)
     dt = time.perf_counter() - t0
     if p.returncode != 0:
+        if may_refuse and p.returncode == 1 and "VCF line " in p.stderr:
+            raise Refused(p.stderr[p.stderr.index("VCF line "):].splitlines()[0])
         raise SystemExit(f"{argv}: exit {p.returncode}: {p.stderr[-2000:]}")
     return dt
 
@@ -62,6 +71,7 @@ def main():
     ap.add_argument("--flags", choices=sorted(FLAGS), nargs="*", default=sorted(FLAGS))
     ap.add_argument("--dir", type=Path, default=Path(tempfile.gettempdir()))
     ap.add_argument("--host-parser", action="store_true", help="also time one host core on the host parser (reads the genome into memory)")
+    ap.add_argument("--consensus", action="store_true", help="also replay the VCF with the consensus grammar")
     ap.add_argument("--limit", type=int, default=600, help="seconds per command-line run")
     a = ap.parse_args()
     with tempfile.TemporaryDirectory(dir=a.dir) as d:
@@ -71,17 +81,35 @@ def main():
         gen_genome(fa, [per] * a.contigs, 1)
         for name in a.flags:
             args_s, vcf_s, load_gbs, plan_gbs = [], [], [], []
+            cons_s, cons_load, cons_plan, cons_same, cons_refused = [], [], [], True, None
             for r in range(a.repeats):
                 args_s.append(cli(["--seed", 42, "-o", d / "out", fa, "args"] + FLAGS[name], a.limit))
                 vcf_s.append(cli(["--bench-json", d / "b.json", "-o", d / "back", fa, "vcf", d / "out_ms.vcf"], a.limit))
                 st = json.loads((d / "b.json").read_text())
                 load_gbs.append(st["vcf_bytes"] / 1e6 / max(st["vcf_load_kernel_ms"], 1e-9))
                 plan_gbs.append(st["vcf_bytes"] / 1e6 / max(st["vcf_plan_kernel_ms"], 1e-9))
+                if a.consensus and cons_refused is None:
+                    try:
+                        cons_s.append(cli(["--bench-json", d / "c.json", "-o", d / "cons", fa, "vcf", d / "out_ms.vcf", "--consensus"],
+                                          a.limit, may_refuse=True))
+                    except Refused as e:
+                        cons_refused = str(e)
+                        continue
+                    ct = json.loads((d / "c.json").read_text())
+                    cons_load.append(ct["vcf_bytes"] / 1e6 / max(ct["vcf_load_kernel_ms"], 1e-9))
+                    cons_plan.append(ct["vcf_bytes"] / 1e6 / max(ct["vcf_plan_kernel_ms"], 1e-9))
+                    cons_same &= subprocess.run(["cmp", str(d / "out_ms.fa"), str(d / "cons_ms.fa")], capture_output=True).returncode == 0
             same = subprocess.run(["cmp", str(d / "out_ms.fa"), str(d / "back_ms.fa")], capture_output=True).returncode == 0
             out = {"flags": name, "mbases": a.mbases, "vcf_bytes": st["vcf_bytes"], "fasta_identical": same,
                    "args_cli_s": [round(x, 3) for x in args_s], "vcf_cli_s": [round(x, 3) for x in vcf_s],
                    "load_kernels_GBps": [round(x, 1) for x in load_gbs], "plan_kernels_GBps": [round(x, 1) for x in plan_gbs],
                    "parser_kernels_GBps": [round(1 / (1 / x + 1 / y), 1) for x, y in zip(load_gbs, plan_gbs)]}
+            if a.consensus and cons_refused is not None:
+                out["consensus_refused"] = cons_refused
+            elif a.consensus:
+                out.update({"consensus_fasta_identical": cons_same, "consensus_cli_s": [round(x, 3) for x in cons_s],
+                            "consensus_load_kernels_GBps": [round(x, 1) for x in cons_load],
+                            "consensus_plan_kernels_GBps": [round(x, 1) for x in cons_plan]})
             if a.host_parser:
                 from mutation_simulator_amd import _ffi, load_fasta, vcf_replay
                 fasta = load_fasta(fa, 0)
