@@ -1160,10 +1160,8 @@ int msim_dbg_sample_ranges(msim_ctx *p, const msim_range *ranges, int n_ranges, 
                            uint32_t *pos_out, uint64_t *consumed) {
     CTX_FLUSHED(c, p)
     if (!c || !consumed || (n_ranges && !ranges)) return MSIM_ERR_ARG;
-    int64_t d = c->params.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, c->params.block[t]);
     size_t used = 0;
-    const int rc = sample_ranges_host(c, ranges, n_ranges, d, words, (size_t)n_words, pos_out, &used);
+    const int rc = sample_ranges_host(c, ranges, n_ranges, min_block(c->params), words, (size_t)n_words, pos_out, &used);
     *consumed = used;
     return rc;
 }
@@ -1173,10 +1171,8 @@ int msim_dbg_cut_ranges(msim_ctx *p, const msim_range *ranges, int n_ranges, con
                         uint32_t *cut, uint32_t *pool_pos, uint64_t *n_pool_pos, uint64_t *consumed) {
     CTX_FLUSHED(c, p)
     if (!c || !consumed || !n_pool_pos || !cut || (n_ranges && !ranges)) return MSIM_ERR_ARG;
-    int64_t d = c->params.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, c->params.block[t]);
     size_t used = 0, np = 0;
-    const int rc = cut_ranges_host(c, ranges, n_ranges, d, words, (size_t)n_words, cut, pool_pos, &np, &used);
+    const int rc = cut_ranges_host(c, ranges, n_ranges, min_block(c->params), words, (size_t)n_words, cut, pool_pos, &np, &used);
     *consumed = used; *n_pool_pos = np;
     return rc;
 }
@@ -1448,6 +1444,21 @@ int msim_dbg_stream_moments(uint64_t n, uint64_t k, uint64_t K, uint64_t ti_lim,
     if (!out || !n || k >= n) return MSIM_ERR_ARG;
     const StreamMoments a = sample_words_moments(n, k), b = snp_words_moments(K, (unsigned long long)ti_lim);
     out[0] = a.e; out[1] = a.v; out[2] = b.e; out[3] = b.v;
+    return MSIM_OK;
+}
+
+// test support (tests/test_stream_need_host.py, CPU tier): the stream-window arithmetic (plan_windows.h) as gpu_plan_make_room and
+// the engines use it; needs no context.  out: the table's need py, np, bad; of ranges[0]: the big-sample window, the small-sample
+// mean and variance bound, the least randint acceptance
+int msim_dbg_stream_need(const msim_params *params, const msim_range *ranges, int n_ranges, double out[7]) {
+    if (!params || !ranges || n_ranges < 1 || !out) return MSIM_ERR_ARG;
+    const msim_range &r = ranges[0];
+    const double n = (double)range_population(r, min_block(*params)), k = (double)r.k;
+    if (n < 1) return MSIM_ERR_ARG;
+    const StreamNeed need = stream_need(*params, ranges, n_ranges);
+    const StreamMoments m = small_sample_moments(n, k, (double)r.setsize);
+    out[0] = need.py; out[1] = need.np; out[2] = need.bad ? 1.0 : 0.0;
+    out[3] = big_sample_window(n, set_path_need(n, k)); out[4] = m.e; out[5] = m.v; out[6] = randint_acceptance_min(r);
     return MSIM_OK;
 }
 

@@ -16,6 +16,7 @@
 
 #include "ctx.h"
 #include "fast_kernels.h"
+#include "plan_windows.h"
 
 namespace msim {
 
@@ -138,17 +139,11 @@ int dev_grow(Ctx *c, FastPlan *f, DevBuf<T> &b, size_t want) {
     return MSIM_OK;
 }
 
-bool type_drawable(const msim_range &r, int j) {
-    const uint64_t lo = j ? r.cdf_thr[j - 1] : 0;
-    return r.cdf_thr[j] > lo && lo < (1ull << 53);
-}
-
 // msim_range tables -> what the kernels read.  Returns MSIM_OK, MSIM_ERR_VALUE (the reference's ValueError) or
 // MSIM_ERR_UNSUPPORTED with the reason in c->err.
 int prepare(Ctx *c, uint64_t L, const msim_range *ranges, int n_ranges, Prep &P) {
     const msim_params &mp = c->params;
-    int64_t d = mp.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, mp.block[t]);
+    const int64_t d = min_block(mp);
     if (d < 0 || d >= (1ll << 31)) return fail(c, MSIM_ERR_UNSUPPORTED, "fast RNG mode: block sizes beyond 2^31");
     P.d = d;
     for (int t = 0; t < 8; t++) {
@@ -179,7 +174,7 @@ int prepare(Ctx *c, uint64_t L, const msim_range *ranges, int n_ranges, Prep &P)
     for (int i = 0; i < n_ranges; i++) {
         const msim_range &r = ranges[i];
         if (r.k == 0) continue;
-        const int64_t n = (r.stop - (r.k - 1) * d) - r.start;
+        const int64_t n = range_population(r, d);
         // random.sample(range(start, stop - (k - 1) d), k): "Sample larger than population or is negative" (util.py:104)
         if (r.k < 0 || n < r.k) return fail(c, MSIM_ERR_VALUE, "Sample larger than population or is negative");
         if (r.start < 0 || r.stop >= (1ll << 32) || n >= (1ll << 32))
@@ -200,7 +195,7 @@ int prepare(Ctx *c, uint64_t L, const msim_range *ranges, int n_ranges, Prep &P)
                 s.type[j] = (uint8_t)r.types[j];
                 if (!type_drawable(r, j)) continue;
                 const int t = r.types[j];
-                const double p = (double)(std::min<uint64_t>(r.cdf_thr[j], 1ull << 53) - (j ? r.cdf_thr[j - 1] : 0)) / 9007199254740992.0;
+                const double p = type_probability(r, j);
                 if (t == MSIM_SN) continue;
                 D.sn_only = false;
                 if (t == MSIM_TL || t == MSIM_TLI)

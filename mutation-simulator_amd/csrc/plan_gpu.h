@@ -1,6 +1,7 @@
 // GPU sampler interface (plan_gpu.hip)
 #pragma once
 #include "ctx.h"
+#include "plan_windows.h"
 
 namespace msim {
 
@@ -59,6 +60,10 @@ void gpu_plan_abandon(GpuPlan *g);                        // a device engine fai
 // before a contig goes to a device engine: room for its windows in the current session's jump-table span, re-basing the session
 // where there is not (*fits = false: no span holds it -- the host planner's)
 int gpu_plan_make_room(Ctx *c, GpuPlan *g, const msim_range *ranges, int n_ranges, bool *fits);
+// ... and the need itself: words of the CPython and the NumPy stream the contig's windows can ask for (a pure function of its
+// arguments, summed from plan_windows.h; bad: a range every device engine's eligibility refuses)
+struct StreamNeed { double py, np; bool bad; };
+StreamNeed stream_need(const msim_params &P, const msim_range *ranges, int n_ranges);
 
 void gpu_plan_stream_status(Ctx *c, GpuPlan *g, int out[8]);
 
@@ -70,7 +75,6 @@ void gpu_plan_stream_status(Ctx *c, GpuPlan *g, int out[8]);
 //     E = E A / p, Var = E A (1-p)/p^2 + Var A / p^2
 //   SNP draws of K SNPs (mutator.py:428-463): uniform() = 2 words; with probability p_tv a transversion's randint(0, 1) =
 //     _randbelow(2) = getrandbits(2) until < 2, a geometric(1/2) loop: E = K (2 + 2 p_tv), Var = K (2 p_tv + 4 p_tv (1 - p_tv))
-struct StreamMoments { double e, v; };
 StreamMoments sample_words_moments(uint64_t n, uint64_t k);
 StreamMoments snp_words_moments(uint64_t K, unsigned long long ti_lim);
 

@@ -362,46 +362,36 @@ static inline uint64_t span_words(const GpuPlan *g) { return (uint64_t)MT_N + (u
 // (gpu_plan_sync_to_host: any such window is a valid state) and the engine's stream_to_device makes it the origin of a new
 // session; a synchronisation and a fresh cascade every 1.3 G words.  *fits = false: not even an empty span holds this contig
 // (hundreds of millions of candidates on one contig) -- AUTO plans it on the host, which has no such limit.
-// The need is an upper bound built from the engines' own window formulas (enqueue_sample_chain, enqueue_snp_stage, window_of,
-// mixed_link_translocations), summed as if every stage started at the end of the previous one's window.
-int gpu_plan_make_room(Ctx *c, GpuPlan *g, const msim_range *ranges, int n_ranges, bool *fits) {
-    const msim_params &P = c->params;
-    int64_t d = P.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, P.block[t]);
-    double py = 0, np = 0, K = 0, K_chain = 0, pool_mean = 0, pool_var = 0, e_small = 0, var_small = 0;
+// The need is an upper bound built from the engines' own window formulas (plan_windows.h: the very functions enqueue_sample_chain,
+// the host-cut and host-chain windows and window_of call; enqueue_snp_stage, mixed_link_translocations), summed as if every stage
+// started at the end of the previous one's window.  bad: a range no device engine takes (their eligibility refuses it).
+StreamNeed stream_need(const msim_params &P, const msim_range *ranges, int n_ranges) {
+    const int64_t d = min_block(P);
+    double py = 0, K = 0, K_chain = 0, pool_mean = 0, pool_var = 0, e_small = 0, var_small = 0;
     bool has_tl = false, bad = false;
     int n_big = 0;
     for (int i = 0; i < n_ranges; i++) {
         const msim_range &r = ranges[i];
         if (r.k <= 0) continue;
-        const double k = (double)r.k;
-        const double n = (double)((r.stop - (r.k - 1) * d) - r.start);
+        const double k = (double)r.k, n = (double)range_population(r, d);
+        const bool pool = n <= (double)r.setsize;                        // pool path: no rejection, any n
         K += k;
-        if (n < k) bad = true;                                           // ValueError: whoever plans it raises it
-        else if (n <= (double)r.setsize) { e_small += 2.0 * k; var_small += 2.0 * k; }    // pool path: < 2 words per draw
-        else if (n >= 4294967296.0) bad = true;                          // (multi-word getrandbits: no device engine takes it)
-        else {                                                           // set path: the first k distinct accepted draws
-            const double p_acc = n / (double)(1ull << bit_length64((uint64_t)n));
-            const double need = k >= n ? 64.0 * k : -n * std::log1p(-k / n);             // coupon collector
-            if (r.k >= 4096) {                                           // a window of its own (enqueue_sample_chain)
-                const double target = need + 16.0 * std::sqrt(need) + 4096.0;
-                py += target / p_acc + 16.0 * std::sqrt(target) / p_acc + 8192.0;
-                n_big++;
-            } else {                                                     // small ranges share one window (host-cut / host-chain engines)
-                e_small += need / p_acc;
-                var_small += need * (1.0 - p_acc) / (p_acc * p_acc) + 4.0 * (need - k) / (p_acc * p_acc) + need / p_acc;
-            }
+        if (n < k || (!pool && n >= 4294967296.0)) bad = true;           // ValueError: whoever plans it raises it / multi-word getrandbits
+        else if (!pool && r.k >= 4096) {                                 // a window of its own (enqueue_sample_chain)
+            py += big_sample_window(n, set_path_need_bounded(n, k));
+            n_big++;
+        } else {                                                         // small ranges share one window (host-cut / host-chain engines)
+            const StreamMoments m = small_sample_moments(n, k, (double)r.setsize);
+            e_small += m.e; var_small += m.v;
         }
         bool chain = P.block[MSIM_SN] != d;                              // an SNP that blocks rides the chain too
         for (int j = 0; j < r.n_types; j++) {
-            const uint64_t lo = j ? r.cdf_thr[j - 1] : 0;
-            if (!(r.cdf_thr[j] > lo && lo < (1ull << 53))) continue;
             const int t = r.types[j];
-            if (t == MSIM_SN) continue;
+            if (t == MSIM_SN || !type_drawable(r, j)) continue;
             chain = true;
             if (t == MSIM_TL || t == MSIM_TLI) has_tl = true;
             if (t == MSIM_IN) {
-                const double q = (double)(std::min<uint64_t>(r.cdf_thr[j], 1ull << 53) - lo) / 9007199254740992.0;
+                const double q = type_probability(r, j);
                 const double mx = (double)std::max<int64_t>(r.max_len[t], 1);
                 pool_mean += k * q * mx;                                 // (every insert at its longest: a bound, not an estimate)
                 pool_var += k * q * mx * mx;
@@ -410,16 +400,18 @@ int gpu_plan_make_room(Ctx *c, GpuPlan *g, const msim_range *ranges, int n_range
         if (chain) K_chain += k;
     }
     py += e_small + 16.0 * std::sqrt(var_small);
-    if (K_chain > 0) py += 2.0 * K_chain + 32.0 * std::sqrt(K_chain) + 4096.0;              // randint windows (acceptance >= 1/2)
+    if (K_chain > 0) py += randint_window(K_chain, 0.5);                                    // randint windows (acceptance >= 1/2)
     if (has_tl) py += 6.0 * K_chain + 16.0 * std::sqrt(25.0 * K_chain + 1.0) + 4096.0;      // __link_tls
     py += 4.0 * K + 16.0 * std::sqrt(4.0 * K) + 16384.0 + 3.0 * SNP_BLOCK2;                 // SNP draws (<= 4 words each, expected)
     py += 2.0 * 65536.0 + 8192.0 * n_big;
-    np = 2.0 * K + pool_mean + 16.0 * std::sqrt(pool_var) + 4096.0;
-    const double span = (double)(span_words(g) - MT_N);
-    *fits = true;
-    if (bad) return MSIM_OK;                                             // (the engines' eligibility refuses these themselves)
-    *fits = std::isfinite(py) && py < span && np < span;
-    if (!*fits) return MSIM_OK;
+    return StreamNeed{py, 2.0 * K + pool_mean + 16.0 * std::sqrt(pool_var) + 4096.0, bad};
+}
+
+int gpu_plan_make_room(Ctx *c, GpuPlan *g, const msim_range *ranges, int n_ranges, bool *fits) {
+    const StreamNeed need = stream_need(c->params, ranges, n_ranges);
+    const double py = need.py, np = need.np, span = (double)(span_words(g) - MT_N);
+    *fits = need.bad || (std::isfinite(py) && py < span && np < span);   // (bad: the engines' eligibility refuses these themselves)
+    if (need.bad || !*fits) return MSIM_OK;
     const GpuStream &s0 = g->s[0], &s1 = g->s[1];
     const bool live = s0.live || s1.live;
     const double at0 = s0.live ? (double)s0.pos : (double)MT_N, at1 = s1.live ? (double)s1.pos : (double)MT_N;
@@ -722,6 +714,29 @@ static int stream_to_device(Ctx *c, GpuPlan *g, int si) {
     return MSIM_OK;
 }
 
+// The engines' prologue, in two parts because the SNP sampler reserves its record table between them.
+// session_open: both host generators are device streams (nothing to do inside a session); the device PlanState and its mailbox exist.
+static int session_open(Ctx *c, GpuPlan *g) {
+    int rc;
+    if ((rc = stream_to_device(c, g, 0))) return rc;
+    if ((rc = stream_to_device(c, g, 1))) return rc;
+    if (!g->d_ps) MSIM_HIP(c, hipMalloc(&g->d_ps, sizeof(PlanState)));
+    if (!g->h_mail) MSIM_HIP(c, hipHostMalloc(&g->h_mail, sizeof(PlanState), hipHostMallocMapped));
+    return MSIM_OK;
+}
+// chain_open: t0 marks where unverified work starts; the device PlanState holds the stream position.  sampler = false (every
+// engine but the SNP sampler, which keeps an estimate of the position across contigs): that estimate ends here.
+static int chain_open(Ctx *c, GpuPlan *g, bool sampler) {
+    if (!g->t0) { MSIM_HIP(c, hipEventCreate(&g->t0)); MSIM_HIP(c, hipEventCreate(&g->t1)); }
+    if (!g->unverified) MSIM_HIP(c, hipEventRecord(g->t0, c->stream));
+    if (!g->ps_valid) {
+        hipLaunchKernelGGL(k_state_init, dim3(1), dim3(1), 0, c->stream, g->d_ps, (unsigned long long)g->s[0].pos);
+        g->ps_valid = true;
+    }
+    if (!sampler) { g->unverified = true; g->est_ok = false; }
+    return MSIM_OK;
+}
+
 // device stream -> host generator (any 624-word window ending at pos is a valid state)
 int gpu_plan_sync_to_host(Ctx *c, GpuPlan *g) {
     int frc = gpu_plan_finish(c, g);
@@ -750,8 +765,7 @@ int gpu_plan_sync_to_host(Ctx *c, GpuPlan *g) {
 
 bool gpu_plan_eligible(const Ctx *c, const msim_range *ranges, int n_ranges) {
     const msim_params &P = c->params;
-    int64_t d = P.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, P.block[t]);
+    const int64_t d = min_block(P);
     if (P.block[MSIM_SN] != d) return false;              // an SNP could block its successor
     int64_t prev_stop = -1;
     for (int i = 0; i < n_ranges; i++) {
@@ -762,17 +776,11 @@ bool gpu_plan_eligible(const Ctx *c, const msim_range *ranges, int n_ranges) {
         // (mutator.py:121, later range wins) -- only the host planner reproduces that
         if (r.start <= prev_stop) return false;
         prev_stop = r.stop;
-        const int64_t n = (r.stop - (r.k - 1) * d) - r.start;
+        const int64_t n = range_population(r, d);
         if (r.k < 0 || n < r.k) return false;             // ValueError: let the host planner raise it
         if (n <= r.setsize || n >= (1ll << 32)) return false;   // pool path / multi-word getrandbits
         if (r.start < 0 || r.stop >= (1ll << 32)) return false;
-        // type draw must be deterministic SN: every threshold 0 or >= 2^53
-        int zeros = 0;
-        for (int j = 0; j < r.n_types; j++) {
-            if (r.cdf_thr[j] == 0) zeros++;
-            else if (r.cdf_thr[j] < (1ull << 53)) return false;
-        }
-        if (zeros >= r.n_types || r.types[zeros] != MSIM_SN) return false;
+        if (!range_is_deterministic_sn(r)) return false;  // the type draw: every threshold 0 or >= 2^53
     }
     return true;                                          // (a contig that draws nothing is trivially fine)
 }
@@ -844,6 +852,15 @@ static int wait_if_pending(Ctx *c, bool &pending, hipEvent_t ev) {
     return MSIM_OK;
 }
 
+// Capacity of one sub-list of a bin: expected k/n_bins per bin (the last bin is partial), 16 sigma + slack.  Sub-list s of a bin is
+// filled by the scatter workgroups with index == s (mod 16).  Only the workgroups up to the one holding the k-th accepted draw
+// contribute (the window has slack behind it), each at most 8192 * p_acc draws, of which the bin's share is min(1, 2^20 / n).
+static uint32_t sample_bin_cap(uint64_t n, uint32_t k, double p_acc) {
+    const uint32_t nbk = (uint32_t)((double)k / p_acc / SPL_BLOCK) + 3;
+    const double mean = (double)((nbk + BIN_SUBS - 1) / BIN_SUBS) * SPL_BLOCK * p_acc * std::min(1.0, (double)BIN_VALUES / (double)n);
+    return (uint32_t)std::min<double>((double)k + 16.0, 1.25 * mean + 16.0 * std::sqrt(mean) + 512.0);
+}
+
 // Enqueue the chain of one sampled range on the plan stream: where does random.sample() end (exact stream
 // cut in the device PlanState) and which values did it draw (the set, as a bitmap in S.bitmap).
 struct SampleLaunch { SampleSet *S; uint32_t W, bmw, bnb; };
@@ -858,13 +875,10 @@ static int enqueue_sample_chain(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
     PlanState *ps = ps_other ? ps_other : g->d_ps;
     int rc;
     const uint32_t k = (uint32_t)r.k;
-    const uint64_t n = (uint64_t)((r.stop - (r.k - 1) * d) - r.start);
+    const uint64_t n = (uint64_t)range_population(r, d);
     const int bits = bit_length64(n);
-    const double p_acc = (double)n / (double)(1ull << bits);
-    // accepted draws needed ~ -n ln(1 - k/n) (coupon collector); window = that / p_acc, 16-sigma margins
-    const double need_acc = -(double)n * std::log1p(-(double)k / (double)n);
-    const double target = need_acc + 16.0 * std::sqrt(need_acc) + 4096.0;
-    const double wd = target / p_acc + 16.0 * std::sqrt(target) / p_acc + 8192.0;
+    const double p_acc = randbelow_acceptance((double)n);
+    const double wd = big_sample_window((double)n, set_path_need((double)n, (double)k));
     if (wd >= 4.0e9) return fail(c, MSIM_ERR_UNSUPPORTED, "sample window beyond 2^32 words");
     const uint32_t W = (uint32_t)wd;
     SampleSet &S = g->sample[g->unit++ % N_SETS];
@@ -887,17 +901,8 @@ static int enqueue_sample_chain(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
     // ---- chain (plan stream): where does this sample end?
     const uint32_t n_bins = (uint32_t)((n + BIN_VALUES - 1) >> BIN_SHIFT);
     const bool binned = n_bins <= (uint32_t)MAX_BINS;
-    uint32_t bin_cap = 0;
+    const uint32_t bin_cap = binned ? sample_bin_cap(n, k, p_acc) : 0u;
     if (binned) {
-
-        // expected k/n_bins per bin (the last bin is partial), 16-sigma + slack capacity
-        // sub-list s of a bin is filled by the scatter workgroups with index == s (mod 16).  Only the
-        // workgroups up to the one holding the k-th accepted draw contribute (the window has slack
-        // behind it), each at most 8192 * p_acc draws, of which the bin's share is min(1, 2^20 / n).
-        const uint32_t nbk = (uint32_t)((double)k / p_acc / SPL_BLOCK) + 3;
-        const double mean = (double)((nbk + BIN_SUBS - 1) / BIN_SUBS) * SPL_BLOCK * p_acc *
-                            std::min(1.0, (double)BIN_VALUES / (double)n);
-        bin_cap = (uint32_t)std::min<double>((double)k + 16.0, 1.25 * mean + 16.0 * std::sqrt(mean) + 512.0);
         if ((rc = grow(c, (void **)&S.bins, &S.bins_cap, (size_t)n_bins * BIN_SUBS * bin_cap * sizeof(uint32_t), &grew))) return rc;
         if ((rc = grow(c, (void **)&S.cursors, &S.cursors_cap, (size_t)MAX_BINS * BIN_SUBS * sizeof(uint32_t), &grew))) return rc;
         if ((rc = grow(c, (void **)&S.bitmap, &S.bm_cap, (size_t)n_bins * BIN_WORDS * 4, &grew))) return rc;
@@ -961,12 +966,10 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
                                 bool &grew, SampleLaunch &out, bool &took, bool grouped, uint64_t expect, uint32_t soft_half) {
     int rc;
     const uint32_t K = (uint32_t)r.k;
-    const uint64_t n = (uint64_t)((r.stop - (r.k - 1) * d) - r.start);
+    const uint64_t n = (uint64_t)range_population(r, d);
     const int bits = bit_length64(n);
-    const double p_acc = (double)n / (double)(1ull << bits);
-    const double need_acc = -(double)n * std::log1p(-(double)K / (double)n);
-    const double target = need_acc + 16.0 * std::sqrt(need_acc) + 4096.0;
-    const double wd = target / p_acc + 16.0 * std::sqrt(target) / p_acc + 8192.0;
+    const double p_acc = randbelow_acceptance((double)n);
+    const double wd = big_sample_window((double)n, set_path_need((double)n, (double)K));
     if (wd >= 4.0e9) return fail(c, MSIM_ERR_UNSUPPORTED, "sample window beyond 2^32 words");
     const uint32_t W = (uint32_t)wd;                       // (sized for all K draws from H: the core needs fewer)
     const uint32_t F = (uint32_t)(H - lo);
@@ -991,9 +994,7 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
     const uint32_t bmw = (uint32_t)bm_words64;
     const uint32_t bnb = (bmw + BM_THREADS - 1) / BM_THREADS;
     const uint32_t n_bins = (uint32_t)((n + BIN_VALUES - 1) >> BIN_SHIFT);
-    const uint32_t nbk = (uint32_t)((double)K / p_acc / SPL_BLOCK) + 3;
-    const double mean = (double)((nbk + BIN_SUBS - 1) / BIN_SUBS) * SPL_BLOCK * p_acc * std::min(1.0, (double)BIN_VALUES / (double)n);
-    const uint32_t bin_cap = (uint32_t)std::min<double>((double)K + 16.0, 1.25 * mean + 16.0 * std::sqrt(mean) + 512.0);
+    const uint32_t bin_cap = sample_bin_cap(n, K, p_acc);
     if ((rc = grow(c, (void **)&S.cnt, &S.cnt_cap, (size_t)(nb + 2) * sizeof(uint32_t), &grew))) return rc;
     if ((rc = grow(c, (void **)&S.cnt2, &S.cnt2_cap, emit_cnt2_words(bmw) * sizeof(uint32_t), &grew))) return rc;   // (either train's layout: plan_kernels.h)
     if ((rc = grow(c, (void **)&S.acc, &S.acc_cap, (size_t)W * sizeof(uint32_t), &grew))) return rc;
@@ -1281,13 +1282,9 @@ StreamMoments snp_words_moments(uint64_t K, unsigned long long ti_lim) {
 // by gpu_plan_finish at the next synchronising call.
 int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, int n_ranges) {
     const msim_params &P = c->params;
-    int64_t d = P.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, P.block[t]);
+    const int64_t d = min_block(P);
     int rc;
-    if ((rc = stream_to_device(c, g, 0))) return rc;
-    if ((rc = stream_to_device(c, g, 1))) return rc;
-    if (!g->d_ps) MSIM_HIP(c, hipMalloc(&g->d_ps, sizeof(PlanState)));
-    if (!g->h_mail) MSIM_HIP(c, hipHostMalloc(&g->h_mail, sizeof(PlanState), hipHostMallocMapped));
+    if ((rc = session_open(c, g))) return rc;
     uint64_t K = 0;
     for (int i = 0; i < n_ranges; i++) K += (uint64_t)ranges[i].k;
     if (K >= (1ull << 31)) return fail(c, MSIM_ERR_UNSUPPORTED, "more than 2^31 mutations on one contig");
@@ -1307,12 +1304,7 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
     ct.all_snp = true;                                    // every record is an SNP: output offset == position
 
     GpuStream &py = g->s[0];
-    if (!g->t0) { MSIM_HIP(c, hipEventCreate(&g->t0)); MSIM_HIP(c, hipEventCreate(&g->t1)); }
-    if (!g->unverified) MSIM_HIP(c, hipEventRecord(g->t0, c->stream));
-    if (!g->ps_valid) {
-        hipLaunchKernelGGL(k_state_init, dim3(1), dim3(1), 0, c->stream, g->d_ps, (unsigned long long)py.pos);
-        g->ps_valid = true;
-    }
+    if ((rc = chain_open(c, g, true))) return rc;
     uint64_t pos_hi = py.pos;                             // upper bound of the device position
     uint64_t rec_base = 0;
     if (c->chain_only) { g->pass_chain_only++; g->sharded_rank = true; }
@@ -1358,7 +1350,7 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
         SampleLaunch sl;
         // moments of the words this sample consumes: A accepted draws until k distinct values (duplicates: a coupon collector's
         // first k), each after a geometric number of rejected words (_randbelow)
-        const double n_d = (double)((r.stop - (r.k - 1) * d) - r.start);
+        const double n_d = (double)range_population(r, d);
         const StreamMoments ms = sample_words_moments((uint64_t)n_d, (uint64_t)k);
         const double e_samp = ms.e, v_samp = ms.v;
         bool ahead = false;
@@ -1467,24 +1459,16 @@ static int grow_host(Ctx *c, void **p, size_t *cap, size_t want_bytes) {
     return MSIM_OK;
 }
 
-// Which non-SNP types can the type draw of this range produce?  (thresholds are cumulative: entry j is
-// drawn iff thr[j-1] < thr[j], with thr[-1] = 0, and only below 2^53)
-static bool range_type_drawable(const msim_range &r, int j) {
-    const uint64_t lo = j ? r.cdf_thr[j - 1] : 0;
-    return r.cdf_thr[j] > lo && lo < (1ull << 53);
-}
-
 static bool range_draws_translocations(const msim_range &r) {
     for (int j = 0; j < r.n_types; j++)
-        if ((r.types[j] == MSIM_TL || r.types[j] == MSIM_TLI) && range_type_drawable(r, j)) return true;
+        if ((r.types[j] == MSIM_TL || r.types[j] == MSIM_TLI) && type_drawable(r, j)) return true;
     return false;
 }
 
 // SV mix on one large set-path range (ARGS mode: one range per contig): SNPs plus any of IN/DE/DU/IV/TL/TLI.
 bool gpu_plan_mixed_eligible(const Ctx *c, const msim_range *ranges, int n_ranges) {
     const msim_params &P = c->params;
-    int64_t d = P.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, P.block[t]);
+    const int64_t d = min_block(P);
     if (P.block[MSIM_SN] != d) return false;              // an SNP could block its successor: the chain needs all candidates
     const msim_range *one = nullptr;
     for (int i = 0; i < n_ranges; i++) {
@@ -1495,12 +1479,12 @@ bool gpu_plan_mixed_eligible(const Ctx *c, const msim_range *ranges, int n_range
     if (!one) return false;
     const msim_range &r = *one;
     if (r.k < 4096 || r.k >= (1ll << 31)) return false;
-    const int64_t n = (r.stop - (r.k - 1) * d) - r.start;
+    const int64_t n = range_population(r, d);
     if (n < r.k || n <= r.setsize || n >= (1ll << 32)) return false;
     if (r.start < 0 || r.stop >= (1ll << 32)) return false;
     if (r.n_types < 1 || r.n_types > 8) return false;
     for (int j = 0; j < r.n_types; j++) {
-        if (!range_type_drawable(r, j)) continue;
+        if (!type_drawable(r, j)) continue;
         const int t = r.types[j];
         if (t == MSIM_SN) continue;
         if (t == MSIM_TLI) continue;                      // an insertion site: no length draw
@@ -1821,26 +1805,14 @@ static int mixed_link_translocations(Ctx *c, GpuPlan *g, MixedSet &M, uint32_t n
 
 int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, int n_ranges) {
     const msim_params &P = c->params;
-    int64_t d = P.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, P.block[t]);
+    const int64_t d = min_block(P);
     const msim_range *rp = nullptr;
     for (int i = 0; i < n_ranges; i++) if (ranges[i].k) rp = &ranges[i];
     const msim_range &r = *rp;
     const uint32_t k = (uint32_t)r.k;
     int rc;
-    if ((rc = stream_to_device(c, g, 0))) return rc;
-    if ((rc = stream_to_device(c, g, 1))) return rc;
-    if (!g->d_ps) MSIM_HIP(c, hipMalloc(&g->d_ps, sizeof(PlanState)));
-    if (!g->h_mail) MSIM_HIP(c, hipHostMalloc(&g->h_mail, sizeof(PlanState), hipHostMallocMapped));
+    if ((rc = session_open(c, g)) || (rc = chain_open(c, g, false))) return rc;
     GpuStream &py = g->s[0], &np = g->s[1];
-    if (!g->t0) { MSIM_HIP(c, hipEventCreate(&g->t0)); MSIM_HIP(c, hipEventCreate(&g->t1)); }
-    if (!g->unverified) MSIM_HIP(c, hipEventRecord(g->t0, c->stream));
-    if (!g->ps_valid) {
-        hipLaunchKernelGGL(k_state_init, dim3(1), dim3(1), 0, c->stream, g->d_ps, (unsigned long long)py.pos);
-        g->ps_valid = true;
-    }
-    g->unverified = true;
-    g->est_ok = false;                                    // (the SNP sampler's estimate of the position ends here)
     bool grew = false;
     MixedSet &M = g->mixed[g->mixed_unit++ % N_SETS];
     if ((rc = wait_if_pending(c, M.pending, M.emit_done))) return rc;          // its last emit may still read it
@@ -1895,11 +1867,8 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
     // is known here: a 16-sigma bound of the type draw's binomial is copied (the rest, if ever, afterwards).
     if ((rc = ensure_signals(c, g))) return rc;
     double q_nsn = 0;
-    for (int j = 0; j < r.n_types; j++) {
-        const uint64_t lo = j ? r.cdf_thr[j - 1] : 0;
-        if (r.types[j] != MSIM_SN && r.cdf_thr[j] > lo && lo < (1ull << 53))
-            q_nsn += (double)(std::min<uint64_t>(r.cdf_thr[j], 1ull << 53) - lo) / 9007199254740992.0;
-    }
+    for (int j = 0; j < r.n_types; j++)
+        if (r.types[j] != MSIM_SN && type_drawable(r, j)) q_nsn += type_probability(r, j);
     q_nsn = std::min(1.0, q_nsn);
     const uint32_t n_hi = (uint32_t)std::min<double>(k, q_nsn * k + 16.0 * std::sqrt(q_nsn * (1.0 - q_nsn) * k) + 64.0);
     const size_t ccut[4] = {0, (size_t)n_hi / 8, (size_t)n_hi / 2, (size_t)n_hi};
@@ -1922,14 +1891,8 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
     // The accept tables of the boundary walk depend on where the sample ended (the device knows) and on the window's size --
     // which follows from the number of non-SNP candidates, known only after the poll: they are launched BEHIND the mailbox
     // kernel over a 16-sigma bound of it, so that they are under way while the host still polls.
-    double acc_min = 1.0;                                  // least acceptance of randint among the types this range draws
-    for (int j = 0; j < r.n_types; j++) {
-        const int t = r.types[j];
-        if (t == MSIM_SN || t == MSIM_TLI || !range_type_drawable(r, j)) continue;
-        const int64_t w = r.max_len[t] - r.min_len[t] + 1;
-        if (w >= 1 && w < (1ll << 32)) acc_min = std::min(acc_min, (double)w / (double)(1ull << bit_length64((uint64_t)w)));
-    }
-    auto window_of = [&](double n) { return n / acc_min + 16.0 * std::sqrt(n) / acc_min + 4096.0; };
+    const double acc_min = randint_acceptance_min(r);      // least acceptance of randint among the types this range draws
+    auto window_of = [&](double n) { return randint_window(n, acc_min); };
     ChainClasses cc;
     const bool tables = chain_classes(r, cc);              // the host walks "next accepted draw" tables (ctx.h)
     const uint32_t lg = chain_lg_rows(cc);
@@ -2093,27 +2056,16 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
 // but the cuts: the device repeats the acceptance test over every range's interval, builds the sorted sample
 // in a contig-wide bitmap and from it the records (k_interval_bits, k_walk_expand); the SNP transducer of
 // section 5 and APPLY follow as for every other engine.
-static bool range_is_deterministic_sn(const msim_range &r) {
-    if (r.n_types < 1 || r.n_types > 8) return false;
-    int zeros = 0;
-    for (int j = 0; j < r.n_types; j++) {
-        if (r.cdf_thr[j] == 0) zeros++;
-        else if (r.cdf_thr[j] < (1ull << 53)) return false;
-    }
-    return zeros < r.n_types && r.types[zeros] == MSIM_SN;
-}
-
 bool gpu_plan_hostsample_eligible(const Ctx *c, const msim_range *ranges, int n_ranges) {
     const msim_params &P = c->params;
-    int64_t d = P.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, P.block[t]);
+    const int64_t d = min_block(P);
     if (P.block[MSIM_SN] != d) return false;
     int64_t prev_stop = -1;
     uint64_t K = 0;
     for (int i = 0; i < n_ranges; i++) {
         const msim_range &r = ranges[i];
         if (r.k == 0) continue;
-        const int64_t n = (r.stop - (r.k - 1) * d) - r.start;
+        const int64_t n = range_population(r, d);
         if (r.k < 0 || n < r.k || n >= (1ll << 32)) return false;        // ValueError / multi-word: host planner decides
         if (r.start <= prev_stop || r.stop >= (1ll << 32)) return false; // overlapping or unsorted ranges: dict semantics
         if (!range_is_deterministic_sn(r)) return false;
@@ -2128,22 +2080,10 @@ int plan_contig_gpu_hostsample(Ctx *c, GpuPlan *g, Contig &ct, const msim_range 
     static std::chrono::steady_clock::time_point last_exit;
     const auto tp0 = std::chrono::steady_clock::now();
     const msim_params &P = c->params;
-    int64_t d = P.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, P.block[t]);
+    const int64_t d = min_block(P);
     int rc;
-    if ((rc = stream_to_device(c, g, 0))) return rc;
-    if ((rc = stream_to_device(c, g, 1))) return rc;
-    if (!g->d_ps) MSIM_HIP(c, hipMalloc(&g->d_ps, sizeof(PlanState)));
-    if (!g->h_mail) MSIM_HIP(c, hipHostMalloc(&g->h_mail, sizeof(PlanState), hipHostMallocMapped));
+    if ((rc = session_open(c, g)) || (rc = chain_open(c, g, false))) return rc;
     GpuStream &py = g->s[0];
-    if (!g->t0) { MSIM_HIP(c, hipEventCreate(&g->t0)); MSIM_HIP(c, hipEventCreate(&g->t1)); }
-    if (!g->unverified) MSIM_HIP(c, hipEventRecord(g->t0, c->stream));
-    if (!g->ps_valid) {
-        hipLaunchKernelGGL(k_state_init, dim3(1), dim3(1), 0, c->stream, g->d_ps, (unsigned long long)py.pos);
-        g->ps_valid = true;
-    }
-    g->unverified = true;
-    g->est_ok = false;                                    // (the SNP sampler's estimate of the position ends here)
     // word window: expected consumption of every sample + 16 sigma of the total
     uint64_t K = 0, K_pool = 0;
     uint32_t n_draw = 0;
@@ -2152,13 +2092,11 @@ int plan_contig_gpu_hostsample(Ctx *c, GpuPlan *g, Contig &ct, const msim_range 
         const msim_range &r = ranges[i];
         if (r.k == 0) continue;
         n_draw++;
-        const double k = (double)r.k, n = (double)((r.stop - (r.k - 1) * d) - r.start);
+        const double k = (double)r.k, n = (double)range_population(r, d);
         K += (uint64_t)r.k;
-        if (n <= (double)r.setsize) { K_pool += (uint64_t)r.k; e_words += 2.0 * k; var += 2.0 * k; continue; }   // pool path: < 2 words per draw
-        const double p_acc = n / (double)(1ull << bit_length64((uint64_t)n));
-        const double need = k >= n ? 64.0 * k : -n * std::log1p(-k / n);                // coupon collector
-        e_words += need / p_acc;
-        var += need * (1.0 - p_acc) / (p_acc * p_acc) + 4.0 * (need - k) / (p_acc * p_acc) + need / p_acc;
+        if (n <= (double)r.setsize) K_pool += (uint64_t)r.k;
+        const StreamMoments m = small_sample_moments(n, k, (double)r.setsize);
+        e_words += m.e; var += m.v;
     }
     const double wd = e_words + 16.0 * std::sqrt(var) + 65536.0;
     if (wd >= 4.0e9) return fail(c, MSIM_ERR_UNSUPPORTED, "sample window beyond 2^32 words");
@@ -2212,7 +2150,7 @@ int plan_contig_gpu_hostsample(Ctx *c, GpuPlan *g, Contig &ct, const msim_range 
         for (int i = 0; i < n_ranges; i++) {
             const msim_range &r = ranges[i];
             if (r.k == 0) continue;
-            const int64_t n = (r.stop - (r.k - 1) * d) - r.start;
+            const int64_t n = range_population(r, d);
             WalkRange w;
             w.start = (uint32_t)r.start; w.k = (uint32_t)r.k; w.n = (uint32_t)n; w.rec_base = base;
             w.pool = n <= r.setsize ? 1u : 0u;
@@ -2334,8 +2272,7 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
     static const bool prof = getenv("MSIM_CHAIN_PROF") != nullptr;
     const auto tp0 = std::chrono::steady_clock::now();
     const msim_params &P = c->params;
-    int64_t d = P.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, P.block[t]);
+    const int64_t d = min_block(P);
     int rc;
     if (g->mm_for != ranges || g->mm_n != n_ranges) {
         if (!multimix_prepare(c, ct.len, ranges, n_ranges, g->mm_sets)) return fail(c, MSIM_ERR_UNSUPPORTED, "outside the host-chain engine");
@@ -2344,34 +2281,20 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
     const MixSets &ms = g->mm_sets;
     const uint32_t K = (uint32_t)ms.K, n_draw = ms.n_draw, n_sets = (uint32_t)ms.rep.size();
     const uint32_t lg = chain_lg_rows(ms.gcc);
-    if ((rc = stream_to_device(c, g, 0))) return rc;
-    if ((rc = stream_to_device(c, g, 1))) return rc;
-    if (!g->d_ps) MSIM_HIP(c, hipMalloc(&g->d_ps, sizeof(PlanState)));
-    if (!g->h_mail) MSIM_HIP(c, hipHostMalloc(&g->h_mail, sizeof(PlanState), hipHostMallocMapped));
+    if ((rc = session_open(c, g)) || (rc = chain_open(c, g, false))) return rc;
     GpuStream &py = g->s[0], &np = g->s[1];
-    if (!g->t0) { MSIM_HIP(c, hipEventCreate(&g->t0)); MSIM_HIP(c, hipEventCreate(&g->t1)); }
-    if (!g->unverified) MSIM_HIP(c, hipEventRecord(g->t0, c->stream));
-    if (!g->ps_valid) {
-        hipLaunchKernelGGL(k_state_init, dim3(1), dim3(1), 0, c->stream, g->d_ps, (unsigned long long)py.pos);
-        g->ps_valid = true;
-    }
-    g->unverified = true;
-    g->est_ok = false;                                    // (the SNP sampler's estimate of the position ends here)
     // ---- sizes: the word window (every sample + every randint, 16 sigma of the total) and the chain length
     double e_words = 0, var = 0, e_ch = 0, var_ch = 0;
     std::vector<double> q_nsn(n_sets, 0.0), acc_min(n_sets, 1.0), q_tl(n_sets, 0.0);
     for (uint32_t s = 0; s < n_sets; s++) {
         const msim_range &r = ranges[ms.rep[s]];
         for (int j = 0; j < r.n_types; j++) {
-            if (!range_type_drawable(r, j) || r.types[j] == MSIM_SN) continue;
-            const uint64_t lo = j ? r.cdf_thr[j - 1] : 0;
-            const double q = (double)(std::min<uint64_t>(r.cdf_thr[j], 1ull << 53) - lo) / 9007199254740992.0;
+            if (!type_drawable(r, j) || r.types[j] == MSIM_SN) continue;
+            const double q = type_probability(r, j);
             q_nsn[s] += q;
             if (r.types[j] == MSIM_TL || r.types[j] == MSIM_TLI) q_tl[s] += q;
-            if (r.types[j] == MSIM_TLI) continue;                     // (draws nothing in the boundary pass)
-            const int64_t w = r.max_len[r.types[j]] - r.min_len[r.types[j]] + 1;
-            acc_min[s] = std::min(acc_min[s], (double)w / (double)(1ull << bit_length64((uint64_t)w)));
         }
+        acc_min[s] = randint_acceptance_min(r);                       // (multimix_prepare let only widths 1 .. 2^24 - 1 through)
         q_nsn[s] = std::min(1.0, q_nsn[s]);
     }
     {
@@ -2380,14 +2303,9 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
             const msim_range &r = ranges[i];
             if (r.k == 0) continue;
             const uint32_t s = ms.set_of[di++];
-            const double k = (double)r.k, n = (double)((r.stop - (r.k - 1) * d) - r.start);
-            if (n <= (double)r.setsize) { e_words += 2.0 * k; var += 2.0 * k; }           // pool path: < 2 words per draw
-            else {
-                const double p_acc = n / (double)(1ull << bit_length64((uint64_t)n));
-                const double need = k >= n ? 64.0 * k : -n * std::log1p(-k / n);          // coupon collector
-                e_words += need / p_acc;
-                var += need * (1.0 - p_acc) / (p_acc * p_acc) + 4.0 * (need - k) / (p_acc * p_acc) + need / p_acc;
-            }
+            const double k = (double)r.k, n = (double)range_population(r, d);
+            const StreamMoments sm = small_sample_moments(n, k, (double)r.setsize);
+            e_words += sm.e; var += sm.v;
             const double m = k * q_nsn[s];                                                 // randint draws: at most one per non-SNP
             e_ch += m; var_ch += m * (1.0 - q_nsn[s]);
             e_words += m / acc_min[s];

@@ -20,6 +20,7 @@
 #include <unordered_map>
 
 #include "ctx.h"
+#include "plan_windows.h"
 
 #if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
 #include <immintrin.h>
@@ -349,10 +350,8 @@ static bool chain_classes_add(const msim_range &r, ChainClasses &g, uint8_t cls_
     for (int t = 0; t < 8; t++) cls_of[t] = 0;
     for (int t : {MSIM_IN, MSIM_DE, MSIM_DU, MSIM_IV, MSIM_TL}) {
         bool drawn = false;                                  // can the type draw of this range produce t at all?
-        for (int j = 0; j < r.n_types && j < 8; j++) {
-            const uint64_t lo = j ? r.cdf_thr[j - 1] : 0;
-            if (r.types[j] == t && r.cdf_thr[j] > lo && lo < (1ull << 53)) drawn = true;
-        }
+        for (int j = 0; j < r.n_types && j < 8; j++)
+            if (r.types[j] == t && type_drawable(r, j)) drawn = true;
         if (!drawn) continue;                                // its length bounds do not matter (class 0 is never looked up)
         const int64_t w = r.max_len[t] - r.min_len[t] + 1;
         if (w < 1 || w >= (1ll << 24)) return false;                 // value field of a table entry: 24 bits (23 beyond four classes: below)
@@ -568,7 +567,7 @@ int cut_ranges_host(Ctx *c, const msim_range *ranges, int n_ranges, int64_t d, c
         const msim_range &r = ranges[ri];
         const int64_t k = r.k;
         if (k == 0) continue;
-        const int64_t n = (r.stop - (k - 1) * d) - r.start;          // util.py:104
+        const int64_t n = range_population(r, d);                // util.py:104
         if (k < 0 || k > n) return fail(c, MSIM_ERR_VALUE, "Sample larger than population or is negative");
         if (n >= (1ll << 32)) return fail(c, MSIM_ERR_UNSUPPORTED, "sampling range of 2^32 or more positions");
         if (w >= (1ull << 32)) return overflow();
@@ -665,7 +664,7 @@ static inline int sample_one_range(const msim_range &r, int64_t d, const uint32_
     size_t w = *w_io, at = 0;
     SP_T0();
     const int64_t k = r.k;
-    const int64_t n = (r.stop - (k - 1) * d) - r.start;              // util.py:104
+    const int64_t n = range_population(r, d);                    // util.py:104
     if (k < 0 || k > n) return -1;
     if (n >= (1ll << 32)) return -2;
     const uint32_t base = (uint32_t)r.start, dd = (uint32_t)d;
@@ -804,16 +803,10 @@ int sample_ranges_host(Ctx *c, const msim_range *ranges, int n_ranges, int64_t d
 // General host-chain engine (ctx.h).  Per drawing range, in stream order: sample() -> sorted positions; the
 // candidates on the chain (types known by ordinal) walk the boundary pass over the accept tables; the stream
 // position after the walk is where the next range's sample starts.
-static bool type_drawable(const msim_range &r, int j) {
-    const uint64_t lo = j ? r.cdf_thr[j - 1] : 0;
-    return r.cdf_thr[j] > lo && lo < (1ull << 53);
-}
-
 bool multimix_prepare(const Ctx *c, uint64_t L, const msim_range *ranges, int n_ranges, MixSets &ms) {
     ms = MixSets{};
     const msim_params &P = c->params;
-    int64_t d = P.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, P.block[t]);
+    const int64_t d = min_block(P);
     if (L >= (1ull << 31)) return false;                              // ChainWalk's clamp arithmetic
     for (int t = 1; t <= 7; t++)
         if (P.block[t] >= (1ll << 31)) return false;
@@ -825,7 +818,7 @@ bool multimix_prepare(const Ctx *c, uint64_t L, const msim_range *ranges, int n_
     for (int i = 0; i < n_ranges; i++) {
         const msim_range &r = ranges[i];
         if (r.k == 0) continue;                                       // draws nothing (mutator.py:163-164)
-        const int64_t n = (r.stop - (r.k - 1) * d) - r.start;
+        const int64_t n = range_population(r, d);
         if (r.k < 0 || n < r.k || n >= (1ll << 32)) return false;     // ValueError / multi-word getrandbits: host planner
         if (r.start <= prev_stop || r.start < 0 || r.stop > (int64_t)L) return false;   // overlapping / unsorted / outside
         prev_stop = r.stop;
@@ -1196,8 +1189,7 @@ int multimix_walk_host(Ctx *c, uint64_t L, const msim_range *ranges, int n_range
 // records) -- same algorithm, no kernels -- so the CPU tier can compare it with plan_contig_host.
 int multimix_plan_emulated(Ctx *c, uint64_t L, const msim_range *ranges, int n_ranges, HostPlan &out) {
     const msim_params &P = c->params;
-    int64_t d = P.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, P.block[t]);
+    const int64_t d = min_block(P);
     MixSets ms;
     if (!multimix_prepare(c, L, ranges, n_ranges, ms)) return fail(c, MSIM_ERR_UNSUPPORTED, "outside the host-chain engine");
     const size_t K = (size_t)ms.K;
@@ -1288,8 +1280,7 @@ int multimix_plan_emulated(Ctx *c, uint64_t L, const msim_range *ranges, int n_r
 int plan_contig_host(Ctx *c, uint64_t L, const msim_range *ranges, int n_ranges, HostPlan &out) {
     const auto t0 = std::chrono::steady_clock::now();
     const msim_params &P = c->params;
-    int64_t d = P.block[1];
-    for (int t = 2; t <= 7; t++) d = std::min(d, P.block[t]);       // min(mut_block.values())
+    const int64_t d = min_block(P);                                 // min(mut_block.values())
     const int64_t chrom_len = (int64_t)L;
 
     std::vector<Cand> all;                                           // `muts` of mutator.py:112
@@ -1300,7 +1291,7 @@ int plan_contig_host(Ctx *c, uint64_t L, const msim_range *ranges, int n_ranges,
         const msim_range &r = ranges[ri];
         if (r.n_types < 1 || r.n_types > 8) return fail(c, MSIM_ERR_ARG, "msim_range.n_types out of range");
         const int64_t k = r.k;
-        const int64_t n = (r.stop - (k - 1) * d) - r.start;          // util.py:104
+        const int64_t n = range_population(r, d);                // util.py:104
         int rc = sample_sorted(c, c->py, n, k, r.setsize, pos);
         if (rc) return rc;
         if (k == 0) continue;                                        // mutator.py:163-164
