@@ -276,6 +276,39 @@ int msim_render_vcf(const msim_record *recs, uint64_t n_records, const uint8_t *
                     const uint8_t *bases, uint64_t len, const char *seq_name,
                     char *out, uint64_t cap, uint64_t *needed);
 
+/* The same lines with a phased genotype column: gt[i] is record i's genotype byte (bit 0: on haplotype 1, bit 1: on haplotype 2;
+ * 1, 2 or 3 -- anything else: MSIM_ERR_ARG) and its line ends in "GT\t1|0", "0|1" or "1|1".  Indexed by RECORD: a suppressed
+ * line shifts nothing.  gt == NULL: msim_render_vcf's bytes.  The cross-check of the device text of a genotyped contig.   */
+int msim_render_vcf_gt(const msim_record *recs, const uint8_t *gt, uint64_t n_records, const uint8_t *insert_pool,
+                       const uint8_t *bases, uint64_t len, const char *seq_name, char *out, uint64_t cap, uint64_t *needed);
+
+/* ---- diploid runs: two haplotypes of one record table (csrc/haplotype.hip) ------------------------------------------------ */
+/* A record table is a list of independent edits -- no record consumes input another one consumes, a TLI copies its span from
+ * the INPUT -- so any subset of it is a table APPLY takes.  A diploid run plans once, gives every record a GENOTYPE byte (bit 0:
+ * on haplotype 1, bit 1: on haplotype 2; never 0) kept beside the table (msim_record.rsv stays 0), and applies the two subsets.
+ *   msim_genotype_contig   draws the genotypes of a planned contig's table on the device; synchronises like msim_fetch_records
+ *                          (pending emission groups are flushed, device-side sizes collected).  Philox4x32-10, counter
+ *                          (record index in the full table, 0, seq, tag 20), key = the 64-bit `key`; neither MT19937 stream moves:
+ *                            heterozygous iff (low 64 bits >> 11) < het_thr   het_thr = ceil(F * 2^53) <= 2^53, the caller's float
+ *                            phase = bit 0 of the high 64 bits                0: haplotype 1, 1: haplotype 2
+ *                          else the record is on both.  A TLI takes the draw of the TL record whose pos is its `extra` (a
+ *                          translocation moves as a whole); without such a record in the table it keeps its own.
+ *   msim_set_genotypes / msim_fetch_genotypes   install / read the array (one byte per record of the FULL table; a value
+ *                          outside 1..3: MSIM_ERR_ARG).  Fetching from a contig without genotypes: MSIM_ERR_ARG.
+ *   msim_select_haplotype  hap 1 or 2: the records with that bit set, in table order, become the contig's ACTIVE table -- same
+ *                          pos / stop / extra / type / aux, same insert pool, host-known size; msim_apply_contig takes it through
+ *                          the device scan.  hap 0: the full table is the active one again.  The active table is what
+ *                          msim_apply_contig, msim_result_sizes, msim_fetch_records, msim_render_chain_device and the framed
+ *                          fetches behind APPLY read; a selection leaves the contig un-applied.  msim_render_vcf_device(_file)
+ *                          always render the FULL table, with the phased GT column once the contig has genotypes.
+ *                          Selecting 1 or 2 without genotypes: MSIM_ERR_ARG.
+ * A new plan of the contig, msim_clear and msim_release_result drop the genotypes and the selection.  On a host-only context
+ * the three calls run sequential restatements over the host's table.                                                     */
+int msim_genotype_contig(msim_ctx *ctx, int contig, uint64_t key, uint32_t seq, uint64_t het_thr);
+int msim_set_genotypes(msim_ctx *ctx, int contig, const uint8_t *gt);
+int msim_fetch_genotypes(msim_ctx *ctx, int contig, uint8_t *dst);
+int msim_select_haplotype(msim_ctx *ctx, int contig, int hap);
+
 /* ---- liftover chain: the record table as a coordinate map (UCSC chain format; liftOver, CrossMap, bcftools consensus -c) ---- */
 /* One chain per contig, reference = target, mutated = query, both on the + strand:
  *   chain <score> <tName> <tSize> + <tStart> <tEnd> <qName> <qSize> + <qStart> <qEnd> <id>\n

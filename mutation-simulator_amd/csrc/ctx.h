@@ -59,6 +59,25 @@ struct Contig {
     std::vector<msim_record> h_recs;
     std::vector<uint8_t> h_pool;
     std::vector<uint8_t> h_in;        // ... and the bases, once msim_vcf_host_bases gave them (the VCF replay's host parser reads them)
+    // diploid runs (haplotype.hip): one genotype byte per record of the FULL table (bit 0: on haplotype 1, bit 1: on haplotype 2),
+    // kept beside the table -- no kernel of PLAN or APPLY sees it.  While a haplotype is selected (hap != 0), d_recs / n_rec /
+    // all_snp ... above describe that haplotype's compacted table (the ACTIVE table: what APPLY, the chain and the fetches read)
+    // and `full` keeps the planner's; the VCF text always reads the full one (haplotype.hip: vcf_table).
+    bool have_gt = false;
+    uint8_t *d_gt = nullptr;
+    size_t cap_gt = 0;
+    std::vector<uint8_t> h_gt;        // (host-only context)
+    int hap = 0;                      // 0: the active table is the full one
+    msim_record *d_recs_hap = nullptr;    // hap == 0: the compacted tables' buffer (kept across selections); else: unused
+    size_t cap_recs_hap = 0;
+    struct FullTable {                // hap != 0: the planner's table and what it had told APPLY about it
+        msim_record *d_recs = nullptr;
+        size_t cap_recs = 0;
+        uint64_t n_rec = 0;
+        bool all_snp = false, delta_known = false;
+        long long known_delta = 0;
+        std::vector<msim_record> h_recs;
+    } full;
 };
 
 constexpr uint64_t PAD = 64;          // slack after every byte buffer so 16-B vector accesses stay in bounds
@@ -157,6 +176,19 @@ bool deferred_apply_holds(const Ctx *c, int contig);
 // msim_api.hip: what the VCF replay (vcf_parse.hip) shares with the planners' installation path
 int ctx_drain(Ctx *c);                // everything enqueued has completed, deferred results collected
 void contig_reset(Contig &g);         // forget a contig's plan / apply results (buffers stay allocated)
+// haplotype.hip: the full table becomes the active one again (pointers only, nothing is launched); drop the genotypes
+void hap_restore_full(Contig &g);
+void hap_forget(Contig &g);
+int hap_free(Ctx *c, Contig &g);
+// the table the VCF text is rendered from: the full one, whichever is active
+struct TableView { const msim_record *d_recs; uint64_t n_rec; bool all_snp; const uint8_t *d_gt; };
+TableView vcf_table(const Contig &g);
+// (the callers drained the context first)
+int hap_genotype(Ctx *c, Contig &g, uint64_t key, uint32_t seq, uint64_t het_thr);
+int hap_set_genotypes(Ctx *c, Contig &g, const uint8_t *gt);
+int hap_fetch_genotypes(Ctx *c, Contig &g, uint8_t *dst);
+int hap_select(Ctx *c, Contig &g, int hap);
+uint32_t hap_block();                  // records of a workgroup of the compaction kernels, for the tests' edge cases
 int table_install(Ctx *c, Contig *g, std::vector<msim_record> &recs, std::vector<uint8_t> &pool, bool empty);   // install_host_table
 int table_check(Ctx *c, uint64_t L, const msim_record *recs, uint64_t n, uint64_t pool_len, long long *delta, uint64_t *bad_index,
                 const char **bad_what);                                                                       // check_record_table

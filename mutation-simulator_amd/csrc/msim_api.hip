@@ -178,6 +178,7 @@ static void build_lut(uint8_t *lut) {
 static void reset_contig(Contig &g);
 void contig_reset(Contig &g) { reset_contig(g); }
 static void reset_contig(Contig &g) {   // (callers also drop the context's text cache: see text_kind)
+    hap_forget(g);                                         // (a selected haplotype's table, the genotypes: gone with the plan)
     g.planned = g.applied = false;
     g.defer_apply = false;
     g.tile_index_by_plan = false;
@@ -193,6 +194,10 @@ static void reset_contig(Contig &g) {   // (callers also drop the context's text
 }
 
 static int free_contig(Ctx *c, Contig &g, bool keep_input) {
+    {
+        const int rc = hap_free(c, g);
+        if (rc) return rc;
+    }
     if (g.d_recs) { MSIM_HIP(c, hipFree(g.d_recs)); g.d_recs = nullptr; }
     if (g.d_pool) { MSIM_HIP(c, hipFree(g.d_pool)); g.d_pool = nullptr; }
     if (g.d_out) { MSIM_HIP(c, hipFree(g.d_out)); g.d_out = nullptr; }
@@ -842,6 +847,73 @@ int msim_release_result(msim_ctx *p, int contig) {
     }
     return free_contig(c, *g, true);
 }
+
+// ---- diploid runs: genotypes beside the record table, one haplotype's records as the active table (haplotype.hip) --------
+static int genotyped_contig(Ctx *c, int contig, bool need_gt, Contig **out) {
+    Contig *g = get_contig(c, contig);
+    if (!g) return MSIM_ERR_ARG;
+    if (!g->planned) return fail(c, MSIM_ERR_ARG, "contig has not been planned");
+    if (need_gt && !g->have_gt) return fail(c, MSIM_ERR_ARG, "contig has no genotypes (msim_genotype_contig / msim_set_genotypes)");
+    const int rc = drain(c);                               // the table is complete, its sizes are collected, nothing reads it
+    if (rc) return rc;
+    c->text_kind = 0;
+    *out = g;
+    return MSIM_OK;
+}
+
+int msim_genotype_contig(msim_ctx *p, int contig, uint64_t key, uint32_t seq, uint64_t het_thr) {
+    CTX_FLUSHED(c, p)
+    if (!c || het_thr > (1ull << 53)) return MSIM_ERR_ARG;
+    Contig *g;
+    const int rc = genotyped_contig(c, contig, false, &g);
+    if (rc) return rc;
+    TraceRange tr("msim genotype draw");
+    return hap_genotype(c, *g, key, seq, het_thr);
+}
+
+int msim_set_genotypes(msim_ctx *p, int contig, const uint8_t *gt) {
+    CTX_FLUSHED(c, p)
+    if (!c) return MSIM_ERR_ARG;
+    Contig *g;
+    const int rc = genotyped_contig(c, contig, false, &g);
+    if (rc) return rc;
+    if (!gt && (g->hap ? g->full.n_rec : g->n_rec)) return MSIM_ERR_ARG;
+    return hap_set_genotypes(c, *g, gt);
+}
+
+int msim_fetch_genotypes(msim_ctx *p, int contig, uint8_t *dst) {
+    CTX_FLUSHED(c, p)
+    if (!c) return MSIM_ERR_ARG;
+    Contig *g;
+    const int rc = genotyped_contig(c, contig, true, &g);
+    if (rc) return rc;
+    if (!dst && (g->hap ? g->full.n_rec : g->n_rec)) return MSIM_ERR_ARG;
+    return hap_fetch_genotypes(c, *g, dst);
+}
+
+// Ordering of a diploid run's second haplotype against its first.  The compacted table, d_off, the tile index and d_out are the
+// contig's own buffers, and the second haplotype's selection and APPLY write all of them again.  Who may still read them?
+//   - the first haplotype's APPLY (tile index, rewrite: the contig's apply stream) reads the table and d_off and writes d_out;
+//   - its FASTA text: k_frame reads d_out on the context's stream and writes a buffer of the FASTA output channel; what the
+//     channel has in flight afterwards -- up to two transfers, device -> pinned ring -> file on the channel's own stream --
+//     reads THAT buffer, never d_out (file_io.hip: file_enqueue records its event behind k_frame and returns);
+//   - its liftover chain: kernels on the context's stream over the table, waited for inside the call.
+// genotyped_contig() drains the context before anything is selected: apply_finish waits for every APPLY in flight on whichever
+// stream it runs, then the context's stream and the emit stream are waited for -- k_frame has read the last byte of d_out, and
+// the channel's queued transfers own their bytes.  So the selection needs no event of its own, and none of the queued
+// transfers has to finish first: the second haplotype's APPLY overlaps the first one's way to its file.
+int msim_select_haplotype(msim_ctx *p, int contig, int hap) {
+    CTX_FLUSHED(c, p)
+    if (!c || hap < 0 || hap > 2) return MSIM_ERR_ARG;
+    Contig *g;
+    const int rc = genotyped_contig(c, contig, hap != 0, &g);
+    if (rc) return rc;
+    TraceRange tr("msim select haplotype");
+    return hap_select(c, *g, hap);
+}
+
+// test support: records of a workgroup of the compaction kernels
+uint32_t msim_dbg_hap_block(void) { return hap_block(); }
 
 // ---- text on the device -------------------------------------------------
 static int text_copy_out(Ctx *c, uint8_t *out, uint64_t cap, uint64_t *needed) {

@@ -46,19 +46,22 @@ struct Sink {
 inline void line_head(Sink &s, const char *name, size_t name_len, uint64_t start) {
     s.put(name, name_len); s.put('\t'); s.num(start); s.lit("\t.\t");
 }
-inline void line_tail(Sink &s, const char *svtype, uint64_t end, uint64_t len) {
+// gt: the record's genotype byte (bit 0: on haplotype 1, bit 1: on haplotype 2) -> "a|b"; 0: the haploid "1"
+inline void line_tail(Sink &s, const char *svtype, uint64_t end, uint64_t len, uint8_t gt) {
     s.lit("\t.\t.\t");
     if (svtype) { s.lit("SVTYPE="); s.lit(svtype); s.lit(";END="); s.num(end); s.lit(";SVLEN="); s.num(len); }
     else s.put('.');
-    s.lit("\tGT\t1\n");
+    if (!gt) { s.lit("\tGT\t1\n"); return; }
+    s.lit("\tGT\t"); s.put((char)('0' + (gt & 1))); s.put('|'); s.put((char)('0' + ((gt >> 1) & 1))); s.put('\n');
 }
 
 uint64_t render(const msim_record *recs, uint64_t n, const uint8_t *pool, const uint8_t *in, uint64_t L,
-                const char *name, char *out) {
+                const char *name, char *out, const uint8_t *gt = nullptr) {
     Sink s(out);
     const size_t name_len = strlen(name);
     for (uint64_t i = 0; i < n; i++) {
         const msim_record &r = recs[i];
+        const uint8_t g = gt ? gt[i] : (uint8_t)0;                   // (indexed by record: a suppressed line shifts nothing)
         const uint64_t pos = r.pos, stop = r.stop;
         switch (r.type) {
             case MSIM_SN: {                                          // mutator.py:334-341
@@ -67,7 +70,7 @@ uint64_t render(const msim_record *recs, uint64_t n, const uint8_t *pool, const 
                 if (ref == alt) break;                               // vcf_writer.py:123
                 line_head(s, name, name_len, pos + 1);
                 s.put((char)ref); s.put('\t'); s.put((char)alt);
-                line_tail(s, nullptr, 0, 0);
+                line_tail(s, nullptr, 0, 0, g);
                 break;
             }
             case MSIM_IN: {                                          // mutator.py:343-358
@@ -77,12 +80,12 @@ uint64_t render(const msim_record *recs, uint64_t n, const uint8_t *pool, const 
                     const char ref = (char)T.conv[in[pos - 1]];
                     line_head(s, name, name_len, pos);
                     s.put(ref); s.put('\t'); s.put(ref); s.put((const char *)ins, len);
-                    line_tail(s, "INS", pos, len);
+                    line_tail(s, "INS", pos, len, g);
                 } else {
                     const char ref = (char)T.conv[in[0]];
                     line_head(s, name, name_len, 1);
                     s.put(ref); s.put('\t'); s.put((const char *)ins, len); s.put(ref);
-                    line_tail(s, "INS", 1, len);
+                    line_tail(s, "INS", 1, len, g);
                 }
                 break;
             }
@@ -101,7 +104,7 @@ uint64_t render(const msim_record *recs, uint64_t n, const uint8_t *pool, const 
                 if (rev) for (uint64_t q = 0; q < ilen; q++) s.put((char)T.comp[T.conv[in[hi - 1 - q]]]);
                 else for (uint64_t q = 0; q < ilen; q++) s.put((char)T.conv[in[src + q]]);
                 if (!after) s.put(ref);
-                line_tail(s, "INS:ME", start, ilen);
+                line_tail(s, "INS:ME", start, ilen, g);
                 break;
             }
             case MSIM_TL:
@@ -113,7 +116,7 @@ uint64_t render(const msim_record *recs, uint64_t n, const uint8_t *pool, const 
                 for (uint64_t q = lo; q < hi; q++) s.put((char)T.conv[in[q]]);
                 s.put('\t');
                 s.put((char)T.conv[in[pos > 0 ? lo : hi - 1]]);      // REF[0] / REF[-1]
-                line_tail(s, r.type == MSIM_DE ? "DEL" : "DEL:ME", end, stop - pos + 1);
+                line_tail(s, r.type == MSIM_DE ? "DEL" : "DEL:ME", end, stop - pos + 1, g);
                 break;
             }
             case MSIM_IV: {                                          // mutator.py:379-387
@@ -126,7 +129,7 @@ uint64_t render(const msim_record *recs, uint64_t n, const uint8_t *pool, const 
                 for (uint64_t q = 0; q < len; q++) s.put((char)T.conv[in[pos + q]]);
                 s.put('\t');
                 for (uint64_t q = 0; q < len; q++) s.put((char)T.comp[T.conv[in[stop - q]]]);
-                line_tail(s, "INV", stop + 1, 0);
+                line_tail(s, "INV", stop + 1, 0, g);
                 break;
             }
             case MSIM_DU: {                                          // mutator.py:389-399
@@ -134,7 +137,7 @@ uint64_t render(const msim_record *recs, uint64_t n, const uint8_t *pool, const 
                 line_head(s, name, name_len, pos + 1);
                 s.put((const char *)in + pos, len); s.put('\t');
                 s.put((const char *)in + pos, len); s.put((const char *)in + pos, len);
-                line_tail(s, "DUP", pos + len, len);
+                line_tail(s, "DUP", pos + len, len, g);
                 break;
             }
             default: break;
@@ -253,5 +256,20 @@ extern "C" int msim_render_vcf(const msim_record *recs, uint64_t n_records, cons
     if (!out) return MSIM_OK;
     if (cap < want) return MSIM_ERR_ARG;
     render(recs, n_records, insert_pool, bases, len, seq_name, out);
+    return MSIM_OK;
+}
+
+extern "C" int msim_render_vcf_gt(const msim_record *recs, const uint8_t *gt, uint64_t n_records, const uint8_t *insert_pool,
+                                  const uint8_t *bases, uint64_t len, const char *seq_name, char *out,
+                                  uint64_t cap, uint64_t *needed) {
+    if ((n_records && !recs) || !seq_name || !needed || (len && !bases)) return MSIM_ERR_ARG;
+    if (gt)
+        for (uint64_t i = 0; i < n_records; i++)
+            if (gt[i] < 1 || gt[i] > 3) return MSIM_ERR_ARG;
+    const uint64_t want = render(recs, n_records, insert_pool, bases, len, seq_name, nullptr, gt);
+    *needed = want;
+    if (!out) return MSIM_OK;
+    if (cap < want) return MSIM_ERR_ARG;
+    render(recs, n_records, insert_pool, bases, len, seq_name, out, gt);
     return MSIM_OK;
 }

@@ -312,8 +312,11 @@ __device__ __forceinline__ unsigned long long vcf_svname(uint32_t t, uint32_t &n
     return t == 1 ? INS : t == 2 ? DEL : t == 3 ? INV : t == 4 ? DUP : t == 5 ? INSME : DELME;
 }
 
-template <class S>
-__device__ __forceinline__ void vcf_emit(S &s, const VcfLine &d, const uint8_t *name, uint32_t name_len, const uint8_t *lut) {
+// GT (a genotyped contig, diploid runs): the sample column is the record's phased genotype "a|b" -- a = bit 0, b = bit 1 of its
+// genotype byte -- instead of the haploid "1": the line is two bytes longer.  A template parameter, so that a contig without
+// genotypes runs the instructions it always ran.
+template <bool GT, class S>
+__device__ __forceinline__ void vcf_emit(S &s, const VcfLine &d, const uint8_t *name, uint32_t name_len, const uint8_t *lut, uint32_t gt) {
     s.begin(d);
     s.name(name, name_len);
     s.put('\t');
@@ -337,7 +340,12 @@ __device__ __forceinline__ void vcf_emit(S &s, const VcfLine &d, const uint8_t *
     } else {
         s.put('.');
     }
-    s.lit("\tGT\t1\n");
+    if (GT) {
+        s.lit("\tGT\t");
+        s.chars((uint32_t)('0' + (gt & 1u)) | ((uint32_t)'|' << 8) | ((uint32_t)('0' + ((gt >> 1) & 1u)) << 16) | ((uint32_t)'\n' << 24), 4);
+    } else {
+        s.lit("\tGT\t1\n");
+    }
 }
 
 // Which waves the stage scheme cannot describe (wave-uniform): 64 lines spanning 4 GiB of text, source addresses beyond 2^48 (the
@@ -429,9 +437,9 @@ __device__ __forceinline__ void vcf_unit_store(const VcfUnit &u, char *__restric
 }
 
 // the line of an SNP record (mutator.py:334-341, vcf_writer.py:118-126) at p: name \t POS \t . \t REF \t ALT \t . \t . \t . \t GT \t 1 \n
-template <class P>
+template <bool GT, class P>
 __device__ __forceinline__ void snp_line(P p, const uint8_t *__restrict__ name, uint32_t name_len, unsigned long long start, int nd,
-                                         uint8_t ref, uint8_t alt) {
+                                         uint8_t ref, uint8_t alt, uint32_t gt) {
     for (uint32_t q = 0; q < name_len; q++) p[q] = (char)name[q];
     p += name_len;
     *p++ = '\t';
@@ -440,7 +448,8 @@ __device__ __forceinline__ void snp_line(P p, const uint8_t *__restrict__ name, 
     p += nd;
     const char tail[18] = {'\t', '.', '\t', (char)ref, '\t', (char)alt, '\t', '.', '\t', '.', '\t', '.', '\t', 'G', 'T', '\t', '1', '\n'};
 #pragma unroll
-    for (int q = 0; q < 18; q++) p[q] = tail[q];
+    for (int q = 0; q < (GT ? 16 : 18); q++) p[q] = tail[q];
+    if (GT) { p[16] = (char)('0' + (gt & 1u)); p[17] = '|'; p[18] = (char)('0' + ((gt >> 1) & 1u)); p[19] = '\n'; }
 }
 
 // len_io: the lines' lengths -- written by the length pass, read by the write pass.  ra: REF | ALT << 8 of every SNP record, left
@@ -464,7 +473,7 @@ constexpr uint32_t VCF_O_PCS = VCF_O_GS + VCF_UNITS * 4;                        
 constexpr uint32_t VCF_O_PRE = VCF_O_PCS + 64 * VCF_SLOTS * sizeof(VcfPiece);          // u32[64 * VCF_SLOTS + 1] (+ pad)
 constexpr uint32_t VCF_WAVE_LDS = VCF_O_PRE + (64 * VCF_SLOTS + 4) * 4;
 
-template <bool WRITE, bool ALL_SNP>
+template <bool WRITE, bool ALL_SNP, bool GT>
 __global__ __launch_bounds__(TX_THREADS) void k_vcf_lines(const msim_record *__restrict__ recs, uint32_t n_rec,
                                                           const uint8_t *__restrict__ pool,
                                                           const uint8_t *__restrict__ in, unsigned long long L,
@@ -472,7 +481,8 @@ __global__ __launch_bounds__(TX_THREADS) void k_vcf_lines(const msim_record *__r
                                                           const uint8_t *__restrict__ lut_g,
                                                           uint32_t *__restrict__ len_io, uint16_t *__restrict__ ra,
                                                           const unsigned long long *__restrict__ off,
-                                                          char *__restrict__ text, uint32_t plain) {
+                                                          char *__restrict__ text, uint32_t plain,
+                                                          const uint8_t *__restrict__ gt_g) {
     __shared__ uint8_t lut[1280];
     __shared__ uint8_t lname[64];                                        // the sequence name (every line starts with it)
     constexpr uint32_t WB = !WRITE ? 16 : ALL_SNP ? VCF_STAGE : VCF_WAVE_LDS;
@@ -489,6 +499,7 @@ __global__ __launch_bounds__(TX_THREADS) void k_vcf_lines(const msim_record *__r
     const bool valid = mine < n_rec;
     msim_record my{};
     if (valid) my = recs[mine];
+    const uint32_t my_gt = GT && valid ? gt_g[mine] : 0u;                // (by record, not by line: suppressed lines shift nothing)
     const bool is_snp = ALL_SNP || my.type == MSIM_SN;
     if (!WRITE) {                                                        // ---- length pass
         if (!valid) return;
@@ -496,13 +507,13 @@ __global__ __launch_bounds__(TX_THREADS) void k_vcf_lines(const msim_record *__r
             const unsigned long long start = (unsigned long long)my.pos + 1;
             const uint8_t x = in[my.pos];
             const uint8_t ref = lut[768 + x], alt = lut[(uint32_t)my.aux * 256 + x];      // ti / tv column of conv(x)
-            len_io[mine] = ref == alt ? 0u : name_len + (uint32_t)ndigits(start) + 19u;   // vcf_writer.py:123: REF == ALT suppressed
+            len_io[mine] = ref == alt ? 0u : name_len + (uint32_t)ndigits(start) + (GT ? 21u : 19u);   // vcf_writer.py:123: REF == ALT suppressed
             ra[mine] = (uint16_t)((uint32_t)ref | ((uint32_t)alt << 8));
         } else if (!ALL_SNP) {
             const VcfLine d = vcf_describe<true>(my, pool, in, L, lut, 0);
             CSink s;
             s.n = 0;
-            if (!d.none) vcf_emit(s, d, name, name_len, lut);
+            if (!d.none) vcf_emit<GT>(s, d, name, name_len, lut, my_gt);
             len_io[mine] = (uint32_t)s.n;
         }
         return;
@@ -522,8 +533,8 @@ __global__ __launch_bounds__(TX_THREADS) void k_vcf_lines(const msim_record *__r
         if (valid && my_len) {
             const uint32_t r2 = ra[mine];
             const unsigned long long start = (unsigned long long)my.pos + 1;
-            if (staged) snp_line(&stage[phase + (uint32_t)(my_off - start0)], name, name_len, start, ndigits(start), (uint8_t)r2, (uint8_t)(r2 >> 8));
-            else snp_line(text + my_off, name, name_len, start, ndigits(start), (uint8_t)r2, (uint8_t)(r2 >> 8));
+            if (staged) snp_line<GT>(&stage[phase + (uint32_t)(my_off - start0)], name, name_len, start, ndigits(start), (uint8_t)r2, (uint8_t)(r2 >> 8), my_gt);
+            else snp_line<GT>(text + my_off, name, name_len, start, ndigits(start), (uint8_t)r2, (uint8_t)(r2 >> 8), my_gt);
         }
         if (!staged) return;
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");      // (flat stores into LDS complete out of order with ds reads: wait for both)
@@ -581,7 +592,7 @@ __global__ __launch_bounds__(TX_THREADS) void k_vcf_lines(const msim_record *__r
             if (in_group && live) {
                 s.w = phase + (uint32_t)(cp_excl - cp_lo);
                 s.n = my_off;
-                vcf_emit(s, d, nm, name_len, lut);
+                vcf_emit<GT>(s, d, nm, name_len, lut, my_gt);
             }
             // ---- the pieces' interiors: source -> text
             uint32_t cnt[VCF_SLOTS], tot = 0;
@@ -637,12 +648,13 @@ __global__ __launch_bounds__(TX_THREADS) void k_vcf_lines(const msim_record *__r
 }
 
 // The waves k_vcf_lines<true, false> left alone: every lane writes its own line byte by byte.
+template <bool GT>
 __global__ __launch_bounds__(TX_THREADS) void k_vcf_plain(const msim_record *__restrict__ recs, uint32_t n_rec,
                                                           const uint8_t *__restrict__ pool, const uint8_t *__restrict__ in,
                                                           unsigned long long L, const uint8_t *__restrict__ name, uint32_t name_len,
                                                           const uint8_t *__restrict__ lut_g, const uint32_t *__restrict__ len_io,
                                                           const uint16_t *__restrict__ ra, const unsigned long long *__restrict__ off,
-                                                          char *__restrict__ text, uint32_t plain) {
+                                                          char *__restrict__ text, uint32_t plain, const uint8_t *__restrict__ gt_g) {
     __shared__ uint8_t lut[1280];
     for (int i = threadIdx.x; i < 1280 / 4; i += TX_THREADS)
         reinterpret_cast<uint32_t *>(lut)[i] = reinterpret_cast<const uint32_t *>(lut_g)[i];
@@ -662,7 +674,7 @@ __global__ __launch_bounds__(TX_THREADS) void k_vcf_plain(const msim_record *__r
     const VcfLine d = vcf_describe<false>(my, pool, in, L, lut, my.type == MSIM_SN ? (uint32_t)ra[mine] : 0u);
     DSink s;
     s.text = text; s.n = my_off;
-    vcf_emit(s, d, name, name_len, lut);
+    vcf_emit<GT>(s, d, name, name_len, lut, GT ? (uint32_t)gt_g[mine] : 0u);
 }
 
 // ---- exclusive u64 scan of u32 lengths (2048 per workgroup)
@@ -1042,7 +1054,9 @@ __global__ __launch_bounds__(TX_THREADS) void k_gather(const uint8_t *__restrict
 
 // VCF text of one contig into the context's text buffer; returns its size.
 int vcf_render_device(Ctx *c, Contig &g, const char *seq_name, uint64_t *bytes, uint8_t **buf, size_t *cap) {
-    const uint32_t n = (uint32_t)g.n_rec;
+    // (diploid runs: the text is the FULL table's whichever haplotype is selected, its sample column the records' genotypes)
+    const TableView tv = vcf_table(g);
+    const uint32_t n = (uint32_t)tv.n_rec;
     *bytes = 0;
     const bool own = buf == nullptr;
     if (own) { buf = &c->d_text; cap = &c->cap_text; }
@@ -1067,10 +1081,12 @@ int vcf_render_device(Ctx *c, Contig &g, const char *seq_name, uint64_t *bytes, 
     const uint8_t *in = g.d_in + PAD;
     const uint8_t *pool = g.d_pool ? g.d_pool + PAD : nullptr;
     const dim3 grid((n + 64 * TX_WAVES - 1) / (64 * TX_WAVES));           // a wave takes 64 consecutive records
-#define MSIM_VCF_LINES(W, ...) do { if (g.all_snp) hipLaunchKernelGGL((k_vcf_lines<W, true>), __VA_ARGS__); \
-                                    else hipLaunchKernelGGL((k_vcf_lines<W, false>), __VA_ARGS__); } while (0)
-    MSIM_VCF_LINES(false, grid, dim3(TX_THREADS), 0, st, g.d_recs, n, pool, in, (unsigned long long)g.len,
-                   d_name, (uint32_t)name_len, ctx_lut(c), d_len, d_ra, (const unsigned long long *)nullptr, (char *)nullptr, 0u);
+#define MSIM_VCF_LINES(W, ...) do { if (tv.d_gt) { if (tv.all_snp) hipLaunchKernelGGL((k_vcf_lines<W, true, true>), __VA_ARGS__); \
+                                                   else hipLaunchKernelGGL((k_vcf_lines<W, false, true>), __VA_ARGS__); } \
+                                    else if (tv.all_snp) hipLaunchKernelGGL((k_vcf_lines<W, true, false>), __VA_ARGS__); \
+                                    else hipLaunchKernelGGL((k_vcf_lines<W, false, false>), __VA_ARGS__); } while (0)
+    MSIM_VCF_LINES(false, grid, dim3(TX_THREADS), 0, st, tv.d_recs, n, pool, in, (unsigned long long)g.len,
+                   d_name, (uint32_t)name_len, ctx_lut(c), d_len, d_ra, (const unsigned long long *)nullptr, (char *)nullptr, 0u, tv.d_gt);
     hipLaunchKernelGGL(k_len_reduce, dim3(nb), dim3(TX_THREADS), 0, st, d_len, n, d_sums);
     hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, d_sums, nb, c->h_mail);
     hipLaunchKernelGGL(k_len_offsets, dim3(nb), dim3(TX_THREADS), 0, st, d_len, n, d_sums, d_off);
@@ -1080,16 +1096,21 @@ int vcf_render_device(Ctx *c, Contig &g, const char *seq_name, uint64_t *bytes, 
     rc = dev_reserve(c, (void **)buf, cap, total + 64);
     if (rc) return rc;
     if (total) {
-        MSIM_VCF_LINES(true, grid, dim3(TX_THREADS), 0, st, g.d_recs, n, pool, in, (unsigned long long)g.len,
+        MSIM_VCF_LINES(true, grid, dim3(TX_THREADS), 0, st, tv.d_recs, n, pool, in, (unsigned long long)g.len,
                        d_name, (uint32_t)name_len, ctx_lut(c), d_len, d_ra, d_off, reinterpret_cast<char *>(*buf),
-                       (getenv("MSIM_DBG_VCF_PLAIN") || name_len > VCF_MAX_NAME) ? 1u : 0u);      // (the plain path: test hook, huge names)
+                       (getenv("MSIM_DBG_VCF_PLAIN") || name_len > VCF_MAX_NAME) ? 1u : 0u, tv.d_gt);      // (the plain path: test hook, huge names)
 #undef MSIM_VCF_LINES
         // waves the stage scheme cannot describe (vcf_wave_is_plain): only a text of 4 GiB and more can hold one
         const uint32_t plain = (getenv("MSIM_DBG_VCF_PLAIN") || name_len > VCF_MAX_NAME) ? 1u : 0u;
         const bool far = (((uintptr_t)(in + g.len) | (uintptr_t)(pool + (1ull << 32))) >> 48) != 0;
-        if (!g.all_snp && (plain || far || total >= (1ull << 32) - 16))
-            hipLaunchKernelGGL(k_vcf_plain, grid, dim3(TX_THREADS), 0, st, g.d_recs, n, pool, in, (unsigned long long)g.len, d_name,
-                               (uint32_t)name_len, ctx_lut(c), d_len, d_ra, d_off, reinterpret_cast<char *>(*buf), plain);
+        if (!tv.all_snp && (plain || far || total >= (1ull << 32) - 16)) {
+            if (tv.d_gt)
+                hipLaunchKernelGGL(k_vcf_plain<true>, grid, dim3(TX_THREADS), 0, st, tv.d_recs, n, pool, in, (unsigned long long)g.len, d_name,
+                                   (uint32_t)name_len, ctx_lut(c), d_len, d_ra, d_off, reinterpret_cast<char *>(*buf), plain, tv.d_gt);
+            else
+                hipLaunchKernelGGL(k_vcf_plain<false>, grid, dim3(TX_THREADS), 0, st, tv.d_recs, n, pool, in, (unsigned long long)g.len, d_name,
+                                   (uint32_t)name_len, ctx_lut(c), d_len, d_ra, d_off, reinterpret_cast<char *>(*buf), plain, (const uint8_t *)nullptr);
+        }
         MSIM_HIP(c, hipGetLastError());
     }
     if (own) c->text_len = total;

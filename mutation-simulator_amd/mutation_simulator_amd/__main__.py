@@ -9,6 +9,7 @@ from timeit import default_timer as timer
 
 from . import *  # noqa: F401,F403  (same style of namespace as the reference entry point)
 from ._ffi import MsimError, MsimUnsupported
+from .argument_parser import ploidy_refusal
 from .fasta_io import is_gzip
 
 _INIT_ERRORS = (FileNotFoundError, ITNotEnoughAvailChromsError, RatesTooHighError, RatesTooLowError,
@@ -33,6 +34,10 @@ class ChainUnsupportedError(Exception):
     """--chain together with what it does not cover (the IT pass, a sharded run)."""
 
 
+class PloidyUnsupportedError(Exception):
+    """--ploidy 2 together with what it does not cover (argument_parser.ploidy_refusal)."""
+
+
 class CompressedInputUnsupportedError(Exception):
     """A gzip-compressed input together with what does not cover it (a sharded run)."""
 
@@ -49,6 +54,9 @@ def initialize(argv=None):
     t0 = timer()
     args = get_args(argv)
     STAGES["parse_args"] = timer() - t0
+    refusal = ploidy_refusal(args)
+    if refusal:
+        exit_with_error(PloidyUnsupportedError(refusal), args.no_color)
     if args.mode == "vcf" and (args.gpus or 1) > 1:
         exit_with_error(VcfModeUnsupportedError("the vcf mode needs a single-GPU run (--gpus 1)"), args.no_color)
     if args.bgzip and args.mode == "it":
@@ -90,6 +98,9 @@ def initialize(argv=None):
     if args.bgzip and sim.has_it:
         exit_with_error(BgzipUnsupportedError("--bgzip does not apply to the interchromosomal pass (it lines in the RMT)"),
                         args.no_color)
+    refusal = ploidy_refusal(args, sim.has_it)
+    if refusal:
+        exit_with_error(PloidyUnsupportedError(refusal), args.no_color)
     if args.chain and sim.has_it:
         exit_with_error(ChainUnsupportedError("--chain does not apply to the interchromosomal pass (it lines in the RMT)"),
                         args.no_color)

@@ -120,6 +120,11 @@ SYMBOLS = [
     ("msim_result_device_ptr", C.c_int, [_VP, C.c_int, _U64P, _U64P]),
     ("msim_render_vcf", C.c_int, [_VP, C.c_uint64, _VP, _VP, C.c_uint64, C.c_char_p, _VP,
                                   C.c_uint64, _U64P]),
+    ("msim_render_vcf_gt", C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP, C.c_uint64, C.c_char_p, _VP, C.c_uint64, _U64P]),
+    ("msim_genotype_contig", C.c_int, [_VP, C.c_int, C.c_uint64, C.c_uint32, C.c_uint64]),
+    ("msim_set_genotypes", C.c_int, [_VP, C.c_int, _VP]),
+    ("msim_fetch_genotypes", C.c_int, [_VP, C.c_int, _VP]),
+    ("msim_select_haplotype", C.c_int, [_VP, C.c_int, C.c_int]),
     ("msim_render_chain", C.c_int, [_VP, C.c_uint64, C.c_uint64, C.c_char_p, C.c_char_p, C.c_uint64, _VP, C.c_uint64, _U64P]),
     ("msim_render_chain_device", C.c_int, [_VP, C.c_int, C.c_char_p, C.c_char_p, C.c_uint64, _VP, C.c_uint64, _U64P]),
     ("msim_render_vcf_device", C.c_int, [_VP, C.c_int, C.c_char_p, _VP, C.c_uint64, _U64P]),
@@ -511,6 +516,28 @@ class Engine:
         pool = np.zeros(n_pool, dtype=np.uint8)
         self._check(self.lib.msim_fetch_records(self.h, contig, _ptr(recs), _ptr(pool)))
         return recs, pool
+
+    # ------------------------------------------------------------------ diploid runs (msim.h: genotypes, haplotype selection)
+    def genotype_contig(self, contig: int, key: int, seq: int, het_thr: int):
+        """Draw a genotype byte (1: haplotype 1, 2: haplotype 2, 3: both) for every record of the planned contig's table:
+        Philox counter (record index, 0, ``seq``, tag 20) under the 64-bit ``key``; heterozygous iff the 53-bit sample is below
+        ``het_thr`` = ceil(F * 2**53).  No MT19937 stream moves."""
+        self._check(self.lib.msim_genotype_contig(self.h, contig, int(key) & (2**64 - 1), int(seq), int(het_thr)), contig)
+
+    def set_genotypes(self, contig: int, gt: np.ndarray):
+        gt = np.ascontiguousarray(gt, dtype=np.uint8)
+        self._check(self.lib.msim_set_genotypes(self.h, contig, _ptr(gt)), contig)
+
+    def fetch_genotypes(self, contig: int, n_records: int) -> np.ndarray:
+        """The genotype bytes of the contig's FULL table (``n_records``: its size, whichever haplotype is selected)."""
+        out = np.zeros(n_records, dtype=np.uint8)
+        self._check(self.lib.msim_fetch_genotypes(self.h, contig, _ptr(out)), contig)
+        return out
+
+    def select_haplotype(self, contig: int, hap: int):
+        """``hap`` 1 / 2: the records on that haplotype become the contig's active table (APPLY, sizes, record fetch, chain);
+        0: the full table again.  The VCF text is always the full table's."""
+        self._check(self.lib.msim_select_haplotype(self.h, contig, int(hap)), contig)
 
     # ------------------------------------------------------------------ VCF replay (msim.h: msim_vcf_*)
     def vcf_load(self, text) -> tuple:
@@ -1019,6 +1046,40 @@ def render_vcf(recs: np.ndarray, pool: np.ndarray, bases: np.ndarray, seq_name: 
     if rc != OK:
         raise MsimError(f"msim_render_vcf failed ({rc})")
     return out.tobytes()
+
+
+def render_vcf_gt(recs: np.ndarray, gt, pool: np.ndarray, bases: np.ndarray, seq_name: str) -> bytes:
+    """``msim_render_vcf_gt``: the record lines with the phased genotype column of ``gt`` (one byte per record, 1..3; None: the
+    haploid column of ``render_vcf``).  Host helper; no GPU, no context."""
+    lib = load()
+    recs = np.ascontiguousarray(recs)
+    pool = np.ascontiguousarray(pool, dtype=np.uint8)
+    bases = np.ascontiguousarray(bases, dtype=np.uint8)
+    g = None if gt is None else np.ascontiguousarray(gt, dtype=np.uint8)
+    if g is not None and g.shape[0] != recs.shape[0]:
+        raise MsimError("render_vcf_gt: one genotype byte per record")
+    need = C.c_uint64()
+    name = seq_name.encode("utf-8", "replace")
+    gp = None if g is None else _ptr(g)
+    rc = lib.msim_render_vcf_gt(_ptr(recs), gp, recs.shape[0], _ptr(pool), _ptr(bases), bases.shape[0], name, None, 0, C.byref(need))
+    if rc != OK:
+        err = MsimError(f"msim_render_vcf_gt failed ({rc})")
+        err.code = rc
+        raise err
+    out = np.empty(need.value, dtype=np.uint8)
+    rc = lib.msim_render_vcf_gt(_ptr(recs), gp, recs.shape[0], _ptr(pool), _ptr(bases), bases.shape[0], name, _ptr(out), need.value,
+                                C.byref(need))
+    if rc != OK:
+        raise MsimError(f"msim_render_vcf_gt failed ({rc})")
+    return out.tobytes()
+
+
+def hap_block() -> int:
+    """Records of a workgroup of the haplotype compaction kernels (csrc/haplotype.hip: HAP_BLOCK), where their edge cases lie
+    (msim_dbg_hap_block: exported, not part of include/msim.h)."""
+    fn = load().msim_dbg_hap_block
+    fn.restype, fn.argtypes = C.c_uint32, []
+    return int(fn())
 
 
 VCF_GROUP_DTYPE = np.dtype([("name_off", "<u8"), ("first_line", "<u8"), ("n_lines", "<u8"), ("name_len", "<u4"), ("rsv", "<u4")])   # msim_vcf_group

@@ -1,8 +1,12 @@
 """Command line of ``mutation-simulator`` -- flag-for-flag the reference's ``args`` and ``rmt``
 sub-commands (reference argument_parser.py:31-240) plus a few additions of ours that never change
-a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bgzip``, ``--chain``, ``--bench-json``, and the ``vcf`` sub-command
+a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bgzip``, ``--chain``, ``--ploidy``, ``--het``, ``--bench-json``, and the ``vcf`` sub-command
 (``vcf_replay.py``: the mutated Fasta again from the reference and a run's VCF; it writes ``<outbase>_ms.fa`` and, with
 ``--chain``, ``<outbase>_ms.chain``; with ``--consensus [--sample NAME] [--haplotype N]`` the VCF may come from anywhere).
+
+``--ploidy 2 [--het F]`` (``args`` / ``rmt``) writes two haplotype Fastas, ``<outbase>_ms_h1<suffix>`` and ``<outbase>_ms_h2<suffix>``
+(``args.outfasta_h1`` / ``outfasta_h2``; ``<outbase>_ms<suffix>`` is not written), one phased ``<outbase>_ms.vcf`` and, with ``--chain``,
+``<outbase>_ms_h1.chain`` / ``_h2.chain`` (``outchain_h1`` / ``outchain_h2``).  ``ploidy_refusal`` words what a diploid run does not cover.
 
 The ``it`` sub-command (inter-chromosomal translocations, reference it_mutator.py: a second pass over
 the Fasta) runs through ``ITMutator`` / ``BedpeWriter``.  ``--rng fast`` applies to the mutation pass
@@ -41,6 +45,11 @@ def add_outfile_names(args: Namespace) -> Namespace:
     args.outvcf = args.outfasta.with_suffix(".vcf")
     args.outbedpe = args.outfastait.with_suffix(".bedpe")
     args.outchain = args.outfasta.with_suffix(".chain")
+    if getattr(args, "ploidy", 1) == 2:           # a diploid run: a Fasta (and a chain) per haplotype, ONE phased VCF
+        for h in ("h1", "h2"):
+            fa = args.outfasta.with_stem(f"{args.outfasta.stem}_{h}")
+            setattr(args, f"outfasta_{h}", fa)
+            setattr(args, f"outchain_{h}", fa.with_suffix(".chain"))
     if getattr(args, "bgzip", False):             # BGZF-compressed mutation-pass outputs: <name>.gz
         args.outfasta = args.outfasta.with_name(args.outfasta.name + ".gz")
         args.outvcf = args.outvcf.with_name(args.outvcf.name + ".gz")
@@ -97,6 +106,14 @@ def build_parser() -> ArgumentParser:
                              "also with --bgzip. The run goes contig by contig (an assembly of thousands of small scaffolds "
                              "loses the speed of the batched pass; the output bytes are the same). Not with it / it lines in "
                              "the RMT / --gpus N > 1")
+    parser.add_argument("--ploidy", type=int, choices=[1, 2], default=1,
+                        help="2: a diploid run -- the mutation pass of --ploidy 1, then every mutation is given a genotype and "
+                             "the run writes two haplotype Fastas (<outbase>_ms_h1, <outbase>_ms_h2 instead of <outbase>_ms), one "
+                             "VCF with phased genotypes (1|0, 0|1, 1|1) and, with --chain, a chain file per haplotype. The run "
+                             "goes contig by contig. Not with it / it lines in the RMT / vcf / --gpus N > 1 / --bgzip. Default = 1")
+    parser.add_argument("--het", type=float, default=None, metavar="F",
+                        help="With --ploidy 2: the fraction of heterozygous mutations, in [0, 1]; a heterozygous mutation is on "
+                             "haplotype 1 or 2 with equal chance, every other one on both. Default = 0.5")
     parser.add_argument("--bench-json", type=Path, default=None,
                         help="Write per-stage timings of the mutation pass to this JSON file")
 
@@ -145,9 +162,36 @@ def build_parser() -> ArgumentParser:
     return parser
 
 
+def ploidy_refusal(args: Namespace, has_it: bool = False):
+    """What a ``--ploidy 2`` run does not cover, as the message to refuse it with; None: the run can go ahead.  ``has_it``: the
+    settings hold interchromosomal translocations (``it`` lines of an RMT -- known once the RMT is read)."""
+    if getattr(args, "ploidy", 1) != 2:
+        return None
+    if args.mode == "it":
+        return "--ploidy 2 does not apply to the interchromosomal pass (it)"
+    if has_it:
+        return "--ploidy 2 does not apply to the interchromosomal pass (it lines in the RMT)"
+    if args.mode == "vcf":
+        return "--ploidy 2 does not apply to the vcf mode (it replays one haplotype: vcf --consensus --haplotype N)"
+    if (args.gpus or 1) > 1:
+        return "--ploidy 2 needs a single-GPU run (--gpus 1)"
+    if getattr(args, "bgzip", False):
+        return ("--ploidy 2 does not write BGZF yet (--bgzip): a second Fasta stream needs a third BGZF output channel, "
+                "which is a follow-up; compress the three files afterwards (bgzip)")
+    return None
+
+
 def get_args(argv=None) -> Namespace:
     parser = build_parser()
     args = parser.parse_args(argv)
+    if args.het is not None and args.ploidy != 2:
+        parser.error("--het needs --ploidy 2")
+    if args.het is not None and not 0.0 <= args.het <= 1.0:      # (NaN fails both comparisons)
+        parser.error("--het is a fraction in [0, 1]")
+    if args.ploidy == 2 and args.het is None:
+        args.het = 0.5
+    if args.mode == "vcf" and args.ploidy != 2:        # (the namespace of a replay stays as it was; --ploidy 2 is refused later)
+        del args.ploidy, args.het
     if args.mode == "vcf":
         if not args.consensus and (args.sample is not None or args.haplotype is not None):
             parser.error("--sample and --haplotype need --consensus")

@@ -16,12 +16,15 @@ changed is *where* the work happens:
   FastaWriter.write per base               -> msim_fetch_sequence_framed: line-wrapped on the device, one write
   VcfWriter.write per record               -> msim_render_vcf_device: record lines rendered on the device
   (no counterpart: --chain)                -> msim_render_chain_device: the record table as a liftover chain
+  (no counterpart: --ploidy 2)             -> msim_genotype_contig + msim_select_haplotype: one plan, a genotype per record,
+                                              the two haplotypes' records applied one after the other
 
 All floating-point expressions of the path are evaluated here with the reference's own formulas
 (``plan_descriptors``); the C-ABI takes integers only.
 """
 from __future__ import annotations
 
+import hashlib
 import os
 import random
 import sys
@@ -318,6 +321,10 @@ class Mutator:
 
     _bgzip = False                                     # --bgzip: BGZF writers (subclasses that open writers of their own: plain)
     _chain_writer = None                               # --chain: the liftover chain file (subclasses without one: none)
+    _diploid = False                                   # --ploidy 2: two haplotype Fastas (+ chains), one phased VCF
+    _fasta_writer_h2 = None
+    _chain_writer_h2 = None
+    _gt_key = 0
 
     def __init__(self, args, fasta, sim, engine: Optional["_ffi.Engine"] = None):
         self._args = args
@@ -327,8 +334,18 @@ class Mutator:
         dev = getattr(args, "device", 0) or 0
         # --chain: the liftover chains, contig by contig behind the VCF lines.  Opened first: a chain path that cannot be
         # written ends the run (ChainWriterError) before the other two files exist.
-        self._chain_writer = ChainWriter(args.outchain) if getattr(args, "chain", False) else None
-        self._fasta_writer = FastaWriter(args.outfasta, bgzip=self._bgzip, device=dev)
+        # --ploidy 2: haplotype 1 goes through the writers every run has, haplotype 2 through a second instance of each
+        self._diploid = int(getattr(args, "ploidy", 1) or 1) == 2
+        if self._diploid:
+            self._het_thr = _ceil_scaled(float(args.het))  # heterozygous iff the 53-bit sample is below ceil(F * 2**53)
+            if getattr(args, "chain", False):
+                self._chain_writer = ChainWriter(args.outchain_h1)
+                self._chain_writer_h2 = ChainWriter(args.outchain_h2)
+            self._fasta_writer = FastaWriter(args.outfasta_h1, device=dev)
+            self._fasta_writer_h2 = FastaWriter(args.outfasta_h2, device=dev)
+        else:
+            self._chain_writer = ChainWriter(args.outchain) if getattr(args, "chain", False) else None
+            self._fasta_writer = FastaWriter(args.outfasta, bgzip=self._bgzip, device=dev)
         self._vcf_writer = VcfWriter(args.outvcf, bgzip=self._bgzip, device=dev)
         self._vcf_writer.write_header(getattr(args, "genome_name", args.infile.name), fasta, sim.assembly_name, sim.species_name,
                                       sim.sample_name)
@@ -358,9 +375,12 @@ class Mutator:
             side.start()
         try:
             self._fasta_writer.close()
+            if self._fasta_writer_h2 is not None:
+                self._fasta_writer_h2.close()
             self._vcf_writer.close()
-            if self._chain_writer is not None:
-                self._chain_writer.close()
+            for cw in (self._chain_writer, self._chain_writer_h2):
+                if cw is not None:
+                    cw.close()
         finally:
             if side is not None:
                 side.join()
@@ -386,6 +406,11 @@ class Mutator:
         return eng
 
     def _seed_engine(self, eng):
+        if self._diploid:
+            # The genotype draws' Philox key: 64 bits hashed from CPython's generator state as the run finds it -- nothing is
+            # drawn, so both streams (and the key of --rng fast below) are the haploid run's; the same --seed, the same genotypes.
+            words = np.array(random.getstate()[1], dtype=np.uint32)          # the 624 words and the index
+            self._gt_key = int.from_bytes(hashlib.blake2b(words.tobytes(), digest_size=8).digest(), "little")
         if self._fast_rng:
             eng.set_fast_key(random.getrandbits(64))       # (from Python's generator: --seed / random.seed() decide the run)
         else:
@@ -533,11 +558,58 @@ class Mutator:
             self._warn_empty(chrom)
             done.add("warned")
         bpl = self._fasta.faidx.index[rec.name].lenc
+        if self._diploid:
+            return self._run_contig_diploid(eng, chrom, rec, cid, bpl, done, t1)
         if "header" not in done:                       # the reference writes it before it mutates (mutator.py:131-133)
             self._fasta_writer.set_bpl(bpl)
             self._fasta_writer.write_header(rec.long_name)
             done.add("header")
         eng.apply_contig(cid)
+        t3 = self._fasta_egress(eng, cid, bpl, self._fasta_writer, t1)
+        self._vcf_egress(eng, cid, rec, t3)
+        if self._chain_writer is not None and "chain" not in done:
+            t4 = time.perf_counter()
+            self._chain_writer.write_contig(eng, cid, rec.name, chrom.number)
+            done.add("chain")
+            t["chain_egress_s"] = t.get("chain_egress_s", 0.0) + time.perf_counter() - t4
+        eng.clear()
+
+    def _run_contig_diploid(self, eng, chrom, rec, cid, bpl, done, t1):
+        """The planned contig as two haplotypes: a genotype per record (Philox: no stream moves), then per haplotype its records
+        selected on the device, applied and written -- Fasta, chain --, then the full table's VCF lines with the phased GT.
+        Every record is on at least one haplotype, so a base the haploid run raises KeyError for is met by one of the two: the
+        lower of their first errors is the haploid run's."""
+        t = self._t
+        eng.genotype_contig(cid, self._gt_key, chrom.number, self._het_thr)
+        key_errors = []
+        for hap, fw, cw in ((1, self._fasta_writer, self._chain_writer), (2, self._fasta_writer_h2, self._chain_writer_h2)):
+            if ("header", hap) not in done:
+                fw.set_bpl(bpl)
+                fw.write_header(rec.long_name)
+                done.add(("header", hap))
+            eng.select_haplotype(cid, hap)
+            try:
+                eng.apply_contig(cid)
+                t1 = self._fasta_egress(eng, cid, bpl, fw, t1)
+            except KeyError:
+                key_errors.append(eng.key_error(cid))
+                t1 = time.perf_counter()
+                continue
+            if cw is not None and ("chain", hap) not in done:
+                t4 = time.perf_counter()
+                cw.write_contig(eng, cid, rec.name, chrom.number)
+                done.add(("chain", hap))
+                t1 = time.perf_counter()
+                t["chain_egress_s"] = t.get("chain_egress_s", 0.0) + t1 - t4
+        if key_errors:
+            raise KeyError(min(key_errors, key=lambda e: e[1])[0])
+        eng.select_haplotype(cid, 0)
+        self._vcf_egress(eng, cid, rec, t1)
+        eng.clear()
+
+    def _fasta_egress(self, eng, cid, bpl, writer, t1):
+        """The applied contig's body into ``writer``'s file; returns the time behind it (``t1``: when PLAN + APPLY began)."""
+        t = self._t
         # Egress.  Line framing and VCF text are rendered on the device and libmsim's output channels write them into the
         # files' next spans (csrc/file_io.hip: device -> pinned ring -> pwrite on a thread per file) while this thread goes on
         # with the next contig; mutate() joins them (file_wait) before the writers are closed.
@@ -549,26 +621,30 @@ class Mutator:
             t2 = time.perf_counter()
             t["plan_apply_s"] += t2 - t1
             q, r = divmod(n_text, bpl + 1)              # text = L + L // bpl bytes  ->  L
-            fd, pos = self._fasta_writer.native_span()
+            fd, pos = writer.native_span()
             try:
                 n_done = eng.fetch_sequence_framed_to_file(cid, bpl, fd, pos) if NATIVE_FILE_EGRESS else None
             except _ffi.MsimUnsupported:                # the file cannot be mapped there: through a mapping made here
                 n_done = None
             if n_done is not None:
-                self._fasta_writer.commit_native(pos, n_done, q * bpl + r)
+                writer.commit_native(pos, n_done, q * bpl + r)
             else:
-                region = self._fasta_writer.map_region(n_text)
+                region = writer.map_region(n_text)
                 try:
                     eng.fetch_sequence_framed_into(cid, bpl, region.view)
                 finally:
-                    self._fasta_writer.commit_region(region, q * bpl + r)
+                    writer.commit_region(region, q * bpl + r)
         else:
             text = eng.fetch_sequence(cid)
             t2 = time.perf_counter()
             t["plan_apply_s"] += t2 - t1
-            self._fasta_writer.write_array(text)
+            writer.write_array(text)
         t3 = time.perf_counter()
         t["fasta_egress_s"] += t3 - t2
+        return t3
+
+    def _vcf_egress(self, eng, cid, rec, t3):
+        t = self._t
         fd, pos = self._vcf_writer.native_span()
         try:
             n_done = eng.render_vcf_device_to_file(cid, rec.name, fd, pos) if NATIVE_FILE_EGRESS else None
@@ -585,12 +661,6 @@ class Mutator:
             finally:
                 self._vcf_writer.commit_region(region)
         t["vcf_egress_s"] += time.perf_counter() - t3
-        if self._chain_writer is not None and "chain" not in done:
-            t4 = time.perf_counter()
-            self._chain_writer.write_contig(eng, cid, rec.name, chrom.number)
-            done.add("chain")
-            t["chain_egress_s"] = t.get("chain_egress_s", 0.0) + time.perf_counter() - t4
-        eng.clear()
 
     def _units(self, chroms):
         """mutate()'s contig loop (mutator.py:111-141) cut into units of work: a run of >= 2 small contigs (ONE pass through
@@ -601,6 +671,8 @@ class Mutator:
         if self._fast_rng:                             # no chain to amortise, and batches are planned on the host's streams
             return [(q, q + 1) for q in range(n)]
         if self._chain_writer is not None:             # --chain: a batch keeps no per-contig table to render a chain from
+            return [(q, q + 1) for q in range(n)]
+        if self._diploid:                              # --ploidy 2: ... nor one to select a haplotype from
             return [(q, q + 1) for q in range(n)]
         tab = getattr(self._fasta, "index_table", None)
         if (isinstance(chroms, StdChromosomes) and tab is not None and len(tab) == n
