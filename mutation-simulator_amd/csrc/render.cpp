@@ -112,6 +112,7 @@ uint64_t render(const msim_record *recs, uint64_t n, const uint8_t *pool, const 
                 uint64_t start = pos, end = stop + 1, lo = pos - 1;
                 if (pos == 0) { start = 1; end = stop + 2; lo = 0; }
                 const uint64_t hi = end < L ? end : L;               // slice clamps at len(sequence)
+                if (hi - lo == 1) break;                             // a contig of one base: REF == ALT == seq[0], suppressed
                 line_head(s, name, name_len, start);
                 for (uint64_t q = lo; q < hi; q++) s.put((char)T.conv[in[q]]);
                 s.put('\t');

@@ -274,6 +274,7 @@ __device__ __forceinline__ VcfLine vcf_describe(const msim_record &r, const uint
             d.start = pos;
             if (pos == 0) { d.start = 1; end = stop + 2; lo = 0; }
             const unsigned long long hi = end < L ? end : L;             // slice clamps at len(sequence)
+            d.none = hi - lo == 1;                                       // a contig of one base: REF == ALT == seq[0], suppressed
             d.src[0] = in + lo; d.len[0] = hi - lo; d.mode = 1u;
             d.mid = (uint32_t)'\t' | ((uint32_t)lut[768 + in[pos > 0 ? lo : hi - 1]] << 8); d.n_mid = 2;     // REF[0] / REF[-1]
             d.svtype = r.type == MSIM_DE ? 2 : 6; d.end = end; d.svlen = stop - pos + 1;

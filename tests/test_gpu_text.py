@@ -145,8 +145,11 @@ def test_vcf_device_snp_lines_at_the_staging_limit(name_len):
         eng.close()
 
 
-@pytest.mark.parametrize("bpl", [1, 7, 60, 61, 4096])
+@pytest.mark.parametrize("bpl", [1, 7, 60, 61, 4096, 15, 16, 17, 31, 32, 33])
 def test_framed_fetch_equals_fasta_writer_rule(bpl):
+    """k_frame takes lines of 16 bases and more with two 16-byte loads and a mask, shorter ones byte by byte: widths on both
+    sides of 16 and of 32, sequences that end one base in front of, on and one base behind a full line, and ones of a single
+    16-byte group and less."""
     L = 123_457
     eng = _ffi.Engine(0)
     eng.seed(3, 3)
@@ -158,6 +161,10 @@ def test_framed_fetch_equals_fasta_writer_rule(bpl):
     # exact multiple of the line width: the last line is full and keeps its newline
     cid2 = _plan_apply(eng, random_bases(bpl * 5, 1), [])
     assert eng.fetch_sequence_framed(cid2, bpl).tobytes() == _wrap(eng.fetch_sequence(cid2), bpl)
+    for L2 in (0, 1, 15, 16, 17, bpl * 5 - 1, bpl * 5 + 1, bpl * 259 - 1, bpl * 259, bpl * 259 + 1):
+        bases2 = random_bases(L2, 2 + L2 % 5)
+        cid3 = _plan_apply(eng, bases2, [])
+        assert eng.fetch_sequence_framed(cid3, bpl).tobytes() == _wrap(bases2, bpl), L2
     eng.close()
 
 
@@ -182,8 +189,10 @@ def test_framed_fetch_through_the_real_writer(tmp_path):
     eng.close()
 
 
-@pytest.mark.parametrize("lenc,eol", [(60, b"\n"), (60, b"\r\n"), (1, b"\n"), (113, b"\n")])
+@pytest.mark.parametrize("lenc,eol", [(60, b"\n"), (60, b"\r\n"), (1, b"\n"), (113, b"\n"), (15, b"\n"), (16, b"\n"), (17, b"\n"),
+                                      (31, b"\n"), (32, b"\n"), (33, b"\n"), (16, b"\r\n"), (17, b"\r\n")])
 def test_ingest_from_text_equals_host_parse(lenc, eol):
+    """k_gather switches formulation at a line width of 16 as k_frame does: the same widths and sequence lengths."""
     L = 250_003
     bases = decorate(random_bases(L, 8), 9, lower=12)                      # lower-case stretches included
     raw = bases.tobytes()
@@ -197,6 +206,11 @@ def test_ingest_from_text_equals_host_parse(lenc, eol):
     assert np.array_equal(eng.read_contig(cid2), want)
     with pytest.raises(_ffi.MsimError):
         eng.add_contig_text(np.frombuffer(body[:1000], dtype=np.uint8), L, lenc, lenc + len(eol))
+    for L2 in (0, 1, 15, 16, 17, lenc * 5 - 1, lenc * 5, lenc * 5 + 1, lenc * 259 - 1, lenc * 259, lenc * 259 + 1):
+        raw2 = decorate(random_bases(L2, 3 + L2 % 7), 4, lower=3).tobytes() if L2 > 64 else random_bases(L2, 3 + L2 % 7).tobytes().lower()
+        body2 = eol.join(raw2[i:i + lenc] for i in range(0, L2, lenc)) + eol
+        cid3 = eng.add_contig_text(np.frombuffer(body2, dtype=np.uint8), L2, lenc, lenc + len(eol))
+        assert eng.read_contig(cid3).tobytes() == raw2.upper(), L2
     eng.close()
 
 
