@@ -18,6 +18,7 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from deflate_build import _Bits
 from helpers import CASES, all_case_names, case_input_bytes, case_meta, mask_vcf, sha256
 from mutation_simulator_amd import _ffi
 from mutation_simulator_amd import __main__ as msa_main
@@ -156,22 +157,6 @@ def test_empty_file(engine):
 
 
 # ------------------------------------------------------------------ corrupted members: input validation
-class _Bits:
-    def __init__(self):
-        self.acc, self.n = 0, 0
-
-    def put(self, v, nb):                                       # LSB first (header fields, extra bits)
-        self.acc |= v << self.n
-        self.n += nb
-
-    def code(self, c, nb):                                      # a Huffman code: most significant bit first
-        for k in range(nb - 1, -1, -1):
-            self.put((c >> k) & 1, 1)
-
-    def bytes(self):
-        return self.acc.to_bytes((self.n + 7) // 8, "little")
-
-
 def _distance_before_start() -> bytes:
     """A fixed-Huffman block: literal 'A', then <length 3, distance 5> with one byte produced so far."""
     b = _Bits()
