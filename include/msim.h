@@ -552,6 +552,22 @@ int msim_gather_plan(int n, const int *owner, const uint64_t *out_len, const uin
  * render its VCF lines with msim_render_vcf).                                                                            */
 int msim_gather_fetch(msim_ctx *ctx, uint64_t device_addr, uint64_t bytes, void *dst);
 
+/* ---- test support: the SNP ti/tv transducer on the caller's words -------------------------------------------------- */
+/* Runs the three passes that turn CPython-stream words into SNP outcomes -- the map pass over whole blocks of
+ * MSIM_SNP_BLOCK_WORDS words, the scan that finds where the K-th SNP's draws end, the outcome pass -- over `words` (raw,
+ * untempered), in buffers of the call's own: synchronous, no contig, no stream session.  ti_lim: a uniform 53-bit sample
+ * below it is a transition.  The draws start at word `start`; only the n_words / MSIM_SNP_BLOCK_WORDS whole blocks are
+ * mapped and drawn from.
+ *   lanes:  (n_blocks + 1) * 256 * 4 uint32 -- per lane of every block A, B, T masks and packed map; the last block's
+ *           worth is a guard the call fills with 0xee and no pass may touch
+ *   maps:   (n_blocks + 1) * 4 uint32 -- per block the counts from the three start states and the end states; guard as above
+ *   end_pos: the word behind the one the K-th SNP completes on; flags: 2 = fewer than K SNPs complete (end_pos unset)
+ *   aux:    aux_off + K + 16 bytes -- aux_off (< 64) guard bytes 0xee, the K outcomes by rank (0 transition, 1 / 2 the
+ *           transversion column), 16 guard bytes; the outcome array starts aux_off bytes behind a 256-byte boundary     */
+#define MSIM_SNP_BLOCK_WORDS 8192
+int msim_dbg_snp_draws(msim_ctx *ctx, const uint32_t *words, uint64_t n_words, uint64_t ti_lim, uint64_t start, uint32_t K,
+                       uint32_t aux_off, uint32_t *lanes, uint32_t *maps, uint64_t *end_pos, uint32_t *flags, uint8_t *aux);
+
 /* ---- stats -------------------------------------------------------------------------------------- */
 int msim_stats(msim_ctx *ctx, msim_timing *out);
 int msim_reset_stats(msim_ctx *ctx);

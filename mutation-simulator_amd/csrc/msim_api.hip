@@ -1451,6 +1451,18 @@ int msim_dbg_emit_train(msim_ctx *p, int n_jobs, const uint64_t *const *bitmaps,
                               n_recs, first);
 }
 
+// The SNP ti/tv transducer (plan_kernels.h section 5) over words the caller made: k_snp_maps_abs, k_snp_scan_cut_abs and the outcome
+// pass in buffers of the call's own (include/msim.h).  Synchronous; touches no contig and no stream session.
+int msim_dbg_snp_draws(msim_ctx *p, const uint32_t *words, uint64_t n_words, uint64_t ti_lim, uint64_t start, uint32_t K,
+                       uint32_t aux_off, uint32_t *lanes, uint32_t *maps, uint64_t *end_pos, uint32_t *flags, uint8_t *aux) {
+    CTX_FLUSHED(c, p)
+    if (!c) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    int rc = drain(c);
+    if (rc) return rc;
+    return gpu_dbg_snp_draws(c, words, n_words, ti_lim, start, K, aux_off, lanes, maps, end_pos, flags, aux);
+}
+
 // The device halves of the SV-mix and host-chain engines over tables the caller made (plan_gpu.hip: gpu_dbg_*): the engines' own
 // launch helpers in buffers of the call's own.  Synchronous; no contig, no stream session.  Each refuses with MSIM_ERR_ARG,
 // before anything is launched, whatever the planners cannot produce.

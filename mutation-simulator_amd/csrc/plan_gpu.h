@@ -41,6 +41,9 @@ bool gpu_emit_pending(Ctx *c, int contig, bool mark_apply);
 int gpu_dbg_emit_train(Ctx *c, int n_jobs, const uint64_t *const *bm, const uint32_t *n_words, const uint32_t *start,
                        const uint64_t *len, const uint8_t *const *aux8, uint32_t d, int train, uint32_t tile_shift,
                        msim_record *const *recs, const uint64_t *cap_recs, uint64_t *n_recs, int32_t *const *first);
+// test support (msim_dbg_snp_draws): the SNP transducer's map, scan and outcome passes over the caller's words
+int gpu_dbg_snp_draws(Ctx *c, const uint32_t *words, uint64_t n_words, uint64_t ti_lim, uint64_t start, uint32_t K, uint32_t aux_off,
+                      uint32_t *lanes, uint32_t *maps, uint64_t *end_pos, uint32_t *flags, uint8_t *aux);
 // test support (msim_dbg_candidates / msim_dbg_accept_tables / msim_dbg_mixed_emit): the device halves of the SV-mix and host-chain
 // engines -- the engines' own launch helpers -- over tables the caller made (plan_gpu.hip);
 // rt: MixRangeDev[n_draw], sets: TypeTable[n_sets] (plan_kernels.h)

@@ -1257,6 +1257,57 @@ int gpu_dbg_emit_train(Ctx *c, int n_jobs, const uint64_t *const *bm, const uint
     return MSIM_OK;
 }
 
+// test support (msim_dbg_snp_draws): the SNP transducer's three passes -- k_snp_maps_abs over the whole blocks, k_snp_scan_cut_abs
+// from `start`, k_snp_emit_abs into a byte array by rank -- over words the caller made, in buffers of its own, synchronous.
+// The window is everything from `start` to the end of the last whole block.  lanes / maps: one guard block beyond the mapped
+// ones; aux: aux_off guard bytes, K outcomes, 16 guard bytes (include/msim.h).  The outcome pass runs as k_snp_emit_abs: the
+// body the train's k_snp_emit_abs_b / k_snp_emit_count_b share; their job table (emit_job_of, eblk0) runs in the whole-path tests only (tests/test_gpu_emit_train_vs_host.py).
+int gpu_dbg_snp_draws(Ctx *c, const uint32_t *words, uint64_t n_words, uint64_t ti_lim, uint64_t start, uint32_t K, uint32_t aux_off,
+                      uint32_t *lanes, uint32_t *maps, uint64_t *end_pos, uint32_t *flags, uint8_t *aux) {
+    const uint64_t n_blocks = n_words / SNP_BLOCK2;
+    if (!words || !lanes || !maps || !end_pos || !flags || !aux || !n_blocks || n_words >= (1ull << 28) || start >= n_blocks * SNP_BLOCK2 ||
+        !K || K > n_words || aux_off >= 64)
+        return fail(c, MSIM_ERR_ARG, "msim_dbg_snp_draws: bad argument");
+    static_assert(sizeof(SnpLane) == 16 && sizeof(SnpMap) == 16, "msim_dbg_snp_draws hands both out as four uint32");
+    const uint32_t W = (uint32_t)(n_blocks * SNP_BLOCK2 - start);
+    const uint32_t nb = (uint32_t)(n_blocks - start / SNP_BLOCK2);
+    const size_t sz_lanes = (size_t)(n_blocks + 1) * SNP_THREADS * sizeof(SnpLane), sz_maps = (size_t)(n_blocks + 1) * sizeof(SnpMap);
+    const size_t sz_aux = (size_t)aux_off + K + 16;
+    struct Dev { void *p[7] = {}; ~Dev() { for (void *q : p) if (q) (void)hipFree(q); } } dev;
+    const size_t sz[7] = {(size_t)n_words * 4, sz_lanes, sz_maps, (size_t)(nb + 1) * sizeof(SnpMap), sizeof(PlanState), 64, sz_aux};
+    for (int q = 0; q < 7; q++) MSIM_HIP(c, hipMalloc(&dev.p[q], sz[q]));
+    const uint32_t *d_raw = static_cast<const uint32_t *>(dev.p[0]);
+    SnpLane *d_lanes = static_cast<SnpLane *>(dev.p[1]);
+    SnpMap *d_maps = static_cast<SnpMap *>(dev.p[2]), *d_win = static_cast<SnpMap *>(dev.p[3]);
+    PlanState *d_ps = static_cast<PlanState *>(dev.p[4]);
+    unsigned long long *d_base = static_cast<unsigned long long *>(dev.p[5]);
+    uint8_t *d_aux = static_cast<uint8_t *>(dev.p[6]);
+    hipStream_t st = c->stream;
+    PlanState ps;
+    memset(&ps, 0, sizeof ps);
+    ps.pos = ps.snp_base = start;
+    MSIM_HIP(c, hipMemcpyAsync(dev.p[0], words, sz[0], hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemcpyAsync(d_ps, &ps, sizeof ps, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemsetAsync(d_lanes, 0xee, sz_lanes, st));
+    MSIM_HIP(c, hipMemsetAsync(d_maps, 0xee, sz_maps, st));
+    MSIM_HIP(c, hipMemsetAsync(d_win, 0, sz[3], st));
+    MSIM_HIP(c, hipMemsetAsync(d_aux, 0xee, sz_aux, st));
+    hipLaunchKernelGGL(k_snp_maps_abs, dim3((uint32_t)n_blocks), dim3(SNP_THREADS), 0, st, d_raw, (uint32_t)n_words,
+                       (unsigned long long)ti_lim, 0u, d_maps, d_lanes);
+    hipLaunchKernelGGL(k_snp_scan_cut_abs, dim3(1), dim3(SNP_THREADS), 0, st, d_lanes, d_ps, W, d_maps, d_win, nb, K, d_base, ~0ull);
+    hipLaunchKernelGGL(k_snp_emit_abs, dim3(nb), dim3(SNP_THREADS), 0, st, d_lanes, d_base, W, d_win, nb,
+                       (msim_record *)nullptr, K, (const uint32_t *)nullptr, d_aux + aux_off);
+    MSIM_HIP(c, hipGetLastError());
+    MSIM_HIP(c, hipMemcpyAsync(lanes, d_lanes, sz_lanes, hipMemcpyDeviceToHost, st));
+    MSIM_HIP(c, hipMemcpyAsync(maps, d_maps, sz_maps, hipMemcpyDeviceToHost, st));
+    MSIM_HIP(c, hipMemcpyAsync(aux, d_aux, sz_aux, hipMemcpyDeviceToHost, st));
+    MSIM_HIP(c, hipMemcpyAsync(&ps, d_ps, sizeof ps, hipMemcpyDeviceToHost, st));
+    MSIM_HIP(c, wait_stream(st));
+    *end_pos = ps.pos;
+    *flags = ps.flags;
+    return MSIM_OK;
+}
+
 bool gpu_emit_pending(Ctx *c, int contig, bool mark_apply) {
     GpuPlan *g = c->gpu;
     if (!g) return false;

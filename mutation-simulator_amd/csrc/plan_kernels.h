@@ -1001,13 +1001,17 @@ __global__ __launch_bounds__(BM_THREADS) void k_bitmap_expand_tiles_b(EmitJobs J
 // states: 0 expect 1st uniform word, 1 expect 2nd (decides ti / tv), 2 inside randbelow(2)
 struct SnpMap { uint32_t c[3]; uint32_t e; };            // per start state: emitted count, end state (2 bits each)
 
+// the count from start state s, s known at run time only: by selects -- an indexed read of c[] makes the compiler keep every map
+// in memory (12 bytes per lane and map of LDS, or scratch: 16 KB and 96 bytes per lane in k_snp_scan_cut_abs, on the chain)
+__device__ __forceinline__ uint32_t snp_count(const SnpMap &m, uint32_t s) { return s == 0 ? m.c[0] : s == 1 ? m.c[1] : m.c[2]; }
+
 __device__ __forceinline__ SnpMap snp_compose(const SnpMap &f, const SnpMap &g) {   // f first, then g
     SnpMap r;
     r.e = 0;
 #pragma unroll
     for (int s = 0; s < 3; s++) {
         const uint32_t mid = (f.e >> (2 * s)) & 3;
-        r.c[s] = f.c[s] + g.c[mid];
+        r.c[s] = f.c[s] + snp_count(g, mid);
         r.e |= ((g.e >> (2 * mid)) & 3) << (2 * s);
     }
     return r;
@@ -1245,17 +1249,17 @@ __global__ __launch_bounds__(SNP_THREADS) void k_snp_scan_cut_abs(const SnpLane 
             const SnpMap nxt = snp_compose(run, v[q]);
             if (i0 + q < nb) {
                 SnpMap r;
-                r.c[0] = c_count + run.c[c_state];
+                r.c[0] = c_count + snp_count(run, c_state);
                 r.c[1] = r.c[2] = 0;
                 r.e = (run.e >> (2 * c_state)) & 3;
                 win_maps[i0 + q] = r;
                 // the block in which the K-th SNP completes: count-before < K <= count-after
-                const uint32_t after = c_count + nxt.c[c_state];
+                const uint32_t after = c_count + snp_count(nxt, c_state);
                 if (r.c[0] < K && K <= after) { s_blk = i0 + q; s_bs = r.e; s_bc = r.c[0]; }
             }
             run = nxt;
         }
-        const uint32_t n_count = c_count + total.c[c_state], n_state = (total.e >> (2 * c_state)) & 3;
+        const uint32_t n_count = c_count + snp_count(total, c_state), n_state = (total.e >> (2 * c_state)) & 3;
         __syncthreads();
         c_count = n_count;
         c_state = n_state;
@@ -1274,7 +1278,7 @@ __global__ __launch_bounds__(SNP_THREADS) void k_snp_scan_cut_abs(const SnpLane 
     SnpMap tot2;
     const SnpMap ex = snp_block_scan2(snp_lane_map_of(Lb, m), wave_tot, tot2);
     const uint32_t st = (ex.e >> (2 * bs)) & 3;
-    const uint32_t idx = bc + ex.c[bs];                   // SNPs completed before this lane's words
+    const uint32_t idx = bc + snp_count(ex, bs);          // SNPs completed before this lane's words
     uint32_t emits, from2;
     (void)snp_lane_emits(st, m, emits, from2);
     const uint32_t mine = (uint32_t)__popc(emits);
@@ -1307,7 +1311,7 @@ __device__ __forceinline__ void snp_emit_body(const SnpLane *__restrict__ lanes,
     const SnpMap ex = snp_block_scan2(snp_lane_map_of(Lm, m), wave_tot, total);
     const uint32_t bs = win_maps[blk].e;
     const uint32_t st = (ex.e >> (2 * bs)) & 3;
-    uint32_t idx = bc + ex.c[bs];
+    uint32_t idx = bc + snp_count(ex, bs);
     uint32_t emits, from2;
     (void)snp_lane_emits(st, m, emits, from2);
     while (emits && idx < K) {                            // aux: 0 transition, 1/2 transversion column (bit 30)

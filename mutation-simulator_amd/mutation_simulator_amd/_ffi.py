@@ -168,6 +168,8 @@ SYMBOLS = [
     ("msim_gather_to_root", C.c_int, [_VP, C.c_int, _IP, _IP, _U64P, _U64P, _U64P, C.c_int, _U64P]),
     ("msim_gather_plan", C.c_int, [C.c_int, _IP, _U64P, _U64P, _U64P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), _IP]),
     ("msim_gather_fetch", C.c_int, [_VP, C.c_uint64, C.c_uint64, _VP]),
+    ("msim_dbg_snp_draws", C.c_int, [_VP, _VP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _VP, _VP, _U64P,
+                                     _U32P, _VP]),
     ("msim_stats", C.c_int, [_VP, C.POINTER(Timing)]),
     ("msim_reset_stats", C.c_int, [_VP]),
 ]
@@ -630,6 +632,22 @@ class Engine:
         self._check(fn(self.h, n, ptrs(bms), _ptr(n_words), _ptr(start), _ptr(length), ptrs(auxs), int(d), int(train),
                        ptrs(recs), _ptr(cap_a), _ptr(n_recs), ptrs(firsts) if firsts else None))
         return tile, [(recs[i][:int(n_recs[i])], firsts[i] if firsts and n_tiles[i] else None) for i in range(n)]
+
+    def snp_draws(self, words, ti_lim: int, start: int, K: int, aux_off: int = 0):
+        """The SNP ti/tv transducer over the caller's RAW CPython-stream ``words``: map pass over the whole blocks of 8192
+        words, the scan for the end of ``K`` SNPs' draws from word ``start``, the outcome pass (msim_dbg_snp_draws).  Returns a
+        dict: lanes (blocks + 1, 256, 4) uint32 = A, B, T, packed map per lane, maps (blocks + 1, 4) uint32 = counts from
+        the three start states and end states per block -- the last block of both is a guard of 0xee bytes --, end_pos,
+        flags, and aux = ``aux_off`` guard bytes, the K outcomes by rank, 16 guard bytes."""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        n_blocks = words.shape[0] // 8192
+        lanes = np.zeros((n_blocks + 1, 256, 4), dtype=np.uint32)
+        maps = np.zeros((n_blocks + 1, 4), dtype=np.uint32)
+        aux = np.zeros(int(aux_off) + int(K) + 16, dtype=np.uint8)
+        end_pos, flags = C.c_uint64(0), C.c_uint32(0)
+        self._check(self.lib.msim_dbg_snp_draws(self.h, _ptr(words), words.shape[0], int(ti_lim), int(start), int(K), int(aux_off),
+                                                _ptr(lanes), _ptr(maps), C.byref(end_pos), C.byref(flags), _ptr(aux)))
+        return {"lanes": lanes, "maps": maps, "end_pos": int(end_pos.value), "flags": int(flags.value), "aux": aux}
 
     def candidates(self, np_words, sets, bitmap=None, start: int = 0, d: int = 1, K: int = 0, ranges=None, all: bool = False):
         """The candidate front of the SV-mix (``bitmap`` given: one range, ``sets`` one TYPE_TABLE_DTYPE entry) or host-chain

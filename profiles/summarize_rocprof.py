@@ -100,5 +100,27 @@ def timeline(db, which="-1", max_rows="400", groups="1", marker="k_state_init"):
         print(f"{(st - t0) / 1e3:10.1f} {(en - st) / 1e3:8.1f} {q!s:>6s}  {short(name)} ({grid})")
 
 
+def launches(db, *kernels):
+    """Per named kernel: the spread of its dispatches' durations, LDS and VGPRs as dispatched, its largest grids one by one
+    and the time per workgroup of 256 over all dispatches (what compares two versions of a kernel whose launches differ in
+    size within a run)."""
+    import statistics
+    c = sqlite3.connect(db)
+    rows = list(c.execute("select start, end, name, grid_x, lds_size, vgpr_count from kernels order by start"))
+    short = lambda n: n.replace("msim::(anonymous namespace)::", "").replace("msim::", "").split("(")[0]
+    for pat in kernels:
+        sel = [(e - s, g, l, v) for s, e, n, g, l, v in rows if short(n) == pat]
+        if not sel:
+            print(f"{pat}: no dispatches")
+            continue
+        d = [x[0] / 1e3 for x in sel]
+        print(f"{pat}: n={len(d)} min={min(d):.1f} med={statistics.median(d):.1f} avg={sum(d) / len(d):.1f} max={max(d):.1f} us"
+              f"  lds={sel[0][2]} vgpr={sel[0][3]}")
+        big = sorted(sel, key=lambda x: -x[1])[:12]
+        print("   largest grids (dur_us, grid_x):", [(round(x[0] / 1e3, 1), x[1]) for x in big])
+        wgs = sum(x[1] for x in sel) // 256
+        print(f"   all dispatches: {wgs} workgroups in {sum(x[0] for x in sel) / 1e3:.1f} us = {sum(x[0] for x in sel) / max(wgs, 1):.2f} ns per workgroup")
+
+
 if __name__ == "__main__":
-    {"stats": stats, "pmc": pmc, "text": text, "timeline": timeline}[sys.argv[1]](*sys.argv[2:])
+    {"stats": stats, "pmc": pmc, "text": text, "timeline": timeline, "launches": launches}[sys.argv[1]](*sys.argv[2:])
