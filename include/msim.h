@@ -552,6 +552,36 @@ int msim_gather_plan(int n, const int *owner, const uint64_t *out_len, const uin
  * render its VCF lines with msim_render_vcf).                                                                            */
 int msim_gather_fetch(msim_ctx *ctx, uint64_t device_addr, uint64_t bytes, void *dst);
 
+/* ---- context-dependent SNPs: a 96-channel mutational spectrum (csrc/spectrum.hip, spectrum.h) ------------------------------- */
+/* A second way to draw SNPs, the only PLAN engine that reads the genome: every ELIGIBLE site of a contig mutates independently,
+ * with a probability its trinucleotide decides.  code(A, C, G, T) = 0..3, every other byte (N, IUPAC, U, -) is invalid; site p
+ * is eligible iff 1 <= p <= L - 2 and b[p-1], b[p], b[p+1] are valid; ctx = 16 code(b[p-1]) + 4 code(b[p]) + code(b[p+1]).
+ *   msim_context_counts        device census of a resident contig: counts[ctx] over its eligible sites, *n_valid their sum.
+ *   msim_plan_contig_spectrum  thr[3 ctx + i], i = 0..2: the cumulative probabilities of the SN record's aux values 0, 1, 2 in
+ *                              context ctx (0 the transition, 1 / 2 the transversion table's columns), scaled by 2^64, each triple
+ *                              non-decreasing (MSIM_ERR_ARG otherwise) -- the caller's exact arithmetic
+ *                              (mutation_simulator_amd/spectrum.py).  For an eligible site p: v = Philox4x32-10, counter
+ *                              (p >> 1, 0, seq, tag 21) under the 64-bit `key`; r = the high 64 bits of v for an odd p, the low
+ *                              64 for an even one; j = #{i : thr[3 ctx + i] <= r}; j == 3: nothing, else the record
+ *                              {pos = p, stop = p, extra = 0, MSIM_SN, aux = j, rsv = 0}.  Records come out in position order
+ *                              and the contig is left PLANNED as the VCF replay's parser leaves one (an SNP-only table of
+ *                              host-known size, no insert pool): msim_plan_was_empty, msim_apply_contig, the renderers,
+ *                              msim_genotype_contig and the chain follow unchanged.  Works in any device context (a fast
+ *                              context's queue is flushed first); no MT19937 stream moves, msim_set_params is not needed.
+ *                              MSIM_ERR_HIP on a host-only context; MSIM_ERR_UNSUPPORTED for 2^31 records or more.
+ *   msim_spectrum_timing       the census's and the plans' kernel time on the device (HIP events) since the context was made or
+ *                              msim_reset_stats.
+ * MSIM_SPECTRUM_TILE: the bases one workgroup of the sampler takes -- where the kernels' edge cases lie.
+ * msim_dbg_context_counts / msim_dbg_spectrum_plan: the same two results by sequential host loops over the caller's bases --
+ * no context, no GPU (error text: msim_last_error with a NULL context).  recs == NULL: *n_recs only; cap < *n_recs: MSIM_ERR_ARG. */
+#define MSIM_SPECTRUM_TILE 4096
+int msim_context_counts(msim_ctx *ctx, int contig, uint64_t counts[64], uint64_t *n_valid);
+int msim_plan_contig_spectrum(msim_ctx *ctx, int contig, const uint64_t thr[192], uint64_t key, uint32_t seq);
+int msim_spectrum_timing(msim_ctx *ctx, double *census_ms, double *plan_ms);
+int msim_dbg_context_counts(const uint8_t *bases, uint64_t L, uint64_t counts[64], uint64_t *n_valid);
+int msim_dbg_spectrum_plan(const uint8_t *bases, uint64_t L, const uint64_t thr[192], uint64_t key, uint32_t seq,
+                           msim_record *recs, uint64_t cap, uint64_t *n_recs);
+
 /* ---- test support: the SNP ti/tv transducer on the caller's words -------------------------------------------------- */
 /* Runs the three passes that turn CPython-stream words into SNP outcomes -- the map pass over whole blocks of
  * MSIM_SNP_BLOCK_WORDS words, the scan that finds where the K-th SNP's draws end, the outcome pass -- over `words` (raw,

@@ -88,6 +88,7 @@ struct Comm;                          // comm.cpp: RCCL communicator + receive b
 struct Batch;                         // msim_api.hip: state of msim_batch_run
 struct FileIo;                        // file_io.hip: the output channels (thread + stream + pinned ring per output file)
 struct VcfState;                      // vcf_parse.hip: the VCF text of a replay, its line starts and groups
+struct SpectrumState;                 // spectrum.hip: scratch, thresholds and kernel times of the context-dependent SNP engine
 
 struct Ctx {
     int device = 0;
@@ -106,6 +107,7 @@ struct Ctx {
     Batch *batch = nullptr;           // last batch of small contigs (host buffers)
     FileIo *file_io = nullptr;        // file_io.hip (made on first use)
     VcfState *vcf = nullptr;          // vcf_parse.hip (msim_vcf_load .. msim_vcf_release)
+    SpectrumState *spectrum = nullptr;    // spectrum.hip (made on first use)
     msim_params params{};
     bool have_params = false;
     std::vector<Contig> contigs;
@@ -193,6 +195,8 @@ int table_install(Ctx *c, Contig *g, std::vector<msim_record> &recs, std::vector
 int table_check(Ctx *c, uint64_t L, const msim_record *recs, uint64_t n, uint64_t pool_len, long long *delta, uint64_t *bad_index,
                 const char **bad_what);                                                                       // check_record_table
 void vcf_state_destroy(Ctx *c);       // vcf_parse.hip
+void spectrum_state_destroy(Ctx *c);  // spectrum.hip (the caller has waited for the context's streams)
+void spectrum_reset_timing(Ctx *c);   // msim_reset_stats: msim_spectrum_timing counts from here
 
 // plan_host.cpp
 struct HostPlan {

@@ -40,6 +40,7 @@ constexpr uint32_t TAG_POS = 17;       // x = draw index >> 1, y = leaf (numbere
 constexpr uint32_t TAG_CAND = 18;      // x = candidate ordinal: low 64 bits -> type (53 bits), high 64 -> length, or the SNP's outcome
 constexpr uint32_t TAG_INS = 19;       // x = 64-base chunk of the insert, y = candidate ordinal
 constexpr uint32_t TAG_GT = 20;        // x = record index in the contig's full table: low 64 bits -> heterozygous (53 bits), bit 0 of the high 64 -> phase
+constexpr uint32_t TAG_CTX = 21;       // x = site >> 1, y = 0: low 64 bits -> the even site's outcome, high 64 -> the odd site's (spectrum.h)
 constexpr int LG_LEAF_MIN = 10, LG_LEAF_MAX = 16;
 constexpr uint32_t LEAF_TARGET = 224;  // a leaf should hold about this many points or more (up to twice as many): 96 -> 224 in round 5 (A/B on one box, interleaved: c4 -5 %, c4sv -4 %, c3 -1 %, c2 +-0; 320: c3 +4 %)
 

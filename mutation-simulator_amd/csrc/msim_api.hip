@@ -363,6 +363,7 @@ void msim_destroy(msim_ctx *p) {
     batch_free(c);
     lap(2);
     comm_destroy(c);
+    spectrum_state_destroy(c);
     fast_plan_destroy(c);
     gpu_plan_destroy(c->gpu);
     lap(3);
@@ -1626,6 +1627,7 @@ int msim_reset_stats(msim_ctx *p) {
         if (rc) return rc;
     }
     c->t = msim_timing{};
+    spectrum_reset_timing(c);
     return MSIM_OK;
 }
 

@@ -1,0 +1,404 @@
+// Context-dependent SNPs ("--spectrum"): the one PLAN engine that reads the genome (msim.h: msim_context_counts,
+// msim_plan_contig_spectrum).  Every eligible site mutates independently with a probability its trinucleotide decides;
+// the arithmetic is spectrum.h's, shared with the host restatements at the end of this file.
+//
+// Device path (gfx950), everything on the context's stream:
+//   census   k_ctx_census: 16 bases a lane by one 16-byte load + the two halo bytes, 64 16-bit counters per LANE in LDS (no
+//            two lanes share a word or, within a wave, a bank), summed per workgroup at the end: one device-scope add per
+//            bin and workgroup
+//   plan     k_spectrum_draw: a tile of MSIM_SPECTRUM_TILE bases a workgroup; per site the context, the Philox draw (one
+//            call per two sites) and the compare against the context's last threshold (64 x 8 B in LDS; the other two are
+//            read on a hit only) -> per lane a 32-bit OUTCOME word (2 bits a site), per tile the hit count
+//            k_scan_u32 over the tile counts (scan_kernels.h)
+//            k_spectrum_emit: reads the outcome words only -- no base, no draw a second time -- and stores the records at
+//            tile offset + prefix of the lanes in front (wave scan by shuffles + the waves' sums), 16 bytes a store
+// The host waits once between scan and emit: the record table is allocated at its exact size.
+#include <algorithm>
+#include <cstring>
+#include <string>
+
+#include "ctx.h"
+#include "plan_gpu.h"
+#include "scan_kernels.h"
+#include "spectrum.h"
+
+namespace msim {
+
+using fastrng::Key;
+using fastrng::U4;
+
+struct SpectrumState {
+    unsigned long long *d_counts = nullptr;   // 64 census bins
+    uint64_t *d_thr = nullptr;                // 192 thresholds
+    uint32_t *d_words = nullptr;              // one outcome word per lane of every tile
+    uint32_t *d_tile = nullptr;               // hits per tile, then their exclusive scan; [n_tiles]: the total
+    size_t cap_words = 0, cap_tile = 0;
+    unsigned long long *h_pin = nullptr;      // pinned: [0..63] census bins / [0..191] thresholds on their way up, [192] the total
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    double census_ms = 0, plan_ms = 0;
+};
+
+namespace {
+
+static_assert(spectrum::TILE == MSIM_SPECTRUM_TILE, "msim.h and spectrum.h must agree on the tile");
+constexpr int LANES = (int)spectrum::TILE_LANES, SITES = (int)spectrum::SITES_PER_LANE;
+constexpr int CENSUS_AHEAD = 4;
+constexpr unsigned CENSUS_MAX_BLOCKS = 2048;  // longer contigs stride (k_ctx_census counts on that: 2^20 tiles / 2048 = 512 a workgroup)
+
+// bases [p0 - 1, p0 + 17) of the contig: the lane's 16 sites and their halo, zeros -- no base -- outside [0, L)
+struct LaneBytes { uint32_t q[4], left, right; };
+__device__ __forceinline__ LaneBytes lane_load(const uint8_t *__restrict__ b, uint64_t L, uint64_t p0) {
+    LaneBytes x{{0, 0, 0, 0}, 0, 0};
+    if (p0 < L) {                                           // (the allocation's slack covers a partial last piece)
+        const uint4 w = *reinterpret_cast<const uint4 *>(b + p0);
+        x.q[0] = w.x; x.q[1] = w.y; x.q[2] = w.z; x.q[3] = w.w;
+        if (p0 > 0) x.left = b[p0 - 1];
+        if (p0 + SITES < L) x.right = b[p0 + SITES];
+        else if (p0 + SITES > L) {                          // the contig's last lane: the bytes behind its end
+            const uint32_t n = (uint32_t)(L - p0);          // 1..15 bases
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                x.q[k] = n >= 4u * k + 4u ? x.q[k] : n <= 4u * k ? 0u : x.q[k] & ((1u << (8 * (n - 4u * k))) - 1u);
+        }
+    }
+    return x;
+}
+// ... and their codes (a zero byte is no base: CODE_INVALID)
+__device__ __forceinline__ void lane_codes(const LaneBytes &x, uint32_t code[SITES + 2]) {
+    code[0] = spectrum::base_code(x.left);
+    code[SITES + 1] = spectrum::base_code(x.right);
+#pragma unroll
+    for (int i = 0; i < SITES; i++) {
+        const uint32_t ch = (x.q[i >> 2] >> (8 * (i & 3))) & 0xffu;
+        code[i + 1] = spectrum::base_code(ch);
+    }
+}
+// site i of the lane (0..15): eligible iff no code of the three has the invalid bit
+__device__ __forceinline__ bool site_ctx(const uint32_t code[SITES + 2], int i, uint32_t &ctx) {
+    ctx = (16 * code[i] + 4 * code[i + 1] + code[i + 2]) & 63u;     // (masked: an ineligible site's value indexes nothing out of range)
+    return ((code[i] | code[i + 1] | code[i + 2]) & spectrum::CODE_INVALID) == 0;
+}
+
+// Every lane counts into 64 16-bit counters of its own (two bins a word, the lane's column of `cnt`): no two lanes share a
+// word and a wave's 64 adds go to 64 different banks, so an add is one conflict-free ds_add whatever the genome holds -- a
+// homopolymer run costs what random bases cost.  A workgroup takes at most 512 tiles (the grid stops at CENSUS_MAX_BLOCKS only
+// beyond that many tiles in all, and a contig has fewer than 2^20), 16 sites a lane each: 8192 a counter at most.
+__global__ __launch_bounds__(LANES) void k_ctx_census(const uint8_t *__restrict__ b, uint64_t L, uint64_t n_tiles,
+                                                      unsigned long long *__restrict__ counts) {
+    __shared__ uint32_t cnt[32][LANES];
+    __shared__ uint32_t part[LANES / 64][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int w = 0; w < 32; w++) cnt[w][threadIdx.x] = 0;  // (a lane's own column: no barrier before its adds)
+    // CENSUS_AHEAD tiles a round, all their loads in flight before the first is counted (16 waves a CU with one 16-byte load
+    // each are little for the memory system to work on; measured it is worth 2 %: the decode below bounds the kernel, NOTES 20)
+    for (uint64_t first = blockIdx.x; first < n_tiles; first += (uint64_t)gridDim.x * CENSUS_AHEAD) {
+        LaneBytes x[CENSUS_AHEAD];
+#pragma unroll
+        for (int k = 0; k < CENSUS_AHEAD; k++) {
+            const uint64_t tile = first + (uint64_t)k * gridDim.x;
+            x[k] = lane_load(b, L, tile < n_tiles ? tile * spectrum::TILE + (uint64_t)threadIdx.x * SITES : L);
+        }
+#pragma unroll
+        for (int k = 0; k < CENSUS_AHEAD; k++) {
+            uint32_t code[SITES + 2];
+            lane_codes(x[k], code);
+#pragma unroll
+            for (int i = 0; i < SITES; i++) {
+                uint32_t ctx;
+                const uint32_t one = site_ctx(code, i, ctx) ? 1u : 0u;
+                atomicAdd(&cnt[ctx >> 1][threadIdx.x], one << (16 * (ctx & 1)));
+            }
+        }
+    }
+    __syncthreads();
+    // bin `lane` over the 64 columns of quarter `wave`: the rotation keeps a wave's 64 reads on 64 banks
+    uint32_t s = 0;
+#pragma unroll 8
+    for (int i = 0; i < 64; i++) s += (cnt[lane >> 1][wave * 64 + ((i + lane) & 63)] >> (16 * (lane & 1))) & 0xffffu;
+    part[wave][lane] = s;
+    __syncthreads();
+    if (threadIdx.x < 64) {
+        uint32_t total = 0;
+#pragma unroll
+        for (int w = 0; w < LANES / 64; w++) total += part[w][threadIdx.x];
+        if (total) atomicAdd(&counts[threadIdx.x], (unsigned long long)total);
+    }
+}
+
+__global__ __launch_bounds__(LANES) void k_spectrum_draw(const uint8_t *__restrict__ b, uint64_t L, const uint64_t *__restrict__ thr,
+                                                         Key key, uint32_t *__restrict__ words, uint32_t *__restrict__ tile_cnt) {
+    __shared__ uint64_t s_thr[192];
+    __shared__ uint64_t s_top[64];                          // thr[3 ctx + 2]: at or above it nothing happens
+    __shared__ uint32_t s_cnt[LANES / 64];
+    if (threadIdx.x < 192) s_thr[threadIdx.x] = thr[threadIdx.x];
+    if (threadIdx.x < 64) s_top[threadIdx.x] = thr[3 * threadIdx.x + 2];
+    __syncthreads();
+    const uint64_t p0 = (uint64_t)blockIdx.x * spectrum::TILE + (uint64_t)threadIdx.x * SITES;
+    uint32_t code[SITES + 2];
+    lane_codes(lane_load(b, L, p0), code);
+    uint32_t word = 0, hits = 0;
+#pragma unroll
+    for (int k = 0; k < SITES / 2; k++) {                   // p0 is even: sites 2k (low 64 bits) and 2k + 1 (high 64 bits) share a call
+        const U4 v = fastrng::draw4(key, (uint32_t)(p0 >> 1) + k, 0, fastrng::TAG_CTX);
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const int i = 2 * k + h;
+            const uint64_t r = h ? fastrng::hi64(v) : fastrng::lo64(v);
+            uint32_t ctx, j = 3;
+            if (site_ctx(code, i, ctx) && r < s_top[ctx]) {
+                j = (uint32_t)(s_thr[3 * ctx] <= r) + (uint32_t)(s_thr[3 * ctx + 1] <= r);
+                hits++;
+            }
+            word |= j << (2 * i);
+        }
+    }
+    words[(uint64_t)blockIdx.x * LANES + threadIdx.x] = word;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) hits += __shfl_xor(hits, o, 64);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = hits;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0;
+#pragma unroll
+        for (int w = 0; w < LANES / 64; w++) s += s_cnt[w];
+        tile_cnt[blockIdx.x] = s;
+    }
+}
+
+__global__ __launch_bounds__(LANES) void k_spectrum_emit(const uint32_t *__restrict__ words, const uint32_t *__restrict__ tile_off,
+                                                         msim_record *__restrict__ recs) {
+    __shared__ uint32_t s_cnt[LANES / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint32_t word = words[(uint64_t)blockIdx.x * LANES + threadIdx.x];
+    uint32_t open = (~word | (~word >> 1)) & 0x55555555u;   // bit 2i: site i's outcome is not 3
+    const uint32_t mine = (uint32_t)__popc(open);
+    uint32_t incl = mine;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t t = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += t;
+    }
+    if (lane == 63) s_cnt[wave] = incl;
+    __syncthreads();
+    uint64_t dst = tile_off[blockIdx.x] + (incl - mine);
+#pragma unroll
+    for (int w = 0; w < LANES / 64 - 1; w++) if (w < wave) dst += s_cnt[w];
+    const uint32_t p0 = blockIdx.x * spectrum::TILE + threadIdx.x * SITES;   // (contigs are below 2^32 bases)
+    uint4 *out = reinterpret_cast<uint4 *>(recs);
+    while (open) {
+        const uint32_t bit = (uint32_t)__ffs((int)open) - 1;
+        open &= open - 1;
+        const uint32_t p = p0 + (bit >> 1), j = (word >> bit) & 3u;
+        out[dst++] = make_uint4(p, p, 0u, (uint32_t)MSIM_SN | (j << 8));     // pos, stop, extra, {type, aux, rsv}
+    }
+}
+
+inline uint64_t tiles_of(uint64_t L) { return (L + spectrum::TILE - 1) / spectrum::TILE; }
+
+int state_of(Ctx *c, SpectrumState **out) {
+    if (!c->spectrum) {
+        SpectrumState *S = new SpectrumState;
+        c->spectrum = S;
+        MSIM_HIP(c, hipMalloc((void **)&S->d_counts, 64 * sizeof(unsigned long long)));
+        MSIM_HIP(c, hipMalloc((void **)&S->d_thr, 192 * sizeof(uint64_t)));
+        MSIM_HIP(c, hipHostMalloc((void **)&S->h_pin, 193 * sizeof(unsigned long long), hipHostMallocDefault));
+        MSIM_HIP(c, hipEventCreate(&S->e0));
+        MSIM_HIP(c, hipEventCreate(&S->e1));
+    }
+    *out = c->spectrum;
+    return MSIM_OK;
+}
+
+// end of a timed stretch (begun by a record of e0): wait for the stream, add the kernels' time
+int stretch_end(Ctx *c, SpectrumState *S, double *acc) {
+    MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+    MSIM_HIP(c, wait_stream(c->stream));
+    float ms = 0;
+    MSIM_HIP(c, hipEventElapsedTime(&ms, S->e0, S->e1));
+    *acc += ms;
+    return MSIM_OK;
+}
+
+int census_device(Ctx *c, SpectrumState *S, const Contig &g, uint64_t counts[64]) {
+    const uint64_t n_tiles = tiles_of(g.len);
+    if (!n_tiles) { memset(counts, 0, 64 * sizeof(uint64_t)); return MSIM_OK; }
+    MSIM_HIP(c, hipMemsetAsync(S->d_counts, 0, 64 * sizeof(unsigned long long), c->stream));
+    MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+    const unsigned blocks = (unsigned)std::min<uint64_t>(n_tiles, CENSUS_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_ctx_census, dim3(blocks), dim3(LANES), 0, c->stream, g.d_in + PAD, g.len, n_tiles, S->d_counts);
+    MSIM_HIP(c, hipGetLastError());
+    MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+    MSIM_HIP(c, hipMemcpyAsync(S->h_pin, S->d_counts, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    MSIM_HIP(c, wait_stream(c->stream));
+    float ms = 0;
+    MSIM_HIP(c, hipEventElapsedTime(&ms, S->e0, S->e1));
+    S->census_ms += ms;
+    for (int i = 0; i < 64; i++) counts[i] = S->h_pin[i];
+    return MSIM_OK;
+}
+
+// leaves the contig planned as plan_device (vcf_parse.hip) does: an SNP-only table of host-known size, no insert pool
+int plan_device(Ctx *c, SpectrumState *S, Contig *g, const uint64_t thr[192], uint64_t key64, uint32_t seq) {
+    int rc = ctx_drain(c);                                 // this contig's buffers may still be read by its last APPLY
+    if (rc) return rc;
+    contig_reset(*g);
+    c->text_kind = 0;
+    g->apply_stream = nullptr;
+    const uint64_t n_tiles = tiles_of(g->len);
+    uint64_t n_rec = 0;
+    if (n_tiles) {
+        rc = dev_reserve(c, (void **)&S->d_words, &S->cap_words, (size_t)n_tiles * LANES * sizeof(uint32_t));
+        if (!rc) rc = dev_reserve(c, (void **)&S->d_tile, &S->cap_tile, (size_t)(n_tiles + 1) * sizeof(uint32_t));
+        if (rc) return rc;
+        memcpy(S->h_pin, thr, 192 * sizeof(uint64_t));
+        MSIM_HIP(c, hipMemcpyAsync(S->d_thr, S->h_pin, 192 * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        const Key key{(uint32_t)key64, (uint32_t)(key64 >> 32), seq};
+        MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+        hipLaunchKernelGGL(k_spectrum_draw, dim3((unsigned)n_tiles), dim3(LANES), 0, c->stream, g->d_in + PAD, g->len, S->d_thr, key,
+                           S->d_words, S->d_tile);
+        hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, S->d_tile, (uint32_t)n_tiles);
+        MSIM_HIP(c, hipGetLastError());
+        MSIM_HIP(c, hipMemcpyAsync(S->h_pin + 192, S->d_tile + n_tiles, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        if ((rc = stretch_end(c, S, &S->plan_ms))) return rc;
+        n_rec = *reinterpret_cast<const uint32_t *>(S->h_pin + 192);
+        if (n_rec >= (1ull << 31)) return fail(c, MSIM_ERR_UNSUPPORTED, "2^31 or more mutations on one contig");
+    }
+    if (n_rec) {
+        rc = dev_reserve(c, (void **)&g->d_recs, &g->cap_recs, (size_t)n_rec * sizeof(msim_record));
+        if (rc) return rc;
+        MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+        hipLaunchKernelGGL(k_spectrum_emit, dim3((unsigned)n_tiles), dim3(LANES), 0, c->stream, S->d_words, S->d_tile, g->d_recs);
+        MSIM_HIP(c, hipGetLastError());
+        if ((rc = stretch_end(c, S, &S->plan_ms))) return rc;
+    }
+    rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, 2 * PAD);
+    if (rc) return rc;
+    g->n_rec = n_rec;
+    g->pool_len = 0;
+    g->plan_empty = n_rec == 0;
+    g->all_snp = true;
+    g->planned = true;
+    return MSIM_OK;
+}
+
+bool thresholds_ordered(const uint64_t thr[192], int *bad_ctx) {
+    for (int x = 0; x < 64; x++)
+        if (thr[3 * x] > thr[3 * x + 1] || thr[3 * x + 1] > thr[3 * x + 2]) { *bad_ctx = x; return false; }
+    return true;
+}
+
+int flushed(Ctx *c) {
+    int rc = flush_deferred_apply(c);
+    if (!rc && c->fast) rc = fast_plan_flush(c);
+    if (!rc && c->gpu) rc = gpu_emit_flush(c);
+    return rc;
+}
+
+}  // namespace
+
+void spectrum_state_destroy(Ctx *c) {
+    SpectrumState *S = c->spectrum;
+    if (!S) return;
+    void *bufs[] = {S->d_counts, S->d_thr, S->d_words, S->d_tile};
+    for (void *p : bufs) if (p) (void)hipFree(p);
+    if (S->h_pin) (void)hipHostFree(S->h_pin);
+    if (S->e0) (void)hipEventDestroy(S->e0);
+    if (S->e1) (void)hipEventDestroy(S->e1);
+    delete S;
+    c->spectrum = nullptr;
+}
+
+void spectrum_reset_timing(Ctx *c) {
+    if (c->spectrum) c->spectrum->census_ms = c->spectrum->plan_ms = 0;
+}
+
+}  // namespace msim
+
+using namespace msim;
+
+extern "C" {
+
+int msim_context_counts(msim_ctx *p, int contig, uint64_t counts[64], uint64_t *n_valid) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c || !counts || !n_valid) return MSIM_ERR_ARG;
+    int rc = flushed(c);
+    if (rc) return rc;
+    if (c->host_only) return fail(c, MSIM_ERR_HIP, "host-only context: this call needs the GPU");
+    if (contig < 0 || (size_t)contig >= c->contigs.size()) return fail(c, MSIM_ERR_ARG, "no such contig");
+    SpectrumState *S;
+    if ((rc = state_of(c, &S))) return rc;
+    TraceRange tr("msim context census");
+    if ((rc = census_device(c, S, c->contigs[(size_t)contig], counts))) return rc;
+    uint64_t n = 0;
+    for (int i = 0; i < 64; i++) n += counts[i];
+    *n_valid = n;
+    return MSIM_OK;
+}
+
+int msim_plan_contig_spectrum(msim_ctx *p, int contig, const uint64_t thr[192], uint64_t key, uint32_t seq) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c || !thr) return MSIM_ERR_ARG;
+    int rc = flushed(c);                                   // (a fast context's queue goes out first)
+    if (rc) return rc;
+    if (c->host_only) return fail(c, MSIM_ERR_HIP, "host-only context: this call needs the GPU");
+    if (contig < 0 || (size_t)contig >= c->contigs.size()) return fail(c, MSIM_ERR_ARG, "no such contig");
+    int bad = 0;
+    if (!thresholds_ordered(thr, &bad))
+        return fail(c, MSIM_ERR_ARG, "spectrum thresholds of context " + std::to_string(bad) + " are not non-decreasing");
+    SpectrumState *S;
+    if ((rc = state_of(c, &S))) return rc;
+    TraceRange tr("msim PLAN contig (spectrum)");
+    return plan_device(c, S, &c->contigs[(size_t)contig], thr, key, seq);
+}
+
+int msim_spectrum_timing(msim_ctx *p, double *census_ms, double *plan_ms) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c) return MSIM_ERR_ARG;
+    if (census_ms) *census_ms = c->spectrum ? c->spectrum->census_ms : 0.0;
+    if (plan_ms) *plan_ms = c->spectrum ? c->spectrum->plan_ms : 0.0;
+    return MSIM_OK;
+}
+
+// ---- sequential host restatements: no context, no GPU ------------------------------------------------------------------
+int msim_dbg_context_counts(const uint8_t *bases, uint64_t L, uint64_t counts[64], uint64_t *n_valid) {
+    if ((!bases && L) || !counts || !n_valid) return MSIM_ERR_ARG;
+    memset(counts, 0, 64 * sizeof(uint64_t));
+    uint64_t n = 0;
+    for (uint64_t q = 1; q + 1 < L; q++) {
+        const uint32_t a = spectrum::base_code(bases[q - 1]), m = spectrum::base_code(bases[q]), z = spectrum::base_code(bases[q + 1]);
+        if ((a | m | z) & spectrum::CODE_INVALID) continue;
+        counts[16 * a + 4 * m + z]++;
+        n++;
+    }
+    *n_valid = n;
+    return MSIM_OK;
+}
+
+int msim_dbg_spectrum_plan(const uint8_t *bases, uint64_t L, const uint64_t thr[192], uint64_t key, uint32_t seq, msim_record *recs,
+                           uint64_t cap, uint64_t *n_recs) {
+    if ((!bases && L) || !thr || !n_recs) return MSIM_ERR_ARG;
+    if (L >= (1ull << 32)) return fail(nullptr, MSIM_ERR_UNSUPPORTED, "contig of 4 GiB or more");
+    int bad = 0;
+    if (!thresholds_ordered(thr, &bad))
+        return fail(nullptr, MSIM_ERR_ARG, "spectrum thresholds of context " + std::to_string(bad) + " are not non-decreasing");
+    const Key k{(uint32_t)key, (uint32_t)(key >> 32), seq};
+    uint64_t n = 0;
+    for (uint64_t q = 1; q + 1 < L; q++) {
+        const uint32_t a = spectrum::base_code(bases[q - 1]), m = spectrum::base_code(bases[q]), z = spectrum::base_code(bases[q + 1]);
+        if ((a | m | z) & spectrum::CODE_INVALID) continue;
+        const U4 v = fastrng::draw4(k, (uint32_t)(q >> 1), 0, fastrng::TAG_CTX);
+        const uint32_t j = spectrum::outcome(thr + 3 * (16 * a + 4 * m + z), spectrum::site_bits(v, q));
+        if (j == 3) continue;
+        if (recs) {
+            if (n >= cap) return fail(nullptr, MSIM_ERR_ARG, "buffers too small");
+            recs[n] = msim_record{(uint32_t)q, (uint32_t)q, 0u, (uint8_t)MSIM_SN, (uint8_t)j, 0};
+        }
+        n++;
+    }
+    if (n >= (1ull << 31)) return fail(nullptr, MSIM_ERR_UNSUPPORTED, "2^31 or more mutations on one contig");
+    *n_recs = n;
+    return MSIM_OK;
+}
+
+}  // extern "C"

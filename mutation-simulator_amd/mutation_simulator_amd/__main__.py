@@ -9,7 +9,8 @@ from timeit import default_timer as timer
 
 from . import *  # noqa: F401,F403  (same style of namespace as the reference entry point)
 from ._ffi import MsimError, MsimUnsupported
-from .argument_parser import ploidy_refusal
+from .argument_parser import ploidy_refusal, spectrum_refusal
+from .spectrum import SpectrumError
 from .fasta_io import is_gzip
 
 _INIT_ERRORS = (FileNotFoundError, ITNotEnoughAvailChromsError, RatesTooHighError, RatesTooLowError,
@@ -38,6 +39,10 @@ class PloidyUnsupportedError(Exception):
     """--ploidy 2 together with what it does not cover (argument_parser.ploidy_refusal)."""
 
 
+class SpectrumUnsupportedError(Exception):
+    """--spectrum together with what it does not cover (argument_parser.spectrum_refusal)."""
+
+
 class CompressedInputUnsupportedError(Exception):
     """A gzip-compressed input together with what does not cover it (a sharded run)."""
 
@@ -57,6 +62,15 @@ def initialize(argv=None):
     refusal = ploidy_refusal(args)
     if refusal:
         exit_with_error(PloidyUnsupportedError(refusal), args.no_color)
+    refusal = spectrum_refusal(args)
+    if refusal:
+        exit_with_error(SpectrumUnsupportedError(refusal), args.no_color)
+    if getattr(args, "spectrum", None) is not None:    # (read before the GPU comes up: a file that cannot be used ends the run here)
+        from .spectrum import load as load_spectrum
+        try:
+            args.spectrum_weights = load_spectrum(args.spectrum, args.signature)
+        except SpectrumError as e:
+            exit_with_error(e, args.no_color)
     if args.mode == "vcf" and (args.gpus or 1) > 1:
         exit_with_error(VcfModeUnsupportedError("the vcf mode needs a single-GPU run (--gpus 1)"), args.no_color)
     if args.bgzip and args.mode == "it":
@@ -160,11 +174,13 @@ def main(argv=None):
                 stats = dict(mutator.stats)
                 from . import mutator as _m
                 stats["replanned_contigs"] = _m.REPLANNED_CONTIGS     # device window overflows recovered on the host (expected: 0)
+                if getattr(args, "spectrum", None) is not None:
+                    stats["census_ms"], stats["spectrum_plan_ms"] = (round(x, 4) for x in mutator.spectrum_ms)
                 stats["cli_s"] = {"load_index_settings": round(loaded - start, 4), "mutate_and_write": round(timer() - loaded, 4),
                                   "parse_args": round(STAGES.get("parse_args", 0.0), 4), "load_index": round(STAGES.get("load_index", 0.0), 4),
                                   "open_writers": round(t1 - t0, 4), "mutate": round(t2 - t1, 4), "close": round(timer() - t2, 4)}
                 args.bench_json.write_text(json.dumps(stats, indent=1) + "\n")
-        except (FastaWriterError, VcfWriterError, ChainWriterError, MsimError) as e:
+        except (FastaWriterError, VcfWriterError, ChainWriterError, MsimError, SpectrumError) as e:
             exit_with_error(e, args.no_color)
     if sim.has_it:                         # the second pass reads what the first one wrote (reference __main__.py:88-102)
         if sim.has_mutations:

@@ -170,9 +170,15 @@ SYMBOLS = [
     ("msim_gather_fetch", C.c_int, [_VP, C.c_uint64, C.c_uint64, _VP]),
     ("msim_dbg_snp_draws", C.c_int, [_VP, _VP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _VP, _VP, _U64P,
                                      _U32P, _VP]),
+    ("msim_context_counts", C.c_int, [_VP, C.c_int, _VP, _U64P]),
+    ("msim_plan_contig_spectrum", C.c_int, [_VP, C.c_int, _VP, C.c_uint64, C.c_uint32]),
+    ("msim_spectrum_timing", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    ("msim_dbg_context_counts", C.c_int, [_VP, C.c_uint64, _VP, _U64P]),
+    ("msim_dbg_spectrum_plan", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, C.c_uint32, _VP, C.c_uint64, _U64P]),
     ("msim_stats", C.c_int, [_VP, C.POINTER(Timing)]),
     ("msim_reset_stats", C.c_int, [_VP]),
 ]
+SPECTRUM_TILE = 4096     # msim.h: MSIM_SPECTRUM_TILE, the bases one workgroup of the spectrum sampler takes
 
 _lib = None
 
@@ -585,6 +591,26 @@ class Engine:
 
     def vcf_release(self):
         self._check(self.lib.msim_vcf_release(self.h))
+
+    # ------------------------------------------------------------------ context-dependent SNPs (msim.h: a 96-channel spectrum)
+    def context_counts(self, contig: int):
+        """Device census of a resident contig: (counts of its eligible sites per trinucleotide context, uint64[64]; their sum)."""
+        counts = np.zeros(64, dtype=np.uint64)
+        n = C.c_uint64()
+        self._check(self.lib.msim_context_counts(self.h, int(contig), _ptr(counts), C.byref(n)), contig)
+        return counts, n.value
+
+    def plan_contig_spectrum(self, contig: int, thr, key: int, seq: int):
+        """Every eligible site of the contig mutates by its own Philox draw (counter (site >> 1, 0, ``seq``, tag 21) under the
+        64-bit ``key``) against ``thr`` (192 thresholds, ``spectrum.thresholds``); leaves the contig planned."""
+        thr = _thr_array(thr)
+        self._check(self.lib.msim_plan_contig_spectrum(self.h, int(contig), _ptr(thr), int(key) & (2**64 - 1), int(seq)), contig)
+
+    def spectrum_timing(self) -> tuple:
+        """(census, plan) kernel milliseconds since ``reset_stats`` (HIP events)."""
+        a, b = C.c_double(), C.c_double()
+        self._check(self.lib.msim_spectrum_timing(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     # test hooks (msim_dbg_*: exported, not part of include/msim.h)
     def set_records(self, contig: int, recs: np.ndarray, pool: np.ndarray, with_offsets: bool = False):
@@ -1098,6 +1124,52 @@ def hap_block() -> int:
     fn = load().msim_dbg_hap_block
     fn.restype, fn.argtypes = C.c_uint32, []
     return int(fn())
+
+
+def _thr_array(thr) -> np.ndarray:
+    thr = np.array([int(x) for x in thr], dtype=np.uint64) if not isinstance(thr, np.ndarray) else np.ascontiguousarray(thr, dtype=np.uint64)
+    if thr.shape != (192,):
+        raise ValueError("a spectrum has 192 thresholds (64 contexts x 3 alternative bases)")
+    return thr
+
+
+def _host_error(rc: int) -> MsimError:
+    err = (MsimUnsupported if rc == ERR_UNSUPPORTED else MsimError)(f"libmsim error {rc}: {load().msim_last_error(None).decode()}")
+    err.code = rc
+    return err
+
+
+def context_counts_host(bases) -> tuple:
+    """``msim_dbg_context_counts``: the census of ``Engine.context_counts`` by a sequential host loop over ``bases`` (uint8,
+    upper-cased).  No context, no GPU."""
+    lib = load()
+    bases = _as_u8(bases)
+    counts = np.zeros(64, dtype=np.uint64)
+    n = C.c_uint64()
+    rc = lib.msim_dbg_context_counts(C.c_void_p(bases.ctypes.data) if len(bases) else None, len(bases), _ptr(counts), C.byref(n))
+    if rc != OK:
+        raise _host_error(rc)
+    return counts, n.value
+
+
+def spectrum_plan_host(bases, thr, key: int, seq: int) -> np.ndarray:
+    """``msim_dbg_spectrum_plan``: the record table ``Engine.plan_contig_spectrum`` leaves (RECORD_DTYPE), by a sequential host
+    loop.  No context, no GPU."""
+    lib = load()
+    bases = _as_u8(bases)
+    thr = _thr_array(thr)
+    src = C.c_void_p(bases.ctypes.data) if len(bases) else None
+    n = C.c_uint64()
+    key = int(key) & (2**64 - 1)
+    rc = lib.msim_dbg_spectrum_plan(src, len(bases), _ptr(thr), key, int(seq), None, 0, C.byref(n))
+    if rc != OK:
+        raise _host_error(rc)
+    recs = np.zeros(n.value, dtype=RECORD_DTYPE)
+    if n.value:
+        rc = lib.msim_dbg_spectrum_plan(src, len(bases), _ptr(thr), key, int(seq), _ptr(recs), n.value, C.byref(n))
+        if rc != OK:
+            raise _host_error(rc)
+    return recs
 
 
 VCF_GROUP_DTYPE = np.dtype([("name_off", "<u8"), ("first_line", "<u8"), ("n_lines", "<u8"), ("name_len", "<u4"), ("rsv", "<u4")])   # msim_vcf_group

@@ -1,6 +1,7 @@
 """Command line of ``mutation-simulator`` -- flag-for-flag the reference's ``args`` and ``rmt``
 sub-commands (reference argument_parser.py:31-240) plus a few additions of ours that never change
-a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bgzip``, ``--chain``, ``--ploidy``, ``--het``, ``--bench-json``, and the ``vcf`` sub-command
+a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bgzip``, ``--chain``, ``--ploidy``, ``--het``, ``--bench-json``, ``--spectrum`` / ``--signature``
+(options of ``args``: SNPs drawn per trinucleotide context, ``spectrum.py``; ``spectrum_refusal`` words what such a run does not cover), and the ``vcf`` sub-command
 (``vcf_replay.py``: the mutated Fasta again from the reference and a run's VCF; it writes ``<outbase>_ms.fa`` and, with
 ``--chain``, ``<outbase>_ms.chain``; with ``--consensus [--sample NAME] [--haplotype N]`` the VCF may come from anywhere).
 
@@ -143,6 +144,14 @@ def build_parser() -> ArgumentParser:
         p_args.add_argument(short, long, default=default,
                             help=f"{what} name for the VCF file. Default = '{default}'")
 
+    p_args.add_argument("--spectrum", type=Path, default=None, metavar="FILE",
+                        help="Draw the SNPs per trinucleotide context from a 96-channel mutational spectrum (rows N[X>Y]N with X in "
+                             "C, T -- COSMIC's SBS tables as published): every site mutates independently, -sn is the expected "
+                             "fraction of a contig's sites, the file decides which. -snb and -titv do not apply. Needs --rng fast; "
+                             "SNPs only; not with --gpus N > 1")
+    p_args.add_argument("--signature", default=None, metavar="NAME",
+                        help="With --spectrum: the column of the file's header to use. Default = the first value column")
+
     p_it = sub.add_parser("it", help="Generate interchromosomal translocations via the command line")
     p_it.add_argument("interchromosomalrate", type=float,
                       help="Rate of interchromosomal translocations")
@@ -181,6 +190,28 @@ def ploidy_refusal(args: Namespace, has_it: bool = False):
     return None
 
 
+def spectrum_refusal(args: Namespace):
+    """What a ``--spectrum`` run does not cover, as the message to refuse it with; None: the run can go ahead (or has no
+    spectrum)."""
+    if getattr(args, "spectrum", None) is None:
+        return None
+    if args.mode != "args":
+        return f"--spectrum does not apply to the {args.mode} mode (it belongs to args: -sn RATE --spectrum FILE)"
+    if getattr(args, "rng", "compat") != "fast":
+        return ("--spectrum needs --rng fast: its SNPs are drawn per site from a counter-based generator and are not the "
+                "reference's numbers under any seed (--rng compat promises those)")
+    rates = {"-in": args.insert, "-de": args.deletion, "-iv": args.inversion, "-du": args.duplication, "-tl": args.translocation}
+    others = [flag for flag, rate in rates.items() if rate]
+    if others:
+        return (f"--spectrum draws SNPs only ({', '.join(others)} given): structural variants beside a spectrum are a follow-up; "
+                "run them as a second pass")
+    if not args.snp:
+        return "--spectrum needs an SNP rate (-sn RATE): the expected fraction of a contig's sites that mutate"
+    if (args.gpus or 1) > 1:
+        return "--spectrum needs a single-GPU run (--gpus 1)"
+    return None
+
+
 def get_args(argv=None) -> Namespace:
     parser = build_parser()
     args = parser.parse_args(argv)
@@ -190,6 +221,8 @@ def get_args(argv=None) -> Namespace:
         parser.error("--het is a fraction in [0, 1]")
     if args.ploidy == 2 and args.het is None:
         args.het = 0.5
+    if getattr(args, "signature", None) is not None and args.spectrum is None:
+        parser.error("--signature needs --spectrum")
     if args.mode == "vcf" and args.ploidy != 2:        # (the namespace of a replay stays as it was; --ploidy 2 is refused later)
         del args.ploidy, args.het
     if args.mode == "vcf":

@@ -16,6 +16,8 @@ changed is *where* the work happens:
   FastaWriter.write per base               -> msim_fetch_sequence_framed: line-wrapped on the device, one write
   VcfWriter.write per record               -> msim_render_vcf_device: record lines rendered on the device
   (no counterpart: --chain)                -> msim_render_chain_device: the record table as a liftover chain
+  (no counterpart: --spectrum)             -> msim_context_counts + msim_plan_contig_spectrum: a census of the contig's
+                                              trinucleotides, then a draw per site in place of msim_plan_contig
   (no counterpart: --ploidy 2)             -> msim_genotype_contig + msim_select_haplotype: one plan, a genotype per record,
                                               the two haplotypes' records applied one after the other
 
@@ -34,7 +36,7 @@ from typing import Optional
 
 import numpy as np
 
-from . import _ffi
+from . import _ffi, spectrum
 from .chain_writer import ChainWriter
 from .fasta_writer import FastaWriter
 from .mut_types import MutType
@@ -325,6 +327,9 @@ class Mutator:
     _fasta_writer_h2 = None
     _chain_writer_h2 = None
     _gt_key = 0
+    _fast_key = 0                                      # --rng fast: the run's Philox key (--spectrum draws under it too)
+    _spectrum = None                                   # --spectrum: the 96 channel weights (spectrum.CHANNELS order)
+    spectrum_ms = (0.0, 0.0)                           # ... and the census's / the plans' kernel time of the last mutate()
 
     def __init__(self, args, fasta, sim, engine: Optional["_ffi.Engine"] = None):
         self._args = args
@@ -346,6 +351,8 @@ class Mutator:
         else:
             self._chain_writer = ChainWriter(args.outchain) if getattr(args, "chain", False) else None
             self._fasta_writer = FastaWriter(args.outfasta, bgzip=self._bgzip, device=dev)
+        if getattr(args, "spectrum", None) is not None:
+            self._spectrum = getattr(args, "spectrum_weights", None) or spectrum.load(args.spectrum, getattr(args, "signature", None))
         self._vcf_writer = VcfWriter(args.outvcf, bgzip=self._bgzip, device=dev)
         self._vcf_writer.write_header(getattr(args, "genome_name", args.infile.name), fasta, sim.assembly_name, sim.species_name,
                                       sim.sample_name)
@@ -412,7 +419,8 @@ class Mutator:
             words = np.array(random.getstate()[1], dtype=np.uint32)          # the 624 words and the index
             self._gt_key = int.from_bytes(hashlib.blake2b(words.tobytes(), digest_size=8).digest(), "little")
         if self._fast_rng:
-            eng.set_fast_key(random.getrandbits(64))       # (from Python's generator: --seed / random.seed() decide the run)
+            self._fast_key = random.getrandbits(64)        # (from Python's generator: --seed / random.seed() decide the run)
+            eng.set_fast_key(self._fast_key)
         else:
             export_python_streams(eng)
 
@@ -552,8 +560,15 @@ class Mutator:
             cid = eng.add_contig(rec.bases)
         t1 = time.perf_counter()
         t["ingest_s"] += t1 - t0
-        table = plan_table(chrom)
-        eng.plan_contig(cid, table)
+        if self._spectrum is not None:
+            # --spectrum: the one plan that reads the genome -- a census of the contig's trinucleotides, the channels'
+            # probabilities from it in exact arithmetic (spectrum.py), a draw per site on the device
+            counts, _ = eng.context_counts(cid)
+            thr = spectrum.thresholds(counts, self._spectrum, self._args.snp)
+            eng.plan_contig_spectrum(cid, thr, self._fast_key, chrom.number)
+        else:
+            table = plan_table(chrom)
+            eng.plan_contig(cid, table)
         if eng.plan_was_empty(cid) and "warned" not in done:
             self._warn_empty(chrom)
             done.add("warned")
@@ -752,4 +767,6 @@ class Mutator:
             if not self._fast_rng:
                 import_python_streams(eng)
             self.stats = eng.stats()
+            if self._spectrum is not None:
+                self.spectrum_ms = eng.spectrum_timing()
             self.stats["contig_path_s"] = {k: round(v, 4) for k, v in self._t.items()}
