@@ -180,6 +180,8 @@ struct GpuPlan {
     int emit_train = 0;                 //   launches of an emission group's train: 3, 6, or 0 = by the context's role (gpu_emit_flush; MSIM_EMIT_TRAIN)
     uint32_t max_chunks = MT_JUMP_MAX_CHUNKS;   //   chunks one (re)seeded session may span (MSIM_DBG_JUMP_MAX_CHUNKS lowers it)
     uint32_t rebases = 0;               //   sessions ended because the next contig would not fit into the span
+    uint32_t cand_cap = 0xffffffffu;    //   test knob (MSIM_DBG_CAND_CAP): caps the 16-sigma bound of the chain's candidates, so
+                                        //   that the "beyond the bound" paths of the SV-mix and host-chain engines run
     // anchored windows: the CPython stream's position as the host knows it between two exact readings -- mean and variance of
     // the words consumed since (the sampler's rejections and duplicates, the SNP draws' transversion loops), a hard lower bound
     hipStream_t prep_stream = nullptr;  //   the off-chain part of the samples: the stream of the sample being enqueued,
@@ -236,6 +238,7 @@ GpuPlan *gpu_plan_create() {
     if (const char *e = getenv("MSIM_EMIT_GROUP")) g->emit_group = std::min(EMIT_G, std::max(0, atoi(e)));
     if (const char *e = getenv("MSIM_DBG_JUMP_MAX_CHUNKS"))
         g->max_chunks = (uint32_t)std::min<long>(MT_JUMP_MAX_CHUNKS, std::max<long>(2, atol(e)));
+    if (const char *e = getenv("MSIM_DBG_CAND_CAP")) g->cand_cap = (uint32_t)std::min<long>(0xffffffffl, std::max<long>(1, atol(e)));
     if (const char *e = getenv("MSIM_EMIT_TRAIN")) g->emit_train = atoi(e) == 3 ? 3 : atoi(e) == 6 ? 6 : 0;
     if (getenv("MSIM_NO_AHEAD")) g->ahead = 0;
     else if (const char *e = getenv("MSIM_AHEAD")) g->ahead = std::min(2, std::max(0, atoi(e)));
@@ -1621,6 +1624,71 @@ static int ensure_signals(Ctx *c, GpuPlan *g) {
     return MSIM_OK;
 }
 
+// ---- The piecewise hand-over of the engines with a host chain: what the device made for the host (candidates, accept tables,
+// word window) goes to pinned memory in three pieces -- 1/8, 3/8, 1/2 of the positions -- with an event behind each, and the
+// host starts on the first piece while the others are in flight: it consumes a table at ~3 GB/s, the copies deliver 50 GB/s.
+// The candidates travel the same way: with one copy of 3.75 MB (a big contig of config 3) it was the candidates, not the table,
+// that the walk waited for.  One piece: a plain copy with its event (the host-chain engine's candidates).
+// A lane is one array of a hand-over: `stride` bytes per position, `tail` positions more in the last piece (the accept tables'
+// end-of-window sentinel where the pieces are counted in words).  Lanes share the pieces; per piece their copies go out in order.
+struct HandLane { void *dst; const void *src; size_t stride, tail; };
+struct Handover {
+    Ctx *c = nullptr;
+    hipEvent_t *ev = nullptr;            // one per piece (GpuPlan::ev_piece / ev_cpiece / ev_cand)
+    const char *what = nullptr;          // names the wait at its deadline (spin_event)
+    size_t cut[4] = {0, 0, 0, 0};
+    int pieces = 0, next = 0;            // next: first piece the host has not taken yet
+    double wait_us = 0;                  // what the host spent in more()
+    // sender: positions [from, to) of every lane, copied on `s` with ev_[q] recorded behind piece q (an empty piece too)
+    int send(Ctx *c_, hipStream_t s, hipEvent_t *ev_, const char *what_, size_t from, size_t to, std::initializer_list<HandLane> lanes,
+             int pieces_ = 3) {
+        const size_t c1 = pieces_ == 1 ? to : from + (to - from) / 8, c2 = pieces_ == 1 ? to : from + (to - from) / 2;
+        *this = Handover{c_, ev_, what_, {from, c1, c2, to}, pieces_, 0, 0.0};
+        for (int q = 0; q < pieces; q++) {
+            const size_t a = cut[q], b = cut[q + 1];
+            for (const HandLane &l : lanes) {
+                const size_t bl = b + (q == pieces - 1 ? l.tail : 0);
+                if (bl > a)
+                    MSIM_HIP(c, hipMemcpyAsync(static_cast<uint8_t *>(l.dst) + a * l.stride, static_cast<const uint8_t *>(l.src) + a * l.stride,
+                                               (bl - a) * l.stride, hipMemcpyDeviceToHost, s));
+            }
+            MSIM_HIP(c, hipEventRecord(ev[q], s));
+        }
+        return MSIM_OK;
+    }
+    bool drained() const { return next >= pieces; }      // the host has taken every piece (or nothing was sent)
+    hipEvent_t last() const { return ev[pieces - 1]; }   // behind the last copy
+    // consumer: block until the next piece has landed; *avail = positions [.., *avail) are there.  Drained: nothing happens.
+    int more(size_t *avail) {
+        if (drained()) return MSIM_OK;
+        const auto w0 = std::chrono::steady_clock::now();
+        const int rc = spin_event(c, ev[next], what);
+        wait_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count();
+        if (!rc) *avail = cut[++next];
+        return rc;
+    }
+    WordFeed feed() { return WordFeed{[](void *u, size_t *avail) { return static_cast<Handover *>(u)->more(avail); }, this}; }
+};
+
+// The chain's candidates go to the host beside the plan stream, on the copy stream, and before their number is known there: a
+// 16-sigma bound of it first (from = 0: behind everything on the plan stream so far), the rest -- if ever -- after the poll.
+// ids: nsn_pos or nsn_rank -> its pinned block; types likewise.  pieces: 3, or 1 copy.  ev_cand: behind every copy so far.
+static int cands_to_host(Ctx *c, GpuPlan *g, Handover &ho, HandLane ids, HandLane types, size_t from, size_t to, int pieces) {
+    if (!from) {
+        hipEvent_t se = next_chain_event(g);
+        MSIM_HIP(c, hipEventRecord(se, c->stream));
+        MSIM_HIP(c, hipStreamWaitEvent(g->copy_stream, se, 0));
+    }
+    const bool one = pieces == 1;                          // (its event is ev_cand itself)
+    const int rc = ho.send(c, g->copy_stream, one ? &g->ev_cand : g->ev_cpiece, one ? "spin_event(candidates of the host chain, copy stream)"
+                           : "spin_event(candidate piece, copy stream)", from, to, {ids, types}, pieces);
+    if (!rc && !one) MSIM_HIP(c, hipEventRecord(g->ev_cand, g->copy_stream));
+    return rc;
+}
+
+// A device engine gives up on a contig (a window overflowed, the host chain failed): nothing of the session is known any more
+static void plan_failed(GpuPlan *g) { g->s[0].live = g->s[1].live = false; g->unverified = false; }
+
 // Exact stream position + counts from the mailbox, chain time accounted -- without draining the stream: the mailbox
 // kernel writes a sequence word last and the host polls it (a stream synchronisation costs 25-35 us of wake-up
 // latency per call, twice per contig)
@@ -1643,8 +1711,7 @@ static int mixed_poll(Ctx *c, GpuPlan *g, PlanState &h, F &&behind_mailbox) {
     c->t.plan_gpu_ms += ms;
     h = *g->h_mail;
     if (h.flags & (FLAG_SAMPLE_OVERFLOW | FLAG_SNP_OVERFLOW)) {
-        g->s[0].live = g->s[1].live = false;
-        g->unverified = false;
+        plan_failed(g);
         return fail(c, MSIM_ERR_HIP, "GPU sampler: a stream window overflowed its margin (16 sigma; 8 for the start of a sample planned ahead of the chain; results discarded)");
     }
     c->t.py_words += h.pos - g->verified_pos;
@@ -1854,6 +1921,55 @@ static int mixed_link_translocations(Ctx *c, GpuPlan *g, MixedSet &M, uint32_t n
     return MSIM_OK;
 }
 
+// ---- What the SV-mix, host-cut and host-chain engines share besides the hand-over
+// The next scratch set.  Its last emit may still read it: the plan stream waits for that -- or the HOST does, where the host is
+// about to write the set's pinned staging (walk_h / mm_h), whose copy to the device may still be in flight.
+static int mixed_acquire(Ctx *c, GpuPlan *g, bool host_writes_staging, MixedSet *&out) {
+    MixedSet &M = g->mixed[g->mixed_unit++ % N_SETS];
+    int rc;
+    if (host_writes_staging) {
+        if (M.pending) MSIM_HIP(c, wait_event(M.emit_done));
+        M.pending = false;
+    } else if ((rc = wait_if_pending(c, M.pending, M.emit_done))) return rc;
+    if (!M.emit_done) MSIM_HIP(c, hipEventCreateWithFlags(&M.emit_done, hipEventDisableTiming));
+    out = &M;
+    return MSIM_OK;
+}
+
+static TypeTable type_table_of(const msim_range &r) {
+    TypeTable tt{};
+    tt.n = (uint32_t)r.n_types;
+    for (int j = 0; j < r.n_types; j++) { tt.thr[j] = r.cdf_thr[j]; tt.type[j] = (uint8_t)r.types[j]; }
+    return tt;
+}
+
+// the share of a range's candidates that is on the chain: every type but SNP that its draw can produce
+static double chain_share(const msim_range &r) {
+    double q = 0;
+    for (int j = 0; j < r.n_types; j++)
+        if (r.types[j] != MSIM_SN && type_drawable(r, j)) q += type_probability(r, j);
+    return std::min(1.0, q);
+}
+
+// What the host decided about the chain's n candidates, from chain order back to candidate order (k candidates): the stops and,
+// with translocations, what __link_tls decided (linked spans, flags, tombstones).  visit_*: the host-chain engine's visit table,
+// which travels between the stops' copy and their scatter.  No launch is checked here: the caller asks hipGetLastError.
+static int verdicts_to_device(Ctx *c, GpuPlan *g, MixedSet &M, uint32_t n, uint32_t k, bool has_tl, uint32_t *visit_d = nullptr,
+                              const uint32_t *visit_h = nullptr, size_t n_visit = 0) {
+    if (n) MSIM_HIP(c, hipMemcpyAsync(M.nsn_stop, g->h_nstop, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if (n_visit) MSIM_HIP(c, hipMemcpyAsync(visit_d, visit_h, n_visit * 4, hipMemcpyHostToDevice, c->stream));
+    if (n) stop_scatter_launch(c->stream, M.nsn_rank, M.nsn_stop, n, M.cand_stop);
+    if (has_tl) {
+        MSIM_HIP(c, hipMemsetAsync(M.cand_aux, 0, (size_t)k, c->stream));
+        if (n) {
+            MSIM_HIP(c, hipMemcpyAsync(M.nsn_extra, g->h_nextra, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            MSIM_HIP(c, hipMemcpyAsync(M.nsn_aux, g->h_naux, (size_t)n, hipMemcpyHostToDevice, c->stream));
+            link_scatter_launch(c->stream, M.nsn_rank, M.nsn_extra, M.nsn_aux, n, M.cand_extra, M.cand_aux);
+        }
+    }
+    return MSIM_OK;
+}
+
 int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, int n_ranges) {
     const msim_params &P = c->params;
     const int64_t d = min_block(P);
@@ -1865,9 +1981,9 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
     if ((rc = session_open(c, g)) || (rc = chain_open(c, g, false))) return rc;
     GpuStream &py = g->s[0], &np = g->s[1];
     bool grew = false;
-    MixedSet &M = g->mixed[g->mixed_unit++ % N_SETS];
-    if ((rc = wait_if_pending(c, M.pending, M.emit_done))) return rc;          // its last emit may still read it
-    if (!M.emit_done) MSIM_HIP(c, hipEventCreateWithFlags(&M.emit_done, hipEventDisableTiming));
+    MixedSet *Mp;
+    if ((rc = mixed_acquire(c, g, false, Mp))) return rc;
+    MixedSet &M = *Mp;
     const uint32_t nbk = (k + CB_BLOCK - 1) / CB_BLOCK;
     if ((rc = grow(c, (void **)&M.cand_pos, &M.cap_pos, (size_t)k * 4 + 64, &grew))) return rc;
     if ((rc = grow(c, (void **)&M.cand_type, &M.cap_type, (size_t)k + 64, &grew))) return rc;
@@ -1906,39 +2022,18 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
     SampleSet &S = *sl.S;
     const uint64_t np_base = np.pos;                       // exact: the NumPy stream never rejects
     if ((rc = ensure_words(c, g, 1, np_base + 2ull * k + 1))) return rc;
-    TypeTable tt{};
-    tt.n = (uint32_t)r.n_types;
-    for (int j = 0; j < r.n_types; j++) { tt.thr[j] = r.cdf_thr[j]; tt.type[j] = (uint8_t)r.types[j]; }
     cand_front_launch(c->stream, reinterpret_cast<const uint64_t *>(S.bitmap), sl.bmw, S.cnt2, (uint32_t)r.start, (uint32_t)d, np.d_raw,
-                      (unsigned long long)np_base, tt, M.cand_pos, M.cand_type);
+                      (unsigned long long)np_base, type_table_of(r), M.cand_pos, M.cand_type);
     nsn_compact_launch(c->stream, M.cand_pos, M.cand_type, k, cnt_nsn, M.nsn_pos, M.nsn_type, M.nsn_rank, g->d_ps, false);
     MSIM_HIP(c, hipGetLastError());
     S.pending = false;                                     // consumed on the plan stream itself
-    // The host walks the non-SNP candidates.  Their copy starts at once, beside the plan stream and before their number
-    // is known here: a 16-sigma bound of the type draw's binomial is copied (the rest, if ever, afterwards).
+    // The host walks the non-SNP candidates.  Their copy starts at once: a 16-sigma bound of the type draw's binomial, in pieces
     if ((rc = ensure_signals(c, g))) return rc;
-    double q_nsn = 0;
-    for (int j = 0; j < r.n_types; j++)
-        if (r.types[j] != MSIM_SN && type_drawable(r, j)) q_nsn += type_probability(r, j);
-    q_nsn = std::min(1.0, q_nsn);
-    const uint32_t n_hi = (uint32_t)std::min<double>(k, q_nsn * k + 16.0 * std::sqrt(q_nsn * (1.0 - q_nsn) * k) + 64.0);
-    const size_t ccut[4] = {0, (size_t)n_hi / 8, (size_t)n_hi / 2, (size_t)n_hi};
-    {
-        hipEvent_t se = next_chain_event(g);
-        MSIM_HIP(c, hipEventRecord(se, c->stream));
-        MSIM_HIP(c, hipStreamWaitEvent(g->copy_stream, se, 0));
-        // in three pieces (1/8, 3/8, 1/2), like the tables: the walk starts on the first one -- with one copy of 3.75 MB (a big
-        // contig of config 3) it was the candidates, not the table, that the walk waited for
-        for (int q = 0; q < 3; q++) {
-            const size_t a = ccut[q], b = ccut[q + 1];
-            if (b > a) {
-                MSIM_HIP(c, hipMemcpyAsync(g->h_npos + a, M.nsn_pos + a, (b - a) * 4, hipMemcpyDeviceToHost, g->copy_stream));
-                MSIM_HIP(c, hipMemcpyAsync(g->h_ntype + a, M.nsn_type + a, b - a, hipMemcpyDeviceToHost, g->copy_stream));
-            }
-            MSIM_HIP(c, hipEventRecord(g->ev_cpiece[q], g->copy_stream));
-        }
-        MSIM_HIP(c, hipEventRecord(g->ev_cand, g->copy_stream));
-    }
+    const double q_nsn = chain_share(r);
+    const uint32_t n_hi = std::min(g->cand_cap, (uint32_t)std::min<double>(k, q_nsn * k + 16.0 * std::sqrt(q_nsn * (1.0 - q_nsn) * k) + 64.0));
+    const HandLane c_pos{g->h_npos, M.nsn_pos, 4, 0}, c_type{g->h_ntype, M.nsn_type, 1, 0};
+    Handover cands, cands_rest, tabs;
+    if ((rc = cands_to_host(c, g, cands, c_pos, c_type, 0, n_hi, 3))) return rc;
     // The accept tables of the boundary walk depend on where the sample ended (the device knows) and on the window's size --
     // which follows from the number of non-SNP candidates, known only after the poll: they are launched BEHIND the mailbox
     // kernel over a 16-sigma bound of it, so that they are under way while the host still polls.
@@ -1949,7 +2044,11 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
     const uint32_t lg = chain_lg_rows(cc);
     const bool early = tables && n_hi > 0 && window_of((double)n_hi) < 4.0e9;
     const uint32_t Wb_hi = early ? (uint32_t)window_of((double)n_hi) : 0u;
-    size_t cut[4] = {0, 0, 0, 0};
+    // the tables' hand-over, Wb + 1 rows of 1 << lg entries: on the plan stream, behind the kernel that makes them
+    auto tables_to_host = [&](uint32_t Wb) {
+        return tabs.send(c, c->stream, g->ev_piece, "spin_event(accept-table piece, plan stream)", 0, (size_t)Wb + 1,
+                         {HandLane{g->h_words, M.words, (size_t)4 << lg, 0}});
+    };
     if (early) {
         const size_t bytes = ((size_t)(Wb_hi + 1) << lg) * 4;
         if (g->cap_h_words < bytes) {
@@ -1965,16 +2064,7 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
         if (!early) return MSIM_OK;
         accept_tables_ps_launch(c->stream, py.d_raw, g->d_ps, Wb_hi, cc, lg, M.words);
         MSIM_HIP(c, hipGetLastError());
-        // three pieces (1/8, 3/8, 1/2 of the positions): the walk starts on the first one while the others are in flight -- it
-        // consumes the table at ~3 GB/s, the copies deliver 50 GB/s
-        cut[1] = (size_t)(Wb_hi + 1) / 8; cut[2] = (size_t)(Wb_hi + 1) / 2; cut[3] = (size_t)Wb_hi + 1;
-        for (int q = 0; q < 3; q++) {
-            if (cut[q + 1] > cut[q])
-                MSIM_HIP(c, hipMemcpyAsync(g->h_words + (cut[q] << lg), M.words + (cut[q] << lg), ((cut[q + 1] - cut[q]) << lg) * 4,
-                                           hipMemcpyDeviceToHost, c->stream));
-            MSIM_HIP(c, hipEventRecord(g->ev_piece[q], c->stream));
-        }
-        return MSIM_OK;
+        return tables_to_host(Wb_hi);
     });
     if (rc) return rc;
     const auto tq1 = std::chrono::steady_clock::now();
@@ -2000,26 +2090,16 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
             if ((rc = grow(c, (void **)&M.words, &M.cap_words, words_bytes, &grew))) return rc;
             if ((rc = ensure_words(c, g, 0, p_b + Wb + 1))) return rc;
         }
-        if (n_nsn > n_hi) {                                // beyond 16 sigma: the rest of the candidates
-            MSIM_HIP(c, hipMemcpyAsync(g->h_npos + n_hi, M.nsn_pos + n_hi, (size_t)(n_nsn - n_hi) * 4, hipMemcpyDeviceToHost, g->copy_stream));
-            MSIM_HIP(c, hipMemcpyAsync(g->h_ntype + n_hi, M.nsn_type + n_hi, (size_t)(n_nsn - n_hi), hipMemcpyDeviceToHost, g->copy_stream));
-            MSIM_HIP(c, hipEventRecord(g->ev_cand, g->copy_stream));
-        }
+        if (n_nsn > n_hi && (rc = cands_to_host(c, g, cands_rest, c_pos, c_type, n_hi, n_nsn, 1))) return rc;   // beyond 16 sigma
         if (tables) {
             if (!early_ok) {                               // (not launched behind the mailbox: now, with the exact window)
                 accept_tables_launch(c->stream, py.d_raw, (unsigned long long)p_b, Wb, cc, lg, M.words);
                 MSIM_HIP(c, hipGetLastError());
-                cut[0] = 0; cut[1] = (size_t)(Wb + 1) / 8; cut[2] = (size_t)(Wb + 1) / 2; cut[3] = (size_t)Wb + 1;
-                for (int q = 0; q < 3; q++) {
-                    if (cut[q + 1] > cut[q])
-                        MSIM_HIP(c, hipMemcpyAsync(g->h_words + (cut[q] << lg), M.words + (cut[q] << lg),
-                                                   ((cut[q + 1] - cut[q]) << lg) * 4, hipMemcpyDeviceToHost, c->stream));
-                    MSIM_HIP(c, hipEventRecord(g->ev_piece[q], c->stream));
-                }
+                if ((rc = tables_to_host(Wb))) return rc;
             }
             MSIM_HIP(c, hipEventRecord(g->t1, c->stream));
             if (c->deferred_apply >= 0) MSIM_HIP(c, hipStreamWaitEvent(c->emit_stream, g->ev_cand, 0));   // (... and behind the candidates' copies)
-            if ((rc = flush_deferred_apply_behind(c, g->ev_piece[2]))) return rc;   // the previous contig's APPLY
+            if ((rc = flush_deferred_apply_behind(c, tabs.last()))) return rc;   // the previous contig's APPLY
             const auto w0 = std::chrono::steady_clock::now();
             ChainWalk cw;
             if ((rc = cw.init(c, r, ct.len, cc, Wb))) return rc;
@@ -2028,25 +2108,22 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
             auto tp = std::chrono::steady_clock::now();
             auto lap = [&](double &acc) { const auto n = std::chrono::steady_clock::now(); acc += std::chrono::duration<double, std::micro>(n - tp).count(); tp = n; };
             // candidates and table both arrive in pieces; the walk runs over what is there and waits for whichever ran out
-            int ci = 0, ti = 0;
             size_t avail_c = 0, avail_w = 0;
             while (!rc && cw.j < n_nsn) {
                 const bool need_c = cw.j >= avail_c, need_w = (cw.ws >> cw.lg_rows) >= avail_w;
                 if (!need_c && !need_w) break;             // (run stops for one of the two reasons only)
                 if (need_c) {
                     const size_t had = avail_c;
-                    if (ci < 3) { if ((rc = spin_event(c, g->ev_cpiece[ci], "spin_event(candidate piece, copy stream)"))) break; avail_c = std::min<size_t>(ccut[++ci], n_nsn); }
-                    else if (avail_c < n_nsn) { if ((rc = spin_event(c, g->ev_cand, "spin_event(candidates of the host chain, copy stream)"))) break; avail_c = n_nsn; }   // (beyond 16 sigma)
-                    else break;
+                    Handover &from = cands.drained() ? cands_rest : cands;   // (the rest: beyond 16 sigma)
+                    if (from.drained() || (rc = from.more(&avail_c))) break;
+                    avail_c = std::min<size_t>(avail_c, n_nsn);
                     if (!ChainWalk::types_ok(g->h_ntype + had, avail_c - had, has_tl)) {
                         rc = fail(c, MSIM_ERR_HIP, "boundary chain: candidate type outside the range's draw");
                         break;
                     }
                 }
                 if (need_w) {
-                    if (ti >= 3) break;                    // the window is used up: finish() reports it
-                    if ((rc = spin_event(c, g->ev_piece[ti], "spin_event(accept-table piece, plan stream)"))) break;
-                    avail_w = cut[++ti];
+                    if (tabs.drained() || (rc = tabs.more(&avail_w))) break;   // (drained: the window is used up, finish() reports it)
                 }
                 lap(t_wait);
                 if (has_tl) cw.run_tl(g->h_npos, g->h_ntype, avail_c, g->h_words, avail_w, g->h_nstop);
@@ -2081,20 +2158,11 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
                                      &consumed, &kept_host, &delta_host);
         }
         if (!rc && has_tl) rc = mixed_link_translocations(c, g, M, n_nsn, p_b, consumed, grew);
-        if (rc) { g->s[0].live = g->s[1].live = false; g->unverified = false; return rc; }
+        if (rc) { plan_failed(g); return rc; }
         MSIM_HIP(c, hipEventRecord(g->t0, c->stream));    // the host chain is not GPU time
-        MSIM_HIP(c, hipMemcpyAsync(M.nsn_stop, g->h_nstop, (size_t)n_nsn * 4, hipMemcpyHostToDevice, c->stream));
-        stop_scatter_launch(c->stream, M.nsn_rank, M.nsn_stop, n_nsn, M.cand_stop);
     }
-    if (has_tl) {
-        MSIM_HIP(c, hipMemsetAsync(M.cand_aux, 0, (size_t)k, c->stream));
-        if (n_nsn) {
-            MSIM_HIP(c, hipMemcpyAsync(M.nsn_extra, g->h_nextra, (size_t)n_nsn * 4, hipMemcpyHostToDevice, c->stream));
-            MSIM_HIP(c, hipMemcpyAsync(M.nsn_aux, g->h_naux, (size_t)n_nsn, hipMemcpyHostToDevice, c->stream));
-            link_scatter_launch(c->stream, M.nsn_rank, M.nsn_extra, M.nsn_aux, n_nsn, M.cand_extra, M.cand_aux);
-        }
-        MSIM_HIP(c, hipGetLastError());
-    }
+    if ((rc = verdicts_to_device(c, g, M, n_nsn, k, has_tl))) return rc;
+    if (has_tl) MSIM_HIP(c, hipGetLastError());
     const uint64_t p_s = p_b + consumed;                   // the SNP draws of __mutate_sequence start here
     return mixed_emit(c, g, ct, M, k, p_s, nullptr, 0, nullptr, false, grew, has_tl);
 }
@@ -2153,13 +2221,9 @@ int plan_contig_gpu_hostsample(Ctx *c, GpuPlan *g, Contig &ct, const msim_range 
     if (wd >= 4.0e9) return fail(c, MSIM_ERR_UNSUPPORTED, "sample window beyond 2^32 words");
     const uint32_t W = (uint32_t)wd;
     bool grew = false;
-    MixedSet &M = g->mixed[g->mixed_unit++ % N_SETS];
-    if ((rc = wait_if_pending(c, M.pending, M.emit_done))) return rc;
-    if (M.pending) {                                       // the pinned range table of this set may still be in flight
-        MSIM_HIP(c, wait_event(M.emit_done));
-        M.pending = false;
-    }
-    if (!M.emit_done) MSIM_HIP(c, hipEventCreateWithFlags(&M.emit_done, hipEventDisableTiming));
+    MixedSet *Mp;
+    if ((rc = mixed_acquire(c, g, true, Mp))) return rc;   // (the host writes the set's pinned range table below)
+    MixedSet &M = *Mp;
     // what the host hands back: one cut per drawing range (+ the end) and the pool-path positions
     const size_t n_back = (size_t)n_draw + 1 + K_pool;
     if ((rc = grow(c, (void **)&M.words, &M.cap_words, (size_t)W * 4, &grew))) return rc;
@@ -2212,47 +2276,31 @@ int plan_contig_gpu_hostsample(Ctx *c, GpuPlan *g, Contig &ct, const msim_range 
     if ((rc = ensure_words(c, g, 0, py.pos + W + 1))) return rc;
     hipLaunchKernelGGL(k_temper_window_ps, dim3((W + 255) / 256), dim3(256), 0, c->stream, py.d_raw, g->d_ps, W, M.words);
     MSIM_HIP(c, hipGetLastError());
-    // the window comes over in three pieces (1/8, 3/8, 1/2); the host starts on the first while the others are in flight
     if ((rc = ensure_signals(c, g))) return rc;
-    struct Feed { Ctx *c; GpuPlan *g; size_t cut[4]; int next; double wait_us; } fd{c, g, {0, (size_t)W / 8, (size_t)W / 2, (size_t)W}, 0, 0.0};
-    for (int q = 0; q < 3; q++) {
-        if (fd.cut[q + 1] > fd.cut[q])
-            MSIM_HIP(c, hipMemcpyAsync(g->h_words + fd.cut[q], M.words + fd.cut[q], (fd.cut[q + 1] - fd.cut[q]) * 4,
-                                       hipMemcpyDeviceToHost, c->stream));
-        MSIM_HIP(c, hipEventRecord(g->ev_piece[q], c->stream));
-    }
+    Handover win;                                          // the window comes over in pieces
+    if ((rc = win.send(c, c->stream, g->ev_piece, "spin_event(word-window piece, plan stream)", 0, W, {HandLane{g->h_words, M.words, 4, 0}})))
+        return rc;
     MSIM_HIP(c, hipEventRecord(g->t1, c->stream));
     MSIM_HIP(c, hipMemcpyAsync(M.walk_d, M.walk_h, (size_t)n_draw * sizeof(WalkRange), hipMemcpyHostToDevice, c->stream));
     const auto tp1 = std::chrono::steady_clock::now();
-    const auto tp2 = tp1;
     // ---- the host finds the stream cuts (and samples the pool-path ranges); everything per position stays here
     size_t consumed = 0, n_pool_pos = 0;
     uint32_t *h_cut = g->h_npos, *h_pool = g->h_npos + n_draw + 1;
-    WordFeed feed;
-    feed.user = &fd;
-    feed.more = [](void *u, size_t *avail) -> int {
-        Feed &f = *static_cast<Feed *>(u);
-        if (f.next >= 3) return MSIM_OK;
-        const auto w0 = std::chrono::steady_clock::now();
-        const int rc = spin_event(f.c, f.g->ev_piece[f.next], "spin_event(word-window piece, plan stream)");
-        f.wait_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count();
-        if (!rc) *avail = f.cut[++f.next];
-        return rc;
-    };
-    if ((rc = flush_deferred_apply_behind(c, g->ev_piece[2]))) return rc;   // the previous contig's APPLY
+    const WordFeed feed = win.feed();
+    if ((rc = flush_deferred_apply_behind(c, win.last()))) return rc;   // the previous contig's APPLY
     {
         const auto cw0 = std::chrono::steady_clock::now();
         rc = cut_ranges_host(c, ranges, n_ranges, d, g->h_words, W, h_cut, h_pool, &n_pool_pos, &consumed, &feed);
         const double all_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - cw0).count();
-        c->t.host_walk_wait_ms += fd.wait_us * 1e-3;
-        c->t.host_walk_run_ms += std::max(0.0, all_ms - fd.wait_us * 1e-3);
+        c->t.host_walk_wait_ms += win.wait_us * 1e-3;
+        c->t.host_walk_run_ms += std::max(0.0, all_ms - win.wait_us * 1e-3);
         c->t.host_cut_words += consumed;
     }
     if (!rc) {
         MSIM_HIP(c, wait_event(g->t1));           // all pieces landed (usually long ago): the pinned window is free again
         rc = span_close(c, g);
     }
-    if (rc) { g->s[0].live = g->s[1].live = false; g->unverified = false; M.wbits_dirty = true; return rc; }
+    if (rc) { plan_failed(g); M.wbits_dirty = true; return rc; }
     const auto tp3 = std::chrono::steady_clock::now();
     MSIM_HIP(c, hipEventRecord(g->t0, c->stream));        // the host chain is not GPU time
     MSIM_HIP(c, hipMemcpyAsync(M.cand_pos, g->h_npos, ((size_t)n_draw + 1 + n_pool_pos) * 4, hipMemcpyHostToDevice, c->stream));
@@ -2293,7 +2341,7 @@ int plan_contig_gpu_hostsample(Ctx *c, GpuPlan *g, Contig &ct, const msim_range 
         const auto tp4 = std::chrono::steady_clock::now();
         auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
         fprintf(stderr, "hostcut: n_draw %u K %llu W %u | outside %.0f setup %.0f wait %.0f cut %.0f post %.0f us\n", n_draw, (unsigned long long)K, W,
-                us(last_exit, tp0), us(tp0, tp1), us(tp1, tp2), us(tp2, tp3), us(tp3, tp4));
+                us(last_exit, tp0), us(tp0, tp1), win.wait_us, us(tp1, tp3) - win.wait_us, us(tp3, tp4));
         last_exit = tp4;
     }
     return MSIM_OK;
@@ -2339,14 +2387,10 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
     std::vector<double> q_nsn(n_sets, 0.0), acc_min(n_sets, 1.0), q_tl(n_sets, 0.0);
     for (uint32_t s = 0; s < n_sets; s++) {
         const msim_range &r = ranges[ms.rep[s]];
-        for (int j = 0; j < r.n_types; j++) {
-            if (!type_drawable(r, j) || r.types[j] == MSIM_SN) continue;
-            const double q = type_probability(r, j);
-            q_nsn[s] += q;
-            if (r.types[j] == MSIM_TL || r.types[j] == MSIM_TLI) q_tl[s] += q;
-        }
+        for (int j = 0; j < r.n_types; j++)
+            if (type_drawable(r, j) && (r.types[j] == MSIM_TL || r.types[j] == MSIM_TLI)) q_tl[s] += type_probability(r, j);
         acc_min[s] = randint_acceptance_min(r);                       // (multimix_prepare let only widths 1 .. 2^24 - 1 through)
-        q_nsn[s] = std::min(1.0, q_nsn[s]);
+        q_nsn[s] = chain_share(r);
     }
     {
         uint32_t di = 0;
@@ -2368,15 +2412,11 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
     const double wd = e_words + 16.0 * std::sqrt(var) + 65536.0;
     if (wd >= 1.0e9) return fail(c, MSIM_ERR_UNSUPPORTED, "host-chain window beyond 2^30 words");
     const uint32_t W = (uint32_t)wd;
-    const uint32_t n_hi = ms.sn_chained ? K : (uint32_t)std::min<double>(K, e_ch + 16.0 * std::sqrt(var_ch) + 64.0);
+    const uint32_t n_hi = std::min(g->cand_cap, ms.sn_chained ? K : (uint32_t)std::min<double>(K, e_ch + 16.0 * std::sqrt(var_ch) + 64.0));
     bool grew = false;
-    MixedSet &M = g->mixed[g->mixed_unit++ % N_SETS];
-    if ((rc = wait_if_pending(c, M.pending, M.emit_done))) return rc;
-    if (M.pending) {                                       // the pinned tables of this set may still be in flight
-        MSIM_HIP(c, wait_event(M.emit_done));
-        M.pending = false;
-    }
-    if (!M.emit_done) MSIM_HIP(c, hipEventCreateWithFlags(&M.emit_done, hipEventDisableTiming));
+    MixedSet *Mp;
+    if ((rc = mixed_acquire(c, g, true, Mp))) return rc;   // (the host writes the set's pinned tables below)
+    MixedSet &M = *Mp;
     const uint32_t nbk = (K + CB_BLOCK - 1) / CB_BLOCK;
     const size_t n_slots = ((size_t)W + 1) << lg;
     if ((rc = grow(c, (void **)&M.cand_pos, &M.cap_pos, (size_t)K * 4 + 64, &grew))) return rc;
@@ -2432,13 +2472,7 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
             base += (uint32_t)r.k;
             di++;
         }
-        for (uint32_t s = 0; s < n_sets; s++) {
-            const msim_range &r = ranges[ms.rep[s]];
-            TypeTable tt{};
-            tt.n = (uint32_t)r.n_types;
-            for (int j = 0; j < r.n_types; j++) { tt.thr[j] = r.cdf_thr[j]; tt.type[j] = (uint8_t)r.types[j]; }
-            sets_h[s] = tt;
-        }
+        for (uint32_t s = 0; s < n_sets; s++) sets_h[s] = type_table_of(ranges[ms.rep[s]]);
     }
     // ---- 1. device: word window, accept tables, candidate types, the chain's candidates
     const uint64_t np_base = np.pos;                       // exact: the NumPy stream never rejects
@@ -2449,58 +2483,33 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
     types_multi_launch(c->stream, np.d_raw, (unsigned long long)np_base, K, rt_d, n_draw, sets_d, M.cand_type);
     nsn_compact_launch(c->stream, nullptr, M.cand_type, K, M.cnt, nullptr, M.nsn_type, M.nsn_rank, g->d_ps, ms.sn_chained);
     MSIM_HIP(c, hipGetLastError());
-    {   // the chain's candidates go over beside the plan stream, a 16-sigma bound of their number first
-        hipEvent_t se = next_chain_event(g);
-        MSIM_HIP(c, hipEventRecord(se, c->stream));
-        MSIM_HIP(c, hipStreamWaitEvent(g->copy_stream, se, 0));
-        MSIM_HIP(c, hipMemcpyAsync(g->h_nrank, M.nsn_rank, (size_t)n_hi * 4, hipMemcpyDeviceToHost, g->copy_stream));
-        MSIM_HIP(c, hipMemcpyAsync(g->h_ntype, M.nsn_type, (size_t)n_hi, hipMemcpyDeviceToHost, g->copy_stream));
-        MSIM_HIP(c, hipEventRecord(g->ev_cand, g->copy_stream));
-    }
+    const HandLane c_rank{g->h_nrank, M.nsn_rank, 4, 0}, c_type{g->h_ntype, M.nsn_type, 1, 0};
+    Handover cands, win;
+    if ((rc = cands_to_host(c, g, cands, c_rank, c_type, 0, n_hi, 1))) return rc;   // a 16-sigma bound of their number, in one copy
     hipLaunchKernelGGL(k_temper_window_ps, dim3((W + 255) / 256), dim3(256), 0, c->stream, py.d_raw, g->d_ps, W, M.words);
     accept_tables_ps_launch(c->stream, py.d_raw, g->d_ps, W, ms.gcc, lg, M.tables);
     MSIM_HIP(c, hipGetLastError());
-    // window and tables come over in three pieces (1/8, 3/8, 1/2); the host starts on the first while the others are in flight.
-    // Their copies go out behind the mailbox kernel, before the host polls: nothing of them depends on what the poll tells.
-    struct Feed { Ctx *c; GpuPlan *g; size_t cut[4]; int next; double wait_us; } fd{c, g, {0, (size_t)W / 8, (size_t)W / 2, (size_t)W}, 0, 0.0};
+    // Window and tables come over in the same pieces, the tables with their end-of-window sentinel.  Their copies go out
+    // behind the mailbox kernel, before the host polls: nothing of them depends on what the poll tells.
     PlanState h;
     rc = mixed_poll(c, g, h, [&]() -> int {                // exact stream position + the chain's length
-        for (int q = 0; q < 3; q++) {
-            const size_t a = fd.cut[q], b = fd.cut[q + 1], tb = q == 2 ? (size_t)W + 1 : b;   // (+ the end-of-window sentinel)
-            if (b > a) MSIM_HIP(c, hipMemcpyAsync(g->h_win + a, M.words + a, (b - a) * 4, hipMemcpyDeviceToHost, c->stream));
-            if (tb > a) MSIM_HIP(c, hipMemcpyAsync(g->h_words + (a << lg), M.tables + (a << lg), ((tb - a) << lg) * 4, hipMemcpyDeviceToHost, c->stream));
-            MSIM_HIP(c, hipEventRecord(g->ev_piece[q], c->stream));
-        }
-        return MSIM_OK;
+        return win.send(c, c->stream, g->ev_piece, "spin_event(word-window piece, plan stream)", 0, W,
+                        {HandLane{g->h_win, M.words, 4, 0}, HandLane{g->h_words, M.tables, (size_t)4 << lg, 1}});
     });
     if (rc) return rc;
     const uint32_t n_ch = h.n_nsn;
     const uint64_t p0 = h.pos;
     np.pos = np_base + 2ull * K;
     c->t.np_words += 2ull * K;
-    if (n_ch > n_hi) {                                     // beyond 16 sigma: the rest of the chain's candidates
-        MSIM_HIP(c, hipMemcpyAsync(g->h_nrank + n_hi, M.nsn_rank + n_hi, (size_t)(n_ch - n_hi) * 4, hipMemcpyDeviceToHost, g->copy_stream));
-        MSIM_HIP(c, hipMemcpyAsync(g->h_ntype + n_hi, M.nsn_type + n_hi, (size_t)(n_ch - n_hi), hipMemcpyDeviceToHost, g->copy_stream));
-        MSIM_HIP(c, hipEventRecord(g->ev_cand, g->copy_stream));
-    }
+    if (n_ch > n_hi && (rc = cands_to_host(c, g, cands, c_rank, c_type, n_hi, n_ch, 1))) return rc;   // beyond 16 sigma
     MSIM_HIP(c, hipEventRecord(g->t1, c->stream));
     if (c->deferred_apply >= 0) MSIM_HIP(c, hipStreamWaitEvent(c->emit_stream, g->ev_cand, 0));   // (behind the candidates' copies too)
-    if ((rc = flush_deferred_apply_behind(c, g->ev_piece[2]))) return rc;   // the previous contig's APPLY
+    if ((rc = flush_deferred_apply_behind(c, win.last()))) return rc;   // the previous contig's APPLY
     const auto tp1 = std::chrono::steady_clock::now();
     // ---- 2. the chain, on the host
-    size_t consumed = 0;
-    WordFeed feed;
-    feed.user = &fd;
-    feed.more = [](void *u, size_t *avail) -> int {
-        Feed &f = *static_cast<Feed *>(u);
-        if (f.next >= 3) return MSIM_OK;
-        const auto w0 = std::chrono::steady_clock::now();
-        const int rc = spin_event(f.c, f.g->ev_piece[f.next], "spin_event(word-window piece, plan stream)");
-        f.wait_us += std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - w0).count();
-        if (!rc) *avail = f.cut[++f.next];
-        return rc;
-    };
-    rc = spin_event(c, g->ev_cand, "spin_event(candidates of the host chain, copy stream)");
+    size_t consumed = 0, n_there = 0;
+    const WordFeed feed = win.feed();
+    rc = cands.more(&n_there);                             // all of the chain's candidates (one copy, or the rest of them)
     const auto mw0 = std::chrono::steady_clock::now();
     c->t.host_walk_wait_ms += std::chrono::duration<double, std::milli>(mw0 - tp1).count();
     if (!rc) rc = multimix_walk_host(c, ct.len, ranges, n_ranges, d, ms, g->h_win, g->h_words, W, g->h_nrank, g->h_ntype, n_ch,
@@ -2508,30 +2517,20 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
                                      ms.has_tl ? g->h_naux : nullptr);
     {
         const double all_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - mw0).count();
-        c->t.host_walk_wait_ms += fd.wait_us * 1e-3;
-        c->t.host_walk_run_ms += std::max(0.0, all_ms - fd.wait_us * 1e-3);
+        c->t.host_walk_wait_ms += win.wait_us * 1e-3;
+        c->t.host_walk_run_ms += std::max(0.0, all_ms - win.wait_us * 1e-3);
         c->t.host_walk_candidates += K;
     }
     if (!rc) {
         MSIM_HIP(c, wait_event(g->t1));           // all pieces landed (usually long ago): the pinned blocks are free again
         rc = span_close(c, g);
     }
-    if (rc) { g->s[0].live = g->s[1].live = false; g->unverified = false; return rc; }
+    if (rc) { plan_failed(g); return rc; }
     const auto tp2 = std::chrono::steady_clock::now();
     MSIM_HIP(c, hipEventRecord(g->t0, c->stream));        // the host chain is not GPU time
     // ---- 3. back on the device
     MSIM_HIP(c, hipMemcpyAsync(M.cand_pos, g->h_npos, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
-    if (n_ch) MSIM_HIP(c, hipMemcpyAsync(M.nsn_stop, g->h_nstop, (size_t)n_ch * 4, hipMemcpyHostToDevice, c->stream));
-    MSIM_HIP(c, hipMemcpyAsync(visit_d, visit_h, (size_t)n_draw * 4, hipMemcpyHostToDevice, c->stream));
-    if (n_ch) stop_scatter_launch(c->stream, M.nsn_rank, M.nsn_stop, n_ch, M.cand_stop);
-    if (ms.has_tl) {                                       // what __link_tls decided: linked spans, flags, tombstones
-        MSIM_HIP(c, hipMemsetAsync(M.cand_aux, 0, (size_t)K, c->stream));
-        if (n_ch) {
-            MSIM_HIP(c, hipMemcpyAsync(M.nsn_extra, g->h_nextra, (size_t)n_ch * 4, hipMemcpyHostToDevice, c->stream));
-            MSIM_HIP(c, hipMemcpyAsync(M.nsn_aux, g->h_naux, (size_t)n_ch, hipMemcpyHostToDevice, c->stream));
-            link_scatter_launch(c->stream, M.nsn_rank, M.nsn_extra, M.nsn_aux, n_ch, M.cand_extra, M.cand_aux);
-        }
-    }
+    if ((rc = verdicts_to_device(c, g, M, n_ch, K, ms.has_tl, visit_d, visit_h, n_draw))) return rc;
     MSIM_HIP(c, hipGetLastError());
     rc = mixed_emit(c, g, ct, M, K, p0 + consumed, rt_d, n_draw, visit_d, ms.sn_chained, grew, ms.has_tl);
     if (prof) {

@@ -87,7 +87,8 @@ td = Path(tempfile.mkdtemp())
 res = run_product_case(meta, td, extra_argv=["--bench-json", str(td / "stats.json")])
 st = json.loads((td / "stats.json").read_text())
 print(json.dumps(dict(exc=repr(res["exception"]), code=res["exit_code"], fasta=sha256(res["fasta"]), vcf=sha256(res["vcf"]),
-                      stderr=res["stderr"], replanned=mutator.REPLANNED_CONTIGS, rebases=st.get("stream_rebases"))))
+                      stderr=res["stderr"], replanned=mutator.REPLANNED_CONTIGS, rebases=st.get("stream_rebases"),
+                      engines={{k: v for k, v in st.items() if k.startswith("contigs_") and v}})))
 """
 
 
@@ -107,3 +108,30 @@ def test_cli_goldens_with_a_small_span(name, chunks, min_rebases):
     assert got["fasta"] == meta["fasta_sha256"] and got["vcf"] == meta["vcf_sha256"]
     assert got["stderr"] == meta["stderr"]
     assert got["rebases"] is not None and got["rebases"] >= min_rebases, got
+
+
+@pytest.mark.parametrize("cap", [1, 257])
+@pytest.mark.parametrize("name,engines", [("svmix_1mb", {"contigs_svmix": 1}),
+                                          ("rmt_svstd_blocks_3mb", {"contigs_hostchain": 1, "contigs_batch": 2}),
+                                          ("readme_mix_tl", {"contigs_svmix": 1})])
+def test_cli_goldens_with_late_chain_candidates(name, engines, cap):
+    """The SV-mix and host-chain engines copy a 16-sigma BOUND of the chain's candidates to the host before their number is
+    known and "the rest, if ever" after the poll -- a path no input reaches.  ``MSIM_DBG_CAND_CAP=N`` (read when a context is
+    created) lowers the bound to N, so every contig whose chain is longer than N takes it: with N = 1 the rest is everything
+    but one candidate and the SV-mix engine also throws away the accept tables it launched early over the bound's window
+    and builds them again over the exact one; with N = 257 the bound's three pieces are non-empty and the rest follows them.
+    Both are below every contig's chain length here -- the goldens' non-SNP VCF records per contig (no chain candidate makes
+    more than one), counted with the CPU oracle: svmix_1mb 2295; rmt_svstd_blocks_3mb v1 4835 (its two small contigs go to the batch planner); readme_mix_tl
+    (one range drawing TL: the SV-mix engine's translocation walk and __link_tls) 4684 -- so the path is certain without a
+    counter.  The reference's own bytes, stderr, nothing re-planned; the engine counters say who planned the contigs."""
+    meta = case_meta(name)
+    env = dict(os.environ, MSIM_DBG_CAND_CAP=str(cap))
+    out = subprocess.run([sys.executable, "-c", _CLI_SCRIPT.format(paths=sys.path[:8], name=name)], env=env, capture_output=True,
+                         text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    got = json.loads(out.stdout.strip().splitlines()[-1])
+    assert got["exc"] == "None" and got["code"] is None
+    assert got["engines"] == engines, got["engines"]
+    assert got["replanned"] == 0
+    assert got["fasta"] == meta["fasta_sha256"] and got["vcf"] == meta["vcf_sha256"]
+    assert got["stderr"] == meta["stderr"]
