@@ -581,6 +581,28 @@ int msim_spectrum_timing(msim_ctx *ctx, double *census_ms, double *plan_ms);
 int msim_dbg_context_counts(const uint8_t *bases, uint64_t L, uint64_t counts[64], uint64_t *n_valid);
 int msim_dbg_spectrum_plan(const uint8_t *bases, uint64_t L, const uint64_t thr[192], uint64_t key, uint32_t seq,
                            msim_record *recs, uint64_t cap, uint64_t *n_recs);
+/* The sampler's inverse, a PROFILE: a planned contig's record table counted against its resident reference bases.
+ *   msim_sbs_counts      an SN record at p has a channel iff p is an eligible site (above); the channel is the pyrimidine-folded
+ *                        N[X>Y]N of (ctx, aux): substitution-major (C>A, C>G, C>T, T>A, T>C, T>G), then the 5' base, then the 3'
+ *                        base; a purine centre is read off the other strand.  The context is always the REFERENCE's: neighbouring
+ *                        SNPs do not see each other, and an applied contig counts as before.  tallies[0]: SN records without a
+ *                        channel (the contig's first or last base, a neighbourhood holding N, IUPAC, U or -); tallies[t],
+ *                        t = MSIM_SN .. MSIM_TLI: the records of type t -- so sum(channels) + tallies[0] == tallies[MSIM_SN].
+ *                        Any planned contig that is not released, whichever call left its table (the planners of every engine,
+ *                        msim_plan_contig_spectrum, msim_vcf_plan_contig, msim_dbg_set_records); with a haplotype selected, the
+ *                        table msim_fetch_records returns.  Synchronises like msim_fetch_records; changes nothing on the contig,
+ *                        no generator moves.  An empty table: zeros, nothing launched.  MSIM_ERR_HIP on a host-only context.
+ *   msim_sbs_timing      the profile kernel's time on the device (HIP events) since the context was made or msim_reset_stats.
+ * MSIM_SBS_PASS: the records one workgroup of the kernel takes per pass -- where its edge cases lie.
+ * msim_dbg_sbs_counts: the same result by a sequential host loop over the caller's bases and records -- no context, no GPU
+ * (MSIM_ERR_ARG for a record of unknown type; error text: msim_last_error with a NULL context).                               */
+#define MSIM_SBS_CHANNELS 96
+#define MSIM_SBS_TALLIES   8
+#define MSIM_SBS_PASS   1024
+int msim_sbs_counts(msim_ctx *ctx, int contig, uint64_t channels[96], uint64_t tallies[8]);
+int msim_sbs_timing(msim_ctx *ctx, double *kernel_ms);
+int msim_dbg_sbs_counts(const uint8_t *bases, uint64_t L, const msim_record *recs, uint64_t n_records,
+                        uint64_t channels[96], uint64_t tallies[8]);
 
 /* ---- test support: the SNP ti/tv transducer on the caller's words -------------------------------------------------- */
 /* Runs the three passes that turn CPython-stream words into SNP outcomes -- the map pass over whole blocks of

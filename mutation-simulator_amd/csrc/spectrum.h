@@ -32,6 +32,17 @@ MSIM_FHD inline uint32_t outcome(const uint64_t *thr3, uint64_t r) {
     return (uint32_t)(thr3[0] <= r) + (uint32_t)(thr3[1] <= r) + (uint32_t)(thr3[2] <= r);
 }
 
+// The SBS-96 channel of an SN record in a valid context (msim_sbs_counts): substitution-major (C>A, C>G, C>T, T>A, T>C, T>G), then
+// the 5' base, then the 3' base, pyrimidine-centred -- a purine centre is read off the other strand (3 - code complements).
+// l, m, r: the codes of b[p-1], b[p], b[p+1]; aux 0..2: the rewrite's alternative (A>G,T,C  C>T,A,G  G>A,C,T  T>C,G,A).
+// The substitution of (m, aux) sits in nibble 4 m + aux of the constant.
+MSIM_FHD inline uint32_t sbs_channel(uint32_t l, uint32_t m, uint32_t r, uint32_t aux) {
+    const uint32_t sub = (uint32_t)(0x0354001201020534ull >> (4 * (4 * m + aux))) & 7u;
+    const bool purine = (m & 1u) == 0;
+    return 16 * sub + 4 * (purine ? 3 - r : l) + (purine ? 3 - l : r);
+}
+constexpr uint32_t SBS_BINS = 96 + 8;                      // the channels, then msim_sbs_counts' tallies
+
 MSIM_FHD inline uint64_t site_bits(const fastrng::U4 &v, uint64_t p) { return (p & 1) ? fastrng::hi64(v) : fastrng::lo64(v); }
 
 }  // namespace spectrum

@@ -12,6 +12,9 @@
 //            k_scan_u32 over the tile counts (scan_kernels.h)
 //            k_spectrum_emit: reads the outcome words only -- no base, no draw a second time -- and stores the records at
 //            tile offset + prefix of the lanes in front (wave scan by shuffles + the waves' sums), 16 bytes a store
+//   profile  k_sbs_count (msim_sbs_counts), the sampler's inverse: one 16-byte record a lane and step, the three bases around an
+//            SN record's position gathered from the resident contig, 104 16-bit counters per LANE in LDS (96 channels + 8
+//            tallies) as in the census, summed per workgroup at the end
 // The host waits once between scan and emit: the record table is allocated at its exact size.
 #include <algorithm>
 #include <cstring>
@@ -29,13 +32,15 @@ using fastrng::U4;
 
 struct SpectrumState {
     unsigned long long *d_counts = nullptr;   // 64 census bins
+    unsigned long long *d_sbs = nullptr;      // SBS_SLOTS x 104 profile bins (spectrum::SBS_BINS)
+    unsigned long long *h_sbs = nullptr;      // pinned copy of them
     uint64_t *d_thr = nullptr;                // 192 thresholds
     uint32_t *d_words = nullptr;              // one outcome word per lane of every tile
     uint32_t *d_tile = nullptr;               // hits per tile, then their exclusive scan; [n_tiles]: the total
     size_t cap_words = 0, cap_tile = 0;
     unsigned long long *h_pin = nullptr;      // pinned: [0..63] census bins / [0..191] thresholds on their way up, [192] the total
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    double census_ms = 0, plan_ms = 0;
+    double census_ms = 0, plan_ms = 0, sbs_ms = 0;
 };
 
 namespace {
@@ -194,6 +199,84 @@ __global__ __launch_bounds__(LANES) void k_spectrum_emit(const uint32_t *__restr
     }
 }
 
+// ---- the profile: SN records counted into their SBS-96 channels (msim_sbs_counts) ------------------------------------------
+constexpr int SBS_AHEAD = 4;                                // records a lane and pass: their loads and gathers are in flight together
+constexpr uint32_t SBS_PASS = LANES * SBS_AHEAD;            // records of a workgroup's pass, contiguous: 1 KB a wave and load
+static_assert(SBS_PASS == MSIM_SBS_PASS, "msim.h and spectrum.hip must agree on the pass");
+constexpr unsigned SBS_MAX_BLOCKS = 512;                    // more passes than that stride (k_sbs_count counts on it); two workgroups a CU:
+                                                            // every workgroup pays for zeroing and summing 52 KB of counters (NOTES 21)
+constexpr int SBS_BINS = (int)spectrum::SBS_BINS, SBS_WORDS = SBS_BINS / 2;
+constexpr int SBS_SLOTS = 16;                               // copies of the result the workgroups' final adds spread over (k_sbs_count)
+static_assert(sizeof(msim_record) == sizeof(uint4), "a record is one 16-byte load");
+
+// The bin of one record ({pos, stop, extra, type | aux << 8 | rsv << 16}): an SN record's channel, 96 (tallies[0]) for an SN
+// record without one, 96 + type for every other type; *one = 0 for what is no record (type 0: the padding of the last pass).
+// tallies[1] has no bin: the host sums it.  b[p - 1] and b[p + 1] are read only where they lie inside [0, L).
+__device__ __forceinline__ uint32_t sbs_bin(const uint8_t *__restrict__ b, uint64_t L, const uint4 &rec, uint32_t *one) {
+    const uint32_t p = rec.x, type = rec.w & 0xffu, aux = (rec.w >> 8) & 0xffu;
+    *one = (type >= (uint32_t)MSIM_SN && type <= (uint32_t)MSIM_TLI) ? 1u : 0u;
+    if (type != (uint32_t)MSIM_SN) return 96u + (*one ? type : 0u);
+    uint32_t bin = 96u;
+    if (p >= 1 && (uint64_t)p + 1 < L && aux < 3) {
+        const uint32_t l = spectrum::base_code(b[p - 1]), m = spectrum::base_code(b[p]), r = spectrum::base_code(b[p + 1]);
+        if (((l | m | r) & spectrum::CODE_INVALID) == 0) bin = spectrum::sbs_channel(l, m, r, aux);
+    }
+    return bin;
+}
+
+// Lane-private counters as in k_ctx_census: 104 16-bit bins a lane, two a word, the lane's column of `cnt` (52 KB a workgroup,
+// three workgroups a CU) -- an add is one conflict-free ds_add wherever the records fall, and a real spectrum puts most of
+// them into a handful of channels.  A table has fewer than 2^31 records, so fewer than 2^21 passes; the grid stops at
+// SBS_MAX_BLOCKS only beyond that many passes: a workgroup takes at most 4096 of them, SBS_AHEAD records a lane each -- 16 384
+// a counter at most, whatever the table holds.  The workgroups' final adds go to SBS_SLOTS copies of the result (the host sums
+// them): on one copy, 96 busy channels cost 96 adds to the same few lines per workgroup and a one-channel table ran faster.
+__global__ __launch_bounds__(LANES) void k_sbs_count(const uint8_t *__restrict__ b, uint64_t L, const uint4 *__restrict__ recs,
+                                                     uint64_t n_rec, uint64_t n_pass, unsigned long long *__restrict__ out) {
+    __shared__ uint32_t cnt[SBS_WORDS][LANES];
+    __shared__ uint32_t part[2][SBS_BINS];
+#pragma unroll
+    for (int w = 0; w < SBS_WORDS; w++) cnt[w][threadIdx.x] = 0;   // (a lane's own column: no barrier before its adds)
+    for (uint64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
+        uint4 rec[SBS_AHEAD];
+#pragma unroll
+        for (int k = 0; k < SBS_AHEAD; k++) {
+            const uint64_t i = pass * SBS_PASS + (uint64_t)k * LANES + threadIdx.x;
+            rec[k] = i < n_rec ? recs[i] : make_uint4(0u, 0u, 0u, 0u);
+        }
+        uint32_t bin[SBS_AHEAD], one[SBS_AHEAD];
+#pragma unroll
+        for (int k = 0; k < SBS_AHEAD; k++) bin[k] = sbs_bin(b, L, rec[k], &one[k]);
+#pragma unroll
+        for (int k = 0; k < SBS_AHEAD; k++) atomicAdd(&cnt[bin[k] >> 1][threadIdx.x], one[k] << (16 * (bin[k] & 1)));
+    }
+    __syncthreads();
+    // bin t (or t - 104) over one half of the columns: the rotation keeps a wave's 64 reads on 64 banks
+    if (threadIdx.x < 2 * SBS_BINS) {
+        const int half = threadIdx.x >= SBS_BINS ? 1 : 0, bn = (int)threadIdx.x - half * SBS_BINS;
+        uint32_t s = 0;
+#pragma unroll 8
+        for (int i = 0; i < LANES / 2; i++)
+            s += (cnt[bn >> 1][half * (LANES / 2) + ((i + (int)threadIdx.x) & (LANES / 2 - 1))] >> (16 * (bn & 1))) & 0xffffu;
+        part[half][bn] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < SBS_BINS) {
+        const uint32_t total = part[0][threadIdx.x] + part[1][threadIdx.x];
+        if (total) atomicAdd(&out[(blockIdx.x & (SBS_SLOTS - 1)) * SBS_BINS + threadIdx.x], (unsigned long long)total);
+    }
+}
+
+// bins 0..95 the channels, 96.. the tallies; tallies[1] = every SN record = the channels' sum + tallies[0]
+void sbs_finish(const unsigned long long *slots, uint64_t channels[96], uint64_t tallies[8]) {
+    unsigned long long bins[SBS_BINS] = {};
+    for (int s = 0; s < SBS_SLOTS; s++)
+        for (int i = 0; i < SBS_BINS; i++) bins[i] += slots[s * SBS_BINS + i];
+    uint64_t sn = bins[96];
+    for (int i = 0; i < 96; i++) { channels[i] = bins[i]; sn += bins[i]; }
+    for (int t = 0; t < 8; t++) tallies[t] = bins[96 + t];
+    tallies[1] = sn;
+}
+
 inline uint64_t tiles_of(uint64_t L) { return (L + spectrum::TILE - 1) / spectrum::TILE; }
 
 int state_of(Ctx *c, SpectrumState **out) {
@@ -201,6 +284,8 @@ int state_of(Ctx *c, SpectrumState **out) {
         SpectrumState *S = new SpectrumState;
         c->spectrum = S;
         MSIM_HIP(c, hipMalloc((void **)&S->d_counts, 64 * sizeof(unsigned long long)));
+        MSIM_HIP(c, hipMalloc((void **)&S->d_sbs, SBS_SLOTS * SBS_BINS * sizeof(unsigned long long)));
+        MSIM_HIP(c, hipHostMalloc((void **)&S->h_sbs, SBS_SLOTS * SBS_BINS * sizeof(unsigned long long), hipHostMallocDefault));
         MSIM_HIP(c, hipMalloc((void **)&S->d_thr, 192 * sizeof(uint64_t)));
         MSIM_HIP(c, hipHostMalloc((void **)&S->h_pin, 193 * sizeof(unsigned long long), hipHostMallocDefault));
         MSIM_HIP(c, hipEventCreate(&S->e0));
@@ -235,6 +320,28 @@ int census_device(Ctx *c, SpectrumState *S, const Contig &g, uint64_t counts[64]
     MSIM_HIP(c, hipEventElapsedTime(&ms, S->e0, S->e1));
     S->census_ms += ms;
     for (int i = 0; i < 64; i++) counts[i] = S->h_pin[i];
+    return MSIM_OK;
+}
+
+// the contig's ACTIVE table (the caller drained the context: the table is complete, its size collected, nothing writes it)
+int sbs_device(Ctx *c, SpectrumState *S, const Contig &g, uint64_t channels[96], uint64_t tallies[8]) {
+    memset(channels, 0, 96 * sizeof(uint64_t));
+    memset(tallies, 0, 8 * sizeof(uint64_t));
+    if (!g.n_rec) return MSIM_OK;
+    const uint64_t n_pass = (g.n_rec + SBS_PASS - 1) / SBS_PASS;
+    MSIM_HIP(c, hipMemsetAsync(S->d_sbs, 0, SBS_SLOTS * SBS_BINS * sizeof(unsigned long long), c->stream));
+    MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+    const unsigned blocks = (unsigned)std::min<uint64_t>(n_pass, SBS_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_sbs_count, dim3(blocks), dim3(LANES), 0, c->stream, g.d_in + PAD, g.len,
+                       reinterpret_cast<const uint4 *>(g.d_recs), g.n_rec, n_pass, S->d_sbs);
+    MSIM_HIP(c, hipGetLastError());
+    MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+    MSIM_HIP(c, hipMemcpyAsync(S->h_sbs, S->d_sbs, SBS_SLOTS * SBS_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    MSIM_HIP(c, wait_stream(c->stream));
+    float ms = 0;
+    MSIM_HIP(c, hipEventElapsedTime(&ms, S->e0, S->e1));
+    S->sbs_ms += ms;
+    sbs_finish(S->h_sbs, channels, tallies);
     return MSIM_OK;
 }
 
@@ -300,9 +407,10 @@ int flushed(Ctx *c) {
 void spectrum_state_destroy(Ctx *c) {
     SpectrumState *S = c->spectrum;
     if (!S) return;
-    void *bufs[] = {S->d_counts, S->d_thr, S->d_words, S->d_tile};
+    void *bufs[] = {S->d_counts, S->d_sbs, S->d_thr, S->d_words, S->d_tile};
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (S->h_pin) (void)hipHostFree(S->h_pin);
+    if (S->h_sbs) (void)hipHostFree(S->h_sbs);
     if (S->e0) (void)hipEventDestroy(S->e0);
     if (S->e1) (void)hipEventDestroy(S->e1);
     delete S;
@@ -310,7 +418,7 @@ void spectrum_state_destroy(Ctx *c) {
 }
 
 void spectrum_reset_timing(Ctx *c) {
-    if (c->spectrum) c->spectrum->census_ms = c->spectrum->plan_ms = 0;
+    if (c->spectrum) c->spectrum->census_ms = c->spectrum->plan_ms = c->spectrum->sbs_ms = 0;
 }
 
 }  // namespace msim
@@ -360,6 +468,59 @@ int msim_spectrum_timing(msim_ctx *p, double *census_ms, double *plan_ms) {
     return MSIM_OK;
 }
 
+// The contig's record table counted against its resident reference bases.  Planned is enough, applied does not matter: d_in
+// stays the reference.  With a haplotype selected the active table is that haplotype's (what msim_fetch_records returns).
+int msim_sbs_counts(msim_ctx *p, int contig, uint64_t channels[96], uint64_t tallies[8]) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c || !channels || !tallies) return MSIM_ERR_ARG;
+    int rc = flushed(c);
+    if (rc) return rc;
+    if (c->host_only) return fail(c, MSIM_ERR_HIP, "host-only context: this call needs the GPU");
+    if (contig < 0 || (size_t)contig >= c->contigs.size()) return fail(c, MSIM_ERR_ARG, "no such contig");
+    const Contig &g = c->contigs[(size_t)contig];
+    if (!g.planned) return fail(c, MSIM_ERR_ARG, "contig has not been planned");
+    if ((rc = ctx_drain(c))) return rc;                    // the table's last bytes come from the emit stream
+    SpectrumState *S;
+    if ((rc = state_of(c, &S))) return rc;
+    TraceRange tr("msim SBS-96 profile");
+    return sbs_device(c, S, g, channels, tallies);
+}
+
+int msim_sbs_timing(msim_ctx *p, double *kernel_ms) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c) return MSIM_ERR_ARG;
+    if (kernel_ms) *kernel_ms = c->spectrum ? c->spectrum->sbs_ms : 0.0;
+    return MSIM_OK;
+}
+
+// measurement support (tools/sbs_profile_bench.py; exported, not part of msim.h): a device-to-device copy of the contig's active
+// record table into the context's scratch, timed by HIP events -- the streaming floor msim_sbs_counts' kernel is held against
+int msim_dbg_sbs_copy_floor(msim_ctx *p, int contig, double *ms) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c || !ms) return MSIM_ERR_ARG;
+    int rc = flushed(c);
+    if (rc) return rc;
+    if (c->host_only) return fail(c, MSIM_ERR_HIP, "host-only context: this call needs the GPU");
+    if (contig < 0 || (size_t)contig >= c->contigs.size()) return fail(c, MSIM_ERR_ARG, "no such contig");
+    const Contig &g = c->contigs[(size_t)contig];
+    if (!g.planned) return fail(c, MSIM_ERR_ARG, "contig has not been planned");
+    if ((rc = ctx_drain(c))) return rc;
+    *ms = 0;
+    if (!g.n_rec) return MSIM_OK;
+    SpectrumState *S;
+    if ((rc = state_of(c, &S))) return rc;
+    const size_t bytes = (size_t)g.n_rec * sizeof(msim_record);
+    if ((rc = ensure_scratch(c, bytes))) return rc;
+    MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+    MSIM_HIP(c, hipMemcpyAsync(c->d_scratch, g.d_recs, bytes, hipMemcpyDeviceToDevice, c->stream));
+    MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+    MSIM_HIP(c, wait_stream(c->stream));
+    float t = 0;
+    MSIM_HIP(c, hipEventElapsedTime(&t, S->e0, S->e1));
+    *ms = t;
+    return MSIM_OK;
+}
+
 // ---- sequential host restatements: no context, no GPU ------------------------------------------------------------------
 int msim_dbg_context_counts(const uint8_t *bases, uint64_t L, uint64_t counts[64], uint64_t *n_valid) {
     if ((!bases && L) || !counts || !n_valid) return MSIM_ERR_ARG;
@@ -398,6 +559,27 @@ int msim_dbg_spectrum_plan(const uint8_t *bases, uint64_t L, const uint64_t thr[
     }
     if (n >= (1ull << 31)) return fail(nullptr, MSIM_ERR_UNSUPPORTED, "2^31 or more mutations on one contig");
     *n_recs = n;
+    return MSIM_OK;
+}
+
+int msim_dbg_sbs_counts(const uint8_t *bases, uint64_t L, const msim_record *recs, uint64_t n_records, uint64_t channels[96],
+                        uint64_t tallies[8]) {
+    if ((!bases && L) || (!recs && n_records) || !channels || !tallies) return MSIM_ERR_ARG;
+    memset(channels, 0, 96 * sizeof(uint64_t));
+    memset(tallies, 0, 8 * sizeof(uint64_t));
+    for (uint64_t i = 0; i < n_records; i++) {
+        const msim_record &r = recs[i];
+        if (r.type < MSIM_SN || r.type > MSIM_TLI) return fail(nullptr, MSIM_ERR_ARG, "record " + std::to_string(i) + ": unknown type");
+        tallies[r.type]++;
+        if (r.type != MSIM_SN) continue;
+        const uint64_t q = r.pos;
+        uint32_t a = spectrum::CODE_INVALID, m = a, z = a;
+        if (q >= 1 && q + 1 < L && r.aux < 3) {
+            a = spectrum::base_code(bases[q - 1]); m = spectrum::base_code(bases[q]); z = spectrum::base_code(bases[q + 1]);
+        }
+        if ((a | m | z) & spectrum::CODE_INVALID) tallies[0]++;
+        else channels[spectrum::sbs_channel(a, m, z, r.aux)]++;
+    }
     return MSIM_OK;
 }
 

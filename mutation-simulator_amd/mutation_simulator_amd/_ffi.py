@@ -175,10 +175,15 @@ SYMBOLS = [
     ("msim_spectrum_timing", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     ("msim_dbg_context_counts", C.c_int, [_VP, C.c_uint64, _VP, _U64P]),
     ("msim_dbg_spectrum_plan", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, C.c_uint32, _VP, C.c_uint64, _U64P]),
+    ("msim_sbs_counts", C.c_int, [_VP, C.c_int, _VP, _VP]),
+    ("msim_sbs_timing", C.c_int, [_VP, C.POINTER(C.c_double)]),
+    ("msim_dbg_sbs_counts", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP]),
     ("msim_stats", C.c_int, [_VP, C.POINTER(Timing)]),
     ("msim_reset_stats", C.c_int, [_VP]),
 ]
 SPECTRUM_TILE = 4096     # msim.h: MSIM_SPECTRUM_TILE, the bases one workgroup of the spectrum sampler takes
+SBS_CHANNELS, SBS_TALLIES = 96, 8    # msim.h: MSIM_SBS_CHANNELS, MSIM_SBS_TALLIES
+SBS_PASS = 1024          # msim.h: MSIM_SBS_PASS, the records one workgroup of the profile kernel takes per pass
 
 _lib = None
 
@@ -611,6 +616,20 @@ class Engine:
         a, b = C.c_double(), C.c_double()
         self._check(self.lib.msim_spectrum_timing(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def sbs_counts(self, contig: int) -> tuple:
+        """The SBS-96 profile of a planned contig's record table against its resident reference bases: (SN records per channel
+        in ``spectrum.CHANNELS`` order, uint64[96]; tallies, uint64[8]: [0] SN records without a channel, [t] records of type t)."""
+        channels = np.zeros(SBS_CHANNELS, dtype=np.uint64)
+        tallies = np.zeros(SBS_TALLIES, dtype=np.uint64)
+        self._check(self.lib.msim_sbs_counts(self.h, int(contig), _ptr(channels), _ptr(tallies)), contig)
+        return channels, tallies
+
+    def sbs_timing(self) -> float:
+        """The profile kernel's milliseconds since ``reset_stats`` (HIP events)."""
+        a = C.c_double()
+        self._check(self.lib.msim_sbs_timing(self.h, C.byref(a)))
+        return a.value
 
     # test hooks (msim_dbg_*: exported, not part of include/msim.h)
     def set_records(self, contig: int, recs: np.ndarray, pool: np.ndarray, with_offsets: bool = False):
@@ -1170,6 +1189,21 @@ def spectrum_plan_host(bases, thr, key: int, seq: int) -> np.ndarray:
         if rc != OK:
             raise _host_error(rc)
     return recs
+
+
+def sbs_counts_host(bases, recs) -> tuple:
+    """``msim_dbg_sbs_counts``: what ``Engine.sbs_counts`` returns, by a sequential host loop over ``bases`` (uint8, upper-cased)
+    and ``recs`` (RECORD_DTYPE).  No context, no GPU."""
+    lib = load()
+    bases = _as_u8(bases)
+    recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+    channels = np.zeros(SBS_CHANNELS, dtype=np.uint64)
+    tallies = np.zeros(SBS_TALLIES, dtype=np.uint64)
+    rc = lib.msim_dbg_sbs_counts(C.c_void_p(bases.ctypes.data) if len(bases) else None, len(bases),
+                                 C.c_void_p(recs.ctypes.data) if len(recs) else None, len(recs), _ptr(channels), _ptr(tallies))
+    if rc != OK:
+        raise _host_error(rc)
+    return channels, tallies
 
 
 VCF_GROUP_DTYPE = np.dtype([("name_off", "<u8"), ("first_line", "<u8"), ("n_lines", "<u8"), ("name_len", "<u4"), ("rsv", "<u4")])   # msim_vcf_group

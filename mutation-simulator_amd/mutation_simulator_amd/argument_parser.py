@@ -3,7 +3,9 @@ sub-commands (reference argument_parser.py:31-240) plus a few additions of ours 
 a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bgzip``, ``--chain``, ``--ploidy``, ``--het``, ``--bench-json``, ``--spectrum`` / ``--signature``
 (options of ``args``: SNPs drawn per trinucleotide context, ``spectrum.py``; ``spectrum_refusal`` words what such a run does not cover), and the ``vcf`` sub-command
 (``vcf_replay.py``: the mutated Fasta again from the reference and a run's VCF; it writes ``<outbase>_ms.fa`` and, with
-``--chain``, ``<outbase>_ms.chain``; with ``--consensus [--sample NAME] [--haplotype N]`` the VCF may come from anywhere).
+``--chain``, ``<outbase>_ms.chain``; with ``--consensus [--sample NAME] [--haplotype N]`` the VCF may come from anywhere), and the ``profile`` sub-command (``profile.py``:
+the SBS-96 spectrum of a VCF's SNPs against the reference, counted on the GPU; it writes ``<outbase>_ms.sbs96.tsv``, a file
+``--spectrum`` reads; ``profile_refusal`` words what it does not cover).
 
 ``--ploidy 2 [--het F]`` (``args`` / ``rmt``) writes two haplotype Fastas, ``<outbase>_ms_h1<suffix>`` and ``<outbase>_ms_h2<suffix>``
 (``args.outfasta_h1`` / ``outfasta_h2``; ``<outbase>_ms<suffix>`` is not written), one phased ``<outbase>_ms.vcf`` and, with ``--chain``,
@@ -46,6 +48,8 @@ def add_outfile_names(args: Namespace) -> Namespace:
     args.outvcf = args.outfasta.with_suffix(".vcf")
     args.outbedpe = args.outfastait.with_suffix(".bedpe")
     args.outchain = args.outfasta.with_suffix(".chain")
+    if getattr(args, "mode", None) == "profile":  # (only there: the other modes' namespaces stay as they were)
+        args.outprofile = args.outfasta.with_suffix(".sbs96.tsv")
     if getattr(args, "ploidy", 1) == 2:           # a diploid run: a Fasta (and a chain) per haplotype, ONE phased VCF
         for h in ("h1", "h2"):
             fa = args.outfasta.with_stem(f"{args.outfasta.stem}_{h}")
@@ -168,7 +172,38 @@ def build_parser() -> ArgumentParser:
                        help="With --consensus: the sample column to follow. Default = the first one")
     p_vcf.add_argument("--haplotype", type=int, default=None, metavar="N",
                        help="With --consensus: which allele of the genotype to apply, counted from 1. Default = 1")
+
+    p_prof = sub.add_parser("profile", help="Count the SBS-96 spectrum of a VCF's SNPs against the reference Fasta: a file "
+                                            "args --spectrum reads")
+    p_prof.add_argument("vcffile", type=Path, help="Path to the VCF file (text or BGZF-compressed)")
+    p_prof.add_argument("--consensus", action="store_true", default=False,
+                        help="Take any VCF, not only one this program wrote: count one haplotype of one sample, the "
+                             "records vcf --consensus would apply")
+    p_prof.add_argument("--sample", default=None, metavar="NAME",
+                        help="With --consensus: the sample column to follow. Default = the first one")
+    p_prof.add_argument("--haplotype", type=int, default=None, metavar="N",
+                        help="With --consensus: which allele of the genotype to count, counted from 1. Default = 1")
+    p_prof.add_argument("--per-contig", action="store_true", default=False, dest="per_contig",
+                        help="Add one column per contig, named by the contig, behind the genome-wide one")
+    p_prof.add_argument("--name", default="profile", metavar="NAME",
+                        help="Name of the genome-wide column (what --signature picks). Default = 'profile'")
     return parser
+
+
+def profile_refusal(args: Namespace):
+    """What the ``profile`` mode does not cover, as the message to refuse it with; None: the run can go ahead (or is no
+    profile).  ``--seed`` and ``--rng`` have no effect, as in ``vcf``: nothing is drawn."""
+    if args.mode != "profile":
+        return None
+    if getattr(args, "ploidy", 1) == 2:
+        return "--ploidy 2 does not apply to the profile mode (it counts one haplotype: profile --consensus --haplotype N)"
+    if getattr(args, "chain", False):
+        return "--chain does not apply to the profile mode (nothing is applied: there is no mutated genome to lift over to)"
+    if getattr(args, "bgzip", False):
+        return "--bgzip does not apply to the profile mode (it writes one small text table)"
+    if (args.gpus or 1) > 1:
+        return "the profile mode needs a single-GPU run (--gpus 1)"
+    return None
 
 
 def ploidy_refusal(args: Namespace, has_it: bool = False):
@@ -232,6 +267,11 @@ def get_args(argv=None) -> Namespace:
             parser.error("--haplotype counts from 1")
         if not args.consensus:                         # (the namespace of a plain replay stays as it was)
             del args.consensus, args.sample, args.haplotype
+    if args.mode == "profile":
+        if not args.consensus and (args.sample is not None or args.haplotype is not None):
+            parser.error("--sample and --haplotype need --consensus")
+        if args.haplotype is not None and args.haplotype < 1:
+            parser.error("--haplotype counts from 1")
     if args.quiet:
         args.ignore_warnings = True
         args.no_progress = True

@@ -179,6 +179,46 @@ def parse(text: str, signature: str | None = None, where: str = "spectrum") -> l
     return out
 
 
+def column_name_refusal(names):
+    """Why ``names`` cannot head the columns of a table ``parse`` reads back, or None: tab, comma and blank are its
+    separators, and ``--signature`` picks the first column of a name."""
+    seen = set()
+    for name in names:
+        if not name or any(ch in name for ch in "\t, \n\r"):
+            return f"column name {name!r} is empty or holds a tab, a comma or a blank (the spectrum table's separators)"
+        if name in seen:
+            return f"column name {name!r} appears twice"
+        seen.add(name)
+    return None
+
+
+def opportunities(counts) -> list:
+    """The 32 pyrimidine-centred contexts with the eligible sites a channel of theirs can be reached from,
+    ``counts[ctx] + counts[rc(ctx)]`` (a census, ``Engine.context_counts``): the denominator that turns counts into rates."""
+    counts = [int(x) for x in counts]
+    assert len(counts) == 64
+    return [(context_name(ctx), counts[ctx] + counts[rc(ctx)]) for ctx in range(64) if context_name(ctx)[1] in "CT"]
+
+
+def render_profile(columns, opportunities=None, notes=()) -> str:
+    """The text of a spectrum table holding counts (``profile`` mode): ``#`` comment lines first -- ``notes``, then one
+    ``# opportunities XYZ n`` line per pair of ``opportunities`` -- a header ``Type<TAB>name...``, and the 96 rows in ``CHANNELS``
+    order with integer counts.  ``columns``: (name, 96 counts) pairs.  ``parse(text, name)`` returns exactly those counts, as
+    floats, for every column (counts are below 2**53)."""
+    columns = [(str(name), [int(x) for x in values]) for name, values in columns]
+    refusal = "no column" if not columns else column_name_refusal([name for name, _ in columns])
+    if refusal:
+        raise SpectrumError(f"profile: {refusal}")
+    if any(len(values) != 96 or min(values) < 0 or max(values) >= 1 << 53 for _, values in columns):
+        raise SpectrumError("profile: a column holds 96 counts in [0, 2**53)")
+    lines = [f"# {note}" for note in notes]
+    lines += [f"# opportunities {name} {int(n)}" for name, n in (opportunities or ())]
+    lines.append("\t".join(["Type"] + [name for name, _ in columns]))
+    for i, channel in enumerate(CHANNELS):
+        lines.append("\t".join([channel] + [str(values[i]) for _, values in columns]))
+    return "\n".join(lines) + "\n"
+
+
 def load(path, signature: str | None = None) -> list:
     path = Path(path)
     try:
