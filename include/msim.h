@@ -604,6 +604,60 @@ int msim_sbs_timing(msim_ctx *ctx, double *kernel_ms);
 int msim_dbg_sbs_counts(const uint8_t *bases, uint64_t L, const msim_record *recs, uint64_t n_records,
                         uint64_t channels[96], uint64_t tallies[8]);
 
+/* ---- compare: a truth table scored against a calls table (csrc/compare.hip, compare.h) ----------------------------------------- */
+/* Two record tables planned on the SAME resident contig -- A, the truth, HELD beside the contig; B, the calls, the contig's current
+ * table -- joined record by record.  Which records are one variant:
+ *   SN                same pos and same aux.
+ *   DU, IV, TL, TLI   identical pos, stop and aux; TLI also extra.
+ *   DE, IN            same type, same length n = stop - pos + 1, and one a shifted placement of the other.  With g the contig's
+ *                     bases and L its length: a deletion of g[p..q] may move one base left iff p > 0 and g[p-1] == g[q], one base
+ *                     right iff q + 1 < L and g[q+1] == g[p]; an insertion of S in front of base p may move left iff p > 0 and
+ *                     g[p-1] == S[n-1] (S becomes S[n-1] + S[:n-1]), right iff p + 1 <= L - 1 and g[p] == S[0] (S becomes
+ *                     S[1:] + g[p]).  So an insertion b at distance d = pos_b - pos_a inside a's interval is a iff
+ *                     S_b[i] == S_a[(i + d) mod n] for all i.  No pool is rewritten.
+ *                     A step is taken only if the genome byte it brings in (g[p-1] to the left; g[q+1] / g[p] to the right) is A, C,
+ *                     G or T -- a run of N never shifts -- and a record never leaves the window of MSIM_CMP_WINDOW bases its pos lies
+ *                     in (pos >> 16).  A step is checked in this order: the contig's end, that byte, the comparison, the window.
+ *                     Every A indel so gets the interval [lo, hi] of its placements, each record normalised on its own against the
+ *                     reference (as `bcftools norm` does): neighbouring variants do not see each other.
+ * One to one: inside one class (type, length, interval, an insert's bytes up to rotation) the i-th record of A by position matches the
+ * i-th of B.  One lane per A record finds its rank by scanning A to the left while pos >= lo, binary-searches B for lo, scans B up to
+ * hi for the record of that rank in the class and sets that record's flag byte; a second launch tallies B from the flags.
+ * MSIM_CMP_EXACT: lo = hi = pos for every record -- the literal comparison.
+ *   counts[type][bin][4]   type = MSIM_SN .. MSIM_TLI (row 0 unused); bin: for IN and DE the length bin 1, 2-5, 6-20, 21-50, 51 and
+ *                          above, bin 0 for every other type; the four values: truth matched, truth missed, calls matched, calls
+ *                          extra.  Truth matched == calls matched in every cell.
+ *   tallies[2]             A indels whose walk a window edge stopped; A indels whose walk a byte outside A, C, G, T stopped.
+ *   msim_cmp_hold      a device copy of the contig's current table (records and insert pool; with a haplotype selected the table
+ *                      msim_fetch_records returns) becomes its HELD table, replacing one held before.  It survives a new plan of the
+ *                      contig and msim_release_result; msim_cmp_release (contig -1: every contig's), msim_clear and msim_destroy
+ *                      drop it.
+ *   msim_cmp_counts    held against current.  Synchronises like msim_sbs_counts; changes neither table.  Two empty tables: zeros,
+ *                      nothing launched.  MSIM_ERR_ARG without a held table or on an unplanned contig, MSIM_ERR_HIP on a host-only
+ *                      context.
+ *   msim_cmp_fetch     the held table's sizes, and into whichever destination is not NULL its records, its pool and the flag bytes of
+ *                      the contig's last msim_cmp_counts: one per held record, one per current record, 1 = matched (MSIM_ERR_ARG
+ *                      when the flags are asked for and there was no such call, or the current table has changed since).
+ *   msim_cmp_timing    the two kernels' time on the device (HIP events) since the context was made or msim_reset_stats.
+ * MSIM_CMP_PASS: the records one workgroup of the kernels takes per pass -- where their edge cases lie.
+ * msim_dbg_cmp_counts: the same counts, tallies and flags (either flag array may be NULL) by a sequential host loop over the
+ * caller's bases and two tables -- no context, no GPU (MSIM_ERR_ARG for a record of unknown type; error text: msim_last_error with
+ * a NULL context).                                                                                                                  */
+#define MSIM_CMP_EXACT  1u
+#define MSIM_CMP_BINS   5
+#define MSIM_CMP_PASS   256
+#define MSIM_CMP_WINDOW 65536
+int msim_cmp_hold(msim_ctx *ctx, int contig);
+int msim_cmp_release(msim_ctx *ctx, int contig);
+int msim_cmp_counts(msim_ctx *ctx, int contig, uint32_t flags, uint64_t *counts, uint64_t tallies[2]);
+int msim_cmp_fetch(msim_ctx *ctx, int contig, uint64_t *n_held, uint64_t *held_pool_len, msim_record *held, uint8_t *held_pool,
+                   uint8_t *held_flags, uint8_t *current_flags);
+int msim_cmp_timing(msim_ctx *ctx, double *kernel_ms);
+int msim_dbg_cmp_counts(const uint8_t *bases, uint64_t L, const msim_record *truth, uint64_t n_truth, const uint8_t *truth_pool,
+                        uint64_t truth_pool_len, const msim_record *calls, uint64_t n_calls, const uint8_t *calls_pool,
+                        uint64_t calls_pool_len, uint32_t flags, uint64_t *counts, uint64_t tallies[2], uint8_t *truth_flags,
+                        uint8_t *calls_flags);
+
 /* ---- test support: the SNP ti/tv transducer on the caller's words -------------------------------------------------- */
 /* Runs the three passes that turn CPython-stream words into SNP outcomes -- the map pass over whole blocks of
  * MSIM_SNP_BLOCK_WORDS words, the scan that finds where the K-th SNP's draws end, the outcome pass -- over `words` (raw,

@@ -1,0 +1,151 @@
+// The compare mode ("compare truth.vcf calls.vcf"): what the device kernels (compare.hip) and the sequential host restatement
+// (msim_dbg_cmp_counts) share -- the matching rules of include/msim.h, integer and byte arithmetic only.
+//
+//   interval   an IN / DE record's placements [lo, hi]: the walk to the left and to the right, one base a step, each step
+//              checked in this order -- the contig's end (stops silently), the genome byte the step compares (not A, C, G or T:
+//              stops, STOP_BASE), the comparison itself (stops silently), the window of the record's pos (stops, STOP_WINDOW)
+//   same       two records are one variant: type and length, the other's pos inside the interval (the caller's scan sees to
+//              that), an insert's bytes up to the rotation by the distance; every other type field by field
+//   partner    the rank of record i in its class among A's records to the left, the record of that rank in B's scan of
+//              [lo, hi]
+// A, B: position-sorted tables (pos strictly increasing, what every planner and msim_dbg_set_records guarantee).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <stdint.h>
+
+#include "../../include/msim.h"
+#include "fast_math.h"
+
+namespace msim {
+namespace cmp {
+
+constexpr uint32_t WINDOW_SHIFT = 16;                      // MSIM_CMP_WINDOW = 1 << 16
+constexpr uint32_t STOP_WINDOW = 1u, STOP_BASE = 2u;       // why a walk ended (Span::stops): msim_cmp_counts' two tallies
+constexpr uint32_t CELLS = 15;                             // (type, bin) pairs that exist: 7 types in bin 0, IN and DE in bins 1..4
+constexpr uint32_t COUNTERS = 2 * CELLS + 2;               // per cell matched / unmatched, then the two tallies
+static_assert(MSIM_CMP_BINS == 5, "the cells are laid out for five length bins");
+
+struct Rec { uint32_t pos, stop, extra, type, aux; };
+struct Table { const msim_record *recs; uint64_t n; const uint8_t *pool; uint64_t pool_len; };
+struct Span { uint32_t lo, hi, stops; };
+
+MSIM_FHD inline Rec rec_at(const msim_record *t, uint64_t i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint4 w = reinterpret_cast<const uint4 *>(t)[i];  // one 16-byte load (tables are device allocations: aligned)
+    return Rec{w.x, w.y, w.z, w.w & 0xffu, (w.w >> 8) & 0xffu};
+#else
+    return Rec{t[i].pos, t[i].stop, t[i].extra, t[i].type, t[i].aux};
+#endif
+}
+
+MSIM_FHD inline bool acgt(uint32_t b) { return b == 'A' || b == 'C' || b == 'G' || b == 'T'; }
+MSIM_FHD inline bool known_type(uint32_t type) { return type >= (uint32_t)MSIM_SN && type <= (uint32_t)MSIM_TLI; }
+MSIM_FHD inline bool indel(uint32_t type) { return type == (uint32_t)MSIM_IN || type == (uint32_t)MSIM_DE; }
+MSIM_FHD inline uint32_t len_bin(uint32_t n) { return n <= 1 ? 0u : n <= 5 ? 1u : n <= 20 ? 2u : n <= 50 ? 3u : 4u; }
+// the cell of a record: its type in bin 0, an indel's in its length bin
+MSIM_FHD inline uint32_t cell_of(const Rec &r) {
+    const uint32_t bin = indel(r.type) ? len_bin(r.stop - r.pos + 1u) : 0u;
+    return bin == 0 ? r.type - 1u : (r.type == (uint32_t)MSIM_IN ? 6u : 10u) + bin;
+}
+// ... and back: counts[type][bin] of the cell
+MSIM_FHD inline void cell_index(uint32_t cell, uint32_t *type, uint32_t *bin) {
+    if (cell < 7) { *type = cell + 1; *bin = 0; }
+    else if (cell < 11) { *type = MSIM_IN; *bin = cell - 6; }
+    else { *type = MSIM_DE; *bin = cell - 10; }
+}
+
+// an indel the walk is written for: inside the contig, an insert inside its pool (what table_check guarantees, checked again
+// because nothing else keeps a read inside its buffer)
+MSIM_FHD inline bool walkable(const Rec &r, uint64_t L, uint64_t pool_len) {
+    if (!indel(r.type) || r.stop < r.pos || r.pos >= L) return false;
+    const uint64_t n = (uint64_t)r.stop - r.pos + 1;
+    return r.type == (uint32_t)MSIM_DE ? r.stop < L : (r.extra <= pool_len && n <= pool_len - r.extra);
+}
+
+MSIM_FHD inline Span interval(const uint8_t *g, uint64_t L, const Rec &a, const uint8_t *pool, uint64_t pool_len, bool exact) {
+    Span s{a.pos, a.pos, 0u};
+    if (exact || !walkable(a, L, pool_len)) return s;
+    const uint32_t n = a.stop - a.pos + 1u, win = a.pos >> WINDOW_SHIFT;
+    const bool del = a.type == (uint32_t)MSIM_DE;
+    const uint8_t *S = pool + a.extra;
+    {   // to the left: g[p - 1] against the deletion's last base g[p + n - 1] / the insert's last byte, which rotates
+        uint32_t p = a.pos, k = n - 1;
+        while (p > 0) {
+            const uint32_t in = g[p - 1];
+            if (!acgt(in)) { s.stops |= STOP_BASE; break; }
+            if (in != (del ? (uint32_t)g[(uint64_t)p + n - 1] : (uint32_t)S[k])) break;
+            if (((p - 1) >> WINDOW_SHIFT) != win) { s.stops |= STOP_WINDOW; break; }
+            p--;
+            k = k ? k - 1 : n - 1;
+        }
+        s.lo = p;
+    }
+    {   // to the right: the base behind the deletion g[p + n] against its first g[p] / g[p] against the insert's first byte
+        uint64_t p = a.pos;
+        uint32_t k = 0;
+        while (del ? p + n < L : p + 1 < L) {
+            const uint32_t in = del ? g[p + n] : g[p];
+            if (!acgt(in)) { s.stops |= STOP_BASE; break; }
+            if (in != (del ? (uint32_t)g[p] : (uint32_t)S[k])) break;
+            if (((p + 1) >> WINDOW_SHIFT) != win) { s.stops |= STOP_WINDOW; break; }
+            p++;
+            k = k + 1 == n ? 0 : k + 1;
+        }
+        s.hi = (uint32_t)p;
+    }
+    return s;
+}
+
+// Is b the variant a is?  For indels the caller has b.pos inside a's interval; an insert's bytes: S_b[i] == S_a[(i + d) mod n],
+// d = b.pos - a.pos.  pool_b / pool_b_len: the pool b's insert lies in (a's own was checked by walkable()).
+MSIM_FHD inline bool same(const Rec &a, const uint8_t *pool_a, bool a_walkable, const Rec &b, const uint8_t *pool_b,
+                          uint64_t pool_b_len) {
+    if (a.type != b.type) return false;
+    if (!indel(a.type))
+        return a.pos == b.pos && a.aux == b.aux && (a.type == (uint32_t)MSIM_SN || a.stop == b.stop) &&
+               (a.type != (uint32_t)MSIM_TLI || a.extra == b.extra);
+    if (!a_walkable || b.stop < b.pos || b.stop - b.pos != a.stop - a.pos) return false;
+    if (a.type == (uint32_t)MSIM_DE) return true;
+    const uint32_t n = a.stop - a.pos + 1u;
+    if (b.extra > pool_b_len || n > pool_b_len - b.extra) return false;
+    const int64_t d = (int64_t)b.pos - (int64_t)a.pos;
+    uint32_t k = (uint32_t)(((d % (int64_t)n) + (int64_t)n) % (int64_t)n);
+    const uint8_t *Sa = pool_a + a.extra, *Sb = pool_b + b.extra;
+    for (uint32_t i = 0; i < n; i++) {
+        if (Sb[i] != Sa[k]) return false;
+        k = k + 1 == n ? 0 : k + 1;
+    }
+    return true;
+}
+
+// The record of B that A's record i matches, or -1; *span: i's interval and why its walks ended.
+MSIM_FHD inline int64_t partner(const uint8_t *g, uint64_t L, const Table &A, uint64_t i, const Table &B, bool exact, Span *span) {
+    const Rec a = rec_at(A.recs, i);
+    const Span s = interval(g, L, a, A.pool, A.pool_len, exact);
+    *span = s;
+    const bool ok = !indel(a.type) || walkable(a, L, A.pool_len);
+    uint64_t rank = 0;                                     // records of a's class in front of it
+    for (uint64_t j = i; j > 0; j--) {
+        const Rec o = rec_at(A.recs, j - 1);
+        if (o.pos < s.lo) break;
+        if (same(a, A.pool, ok, o, A.pool, A.pool_len)) rank++;
+    }
+    uint64_t lo = 0, hi = B.n;                             // the first record of B at or behind s.lo
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (rec_at(B.recs, mid).pos < s.lo) lo = mid + 1; else hi = mid;
+    }
+    for (uint64_t j = lo; j < B.n; j++) {
+        const Rec o = rec_at(B.recs, j);
+        if (o.pos > s.hi) break;
+        if (same(a, A.pool, ok, o, B.pool, B.pool_len)) {
+            if (rank == 0) return (int64_t)j;
+            rank--;
+        }
+    }
+    return -1;
+}
+
+}  // namespace cmp
+}  // namespace msim

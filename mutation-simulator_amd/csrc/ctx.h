@@ -89,6 +89,7 @@ struct Batch;                         // msim_api.hip: state of msim_batch_run
 struct FileIo;                        // file_io.hip: the output channels (thread + stream + pinned ring per output file)
 struct VcfState;                      // vcf_parse.hip: the VCF text of a replay, its line starts and groups
 struct SpectrumState;                 // spectrum.hip: scratch, thresholds and kernel times of the context-dependent SNP engine
+struct CompareState;                  // compare.hip: the held tables of the compare mode, its result buffers and kernel time
 
 struct Ctx {
     int device = 0;
@@ -108,6 +109,7 @@ struct Ctx {
     FileIo *file_io = nullptr;        // file_io.hip (made on first use)
     VcfState *vcf = nullptr;          // vcf_parse.hip (msim_vcf_load .. msim_vcf_release)
     SpectrumState *spectrum = nullptr;    // spectrum.hip (made on first use)
+    CompareState *compare = nullptr;      // compare.hip (made on first use)
     msim_params params{};
     bool have_params = false;
     std::vector<Contig> contigs;
@@ -197,6 +199,9 @@ int table_check(Ctx *c, uint64_t L, const msim_record *recs, uint64_t n, uint64_
 void vcf_state_destroy(Ctx *c);       // vcf_parse.hip
 void spectrum_state_destroy(Ctx *c);  // spectrum.hip (the caller has waited for the context's streams)
 void spectrum_reset_timing(Ctx *c);   // msim_reset_stats: msim_spectrum_timing counts from here
+void compare_state_destroy(Ctx *c);   // compare.hip (the caller has waited for the context's streams)
+void compare_drop_all(Ctx *c);        // msim_clear: every held table goes with the contigs
+void compare_reset_timing(Ctx *c);    // msim_reset_stats: msim_cmp_timing counts from here
 
 // plan_host.cpp
 struct HostPlan {

@@ -364,6 +364,7 @@ void msim_destroy(msim_ctx *p) {
     lap(2);
     comm_destroy(c);
     spectrum_state_destroy(c);
+    compare_state_destroy(c);
     fast_plan_destroy(c);
     gpu_plan_destroy(c->gpu);
     lap(3);
@@ -510,6 +511,7 @@ int msim_clear(msim_ctx *p) {
         if (rc) return rc;
     }
     c->contigs.clear();
+    compare_drop_all(c);                                   // (held tables belong to contigs that are gone)
     c->text_kind = 0;
     return MSIM_OK;
 }
@@ -1628,6 +1630,7 @@ int msim_reset_stats(msim_ctx *p) {
     }
     c->t = msim_timing{};
     spectrum_reset_timing(c);
+    compare_reset_timing(c);
     return MSIM_OK;
 }
 

@@ -1,6 +1,6 @@
 """``mutation-simulator file {args,rmt,it}`` (reference __main__.py:34-111) on an MI355X, plus ``file vcf truth.vcf``
-(``--consensus``: any VCF, one haplotype of one sample) and ``file profile calls.vcf`` (the VCF's SBS-96 spectrum, counted
-against the reference)."""
+(``--consensus``: any VCF, one haplotype of one sample), ``file profile calls.vcf`` (the VCF's SBS-96 spectrum, counted
+against the reference) and ``file compare truth.vcf calls.vcf`` (the calls scored against the truth)."""
 from __future__ import annotations
 
 import json
@@ -10,7 +10,7 @@ from timeit import default_timer as timer
 
 from . import *  # noqa: F401,F403  (same style of namespace as the reference entry point)
 from ._ffi import MsimError, MsimUnsupported
-from .argument_parser import ploidy_refusal, profile_refusal, spectrum_refusal
+from .argument_parser import compare_refusal, ploidy_refusal, profile_refusal, spectrum_refusal
 from .spectrum import SpectrumError
 from .fasta_io import is_gzip
 
@@ -48,6 +48,10 @@ class ProfileUnsupportedError(Exception):
     """The profile mode together with what it does not cover (argument_parser.profile_refusal)."""
 
 
+class CompareUnsupportedError(Exception):
+    """The compare mode together with what it does not cover (argument_parser.compare_refusal)."""
+
+
 class CompressedInputUnsupportedError(Exception):
     """A gzip-compressed input together with what does not cover it (a sharded run)."""
 
@@ -67,6 +71,9 @@ def initialize(argv=None):
     refusal = profile_refusal(args)
     if refusal:
         exit_with_error(ProfileUnsupportedError(refusal), args.no_color)
+    refusal = compare_refusal(args)
+    if refusal:
+        exit_with_error(CompareUnsupportedError(refusal), args.no_color)
     refusal = ploidy_refusal(args)
     if refusal:
         exit_with_error(PloidyUnsupportedError(refusal), args.no_color)
@@ -107,7 +114,7 @@ def initialize(argv=None):
         args.genome_name = args.infile.name
         if fasta.compressed and args.infile.suffix.lower() in (".gz", ".bgz") and args.infile.stem:
             args.genome_name = args.infile.stem
-        if args.mode in ("vcf", "profile"):            # a replay and a profile have no settings and draw nothing
+        if args.mode in ("vcf", "profile", "compare"):     # a replay, a profile and a comparison have no settings and draw nothing
             return args, fasta, None
         if args.mode == "args":
             sim = SimulationSettings.from_args(args, fasta, args.ignore_warnings)
@@ -178,6 +185,25 @@ def main(argv=None):
                 stats["cli_s"] = {"load_index": round(STAGES.get("load_index", 0.0), 4), "profile": round(timer() - loaded, 4)}
                 args.bench_json.write_text(json.dumps(stats, indent=1) + "\n")
         except (ProfileError, SpectrumError, VcfReplayError, MsimError, OSError, UnsupportedCompressionFormat, ValueError) as e:
+            exit_with_error(e, args.no_color)
+        if not args.quiet:
+            print_success(f"Mutation-Simulator finished in: {round(timer() - start, 4)}s", args.no_color)
+        return
+    if args.mode == "compare":                         # (--seed / --rng have no effect: no generator is touched)
+        from .compare import Compare, CompareError
+        from .vcf_replay import VcfReplayError
+        try:
+            compare = Compare(args, fasta)
+            try:
+                compare.run()
+            finally:
+                compare.close()
+            fasta.close()
+            if args.bench_json:
+                stats = dict(compare.stats)
+                stats["cli_s"] = {"load_index": round(STAGES.get("load_index", 0.0), 4), "compare": round(timer() - loaded, 4)}
+                args.bench_json.write_text(json.dumps(stats, indent=1) + "\n")
+        except (CompareError, VcfReplayError, MsimError, OSError, UnsupportedCompressionFormat, ValueError) as e:
             exit_with_error(e, args.no_color)
         if not args.quiet:
             print_success(f"Mutation-Simulator finished in: {round(timer() - start, 4)}s", args.no_color)

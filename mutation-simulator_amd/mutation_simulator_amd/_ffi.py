@@ -178,9 +178,20 @@ SYMBOLS = [
     ("msim_sbs_counts", C.c_int, [_VP, C.c_int, _VP, _VP]),
     ("msim_sbs_timing", C.c_int, [_VP, C.POINTER(C.c_double)]),
     ("msim_dbg_sbs_counts", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP]),
+    ("msim_cmp_hold", C.c_int, [_VP, C.c_int]),
+    ("msim_cmp_release", C.c_int, [_VP, C.c_int]),
+    ("msim_cmp_counts", C.c_int, [_VP, C.c_int, C.c_uint32, _VP, _VP]),
+    ("msim_cmp_fetch", C.c_int, [_VP, C.c_int, _U64P, _U64P, _VP, _VP, _VP, _VP]),
+    ("msim_cmp_timing", C.c_int, [_VP, C.POINTER(C.c_double)]),
+    ("msim_dbg_cmp_counts", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64,
+                                      C.c_uint32, _VP, _VP, _VP, _VP]),
     ("msim_stats", C.c_int, [_VP, C.POINTER(Timing)]),
     ("msim_reset_stats", C.c_int, [_VP]),
 ]
+CMP_EXACT = 1            # msim.h: MSIM_CMP_EXACT, the literal comparison
+CMP_BINS = 5             # msim.h: MSIM_CMP_BINS, the length bins of IN and DE (1, 2-5, 6-20, 21-50, 51 and above)
+CMP_PASS = 256           # msim.h: MSIM_CMP_PASS, the records one workgroup of the compare kernels takes per pass
+CMP_WINDOW = 65536       # msim.h: MSIM_CMP_WINDOW, the bases an indel's placements stay inside
 SPECTRUM_TILE = 4096     # msim.h: MSIM_SPECTRUM_TILE, the bases one workgroup of the spectrum sampler takes
 SBS_CHANNELS, SBS_TALLIES = 96, 8    # msim.h: MSIM_SBS_CHANNELS, MSIM_SBS_TALLIES
 SBS_PASS = 1024          # msim.h: MSIM_SBS_PASS, the records one workgroup of the profile kernel takes per pass
@@ -629,6 +640,46 @@ class Engine:
         """The profile kernel's milliseconds since ``reset_stats`` (HIP events)."""
         a = C.c_double()
         self._check(self.lib.msim_sbs_timing(self.h, C.byref(a)))
+        return a.value
+
+    # ------------------------------------------------------------------ compare (msim.h: a truth table against a calls table)
+    def cmp_hold(self, contig: int):
+        """A device copy of the planned contig's current table (records and insert pool) becomes its held table: the truth
+        of the following ``cmp_counts``.  It survives a new plan of the contig and ``release_result``."""
+        self._check(self.lib.msim_cmp_hold(self.h, int(contig)), contig)
+
+    def cmp_release(self, contig: int = -1):
+        """Drop the contig's held table (-1: every contig's)."""
+        self._check(self.lib.msim_cmp_release(self.h, int(contig)))
+
+    def cmp_counts(self, contig: int, exact: bool = False) -> tuple:
+        """The contig's held table (truth) scored against its current one (calls): (uint64[8, CMP_BINS, 4] by record type and
+        length bin -- truth matched, truth missed, calls matched, calls extra; uint64[2]: truth indels whose walk a window edge
+        stopped, ... a byte outside ACGT stopped).  ``exact``: the literal comparison, no shifting."""
+        counts = np.zeros((8, CMP_BINS, 4), dtype=np.uint64)
+        tallies = np.zeros(2, dtype=np.uint64)
+        self._check(self.lib.msim_cmp_counts(self.h, int(contig), CMP_EXACT if exact else 0, _ptr(counts), _ptr(tallies)), contig)
+        return counts, tallies
+
+    def cmp_fetch(self, contig: int, flags: bool = True) -> tuple:
+        """(held records, held pool, a flag byte per held record, a flag byte per current record) of the contig's last
+        ``cmp_counts``; 1 = matched.  ``flags=False``: the held table only (the flag arrays are None)."""
+        n, m = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.msim_cmp_fetch(self.h, int(contig), C.byref(n), C.byref(m), None, None, None, None), contig)
+        recs = np.zeros(n.value, dtype=RECORD_DTYPE)
+        pool = np.zeros(m.value, dtype=np.uint8)
+        fa = fb = None
+        if flags:
+            fa = np.zeros(n.value, dtype=np.uint8)
+            fb = np.zeros(self.result_sizes(contig, applied=False)[1], dtype=np.uint8)
+        self._check(self.lib.msim_cmp_fetch(self.h, int(contig), None, None, _ptr(recs), _ptr(pool),
+                                            _ptr(fa) if flags else None, _ptr(fb) if flags else None), contig)
+        return recs, pool, fa, fb
+
+    def cmp_timing(self) -> float:
+        """The compare kernels' milliseconds since ``reset_stats`` (HIP events)."""
+        a = C.c_double()
+        self._check(self.lib.msim_cmp_timing(self.h, C.byref(a)))
         return a.value
 
     # test hooks (msim_dbg_*: exported, not part of include/msim.h)
@@ -1204,6 +1255,31 @@ def sbs_counts_host(bases, recs) -> tuple:
     if rc != OK:
         raise _host_error(rc)
     return channels, tallies
+
+
+def cmp_counts_host(bases, truth, truth_pool, calls, calls_pool, exact: bool = False) -> tuple:
+    """``msim_dbg_cmp_counts``: what ``Engine.cmp_counts`` returns and the two flag arrays of ``Engine.cmp_fetch`` -- (counts,
+    tallies, truth flags, calls flags) -- by a sequential host loop over ``bases`` (uint8, upper-cased) and two tables
+    (RECORD_DTYPE, insert pools uint8).  No context, no GPU."""
+    lib = load()
+    bases = _as_u8(bases)
+    truth = np.ascontiguousarray(truth, dtype=RECORD_DTYPE)
+    calls = np.ascontiguousarray(calls, dtype=RECORD_DTYPE)
+    truth_pool = np.ascontiguousarray(truth_pool, dtype=np.uint8)
+    calls_pool = np.ascontiguousarray(calls_pool, dtype=np.uint8)
+    counts = np.zeros((8, CMP_BINS, 4), dtype=np.uint64)
+    tallies = np.zeros(2, dtype=np.uint64)
+    fa = np.zeros(len(truth), dtype=np.uint8)
+    fb = np.zeros(len(calls), dtype=np.uint8)
+
+    def ptr(a):
+        return C.c_void_p(a.ctypes.data) if len(a) else None
+    rc = lib.msim_dbg_cmp_counts(ptr(bases), len(bases), ptr(truth), len(truth), ptr(truth_pool), len(truth_pool), ptr(calls),
+                                 len(calls), ptr(calls_pool), len(calls_pool), CMP_EXACT if exact else 0, _ptr(counts),
+                                 _ptr(tallies), ptr(fa), ptr(fb))
+    if rc != OK:
+        raise _host_error(rc)
+    return counts, tallies, fa, fb
 
 
 VCF_GROUP_DTYPE = np.dtype([("name_off", "<u8"), ("first_line", "<u8"), ("n_lines", "<u8"), ("name_len", "<u4"), ("rsv", "<u4")])   # msim_vcf_group

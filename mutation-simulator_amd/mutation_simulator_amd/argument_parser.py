@@ -5,7 +5,10 @@ a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bgzip``, ``--cha
 (``vcf_replay.py``: the mutated Fasta again from the reference and a run's VCF; it writes ``<outbase>_ms.fa`` and, with
 ``--chain``, ``<outbase>_ms.chain``; with ``--consensus [--sample NAME] [--haplotype N]`` the VCF may come from anywhere), and the ``profile`` sub-command (``profile.py``:
 the SBS-96 spectrum of a VCF's SNPs against the reference, counted on the GPU; it writes ``<outbase>_ms.sbs96.tsv``, a file
-``--spectrum`` reads; ``profile_refusal`` words what it does not cover).
+``--spectrum`` reads; ``profile_refusal`` words what it does not cover), and the ``compare`` sub-command (``compare.py``: a calls
+VCF scored against a truth VCF on the GPU, indels matched up to their placement inside a repeat; it writes
+``<outbase>_ms.compare.tsv`` and, with ``--list``, ``<outbase>_ms.compare.records.tsv``; ``compare_refusal`` words what it does
+not cover).
 
 ``--ploidy 2 [--het F]`` (``args`` / ``rmt``) writes two haplotype Fastas, ``<outbase>_ms_h1<suffix>`` and ``<outbase>_ms_h2<suffix>``
 (``args.outfasta_h1`` / ``outfasta_h2``; ``<outbase>_ms<suffix>`` is not written), one phased ``<outbase>_ms.vcf`` and, with ``--chain``,
@@ -50,6 +53,9 @@ def add_outfile_names(args: Namespace) -> Namespace:
     args.outchain = args.outfasta.with_suffix(".chain")
     if getattr(args, "mode", None) == "profile":  # (only there: the other modes' namespaces stay as they were)
         args.outprofile = args.outfasta.with_suffix(".sbs96.tsv")
+    if getattr(args, "mode", None) == "compare":
+        args.outcompare = args.outfasta.with_suffix(".compare.tsv")
+        args.outcompare_records = args.outfasta.with_suffix(".compare.records.tsv")
     if getattr(args, "ploidy", 1) == 2:           # a diploid run: a Fasta (and a chain) per haplotype, ONE phased VCF
         for h in ("h1", "h2"):
             fa = args.outfasta.with_stem(f"{args.outfasta.stem}_{h}")
@@ -187,7 +193,43 @@ def build_parser() -> ArgumentParser:
                         help="Add one column per contig, named by the contig, behind the genome-wide one")
     p_prof.add_argument("--name", default="profile", metavar="NAME",
                         help="Name of the genome-wide column (what --signature picks). Default = 'profile'")
+
+    p_cmp = sub.add_parser("compare", help="Score a calls VCF against a truth VCF on the reference Fasta: recall and precision "
+                                           "per variant type and length, indels matched wherever a repeat lets them stand")
+    p_cmp.add_argument("truthfile", type=Path, help="Path to the truth VCF file (text or BGZF-compressed)")
+    p_cmp.add_argument("callsfile", type=Path, help="Path to the calls VCF file (text or BGZF-compressed)")
+    p_cmp.add_argument("--truth-sample", default=None, metavar="NAME", dest="truth_sample",
+                       help="The sample column of the truth VCF to follow. Default = the first one")
+    p_cmp.add_argument("--truth-haplotype", type=int, default=None, metavar="N", dest="truth_haplotype",
+                       help="Which allele of the truth genotype to score against, counted from 1. Default = 1")
+    p_cmp.add_argument("--sample", default=None, metavar="NAME",
+                       help="The sample column of the calls VCF to follow. Default = the first one")
+    p_cmp.add_argument("--haplotype", type=int, default=None, metavar="N",
+                       help="Which allele of the calls genotype to score, counted from 1. Default = 1")
+    p_cmp.add_argument("--exact", action="store_true", default=False,
+                       help="Compare positions literally: an indel placed elsewhere in its repeat counts as missed and as extra")
+    p_cmp.add_argument("--per-contig", action="store_true", default=False, dest="per_contig",
+                       help="Repeat the table per contig behind the genome-wide one")
+    p_cmp.add_argument("--list", action="store_true", default=False, dest="list_records",
+                       help="Also write <outbase>_ms.compare.records.tsv: one line per unmatched record")
     return parser
+
+
+def compare_refusal(args: Namespace):
+    """What the ``compare`` mode does not cover, as the message to refuse it with; None: the run can go ahead (or is no
+    compare).  ``--seed`` and ``--rng`` have no effect, as in ``vcf``: nothing is drawn."""
+    if args.mode != "compare":
+        return None
+    if getattr(args, "ploidy", 1) == 2:
+        return ("--ploidy 2 does not apply to the compare mode (it scores one haplotype against one: "
+                "compare --truth-haplotype N --haplotype N)")
+    if getattr(args, "chain", False):
+        return "--chain does not apply to the compare mode (nothing is applied: there is no mutated genome to lift over to)"
+    if getattr(args, "bgzip", False):
+        return "--bgzip does not apply to the compare mode (it writes small text tables)"
+    if (args.gpus or 1) > 1:
+        return "the compare mode needs a single-GPU run (--gpus 1)"
+    return None
 
 
 def profile_refusal(args: Namespace):
@@ -272,6 +314,9 @@ def get_args(argv=None) -> Namespace:
             parser.error("--sample and --haplotype need --consensus")
         if args.haplotype is not None and args.haplotype < 1:
             parser.error("--haplotype counts from 1")
+    if args.mode == "compare":
+        if any(h is not None and h < 1 for h in (args.haplotype, args.truth_haplotype)):
+            parser.error("--haplotype and --truth-haplotype count from 1")
     if args.quiet:
         args.ignore_warnings = True
         args.no_progress = True

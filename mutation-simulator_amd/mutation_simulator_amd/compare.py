@@ -1,0 +1,160 @@
+"""``mutation-simulator genome.fa compare truth.vcf calls.vcf``: a calls VCF scored against a truth VCF on the GPU -- the step
+behind simulating a genome with a known truth set.
+
+Both files go through the ``vcf`` mode's loader and the consensus grammar (``vcf_replay.load_vcf_text`` / ``plan_all``: any VCF,
+BGZF input, one sample and one haplotype a side, the same "VCF line N: reason" refusals, here with ``truth`` or ``calls`` in
+front).  The truth's record tables are planned first and HELD (``msim_cmp_hold``), the calls' tables are planned over them, and
+``msim_cmp_counts`` joins the two per contig against the resident reference bases (csrc/compare.hip: k_cmp_match, k_cmp_tally).
+Nothing is applied, no Fasta is written, no generator is touched.
+
+Rules (include/msim.h): an SNP matches at the same position with the same alternative base; an insertion or deletion matches a
+record of the same type and length that is a shifted placement of it -- anywhere inside the homopolymer or tandem repeat it
+stands in, an insertion's bytes rotating with it -- as long as both lie in the same window of 65 536 bases and no base outside
+A, C, G, T is stepped over; ``--exact`` compares positions literally.  Inside one class of equivalent records the i-th of the
+truth matches the i-th of the calls.  Counts come per record type and, for insertions and deletions, per length bin.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+from . import _ffi
+from .vcf_replay import MAX_CONTIGS, VcfReplayError, load_vcf_text, plan_all
+
+TYPE_NAMES = (None, "SN", "IN", "DE", "DU", "IV", "TL", "TLI")            # msim.h: MSIM_SN .. MSIM_TLI
+BIN_NAMES = ("1", "2-5", "6-20", "21-50", "51+")                          # msim_cmp_counts: the length bins of IN and DE
+ROWS = [(t, b) for t in range(1, 8) for b in (range(_ffi.CMP_BINS) if t in (2, 3) else (0,))]
+HEADER = ("type", "length", "truth", "calls", "TP", "FN", "FP", "recall", "precision")
+
+
+class CompareError(Exception):
+    """The comparison cannot be made as asked (the message says why)."""
+
+
+def ratio(n: int, d: int) -> str:
+    return "NA" if d == 0 else f"{n / d:.6f}"
+
+
+def row_cells(kind: str, length: str, v) -> list:
+    """One row of the table from (truth matched, truth missed, calls matched, calls extra)."""
+    tm, fn, cm, fp = (int(x) for x in v)
+    return [kind, length, str(tm + fn), str(cm + fp), str(tm), str(fn), str(fp), ratio(tm, tm + fn), ratio(cm, cm + fp)]
+
+
+def render_block(counts) -> list:
+    """The rows of one ``counts[8][CMP_BINS][4]``: a row per type and length bin, then ALL."""
+    counts = np.asarray(counts, dtype=np.uint64)
+    lines = ["\t".join(HEADER)]
+    for t, b in ROWS:
+        lines.append("\t".join(row_cells(TYPE_NAMES[t], BIN_NAMES[b] if t in (2, 3) else ".", counts[t, b])))
+    lines.append("\t".join(row_cells("ALL", ".", counts.reshape(-1, 4).sum(axis=0, dtype=np.uint64))))
+    return lines
+
+
+def render(notes, counts, names=None) -> str:
+    """The text of ``*_ms.compare.tsv``: ``#`` comment lines (``notes``), the genome-wide block (the sum of ``counts`` over
+    its first axis, the contigs) and, with ``names``, a ``# contig NAME`` line and a block per contig."""
+    counts = np.asarray(counts, dtype=np.uint64)
+    lines = [f"# {note}" for note in notes]
+    lines += render_block(counts.sum(axis=0, dtype=np.uint64))
+    for i, name in enumerate(names or ()):
+        lines.append(f"# contig {name}")
+        lines += render_block(counts[i])
+    return "\n".join(lines) + "\n"
+
+
+def record_rows(kind: str, contig: str, recs, flags) -> list:
+    """The lines of ``--list`` for one table: every record whose flag byte is 0."""
+    out = []
+    for r in recs[np.asarray(flags) == 0]:
+        out.append("\t".join([kind, contig, str(int(r["pos"]) + 1), TYPE_NAMES[int(r["type"])],
+                              str(int(r["stop"]) - int(r["pos"]) + 1)]))
+    return out
+
+
+class Compare:
+    """Scores one calls VCF against one truth VCF on the GPU and writes ``*_ms.compare.tsv``."""
+
+    def __init__(self, args, fasta, engine=None):
+        self._args = args
+        self._fasta = fasta
+        self._device = getattr(args, "device", 0) or 0
+        self._engine = engine
+        self._own_engine = engine is None
+        self.stats: dict = {}
+        self.counts = None           # uint64[contigs, 8, CMP_BINS, 4] of the last run
+        self.tallies = None          # uint64[contigs, 2]
+
+    def _plan(self, eng, side: str, path, names, cids, sample, haplotype):
+        """One file's tables onto the contigs; (bytes of its text, load kernel ms, plan kernel ms)."""
+        text = load_vcf_text(path, eng)
+        try:
+            plan_all(eng, text, names, cids, (sample, haplotype or 1))
+        except (VcfReplayError, ValueError) as e:
+            msg = str(e)
+            raise CompareError(f"{side} {msg}" if msg.startswith("VCF line") else f"{side} VCF: {msg}") from None
+        load_ms, plan_ms = eng.vcf_timing()
+        return int(text.shape[0]), load_ms, plan_ms
+
+    def run(self):
+        fa, args = self._fasta, self._args
+        if len(fa) > MAX_CONTIGS:
+            raise _ffi.MsimUnsupported(f"compare mode keeps the genome resident: more than {MAX_CONTIGS} contigs")
+        recs = [fa[i] for i in range(len(fa))]
+        names = [r.name for r in recs]
+        if self._engine is None:
+            self._engine = _ffi.Engine(self._device)
+        eng = self._engine
+        cids = []
+        for rec in recs:
+            if getattr(rec, "uniform", False):         # file text -> HBM: strip + upper-case on the device
+                cids.append(eng.add_contig_text(rec.body, len(rec), rec.lenc, rec.lenb))
+            else:
+                cids.append(eng.add_contig(rec.bases))
+        truth = self._plan(eng, "truth", args.truthfile, names, cids, getattr(args, "truth_sample", None),
+                           getattr(args, "truth_haplotype", None))
+        for cid in cids:
+            eng.cmp_hold(cid)
+        eng.vcf_release()
+        calls = self._plan(eng, "calls", args.callsfile, names, cids, getattr(args, "sample", None), getattr(args, "haplotype", None))
+        # every line of both files is accepted: count, contig by contig
+        exact = bool(getattr(args, "exact", False))
+        cmp0 = eng.cmp_timing()                        # (a caller's engine may have compared before)
+        n = len(cids)
+        self.counts = np.zeros((n, 8, _ffi.CMP_BINS, 4), dtype=np.uint64)
+        self.tallies = np.zeros((n, 2), dtype=np.uint64)
+        listed = []
+        for i, cid in enumerate(cids):
+            self.counts[i], self.tallies[i] = eng.cmp_counts(cid, exact)
+            if getattr(args, "list_records", False):
+                held, _, fa_flags, fb_flags = eng.cmp_fetch(cid)
+                listed += record_rows("FN", names[i], held, fa_flags)
+                listed += record_rows("FP", names[i], eng.fetch_records(cid)[0], fb_flags)
+        self.stats = {"truth_vcf_bytes": truth[0], "calls_vcf_bytes": calls[0], "vcf_load_kernel_ms": truth[1] + calls[1],
+                      "vcf_plan_kernel_ms": truth[2] + calls[2], "cmp_kernel_ms": round(eng.cmp_timing() - cmp0, 4)}
+        eng.vcf_release()
+        eng.cmp_release()
+        args.outcompare.write_text(self.render(names))
+        if getattr(args, "list_records", False):
+            args.outcompare_records.write_text("".join(line + "\n" for line in listed))
+
+    def render(self, names) -> str:
+        args = self._args
+        tallies = self.tallies.sum(axis=0, dtype=np.uint64)
+
+        def followed(sample, haplotype):
+            return f"sample {sample if sample is not None else '(first)'} haplotype {haplotype or 1}"
+        notes = [f"compare: calls {args.callsfile.name} against truth {args.truthfile.name} on "
+                 f"{getattr(args, 'genome_name', args.infile.name)} ({len(names)} contigs)",
+                 f"truth: {followed(getattr(args, 'truth_sample', None), getattr(args, 'truth_haplotype', None))}",
+                 f"calls: {followed(getattr(args, 'sample', None), getattr(args, 'haplotype', None))}",
+                 "matching: " + ("exact (positions compared literally)" if getattr(args, "exact", False)
+                                 else "normalised (an indel matches any placement inside its repeat)"),
+                 f"truth indels whose placements end at a window edge: {int(tallies[0])}",
+                 f"truth indels whose placements end at a base outside ACGT: {int(tallies[1])}"]
+        return render(notes, self.counts, names if getattr(args, "per_contig", False) else None)
+
+    def close(self):
+        eng = self._engine
+        self._engine = None
+        if eng is not None and self._own_engine:
+            eng.close()
