@@ -5,8 +5,7 @@
 //            scan of A to the left, a binary search of B for the interval's start, a scan of B for the record of that rank;
 //            the lane stores its own flag byte and its partner's (no two lanes share a partner) and counts the record
 //   tally    k_cmp_tally: one lane per B record, counted by its flag byte
-// Both kernels count into 32 16-bit counters per LANE in LDS (15 cells x matched / unmatched, two tallies), as k_sbs_count does,
-// summed per workgroup at the end.
+// Both kernels count into 32 lane-private bins (15 cells x matched / unmatched, two tallies: lane_hist.h).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -14,7 +13,7 @@
 
 #include "compare.h"
 #include "ctx.h"
-#include "plan_gpu.h"
+#include "lane_hist.h"
 
 namespace msim {
 
@@ -31,9 +30,9 @@ struct Held {                                  // msim_cmp_hold's copy of one co
 
 struct CompareState {
     std::vector<Held> held;                    // by contig index
-    unsigned long long *d_out = nullptr;       // CMP_SLOTS x (A's counters, B's counters)
+    unsigned long long *d_out = nullptr;       // HIST_SLOTS x (A's counters, B's counters)
     unsigned long long *h_out = nullptr;       // pinned copy of them
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair tm;
     double kernel_ms = 0;
 };
 
@@ -44,45 +43,23 @@ constexpr uint32_t CMP_PASS = LANES;                       // records of a workg
 static_assert(CMP_PASS == MSIM_CMP_PASS, "msim.h and compare.hip must agree on the pass");
 static_assert((1u << cmp::WINDOW_SHIFT) == MSIM_CMP_WINDOW, "msim.h and compare.h must agree on the window");
 constexpr unsigned CMP_MAX_BLOCKS = 2048;                  // more passes than that stride: eight workgroups a CU (16 KB of LDS each)
-constexpr int CMP_BINS = (int)cmp::COUNTERS, CMP_WORDS = CMP_BINS / 2;
-constexpr int CMP_SLOTS = 16;                              // copies of the result the workgroups' final adds spread over
-constexpr size_t OUT_WORDS = (size_t)CMP_SLOTS * 2 * CMP_BINS;
-static_assert(CMP_BINS % 2 == 0 && 2 * CMP_BINS <= LANES, "two counters a word, one lane per counter and half at the end");
+constexpr int CMP_BINS = (int)cmp::COUNTERS;
+constexpr size_t OUT_WORDS = (size_t)HIST_SLOTS * 2 * CMP_BINS;
 static_assert(sizeof(msim_record) == sizeof(uint4), "a record is one 16-byte load");
 
-// Lane-private counters: a table has fewer than 2^31 records, so fewer than 2^23 passes; beyond CMP_MAX_BLOCKS passes the grid
-// strides, a workgroup takes at most 4096 of them and a lane adds at most once per counter and pass: 16 bits hold it.
-__device__ __forceinline__ void count(uint32_t (*cnt)[LANES], uint32_t bin) {
-    atomicAdd(&cnt[bin >> 1][threadIdx.x], 1u << (16 * (bin & 1)));
-}
-
-// the workgroup's counters summed into its slot of `out` (CMP_BINS words a slot)
-__device__ __forceinline__ void flush_counters(uint32_t (*cnt)[LANES], uint32_t (*part)[CMP_BINS], unsigned long long *__restrict__ out) {
-    __syncthreads();
-    if (threadIdx.x < 2 * CMP_BINS) {                      // counter t (or t - CMP_BINS) over one half of the columns, rotated
-        const int half = threadIdx.x >= CMP_BINS ? 1 : 0, bn = (int)threadIdx.x - half * CMP_BINS;
-        uint32_t s = 0;
-#pragma unroll 8
-        for (int i = 0; i < LANES / 2; i++)
-            s += (cnt[bn >> 1][half * (LANES / 2) + ((i + (int)threadIdx.x) & (LANES / 2 - 1))] >> (16 * (bn & 1))) & 0xffffu;
-        part[half][bn] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < CMP_BINS) {
-        const uint32_t total = part[0][threadIdx.x] + part[1][threadIdx.x];
-        if (total) atomicAdd(&out[(blockIdx.x & (CMP_SLOTS - 1)) * 2 * CMP_BINS + threadIdx.x], (unsigned long long)total);
-    }
-}
+// 32 lane-private bins, summed in two halves into the workgroup's slot of `out`: 2 x CMP_BINS words a slot, A's counters in
+// front of B's (lane_hist.h).  A table has fewer than 2^31 records, so fewer than 2^23 passes; beyond CMP_MAX_BLOCKS passes the
+// grid strides, a workgroup takes at most 4096 of them and a lane adds at most once per counter and pass: 16 bits hold it.
+using CmpHist = LaneHist<CMP_BINS, LANES, 2>;
+__device__ __forceinline__ unsigned long long *slot_of(unsigned long long *out) { return out + (blockIdx.x & (HIST_SLOTS - 1)) * 2 * CMP_BINS; }
 
 // flag_b was zeroed before the launch.  Every index below is checked against its table's size; the bases are read inside
 // [0, L) only, the pools inside their lengths (compare.h: walkable, same).
 __global__ __launch_bounds__(LANES) void k_cmp_match(const uint8_t *__restrict__ g, uint64_t L, cmp::Table A, cmp::Table B, uint32_t exact,
                                                      uint64_t n_pass, uint8_t *__restrict__ flag_a, uint8_t *__restrict__ flag_b,
                                                      unsigned long long *__restrict__ out) {
-    __shared__ uint32_t cnt[CMP_WORDS][LANES];
-    __shared__ uint32_t part[2][CMP_BINS];
-#pragma unroll
-    for (int w = 0; w < CMP_WORDS; w++) cnt[w][threadIdx.x] = 0;   // (a lane's own column: no barrier before its adds)
+    __shared__ CmpHist hist;
+    hist.zero();
     for (uint64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
         const uint64_t i = pass * CMP_PASS + threadIdx.x;
         if (i >= A.n) continue;
@@ -92,26 +69,24 @@ __global__ __launch_bounds__(LANES) void k_cmp_match(const uint8_t *__restrict__
         const int64_t j = cmp::partner(g, L, A, i, B, exact != 0, &s);
         flag_a[i] = j >= 0 ? 1 : 0;
         if (j >= 0 && (uint64_t)j < B.n) flag_b[j] = 1;    // a plain byte store: this lane is the only one with this partner
-        count(cnt, 2 * cmp::cell_of(a) + (j >= 0 ? 0u : 1u));
-        if (s.stops & cmp::STOP_WINDOW) count(cnt, 2 * cmp::CELLS);
-        if (s.stops & cmp::STOP_BASE) count(cnt, 2 * cmp::CELLS + 1);
+        hist.add(2 * cmp::cell_of(a) + (j >= 0 ? 0u : 1u), 1u);
+        if (s.stops & cmp::STOP_WINDOW) hist.add(2 * cmp::CELLS, 1u);
+        if (s.stops & cmp::STOP_BASE) hist.add(2 * cmp::CELLS + 1, 1u);
     }
-    flush_counters(cnt, part, out);
+    hist.flush(slot_of(out));
 }
 
 __global__ __launch_bounds__(LANES) void k_cmp_tally(const msim_record *__restrict__ recs, uint64_t n_rec, uint64_t n_pass,
                                                      const uint8_t *__restrict__ flag, unsigned long long *__restrict__ out) {
-    __shared__ uint32_t cnt[CMP_WORDS][LANES];
-    __shared__ uint32_t part[2][CMP_BINS];
-#pragma unroll
-    for (int w = 0; w < CMP_WORDS; w++) cnt[w][threadIdx.x] = 0;
+    __shared__ CmpHist hist;
+    hist.zero();
     for (uint64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
         const uint64_t i = pass * CMP_PASS + threadIdx.x;
         if (i >= n_rec) continue;
         const cmp::Rec b = cmp::rec_at(recs, i);
-        if (cmp::known_type(b.type)) count(cnt, 2 * cmp::cell_of(b) + (flag[i] ? 0u : 1u));
+        if (cmp::known_type(b.type)) hist.add(2 * cmp::cell_of(b) + (flag[i] ? 0u : 1u), 1u);
     }
-    flush_counters(cnt, part, out);
+    hist.flush(slot_of(out));
 }
 
 // counters[0]: A's (matched / missed per cell, the two tallies), counters[1]: B's (matched / extra per cell)
@@ -133,8 +108,7 @@ int state_of(Ctx *c, CompareState **out) {
         c->compare = S;
         MSIM_HIP(c, hipMalloc((void **)&S->d_out, OUT_WORDS * sizeof(unsigned long long)));
         MSIM_HIP(c, hipHostMalloc((void **)&S->h_out, OUT_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
-        MSIM_HIP(c, hipEventCreate(&S->e0));
-        MSIM_HIP(c, hipEventCreate(&S->e1));
+        MSIM_HIP(c, S->tm.create());
     }
     *out = c->compare;
     return MSIM_OK;
@@ -144,26 +118,6 @@ void held_free(Held &h) {
     void *bufs[] = {h.d_recs, h.d_pool, h.d_flag_a, h.d_flag_b};
     for (void *p : bufs) if (p) (void)hipFree(p);
     h = Held{};
-}
-
-int flushed(Ctx *c) {
-    int rc = flush_deferred_apply(c);
-    if (!rc && c->fast) rc = fast_plan_flush(c);
-    if (!rc && c->gpu) rc = gpu_emit_flush(c);
-    return rc;
-}
-
-// the planned contig `contig` of a device context, everything enqueued on it complete
-int planned_contig(Ctx *c, int contig, Contig **out) {
-    int rc = flushed(c);
-    if (rc) return rc;
-    if (c->host_only) return fail(c, MSIM_ERR_HIP, "host-only context: this call needs the GPU");
-    if (contig < 0 || (size_t)contig >= c->contigs.size()) return fail(c, MSIM_ERR_ARG, "no such contig");
-    Contig &g = c->contigs[(size_t)contig];
-    if (!g.planned) return fail(c, MSIM_ERR_ARG, "contig has not been planned");
-    if ((rc = ctx_drain(c))) return rc;                    // the table's last bytes come from the emit stream
-    *out = &g;
-    return MSIM_OK;
 }
 
 Held *held_of(Ctx *c, int contig) {
@@ -185,7 +139,7 @@ int counts_device(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32_t fl
         const cmp::Table B{g.d_recs, g.n_rec, g.pool_len ? g.d_pool + PAD : nullptr, g.pool_len};
         const uint64_t pass_a = (h.n_rec + CMP_PASS - 1) / CMP_PASS, pass_b = (g.n_rec + CMP_PASS - 1) / CMP_PASS;
         MSIM_HIP(c, hipMemsetAsync(S->d_out, 0, OUT_WORDS * sizeof(unsigned long long), c->stream));
-        MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+        MSIM_HIP(c, S->tm.begin(c->stream));
         if (g.n_rec) MSIM_HIP(c, hipMemsetAsync(h.d_flag_b, 0, (size_t)g.n_rec, c->stream));
         if (h.n_rec) {
             hipLaunchKernelGGL(k_cmp_match, dim3((unsigned)std::min<uint64_t>(pass_a, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
@@ -197,14 +151,14 @@ int counts_device(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32_t fl
                                (const msim_record *)g.d_recs, g.n_rec, pass_b, (const uint8_t *)h.d_flag_b, S->d_out + CMP_BINS);
             MSIM_HIP(c, hipGetLastError());
         }
-        MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+        MSIM_HIP(c, S->tm.end(c->stream));                  // (in front of the copy: the kernels alone)
         MSIM_HIP(c, hipMemcpyAsync(S->h_out, S->d_out, OUT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         MSIM_HIP(c, wait_stream(c->stream));
-        float ms = 0;
-        MSIM_HIP(c, hipEventElapsedTime(&ms, S->e0, S->e1));
-        S->kernel_ms += ms;
-        for (int s = 0; s < CMP_SLOTS; s++)
-            cmp_finish(S->h_out + (size_t)s * 2 * CMP_BINS, S->h_out + (size_t)s * 2 * CMP_BINS + CMP_BINS, counts, tallies);
+        const int rc = S->tm.add_elapsed(c, &S->kernel_ms);
+        if (rc) return rc;
+        unsigned long long bins[2 * CMP_BINS];
+        hist_sum_slots(S->h_out, 2 * CMP_BINS, bins, 2 * CMP_BINS);
+        cmp_finish(bins, bins + CMP_BINS, counts, tallies);
     }
     h.counted = true;
     return MSIM_OK;
@@ -224,8 +178,7 @@ void compare_state_destroy(Ctx *c) {
     compare_drop_all(c);
     if (S->d_out) (void)hipFree(S->d_out);
     if (S->h_out) (void)hipHostFree(S->h_out);
-    if (S->e0) (void)hipEventDestroy(S->e0);
-    if (S->e1) (void)hipEventDestroy(S->e1);
+    S->tm.destroy();
     delete S;
     c->compare = nullptr;
 }
@@ -246,7 +199,7 @@ int msim_cmp_hold(msim_ctx *p, int contig) {
     Ctx *c = reinterpret_cast<Ctx *>(p);
     if (!c) return MSIM_ERR_ARG;
     Contig *g;
-    int rc = planned_contig(c, contig, &g);
+    int rc = ctx_device_contig(c, contig, true, &g);
     if (rc) return rc;
     CompareState *S;
     if ((rc = state_of(c, &S))) return rc;
@@ -284,7 +237,7 @@ int msim_cmp_counts(msim_ctx *p, int contig, uint32_t flags, uint64_t *counts, u
     if (!c || !counts || !tallies) return MSIM_ERR_ARG;
     if (flags & ~(uint32_t)MSIM_CMP_EXACT) return fail(c, MSIM_ERR_ARG, "unknown compare flag");
     Contig *g;
-    int rc = planned_contig(c, contig, &g);
+    int rc = ctx_device_contig(c, contig, true, &g);
     if (rc) return rc;
     Held *h = held_of(c, contig);
     if (!h) return fail(c, MSIM_ERR_ARG, "contig has no held table (msim_cmp_hold)");
@@ -331,25 +284,14 @@ int msim_dbg_cmp_copy_floor(msim_ctx *p, int contig, double *ms) {
     Ctx *c = reinterpret_cast<Ctx *>(p);
     if (!c || !ms) return MSIM_ERR_ARG;
     Contig *g;
-    int rc = planned_contig(c, contig, &g);
+    int rc = ctx_device_contig(c, contig, true, &g);
     if (rc) return rc;
     Held *h = held_of(c, contig);
     if (!h) return fail(c, MSIM_ERR_ARG, "contig has no held table (msim_cmp_hold)");
-    *ms = 0;
-    if (!h->n_rec && !g->n_rec) return MSIM_OK;
     CompareState *S;
     if ((rc = state_of(c, &S))) return rc;
-    const size_t bytes_a = (size_t)h->n_rec * sizeof(msim_record), bytes_b = (size_t)g->n_rec * sizeof(msim_record);
-    if ((rc = ensure_scratch(c, bytes_a + bytes_b))) return rc;
-    MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
-    if (bytes_a) MSIM_HIP(c, hipMemcpyAsync(c->d_scratch, h->d_recs, bytes_a, hipMemcpyDeviceToDevice, c->stream));
-    if (bytes_b) MSIM_HIP(c, hipMemcpyAsync((uint8_t *)c->d_scratch + bytes_a, g->d_recs, bytes_b, hipMemcpyDeviceToDevice, c->stream));
-    MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
-    MSIM_HIP(c, wait_stream(c->stream));
-    float t = 0;
-    MSIM_HIP(c, hipEventElapsedTime(&t, S->e0, S->e1));
-    *ms = t;
-    return MSIM_OK;
+    const CopySource tables[2] = {{h->d_recs, (size_t)h->n_rec * sizeof(msim_record)}, {g->d_recs, (size_t)g->n_rec * sizeof(msim_record)}};
+    return copy_floor(c, S->tm, tables, 2, ms);
 }
 
 // ---- sequential host restatement: no context, no GPU -------------------------------------------------------------------

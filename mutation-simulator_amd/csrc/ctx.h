@@ -177,6 +177,37 @@ double wait_limit_seconds();
 int flush_deferred_apply(Ctx *c, bool only_groups = false);
 bool deferred_apply_holds(const Ctx *c, int contig);
 
+// msim_api.hip: what every entry point that needs a result sends out first, in this order -- the deferred APPLY, the counter-based
+// engine's queued plans (as one batch), the SNP sampler's waiting emission group
+int ctx_flush_queued(Ctx *c);
+// ... and the rest of a device call's prologue: the queues flushed, a GPU context, a contig of that index; need_planned: the
+// contig planned and the context drained (the table's last bytes come from the emit stream)
+int ctx_device_contig(Ctx *c, int contig, bool need_planned, Contig **out);
+
+// Kernel time by two HIP events on one stream.  end() goes where the caller's stretch ends -- in front of a result's copy to
+// the host or behind it -- and add_elapsed() follows the caller's own wait for that stream.
+struct EventPair {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    hipError_t create() { const hipError_t e = hipEventCreate(&e0); return e != hipSuccess ? e : hipEventCreate(&e1); }
+    void destroy() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        e0 = e1 = nullptr;
+    }
+    hipError_t begin(hipStream_t s) const { return hipEventRecord(e0, s); }
+    hipError_t end(hipStream_t s) const { return hipEventRecord(e1, s); }
+    int add_elapsed(Ctx *c, double *acc) const {
+        float ms = 0;
+        MSIM_HIP(c, hipEventElapsedTime(&ms, e0, e1));
+        *acc += ms;
+        return MSIM_OK;
+    }
+};
+// measurement support (msim_dbg_*_copy_floor): device-to-device copies of the sources, one behind the other, into the context's
+// scratch, timed by `tm` -- the streaming floor a counting kernel is held against.  *ms = 0 where there is nothing to copy.
+struct CopySource { const void *src; size_t bytes; };
+int copy_floor(Ctx *c, const EventPair &tm, const CopySource *srcs, int n_srcs, double *ms);
+
 // msim_api.hip: what the VCF replay (vcf_parse.hip) shares with the planners' installation path
 int ctx_drain(Ctx *c);                // everything enqueued has completed, deferred results collected
 void contig_reset(Contig &g);         // forget a contig's plan / apply results (buffers stay allocated)

@@ -137,6 +137,40 @@ int flush_deferred_apply(Ctx *c, bool only_groups) {
     }
     return MSIM_OK;
 }
+int ctx_flush_queued(Ctx *c) {
+    int rc = flush_deferred_apply(c);
+    if (!rc && c->fast) rc = fast_plan_flush(c);           // (fast contexts: the plans queued so far, as one batch)
+    if (!rc && c->gpu) rc = gpu_emit_flush(c);             // (SNP sampler: the emission group that is still waiting)
+    return rc;
+}
+int ctx_device_contig(Ctx *c, int contig, bool need_planned, Contig **out) {
+    int rc = ctx_flush_queued(c);
+    if (rc) return rc;
+    if (c->host_only) return fail(c, MSIM_ERR_HIP, "host-only context: this call needs the GPU");
+    if (contig < 0 || (size_t)contig >= c->contigs.size()) return fail(c, MSIM_ERR_ARG, "no such contig");
+    Contig &g = c->contigs[(size_t)contig];
+    if (need_planned) {
+        if (!g.planned) return fail(c, MSIM_ERR_ARG, "contig has not been planned");
+        if ((rc = ctx_drain(c))) return rc;
+    }
+    *out = &g;
+    return MSIM_OK;
+}
+int copy_floor(Ctx *c, const EventPair &tm, const CopySource *srcs, int n_srcs, double *ms) {
+    *ms = 0;
+    size_t total = 0;
+    for (int i = 0; i < n_srcs; i++) total += srcs[i].bytes;
+    if (!total) return MSIM_OK;
+    const int rc = ensure_scratch(c, total);
+    if (rc) return rc;
+    MSIM_HIP(c, tm.begin(c->stream));
+    uint8_t *dst = (uint8_t *)c->d_scratch;
+    for (int i = 0; i < n_srcs; dst += srcs[i++].bytes)
+        if (srcs[i].bytes) MSIM_HIP(c, hipMemcpyAsync(dst, srcs[i].src, srcs[i].bytes, hipMemcpyDeviceToDevice, c->stream));
+    MSIM_HIP(c, tm.end(c->stream));
+    MSIM_HIP(c, wait_stream(c->stream));
+    return tm.add_elapsed(c, ms);
+}
 static int key_error_of(Ctx *c, Contig &g) {
     g.key_reported = true;
     return fail(c, MSIM_ERR_KEY, std::string("KeyError: '") + (char)g.key_base + "'");
@@ -329,9 +363,7 @@ static Ctx *C(msim_ctx *p) { return reinterpret_cast<Ctx *>(p); }
 #define CTX_FLUSHED(c, p)                                   \
     Ctx *c = C(p);                                          \
     if (c) {                                                \
-        int flush_rc_ = flush_deferred_apply(c);            \
-        if (!flush_rc_ && c->fast) flush_rc_ = fast_plan_flush(c);   /* (fast contexts: the plans queued so far, as one batch) */ \
-        if (!flush_rc_ && c->gpu) flush_rc_ = gpu_emit_flush(c);     /* (SNP sampler: the emission group that is still waiting) */ \
+        const int flush_rc_ = ctx_flush_queued(c);          \
         if (flush_rc_) return flush_rc_;                    \
     }
 #define NEED_GPU(c) do { if ((c)->host_only) return fail((c), MSIM_ERR_HIP, "host-only context: this call needs the GPU"); } while (0)

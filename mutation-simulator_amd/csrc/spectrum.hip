@@ -3,9 +3,8 @@
 // the arithmetic is spectrum.h's, shared with the host restatements at the end of this file.
 //
 // Device path (gfx950), everything on the context's stream:
-//   census   k_ctx_census: 16 bases a lane by one 16-byte load + the two halo bytes, 64 16-bit counters per LANE in LDS (no
-//            two lanes share a word or, within a wave, a bank), summed per workgroup at the end: one device-scope add per
-//            bin and workgroup
+//   census   k_ctx_census: 16 bases a lane by one 16-byte load + the two halo bytes, counted into 64 lane-private bins
+//            (lane_hist.h)
 //   plan     k_spectrum_draw: a tile of MSIM_SPECTRUM_TILE bases a workgroup; per site the context, the Philox draw (one
 //            call per two sites) and the compare against the context's last threshold (64 x 8 B in LDS; the other two are
 //            read on a hit only) -> per lane a 32-bit OUTCOME word (2 bits a site), per tile the hit count
@@ -13,15 +12,15 @@
 //            k_spectrum_emit: reads the outcome words only -- no base, no draw a second time -- and stores the records at
 //            tile offset + prefix of the lanes in front (wave scan by shuffles + the waves' sums), 16 bytes a store
 //   profile  k_sbs_count (msim_sbs_counts), the sampler's inverse: one 16-byte record a lane and step, the three bases around an
-//            SN record's position gathered from the resident contig, 104 16-bit counters per LANE in LDS (96 channels + 8
-//            tallies) as in the census, summed per workgroup at the end
+//            SN record's position gathered from the resident contig, counted into 104 lane-private bins (96 channels + 8
+//            tallies: lane_hist.h)
 // The host waits once between scan and emit: the record table is allocated at its exact size.
 #include <algorithm>
 #include <cstring>
 #include <string>
 
 #include "ctx.h"
-#include "plan_gpu.h"
+#include "lane_hist.h"
 #include "scan_kernels.h"
 #include "spectrum.h"
 
@@ -32,14 +31,14 @@ using fastrng::U4;
 
 struct SpectrumState {
     unsigned long long *d_counts = nullptr;   // 64 census bins
-    unsigned long long *d_sbs = nullptr;      // SBS_SLOTS x 104 profile bins (spectrum::SBS_BINS)
+    unsigned long long *d_sbs = nullptr;      // HIST_SLOTS x 104 profile bins (spectrum::SBS_BINS)
     unsigned long long *h_sbs = nullptr;      // pinned copy of them
     uint64_t *d_thr = nullptr;                // 192 thresholds
     uint32_t *d_words = nullptr;              // one outcome word per lane of every tile
     uint32_t *d_tile = nullptr;               // hits per tile, then their exclusive scan; [n_tiles]: the total
     size_t cap_words = 0, cap_tile = 0;
     unsigned long long *h_pin = nullptr;      // pinned: [0..63] census bins / [0..191] thresholds on their way up, [192] the total
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair tm;
     double census_ms = 0, plan_ms = 0, sbs_ms = 0;
 };
 
@@ -84,17 +83,13 @@ __device__ __forceinline__ bool site_ctx(const uint32_t code[SITES + 2], int i, 
     return ((code[i] | code[i + 1] | code[i + 2]) & spectrum::CODE_INVALID) == 0;
 }
 
-// Every lane counts into 64 16-bit counters of its own (two bins a word, the lane's column of `cnt`): no two lanes share a
-// word and a wave's 64 adds go to 64 different banks, so an add is one conflict-free ds_add whatever the genome holds -- a
-// homopolymer run costs what random bases cost.  A workgroup takes at most 512 tiles (the grid stops at CENSUS_MAX_BLOCKS only
-// beyond that many tiles in all, and a contig has fewer than 2^20), 16 sites a lane each: 8192 a counter at most.
+// 64 lane-private bins, summed in four quarters into the one copy of the result (lane_hist.h).  A workgroup takes at most 512
+// tiles (the grid stops at CENSUS_MAX_BLOCKS only beyond that many tiles in all, and a contig has fewer than 2^20), 16 sites a
+// lane each: 8192 a counter at most.
 __global__ __launch_bounds__(LANES) void k_ctx_census(const uint8_t *__restrict__ b, uint64_t L, uint64_t n_tiles,
                                                       unsigned long long *__restrict__ counts) {
-    __shared__ uint32_t cnt[32][LANES];
-    __shared__ uint32_t part[LANES / 64][64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int w = 0; w < 32; w++) cnt[w][threadIdx.x] = 0;  // (a lane's own column: no barrier before its adds)
+    __shared__ LaneHist<64, LANES, 4> hist;
+    hist.zero();
     // CENSUS_AHEAD tiles a round, all their loads in flight before the first is counted (16 waves a CU with one 16-byte load
     // each are little for the memory system to work on; measured it is worth 2 %: the decode below bounds the kernel, NOTES 20)
     for (uint64_t first = blockIdx.x; first < n_tiles; first += (uint64_t)gridDim.x * CENSUS_AHEAD) {
@@ -112,23 +107,11 @@ __global__ __launch_bounds__(LANES) void k_ctx_census(const uint8_t *__restrict_
             for (int i = 0; i < SITES; i++) {
                 uint32_t ctx;
                 const uint32_t one = site_ctx(code, i, ctx) ? 1u : 0u;
-                atomicAdd(&cnt[ctx >> 1][threadIdx.x], one << (16 * (ctx & 1)));
+                hist.add(ctx, one);
             }
         }
     }
-    __syncthreads();
-    // bin `lane` over the 64 columns of quarter `wave`: the rotation keeps a wave's 64 reads on 64 banks
-    uint32_t s = 0;
-#pragma unroll 8
-    for (int i = 0; i < 64; i++) s += (cnt[lane >> 1][wave * 64 + ((i + lane) & 63)] >> (16 * (lane & 1))) & 0xffffu;
-    part[wave][lane] = s;
-    __syncthreads();
-    if (threadIdx.x < 64) {
-        uint32_t total = 0;
-#pragma unroll
-        for (int w = 0; w < LANES / 64; w++) total += part[w][threadIdx.x];
-        if (total) atomicAdd(&counts[threadIdx.x], (unsigned long long)total);
-    }
+    hist.flush(counts);
 }
 
 __global__ __launch_bounds__(LANES) void k_spectrum_draw(const uint8_t *__restrict__ b, uint64_t L, const uint64_t *__restrict__ thr,
@@ -205,8 +188,7 @@ constexpr uint32_t SBS_PASS = LANES * SBS_AHEAD;            // records of a work
 static_assert(SBS_PASS == MSIM_SBS_PASS, "msim.h and spectrum.hip must agree on the pass");
 constexpr unsigned SBS_MAX_BLOCKS = 512;                    // more passes than that stride (k_sbs_count counts on it); two workgroups a CU:
                                                             // every workgroup pays for zeroing and summing 52 KB of counters (NOTES 21)
-constexpr int SBS_BINS = (int)spectrum::SBS_BINS, SBS_WORDS = SBS_BINS / 2;
-constexpr int SBS_SLOTS = 16;                               // copies of the result the workgroups' final adds spread over (k_sbs_count)
+constexpr int SBS_BINS = (int)spectrum::SBS_BINS;
 static_assert(sizeof(msim_record) == sizeof(uint4), "a record is one 16-byte load");
 
 // The bin of one record ({pos, stop, extra, type | aux << 8 | rsv << 16}): an SN record's channel, 96 (tallies[0]) for an SN
@@ -224,18 +206,14 @@ __device__ __forceinline__ uint32_t sbs_bin(const uint8_t *__restrict__ b, uint6
     return bin;
 }
 
-// Lane-private counters as in k_ctx_census: 104 16-bit bins a lane, two a word, the lane's column of `cnt` (52 KB a workgroup,
-// three workgroups a CU) -- an add is one conflict-free ds_add wherever the records fall, and a real spectrum puts most of
-// them into a handful of channels.  A table has fewer than 2^31 records, so fewer than 2^21 passes; the grid stops at
-// SBS_MAX_BLOCKS only beyond that many passes: a workgroup takes at most 4096 of them, SBS_AHEAD records a lane each -- 16 384
-// a counter at most, whatever the table holds.  The workgroups' final adds go to SBS_SLOTS copies of the result (the host sums
-// them): on one copy, 96 busy channels cost 96 adds to the same few lines per workgroup and a one-channel table ran faster.
+// 104 lane-private bins, summed in two halves into the workgroup's slot of `out` (lane_hist.h; 52 KB a workgroup, three
+// workgroups a CU) -- a real spectrum puts most records into a handful of channels.  A table has fewer than 2^31 records, so
+// fewer than 2^21 passes; the grid stops at SBS_MAX_BLOCKS only beyond that many passes: a workgroup takes at most 4096 of
+// them, SBS_AHEAD records a lane each -- 16 384 a counter at most, whatever the table holds.
 __global__ __launch_bounds__(LANES) void k_sbs_count(const uint8_t *__restrict__ b, uint64_t L, const uint4 *__restrict__ recs,
                                                      uint64_t n_rec, uint64_t n_pass, unsigned long long *__restrict__ out) {
-    __shared__ uint32_t cnt[SBS_WORDS][LANES];
-    __shared__ uint32_t part[2][SBS_BINS];
-#pragma unroll
-    for (int w = 0; w < SBS_WORDS; w++) cnt[w][threadIdx.x] = 0;   // (a lane's own column: no barrier before its adds)
+    __shared__ LaneHist<SBS_BINS, LANES, 2> hist;
+    hist.zero();
     for (uint64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
         uint4 rec[SBS_AHEAD];
 #pragma unroll
@@ -247,30 +225,15 @@ __global__ __launch_bounds__(LANES) void k_sbs_count(const uint8_t *__restrict__
 #pragma unroll
         for (int k = 0; k < SBS_AHEAD; k++) bin[k] = sbs_bin(b, L, rec[k], &one[k]);
 #pragma unroll
-        for (int k = 0; k < SBS_AHEAD; k++) atomicAdd(&cnt[bin[k] >> 1][threadIdx.x], one[k] << (16 * (bin[k] & 1)));
+        for (int k = 0; k < SBS_AHEAD; k++) hist.add(bin[k], one[k]);
     }
-    __syncthreads();
-    // bin t (or t - 104) over one half of the columns: the rotation keeps a wave's 64 reads on 64 banks
-    if (threadIdx.x < 2 * SBS_BINS) {
-        const int half = threadIdx.x >= SBS_BINS ? 1 : 0, bn = (int)threadIdx.x - half * SBS_BINS;
-        uint32_t s = 0;
-#pragma unroll 8
-        for (int i = 0; i < LANES / 2; i++)
-            s += (cnt[bn >> 1][half * (LANES / 2) + ((i + (int)threadIdx.x) & (LANES / 2 - 1))] >> (16 * (bn & 1))) & 0xffffu;
-        part[half][bn] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < SBS_BINS) {
-        const uint32_t total = part[0][threadIdx.x] + part[1][threadIdx.x];
-        if (total) atomicAdd(&out[(blockIdx.x & (SBS_SLOTS - 1)) * SBS_BINS + threadIdx.x], (unsigned long long)total);
-    }
+    hist.flush(out + (blockIdx.x & (HIST_SLOTS - 1)) * SBS_BINS);
 }
 
 // bins 0..95 the channels, 96.. the tallies; tallies[1] = every SN record = the channels' sum + tallies[0]
 void sbs_finish(const unsigned long long *slots, uint64_t channels[96], uint64_t tallies[8]) {
-    unsigned long long bins[SBS_BINS] = {};
-    for (int s = 0; s < SBS_SLOTS; s++)
-        for (int i = 0; i < SBS_BINS; i++) bins[i] += slots[s * SBS_BINS + i];
+    unsigned long long bins[SBS_BINS];
+    hist_sum_slots(slots, SBS_BINS, bins, SBS_BINS);
     uint64_t sn = bins[96];
     for (int i = 0; i < 96; i++) { channels[i] = bins[i]; sn += bins[i]; }
     for (int t = 0; t < 8; t++) tallies[t] = bins[96 + t];
@@ -284,43 +247,36 @@ int state_of(Ctx *c, SpectrumState **out) {
         SpectrumState *S = new SpectrumState;
         c->spectrum = S;
         MSIM_HIP(c, hipMalloc((void **)&S->d_counts, 64 * sizeof(unsigned long long)));
-        MSIM_HIP(c, hipMalloc((void **)&S->d_sbs, SBS_SLOTS * SBS_BINS * sizeof(unsigned long long)));
-        MSIM_HIP(c, hipHostMalloc((void **)&S->h_sbs, SBS_SLOTS * SBS_BINS * sizeof(unsigned long long), hipHostMallocDefault));
+        MSIM_HIP(c, hipMalloc((void **)&S->d_sbs, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long)));
+        MSIM_HIP(c, hipHostMalloc((void **)&S->h_sbs, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long), hipHostMallocDefault));
         MSIM_HIP(c, hipMalloc((void **)&S->d_thr, 192 * sizeof(uint64_t)));
         MSIM_HIP(c, hipHostMalloc((void **)&S->h_pin, 193 * sizeof(unsigned long long), hipHostMallocDefault));
-        MSIM_HIP(c, hipEventCreate(&S->e0));
-        MSIM_HIP(c, hipEventCreate(&S->e1));
+        MSIM_HIP(c, S->tm.create());
     }
     *out = c->spectrum;
     return MSIM_OK;
 }
 
-// end of a timed stretch (begun by a record of e0): wait for the stream, add the kernels' time
+// end of a timed stretch (begun by tm.begin) that has its copy to the host inside: wait for the stream, add the time
 int stretch_end(Ctx *c, SpectrumState *S, double *acc) {
-    MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+    MSIM_HIP(c, S->tm.end(c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
-    float ms = 0;
-    MSIM_HIP(c, hipEventElapsedTime(&ms, S->e0, S->e1));
-    *acc += ms;
-    return MSIM_OK;
+    return S->tm.add_elapsed(c, acc);
 }
 
 int census_device(Ctx *c, SpectrumState *S, const Contig &g, uint64_t counts[64]) {
     const uint64_t n_tiles = tiles_of(g.len);
     if (!n_tiles) { memset(counts, 0, 64 * sizeof(uint64_t)); return MSIM_OK; }
     MSIM_HIP(c, hipMemsetAsync(S->d_counts, 0, 64 * sizeof(unsigned long long), c->stream));
-    MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+    MSIM_HIP(c, S->tm.begin(c->stream));
     const unsigned blocks = (unsigned)std::min<uint64_t>(n_tiles, CENSUS_MAX_BLOCKS);
     hipLaunchKernelGGL(k_ctx_census, dim3(blocks), dim3(LANES), 0, c->stream, g.d_in + PAD, g.len, n_tiles, S->d_counts);
     MSIM_HIP(c, hipGetLastError());
-    MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+    MSIM_HIP(c, S->tm.end(c->stream));                      // (in front of the copy: the kernel alone)
     MSIM_HIP(c, hipMemcpyAsync(S->h_pin, S->d_counts, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
-    float ms = 0;
-    MSIM_HIP(c, hipEventElapsedTime(&ms, S->e0, S->e1));
-    S->census_ms += ms;
     for (int i = 0; i < 64; i++) counts[i] = S->h_pin[i];
-    return MSIM_OK;
+    return S->tm.add_elapsed(c, &S->census_ms);
 }
 
 // the contig's ACTIVE table (the caller drained the context: the table is complete, its size collected, nothing writes it)
@@ -329,20 +285,17 @@ int sbs_device(Ctx *c, SpectrumState *S, const Contig &g, uint64_t channels[96],
     memset(tallies, 0, 8 * sizeof(uint64_t));
     if (!g.n_rec) return MSIM_OK;
     const uint64_t n_pass = (g.n_rec + SBS_PASS - 1) / SBS_PASS;
-    MSIM_HIP(c, hipMemsetAsync(S->d_sbs, 0, SBS_SLOTS * SBS_BINS * sizeof(unsigned long long), c->stream));
-    MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+    MSIM_HIP(c, hipMemsetAsync(S->d_sbs, 0, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long), c->stream));
+    MSIM_HIP(c, S->tm.begin(c->stream));
     const unsigned blocks = (unsigned)std::min<uint64_t>(n_pass, SBS_MAX_BLOCKS);
     hipLaunchKernelGGL(k_sbs_count, dim3(blocks), dim3(LANES), 0, c->stream, g.d_in + PAD, g.len,
                        reinterpret_cast<const uint4 *>(g.d_recs), g.n_rec, n_pass, S->d_sbs);
     MSIM_HIP(c, hipGetLastError());
-    MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
-    MSIM_HIP(c, hipMemcpyAsync(S->h_sbs, S->d_sbs, SBS_SLOTS * SBS_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    MSIM_HIP(c, S->tm.end(c->stream));                      // (in front of the copy: the kernel alone)
+    MSIM_HIP(c, hipMemcpyAsync(S->h_sbs, S->d_sbs, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
-    float ms = 0;
-    MSIM_HIP(c, hipEventElapsedTime(&ms, S->e0, S->e1));
-    S->sbs_ms += ms;
     sbs_finish(S->h_sbs, channels, tallies);
-    return MSIM_OK;
+    return S->tm.add_elapsed(c, &S->sbs_ms);
 }
 
 // leaves the contig planned as plan_device (vcf_parse.hip) does: an SNP-only table of host-known size, no insert pool
@@ -361,7 +314,7 @@ int plan_device(Ctx *c, SpectrumState *S, Contig *g, const uint64_t thr[192], ui
         memcpy(S->h_pin, thr, 192 * sizeof(uint64_t));
         MSIM_HIP(c, hipMemcpyAsync(S->d_thr, S->h_pin, 192 * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
         const Key key{(uint32_t)key64, (uint32_t)(key64 >> 32), seq};
-        MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+        MSIM_HIP(c, S->tm.begin(c->stream));
         hipLaunchKernelGGL(k_spectrum_draw, dim3((unsigned)n_tiles), dim3(LANES), 0, c->stream, g->d_in + PAD, g->len, S->d_thr, key,
                            S->d_words, S->d_tile);
         hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, S->d_tile, (uint32_t)n_tiles);
@@ -374,7 +327,7 @@ int plan_device(Ctx *c, SpectrumState *S, Contig *g, const uint64_t thr[192], ui
     if (n_rec) {
         rc = dev_reserve(c, (void **)&g->d_recs, &g->cap_recs, (size_t)n_rec * sizeof(msim_record));
         if (rc) return rc;
-        MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+        MSIM_HIP(c, S->tm.begin(c->stream));
         hipLaunchKernelGGL(k_spectrum_emit, dim3((unsigned)n_tiles), dim3(LANES), 0, c->stream, S->d_words, S->d_tile, g->d_recs);
         MSIM_HIP(c, hipGetLastError());
         if ((rc = stretch_end(c, S, &S->plan_ms))) return rc;
@@ -395,13 +348,6 @@ bool thresholds_ordered(const uint64_t thr[192], int *bad_ctx) {
     return true;
 }
 
-int flushed(Ctx *c) {
-    int rc = flush_deferred_apply(c);
-    if (!rc && c->fast) rc = fast_plan_flush(c);
-    if (!rc && c->gpu) rc = gpu_emit_flush(c);
-    return rc;
-}
-
 }  // namespace
 
 void spectrum_state_destroy(Ctx *c) {
@@ -411,8 +357,7 @@ void spectrum_state_destroy(Ctx *c) {
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (S->h_pin) (void)hipHostFree(S->h_pin);
     if (S->h_sbs) (void)hipHostFree(S->h_sbs);
-    if (S->e0) (void)hipEventDestroy(S->e0);
-    if (S->e1) (void)hipEventDestroy(S->e1);
+    S->tm.destroy();
     delete S;
     c->spectrum = nullptr;
 }
@@ -430,14 +375,13 @@ extern "C" {
 int msim_context_counts(msim_ctx *p, int contig, uint64_t counts[64], uint64_t *n_valid) {
     Ctx *c = reinterpret_cast<Ctx *>(p);
     if (!c || !counts || !n_valid) return MSIM_ERR_ARG;
-    int rc = flushed(c);
+    Contig *g;
+    int rc = ctx_device_contig(c, contig, false, &g);
     if (rc) return rc;
-    if (c->host_only) return fail(c, MSIM_ERR_HIP, "host-only context: this call needs the GPU");
-    if (contig < 0 || (size_t)contig >= c->contigs.size()) return fail(c, MSIM_ERR_ARG, "no such contig");
     SpectrumState *S;
     if ((rc = state_of(c, &S))) return rc;
     TraceRange tr("msim context census");
-    if ((rc = census_device(c, S, c->contigs[(size_t)contig], counts))) return rc;
+    if ((rc = census_device(c, S, *g, counts))) return rc;
     uint64_t n = 0;
     for (int i = 0; i < 64; i++) n += counts[i];
     *n_valid = n;
@@ -447,17 +391,16 @@ int msim_context_counts(msim_ctx *p, int contig, uint64_t counts[64], uint64_t *
 int msim_plan_contig_spectrum(msim_ctx *p, int contig, const uint64_t thr[192], uint64_t key, uint32_t seq) {
     Ctx *c = reinterpret_cast<Ctx *>(p);
     if (!c || !thr) return MSIM_ERR_ARG;
-    int rc = flushed(c);                                   // (a fast context's queue goes out first)
+    Contig *g;
+    int rc = ctx_device_contig(c, contig, false, &g);      // (a fast context's queue goes out first)
     if (rc) return rc;
-    if (c->host_only) return fail(c, MSIM_ERR_HIP, "host-only context: this call needs the GPU");
-    if (contig < 0 || (size_t)contig >= c->contigs.size()) return fail(c, MSIM_ERR_ARG, "no such contig");
     int bad = 0;
     if (!thresholds_ordered(thr, &bad))
         return fail(c, MSIM_ERR_ARG, "spectrum thresholds of context " + std::to_string(bad) + " are not non-decreasing");
     SpectrumState *S;
     if ((rc = state_of(c, &S))) return rc;
     TraceRange tr("msim PLAN contig (spectrum)");
-    return plan_device(c, S, &c->contigs[(size_t)contig], thr, key, seq);
+    return plan_device(c, S, g, thr, key, seq);
 }
 
 int msim_spectrum_timing(msim_ctx *p, double *census_ms, double *plan_ms) {
@@ -473,17 +416,13 @@ int msim_spectrum_timing(msim_ctx *p, double *census_ms, double *plan_ms) {
 int msim_sbs_counts(msim_ctx *p, int contig, uint64_t channels[96], uint64_t tallies[8]) {
     Ctx *c = reinterpret_cast<Ctx *>(p);
     if (!c || !channels || !tallies) return MSIM_ERR_ARG;
-    int rc = flushed(c);
+    Contig *g;
+    int rc = ctx_device_contig(c, contig, true, &g);
     if (rc) return rc;
-    if (c->host_only) return fail(c, MSIM_ERR_HIP, "host-only context: this call needs the GPU");
-    if (contig < 0 || (size_t)contig >= c->contigs.size()) return fail(c, MSIM_ERR_ARG, "no such contig");
-    const Contig &g = c->contigs[(size_t)contig];
-    if (!g.planned) return fail(c, MSIM_ERR_ARG, "contig has not been planned");
-    if ((rc = ctx_drain(c))) return rc;                    // the table's last bytes come from the emit stream
     SpectrumState *S;
     if ((rc = state_of(c, &S))) return rc;
     TraceRange tr("msim SBS-96 profile");
-    return sbs_device(c, S, g, channels, tallies);
+    return sbs_device(c, S, *g, channels, tallies);
 }
 
 int msim_sbs_timing(msim_ctx *p, double *kernel_ms) {
@@ -498,27 +437,13 @@ int msim_sbs_timing(msim_ctx *p, double *kernel_ms) {
 int msim_dbg_sbs_copy_floor(msim_ctx *p, int contig, double *ms) {
     Ctx *c = reinterpret_cast<Ctx *>(p);
     if (!c || !ms) return MSIM_ERR_ARG;
-    int rc = flushed(c);
+    Contig *g;
+    int rc = ctx_device_contig(c, contig, true, &g);
     if (rc) return rc;
-    if (c->host_only) return fail(c, MSIM_ERR_HIP, "host-only context: this call needs the GPU");
-    if (contig < 0 || (size_t)contig >= c->contigs.size()) return fail(c, MSIM_ERR_ARG, "no such contig");
-    const Contig &g = c->contigs[(size_t)contig];
-    if (!g.planned) return fail(c, MSIM_ERR_ARG, "contig has not been planned");
-    if ((rc = ctx_drain(c))) return rc;
-    *ms = 0;
-    if (!g.n_rec) return MSIM_OK;
     SpectrumState *S;
     if ((rc = state_of(c, &S))) return rc;
-    const size_t bytes = (size_t)g.n_rec * sizeof(msim_record);
-    if ((rc = ensure_scratch(c, bytes))) return rc;
-    MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
-    MSIM_HIP(c, hipMemcpyAsync(c->d_scratch, g.d_recs, bytes, hipMemcpyDeviceToDevice, c->stream));
-    MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
-    MSIM_HIP(c, wait_stream(c->stream));
-    float t = 0;
-    MSIM_HIP(c, hipEventElapsedTime(&t, S->e0, S->e1));
-    *ms = t;
-    return MSIM_OK;
+    const CopySource table{g->d_recs, (size_t)g->n_rec * sizeof(msim_record)};
+    return copy_floor(c, S->tm, &table, 1, ms);
 }
 
 // ---- sequential host restatements: no context, no GPU ------------------------------------------------------------------

@@ -53,7 +53,7 @@ struct VcfState {
     uint64_t *d_tile = nullptr;            // 3 x n_tiles: packed sums, the two channels' offsets
     size_t cap_tile = 0;
     unsigned long long *d_mb = nullptr, *h_mb = nullptr;       // 8 words: results of a pass (h_mb pinned)
-    hipEvent_t e0 = nullptr, e1 = nullptr;
+    EventPair tm;
     double load_ms = 0, plan_ms = 0;
     // msim_vcf_select
     uint32_t grammar = 0, sample = 0, hap = 1;
@@ -465,22 +465,14 @@ void free_device(VcfState *S) {
     void *bufs[] = {S->d_text, S->d_ls, S->d_tabcum, S->d_a, S->d_b, S->d_c, S->d_tile, S->d_mb, S->d_cons, S->d_recline};
     for (void *p : bufs) if (p) (void)hipFree(p);
     if (S->h_mb) (void)hipHostFree(S->h_mb);
-    if (S->e0) (void)hipEventDestroy(S->e0);
-    if (S->e1) (void)hipEventDestroy(S->e1);
+    S->tm.destroy();
 }
 
-int elapsed(Ctx *c, VcfState *S, double *acc) {
-    float ms = 0;
-    MSIM_HIP(c, hipEventElapsedTime(&ms, S->e0, S->e1));
-    *acc += ms;
-    return MSIM_OK;
-}
-
-// end of a timed stretch of the load (begun by a record of e0): results back, kernel time added
+// end of a timed stretch of the load (begun by tm.begin): results back, kernel time added
 int phase_end(Ctx *c, VcfState *S) {
-    MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+    MSIM_HIP(c, S->tm.end(c->stream));
     const int rc = fetch_mailbox(c, S);
-    return rc ? rc : elapsed(c, S, &S->load_ms);
+    return rc ? rc : S->tm.add_elapsed(c, &S->load_ms);
 }
 
 // ---- host parser ---------------------------------------------------------------------------------------------------------
@@ -648,8 +640,7 @@ int plan_host_cons(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) {
 int load_device(Ctx *c, VcfState *S, const uint8_t *text, uint64_t n) {
     MSIM_HIP(c, hipHostMalloc((void **)&S->h_mb, 8 * sizeof(unsigned long long), hipHostMallocDefault));
     MSIM_HIP(c, hipMalloc((void **)&S->d_mb, 8 * sizeof(unsigned long long)));
-    MSIM_HIP(c, hipEventCreate(&S->e0));
-    MSIM_HIP(c, hipEventCreate(&S->e1));
+    MSIM_HIP(c, S->tm.create());
     MSIM_HIP(c, hipMalloc((void **)&S->d_text, n + 2 * PAD));
     MSIM_HIP(c, hipMemsetAsync(S->d_text, 0, PAD, c->stream));
     MSIM_HIP(c, hipMemsetAsync(S->d_text + PAD + n, 0, PAD, c->stream));
@@ -665,7 +656,7 @@ int load_device(Ctx *c, VcfState *S, const uint8_t *text, uint64_t n) {
     if (rc) return rc;
     uint64_t *sum = S->d_tile, *off_lo = sum + n_tiles, *off_hi = off_lo + n_tiles;
     MSIM_HIP(c, hipMemsetAsync(S->d_mb, 0, 8 * sizeof(unsigned long long), c->stream));
-    MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+    MSIM_HIP(c, S->tm.begin(c->stream));
     hipLaunchKernelGGL(k_tile_reduce<LineStartF>, dim3((unsigned)n_tiles), dim3(ST), 0, c->stream, lf, n_pieces, sum);
     hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(ST), 0, c->stream, sum, n_tiles, off_lo, off_hi, S->d_mb + 4);
     MSIM_HIP(c, hipGetLastError());
@@ -684,7 +675,7 @@ int load_device(Ctx *c, VcfState *S, const uint8_t *text, uint64_t n) {
     MSIM_HIP(c, hipMemsetAsync(S->d_ls, 0, sizeof(uint64_t), c->stream));
     MSIM_HIP(c, hipMemsetAsync(S->d_tabcum, 0, sizeof(uint32_t), c->stream));
     lf.ls = S->d_ls; lf.tabcum = S->d_tabcum;
-    MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+    MSIM_HIP(c, S->tm.begin(c->stream));
     hipLaunchKernelGGL(k_tile_apply<LineStartF>, dim3((unsigned)n_tiles), dim3(ST), 0, c->stream, lf, n_pieces, off_lo, off_hi);
     MSIM_HIP(c, hipGetLastError());
     if (open_end) {                                        // the last line has no terminator: it ends where one would stand
@@ -710,7 +701,7 @@ int load_device(Ctx *c, VcfState *S, const uint8_t *text, uint64_t n) {
         MSIM_HIP(c, hipMalloc((void **)&g_first, cap * 20));
         g_off = g_first + cap;
         g_len = reinterpret_cast<uint32_t *>(g_off + cap);
-        MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+        MSIM_HIP(c, S->tm.begin(c->stream));
         hipLaunchKernelGGL(k_group_flags, dim3(blocks_for(n_data, 256)), dim3(256), 0, c->stream, t, S->d_ls, S->n_header, n_data, S->d_a, S->d_b);
         GroupF gf{S->d_a, S->d_b, S->d_ls, S->n_header, cap, g_first, g_off, g_len};
         rc = run_scan(c, S, gf, n_data, S->d_mb + 4);
@@ -755,7 +746,7 @@ int plan_device(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) {
         if (rc) return rc;
         S->h_mb[0] = ~0ull; S->h_mb[1] = S->h_mb[2] = S->h_mb[3] = 0;
         MSIM_HIP(c, hipMemcpyAsync(S->d_mb, S->h_mb, 4 * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
-        MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+        MSIM_HIP(c, S->tm.begin(c->stream));
         uint32_t *meta = S->d_a, *ilen = S->d_b, *poff = S->d_c;
         hipLaunchKernelGGL(k_vcf_lines, dim3(blocks_for(cnt, 256)), dim3(256), 0, c->stream, t, S->d_ls, S->d_tabcum, first, cnt, grp->name_len, in,
                            g->len, g->d_recs, meta, ilen, S->d_mb);
@@ -763,9 +754,9 @@ int plan_device(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) {
         if (rc) return rc;
         hipLaunchKernelGGL(k_vcf_neigh, dim3(blocks_for(cnt, 256)), dim3(256), 0, c->stream, g->d_recs, meta, poff, first, cnt, S->d_mb);
         MSIM_HIP(c, hipGetLastError());
-        MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+        MSIM_HIP(c, S->tm.end(c->stream));
         if ((rc = fetch_mailbox(c, S))) return rc;
-        if ((rc = elapsed(c, S, &S->plan_ms))) return rc;
+        if ((rc = S->tm.add_elapsed(c, &S->plan_ms))) return rc;
         // A refusal found so far does not end the pass: an earlier line may still fail in its long part, and the first
         // offending line is the one to name.  Refused lines add nothing to either sum.  With a refusal pending, or with sums
         // of 2^32 or more (where the 32-bit pool offsets have wrapped), the long pass checks only and writes no pool byte.
@@ -780,13 +771,13 @@ int plan_device(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) {
         const uint64_t first = grp->first_line;
         // the group's text: from its first line's start to the start of the line behind its last one
         const uint64_t bytes = S->group_end[(size_t)(grp - S->groups.data())] - grp->name_off + (grp->name_off & 15);
-        MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+        MSIM_HIP(c, S->tm.begin(c->stream));
         hipLaunchKernelGGL(k_vcf_long, dim3(blocks_for((bytes + 15) / 16, 256)), dim3(256), 0, c->stream, S->d_text + PAD, S->d_ls, first, cnt,
                            g->d_recs, S->d_a, g->d_in + PAD, g->d_pool + PAD, pool_len, S->d_mb);
         MSIM_HIP(c, hipGetLastError());
-        MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+        MSIM_HIP(c, S->tm.end(c->stream));
         if ((rc = fetch_mailbox(c, S))) return rc;
-        if ((rc = elapsed(c, S, &S->plan_ms))) return rc;
+        if ((rc = S->tm.add_elapsed(c, &S->plan_ms))) return rc;
     }
     if (cnt && S->h_mb[0] != ~0ull) return vcf_fail(c, S->h_mb[0] >> 4, (uint32_t)(S->h_mb[0] & 15));
     if (too_long) return vcf_fail(c, grp->first_line + 1, VCF_R_LENGTH);
@@ -817,7 +808,7 @@ int plan_device_cons(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) 
         const unsigned piece_blocks = blocks_for((bytes + 15) / 16, 256), line_blocks = blocks_for(cnt, 256);
         S->h_mb[0] = ~0ull; S->h_mb[1] = S->h_mb[2] = S->h_mb[3] = 0;
         MSIM_HIP(c, hipMemcpyAsync(S->d_mb, S->h_mb, 4 * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
-        MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+        MSIM_HIP(c, S->tm.begin(c->stream));
         hipLaunchKernelGGL(k_cons_ends, dim3(line_blocks), dim3(256), 0, c->stream, t, S->d_ls, S->d_tabcum, first, cnt, grp->name_len, S->nf0,
                            S->sample, S->hap, g->len, S->d_cons, S->d_mb);
         hipLaunchKernelGGL(k_cons_sep, dim3(piece_blocks), dim3(256), 0, c->stream, t, S->d_ls, first, cnt, S->d_cons);
@@ -826,9 +817,9 @@ int plan_device_cons(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) 
         if (rc) return rc;
         hipLaunchKernelGGL(k_cons_neigh, dim3(blocks_for(2 * cnt, 256)), dim3(256), 0, c->stream, g->d_recs, S->d_recline, S->d_mb + 4, first, S->d_mb);
         MSIM_HIP(c, hipGetLastError());
-        MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+        MSIM_HIP(c, S->tm.end(c->stream));
         if ((rc = fetch_mailbox(c, S))) return rc;
-        if ((rc = elapsed(c, S, &S->plan_ms))) return rc;
+        if ((rc = S->tm.add_elapsed(c, &S->plan_ms))) return rc;
         // as plan_device: a refusal found so far does not end the pass, and with one pending, or with sums of 2^32 or more,
         // the per-byte pass checks only and writes no pool byte
         too_long = g->len + S->h_mb[1] >= (1ull << 32);
@@ -838,13 +829,13 @@ int plan_device_cons(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) 
         any_sv = S->h_mb[3] & 1;
         rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, (size_t)pool_len + 2 * PAD);
         if (rc) return rc;
-        MSIM_HIP(c, hipEventRecord(S->e0, c->stream));
+        MSIM_HIP(c, S->tm.begin(c->stream));
         hipLaunchKernelGGL(k_cons_long, dim3(piece_blocks), dim3(256), 0, c->stream, t, S->d_ls, first, cnt, S->d_cons, in, g->d_pool + PAD, pool_len,
                            S->d_mb);
         MSIM_HIP(c, hipGetLastError());
-        MSIM_HIP(c, hipEventRecord(S->e1, c->stream));
+        MSIM_HIP(c, S->tm.end(c->stream));
         if ((rc = fetch_mailbox(c, S))) return rc;
-        if ((rc = elapsed(c, S, &S->plan_ms))) return rc;
+        if ((rc = S->tm.add_elapsed(c, &S->plan_ms))) return rc;
         if (S->h_mb[0] != ~0ull) return vcf_fail(c, S->h_mb[0] >> 4, (uint32_t)(S->h_mb[0] & 15));
         if (too_long) return vcf_fail(c, grp->first_line + 1, VCF_R_LENGTH);
     } else {
@@ -876,19 +867,12 @@ void vcf_state_destroy(Ctx *c) {
 
 using namespace msim;
 
-static int flushed(Ctx *c) {
-    int rc = flush_deferred_apply(c);
-    if (!rc && c->fast) rc = fast_plan_flush(c);
-    if (!rc && c->gpu) rc = gpu_emit_flush(c);
-    return rc;
-}
-
 extern "C" {
 
 int msim_vcf_load(msim_ctx *p, const uint8_t *text, uint64_t n, uint64_t *n_lines, uint64_t *n_groups) {
     Ctx *c = reinterpret_cast<Ctx *>(p);
     if (!c || (!text && n)) return MSIM_ERR_ARG;
-    int rc = flushed(c);
+    int rc = ctx_flush_queued(c);
     if (rc) return rc;
     if (n >= (1ull << 40)) return fail(c, MSIM_ERR_UNSUPPORTED, "VCF text of 1 TiB or more");
     vcf_state_destroy(c);
@@ -918,7 +902,7 @@ int msim_vcf_groups(msim_ctx *p, msim_vcf_group *out, uint64_t cap, uint64_t *n_
 int msim_vcf_plan_contig(msim_ctx *p, int contig, int64_t group) {
     Ctx *c = reinterpret_cast<Ctx *>(p);
     if (!c) return MSIM_ERR_ARG;
-    int rc = flushed(c);
+    int rc = ctx_flush_queued(c);
     if (rc) return rc;
     VcfState *S = c->vcf;
     if (!S) return fail(c, MSIM_ERR_ARG, "msim_vcf_plan_contig before msim_vcf_load");
@@ -937,7 +921,7 @@ int msim_vcf_plan_contig(msim_ctx *p, int contig, int64_t group) {
 int msim_vcf_select(msim_ctx *p, uint32_t grammar, uint32_t sample_index, uint32_t haplotype) {
     Ctx *c = reinterpret_cast<Ctx *>(p);
     if (!c) return MSIM_ERR_ARG;
-    int rc = flushed(c);
+    int rc = ctx_flush_queued(c);
     if (rc) return rc;
     VcfState *S = c->vcf;
     if (!S) return fail(c, MSIM_ERR_ARG, "msim_vcf_select before msim_vcf_load");
@@ -992,7 +976,7 @@ int msim_vcf_timing(msim_ctx *p, double *load_kernel_ms, double *plan_kernel_ms)
 int msim_vcf_release(msim_ctx *p) {
     Ctx *c = reinterpret_cast<Ctx *>(p);
     if (!c) return MSIM_ERR_ARG;
-    int rc = flushed(c);
+    int rc = ctx_flush_queued(c);
     if (!rc) rc = ctx_drain(c);
     vcf_state_destroy(c);
     return rc;

@@ -18,7 +18,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _ffi
-from .vcf_replay import MAX_CONTIGS, VcfReplayError, load_vcf_text, plan_all
+from .vcf_replay import VcfReplayError, load_vcf_text, plan_all, resident_genome
 
 TYPE_NAMES = (None, "SN", "IN", "DE", "DU", "IV", "TL", "TLI")            # msim.h: MSIM_SN .. MSIM_TLI
 BIN_NAMES = ("1", "2-5", "6-20", "21-50", "51+")                          # msim_cmp_counts: the length bins of IN and DE
@@ -97,19 +97,10 @@ class Compare:
 
     def run(self):
         fa, args = self._fasta, self._args
-        if len(fa) > MAX_CONTIGS:
-            raise _ffi.MsimUnsupported(f"compare mode keeps the genome resident: more than {MAX_CONTIGS} contigs")
-        recs = [fa[i] for i in range(len(fa))]
-        names = [r.name for r in recs]
         if self._engine is None:
             self._engine = _ffi.Engine(self._device)
         eng = self._engine
-        cids = []
-        for rec in recs:
-            if getattr(rec, "uniform", False):         # file text -> HBM: strip + upper-case on the device
-                cids.append(eng.add_contig_text(rec.body, len(rec), rec.lenc, rec.lenb))
-            else:
-                cids.append(eng.add_contig(rec.bases))
+        _, names, cids = resident_genome(eng, fa, "compare")
         truth = self._plan(eng, "truth", args.truthfile, names, cids, getattr(args, "truth_sample", None),
                            getattr(args, "truth_haplotype", None))
         for cid in cids:

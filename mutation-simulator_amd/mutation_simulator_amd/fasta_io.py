@@ -141,6 +141,14 @@ class FastaRecord:
         return self.bases.tobytes().decode("latin-1")
 
 
+def put_contig(engine, rec) -> int:
+    """``rec`` as a contig of ``engine`` (anything with ``add_contig_text`` and ``add_contig``); its id.  A uniform record goes
+    up as file text -- stripped and upper-cased on the device --, any other as its host-made bases."""
+    if getattr(rec, "uniform", False):
+        return engine.add_contig_text(rec.body, len(rec), rec.lenc, rec.lenb)
+    return engine.add_contig(rec.bases)
+
+
 def _upper_inplace(a: np.ndarray) -> None:
     lower = (a >= 97) & (a <= 122)
     a[lower] -= 32

@@ -16,6 +16,7 @@ import numpy as np
 from . import _ffi
 from ._ffi import Engine as _HostEngine            # (the host-only context that samples: no GPU involved)
 from .bedpe_writer import BedpeWriter
+from .fasta_io import put_contig
 from .fasta_writer import FastaWriter
 from .util import print_warning
 
@@ -186,10 +187,7 @@ class ITMutator:
         uploaded once and stays resident in between (``number``: its key; ``_forget`` drops everything)."""
         if number is not None and number in self._resident:
             return self._resident[number]
-        if getattr(rec, "uniform", False):            # file text -> HBM: strip + upper-case on the device
-            cid = eng.add_contig_text(rec.body, len(rec), rec.lenc, rec.lenb)
-        else:
-            cid = eng.add_contig(rec.bases)
+        cid = put_contig(eng, rec)
         self._slots += 1
         if number is not None:
             self._resident[number] = cid

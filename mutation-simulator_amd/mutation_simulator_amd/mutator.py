@@ -38,6 +38,7 @@ import numpy as np
 
 from . import _ffi, spectrum
 from .chain_writer import ChainWriter
+from .fasta_io import put_contig
 from .fasta_writer import FastaWriter
 from .mut_types import MutType
 from .util import format_warning
@@ -554,10 +555,7 @@ class Mutator:
         t = self._t
         t0 = time.perf_counter()
         rec = self._fasta[chrom.number]
-        if getattr(rec, "uniform", False):            # file text -> HBM: strip + upper-case on the device
-            cid = eng.add_contig_text(rec.body, len(rec), rec.lenc, rec.lenb)
-        else:
-            cid = eng.add_contig(rec.bases)
+        cid = put_contig(eng, rec)
         t1 = time.perf_counter()
         t["ingest_s"] += t1 - t0
         if self._spectrum is not None:

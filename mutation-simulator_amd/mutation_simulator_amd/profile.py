@@ -17,7 +17,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _ffi, spectrum
-from .vcf_replay import MAX_CONTIGS, load_vcf_text, plan_all
+from .vcf_replay import load_vcf_text, plan_all, resident_genome
 
 TALLY_NAMES = ("no context", "SN", "IN", "DE", "DU", "IV", "TL", "TLI")   # msim_sbs_counts: tallies[0..7]
 
@@ -54,24 +54,15 @@ class Profile:
 
     def run(self):
         fa, args = self._fasta, self._args
-        if len(fa) > MAX_CONTIGS:
-            raise _ffi.MsimUnsupported(f"profile mode keeps the genome resident: more than {MAX_CONTIGS} contigs")
-        recs = [fa[i] for i in range(len(fa))]
-        names = [r.name for r in recs]
         per_contig = bool(getattr(args, "per_contig", False))
-        refusal = column_refusal(args.name, names, per_contig)
+        refusal = column_refusal(args.name, [fa[i].name for i in range(len(fa))], per_contig)
         if refusal:                                    # (before anything reaches the GPU)
             raise ProfileError(refusal)
         if self._engine is None:
             self._engine = _ffi.Engine(self._device)
         eng = self._engine
         text = load_vcf_text(args.vcffile, eng)
-        cids = []
-        for rec in recs:
-            if getattr(rec, "uniform", False):         # file text -> HBM: strip + upper-case on the device
-                cids.append(eng.add_contig_text(rec.body, len(rec), rec.lenc, rec.lenb))
-            else:
-                cids.append(eng.add_contig(rec.bases))
+        _, names, cids = resident_genome(eng, fa, "profile")
         consensus = None
         if getattr(args, "consensus", False):
             consensus = (getattr(args, "sample", None), getattr(args, "haplotype", None) or 1)

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _ffi
 from .chain_writer import ChainWriter
-from .fasta_io import UnsupportedCompressionFormat
+from .fasta_io import UnsupportedCompressionFormat, put_contig
 from .fasta_writer import FastaWriter
 
 MAX_CONTIGS = 65536          # contigs one context holds (csrc/ctx.h)
@@ -66,6 +66,16 @@ def sample_column(text: np.ndarray, groups, sample) -> int:
     if names is None or want not in names:
         raise VcfReplayError(f"the VCF has no sample column {sample!r}")
     return names.index(want)
+
+
+def resident_genome(engine, fasta, mode_name: str):
+    """Every record of ``fasta`` as a contig of ``engine``, for the modes that keep the whole genome resident (``vcf``,
+    ``profile``, ``compare``): (records, their names, their contig ids).  A genome of more contigs than a context holds is
+    refused before anything is uploaded."""
+    if len(fasta) > MAX_CONTIGS:
+        raise _ffi.MsimUnsupported(f"{mode_name} mode keeps the genome resident: more than {MAX_CONTIGS} contigs")
+    recs = [fasta[i] for i in range(len(fasta))]
+    return recs, [r.name for r in recs], [put_contig(engine, r) for r in recs]
 
 
 def plan_all(engine, text: np.ndarray, names, contig_ids, consensus=None) -> None:
@@ -121,23 +131,15 @@ class VcfReplay:
 
     def run(self):
         fa = self._fasta
-        if len(fa) > MAX_CONTIGS:
-            raise _ffi.MsimUnsupported(f"vcf mode keeps the genome resident: more than {MAX_CONTIGS} contigs")
         if self._engine is None:
             self._engine = _ffi.Engine(self._device)
         eng = self._engine
         text = load_vcf_text(self._args.vcffile, eng)
-        recs = [fa[i] for i in range(len(fa))]
-        cids = []
-        for rec in recs:
-            if getattr(rec, "uniform", False):         # file text -> HBM: strip + upper-case on the device
-                cids.append(eng.add_contig_text(rec.body, len(rec), rec.lenc, rec.lenb))
-            else:
-                cids.append(eng.add_contig(rec.bases))
+        recs, names, cids = resident_genome(eng, fa, "vcf")
         consensus = None
         if getattr(self._args, "consensus", False):
             consensus = (getattr(self._args, "sample", None), getattr(self._args, "haplotype", None) or 1)
-        plan_all(eng, text, [r.name for r in recs], cids, consensus)
+        plan_all(eng, text, names, cids, consensus)
         # every line is accepted: rewrite and write, contig by contig
         if getattr(self._args, "chain", False):        # the one extra file of this mode: the chains of the replayed tables
             self._chain_writer = ChainWriter(self._args.outchain)      # (first: if it cannot be written, no Fasta is left)

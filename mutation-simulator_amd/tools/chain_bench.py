@@ -31,6 +31,7 @@ def kernels(fa: Path, repeats: int) -> dict:
     import mutation_simulator_amd as msa
     from mutation_simulator_amd import _ffi
     from mutation_simulator_amd import mutator as mm
+    from mutation_simulator_amd.fasta_io import put_contig
     args = msa.get_args([str(fa), "args"] + FLAGS["readme"])
     fasta = msa.load_fasta(args.infile, 0)
     sim = msa.SimulationSettings.from_args(args, fasta, True)
@@ -45,7 +46,7 @@ def kernels(fa: Path, repeats: int) -> dict:
            "vcf_call_ms": [0.0] * repeats}
     for chrom in sim.chromosomes:
         rec = fasta[chrom.number]
-        cid = eng.add_contig_text(rec.body, len(rec), rec.lenc, rec.lenb)
+        cid = put_contig(eng, rec)
         eng.plan_contig(cid, mm.plan_table(chrom))
         eng.sync()
         out["records"] += eng.result_sizes(cid, applied=False)[1]

@@ -227,6 +227,38 @@ def test_shifted_table_of_2_17_plus_1_records(eng, big):
     eng.clear()
 
 
+# ------------------------------------------------------------------------------ 3b. more passes than the grid has workgroups
+GRID = 2048                  # csrc/compare.hip: CMP_MAX_BLOCKS -- beyond that many passes a workgroup takes more than one
+
+
+@pytest.mark.parametrize("n", [GRID * PASS, GRID * PASS + 1], ids=["grid_full", "grid_strides"])
+def test_sn_table_at_and_past_the_grid_cap(eng, n):
+    """An SN record on every base of a contig of ``n`` bases, and the calls: the same table with every 1000th record's
+    alternative base changed.  At ``GRID * PASS`` records every workgroup takes one pass; with one record more the grid
+    strides, workgroup 0 takes two, and the slot of the result a workgroup adds to follows its number, not its pass.  Held
+    against the host restatement (linear in SN records) and the closed form: 524 changed records, each missed once and extra
+    once."""
+    bases = np.frombuffer(b"ACGT", dtype=np.uint8)[np.random.RandomState(5).randint(0, 4, n)]
+    a = np.zeros(n, dtype=_ffi.RECORD_DTYPE)
+    a["pos"] = a["stop"] = np.arange(n, dtype=np.uint32)
+    a["type"] = tw.SN
+    a["aux"] = np.arange(n) % 3
+    changed = np.arange(999, n, 1000)
+    assert len(changed) == 524
+    b = a.copy()
+    b["aux"][changed] = (b["aux"][changed] + 1) % 3
+    cid = install(eng, bases, a, tw.NO_POOL, b, tw.NO_POOL)
+    counts, tallies = eng.cmp_counts(cid)
+    held, _, fa, fb = eng.cmp_fetch(cid)
+    assert held.tobytes() == a.tobytes()
+    same((counts, tallies, fa, fb), _ffi.cmp_counts_host(bases, a, tw.NO_POOL, b, tw.NO_POOL), "host restatement")
+    assert counts[tw.SN, 0].tolist() == [n - 524, 524, n - 524, 524] and int(counts.sum()) == 2 * n and not tallies.any()
+    want = np.ones(n, dtype=np.uint8)
+    want[changed] = 0
+    assert np.array_equal(fa, want) and np.array_equal(fb, want)
+    eng.clear()
+
+
 # ------------------------------------------------------------------------------ 4. the command line
 NAMES = ("ctgA", "ctgB")
 BPL = 60
