@@ -67,22 +67,36 @@ struct GpuStream {
     uint32_t waited_chunks = 0;         // the plan stream already waited for chunks below this
 };
 
+// A scratch block that owns its memory: capacity in BYTES, move-only, frees itself.  Scratch: device memory; Staging: pinned
+// host memory (host_stage_alloc below).  They are grown through Grow alone, which has one rule per kind of block.
+static void dev_free(void *p) { if (p) (void)hipFree(p); }
+static void host_stage_free(void *p);
+template <void (*Free)(void *)> struct Block {
+    void *raw = nullptr; size_t cap = 0;
+    Block() = default;
+    Block(Block &&o) noexcept : raw(o.raw), cap(o.cap) { o.raw = nullptr; o.cap = 0; }
+    ~Block() { Free(raw); }
+};
+using DevBlock = Block<dev_free>;
+using PinBlock = Block<host_stage_free>;
+template <class T> struct Scratch : DevBlock { T *p() const { return static_cast<T *>(raw); } };
+template <class T> struct Staging : PinBlock { T *p() const { return static_cast<T *>(raw); } };
+
 constexpr int N_SETS = 32;               // scratch sets: one per in-flight contig, so the plan stream does not have to
                                          // wait for the emit stream (a cross-stream wait costs tens of us of idle
                                          // queue even when it is about to be satisfied); 288 GB of HBM make this free
 
 struct SampleSet {                       // scratch of one sampled range
-    uint32_t *acc = nullptr; size_t acc_cap = 0;          // accepted draws, stream order
-    uint32_t *cnt = nullptr; size_t cnt_cap = 0;          // per-workgroup accept counts / offsets
-    uint32_t *bitmap = nullptr; size_t bm_cap = 0;        // n-bit de-dup bitmap (bytes)
-    uint32_t *cnt2 = nullptr; size_t cnt2_cap = 0;        // per-workgroup popcounts / ranks
-    uint32_t *bins = nullptr; size_t bins_cap = 0;        // first-k draws grouped by value bin
-    uint32_t *cursors = nullptr; size_t cursors_cap = 0;  // per-bin fill counters
+    Scratch<uint32_t> acc;                                // accepted draws, stream order
+    Scratch<uint32_t> cnt;                                // per-workgroup accept counts / offsets
+    Scratch<uint32_t> bitmap;                             // n-bit de-dup bitmap
+    Scratch<uint32_t> cnt2;                               // per-workgroup popcounts / ranks
+    Scratch<uint32_t> bins;                               // first-k draws grouped by value bin
+    Scratch<uint32_t> cursors;                            // per-bin fill counters
     // anchored windows (enqueue_sample_ahead): bookkeeping of the core window and of the head interval, the accepted draws of
     // the head interval with their per-block offsets, and the event behind the set's off-chain work
     uint8_t *ahead = nullptr;                             // PlanState core | PlanState head | SpecHdr
-    uint32_t *hcnt = nullptr; size_t hcnt_cap = 0;
-    uint32_t *hacc = nullptr; size_t hacc_cap = 0;
+    Scratch<uint32_t> hcnt, hacc;
     hipEvent_t prep_done = nullptr;
     hipEvent_t chain_done = nullptr;                      // behind the set's last kernel on the plan stream (anchored windows)
     uint8_t last_user = 0;                                // since the last finish: 1 a sample on the chain, 2 an anchored window
@@ -91,8 +105,8 @@ struct SampleSet {                       // scratch of one sampled range
     bool pending = false;
 };
 struct SnpSet {                          // scratch of one contig's SNP draws
-    SnpMap *maps = nullptr; size_t cap = 0;
-    uint8_t *aux8 = nullptr; size_t aux_cap = 0;          // one-range contigs: the outcomes by rank (folded into the records by k_bitmap_expand)
+    Scratch<SnpMap> maps;
+    Scratch<uint8_t> aux8;                                // one-range contigs: the outcomes by rank (folded into the records by k_bitmap_expand)
     unsigned long long *base = nullptr;                   // device word: stream position the draws start at
     hipEvent_t emit_done = nullptr;
     hipEvent_t wait_ev = nullptr;                         // (as SampleSet::wait_ev)
@@ -104,29 +118,29 @@ struct SnpDefer { SnpSet *T; uint32_t W2, nb2; };           // what a deferred e
 struct EmitItem { int contig; SampleSet *S; SnpSet *T; uint32_t bmw, bnb, start, K, W2, nb2; msim_record *recs; bool apply; };
 
 struct MixedSet {                        // scratch of one SV-mix range (section 6)
-    uint32_t *cand_pos = nullptr; size_t cap_pos = 0;     // candidates in position order
-    uint8_t *cand_type = nullptr; size_t cap_type = 0;    // MSIM_* id | KEEP_BIT
-    uint32_t *cand_stop = nullptr; size_t cap_stop = 0;   // non-SNP candidates: stop from the host chain
-    uint32_t *nsn_pos = nullptr; size_t cap_npos = 0;     // compacted non-SNP candidates
-    uint8_t *nsn_type = nullptr; size_t cap_ntype = 0;
-    uint32_t *nsn_rank = nullptr; size_t cap_nrank = 0;   // their candidate index
-    uint32_t *nsn_stop = nullptr; size_t cap_nstop = 0;
-    uint32_t *sn_index = nullptr; size_t cap_snidx = 0;   // kept-SNP ordinal -> record index
-    uint32_t *cnt = nullptr; size_t cap_cnt = 0;          // five per-workgroup counter arrays
-    uint32_t *words = nullptr; size_t cap_words = 0;      // tempered word window for the host chain
+    Scratch<uint32_t> cand_pos;                           // candidates in position order
+    Scratch<uint8_t> cand_type;                           // MSIM_* id | KEEP_BIT
+    Scratch<uint32_t> cand_stop;                          // non-SNP candidates: stop from the host chain
+    Scratch<uint32_t> nsn_pos;                            // compacted non-SNP candidates
+    Scratch<uint8_t> nsn_type;
+    Scratch<uint32_t> nsn_rank;                           // their candidate index
+    Scratch<uint32_t> nsn_stop;
+    Scratch<uint32_t> sn_index;                           // kept-SNP ordinal -> record index
+    Scratch<uint32_t> cnt;                                // five per-workgroup counter arrays
+    Scratch<uint32_t> words;                              // tempered word window for the host chain
     unsigned long long *p0_slot = nullptr;                // host-cut contigs: stream position their window started at
-    WalkRange *walk_d = nullptr; size_t cap_walk_d = 0;   // device-walked / host-cut contigs: range table
-    WalkRange *walk_h = nullptr; size_t cap_walk_h = 0;   //   its pinned staging (one per set: the copy is asynchronous)
-    uint32_t *wbits = nullptr; size_t cap_wbits = 0;      //   contig-wide bitmap of sampled positions (zero between uses)
+    Scratch<WalkRange> walk_d;                            // device-walked / host-cut contigs: range table
+    Staging<WalkRange> walk_h;                            //   its pinned staging (one per set: the copy is asynchronous)
+    Scratch<uint32_t> wbits;                              //   contig-wide bitmap of sampled positions (zero between uses)
     bool wbits_dirty = false;                             //   a failed pass may have left bits behind
-    uint32_t *wcnt = nullptr; size_t cap_wcnt = 0;        //   per-workgroup popcounts / ranks of its expansion
-    uint32_t *tables = nullptr; size_t cap_tables = 0;    // host-chain engine: accept tables over the word window
-    uint32_t *cand_extra = nullptr; size_t cap_cextra = 0;   //   translocations: linked span start per candidate,
-    uint8_t *cand_aux = nullptr; size_t cap_caux = 0;        //   flags (reversed / insert_pos > 0 / tombstone),
-    uint32_t *nsn_extra = nullptr; size_t cap_nextra = 0;    //   and their staging in chain order
-    uint8_t *nsn_aux = nullptr; size_t cap_naux = 0;
-    uint8_t *mm_d = nullptr; size_t cap_mm_d = 0;         //   range table | settings' type tables | visit_from
-    uint8_t *mm_h = nullptr; size_t cap_mm_h = 0;         //   its pinned staging (one per set: the copies are asynchronous)
+    Scratch<uint32_t> wcnt;                               //   per-workgroup popcounts / ranks of its expansion
+    Scratch<uint32_t> tables;                             // host-chain engine: accept tables over the word window
+    Scratch<uint32_t> cand_extra;                         //   translocations: linked span start per candidate,
+    Scratch<uint8_t> cand_aux;                            //   flags (reversed / insert_pos > 0 / tombstone),
+    Scratch<uint32_t> nsn_extra;                          //   and their staging in chain order
+    Scratch<uint8_t> nsn_aux;
+    Scratch<uint8_t> mm_d;                                //   range table | settings' type tables | visit_from
+    Staging<uint8_t> mm_h;                                //   its pinned staging (one per set: the copies are asynchronous)
     hipEvent_t emit_done = nullptr;
     bool pending = false;
 };
@@ -135,14 +149,14 @@ struct GpuPlan {
     GpuStream s[2];
     MixedSet mixed[N_SETS];
     uint32_t mixed_unit = 0;
-    uint32_t *h_words = nullptr; size_t cap_h_words = 0;  // pinned host staging of the boundary chain
-    uint32_t *h_npos = nullptr; size_t cap_h_npos = 0;
-    uint8_t *h_ntype = nullptr; size_t cap_h_ntype = 0;
-    uint32_t *h_nstop = nullptr; size_t cap_h_nstop = 0;
-    uint32_t *h_win = nullptr; size_t cap_h_win = 0;      // host-chain engine: the tempered word window (h_words holds the tables)
-    uint32_t *h_nrank = nullptr; size_t cap_h_nrank = 0;  //   candidate ordinals of the chain
-    uint32_t *h_nextra = nullptr; size_t cap_h_nextra = 0;   //   translocations: what __link_tls decided, chain order
-    uint8_t *h_naux = nullptr; size_t cap_h_naux = 0;
+    Staging<uint32_t> h_words;                            // pinned host staging of the boundary chain
+    Staging<uint32_t> h_npos;
+    Staging<uint8_t> h_ntype;
+    Staging<uint32_t> h_nstop;
+    Staging<uint32_t> h_win;                              // host-chain engine: the tempered word window (h_words holds the tables)
+    Staging<uint32_t> h_nrank;                            //   candidate ordinals of the chain
+    Staging<uint32_t> h_nextra;                           //   translocations: what __link_tls decided, chain order
+    Staging<uint8_t> h_naux;
     MixSets mm_sets;                                       //   what gpu_plan_multimix_eligible derived for the contig being planned
     const msim_range *mm_for = nullptr; int mm_n = 0;
     uint32_t *h_seed = nullptr;         // pinned staging of the two host generator states (reseed without a stream sync)
@@ -217,22 +231,6 @@ struct GpuPlan {
     uint64_t est_lo = 0;
 };
 
-static int grow(Ctx *c, void **p, size_t *cap, size_t want_bytes, bool *grew) {
-    if (*cap >= want_bytes) return MSIM_OK;
-    if (!*grew) {                         // a buffer is about to be replaced: nothing may be in flight
-        if (c->gpu) for (auto st : c->gpu->prep_streams) if (st) MSIM_HIP(c, wait_stream(st));
-        MSIM_HIP(c, wait_stream(c->stream));
-        MSIM_HIP(c, wait_stream(c->emit_stream));
-        *grew = true;
-    }
-    if (*p) MSIM_HIP(c, hipFree(*p));
-    *p = nullptr; *cap = 0;
-    const size_t sz = want_bytes + want_bytes / 4 + 4096;
-    MSIM_HIP(c, hipMalloc(p, sz));
-    *cap = sz;
-    return MSIM_OK;
-}
-
 GpuPlan *gpu_plan_create() {
     GpuPlan *g = new GpuPlan();
     if (const char *e = getenv("MSIM_EMIT_GROUP")) g->emit_group = std::min(EMIT_G, std::max(0, atoi(e)));
@@ -249,7 +247,7 @@ GpuPlan *gpu_plan_create() {
     return g;
 }
 
-// Page-locked staging buffers of the engines with a host chain (grow_host): plain 2 MB-aligned memory on huge pages,
+// Page-locked staging buffers of the engines with a host chain (Grow::own): plain 2 MB-aligned memory on huge pages,
 // registered with the runtime.  Measured on the bench box per GiB: hipHostMalloc 182 ms + 90 ms to free; aligned_alloc +
 // MADV_HUGEPAGE + hipHostRegister 43 ms, unregister + free 37 ms -- and copies are just as asynchronous and as fast
 // (57 GB/s; into plain touched memory the "async" copy blocks the caller).  A 1 Gb contig needs 1.7 GB of them at once.
@@ -280,6 +278,70 @@ static void host_stage_free(void *p) {
     munmap(reinterpret_cast<void *>((uintptr_t)hdr[0]), hdr[1]);
 }
 
+// How the scratch blocks grow, one rule per kind; none keeps a block's contents.  One Grow per contig being planned.
+struct Grow {
+    Ctx *c;
+    bool grew = false;                                     // this contig has already drained the streams for a device block
+    // Device scratch of a set.  A block is about to be replaced: nothing may be in flight (once per contig).
+    int operator()(DevBlock &b, size_t want_bytes) {
+        if (b.cap >= want_bytes) return MSIM_OK;
+        if (!grew) {
+            if (c->gpu) for (auto st : c->gpu->prep_streams) if (st) MSIM_HIP(c, wait_stream(st));
+            MSIM_HIP(c, wait_stream(c->stream));
+            MSIM_HIP(c, wait_stream(c->emit_stream));
+            grew = true;
+        }
+        if (b.raw) MSIM_HIP(c, hipFree(b.raw));
+        b.raw = nullptr; b.cap = 0;
+        const size_t sz = want_bytes + want_bytes / 4 + 4096;
+        MSIM_HIP(c, hipMalloc(&b.raw, sz));
+        b.cap = sz;
+        return MSIM_OK;
+    }
+    // A set's own pinned table (walk_h, mm_h): no stream to wait for, mixed_acquire has waited for the set's emit_done on the host.
+    // (also how shared() replaces a block, behind its wait)
+    int own(PinBlock &b, size_t want_bytes) {
+        if (b.cap >= want_bytes) return MSIM_OK;
+        host_stage_free(b.raw);
+        b.raw = nullptr; b.cap = 0;
+        const size_t sz = (want_bytes + want_bytes / 4 + STAGE_HUGE) & ~(STAGE_HUGE - 1);
+        hipError_t e;
+        void *q = host_stage_alloc(sz, &e);
+        if (!q) return e != hipSuccess ? hip_fail(c, e, "hipHostRegister(host staging buffer)") : fail(c, MSIM_ERR_NOMEM, "host staging buffer");
+        b.raw = q;
+        b.cap = sz;
+        return MSIM_OK;
+    }
+    // The context's shared pinned blocks (GpuPlan::h_*), a group at a time.  An earlier contig's copies may still use the old
+    // blocks: before the first of the group is replaced, the plan stream and the copy stream are waited for, once.
+    struct Want { PinBlock &b; size_t bytes; };
+    int shared(std::initializer_list<Want> group) {
+        bool waited = false;
+        for (const Want &w : group) {
+            if (w.b.cap >= w.bytes) continue;
+            if (!waited) {
+                MSIM_HIP(c, wait_stream(c->stream));
+                if (c->gpu && c->gpu->copy_stream) MSIM_HIP(c, wait_stream(c->gpu->copy_stream));
+                waited = true;
+            }
+            if (int rc = own(w.b, w.bytes)) return rc;
+        }
+        return MSIM_OK;
+    }
+};
+
+struct DbgDev {                                            // device blocks of one test-hook call, freed when it returns
+    std::vector<DevBlock> blocks;
+    template <class T> hipError_t bytes(T **out, size_t sz) {            // exactly sz bytes
+        void *q = nullptr;
+        const hipError_t e = hipMalloc(&q, sz);
+        if (e == hipSuccess) { blocks.emplace_back(); blocks.back().raw = q; }
+        *out = static_cast<T *>(q);
+        return e;
+    }
+    template <class T> hipError_t get(T **out, size_t n) { return bytes(out, std::max<size_t>(n * sizeof(T), 4) + PAD); }
+};
+
 void gpu_plan_destroy(GpuPlan *g) {
     if (!g) return;
     if (g->jump_stream) { (void)wait_stream(g->jump_stream); (void)hipStreamDestroy(g->jump_stream); }
@@ -296,37 +358,20 @@ void gpu_plan_destroy(GpuPlan *g) {
         if (s.casc_ev) (void)hipEventDestroy(s.casc_ev);
     }
     for (auto e : g->ev_pool) (void)hipEventDestroy(e);
-    for (auto &t : g->sample) {
-        if (t.acc) (void)hipFree(t.acc);
-        if (t.cnt) (void)hipFree(t.cnt);
-        if (t.bitmap) (void)hipFree(t.bitmap);
-        if (t.cnt2) (void)hipFree(t.cnt2);
-        if (t.bins) (void)hipFree(t.bins);
-        if (t.cursors) (void)hipFree(t.cursors);
+    for (auto &t : g->sample) {                            // (the sets' Scratch / Staging blocks free themselves: delete g)
         if (t.ahead) (void)hipFree(t.ahead);
-        if (t.hcnt) (void)hipFree(t.hcnt);
-        if (t.hacc) (void)hipFree(t.hacc);
         if (t.prep_done) (void)hipEventDestroy(t.prep_done);
         if (t.chain_done) (void)hipEventDestroy(t.chain_done);
         if (t.emit_done) (void)hipEventDestroy(t.emit_done);
     }
     for (auto &t : g->snp) {
-        if (t.maps) (void)hipFree(t.maps);
-        if (t.aux8) (void)hipFree(t.aux8);
         if (t.base) (void)hipFree(t.base);
         if (t.emit_done) (void)hipEventDestroy(t.emit_done);
     }
     for (auto &t : g->mixed) {
-        void *bufs[] = {t.cand_pos, t.cand_type, t.cand_stop, t.nsn_pos, t.nsn_type, t.nsn_rank, t.nsn_stop, t.sn_index,
-                        t.cnt, t.words, t.walk_d, t.wbits, t.wcnt, t.p0_slot, t.tables, t.mm_d, t.cand_extra, t.cand_aux,
-                        t.nsn_extra, t.nsn_aux};
-        for (void *b : bufs) if (b) (void)hipFree(b);
-        host_stage_free(t.walk_h);
-        host_stage_free(t.mm_h);
+        if (t.p0_slot) (void)hipFree(t.p0_slot);
         if (t.emit_done) (void)hipEventDestroy(t.emit_done);
     }
-    void *hb[] = {g->h_words, g->h_npos, g->h_ntype, g->h_nstop, g->h_win, g->h_nrank, g->h_nextra, g->h_naux};
-    for (void *b : hb) host_stage_free(b);
     for (auto e : g->chain_ev) if (e) (void)hipEventDestroy(e);
     for (auto e : g->grp_ev) if (e) (void)hipEventDestroy(e);
     if (g->t0) (void)hipEventDestroy(g->t0);
@@ -871,7 +916,7 @@ struct SampleLaunch { SampleSet *S; uint32_t W, bmw, bnb; };
 // mode samples every contig from words of its own, position 0: nothing to generate, nothing chained).
 // e_limit: the host's (tighter) bound of where the sample ends -- the next stage's window is laid out from min(pos_hi + W,
 // e_limit), so a cut beyond that raises the overflow flag instead of letting the next stage read words nobody made.
-static int enqueue_sample_chain(Ctx *c, GpuPlan *g, const msim_range &r, int64_t d, uint64_t pos_hi, bool &grew,
+static int enqueue_sample_chain(Ctx *c, GpuPlan *g, const msim_range &r, int64_t d, uint64_t pos_hi, Grow &grow,
                                 SampleLaunch &out, const uint32_t *raw_other = nullptr, PlanState *ps_other = nullptr,
                                 uint64_t e_limit = ~0ull) {
     const uint32_t *raw = raw_other ? raw_other : g->s[0].d_raw;
@@ -891,10 +936,10 @@ static int enqueue_sample_chain(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
     const size_t bm_words64 = (size_t)((n + 63) / 64);
     const uint32_t bmw = (uint32_t)bm_words64;
     const uint32_t bnb = (bmw + BM_THREADS - 1) / BM_THREADS;
-    if ((rc = grow(c, (void **)&S.cnt, &S.cnt_cap, (size_t)(nb + 2) * sizeof(uint32_t), &grew))) return rc;
-    if ((rc = grow(c, (void **)&S.cnt2, &S.cnt2_cap, emit_cnt2_words(bmw) * sizeof(uint32_t), &grew))) return rc;   // (either train's layout: plan_kernels.h)
-    if ((rc = grow(c, (void **)&S.acc, &S.acc_cap, (size_t)W * sizeof(uint32_t), &grew))) return rc;
-    if ((rc = grow(c, (void **)&S.bitmap, &S.bm_cap, bm_words64 * 8, &grew))) return rc;
+    if ((rc = grow(S.cnt, (size_t)(nb + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = grow(S.cnt2, emit_cnt2_words(bmw) * sizeof(uint32_t)))) return rc;   // (either train's layout: plan_kernels.h)
+    if ((rc = grow(S.acc, (size_t)W * sizeof(uint32_t)))) return rc;
+    if ((rc = grow(S.bitmap, bm_words64 * 8))) return rc;
     if (!S.emit_done) MSIM_HIP(c, hipEventCreateWithFlags(&S.emit_done, hipEventDisableTiming));
     if (!raw_other) {
         if ((rc = ensure_words(c, g, 0, pos_hi + W + 1, false))) return rc;
@@ -906,34 +951,34 @@ static int enqueue_sample_chain(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
     const bool binned = n_bins <= (uint32_t)MAX_BINS;
     const uint32_t bin_cap = binned ? sample_bin_cap(n, k, p_acc) : 0u;
     if (binned) {
-        if ((rc = grow(c, (void **)&S.bins, &S.bins_cap, (size_t)n_bins * BIN_SUBS * bin_cap * sizeof(uint32_t), &grew))) return rc;
-        if ((rc = grow(c, (void **)&S.cursors, &S.cursors_cap, (size_t)MAX_BINS * BIN_SUBS * sizeof(uint32_t), &grew))) return rc;
-        if ((rc = grow(c, (void **)&S.bitmap, &S.bm_cap, (size_t)n_bins * BIN_WORDS * 4, &grew))) return rc;
+        if ((rc = grow(S.bins, (size_t)n_bins * BIN_SUBS * bin_cap * sizeof(uint32_t)))) return rc;
+        if ((rc = grow(S.cursors, (size_t)MAX_BINS * BIN_SUBS * sizeof(uint32_t)))) return rc;
+        if ((rc = grow(S.bitmap, (size_t)n_bins * BIN_WORDS * 4))) return rc;
     }
     hipLaunchKernelGGL(k_accept_count, dim3(nb), dim3(ACC_THREADS), 0, c->stream, raw, ps, W,
-                       (uint32_t)(32 - bits), (uint32_t)n, S.cnt, ps, binned ? S.cursors : nullptr,
+                       (uint32_t)(32 - bits), (uint32_t)n, S.cnt.p(), ps, binned ? S.cursors.p() : nullptr,
                        binned ? n_bins * BIN_SUBS : 0u);
     // the counts' prefix sums: made by their two consumers themselves where the tail kernel can hold them in LDS (every real
     // contig) -- a launch less on the chain; else by a scan of their own
     static const bool no_fold_scan = getenv("MSIM_NO_SCAN_FOLD") != nullptr;
     const uint32_t raw_counts = (binned && nb < (uint32_t)TAIL_LDS_OFFS && !no_fold_scan) ? 1u : 0u;
-    if (!raw_counts) hipLaunchKernelGGL(k_scan_u32_w4, dim3(1), dim3(256), 0, c->stream, S.cnt, nb);   // (four waves: see the kernel)
+    if (!raw_counts) hipLaunchKernelGGL(k_scan_u32_w4, dim3(1), dim3(256), 0, c->stream, S.cnt.p(), nb);   // (four waves: see the kernel)
     if (binned) {
         hipLaunchKernelGGL(k_bin_scatter, dim3((W + SPL_BLOCK - 1) / SPL_BLOCK), dim3(ACC_THREADS), 0, c->stream, raw, ps, W,
-                           (uint32_t)(32 - bits), (uint32_t)n, k, S.cnt, n_bins, bin_cap, S.cursors, S.bins, S.acc,
+                           (uint32_t)(32 - bits), (uint32_t)n, k, S.cnt.p(), n_bins, bin_cap, S.cursors.p(), S.bins.p(), S.acc.p(),
                            ps, raw_counts);
-        hipLaunchKernelGGL(k_bin_dedupe, dim3(n_bins), dim3(512), 0, c->stream, S.bins, S.cursors, bin_cap, S.bitmap,
+        hipLaunchKernelGGL(k_bin_dedupe, dim3(n_bins), dim3(512), 0, c->stream, S.bins.p(), S.cursors.p(), bin_cap, S.bitmap.p(),
                            ps);
-        hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(1024), 0, c->stream, raw, S.acc, k, S.cnt, nb, W,
-                           (uint32_t)(32 - bits), (uint32_t)n, k, S.bitmap, ps, raw_counts, (const PlanState *)nullptr,
+        hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(1024), 0, c->stream, raw, S.acc.p(), k, S.cnt.p(), nb, W,
+                           (uint32_t)(32 - bits), (uint32_t)n, k, S.bitmap.p(), ps, raw_counts, (const PlanState *)nullptr,
                            (const SpecHdr *)nullptr, (unsigned long long)pos_limit);
     } else {
-        MSIM_HIP(c, hipMemsetAsync(S.bitmap, 0, bm_words64 * 8, c->stream));
+        MSIM_HIP(c, hipMemsetAsync(S.bitmap.p(), 0, bm_words64 * 8, c->stream));
         hipLaunchKernelGGL(k_accept_scatter, dim3(nb), dim3(ACC_THREADS), 0, c->stream, raw, ps, W,
-                           (uint32_t)(32 - bits), (uint32_t)n, S.cnt, S.acc);
-        hipLaunchKernelGGL(k_bitmap_insert, dim3((k + 1023) / 1024), dim3(256), 0, c->stream, S.acc, k, S.bitmap, ps);
-        hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(1024), 0, c->stream, raw, S.acc, 0u, S.cnt, nb, W,
-                           (uint32_t)(32 - bits), (uint32_t)n, k, S.bitmap, ps, 0u, (const PlanState *)nullptr,
+                           (uint32_t)(32 - bits), (uint32_t)n, S.cnt.p(), S.acc.p());
+        hipLaunchKernelGGL(k_bitmap_insert, dim3((k + 1023) / 1024), dim3(256), 0, c->stream, S.acc.p(), k, S.bitmap.p(), ps);
+        hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(1024), 0, c->stream, raw, S.acc.p(), 0u, S.cnt.p(), nb, W,
+                           (uint32_t)(32 - bits), (uint32_t)n, k, S.bitmap.p(), ps, 0u, (const PlanState *)nullptr,
                            (const SpecHdr *)nullptr, (unsigned long long)pos_limit);
     }
     MSIM_HIP(c, hipGetLastError());
@@ -966,7 +1011,7 @@ static int prep_wait_words(Ctx *c, GpuPlan *g, uint64_t upto) {
 // covers the chain kernels enqueued here (the emit stream waited for the plan stream's position at the flush), so no event of the
 // set's own is recorded behind them: one packet less per contig on the chain's queue
 static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t d, uint64_t lo, uint64_t H, uint64_t e_limit,
-                                bool &grew, SampleLaunch &out, bool &took, bool grouped, uint64_t expect, uint32_t soft_half) {
+                                Grow &grow, SampleLaunch &out, bool &took, bool grouped, uint64_t expect, uint32_t soft_half) {
     int rc;
     const uint32_t K = (uint32_t)r.k;
     const uint64_t n = (uint64_t)range_population(r, d);
@@ -998,14 +1043,14 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
     const uint32_t bnb = (bmw + BM_THREADS - 1) / BM_THREADS;
     const uint32_t n_bins = (uint32_t)((n + BIN_VALUES - 1) >> BIN_SHIFT);
     const uint32_t bin_cap = sample_bin_cap(n, K, p_acc);
-    if ((rc = grow(c, (void **)&S.cnt, &S.cnt_cap, (size_t)(nb + 2) * sizeof(uint32_t), &grew))) return rc;
-    if ((rc = grow(c, (void **)&S.cnt2, &S.cnt2_cap, emit_cnt2_words(bmw) * sizeof(uint32_t), &grew))) return rc;   // (either train's layout: plan_kernels.h)
-    if ((rc = grow(c, (void **)&S.acc, &S.acc_cap, (size_t)W * sizeof(uint32_t), &grew))) return rc;
-    if ((rc = grow(c, (void **)&S.bins, &S.bins_cap, (size_t)n_bins * BIN_SUBS * bin_cap * sizeof(uint32_t), &grew))) return rc;
-    if ((rc = grow(c, (void **)&S.cursors, &S.cursors_cap, (size_t)MAX_BINS * BIN_SUBS * sizeof(uint32_t), &grew))) return rc;
-    if ((rc = grow(c, (void **)&S.bitmap, &S.bm_cap, std::max(bm_words64 * 8, (size_t)n_bins * BIN_WORDS * 4), &grew))) return rc;
-    if ((rc = grow(c, (void **)&S.hcnt, &S.hcnt_cap, (size_t)(nbh + 2) * sizeof(uint32_t), &grew))) return rc;
-    if ((rc = grow(c, (void **)&S.hacc, &S.hacc_cap, ((size_t)nbh * ACC_BLOCK + 64) * sizeof(uint32_t), &grew))) return rc;
+    if ((rc = grow(S.cnt, (size_t)(nb + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = grow(S.cnt2, emit_cnt2_words(bmw) * sizeof(uint32_t)))) return rc;   // (either train's layout: plan_kernels.h)
+    if ((rc = grow(S.acc, (size_t)W * sizeof(uint32_t)))) return rc;
+    if ((rc = grow(S.bins, (size_t)n_bins * BIN_SUBS * bin_cap * sizeof(uint32_t)))) return rc;
+    if ((rc = grow(S.cursors, (size_t)MAX_BINS * BIN_SUBS * sizeof(uint32_t)))) return rc;
+    if ((rc = grow(S.bitmap, std::max(bm_words64 * 8, (size_t)n_bins * BIN_WORDS * 4)))) return rc;
+    if ((rc = grow(S.hcnt, (size_t)(nbh + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = grow(S.hacc, ((size_t)nbh * ACC_BLOCK + 64) * sizeof(uint32_t)))) return rc;
     if (!S.ahead) MSIM_HIP(c, hipMalloc(&S.ahead, 2 * sizeof(PlanState) + sizeof(SpecHdr)));
     if (!S.emit_done) MSIM_HIP(c, hipEventCreateWithFlags(&S.emit_done, hipEventDisableTiming));
     if (!S.prep_done) MSIM_HIP(c, hipEventCreateWithFlags(&S.prep_done, hipEventDisableTiming));
@@ -1030,10 +1075,10 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
     // ---- off the chain
     const uint32_t shift = (uint32_t)(32 - bits);
     hipLaunchKernelGGL(k_ahead_count, dim3(nb + nbh), dim3(ACC_THREADS), 0, ps_, raw, ps_core, ps_head, hdr, (unsigned long long)H,
-                       (unsigned long long)lo, W, F, nb, shift, (uint32_t)n, S.cnt, S.cursors, n_bins * BIN_SUBS, S.hcnt, S.hacc);
+                       (unsigned long long)lo, W, F, nb, shift, (uint32_t)n, S.cnt.p(), S.cursors.p(), n_bins * BIN_SUBS, S.hcnt.p(), S.hacc.p());
     hipLaunchKernelGGL(k_bin_scatter, dim3((W + SPL_BLOCK - 1) / SPL_BLOCK), dim3(ACC_THREADS), 0, ps_, raw, ps_core, W, shift,
-                       (uint32_t)n, k_core, S.cnt, n_bins, bin_cap, S.cursors, S.bins, S.acc, ps_core, 1u);
-    hipLaunchKernelGGL(k_bin_dedupe, dim3(n_bins), dim3(512), 0, ps_, S.bins, S.cursors, bin_cap, S.bitmap, ps_core);
+                       (uint32_t)n, k_core, S.cnt.p(), n_bins, bin_cap, S.cursors.p(), S.bins.p(), S.acc.p(), ps_core, 1u);
+    hipLaunchKernelGGL(k_bin_dedupe, dim3(n_bins), dim3(512), 0, ps_, S.bins.p(), S.cursors.p(), bin_cap, S.bitmap.p(), ps_core);
     MSIM_HIP(c, hipGetLastError());
     MSIM_HIP(c, hipEventRecord(S.prep_done, ps_));
     // ---- on the chain: fringe (exact start), tail rounds, cut
@@ -1042,10 +1087,10 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
     const uint32_t items_est = a_max + (uint32_t)(dups_est + 16.0 * std::sqrt(dups_est) + 64.0);
     const uint32_t G = std::max(1u, std::min(256u, (items_est + ACC_THREADS * FRINGE_ITEMS - 1) / (ACC_THREADS * FRINGE_ITEMS)));
     hipLaunchKernelGGL(k_ahead_fringe, dim3(G), dim3(ACC_THREADS), 0, c->stream, raw, g->d_ps, ps_core, ps_head, hdr,
-                       (unsigned long long)lo, F, S.hcnt, nbh, S.hacc, S.acc, K, k_core, shift, (uint32_t)n, S.bitmap,
+                       (unsigned long long)lo, F, S.hcnt.p(), nbh, S.hacc.p(), S.acc.p(), K, k_core, shift, (uint32_t)n, S.bitmap.p(),
                        (unsigned long long)expect, soft_half);
-    hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(1024), 0, c->stream, raw, S.acc, k_core, S.cnt, nb, W, shift, (uint32_t)n,
-                       k_core, S.bitmap, g->d_ps, 1u, ps_core, hdr, (unsigned long long)e_limit);
+    hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(1024), 0, c->stream, raw, S.acc.p(), k_core, S.cnt.p(), nb, W, shift, (uint32_t)n,
+                       k_core, S.bitmap.p(), g->d_ps, 1u, ps_core, hdr, (unsigned long long)e_limit);
     MSIM_HIP(c, hipGetLastError());
     if (!grouped) MSIM_HIP(c, hipEventRecord(S.chain_done, c->stream));
     out.S = &S; out.W = W; out.bmw = bmw; out.bnb = bnb;
@@ -1061,7 +1106,7 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
 // aux8_out (SNP sampler, one drawing range): the outcomes go to a compact byte array by rank instead of into the records; the
 // caller launches the bitmap expansion behind this stage and hands it that array (*aux8_out).
 // defer (with aux8_out): the emit pass is not launched here at all -- the caller queues it for the contig's emission group.
-static int enqueue_snp_stage(Ctx *c, GpuPlan *g, Contig &ct, uint64_t K, const uint32_t *sn_index, uint64_t &pos_hi, bool &grew,
+static int enqueue_snp_stage(Ctx *c, GpuPlan *g, Contig &ct, uint64_t K, const uint32_t *sn_index, uint64_t &pos_hi, Grow &grow,
                              uint8_t **aux8_out = nullptr, SnpDefer *defer = nullptr, uint64_t e_limit = ~0ull) {
     const msim_params &P = c->params;
     GpuStream &py = g->s[0];
@@ -1073,10 +1118,10 @@ static int enqueue_snp_stage(Ctx *c, GpuPlan *g, Contig &ct, uint64_t K, const u
     const uint32_t nb2 = W2 / SNP_BLOCK2 + 2;              // window blocks incl. the partial first one
     SnpSet &T = g->snp[g->snp_unit++ % N_SETS];
     if ((rc = wait_if_pending(c, T.pending, T.wait_ev))) return rc;
-    if ((rc = grow(c, (void **)&T.maps, &T.cap, (size_t)(nb2 + 1) * sizeof(SnpMap), &grew))) return rc;
+    if ((rc = grow(T.maps, (size_t)(nb2 + 1) * sizeof(SnpMap)))) return rc;
     if (aux8_out) {
-        if ((rc = grow(c, (void **)&T.aux8, &T.aux_cap, (size_t)K + 64, &grew))) return rc;
-        *aux8_out = T.aux8;
+        if ((rc = grow(T.aux8, (size_t)K + 64))) return rc;
+        *aux8_out = T.aux8.p();
     }
     if (!T.base) MSIM_HIP(c, hipMalloc(&T.base, 64));
     if (!T.emit_done) MSIM_HIP(c, hipEventCreateWithFlags(&T.emit_done, hipEventDisableTiming));
@@ -1090,7 +1135,7 @@ static int enqueue_snp_stage(Ctx *c, GpuPlan *g, Contig &ct, uint64_t K, const u
         py.maps_ti_lim = P.ti_lim;
     }
     hipLaunchKernelGGL(k_snp_scan_cut_abs, dim3(1), dim3(SNP_THREADS), 0, c->stream, py.d_lanes, g->d_ps, W2,
-                       py.d_maps, T.maps, nb2, (uint32_t)K, T.base,
+                       py.d_maps, T.maps.p(), nb2, (uint32_t)K, T.base,
                        (unsigned long long)(e_limit == ~0ull ? ~0ull : std::min<uint64_t>(pos_hi + W2, e_limit)));
     MSIM_HIP(c, hipGetLastError());
     if (defer) { defer->T = &T; defer->W2 = W2; defer->nb2 = nb2; }
@@ -1099,7 +1144,7 @@ static int enqueue_snp_stage(Ctx *c, GpuPlan *g, Contig &ct, uint64_t K, const u
         MSIM_HIP(c, hipEventRecord(ce, c->stream));
         MSIM_HIP(c, hipStreamWaitEvent(c->emit_stream, ce, 0));
         hipLaunchKernelGGL(k_snp_emit_abs, dim3(nb2), dim3(SNP_THREADS), 0, c->emit_stream, py.d_lanes, T.base, W2,
-                           T.maps, nb2, ct.d_recs, (uint32_t)K, sn_index, aux8_out ? T.aux8 : (uint8_t *)nullptr);
+                           T.maps.p(), nb2, ct.d_recs, (uint32_t)K, sn_index, aux8_out ? T.aux8.p() : (uint8_t *)nullptr);
         MSIM_HIP(c, hipGetLastError());
         if (!aux8_out) {                                  // (else: the caller records it behind the expansion that reads aux8)
             MSIM_HIP(c, hipEventRecord(T.emit_done, c->emit_stream));
@@ -1148,8 +1193,8 @@ int gpu_emit_flush(Ctx *c) {
     for (uint32_t i = 0; i < J.n; i++) {
         const EmitItem &it = items[i];
         EmitJob &T = J.j[i];
-        T.bm = reinterpret_cast<const uint64_t *>(it.S->bitmap); T.cnt2 = it.S->cnt2; T.recs = it.recs; T.aux8 = it.T->aux8;
-        T.base = it.T->base; T.win_maps = it.T->maps;
+        T.bm = reinterpret_cast<const uint64_t *>(it.S->bitmap.p()); T.cnt2 = it.S->cnt2.p(); T.recs = it.recs; T.aux8 = it.T->aux8.p();
+        T.base = it.T->base; T.win_maps = it.T->maps.p();
         T.bmw = it.bmw; T.bnb = it.bnb; T.start = it.start; T.K = it.K; T.W2 = it.W2; T.nb2 = it.nb2;
     }
     hipStream_t es = c->emit_stream;
@@ -1215,12 +1260,10 @@ int gpu_dbg_emit_train(Ctx *c, int n_jobs, const uint64_t *const *bm, const uint
     if (n_jobs < 1 || n_jobs > EMIT_G || (train != 3 && train != 6) || !bm || !n_words || !start || !len || !aux8 || !recs ||
         !cap_recs || !n_recs || tile_shift < 4 || tile_shift > 30)
         return fail(c, MSIM_ERR_ARG, "msim_dbg_emit_train: bad argument");
-    struct Dev { void *p[5] = {nullptr, nullptr, nullptr, nullptr, nullptr}; ~Dev() { for (void *q : p) if (q) (void)hipFree(q); } };
-    std::vector<Dev> dev((size_t)n_jobs);
+    DbgDev dev;
     std::vector<uint64_t> cnt((size_t)n_jobs, 0);
     unsigned long long *d_err = nullptr;
-    struct ErrFree { unsigned long long *&p; ~ErrFree() { if (p) (void)hipFree(p); } } err_free{d_err};
-    MSIM_HIP(c, hipMalloc(&d_err, sizeof(unsigned long long) * EMIT_G));
+    MSIM_HIP(c, dev.bytes(&d_err, sizeof(unsigned long long) * EMIT_G));
     EmitJobs J;
     memset(&J, 0, sizeof J);
     J.n = (uint32_t)n_jobs; J.d = d; J.tile_shift = tile_shift;
@@ -1237,24 +1280,25 @@ int gpu_dbg_emit_train(Ctx *c, int n_jobs, const uint64_t *const *bm, const uint
         const size_t sz[5] = {(size_t)n_words[i] * 8, emit_cnt2_words(n_words[i]) * sizeof(uint32_t),
                               (size_t)(cnt[(size_t)i] + 1) * sizeof(msim_record), (size_t)cnt[(size_t)i] + 1,
                               (n_tiles + 1) * sizeof(int32_t)};
-        for (int q = 0; q < 5; q++) MSIM_HIP(c, hipMalloc(&dev[(size_t)i].p[q], sz[q]));
-        MSIM_HIP(c, hipMemcpyAsync(dev[(size_t)i].p[0], bm[i], sz[0], hipMemcpyHostToDevice, es));
-        MSIM_HIP(c, hipMemcpyAsync(dev[(size_t)i].p[3], aux8[i], (size_t)cnt[(size_t)i], hipMemcpyHostToDevice, es));
-        MSIM_HIP(c, hipMemsetAsync(dev[(size_t)i].p[4], 0xee, sz[4], es));
+        void *p[5];
+        for (int q = 0; q < 5; q++) MSIM_HIP(c, dev.bytes(&p[q], sz[q]));
+        MSIM_HIP(c, hipMemcpyAsync(p[0], bm[i], sz[0], hipMemcpyHostToDevice, es));
+        MSIM_HIP(c, hipMemcpyAsync(p[3], aux8[i], (size_t)cnt[(size_t)i], hipMemcpyHostToDevice, es));
+        MSIM_HIP(c, hipMemsetAsync(p[4], 0xee, sz[4], es));
         EmitJob &T = J.j[i];
-        T.bm = static_cast<const uint64_t *>(dev[(size_t)i].p[0]); T.cnt2 = static_cast<uint32_t *>(dev[(size_t)i].p[1]);
-        T.recs = static_cast<msim_record *>(dev[(size_t)i].p[2]); T.aux8 = static_cast<uint8_t *>(dev[(size_t)i].p[3]);
+        T.bm = static_cast<const uint64_t *>(p[0]); T.cnt2 = static_cast<uint32_t *>(p[1]);
+        T.recs = static_cast<msim_record *>(p[2]); T.aux8 = static_cast<uint8_t *>(p[3]);
         T.bmw = n_words[i]; T.bnb = (n_words[i] + BM_THREADS - 1) / BM_THREADS; T.start = start[i]; T.K = (uint32_t)cnt[(size_t)i];
         if (train == 3 && first && first[i] && n_tiles) {
-            T.first = static_cast<int32_t *>(dev[(size_t)i].p[4]); T.n_tiles = (uint32_t)n_tiles; T.err = d_err + i;
+            T.first = static_cast<int32_t *>(p[4]); T.n_tiles = (uint32_t)n_tiles; T.err = d_err + i;
         }
     }
     emit_train_launch(es, nullptr, J, train == 3);
     MSIM_HIP(c, hipGetLastError());
     for (int i = 0; i < n_jobs; i++) {
-        MSIM_HIP(c, hipMemcpyAsync(recs[i], dev[(size_t)i].p[2], (size_t)cnt[(size_t)i] * sizeof(msim_record), hipMemcpyDeviceToHost, es));
+        MSIM_HIP(c, hipMemcpyAsync(recs[i], J.j[i].recs, (size_t)cnt[(size_t)i] * sizeof(msim_record), hipMemcpyDeviceToHost, es));
         if (J.j[i].first)
-            MSIM_HIP(c, hipMemcpyAsync(first[i], dev[(size_t)i].p[4], ((size_t)J.j[i].n_tiles + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, es));
+            MSIM_HIP(c, hipMemcpyAsync(first[i], J.j[i].first, ((size_t)J.j[i].n_tiles + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, es));
     }
     MSIM_HIP(c, wait_stream(es));
     return MSIM_OK;
@@ -1276,24 +1320,21 @@ int gpu_dbg_snp_draws(Ctx *c, const uint32_t *words, uint64_t n_words, uint64_t 
     const uint32_t nb = (uint32_t)(n_blocks - start / SNP_BLOCK2);
     const size_t sz_lanes = (size_t)(n_blocks + 1) * SNP_THREADS * sizeof(SnpLane), sz_maps = (size_t)(n_blocks + 1) * sizeof(SnpMap);
     const size_t sz_aux = (size_t)aux_off + K + 16;
-    struct Dev { void *p[7] = {}; ~Dev() { for (void *q : p) if (q) (void)hipFree(q); } } dev;
-    const size_t sz[7] = {(size_t)n_words * 4, sz_lanes, sz_maps, (size_t)(nb + 1) * sizeof(SnpMap), sizeof(PlanState), 64, sz_aux};
-    for (int q = 0; q < 7; q++) MSIM_HIP(c, hipMalloc(&dev.p[q], sz[q]));
-    const uint32_t *d_raw = static_cast<const uint32_t *>(dev.p[0]);
-    SnpLane *d_lanes = static_cast<SnpLane *>(dev.p[1]);
-    SnpMap *d_maps = static_cast<SnpMap *>(dev.p[2]), *d_win = static_cast<SnpMap *>(dev.p[3]);
-    PlanState *d_ps = static_cast<PlanState *>(dev.p[4]);
-    unsigned long long *d_base = static_cast<unsigned long long *>(dev.p[5]);
-    uint8_t *d_aux = static_cast<uint8_t *>(dev.p[6]);
+    const size_t sz_raw = (size_t)n_words * 4, sz_win = (size_t)(nb + 1) * sizeof(SnpMap);
+    DbgDev dev;
+    uint32_t *d_raw; SnpLane *d_lanes; SnpMap *d_maps, *d_win; PlanState *d_ps; unsigned long long *d_base; uint8_t *d_aux;
+    MSIM_HIP(c, dev.bytes(&d_raw, sz_raw)); MSIM_HIP(c, dev.bytes(&d_lanes, sz_lanes)); MSIM_HIP(c, dev.bytes(&d_maps, sz_maps));
+    MSIM_HIP(c, dev.bytes(&d_win, sz_win)); MSIM_HIP(c, dev.bytes(&d_ps, sizeof(PlanState))); MSIM_HIP(c, dev.bytes(&d_base, 64));
+    MSIM_HIP(c, dev.bytes(&d_aux, sz_aux));
     hipStream_t st = c->stream;
     PlanState ps;
     memset(&ps, 0, sizeof ps);
     ps.pos = ps.snp_base = start;
-    MSIM_HIP(c, hipMemcpyAsync(dev.p[0], words, sz[0], hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemcpyAsync(d_raw, words, sz_raw, hipMemcpyHostToDevice, st));
     MSIM_HIP(c, hipMemcpyAsync(d_ps, &ps, sizeof ps, hipMemcpyHostToDevice, st));
     MSIM_HIP(c, hipMemsetAsync(d_lanes, 0xee, sz_lanes, st));
     MSIM_HIP(c, hipMemsetAsync(d_maps, 0xee, sz_maps, st));
-    MSIM_HIP(c, hipMemsetAsync(d_win, 0, sz[3], st));
+    MSIM_HIP(c, hipMemsetAsync(d_win, 0, sz_win, st));
     MSIM_HIP(c, hipMemsetAsync(d_aux, 0xee, sz_aux, st));
     hipLaunchKernelGGL(k_snp_maps_abs, dim3((uint32_t)n_blocks), dim3(SNP_THREADS), 0, st, d_raw, (uint32_t)n_words,
                        (unsigned long long)ti_lim, 0u, d_maps, d_lanes);
@@ -1342,7 +1383,7 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
     uint64_t K = 0;
     for (int i = 0; i < n_ranges; i++) K += (uint64_t)ranges[i].k;
     if (K >= (1ull << 31)) return fail(c, MSIM_ERR_UNSUPPORTED, "more than 2^31 mutations on one contig");
-    bool grew = false;
+    Grow grow{c};
     if (!c->chain_only) {   // the record table may still be read by an earlier apply of this contig
         const size_t want = std::max<uint64_t>(K, 1) * sizeof(msim_record);
         if (ct.cap_recs < want || ct.cap_pool < 2 * PAD) {
@@ -1427,10 +1468,10 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
         if (ahead) {
             // the sample ends at or in front of e_lim (and inside its window): what the SNP stage's windows are laid out from
             const uint64_t e_lim = est_hi(~0ull);
-            if ((rc = enqueue_sample_ahead(c, g, r, d, lo, H, e_lim, grew, sl, ahead, grouped, expect, soft_half))) return rc;
+            if ((rc = enqueue_sample_ahead(c, g, r, d, lo, H, e_lim, grow, sl, ahead, grouped, expect, soft_half))) return rc;
             if (ahead) pos_hi = std::min<uint64_t>(H + sl.W, e_lim) - sl.W;      // (+ W below)
         }
-        if (!ahead && (rc = enqueue_sample_chain(c, g, r, d, pos_hi, grew, sl, nullptr, nullptr, est_hi(~0ull)))) return rc;
+        if (!ahead && (rc = enqueue_sample_chain(c, g, r, d, pos_hi, grow, sl, nullptr, nullptr, est_hi(~0ull)))) return rc;
         SampleSet &S = *sl.S;
         const uint32_t W = sl.W, bmw = sl.bmw, bnb = sl.bnb;
         if (grouped) {
@@ -1441,13 +1482,13 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
             // ---- emit (emit stream): the bitmap is the sorted sample -> records
             MSIM_HIP(c, hipStreamWaitEvent(c->emit_stream, ce, 0));
             hipLaunchKernelGGL(k_bitmap_count, dim3(bnb), dim3(BM_THREADS), 0, c->emit_stream,
-                               reinterpret_cast<const uint64_t *>(S.bitmap), bmw, S.cnt2);
-            hipLaunchKernelGGL(k_scan_u32_w4, dim3(1), dim3(256), 0, c->emit_stream, S.cnt2, bnb);
+                               reinterpret_cast<const uint64_t *>(S.bitmap.p()), bmw, S.cnt2.p());
+            hipLaunchKernelGGL(k_scan_u32_w4, dim3(1), dim3(256), 0, c->emit_stream, S.cnt2.p(), bnb);
             if (fold_aux) {                               // the expansion follows the SNP stage (below): it writes complete records
                 late = {&S, bmw, bnb, (uint32_t)r.start};
             } else {
                 hipLaunchKernelGGL(k_bitmap_expand, dim3(bnb), dim3(BM_THREADS), 0, c->emit_stream,
-                                   reinterpret_cast<const uint64_t *>(S.bitmap), bmw, S.cnt2, (uint32_t)r.start, (uint32_t)d,
+                                   reinterpret_cast<const uint64_t *>(S.bitmap.p()), bmw, S.cnt2.p(), (uint32_t)r.start, (uint32_t)d,
                                    ct.d_recs + rec_base, (const uint8_t *)nullptr);
                 MSIM_HIP(c, hipGetLastError());
                 MSIM_HIP(c, hipEventRecord(S.emit_done, c->emit_stream));
@@ -1469,7 +1510,7 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
             g->est_lo += 2 * K;
         }
         // (est_hi(~0): the bound the position is tightened to behind this stage -- the kernel flags a cut beyond it)
-        if ((rc = enqueue_snp_stage(c, g, ct, K, nullptr, pos_hi, grew, late.S ? &aux8 : nullptr, grouped ? &df : nullptr, est_hi(~0ull)))) return rc;
+        if ((rc = enqueue_snp_stage(c, g, ct, K, nullptr, pos_hi, grow, late.S ? &aux8 : nullptr, grouped ? &df : nullptr, est_hi(~0ull)))) return rc;
         pos_hi = est_hi(pos_hi);
         if (grouped) {
             g->emit_d = (uint32_t)d;
@@ -1480,7 +1521,7 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
             SampleSet &S = *late.S;
             SnpSet &T = g->snp[(g->snp_unit - 1) % N_SETS];        // (the set enqueue_snp_stage just took)
             hipLaunchKernelGGL(k_bitmap_expand, dim3(late.bnb), dim3(BM_THREADS), 0, c->emit_stream,
-                               reinterpret_cast<const uint64_t *>(S.bitmap), late.bmw, S.cnt2, late.start, (uint32_t)d,
+                               reinterpret_cast<const uint64_t *>(S.bitmap.p()), late.bmw, S.cnt2.p(), late.start, (uint32_t)d,
                                ct.d_recs, (const uint8_t *)aux8);
             MSIM_HIP(c, hipGetLastError());
             MSIM_HIP(c, hipEventRecord(S.emit_done, c->emit_stream));
@@ -1500,19 +1541,6 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
 }
 
 // ====================================================================== SV mixes (section 6 kernels)
-static int grow_host(Ctx *c, void **p, size_t *cap, size_t want_bytes) {
-    if (*cap >= want_bytes) return MSIM_OK;
-    host_stage_free(*p);
-    *p = nullptr; *cap = 0;
-    const size_t sz = (want_bytes + want_bytes / 4 + STAGE_HUGE) & ~(STAGE_HUGE - 1);
-    hipError_t e;
-    void *q = host_stage_alloc(sz, &e);
-    if (!q) return e != hipSuccess ? hip_fail(c, e, "hipHostRegister(host staging buffer)") : fail(c, MSIM_ERR_NOMEM, "host staging buffer");
-    *p = q;
-    *cap = sz;
-    return MSIM_OK;
-}
-
 static bool range_draws_translocations(const msim_range &r) {
     for (int j = 0; j < r.n_types; j++)
         if ((r.types[j] == MSIM_TL || r.types[j] == MSIM_TLI) && type_drawable(r, j)) return true;
@@ -1833,13 +1861,13 @@ static void emit_records_launch(hipStream_t s, const MixedTables &M, msim_record
 // candidates are in M.cand_stop -> keep flags and counts -> records, insert pool, SNP draws.  p_s: where the SNP draws of
 // __mutate_sequence start in the CPython stream.  rt / visit_from / sn_chained: see k_keep_flags (nullptr for one range).
 static int mixed_emit(Ctx *c, GpuPlan *g, Contig &ct, MixedSet &M, uint32_t k, uint64_t p_s, const MixRangeDev *rt,
-                      uint32_t n_draw, const uint32_t *visit_from, bool sn_chained, bool &grew, bool has_tl = false) {
-    const uint32_t *c_extra = has_tl ? M.cand_extra : nullptr;
-    const uint8_t *c_aux = has_tl ? M.cand_aux : nullptr;
+                      uint32_t n_draw, const uint32_t *visit_from, bool sn_chained, Grow &grow, bool has_tl = false) {
+    const uint32_t *c_extra = has_tl ? M.cand_extra.p() : nullptr;
+    const uint8_t *c_aux = has_tl ? M.cand_aux.p() : nullptr;
     const msim_params &P = c->params;
     GpuStream &py = g->s[0], &np = g->s[1];
     int rc;
-    const MixedTables mt{k, M.cand_pos, M.cand_type, M.cand_stop, c_extra, c_aux, M.cnt, M.sn_index, rt, n_draw, visit_from, sn_chained};
+    const MixedTables mt{k, M.cand_pos.p(), M.cand_type.p(), M.cand_stop.p(), c_extra, c_aux, M.cnt.p(), M.sn_index.p(), rt, n_draw, visit_from, sn_chained};
     hipLaunchKernelGGL(k_set_pos, dim3(1), dim3(1), 0, c->stream, g->d_ps, (unsigned long long)p_s);
 
     // ---- 3. keep flags, counts
@@ -1879,7 +1907,7 @@ static int mixed_emit(Ctx *c, GpuPlan *g, Contig &ct, MixedSet &M, uint32_t k, u
     np.pos += pool_len;
     c->t.np_words += pool_len;
     if (n_sn) {                                          // SNP draws in position order (chain: scan + cut; aux off the chain)
-        if ((rc = enqueue_snp_stage(c, g, ct, n_sn, M.sn_index, pos_hi, grew))) return rc;
+        if ((rc = enqueue_snp_stage(c, g, ct, n_sn, M.sn_index.p(), pos_hi, grow))) return rc;
     }
     MSIM_HIP(c, hipEventRecord(M.emit_done, c->emit_stream));
     M.pending = true;
@@ -1893,9 +1921,9 @@ static int mixed_emit(Ctx *c, GpuPlan *g, Contig &ct, MixedSet &M, uint32_t k, u
 // __link_tls of the SV-mix engine (mutator.py:130-131 -- after the boundary pass, before __mutate_sequence): its draws follow
 // the boundary pass's in the CPython stream, so once the walk knows where that ended, a 16-sigma window of tempered words
 // from there comes over and plan_host.cpp links on it.  consumed grows by the words linking drew.
-static int mixed_link_translocations(Ctx *c, GpuPlan *g, MixedSet &M, uint32_t n_nsn, uint64_t p_b, size_t &consumed, bool &grew) {
+static int mixed_link_translocations(Ctx *c, GpuPlan *g, MixedSet &M, uint32_t n_nsn, uint64_t p_b, size_t &consumed, Grow &grow) {
     size_t n_tl = 0, n_tli = 0;
-    count_translocations(g->h_ntype, g->h_nstop, n_nsn, &n_tl, &n_tli);
+    count_translocations(g->h_ntype.p(), g->h_nstop.p(), n_nsn, &n_tl, &n_tli);
     uint32_t Wl = 0;
     int rc;
     if (n_tl) {                                            // (no TL: `if tls:` is false and nothing is drawn)
@@ -1907,16 +1935,16 @@ static int mixed_link_translocations(Ctx *c, GpuPlan *g, MixedSet &M, uint32_t n
         Wl = (uint32_t)wl;
         const uint64_t p_l = p_b + consumed;
         if ((rc = ensure_words(c, g, 0, p_l + Wl + 1))) return rc;
-        if ((rc = grow(c, (void **)&M.words, &M.cap_words, (size_t)Wl * 4 + 64, &grew))) return rc;
-        if (g->cap_h_win < (size_t)Wl * 4 && (rc = grow_host(c, (void **)&g->h_win, &g->cap_h_win, (size_t)Wl * 4))) return rc;
+        if ((rc = grow(M.words, (size_t)Wl * 4 + 64))) return rc;
+        if ((rc = grow.shared({{g->h_win, (size_t)Wl * 4}}))) return rc;
         hipLaunchKernelGGL(k_temper_window, dim3((Wl + 255) / 256), dim3(256), 0, c->stream, g->s[0].d_raw, (unsigned long long)p_l, Wl,
-                           M.words);
+                           M.words.p());
         MSIM_HIP(c, hipGetLastError());
-        MSIM_HIP(c, hipMemcpyAsync(g->h_win, M.words, (size_t)Wl * 4, hipMemcpyDeviceToHost, c->stream));
+        MSIM_HIP(c, hipMemcpyAsync(g->h_win.p(), M.words.p(), (size_t)Wl * 4, hipMemcpyDeviceToHost, c->stream));
         MSIM_HIP(c, wait_stream(c->stream));
     }
     size_t used = 0;
-    if ((rc = link_translocations(c, g->h_win, Wl, g->h_npos, g->h_ntype, g->h_nstop, g->h_nextra, g->h_naux, n_nsn, &used))) return rc;
+    if ((rc = link_translocations(c, g->h_win.p(), Wl, g->h_npos.p(), g->h_ntype.p(), g->h_nstop.p(), g->h_nextra.p(), g->h_naux.p(), n_nsn, &used))) return rc;
     consumed += used;
     return MSIM_OK;
 }
@@ -1956,15 +1984,15 @@ static double chain_share(const msim_range &r) {
 // which travels between the stops' copy and their scatter.  No launch is checked here: the caller asks hipGetLastError.
 static int verdicts_to_device(Ctx *c, GpuPlan *g, MixedSet &M, uint32_t n, uint32_t k, bool has_tl, uint32_t *visit_d = nullptr,
                               const uint32_t *visit_h = nullptr, size_t n_visit = 0) {
-    if (n) MSIM_HIP(c, hipMemcpyAsync(M.nsn_stop, g->h_nstop, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+    if (n) MSIM_HIP(c, hipMemcpyAsync(M.nsn_stop.p(), g->h_nstop.p(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
     if (n_visit) MSIM_HIP(c, hipMemcpyAsync(visit_d, visit_h, n_visit * 4, hipMemcpyHostToDevice, c->stream));
-    if (n) stop_scatter_launch(c->stream, M.nsn_rank, M.nsn_stop, n, M.cand_stop);
+    if (n) stop_scatter_launch(c->stream, M.nsn_rank.p(), M.nsn_stop.p(), n, M.cand_stop.p());
     if (has_tl) {
-        MSIM_HIP(c, hipMemsetAsync(M.cand_aux, 0, (size_t)k, c->stream));
+        MSIM_HIP(c, hipMemsetAsync(M.cand_aux.p(), 0, (size_t)k, c->stream));
         if (n) {
-            MSIM_HIP(c, hipMemcpyAsync(M.nsn_extra, g->h_nextra, (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
-            MSIM_HIP(c, hipMemcpyAsync(M.nsn_aux, g->h_naux, (size_t)n, hipMemcpyHostToDevice, c->stream));
-            link_scatter_launch(c->stream, M.nsn_rank, M.nsn_extra, M.nsn_aux, n, M.cand_extra, M.cand_aux);
+            MSIM_HIP(c, hipMemcpyAsync(M.nsn_extra.p(), g->h_nextra.p(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            MSIM_HIP(c, hipMemcpyAsync(M.nsn_aux.p(), g->h_naux.p(), (size_t)n, hipMemcpyHostToDevice, c->stream));
+            link_scatter_launch(c->stream, M.nsn_rank.p(), M.nsn_extra.p(), M.nsn_aux.p(), n, M.cand_extra.p(), M.cand_aux.p());
         }
     }
     return MSIM_OK;
@@ -1980,58 +2008,48 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
     int rc;
     if ((rc = session_open(c, g)) || (rc = chain_open(c, g, false))) return rc;
     GpuStream &py = g->s[0], &np = g->s[1];
-    bool grew = false;
+    Grow grow{c};
     MixedSet *Mp;
     if ((rc = mixed_acquire(c, g, false, Mp))) return rc;
     MixedSet &M = *Mp;
     const uint32_t nbk = (k + CB_BLOCK - 1) / CB_BLOCK;
-    if ((rc = grow(c, (void **)&M.cand_pos, &M.cap_pos, (size_t)k * 4 + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.cand_type, &M.cap_type, (size_t)k + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.cand_stop, &M.cap_stop, (size_t)k * 4 + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.nsn_pos, &M.cap_npos, (size_t)k * 4 + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.nsn_type, &M.cap_ntype, (size_t)k + 64, &grew))) return rc;
-    if (g->cap_h_npos < (size_t)k * 4 + 64 || g->cap_h_ntype < (size_t)k + 64 || g->cap_h_nstop < (size_t)k * 4 + 64) {
-        MSIM_HIP(c, wait_stream(c->stream));     // an earlier contig's copies may still use the old blocks
-        if (g->copy_stream) MSIM_HIP(c, wait_stream(g->copy_stream));
-        if ((rc = grow_host(c, (void **)&g->h_npos, &g->cap_h_npos, (size_t)k * 4 + 64))) return rc;
-        if ((rc = grow_host(c, (void **)&g->h_ntype, &g->cap_h_ntype, (size_t)k + 64))) return rc;
-        if ((rc = grow_host(c, (void **)&g->h_nstop, &g->cap_h_nstop, (size_t)k * 4 + 64))) return rc;
-    }
-    if ((rc = grow(c, (void **)&M.nsn_rank, &M.cap_nrank, (size_t)k * 4 + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.nsn_stop, &M.cap_nstop, (size_t)k * 4 + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.sn_index, &M.cap_snidx, (size_t)k * 4 + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.cnt, &M.cap_cnt, mixed_cnt_bytes(nbk), &grew))) return rc;
+    if ((rc = grow(M.cand_pos, (size_t)k * 4 + 64))) return rc;
+    if ((rc = grow(M.cand_type, (size_t)k + 64))) return rc;
+    if ((rc = grow(M.cand_stop, (size_t)k * 4 + 64))) return rc;
+    if ((rc = grow(M.nsn_pos, (size_t)k * 4 + 64))) return rc;
+    if ((rc = grow(M.nsn_type, (size_t)k + 64))) return rc;
+    if ((rc = grow.shared({{g->h_npos, (size_t)k * 4 + 64}, {g->h_ntype, (size_t)k + 64},
+                           {g->h_nstop, (size_t)k * 4 + 64}}))) return rc;
+    if ((rc = grow(M.nsn_rank, (size_t)k * 4 + 64))) return rc;
+    if ((rc = grow(M.nsn_stop, (size_t)k * 4 + 64))) return rc;
+    if ((rc = grow(M.sn_index, (size_t)k * 4 + 64))) return rc;
+    if ((rc = grow(M.cnt, mixed_cnt_bytes(nbk)))) return rc;
     const bool has_tl = range_draws_translocations(r);
     if (has_tl) {                                          // what __link_tls decides, per candidate and in chain order
-        if ((rc = grow(c, (void **)&M.cand_extra, &M.cap_cextra, (size_t)k * 4 + 64, &grew))) return rc;
-        if ((rc = grow(c, (void **)&M.cand_aux, &M.cap_caux, (size_t)k + 64, &grew))) return rc;
-        if ((rc = grow(c, (void **)&M.nsn_extra, &M.cap_nextra, (size_t)k * 4 + 64, &grew))) return rc;
-        if ((rc = grow(c, (void **)&M.nsn_aux, &M.cap_naux, (size_t)k + 64, &grew))) return rc;
-        if (g->cap_h_nextra < (size_t)k * 4 + 64 || g->cap_h_naux < (size_t)k + 64) {
-            MSIM_HIP(c, wait_stream(c->stream));
-            if (g->copy_stream) MSIM_HIP(c, wait_stream(g->copy_stream));
-            if ((rc = grow_host(c, (void **)&g->h_nextra, &g->cap_h_nextra, (size_t)k * 4 + 64))) return rc;
-            if ((rc = grow_host(c, (void **)&g->h_naux, &g->cap_h_naux, (size_t)k + 64))) return rc;
-        }
+        if ((rc = grow(M.cand_extra, (size_t)k * 4 + 64))) return rc;
+        if ((rc = grow(M.cand_aux, (size_t)k + 64))) return rc;
+        if ((rc = grow(M.nsn_extra, (size_t)k * 4 + 64))) return rc;
+        if ((rc = grow(M.nsn_aux, (size_t)k + 64))) return rc;
+        if ((rc = grow.shared({{g->h_nextra, (size_t)k * 4 + 64}, {g->h_naux, (size_t)k + 64}}))) return rc;
     }
-    uint32_t *cnt_nsn = M.cnt;                             // (the other four counter arrays: mixed_emit)
+    uint32_t *cnt_nsn = M.cnt.p();                             // (the other four counter arrays: mixed_emit)
 
     // ---- 1. sample -> bitmap; bitmap -> candidates with types; non-SNP candidates compacted
     SampleLaunch sl;
-    if ((rc = enqueue_sample_chain(c, g, r, d, py.pos, grew, sl))) return rc;
+    if ((rc = enqueue_sample_chain(c, g, r, d, py.pos, grow, sl))) return rc;
     SampleSet &S = *sl.S;
     const uint64_t np_base = np.pos;                       // exact: the NumPy stream never rejects
     if ((rc = ensure_words(c, g, 1, np_base + 2ull * k + 1))) return rc;
-    cand_front_launch(c->stream, reinterpret_cast<const uint64_t *>(S.bitmap), sl.bmw, S.cnt2, (uint32_t)r.start, (uint32_t)d, np.d_raw,
-                      (unsigned long long)np_base, type_table_of(r), M.cand_pos, M.cand_type);
-    nsn_compact_launch(c->stream, M.cand_pos, M.cand_type, k, cnt_nsn, M.nsn_pos, M.nsn_type, M.nsn_rank, g->d_ps, false);
+    cand_front_launch(c->stream, reinterpret_cast<const uint64_t *>(S.bitmap.p()), sl.bmw, S.cnt2.p(), (uint32_t)r.start, (uint32_t)d, np.d_raw,
+                      (unsigned long long)np_base, type_table_of(r), M.cand_pos.p(), M.cand_type.p());
+    nsn_compact_launch(c->stream, M.cand_pos.p(), M.cand_type.p(), k, cnt_nsn, M.nsn_pos.p(), M.nsn_type.p(), M.nsn_rank.p(), g->d_ps, false);
     MSIM_HIP(c, hipGetLastError());
     S.pending = false;                                     // consumed on the plan stream itself
     // The host walks the non-SNP candidates.  Their copy starts at once: a 16-sigma bound of the type draw's binomial, in pieces
     if ((rc = ensure_signals(c, g))) return rc;
     const double q_nsn = chain_share(r);
     const uint32_t n_hi = std::min(g->cand_cap, (uint32_t)std::min<double>(k, q_nsn * k + 16.0 * std::sqrt(q_nsn * (1.0 - q_nsn) * k) + 64.0));
-    const HandLane c_pos{g->h_npos, M.nsn_pos, 4, 0}, c_type{g->h_ntype, M.nsn_type, 1, 0};
+    const HandLane c_pos{g->h_npos.p(), M.nsn_pos.p(), 4, 0}, c_type{g->h_ntype.p(), M.nsn_type.p(), 1, 0};
     Handover cands, cands_rest, tabs;
     if ((rc = cands_to_host(c, g, cands, c_pos, c_type, 0, n_hi, 3))) return rc;
     // The accept tables of the boundary walk depend on where the sample ended (the device knows) and on the window's size --
@@ -2047,22 +2065,19 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
     // the tables' hand-over, Wb + 1 rows of 1 << lg entries: on the plan stream, behind the kernel that makes them
     auto tables_to_host = [&](uint32_t Wb) {
         return tabs.send(c, c->stream, g->ev_piece, "spin_event(accept-table piece, plan stream)", 0, (size_t)Wb + 1,
-                         {HandLane{g->h_words, M.words, (size_t)4 << lg, 0}});
+                         {HandLane{g->h_words.p(), M.words.p(), (size_t)4 << lg, 0}});
     };
     if (early) {
         const size_t bytes = ((size_t)(Wb_hi + 1) << lg) * 4;
-        if (g->cap_h_words < bytes) {
-            MSIM_HIP(c, wait_stream(c->stream));
-            if ((rc = grow_host(c, (void **)&g->h_words, &g->cap_h_words, bytes))) return rc;
-        }
-        if ((rc = grow(c, (void **)&M.words, &M.cap_words, bytes, &grew))) return rc;
+        if ((rc = grow.shared({{g->h_words, bytes}}))) return rc;
+        if ((rc = grow(M.words, bytes))) return rc;
         if ((rc = ensure_words(c, g, 0, py.pos + sl.W + Wb_hi + 2))) return rc;      // (the sample ends below py.pos + W)
     }
     PlanState h;
     const auto tq0 = std::chrono::steady_clock::now();
     rc = mixed_poll(c, g, h, [&]() -> int {
         if (!early) return MSIM_OK;
-        accept_tables_ps_launch(c->stream, py.d_raw, g->d_ps, Wb_hi, cc, lg, M.words);
+        accept_tables_ps_launch(c->stream, py.d_raw, g->d_ps, Wb_hi, cc, lg, M.words.p());
         MSIM_HIP(c, hipGetLastError());
         return tables_to_host(Wb_hi);
     });
@@ -2083,17 +2098,14 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
         const uint32_t Wb = early_ok ? Wb_hi : (uint32_t)wb;
         const size_t words_bytes = tables ? ((size_t)(Wb + 1) << lg) * 4 : (size_t)Wb * 4;
         if (!early_ok) {
-            if (g->cap_h_words < words_bytes) {
-                MSIM_HIP(c, wait_stream(c->stream));
-                if ((rc = grow_host(c, (void **)&g->h_words, &g->cap_h_words, words_bytes))) return rc;
-            }
-            if ((rc = grow(c, (void **)&M.words, &M.cap_words, words_bytes, &grew))) return rc;
+            if ((rc = grow.shared({{g->h_words, words_bytes}}))) return rc;
+            if ((rc = grow(M.words, words_bytes))) return rc;
             if ((rc = ensure_words(c, g, 0, p_b + Wb + 1))) return rc;
         }
         if (n_nsn > n_hi && (rc = cands_to_host(c, g, cands_rest, c_pos, c_type, n_hi, n_nsn, 1))) return rc;   // beyond 16 sigma
         if (tables) {
             if (!early_ok) {                               // (not launched behind the mailbox: now, with the exact window)
-                accept_tables_launch(c->stream, py.d_raw, (unsigned long long)p_b, Wb, cc, lg, M.words);
+                accept_tables_launch(c->stream, py.d_raw, (unsigned long long)p_b, Wb, cc, lg, M.words.p());
                 MSIM_HIP(c, hipGetLastError());
                 if ((rc = tables_to_host(Wb))) return rc;
             }
@@ -2117,7 +2129,7 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
                     Handover &from = cands.drained() ? cands_rest : cands;   // (the rest: beyond 16 sigma)
                     if (from.drained() || (rc = from.more(&avail_c))) break;
                     avail_c = std::min<size_t>(avail_c, n_nsn);
-                    if (!ChainWalk::types_ok(g->h_ntype + had, avail_c - had, has_tl)) {
+                    if (!ChainWalk::types_ok(g->h_ntype.p() + had, avail_c - had, has_tl)) {
                         rc = fail(c, MSIM_ERR_HIP, "boundary chain: candidate type outside the range's draw");
                         break;
                     }
@@ -2126,8 +2138,8 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
                     if (tabs.drained() || (rc = tabs.more(&avail_w))) break;   // (drained: the window is used up, finish() reports it)
                 }
                 lap(t_wait);
-                if (has_tl) cw.run_tl(g->h_npos, g->h_ntype, avail_c, g->h_words, avail_w, g->h_nstop);
-                else cw.run(g->h_npos, g->h_ntype, avail_c, g->h_words, avail_w, g->h_nstop);
+                if (has_tl) cw.run_tl(g->h_npos.p(), g->h_ntype.p(), avail_c, g->h_words.p(), avail_w, g->h_nstop.p());
+                else cw.run(g->h_npos.p(), g->h_ntype.p(), avail_c, g->h_words.p(), avail_w, g->h_nstop.p());
                 lap(t_run);
             }
             if (!rc) rc = spin_event(c, g->ev_cand, "spin_event(candidates of the host chain, copy stream)");       // (every copy into the pinned blocks has landed before they are reused)
@@ -2144,9 +2156,9 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
             }
         } else {
             hipLaunchKernelGGL(k_temper_window, dim3((Wb + 255) / 256), dim3(256), 0, c->stream, py.d_raw,
-                               (unsigned long long)p_b, Wb, M.words);
+                               (unsigned long long)p_b, Wb, M.words.p());
             MSIM_HIP(c, hipGetLastError());
-            MSIM_HIP(c, hipMemcpyAsync(g->h_words, M.words, words_bytes, hipMemcpyDeviceToHost, c->stream));
+            MSIM_HIP(c, hipMemcpyAsync(g->h_words.p(), M.words.p(), words_bytes, hipMemcpyDeviceToHost, c->stream));
             MSIM_HIP(c, hipEventRecord(g->t1, c->stream));
             if ((rc = flush_deferred_apply(c, true))) return rc;
             MSIM_HIP(c, wait_stream(c->stream));
@@ -2154,17 +2166,17 @@ int plan_contig_gpu_mixed(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *rang
             if ((rc = span_close(c, g))) return rc;
             size_t kept_host = 0;
             long long delta_host = 0;                      // both are summed on the device, where the stops end up
-            rc = chain_boundary_host(c, r, ct.len, g->h_npos, g->h_ntype, n_nsn, g->h_words, Wb, g->h_nstop,
+            rc = chain_boundary_host(c, r, ct.len, g->h_npos.p(), g->h_ntype.p(), n_nsn, g->h_words.p(), Wb, g->h_nstop.p(),
                                      &consumed, &kept_host, &delta_host);
         }
-        if (!rc && has_tl) rc = mixed_link_translocations(c, g, M, n_nsn, p_b, consumed, grew);
+        if (!rc && has_tl) rc = mixed_link_translocations(c, g, M, n_nsn, p_b, consumed, grow);
         if (rc) { plan_failed(g); return rc; }
         MSIM_HIP(c, hipEventRecord(g->t0, c->stream));    // the host chain is not GPU time
     }
     if ((rc = verdicts_to_device(c, g, M, n_nsn, k, has_tl))) return rc;
     if (has_tl) MSIM_HIP(c, hipGetLastError());
     const uint64_t p_s = p_b + consumed;                   // the SNP draws of __mutate_sequence start here
-    return mixed_emit(c, g, ct, M, k, p_s, nullptr, 0, nullptr, false, grew, has_tl);
+    return mixed_emit(c, g, ct, M, k, p_s, nullptr, 0, nullptr, false, grow, has_tl);
 }
 
 
@@ -2220,37 +2232,33 @@ int plan_contig_gpu_hostsample(Ctx *c, GpuPlan *g, Contig &ct, const msim_range 
     const double wd = e_words + 16.0 * std::sqrt(var) + 65536.0;
     if (wd >= 4.0e9) return fail(c, MSIM_ERR_UNSUPPORTED, "sample window beyond 2^32 words");
     const uint32_t W = (uint32_t)wd;
-    bool grew = false;
+    Grow grow{c};
     MixedSet *Mp;
     if ((rc = mixed_acquire(c, g, true, Mp))) return rc;   // (the host writes the set's pinned range table below)
     MixedSet &M = *Mp;
     // what the host hands back: one cut per drawing range (+ the end) and the pool-path positions
     const size_t n_back = (size_t)n_draw + 1 + K_pool;
-    if ((rc = grow(c, (void **)&M.words, &M.cap_words, (size_t)W * 4, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.cand_pos, &M.cap_pos, n_back * 4 + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.walk_d, &M.cap_walk_d, (size_t)n_draw * sizeof(WalkRange) + 64, &grew))) return rc;
-    if ((rc = grow_host(c, (void **)&M.walk_h, &M.cap_walk_h, (size_t)n_draw * sizeof(WalkRange) + 64))) return rc;
-    if (g->cap_h_words < (size_t)W * 4 || g->cap_h_npos < n_back * 4 + 64) {
-        MSIM_HIP(c, wait_stream(c->stream));     // an earlier contig's copies may still use the old blocks
-        if ((rc = grow_host(c, (void **)&g->h_words, &g->cap_h_words, (size_t)W * 4))) return rc;
-        if ((rc = grow_host(c, (void **)&g->h_npos, &g->cap_h_npos, n_back * 4 + 64))) return rc;
-    }
+    if ((rc = grow(M.words, (size_t)W * 4))) return rc;
+    if ((rc = grow(M.cand_pos, n_back * 4 + 64))) return rc;
+    if ((rc = grow(M.walk_d, (size_t)n_draw * sizeof(WalkRange) + 64))) return rc;
+    if ((rc = grow.own(M.walk_h, (size_t)n_draw * sizeof(WalkRange) + 64))) return rc;
+    if ((rc = grow.shared({{g->h_words, (size_t)W * 4}, {g->h_npos, n_back * 4 + 64}}))) return rc;
     if (!M.p0_slot) MSIM_HIP(c, hipMalloc(&M.p0_slot, 64));
     const uint32_t bmw = (uint32_t)((ct.len + 63) / 64);  // contig-wide bitmap, 64-bit words
     const uint32_t bnb = (bmw + BM_THREADS - 1) / BM_THREADS;
     {
         const size_t want = (size_t)bmw * 8 + 64;
-        if (M.cap_wbits < want) {
-            const size_t before = M.cap_wbits;
-            if ((rc = grow(c, (void **)&M.wbits, &M.cap_wbits, want, &grew))) return rc;
-            if (M.cap_wbits != before) MSIM_HIP(c, hipMemset(M.wbits, 0, M.cap_wbits));   // k_walk_expand leaves it zeroed
+        if (M.wbits.cap < want) {
+            const size_t before = M.wbits.cap;
+            if ((rc = grow(M.wbits, want))) return rc;
+            if (M.wbits.cap != before) MSIM_HIP(c, hipMemset(M.wbits.p(), 0, M.wbits.cap));   // k_walk_expand leaves it zeroed
         }
         if (M.wbits_dirty) {
-            MSIM_HIP(c, hipMemsetAsync(M.wbits, 0, M.cap_wbits, c->stream));
+            MSIM_HIP(c, hipMemsetAsync(M.wbits.p(), 0, M.wbits.cap, c->stream));
             M.wbits_dirty = false;
         }
     }
-    if ((rc = grow(c, (void **)&M.wcnt, &M.cap_wcnt, (size_t)(bnb + 2) * sizeof(uint32_t), &grew))) return rc;
+    if ((rc = grow(M.wcnt, (size_t)(bnb + 2) * sizeof(uint32_t)))) return rc;
     if (!c->chain_only) {   // the record table may still be read by an earlier apply of this contig
         const size_t want = (size_t)K * sizeof(msim_record);
         if (ct.cap_recs < want || ct.cap_pool < 2 * PAD) {
@@ -2269,28 +2277,28 @@ int plan_contig_gpu_hostsample(Ctx *c, GpuPlan *g, Contig &ct, const msim_range 
             WalkRange w;
             w.start = (uint32_t)r.start; w.k = (uint32_t)r.k; w.n = (uint32_t)n; w.rec_base = base;
             w.pool = n <= r.setsize ? 1u : 0u;
-            M.walk_h[at++] = w;
+            M.walk_h.p()[at++] = w;
             base += (uint32_t)r.k;
         }
     }
     if ((rc = ensure_words(c, g, 0, py.pos + W + 1))) return rc;
-    hipLaunchKernelGGL(k_temper_window_ps, dim3((W + 255) / 256), dim3(256), 0, c->stream, py.d_raw, g->d_ps, W, M.words);
+    hipLaunchKernelGGL(k_temper_window_ps, dim3((W + 255) / 256), dim3(256), 0, c->stream, py.d_raw, g->d_ps, W, M.words.p());
     MSIM_HIP(c, hipGetLastError());
     if ((rc = ensure_signals(c, g))) return rc;
     Handover win;                                          // the window comes over in pieces
-    if ((rc = win.send(c, c->stream, g->ev_piece, "spin_event(word-window piece, plan stream)", 0, W, {HandLane{g->h_words, M.words, 4, 0}})))
+    if ((rc = win.send(c, c->stream, g->ev_piece, "spin_event(word-window piece, plan stream)", 0, W, {HandLane{g->h_words.p(), M.words.p(), 4, 0}})))
         return rc;
     MSIM_HIP(c, hipEventRecord(g->t1, c->stream));
-    MSIM_HIP(c, hipMemcpyAsync(M.walk_d, M.walk_h, (size_t)n_draw * sizeof(WalkRange), hipMemcpyHostToDevice, c->stream));
+    MSIM_HIP(c, hipMemcpyAsync(M.walk_d.p(), M.walk_h.p(), (size_t)n_draw * sizeof(WalkRange), hipMemcpyHostToDevice, c->stream));
     const auto tp1 = std::chrono::steady_clock::now();
     // ---- the host finds the stream cuts (and samples the pool-path ranges); everything per position stays here
     size_t consumed = 0, n_pool_pos = 0;
-    uint32_t *h_cut = g->h_npos, *h_pool = g->h_npos + n_draw + 1;
+    uint32_t *h_cut = g->h_npos.p(), *h_pool = g->h_npos.p() + n_draw + 1;
     const WordFeed feed = win.feed();
     if ((rc = flush_deferred_apply_behind(c, win.last()))) return rc;   // the previous contig's APPLY
     {
         const auto cw0 = std::chrono::steady_clock::now();
-        rc = cut_ranges_host(c, ranges, n_ranges, d, g->h_words, W, h_cut, h_pool, &n_pool_pos, &consumed, &feed);
+        rc = cut_ranges_host(c, ranges, n_ranges, d, g->h_words.p(), W, h_cut, h_pool, &n_pool_pos, &consumed, &feed);
         const double all_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - cw0).count();
         c->t.host_walk_wait_ms += win.wait_us * 1e-3;
         c->t.host_walk_run_ms += std::max(0.0, all_ms - win.wait_us * 1e-3);
@@ -2303,7 +2311,7 @@ int plan_contig_gpu_hostsample(Ctx *c, GpuPlan *g, Contig &ct, const msim_range 
     if (rc) { plan_failed(g); M.wbits_dirty = true; return rc; }
     const auto tp3 = std::chrono::steady_clock::now();
     MSIM_HIP(c, hipEventRecord(g->t0, c->stream));        // the host chain is not GPU time
-    MSIM_HIP(c, hipMemcpyAsync(M.cand_pos, g->h_npos, ((size_t)n_draw + 1 + n_pool_pos) * 4, hipMemcpyHostToDevice, c->stream));
+    MSIM_HIP(c, hipMemcpyAsync(M.cand_pos.p(), g->h_npos.p(), ((size_t)n_draw + 1 + n_pool_pos) * 4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_advance_pos_save, dim3(1), dim3(1), 0, c->stream, g->d_ps, (unsigned long long)consumed, M.p0_slot);
     MSIM_HIP(c, hipGetLastError());
     if (!c->chain_only) {   // records on the emit stream (ordered after any earlier APPLY that still reads this contig's table): the
@@ -2312,15 +2320,15 @@ int plan_contig_gpu_hostsample(Ctx *c, GpuPlan *g, Contig &ct, const msim_range 
         MSIM_HIP(c, hipEventRecord(ce0, c->stream));
         MSIM_HIP(c, hipStreamWaitEvent(c->emit_stream, ce0, 0));
         hipLaunchKernelGGL(k_interval_bits, dim3(((uint32_t)consumed + 255) / 256), dim3(256), 0, c->emit_stream, py.d_raw,
-                           M.p0_slot, (uint32_t)consumed, M.cand_pos, M.walk_d, n_draw, reinterpret_cast<uint32_t *>(M.wbits));
+                           M.p0_slot, (uint32_t)consumed, M.cand_pos.p(), M.walk_d.p(), n_draw, reinterpret_cast<uint32_t *>(M.wbits.p()));
         if (n_pool_pos)
             hipLaunchKernelGGL(k_list_to_bits, dim3(((uint32_t)n_pool_pos + 255) / 256), dim3(256), 0, c->emit_stream,
-                               M.cand_pos + n_draw + 1, (uint32_t)n_pool_pos, reinterpret_cast<uint32_t *>(M.wbits));
+                               M.cand_pos.p() + n_draw + 1, (uint32_t)n_pool_pos, reinterpret_cast<uint32_t *>(M.wbits.p()));
         hipLaunchKernelGGL(k_bitmap_count, dim3(bnb), dim3(BM_THREADS), 0, c->emit_stream,
-                           reinterpret_cast<const uint64_t *>(M.wbits), bmw, M.wcnt);
-        hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->emit_stream, M.wcnt, bnb);
+                           reinterpret_cast<const uint64_t *>(M.wbits.p()), bmw, M.wcnt.p());
+        hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->emit_stream, M.wcnt.p(), bnb);
         hipLaunchKernelGGL(k_walk_expand, dim3(bnb), dim3(BM_THREADS), 0, c->emit_stream,
-                           reinterpret_cast<uint64_t *>(M.wbits), bmw, M.wcnt, M.walk_d, n_draw, (uint32_t)d, ct.d_recs);
+                           reinterpret_cast<uint64_t *>(M.wbits.p()), bmw, M.wcnt.p(), M.walk_d.p(), n_draw, (uint32_t)d, ct.d_recs);
         MSIM_HIP(c, hipGetLastError());
     }
     ct.n_rec = K;
@@ -2329,7 +2337,7 @@ int plan_contig_gpu_hostsample(Ctx *c, GpuPlan *g, Contig &ct, const msim_range 
     ct.all_snp = true;
     uint64_t pos_hi = py.pos + consumed;
     if (K) {                                          // SNP draws in position order (chain: scan + cut; aux off the chain)
-        if ((rc = enqueue_snp_stage(c, g, ct, K, nullptr, pos_hi, grew))) return rc;
+        if ((rc = enqueue_snp_stage(c, g, ct, K, nullptr, pos_hi, grow))) return rc;
     }
     MSIM_HIP(c, hipEventRecord(M.emit_done, c->emit_stream));
     M.pending = true;
@@ -2413,56 +2421,44 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
     if (wd >= 1.0e9) return fail(c, MSIM_ERR_UNSUPPORTED, "host-chain window beyond 2^30 words");
     const uint32_t W = (uint32_t)wd;
     const uint32_t n_hi = std::min(g->cand_cap, ms.sn_chained ? K : (uint32_t)std::min<double>(K, e_ch + 16.0 * std::sqrt(var_ch) + 64.0));
-    bool grew = false;
+    Grow grow{c};
     MixedSet *Mp;
     if ((rc = mixed_acquire(c, g, true, Mp))) return rc;   // (the host writes the set's pinned tables below)
     MixedSet &M = *Mp;
     const uint32_t nbk = (K + CB_BLOCK - 1) / CB_BLOCK;
     const size_t n_slots = ((size_t)W + 1) << lg;
-    if ((rc = grow(c, (void **)&M.cand_pos, &M.cap_pos, (size_t)K * 4 + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.cand_type, &M.cap_type, (size_t)K + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.cand_stop, &M.cap_stop, (size_t)K * 4 + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.nsn_type, &M.cap_ntype, (size_t)K + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.nsn_rank, &M.cap_nrank, (size_t)K * 4 + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.nsn_stop, &M.cap_nstop, (size_t)K * 4 + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.sn_index, &M.cap_snidx, (size_t)K * 4 + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.cnt, &M.cap_cnt, mixed_cnt_bytes(nbk), &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.words, &M.cap_words, (size_t)W * 4 + 64, &grew))) return rc;
-    if ((rc = grow(c, (void **)&M.tables, &M.cap_tables, n_slots * 4 + 64, &grew))) return rc;
+    if ((rc = grow(M.cand_pos, (size_t)K * 4 + 64))) return rc;
+    if ((rc = grow(M.cand_type, (size_t)K + 64))) return rc;
+    if ((rc = grow(M.cand_stop, (size_t)K * 4 + 64))) return rc;
+    if ((rc = grow(M.nsn_type, (size_t)K + 64))) return rc;
+    if ((rc = grow(M.nsn_rank, (size_t)K * 4 + 64))) return rc;
+    if ((rc = grow(M.nsn_stop, (size_t)K * 4 + 64))) return rc;
+    if ((rc = grow(M.sn_index, (size_t)K * 4 + 64))) return rc;
+    if ((rc = grow(M.cnt, mixed_cnt_bytes(nbk)))) return rc;
+    if ((rc = grow(M.words, (size_t)W * 4 + 64))) return rc;
+    if ((rc = grow(M.tables, n_slots * 4 + 64))) return rc;
     if (ms.has_tl) {
-        if ((rc = grow(c, (void **)&M.cand_extra, &M.cap_cextra, (size_t)K * 4 + 64, &grew))) return rc;
-        if ((rc = grow(c, (void **)&M.cand_aux, &M.cap_caux, (size_t)K + 64, &grew))) return rc;
-        if ((rc = grow(c, (void **)&M.nsn_extra, &M.cap_nextra, (size_t)K * 4 + 64, &grew))) return rc;
-        if ((rc = grow(c, (void **)&M.nsn_aux, &M.cap_naux, (size_t)K + 64, &grew))) return rc;
+        if ((rc = grow(M.cand_extra, (size_t)K * 4 + 64))) return rc;
+        if ((rc = grow(M.cand_aux, (size_t)K + 64))) return rc;
+        if ((rc = grow(M.nsn_extra, (size_t)K * 4 + 64))) return rc;
+        if ((rc = grow(M.nsn_aux, (size_t)K + 64))) return rc;
     }
     // range table | type tables | visit_from, one device block and one pinned block per scratch set
     const size_t off_sets = ((size_t)n_draw * sizeof(MixRangeDev) + 63) & ~(size_t)63;
     const size_t off_visit = (off_sets + (size_t)n_sets * sizeof(TypeTable) + 63) & ~(size_t)63;
     const size_t mm_bytes = off_visit + (size_t)n_draw * 4 + 64;
-    if ((rc = grow(c, (void **)&M.mm_d, &M.cap_mm_d, mm_bytes, &grew))) return rc;
-    if ((rc = grow_host(c, (void **)&M.mm_h, &M.cap_mm_h, mm_bytes))) return rc;
-    if (g->cap_h_words < n_slots * 4 || g->cap_h_win < (size_t)W * 4 || g->cap_h_npos < (size_t)K * 4 + 64 ||
-        g->cap_h_ntype < (size_t)K + 64 || g->cap_h_nstop < (size_t)K * 4 + 64 || g->cap_h_nrank < (size_t)K * 4 + 64 ||
-        (ms.has_tl && (g->cap_h_nextra < (size_t)K * 4 + 64 || g->cap_h_naux < (size_t)K + 64))) {
-        MSIM_HIP(c, wait_stream(c->stream));     // an earlier contig's copies may still use the old blocks
-        if (g->copy_stream) MSIM_HIP(c, wait_stream(g->copy_stream));
-        if ((rc = grow_host(c, (void **)&g->h_words, &g->cap_h_words, n_slots * 4))) return rc;
-        if ((rc = grow_host(c, (void **)&g->h_win, &g->cap_h_win, (size_t)W * 4))) return rc;
-        if ((rc = grow_host(c, (void **)&g->h_npos, &g->cap_h_npos, (size_t)K * 4 + 64))) return rc;
-        if ((rc = grow_host(c, (void **)&g->h_ntype, &g->cap_h_ntype, (size_t)K + 64))) return rc;
-        if ((rc = grow_host(c, (void **)&g->h_nstop, &g->cap_h_nstop, (size_t)K * 4 + 64))) return rc;
-        if ((rc = grow_host(c, (void **)&g->h_nrank, &g->cap_h_nrank, (size_t)K * 4 + 64))) return rc;
-        if (ms.has_tl) {
-            if ((rc = grow_host(c, (void **)&g->h_nextra, &g->cap_h_nextra, (size_t)K * 4 + 64))) return rc;
-            if ((rc = grow_host(c, (void **)&g->h_naux, &g->cap_h_naux, (size_t)K + 64))) return rc;
-        }
-    }
-    MixRangeDev *rt_h = reinterpret_cast<MixRangeDev *>(M.mm_h);
-    TypeTable *sets_h = reinterpret_cast<TypeTable *>(M.mm_h + off_sets);
-    uint32_t *visit_h = reinterpret_cast<uint32_t *>(M.mm_h + off_visit);
-    const MixRangeDev *rt_d = reinterpret_cast<const MixRangeDev *>(M.mm_d);
-    const TypeTable *sets_d = reinterpret_cast<const TypeTable *>(M.mm_d + off_sets);
-    uint32_t *visit_d = reinterpret_cast<uint32_t *>(M.mm_d + off_visit);
+    if ((rc = grow(M.mm_d, mm_bytes))) return rc;
+    if ((rc = grow.own(M.mm_h, mm_bytes))) return rc;
+    const size_t tl4 = ms.has_tl ? (size_t)K * 4 + 64 : 0, tl1 = ms.has_tl ? (size_t)K + 64 : 0;   // (0: the block is not wanted)
+    if ((rc = grow.shared({{g->h_words, n_slots * 4}, {g->h_win, (size_t)W * 4}, {g->h_npos, (size_t)K * 4 + 64},
+                        {g->h_ntype, (size_t)K + 64}, {g->h_nstop, (size_t)K * 4 + 64}, {g->h_nrank, (size_t)K * 4 + 64},
+                        {g->h_nextra, tl4}, {g->h_naux, tl1}}))) return rc;
+    MixRangeDev *rt_h = reinterpret_cast<MixRangeDev *>(M.mm_h.p());
+    TypeTable *sets_h = reinterpret_cast<TypeTable *>(M.mm_h.p() + off_sets);
+    uint32_t *visit_h = reinterpret_cast<uint32_t *>(M.mm_h.p() + off_visit);
+    const MixRangeDev *rt_d = reinterpret_cast<const MixRangeDev *>(M.mm_d.p());
+    const TypeTable *sets_d = reinterpret_cast<const TypeTable *>(M.mm_d.p() + off_sets);
+    uint32_t *visit_d = reinterpret_cast<uint32_t *>(M.mm_d.p() + off_visit);
     {
         uint32_t di = 0, base = 0;
         for (int i = 0; i < n_ranges; i++) {
@@ -2479,22 +2475,22 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
     if ((rc = ensure_words(c, g, 0, py.pos + W + 1))) return rc;
     if ((rc = ensure_words(c, g, 1, np_base + 2ull * K + 1))) return rc;
     if ((rc = ensure_signals(c, g))) return rc;
-    MSIM_HIP(c, hipMemcpyAsync(M.mm_d, M.mm_h, off_visit, hipMemcpyHostToDevice, c->stream));
-    types_multi_launch(c->stream, np.d_raw, (unsigned long long)np_base, K, rt_d, n_draw, sets_d, M.cand_type);
-    nsn_compact_launch(c->stream, nullptr, M.cand_type, K, M.cnt, nullptr, M.nsn_type, M.nsn_rank, g->d_ps, ms.sn_chained);
+    MSIM_HIP(c, hipMemcpyAsync(M.mm_d.p(), M.mm_h.p(), off_visit, hipMemcpyHostToDevice, c->stream));
+    types_multi_launch(c->stream, np.d_raw, (unsigned long long)np_base, K, rt_d, n_draw, sets_d, M.cand_type.p());
+    nsn_compact_launch(c->stream, nullptr, M.cand_type.p(), K, M.cnt.p(), nullptr, M.nsn_type.p(), M.nsn_rank.p(), g->d_ps, ms.sn_chained);
     MSIM_HIP(c, hipGetLastError());
-    const HandLane c_rank{g->h_nrank, M.nsn_rank, 4, 0}, c_type{g->h_ntype, M.nsn_type, 1, 0};
+    const HandLane c_rank{g->h_nrank.p(), M.nsn_rank.p(), 4, 0}, c_type{g->h_ntype.p(), M.nsn_type.p(), 1, 0};
     Handover cands, win;
     if ((rc = cands_to_host(c, g, cands, c_rank, c_type, 0, n_hi, 1))) return rc;   // a 16-sigma bound of their number, in one copy
-    hipLaunchKernelGGL(k_temper_window_ps, dim3((W + 255) / 256), dim3(256), 0, c->stream, py.d_raw, g->d_ps, W, M.words);
-    accept_tables_ps_launch(c->stream, py.d_raw, g->d_ps, W, ms.gcc, lg, M.tables);
+    hipLaunchKernelGGL(k_temper_window_ps, dim3((W + 255) / 256), dim3(256), 0, c->stream, py.d_raw, g->d_ps, W, M.words.p());
+    accept_tables_ps_launch(c->stream, py.d_raw, g->d_ps, W, ms.gcc, lg, M.tables.p());
     MSIM_HIP(c, hipGetLastError());
     // Window and tables come over in the same pieces, the tables with their end-of-window sentinel.  Their copies go out
     // behind the mailbox kernel, before the host polls: nothing of them depends on what the poll tells.
     PlanState h;
     rc = mixed_poll(c, g, h, [&]() -> int {                // exact stream position + the chain's length
         return win.send(c, c->stream, g->ev_piece, "spin_event(word-window piece, plan stream)", 0, W,
-                        {HandLane{g->h_win, M.words, 4, 0}, HandLane{g->h_words, M.tables, (size_t)4 << lg, 1}});
+                        {HandLane{g->h_win.p(), M.words.p(), 4, 0}, HandLane{g->h_words.p(), M.tables.p(), (size_t)4 << lg, 1}});
     });
     if (rc) return rc;
     const uint32_t n_ch = h.n_nsn;
@@ -2512,9 +2508,9 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
     rc = cands.more(&n_there);                             // all of the chain's candidates (one copy, or the rest of them)
     const auto mw0 = std::chrono::steady_clock::now();
     c->t.host_walk_wait_ms += std::chrono::duration<double, std::milli>(mw0 - tp1).count();
-    if (!rc) rc = multimix_walk_host(c, ct.len, ranges, n_ranges, d, ms, g->h_win, g->h_words, W, g->h_nrank, g->h_ntype, n_ch,
-                                     g->h_npos, g->h_nstop, visit_h, &consumed, &feed, ms.has_tl ? g->h_nextra : nullptr,
-                                     ms.has_tl ? g->h_naux : nullptr);
+    if (!rc) rc = multimix_walk_host(c, ct.len, ranges, n_ranges, d, ms, g->h_win.p(), g->h_words.p(), W, g->h_nrank.p(), g->h_ntype.p(), n_ch,
+                                     g->h_npos.p(), g->h_nstop.p(), visit_h, &consumed, &feed, ms.has_tl ? g->h_nextra.p() : nullptr,
+                                     ms.has_tl ? g->h_naux.p() : nullptr);
     {
         const double all_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - mw0).count();
         c->t.host_walk_wait_ms += win.wait_us * 1e-3;
@@ -2529,10 +2525,10 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
     const auto tp2 = std::chrono::steady_clock::now();
     MSIM_HIP(c, hipEventRecord(g->t0, c->stream));        // the host chain is not GPU time
     // ---- 3. back on the device
-    MSIM_HIP(c, hipMemcpyAsync(M.cand_pos, g->h_npos, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
+    MSIM_HIP(c, hipMemcpyAsync(M.cand_pos.p(), g->h_npos.p(), (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
     if ((rc = verdicts_to_device(c, g, M, n_ch, K, ms.has_tl, visit_d, visit_h, n_draw))) return rc;
     MSIM_HIP(c, hipGetLastError());
-    rc = mixed_emit(c, g, ct, M, K, p0 + consumed, rt_d, n_draw, visit_d, ms.sn_chained, grew, ms.has_tl);
+    rc = mixed_emit(c, g, ct, M, K, p0 + consumed, rt_d, n_draw, visit_d, ms.sn_chained, grow, ms.has_tl);
     if (prof) {
         const auto tp3 = std::chrono::steady_clock::now();
         auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
@@ -2547,17 +2543,6 @@ int plan_contig_gpu_multimix(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *r
 // device buffers of their own, synchronous, touching no contig and no stream session.  Each checks on the host what the
 // planners guarantee and refuses everything else (MSIM_ERR_ARG) before anything is allocated or launched.
 namespace {
-struct DbgDev {                                            // device blocks of one hook call
-    std::vector<void *> blocks;
-    ~DbgDev() { for (void *q : blocks) if (q) (void)hipFree(q); }
-    template <class T> hipError_t get(T **out, size_t n) {
-        void *q = nullptr;
-        const hipError_t e = hipMalloc(&q, std::max<size_t>(n * sizeof(T), 4) + PAD);
-        if (e == hipSuccess) blocks.push_back(q);
-        *out = static_cast<T *>(q);
-        return e;
-    }
-};
 bool dbg_type_table_ok(const TypeTable &tt) {
     if (tt.n < 1 || tt.n > 8) return false;
     for (uint32_t j = 0; j < tt.n; j++) {

@@ -46,10 +46,11 @@ def _next_words(mt, pos, n=8):
     return [r.getrandbits(32) for _ in range(n)]
 
 
-def _bench_order_vs_oracle(workload, lengths, engines=None, launches=None, sim=None, seed=42, owned=None):
+def _bench_order_vs_oracle(workload, lengths, engines=None, launches=None, sim=None, seed=42, owned=None, warmup=True):
     """All contigs resident, ``bench.one_step`` (the function the driver's number is timed on), THEN the reads.
     ``owned``: this "rank" plans + applies only these contigs and walks the others with ``msim_plan_chain`` (the sharded step of
-    ``bench.py --gpus N``); the oracle still walks every contig."""
+    ``bench.py --gpus N``); the oracle still walks every contig.  ``warmup=False``: the single step only, so that whatever a
+    context's first step does (scratch buffers allocated and replaced) is in the step whose bytes are read."""
     sim = sim or bench.build_settings(workload, lengths)
     dump = dump_sim(sim)
     everything = list(range(len(lengths)))
@@ -59,7 +60,8 @@ def _bench_order_vs_oracle(workload, lengths, engines=None, launches=None, sim=N
         cids = [eng.add_contig_synthetic(L, 1000 + i) if i in mine else None for i, L in enumerate(lengths)]
         eng.set_params(mm.params_descriptor(sim))
         shard_lengths = None if owned is None else lengths
-        bench.one_step(eng, sim, cids, mine, seed, mm.plan_table, shard_lengths)       # warm-up step, as in the bench
+        if warmup:
+            bench.one_step(eng, sim, cids, mine, seed, mm.plan_table, shard_lengths)   # warm-up step, as in the bench
         eng.reset_stats()
         bench.one_step(eng, sim, cids, mine, seed, mm.plan_table, shard_lengths)
         st = eng.stats()
