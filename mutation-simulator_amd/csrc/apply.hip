@@ -60,23 +60,6 @@ constexpr int LUT_BYTES = 1280;
 typedef uint32_t u32x4_a4 __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
-__device__ __forceinline__ void rec_lengths(const msim_record &r, uint32_t &outlen, uint32_t &inlen) {
-    const uint32_t len = r.stop - r.pos + 1;
-    switch (r.type) {
-        case MSIM_SN: outlen = 1; inlen = 1; break;
-        case MSIM_IN: outlen = len + 1; inlen = 1; break;          // insert, then the base itself
-        case MSIM_DE: outlen = 0; inlen = len; break;
-        case MSIM_IV: outlen = len; inlen = len; break;
-        case MSIM_DU: outlen = 2 * len; inlen = len; break;
-        case MSIM_TL: outlen = 0; inlen = len; break;               // excised like a deletion
-        case MSIM_TLI: {                                            // seq[start : stop+1], then the base itself
-            const uint32_t ilen = r.stop + 1 > r.extra ? r.stop + 1 - r.extra : 0;
-            outlen = ilen + 1; inlen = 1; break;
-        }
-        default: outlen = 0; inlen = 0; break;
-    }
-}
-
 // ------------------------------------------------------------------ 1. offsets (delta scan)
 __global__ __launch_bounds__(THREADS) void k_delta_reduce(const msim_record *__restrict__ recs, uint32_t n,
                                                           long long *__restrict__ block_sums) {

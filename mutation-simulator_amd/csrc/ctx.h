@@ -85,7 +85,7 @@ constexpr uint64_t PAD = 64;          // slack after every byte buffer so 16-B v
 struct GpuPlan;
 struct FastPlan;                      // plan_fast.hip: the counter-based PLAN engine's streams + scratch
 struct Comm;                          // comm.cpp: RCCL communicator + receive buffers of the gather
-struct Batch;                         // msim_api.hip: state of msim_batch_run
+struct Batch;                         // batch.hip: state of msim_batch_run
 struct FileIo;                        // file_io.hip: the output channels (thread + stream + pinned ring per output file)
 struct VcfState;                      // vcf_parse.hip: the VCF text of a replay, its line starts and groups
 struct SpectrumState;                 // spectrum.hip: scratch, thresholds and kernel times of the context-dependent SNP engine
@@ -180,6 +180,13 @@ bool deferred_apply_holds(const Ctx *c, int contig);
 // msim_api.hip: what every entry point that needs a result sends out first, in this order -- the deferred APPLY, the counter-based
 // engine's queued plans (as one batch), the SNP sampler's waiting emission group
 int ctx_flush_queued(Ctx *c);
+// Every entry point except msim_plan_contig first enqueues an APPLY that msim_apply_contig deferred (see there).
+#define CTX_FLUSHED(c, p)                                   \
+    ::msim::Ctx *c = reinterpret_cast<::msim::Ctx *>(p);    \
+    if (c) {                                                \
+        const int flush_rc_ = ::msim::ctx_flush_queued(c);  \
+        if (flush_rc_) return flush_rc_;                    \
+    }
 // ... and the rest of a device call's prologue: the queues flushed, a GPU context, a contig of that index; need_planned: the
 // contig planned and the context drained (the table's last bytes come from the emit stream)
 int ctx_device_contig(Ctx *c, int contig, bool need_planned, Contig **out);
@@ -208,8 +215,39 @@ struct EventPair {
 struct CopySource { const void *src; size_t bytes; };
 int copy_floor(Ctx *c, const EventPair &tm, const CopySource *srcs, int n_srcs, double *ms);
 
-// msim_api.hip: what the VCF replay (vcf_parse.hip) shares with the planners' installation path
+// Bytes a record writes (outlen) and bytes of the input it consumes (inlen): THE rule of the rewrite kernels (apply.hip) and of the
+// host's length bookkeeping (batch.hip, check_record_table).  T: uint32_t on the device -- no table the planners make wraps it --,
+// 64 bits where the host judges a table it may yet refuse.  A linked TLI copies in[extra .. stop]; nothing where __link_tls
+// found no TL (extra > stop).  (The TLI term stands in the switch: as a function of its own it changed the kernels' schedule.)
+template <class T> __host__ __device__ __forceinline__ void rec_lengths(const msim_record &r, T &outlen, T &inlen) {
+    const T len = (T)r.stop - (T)r.pos + 1;
+    switch (r.type) {
+        case MSIM_SN: outlen = 1; inlen = 1; break;
+        case MSIM_IN: outlen = len + 1; inlen = 1; break;          // insert, then the base itself
+        case MSIM_DE: outlen = 0; inlen = len; break;
+        case MSIM_IV: outlen = len; inlen = len; break;
+        case MSIM_DU: outlen = 2 * len; inlen = len; break;
+        case MSIM_TL: outlen = 0; inlen = len; break;               // excised like a deletion
+        case MSIM_TLI: {                                            // seq[start : stop+1], then the base itself
+            const T ilen = (T)r.stop + 1 > (T)r.extra ? (T)r.stop + 1 - (T)r.extra : 0;
+            outlen = ilen + 1; inlen = 1; break;
+        }
+        default: outlen = 0; inlen = 0; break;
+    }
+}
+inline long long rec_delta(const msim_record &r) {   // output length change of one record
+    long long outlen, inlen;
+    rec_lengths(r, outlen, inlen);
+    return outlen - inlen;
+}
+
+// msim_api.hip: what the VCF replay (vcf_parse.hip) and the batch (batch.hip) share with the planners' installation path
 int ctx_drain(Ctx *c);                // everything enqueued has completed, deferred results collected
+int new_contig(Ctx *c, uint64_t len, Contig **out);       // appended to c->contigs: d_in allocated, its slack zeroed
+int free_contig(Ctx *c, Contig &g, bool keep_input);      // its device buffers and results (it stays in c->contigs)
+// a host-made table's device half: recs[g->n_rec] and pool[g->pool_len] up on the context's stream, waited for; g->planned
+int upload_table(Ctx *c, Contig *g, const msim_record *recs, const uint8_t *pool);
+void batch_free(Ctx *c);              // batch.hip (msim_destroy)
 void contig_reset(Contig &g);         // forget a contig's plan / apply results (buffers stay allocated)
 // haplotype.hip: the full table becomes the active one again (pointers only, nothing is launched); drop the genotypes
 void hap_restore_full(Contig &g);

@@ -1,13 +1,10 @@
 // C-ABI entry points of libmsim.so (include/msim.h).  gfx950 (MI355X) only.
 #include <algorithm>
-#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstring>
 #include <new>
-#include <system_error>
 #include <thread>
-#include <sys/mman.h>
 
 #include <dlfcn.h>
 
@@ -82,9 +79,6 @@ static hipError_t wait_poll(Q &&query) {
 }
 hipError_t wait_stream(hipStream_t s) { return wait_poll([s]() { return hipStreamQuery(s); }); }
 hipError_t wait_event(hipEvent_t ev) { return wait_poll([ev]() { return hipEventQuery(ev); }); }
-
-struct Batch;
-static void batch_free(Ctx *c);
 
 struct CtxDev {            // small device-side constants owned by the ctx
     uint8_t *d_lut = nullptr;
@@ -227,7 +221,7 @@ static void reset_contig(Contig &g) {   // (callers also drop the context's text
     g.h_pool.clear(); g.h_pool.shrink_to_fit();
 }
 
-static int free_contig(Ctx *c, Contig &g, bool keep_input) {
+int free_contig(Ctx *c, Contig &g, bool keep_input) {
     {
         const int rc = hap_free(c, g);
         if (rc) return rc;
@@ -251,7 +245,7 @@ static Contig *get_contig(Ctx *c, int id) {
     return &c->contigs[(size_t)id];
 }
 
-static int new_contig(Ctx *c, uint64_t len, Contig **out) {
+int new_contig(Ctx *c, uint64_t len, Contig **out) {
     if (len >= (1ull << 32)) return fail(c, MSIM_ERR_UNSUPPORTED, "contig of 4 GiB or more (multi-word getrandbits)");
     if (c->contigs.size() >= (size_t)MAX_CONTIGS) return fail(c, MSIM_ERR_UNSUPPORTED, "more than 65536 contigs in one context");
     Contig g;
@@ -265,6 +259,22 @@ static int new_contig(Ctx *c, uint64_t len, Contig **out) {
     }
     c->contigs.push_back(g);
     *out = &c->contigs.back();
+    return MSIM_OK;
+}
+
+// The device half of a table made on the host (install_host_table; the batch of small contigs, which leaves c->t.upload_ms alone)
+int upload_table(Ctx *c, Contig *g, const msim_record *recs, const uint8_t *pool) {
+    int rc = MSIM_OK;
+    if (g->n_rec) {
+        rc = dev_reserve(c, (void **)&g->d_recs, &g->cap_recs, g->n_rec * sizeof(msim_record));
+        if (rc) return rc;
+        MSIM_HIP(c, hipMemcpyAsync(g->d_recs, recs, g->n_rec * sizeof(msim_record), hipMemcpyHostToDevice, c->stream));
+    }
+    rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, g->pool_len + 2 * PAD);
+    if (rc) return rc;
+    if (g->pool_len) MSIM_HIP(c, hipMemcpyAsync(g->d_pool + PAD, pool, g->pool_len, hipMemcpyHostToDevice, c->stream));
+    MSIM_HIP(c, wait_stream(c->stream));          // (the uploads read pageable vectors; APPLY runs on the emit stream)
+    g->planned = true;
     return MSIM_OK;
 }
 
@@ -359,13 +369,6 @@ int msim_create(int device_id, uint32_t flags, msim_ctx **out) {
 }
 
 static Ctx *C(msim_ctx *p) { return reinterpret_cast<Ctx *>(p); }
-// Every entry point except msim_plan_contig first enqueues an APPLY that msim_apply_contig deferred (see there).
-#define CTX_FLUSHED(c, p)                                   \
-    Ctx *c = C(p);                                          \
-    if (c) {                                                \
-        const int flush_rc_ = ctx_flush_queued(c);          \
-        if (flush_rc_) return flush_rc_;                    \
-    }
 #define NEED_GPU(c) do { if ((c)->host_only) return fail((c), MSIM_ERR_HIP, "host-only context: this call needs the GPU"); } while (0)
 
 void msim_destroy(msim_ctx *p) {
@@ -582,19 +585,9 @@ static int install_host_table(Ctx *c, Contig *g, std::vector<msim_record> &recs,
         g->planned = true;
         return MSIM_OK;
     }
-    int rc = MSIM_OK;
-    if (g->n_rec) {
-        rc = dev_reserve(c, (void **)&g->d_recs, &g->cap_recs, g->n_rec * sizeof(msim_record));
-        if (rc) return rc;
-        MSIM_HIP(c, hipMemcpyAsync(g->d_recs, recs.data(), g->n_rec * sizeof(msim_record), hipMemcpyHostToDevice, c->stream));
-    }
-    rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, g->pool_len + 2 * PAD);
+    const int rc = upload_table(c, g, recs.data(), pool.data());
     if (rc) return rc;
-    if (g->pool_len)
-        MSIM_HIP(c, hipMemcpyAsync(g->d_pool + PAD, pool.data(), g->pool_len, hipMemcpyHostToDevice, c->stream));
-    MSIM_HIP(c, wait_stream(c->stream));
     c->t.upload_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    g->planned = true;
     return MSIM_OK;
 }
 
@@ -1353,7 +1346,7 @@ int msim_dbg_fast_plan(msim_ctx *p, uint64_t L, const msim_range *ranges, int n_
 }
 
 // test support (tests/test_apply_ref_host.py, tests/test_gpu_apply_tables.py): is this a table the rewrite kernels are written
-// for (apply.hip: rec_lengths / rec_view)?  What every planner guarantees, checked: known types, records strictly increasing in
+// for (ctx.h: rec_lengths; apply.hip: rec_view)?  What every planner guarantees, checked: known types, records strictly increasing in
 // pos and consuming disjoint input (SN / IN / TLI their own base, DE / DU / IV / TL pos..stop), every span inside the contig,
 // every insert inside the pool, an SNP's aux a LUT column, every output offset and the mutated length in [0, 2^32).
 // A TLI whose span is empty (extra > stop: __link_tls found no TL, plan_host.cpp) is a planner's table and passes.
@@ -1377,7 +1370,6 @@ static int check_record_table(Ctx *c, uint64_t L, const msim_record *recs, uint6
         if (i && r.pos < next_free) return bad(i, "not behind the input its predecessor consumed (positions strictly increasing, no overlap)");
         const long long len = (long long)r.stop - (long long)r.pos + 1;
         uint64_t last = r.pos;                             // last input position this record consumes
-        long long d = 0;
         switch (r.type) {
             case MSIM_SN:
                 if (r.stop != r.pos) return bad(i, "SNP with stop != pos");
@@ -1386,21 +1378,17 @@ static int check_record_table(Ctx *c, uint64_t L, const msim_record *recs, uint6
             case MSIM_IN:
                 if (len < 1) return bad(i, "stop < pos");
                 if (r.extra > pool_len || (uint64_t)len > pool_len - r.extra) return bad(i, "insert outside the insert pool");
-                d = len;
                 break;
             case MSIM_DE: case MSIM_TL: case MSIM_DU: case MSIM_IV:
                 if (len < 1) return bad(i, "stop < pos");
                 if (r.stop >= L) return bad(i, "stop beyond the contig");
                 last = r.stop;
-                d = (r.type == MSIM_DU) ? len : (r.type == MSIM_IV) ? 0 : -len;
                 break;
             default:                                       // MSIM_TLI: copy of in[extra .. stop]
-                if (r.extra <= r.stop) {
-                    if (r.stop >= L) return bad(i, "linked span beyond the contig");
-                    d = (long long)r.stop + 1 - (long long)r.extra;
-                }
+                if (r.extra <= r.stop && r.stop >= L) return bad(i, "linked span beyond the contig");
                 break;
         }
+        const long long d = rec_delta(r);                  // (ctx.h: the rewrite kernels' own rule)
         const long long o = (long long)r.pos + run;
         if (o < 0 || o >= (1ll << 32)) return bad(i, "output offset outside [0, 2^32)");
         if (off) (*off)[(size_t)i] = (uint32_t)o;
@@ -1668,14 +1656,7 @@ int msim_reset_stats(msim_ctx *p) {
 
 }  // extern "C"
 
-// ---- batch of small contigs ----------------------------------------------------------------------------------------
-// An assembly with thousands of scaffolds pays a fixed ~0.35 ms of HIP API work per contig on the per-contig path
-// (allocations, ~40 runtime calls, two or three synchronising fetches): 20 000 scaffolds of 10 kb ran at 27 Mbases/s.
-// Here mutate()'s loop body (mutator.py:111-141) runs for MANY small contigs in one pass: the host strips the FASTA
-// text and walks the RNG chain contig by contig (plan_contig_host -- these contigs are below every device engine's
-// threshold anyway), the record tables are concatenated with their positions shifted to the contig's place in ONE
-// super-contig, the GPU runs ONE APPLY over it (records never cross a contig border, so the rewrite kernels need no
-// change), and the host frames the mutated stream per contig and renders the VCF lines (msim_render_vcf).
+// what vcf_parse.hip shares with the planners' installation path (ctx.h)
 namespace msim {
 int table_install(Ctx *c, Contig *g, std::vector<msim_record> &recs, std::vector<uint8_t> &pool, bool empty) {
     return ::install_host_table(c, g, recs, pool, empty);
@@ -1685,472 +1666,3 @@ int table_check(Ctx *c, uint64_t L, const msim_record *recs, uint64_t n, uint64_
     return ::check_record_table(c, L, recs, n, pool_len, nullptr, delta, bad_index, bad_what);
 }
 }  // namespace msim
-
-namespace msim {
-
-struct Batch {
-    struct Item { uint64_t base = 0, len = 0, out_start = 0, out_len = 0, rec0 = 0, nrec = 0, pool0 = 0, npool = 0, text0 = 0, ntext = 0,
-                  vcf0 = 0, nvcf = 0; uint32_t bpl = 0; bool empty = true;
-                  const char *header = nullptr; uint32_t header_len = 0; bool nl_before = false; };   // the record's defline (caller's memory)
-    std::vector<Item> items;
-    std::vector<msim_record> recs_rel;       // per-contig coordinates (what the VCF renderer reads)
-    std::vector<uint8_t> pool;
-    uint8_t *h_in = nullptr, *h_out = nullptr;   // page-aligned host staging (see pinned_reserve)
-    size_t cap_in = 0, cap_out = 0;
-    uint8_t *fasta = nullptr; size_t fasta_cap = 0, fasta_len = 0;   // malloc'ed: never zero-filled; framed on demand (msim_batch_view)
-    bool framed = false;
-    char *vcf = nullptr; size_t vcf_cap = 0, vcf_len = 0;
-    uint64_t last_line_bases = 0;            // bases on the (partial) last line of the FASTA text
-    int key_contig = -1;
-};
-
-static void batch_free(Ctx *c) {
-    if (!c->batch) return;
-    file_channel_idle(c, 0);                               // (an output channel may still be writing the batch's texts)
-    file_channel_idle(c, 1);
-    static const bool prof = getenv("MSIM_BATCH_PROF") != nullptr;
-    auto tp = std::chrono::steady_clock::now();
-    auto lap = [&](const char *what) { const auto n = std::chrono::steady_clock::now(); if (prof) fprintf(stderr, "  batch_free %s %.1f ms\n", what, std::chrono::duration<double, std::milli>(n - tp).count()); tp = n; };
-    free(c->batch->h_in); lap("h_in");
-    free(c->batch->h_out); lap("h_out");
-    free(c->batch->fasta); lap("fasta");
-    free(c->batch->vcf); lap("vcf");
-    delete c->batch; lap("vectors");
-    c->batch = nullptr;
-}
-
-template <class T> static bool raw_reserve(T **p, size_t *cap, size_t want) {
-    if (*cap >= want) return true;
-    free(*p);
-    *cap = want + want / 8 + 4096;
-    *p = static_cast<T *>(malloc(*cap));
-    if (!*p) *cap = 0;
-    return *p != nullptr;
-}
-
-// Contigs [0, n) in `parts` consecutive slices, one host thread each (text work of a batch: ingest, framing, VCF lines).
-static int batch_threads() {
-    static const int t = [] {
-        if (const char *e = getenv("MSIM_BATCH_THREADS")) return std::max(1, atoi(e));
-        const unsigned hw = std::thread::hardware_concurrency();
-        return (int)std::min<unsigned>(16, std::max<unsigned>(1, hw / 2));
-    }();
-    return t;
-}
-template <class F> static void parallel_slices(int n, F f) {   // f(part, i0, i1)
-    const int parts = std::max(1, std::min(batch_threads(), n / 64));
-    if (parts == 1) { f(0, 0, n); return; }
-    std::vector<std::thread> th;
-    int started = 1;                                       // slices [0, started) run or have run; the rest falls to this thread
-    try {
-        for (int t = 1; t < parts; t++, started++)
-            th.emplace_back(f, t, (int)((long long)n * t / parts), (int)((long long)n * (t + 1) / parts));
-    } catch (const std::system_error &) {                  // no more threads to be had: the remaining slices run here
-    }
-    f(0, 0, (int)((long long)n / parts));
-    for (int t = started; t < parts; t++) f(t, (int)((long long)n * t / parts), (int)((long long)n * (t + 1) / parts));
-    for (auto &x : th) x.join();
-}
-
-// Staging of a batch's bases on the host: plain page-aligned memory.  Page-locked memory does not pay here: hipHostMalloc
-// pins at ~4 GB/s (90 ms for the 400 MB of a 16 k-contig batch, and as long again to release), while copies to and from
-// touched pageable memory run at the link's speed on this platform and into fresh pages at 20 GB/s.
-static int pinned_reserve(Ctx *c, uint8_t **p, size_t *cap, size_t want) {
-    if (*cap >= want) return MSIM_OK;
-    free(*p);
-    *p = nullptr; *cap = 0;
-    const size_t huge = (size_t)2 << 20;
-    const size_t sz = (want + want / 4 + huge) & ~(huge - 1);
-    *p = static_cast<uint8_t *>(aligned_alloc(huge, sz));
-    if (!*p) return fail(c, MSIM_ERR_NOMEM, "batch staging buffer");
-#ifdef MADV_HUGEPAGE
-    (void)madvise(*p, sz, MADV_HUGEPAGE);                  // 2 MB pages where the kernel grants them: 512x fewer faults and unmaps
-#endif
-    *cap = sz;
-    return MSIM_OK;
-}
-
-static inline size_t batch_header_len(const msim_batch_contig &q) { return q.header_len ? q.header_len : strlen(q.header); }
-
-// output length change of one record (apply.hip: rec_lengths)
-static long long rec_delta(const msim_record &r) {
-    const long long len = (long long)r.stop - (long long)r.pos + 1;
-    switch (r.type) {
-        case MSIM_IN: return len;
-        case MSIM_DE: case MSIM_TL: return -len;
-        case MSIM_DU: return len;
-        case MSIM_TLI: return r.stop + 1 > r.extra ? (long long)r.stop + 1 - (long long)r.extra : 0;
-        default: return 0;
-    }
-}
-
-// FASTA framing of a batch's mutated bases into `dst` (B.fasta_len bytes): '\n' after every bpl bases, none after a partial
-// last line (fasta_writer.py:40-58).  With a header per contig the text is the complete run of FASTA records as FastaWriter
-// would have written them: '>' header '\n' body, and a '\n' before a header iff the previous body ended in a partial line.
-static void batch_frame_into(const Batch &B, uint8_t *out) {
-    parallel_slices((int)B.items.size(), [&](int, int i0, int i1) {
-        for (int i = i0; i < i1; i++) {
-            const Batch::Item &it = B.items[(size_t)i];
-            const uint8_t *src = B.h_out + it.out_start;
-            uint8_t *dst = out + it.text0;
-            if (it.header) {
-                if (it.nl_before) *dst++ = '\n';
-                *dst++ = '>';
-                memcpy(dst, it.header, it.header_len);
-                dst += it.header_len;
-                *dst++ = '\n';
-            }
-            if (!it.bpl) { if (it.out_len) memcpy(dst, src, it.out_len); continue; }
-            uint64_t done = 0;
-            while (done + it.bpl <= it.out_len) { memcpy(dst, src + done, it.bpl); dst[it.bpl] = '\n'; dst += it.bpl + 1; done += it.bpl; }
-            if (done < it.out_len) memcpy(dst, src + done, it.out_len - done);
-        }
-    });
-}
-
-}  // namespace msim
-
-extern "C" {
-
-int msim_batch_run(msim_ctx *p, const msim_batch_contig *contigs, int n) {
-    CTX_FLUSHED(c, p)
-    if (!c || !contigs || n < 1) return MSIM_ERR_ARG;
-    NEED_GPU(c);
-    if (!c->have_params) return fail(c, MSIM_ERR_ARG, "msim_set_params has not been called");
-    TraceRange tr("msim batch of small contigs");
-    static const bool prof = getenv("MSIM_BATCH_PROF") != nullptr;
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    const auto t_0 = now();
-    int rc = drain(c);
-    if (rc) return rc;
-    if (c->gpu) {                                          // the host planner continues from wherever the device streams stand
-        rc = gpu_plan_sync_to_host(c, c->gpu);
-        if (rc) return rc;
-    }
-    if (!c->batch) c->batch = new Batch();
-    Batch &B = *c->batch;
-    B.items.assign((size_t)n, Batch::Item());
-    B.recs_rel.clear(); B.pool.clear(); B.fasta_len = 0; B.vcf_len = 0; B.last_line_bases = 0; B.framed = false;
-    B.key_contig = -1;
-    uint64_t total = 0;
-    for (int i = 0; i < n; i++) {
-        const msim_batch_contig &q = contigs[i];
-        if ((!q.body && q.n_bases) || (q.n_ranges && !q.ranges) || q.n_ranges < 0 || !q.name) return fail(c, MSIM_ERR_ARG, "msim_batch_run: bad contig");
-        if (q.n_bases) {
-            if (q.lenc == 0 || q.lenb < q.lenc) return fail(c, MSIM_ERR_ARG, "line width / line stride of the FASTA body are inconsistent");
-            const uint64_t last = (q.n_bases - 1) / q.lenc * q.lenb + (q.n_bases - 1) % q.lenc;
-            if (last >= q.body_bytes) return fail(c, MSIM_ERR_ARG, "FASTA body shorter than n_bases at this line width");
-        }
-        B.items[(size_t)i].base = total;
-        B.items[(size_t)i].len = q.n_bases;
-        B.items[(size_t)i].bpl = q.lenc;
-        total += q.n_bases;
-    }
-    if (total >= (1ull << 31)) return fail(c, MSIM_ERR_UNSUPPORTED, "batch of 2 GiB or more: split it");
-    // ---- 1. FASTA text -> upper-cased bases (pyfaidx's sequence_always_upper, util.py:84-88) on the host and up to the
-    //         device -- on a thread of its own, beside PLAN: the RNG chain never looks at a base
-    rc = pinned_reserve(c, &B.h_in, &B.cap_in, total + 64);
-    if (rc) return rc;
-    Contig *g;
-    rc = new_contig(c, total, &g);
-    if (rc) return rc;
-    const int gid = (int)c->contigs.size() - 1;
-    // the temporary super-contig leaves the context on EVERY way out of this block (HIP failures included: a contig left
-    // behind would leak its device buffers and shift the ids of the caller's later contigs)
-    struct Drop {
-        Ctx *c; int gid; bool armed = true;
-        void now() { if (armed) { armed = false; (void)free_contig(c, c->contigs[(size_t)gid], false); c->contigs.pop_back(); } }
-        ~Drop() { now(); }
-    } guard{c, gid};
-    auto drop = [&]() { guard.now(); };
-    struct Side {                                           // a helper thread that is always joined before its captures die
-        std::thread th;
-        void join() { if (th.joinable()) th.join(); }
-        ~Side() { join(); }
-    };
-    hipError_t ingest_err = hipSuccess;
-    double ingest_ms = 0;
-    uint8_t *const d_in = g->d_in;                          // (c->contigs does not grow during the batch: g stays valid)
-    auto ingest = [&, d_in]() {
-        const auto a0 = now();
-        parallel_slices(n, [&](int, int i0, int i1) {
-            for (int i = i0; i < i1; i++) {
-                const msim_batch_contig &q = contigs[i];
-                uint8_t *dst = B.h_in + B.items[(size_t)i].base;
-                uint64_t done = 0;
-                const uint8_t *src = q.body;
-                while (done < q.n_bases) {
-                    const uint64_t take = std::min<uint64_t>(q.lenc, q.n_bases - done);
-                    memcpy(dst + done, src, take);
-                    done += take;
-                    src += q.lenb;
-                }
-                for (uint64_t k = 0; k < q.n_bases; k++) {       // (auto-vectorised)
-                    const uint8_t b = dst[k];
-                    dst[k] = (uint8_t)(b - ((b >= 'a' && b <= 'z') ? 32 : 0));
-                }
-            }
-        });
-        ingest_ms = ms(a0, now());
-        if (total) {
-            ingest_err = hipSetDevice(c->device);
-            if (ingest_err == hipSuccess) ingest_err = hipMemcpyAsync(d_in + PAD, B.h_in, total, hipMemcpyHostToDevice, c->stream);
-        }
-    };
-    Side side_in;
-    try { side_in.th = std::thread(ingest); } catch (const std::system_error &) { ingest(); }
-    const auto t_1 = now();
-    for (int i = 0; i < n; i++) {                            // (kept for the framing, which runs when the text is asked for)
-        Batch::Item &it = B.items[(size_t)i];
-        it.header = contigs[i].header;
-        it.header_len = contigs[i].header ? (uint32_t)batch_header_len(contigs[i]) : 0u;
-    }
-    // ---- 2. PLAN: the RNG chain, contig by contig (mutator.py:111-131 + the draws of :334-358)
-    std::vector<msim_record> recs_abs;
-    long long delta_total = 0;
-    bool all_snp = true;
-    HostPlan hp;
-    for (int i = 0; i < n; i++) {
-        const msim_batch_contig &q = contigs[i];
-        Batch::Item &it = B.items[(size_t)i];
-        const uint64_t w_py = c->py.words, w_np = c->np.words;
-        rc = plan_contig_host(c, q.n_bases, q.ranges, q.n_ranges, hp);
-        if (rc) return rc;
-        c->t.contigs_batch++;
-        c->t.py_words += c->py.words - w_py;
-        c->t.np_words += c->np.words - w_np;
-        it.empty = hp.empty;
-        it.rec0 = B.recs_rel.size(); it.nrec = hp.recs.size();
-        it.pool0 = B.pool.size(); it.npool = hp.pool.size();
-        long long delta = 0;
-        for (const msim_record &r : hp.recs) {
-            delta += rec_delta(r);
-            msim_record a = r;
-            a.pos += (uint32_t)it.base;
-            a.stop += (uint32_t)it.base;
-            if (r.type == MSIM_IN) a.extra += (uint32_t)it.pool0;
-            else if (r.type == MSIM_TLI) a.extra += (uint32_t)it.base;
-            if (r.type != MSIM_SN) all_snp = false;
-            recs_abs.push_back(a);
-        }
-        B.recs_rel.insert(B.recs_rel.end(), hp.recs.begin(), hp.recs.end());
-        B.pool.insert(B.pool.end(), hp.pool.begin(), hp.pool.end());
-        it.out_start = (uint64_t)((long long)it.base + delta_total);
-        it.out_len = (uint64_t)((long long)it.len + delta);
-        delta_total += delta;
-    }
-    if (B.pool.size() >= (1ull << 31)) return fail(c, MSIM_ERR_UNSUPPORTED, "batch insert pool of 2 GiB or more: split it");
-    const uint64_t out_total = (uint64_t)((long long)total + delta_total);
-    const auto t_2 = now();
-    // ---- 3. ONE APPLY over the super-contig
-    side_in.join();
-    if (ingest_err != hipSuccess) { drop(); return hip_fail(c, ingest_err, "batch input upload"); }
-    // ---- 3b. VCF record lines (mutator.py:334-399 + vcf_writer.py:118-126) per contig, on the host -- beside the APPLY: they
-    //          read the records and the INPUT bases only
-    int vcf_rc = MSIM_OK;
-    const char *vcf_msg = "";
-    double vcf_ms = 0;
-    auto render_vcf = [&]() {
-        const auto v0 = now();
-    // VCF lines: every slice of contigs renders into a buffer of its own, sized by a cheap upper bound (a line is name +
-        // fixed fields of < 96 bytes + REF and ALT, each at most span + insert + 1 long, twice for a duplication's ALT);
-        // the slices are then joined in contig order
-        const msim_record *all = B.recs_rel.data();
-        const int max_parts = batch_threads();
-        std::vector<char *> part_buf((size_t)max_parts, nullptr);      // malloc'ed: never zero-filled
-        std::vector<uint64_t> part_len((size_t)max_parts, 0);
-        std::vector<int> part_first((size_t)max_parts, -1);
-        std::atomic<bool> bad{false};
-        parallel_slices(n, [&](int part, int i0, int i1) {
-            uint64_t bound = 0;
-            for (int i = i0; i < i1; i++) {
-                const Batch::Item &it = B.items[(size_t)i];
-                const uint64_t nl = (contigs[i].name_len ? contigs[i].name_len : strlen(contigs[i].name)) + 96;
-                for (uint64_t k = 0; k < it.nrec; k++) {
-                    const msim_record &r = all[it.rec0 + k];
-                    const uint64_t span = r.type == MSIM_SN ? 1 : (uint64_t)(r.stop >= r.pos ? r.stop - r.pos + 1 : 0) + 2;
-                    const uint64_t tli = r.type == MSIM_TLI && r.stop + 1 > r.extra ? (uint64_t)r.stop + 1 - r.extra : 0;
-                    bound += nl + 3 * (span + tli) + 8;
-                }
-            }
-            char *out = static_cast<char *>(malloc((size_t)bound + 64));
-            part_buf[(size_t)part] = out;
-            part_first[(size_t)part] = i0;
-            if (!out) { bad = true; return; }
-            uint64_t at = 0;
-            for (int i = i0; i < i1; i++) {
-                Batch::Item &it = B.items[(size_t)i];
-                it.vcf0 = at;                                  // relative to the slice until the join
-                uint64_t need = 0;
-                if (it.nrec) {
-                    const std::string nm = contigs[i].name_len ? std::string(contigs[i].name, contigs[i].name_len) : std::string();
-                    need = render_vcf_unchecked(all + it.rec0, it.nrec, B.pool.data() + it.pool0, B.h_in + it.base, it.len,
-                                                contigs[i].name_len ? nm.c_str() : contigs[i].name, out + at);
-                    if (at + need > bound) bad = true;
-                }
-                it.nvcf = need;
-                at += need;
-            }
-            part_len[(size_t)part] = at;
-        });
-        auto free_parts = [&]() { for (char *q : part_buf) free(q); };
-        if (bad) { free_parts(); vcf_rc = MSIM_ERR_HIP; vcf_msg = "internal: VCF text of a batch: bound too small or out of memory"; return; }
-        // join in slice order (slices are consecutive contig ranges, part index ascending)
-        std::vector<int> order;
-        for (int t = 0; t < max_parts; t++) if (part_first[(size_t)t] >= 0) order.push_back(t);
-        std::sort(order.begin(), order.end(), [&](int x, int y) { return part_first[(size_t)x] < part_first[(size_t)y]; });
-        uint64_t total_vcf = 0;
-        for (int t : order) total_vcf += part_len[(size_t)t];
-        file_channel_idle(c, 1);                            // (the previous batch's VCF text may still be on its way to the file)
-        if (!raw_reserve(&B.vcf, &B.vcf_cap, (size_t)total_vcf + 1)) { free_parts(); vcf_rc = MSIM_ERR_NOMEM; vcf_msg = "batch VCF text"; return; }
-        uint64_t at = 0;
-        for (size_t k = 0; k < order.size(); k++) {
-            const int t = order[k];
-            const int i0 = part_first[(size_t)t], i1 = k + 1 < order.size() ? part_first[(size_t)order[k + 1]] : n;
-            for (int i = i0; i < i1; i++) B.items[(size_t)i].vcf0 += at;
-            if (part_len[(size_t)t]) memcpy(B.vcf + at, part_buf[(size_t)t], (size_t)part_len[(size_t)t]);
-            at += part_len[(size_t)t];
-        }
-        B.vcf_len = (size_t)at;
-        free_parts();
-        vcf_ms = ms(v0, now());
-    };
-    Side side_vcf;
-    try { side_vcf.th = std::thread(render_vcf); } catch (const std::system_error &) { render_vcf(); }
-    g->n_rec = recs_abs.size();
-    g->pool_len = B.pool.size();
-    g->plan_empty = recs_abs.empty();
-    g->all_snp = all_snp;
-    g->delta_known = true;
-    g->known_delta = delta_total;
-    if (g->n_rec) {
-        rc = dev_reserve(c, (void **)&g->d_recs, &g->cap_recs, g->n_rec * sizeof(msim_record));
-        if (rc) return rc;
-        MSIM_HIP(c, hipMemcpyAsync(g->d_recs, recs_abs.data(), g->n_rec * sizeof(msim_record), hipMemcpyHostToDevice, c->stream));
-    }
-    rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, g->pool_len + 2 * PAD);
-    if (rc) return rc;
-    if (g->pool_len) MSIM_HIP(c, hipMemcpyAsync(g->d_pool + PAD, B.pool.data(), g->pool_len, hipMemcpyHostToDevice, c->stream));
-    MSIM_HIP(c, wait_stream(c->stream));          // (the uploads read pageable vectors; APPLY runs on the emit stream)
-    g->planned = true;
-    rc = apply_contig_device(c, *g);
-    if (rc) return rc;
-    rc = pinned_reserve(c, &B.h_out, &B.cap_out, out_total + 64);
-    if (rc) return rc;
-    if (out_total) MSIM_HIP(c, hipMemcpyAsync(B.h_out, g->d_out, out_total, hipMemcpyDeviceToHost, c->emit_stream));
-    rc = apply_finish(c);                                  // synchronises the emit stream: the copy above included
-    if (rc) return rc;
-    if (g->out_len != out_total) return fail(c, MSIM_ERR_HIP, "internal: batch planner and device disagree on the mutated length");
-    if (g->key_error) {                                    // the reference's KeyError: which contig, which base
-        const uint64_t kp = g->key_pos;
-        int who = 0;
-        for (int i = 0; i < n; i++) if (B.items[(size_t)i].base <= kp && kp < B.items[(size_t)i].base + B.items[(size_t)i].len) who = i;
-        B.key_contig = who;
-        const uint8_t kb = g->key_base;
-        return fail(c, MSIM_ERR_KEY, std::string("KeyError: '") + (char)kb + "'");
-    }
-    drop();
-    const auto t_3 = now();
-    // ---- 4. the FASTA text's layout; the framing itself runs when the text is asked for, straight into the caller's
-    //         memory (msim_batch_fetch) or into a buffer of the context (msim_batch_view)
-    uint64_t text_total = 0;
-    for (int i = 0; i < n; i++) {
-        Batch::Item &it = B.items[(size_t)i];
-        it.nl_before = i > 0 && B.items[(size_t)i - 1].bpl && B.items[(size_t)i - 1].out_len % B.items[(size_t)i - 1].bpl;
-        const uint64_t head = it.header ? (it.nl_before ? 1 : 0) + 1 + it.header_len + 1 : 0;
-        it.text0 = text_total;
-        it.ntext = head + (it.bpl ? it.out_len + it.out_len / it.bpl : it.out_len);
-        text_total += it.ntext;
-    }
-    B.fasta_len = (size_t)text_total;
-    B.last_line_bases = B.items.back().bpl ? B.items.back().out_len % B.items.back().bpl : 0;
-    side_vcf.join();
-    if (vcf_rc) return fail(c, vcf_rc, vcf_msg);
-    if (prof)
-        fprintf(stderr, "msim_batch_run: %d contigs, %.1f Mb in %.1f ms: plan %.1f (beside it: ingest %.1f), upload+APPLY+download %.1f (beside it: VCF %.1f), wait for VCF %.1f\n",
-                n, total / 1e6, ms(t_0, now()), ms(t_1, t_2), ingest_ms, ms(t_2, t_3), vcf_ms, ms(t_3, now()));
-    return MSIM_OK;
-}
-
-int msim_batch_sizes(msim_ctx *p, int n, uint64_t *fasta_bytes, uint64_t *vcf_bytes, int32_t *empty, uint64_t *n_records) {
-    CTX_FLUSHED(c, p)
-    if (!c || !c->batch || (size_t)n != c->batch->items.size()) return MSIM_ERR_ARG;
-    for (int i = 0; i < n; i++) {
-        const Batch::Item &it = c->batch->items[(size_t)i];
-        if (fasta_bytes) fasta_bytes[i] = it.ntext;
-        if (vcf_bytes) vcf_bytes[i] = it.nvcf;
-        if (empty) empty[i] = it.empty ? 1 : 0;
-        if (n_records) n_records[i] = it.nrec;
-    }
-    return MSIM_OK;
-}
-
-int msim_batch_fetch(msim_ctx *p, uint8_t *fasta_text, uint64_t fasta_cap, char *vcf_text, uint64_t vcf_cap) {
-    CTX_FLUSHED(c, p)
-    if (!c || !c->batch) return MSIM_ERR_ARG;
-    Batch &B = *c->batch;
-    if (fasta_text) {                                      // framed straight into the caller's memory (a mapped file, say)
-        if (fasta_cap < B.fasta_len) return fail(c, MSIM_ERR_ARG, "fasta buffer too small");
-        if (B.fasta_len && B.framed) memcpy(fasta_text, B.fasta, B.fasta_len);
-        else if (B.fasta_len) batch_frame_into(B, fasta_text);
-    }
-    if (vcf_text) {
-        if (vcf_cap < B.vcf_len) return fail(c, MSIM_ERR_ARG, "vcf buffer too small");
-        if (B.vcf_len) memcpy(vcf_text, B.vcf, B.vcf_len);
-    }
-    return MSIM_OK;
-}
-
-int msim_batch_fetch_file(msim_ctx *p, int fasta_fd, uint64_t fasta_offset, int vcf_fd, uint64_t vcf_offset) {
-    CTX_FLUSHED(c, p)
-    if (!c || !c->batch) return MSIM_ERR_ARG;
-    Batch &B = *c->batch;
-    if (fasta_fd >= 0) {
-        int rc = file_check(c, fasta_fd);
-        if (rc) return rc;
-        file_channel_idle(c, 0);                           // (the previous batch's text may still be read from B.fasta)
-        if (!B.framed) {
-            if (!raw_reserve(&B.fasta, &B.fasta_cap, B.fasta_len + 1)) return fail(c, MSIM_ERR_NOMEM, "batch FASTA text");
-            if (B.fasta_len) batch_frame_into(B, B.fasta);
-            B.framed = true;
-        }
-        rc = file_enqueue_host(c, 0, B.fasta, B.fasta_len, fasta_fd, fasta_offset);
-        if (rc) return rc;
-    }
-    if (vcf_fd >= 0) {
-        int rc = file_check(c, vcf_fd);
-        if (rc) return rc;
-        rc = file_enqueue_host(c, 1, reinterpret_cast<const uint8_t *>(B.vcf), B.vcf_len, vcf_fd, vcf_offset);
-        if (rc) return rc;
-    }
-    return MSIM_OK;
-}
-
-int msim_batch_view(msim_ctx *p, const uint8_t **fasta_text, uint64_t *fasta_bytes, const char **vcf_text, uint64_t *vcf_bytes,
-                    uint64_t *last_line_bases) {
-    CTX_FLUSHED(c, p)
-    if (!c || !c->batch) return MSIM_ERR_ARG;
-    Batch &B = *c->batch;
-    if (fasta_text && !B.framed) {
-        file_channel_idle(c, 0);                           // (the previous batch's text may still be read from B.fasta)
-        if (!raw_reserve(&B.fasta, &B.fasta_cap, B.fasta_len + 1)) return fail(c, MSIM_ERR_NOMEM, "batch FASTA text");
-        if (B.fasta_len) batch_frame_into(B, B.fasta);
-        B.framed = true;
-    }
-    if (fasta_text) *fasta_text = B.fasta;
-    if (fasta_bytes) *fasta_bytes = B.fasta_len;
-    if (vcf_text) *vcf_text = B.vcf;
-    if (vcf_bytes) *vcf_bytes = B.vcf_len;
-    if (last_line_bases) *last_line_bases = B.last_line_bases;
-    return MSIM_OK;
-}
-
-int msim_batch_key_contig(msim_ctx *p, int *contig) {
-    CTX_FLUSHED(c, p)
-    if (!c || !contig || !c->batch) return MSIM_ERR_ARG;
-    *contig = c->batch->key_contig;
-    return MSIM_OK;
-}
-
-}  // extern "C"

@@ -1620,7 +1620,7 @@ __global__ __launch_bounds__(256) void k_link_scatter(const uint32_t *__restrict
     const uint32_t j = blockIdx.x * 256 + threadIdx.x;
     if (j < n_nsn) { cand_extra[nsn_rank[j]] = nsn_extra[j]; cand_aux[nsn_rank[j]] = nsn_aux[j]; }
 }
-// output length change of one kept record (apply.hip: rec_lengths): IN / DU + len, DE / TL - len, IV 0, TLI + the copied span
+// output length change of one kept record (ctx.h: rec_lengths, here over a candidate's separate fields): IN / DU + len, DE / TL - len, IV 0, TLI + the copied span
 __host__ __device__ __forceinline__ long long record_delta(uint8_t type, uint32_t pos, uint32_t stop, uint32_t extra) {
     const long long len = (long long)stop - (long long)pos + 1;
     switch (type) {
