@@ -913,27 +913,21 @@ __global__ __launch_bounds__(THREADS) void k_checksum(const uint8_t *__restrict_
 
 }  // namespace
 
-int dev_reserve(Ctx *c, void **p, size_t *cap, size_t want_bytes) {
-    if (*p && *cap >= want_bytes) return MSIM_OK;
-    if (*p) MSIM_HIP(c, hipFree(*p));
-    *p = nullptr;
-    *cap = 0;
+int dev_reserve(Ctx *c, DevBlock &b, size_t want_bytes) {
+    if (b.raw && b.cap >= want_bytes) return MSIM_OK;
+    MSIM_HIP(c, b.release());
     const size_t sz = want_bytes + (want_bytes >> 4) + 256;
-    MSIM_HIP(c, hipMalloc(p, sz));
-    *cap = sz;
+    MSIM_HIP(c, dev_alloc(b, sz));
     return MSIM_OK;
 }
 
 int ensure_scratch(Ctx *c, size_t bytes) {
-    if (bytes <= c->scratch_bytes) return MSIM_OK;
+    DevBlock &b = c->d_scratch;
+    if (bytes <= b.cap) return MSIM_OK;
     MSIM_HIP(c, wait_stream(c->stream));          // the old block may still be in use
     MSIM_HIP(c, wait_stream(c->emit_stream));
-    if (c->d_scratch) MSIM_HIP(c, hipFree(c->d_scratch));
-    c->d_scratch = nullptr;
-    c->scratch_bytes = 0;
-    size_t want = bytes + (bytes >> 2) + 4096;
-    MSIM_HIP(c, hipMalloc(&c->d_scratch, want));
-    c->scratch_bytes = want;
+    MSIM_HIP(c, b.release());
+    MSIM_HIP(c, dev_alloc(b, bytes + (bytes >> 2) + 4096));
     return MSIM_OK;
 }
 
@@ -949,7 +943,7 @@ int synth_contig_device(Ctx *c, uint8_t *d_dst, uint64_t len, uint64_t seed) {
 int checksum_device(Ctx *c, const uint8_t *d_src, uint64_t len, uint64_t *sum) {
     int rc = ensure_scratch(c, 64);
     if (rc) return rc;
-    unsigned long long *d_sum = reinterpret_cast<unsigned long long *>(c->d_scratch);
+    unsigned long long *d_sum = reinterpret_cast<unsigned long long *>(c->d_scratch.raw);
     MSIM_HIP(c, hipMemsetAsync(d_sum, 0, 8, c->stream));
     if (len) {
         const uint64_t nwords = (len + 7) / 8;
@@ -970,14 +964,12 @@ extern uint8_t *ctx_lut(Ctx *c);
 // KeyError words + length-check words of every contig: two asynchronous copies into pinned memory on the emit stream
 static int enqueue_err_copies(Ctx *c) {
     const size_t nc = c->contigs.size();
-    if (c->cap_h_errs < 2 * nc) {
-        if (c->h_errs) MSIM_HIP(c, hipHostFree(c->h_errs));
-        c->h_errs = nullptr; c->cap_h_errs = 0;
-        MSIM_HIP(c, hipHostMalloc(&c->h_errs, (2 * nc + 64) * sizeof(unsigned long long), hipHostMallocDefault));
-        c->cap_h_errs = 2 * nc + 64;
+    if (c->h_errs.cap < 2 * nc * sizeof(unsigned long long)) {
+        MSIM_HIP(c, c->h_errs.release());
+        MSIM_HIP(c, pin_alloc(c->h_errs, (2 * nc + 64) * sizeof(unsigned long long)));
     }
-    MSIM_HIP(c, hipMemcpyAsync(c->h_errs, c->d_errs, nc * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->emit_stream));
-    MSIM_HIP(c, hipMemcpyAsync(c->h_errs + nc, c->d_errs + MAX_CONTIGS, nc * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->emit_stream));
+    MSIM_HIP(c, hipMemcpyAsync(c->h_errs.p(), c->d_errs.p(), nc * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->emit_stream));
+    MSIM_HIP(c, hipMemcpyAsync(c->h_errs.p() + nc, c->d_errs.p() + MAX_CONTIGS, nc * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->emit_stream));
     return MSIM_OK;
 }
 
@@ -1024,7 +1016,7 @@ int apply_finish(Ctx *c) {
         if (rc) return rc;
         MSIM_HIP(c, wait_stream(c->emit_stream));
     }
-    unsigned long long *errs = c->h_errs, *deltas = c->h_errs + nc;
+    unsigned long long *errs = c->h_errs.p(), *deltas = c->h_errs.p() + nc;
     bool delta_mismatch = false;
     hipEvent_t origin = nullptr;
     std::vector<std::pair<float, float>> spans_all, spans_k;
@@ -1094,13 +1086,13 @@ uint32_t apply_tile_shift() { return (uint32_t)__builtin_ctz((unsigned)TILE); }
 int apply_prepare_tile_index(Ctx *c, Contig &g, hipStream_t st, int32_t **first, uint32_t *n_tiles, uint32_t *tile_shift,
                              unsigned long long **err) {
     const uint32_t nt = (uint32_t)((g.len + TILE - 1) / TILE);      // (SNP-only: the mutated contig is as long as the contig)
-    if (g.cap_first < (size_t)(nt + 1) * sizeof(int32_t)) MSIM_HIP(c, wait_stream(st));
-    const int rc = dev_reserve(c, (void **)&g.d_first, &g.cap_first, (size_t)(nt + 1) * sizeof(int32_t));
+    if (g.d_first.cap < (size_t)(nt + 1) * sizeof(int32_t)) MSIM_HIP(c, wait_stream(st));
+    const int rc = dev_reserve(c, g.d_first, (size_t)(nt + 1) * sizeof(int32_t));
     if (rc) return rc;
-    *first = g.d_first;
+    *first = g.d_first.p();
     *n_tiles = nt;
     *tile_shift = (uint32_t)__builtin_ctz((unsigned)TILE);
-    *err = c->d_errs + g.index;
+    *err = c->d_errs.p() + g.index;
     g.tile_index_by_plan = nt != 0;
     return MSIM_OK;
 }
@@ -1134,8 +1126,8 @@ int apply_batch_device(Ctx *c, const std::vector<int> &ids, bool batch_rewrites)
         if (!g.all_snp && !dyn && ((long long)g.len + g.known_delta < 0 || (long long)g.len + g.known_delta >= (1ll << 32))) continue;
         st = g.apply_stream;
         const uint32_t n_tiles = (uint32_t)((out_bound + TILE - 1) / TILE);
-        if (g.cap_first < (size_t)(n_tiles + 1) * sizeof(int32_t)) MSIM_HIP(c, wait_stream(st));
-        int rc = dev_reserve(c, (void **)&g.d_first, &g.cap_first, (size_t)(n_tiles + 1) * sizeof(int32_t));
+        if (g.d_first.cap < (size_t)(n_tiles + 1) * sizeof(int32_t)) MSIM_HIP(c, wait_stream(st));
+        int rc = dev_reserve(c, g.d_first, (size_t)(n_tiles + 1) * sizeof(int32_t));
         if (rc) return rc;
         if (!g.ea0) {
             MSIM_HIP(c, hipEventCreate(&g.ea0));
@@ -1157,7 +1149,7 @@ int apply_batch_device(Ctx *c, const std::vector<int> &ids, bool batch_rewrites)
             continue;
         }
         TileJob &T = J.j[J.n_jobs++];
-        T.off = g.all_snp ? nullptr : g.d_off; T.recs = g.d_recs; T.dyn = dyn; T.first = g.d_first; T.err = c->d_errs + g.index;
+        T.off = g.all_snp ? nullptr : g.d_off.p(); T.recs = g.d_recs.p(); T.dyn = dyn; T.first = g.d_first.p(); T.err = c->d_errs.p() + g.index;
         T.n = n; T.n_entries = n_tiles + 1; T.entry_base = J.total; T.rsv = 0;
         J.total += n_tiles + 1;
         g.tile_index_done = true;
@@ -1231,7 +1223,7 @@ int apply_contig_device(Ctx *c, Contig &g) {
         int rc = apply_finish(c);
         if (rc) return rc;
     }
-    unsigned long long *d_err = c->d_errs + g.index;
+    unsigned long long *d_err = c->d_errs.p() + g.index;
     if (!(c->rw_collect && g.tile_index_done)) { MSIM_HIP(c, hipEventRecord(g.ea0, st)); g.ea0_is_ea1 = false; }   // (batched: apply_batch_device recorded the batch's)
     // ---- 1. output offsets (skipped for an SNP-only table: no length change, offset == position)
     long long total_delta = 0;
@@ -1239,19 +1231,19 @@ int apply_contig_device(Ctx *c, Contig &g) {
     const uint32_t *d_off = nullptr;
     if (dyn) {
         total_delta = g.all_snp ? 0 : (long long)g.out_cap_len - (long long)g.len;
-        d_off = g.all_snp ? nullptr : g.d_off;
+        d_off = g.all_snp ? nullptr : g.d_off.p();
     } else if (n && !g.all_snp && g.off_ready) {           // planned on the device: the offsets came with the records
         total_delta = g.known_delta;
-        d_off = g.d_off;
+        d_off = g.d_off.p();
     } else if (n && !g.all_snp) {
-        int rc = dev_reserve(c, (void **)&g.d_off, &g.cap_off, (size_t)n * sizeof(uint32_t));
+        int rc = dev_reserve(c, g.d_off, (size_t)n * sizeof(uint32_t));
         if (rc) return rc;
         rc = ensure_scratch(c, (size_t)(nb + 1) * sizeof(long long));
         if (rc) return rc;
-        long long *d_sums = reinterpret_cast<long long *>(c->d_scratch);
-        hipLaunchKernelGGL(k_delta_reduce, dim3(nb), dim3(THREADS), 0, st, g.d_recs, n, d_sums);
+        long long *d_sums = reinterpret_cast<long long *>(c->d_scratch.raw);
+        hipLaunchKernelGGL(k_delta_reduce, dim3(nb), dim3(THREADS), 0, st, g.d_recs.p(), n, d_sums);
         hipLaunchKernelGGL(k_scan_sums, dim3(1), dim3(1024), 0, st, d_sums, nb);
-        hipLaunchKernelGGL(k_offsets, dim3(nb), dim3(THREADS), 0, st, g.d_recs, n, d_sums, g.d_off);
+        hipLaunchKernelGGL(k_offsets, dim3(nb), dim3(THREADS), 0, st, g.d_recs.p(), n, d_sums, g.d_off.p());
         MSIM_HIP(c, hipGetLastError());
         if (g.delta_known) {
             // the planner summed the length changes while it ran the boundary chain: no round trip.  The
@@ -1259,24 +1251,24 @@ int apply_contig_device(Ctx *c, Contig &g) {
             total_delta = g.known_delta;
             hipLaunchKernelGGL(k_publish_u64, dim3(1), dim3(1), 0, st,
                                reinterpret_cast<const unsigned long long *>(d_sums + nb),
-                               c->d_errs + MAX_CONTIGS + g.index);
+                               c->d_errs.p() + MAX_CONTIGS + g.index);
             MSIM_HIP(c, hipGetLastError());
         } else {
             hipLaunchKernelGGL(k_publish_u64, dim3(1), dim3(1), 0, st,
-                               reinterpret_cast<const unsigned long long *>(d_sums + nb), c->h_mail);
+                               reinterpret_cast<const unsigned long long *>(d_sums + nb), c->h_mail.p());
             MSIM_HIP(c, hipGetLastError());
             MSIM_HIP(c, wait_stream(st));
-            total_delta = (long long)*c->h_mail;
+            total_delta = (long long)*c->h_mail.p();
         }
-        d_off = g.d_off;
+        d_off = g.d_off.p();
     }
     const long long out_len_ll = (long long)g.len + total_delta;
     if (out_len_ll < 0 || (uint64_t)out_len_ll >= (1ull << 32))
         return fail(c, MSIM_ERR_UNSUPPORTED, "mutated contig of 4 GiB or more");
     g.out_len = (uint64_t)out_len_ll;
-    if (g.cap_out < g.out_len + PAD) {                     // replacing a buffer: nothing may be in flight on it
+    if (g.d_out.cap < g.out_len + PAD) {                     // replacing a buffer: nothing may be in flight on it
         MSIM_HIP(c, wait_stream(st));
-        int rc = dev_reserve(c, (void **)&g.d_out, &g.cap_out, g.out_len + PAD);
+        int rc = dev_reserve(c, g.d_out, g.out_len + PAD);
         if (rc) return rc;
     }
     // ---- 2. tile index
@@ -1284,18 +1276,18 @@ int apply_contig_device(Ctx *c, Contig &g) {
     int32_t *d_first = nullptr;
     if (n_tiles) {
         if (g.apply_stream) {
-            if (g.cap_first < (size_t)(n_tiles + 1) * sizeof(int32_t)) MSIM_HIP(c, wait_stream(st));
-            int rc = dev_reserve(c, (void **)&g.d_first, &g.cap_first, (size_t)(n_tiles + 1) * sizeof(int32_t));
+            if (g.d_first.cap < (size_t)(n_tiles + 1) * sizeof(int32_t)) MSIM_HIP(c, wait_stream(st));
+            int rc = dev_reserve(c, g.d_first, (size_t)(n_tiles + 1) * sizeof(int32_t));
             if (rc) return rc;
-            d_first = g.d_first;
+            d_first = g.d_first.p();
         } else {
             int rc = ensure_scratch(c, (size_t)(n_tiles + 1) * sizeof(int32_t) + 64);
             if (rc) return rc;
-            d_first = reinterpret_cast<int32_t *>(reinterpret_cast<uint8_t *>(c->d_scratch) + 64);
+            d_first = reinterpret_cast<int32_t *>(reinterpret_cast<uint8_t *>(c->d_scratch.raw) + 64);
         }
         if (!g.tile_index_done) {                          // (else: apply_batch_device did it for the whole batch)
             hipLaunchKernelGGL(k_tile_index, dim3((n_tiles + 1 + THREADS - 1) / THREADS), dim3(THREADS), 0, st,
-                               d_off, g.d_recs, n, d_first, n_tiles + 1, dyn, d_err);
+                               d_off, g.d_recs.p(), n, d_first, n_tiles + 1, dyn, d_err);
             MSIM_HIP(c, hipGetLastError());
         }
     } else {
@@ -1311,8 +1303,8 @@ int apply_contig_device(Ctx *c, Contig &g) {
                                    : (uint64_t)n * 5 + 64 * 4 < (uint64_t)n_tiles * REC_CAP_SMALL * 4;
         RwPending p;
         memset(&p, 0, sizeof p);
-        p.job.in = g.d_in + PAD; p.job.out = g.d_out; p.job.recs = g.d_recs; p.job.off = d_off;
-        p.job.first = d_first; p.job.pool = g.d_pool ? g.d_pool + PAD : nullptr; p.job.err = d_err; p.job.dyn = dyn;
+        p.job.in = g.d_in.p() + PAD; p.job.out = g.d_out.p(); p.job.recs = g.d_recs.p(); p.job.off = d_off;
+        p.job.first = d_first; p.job.pool = g.d_pool.p() ? g.d_pool.p() + PAD : nullptr; p.job.err = d_err; p.job.dyn = dyn;
         p.job.L_out = g.out_len; p.job.n_rec = n; p.job.n_tiles = n_tiles;
         p.variant = g.all_snp ? 0 : (small_win ? 1 : 2);
         p.contig = g.index;
@@ -1323,14 +1315,14 @@ int apply_contig_device(Ctx *c, Contig &g) {
         const bool small_win = dyn ? g.n_struct_est * 2 < (uint64_t)n_tiles * REC_CAP_SMALL
                                    : (uint64_t)n * 5 + 64 * 4 < (uint64_t)n_tiles * REC_CAP_SMALL * 4;
         if (g.all_snp)
-            hipLaunchKernelGGL(k_rewrite_snp, dim3(n_tiles), dim3(THREADS), 0, st, g.d_in + PAD, g.d_out, g.d_recs,
+            hipLaunchKernelGGL(k_rewrite_snp, dim3(n_tiles), dim3(THREADS), 0, st, g.d_in.p() + PAD, g.d_out.p(), g.d_recs.p(),
                                d_first, n, g.out_len, ctx_lut(c), d_err, dyn);
         else if (small_win)
-            hipLaunchKernelGGL(k_rewrite<REC_CAP_SMALL>, dim3(n_tiles), dim3(THREADS), 0, st, g.d_in + PAD, g.d_out, g.d_recs,
-                               d_off, d_first, n, g.out_len, g.d_pool + PAD, ctx_lut(c), d_err, dyn);
+            hipLaunchKernelGGL(k_rewrite<REC_CAP_SMALL>, dim3(n_tiles), dim3(THREADS), 0, st, g.d_in.p() + PAD, g.d_out.p(), g.d_recs.p(),
+                               d_off, d_first, n, g.out_len, g.d_pool.p() + PAD, ctx_lut(c), d_err, dyn);
         else
-            hipLaunchKernelGGL(k_rewrite<REC_CAP>, dim3(n_tiles), dim3(THREADS), 0, st, g.d_in + PAD, g.d_out, g.d_recs,
-                               d_off, d_first, n, g.out_len, g.d_pool + PAD, ctx_lut(c), d_err, dyn);
+            hipLaunchKernelGGL(k_rewrite<REC_CAP>, dim3(n_tiles), dim3(THREADS), 0, st, g.d_in.p() + PAD, g.d_out.p(), g.d_recs.p(),
+                               d_off, d_first, n, g.out_len, g.d_pool.p() + PAD, ctx_lut(c), d_err, dyn);
         MSIM_HIP(c, hipGetLastError());
     }
     if (!hand_over) {

@@ -304,7 +304,7 @@ struct BatchRun {
         rc = apply_contig_device(c, *g);
         if (rc) return rc;
         if (!B.h_out.reserve(out_total + 64)) return fail(c, MSIM_ERR_NOMEM, "batch staging buffer");
-        if (out_total) MSIM_HIP(c, hipMemcpyAsync(B.h_out.p, g->d_out, out_total, hipMemcpyDeviceToHost, c->emit_stream));
+        if (out_total) MSIM_HIP(c, hipMemcpyAsync(B.h_out.p, g->d_out.p(), out_total, hipMemcpyDeviceToHost, c->emit_stream));
         rc = apply_finish(c);                                  // synchronises the emit stream: the copy above included
         if (rc) return rc;
         if (g->out_len != out_total) return fail(c, MSIM_ERR_HIP, "internal: batch planner and device disagree on the mutated length");
@@ -396,7 +396,7 @@ int msim_batch_run(msim_ctx *p, const msim_batch_contig *contigs, int n) {
     if (!R.B.h_in.reserve(R.total + 64)) return fail(c, MSIM_ERR_NOMEM, "batch staging buffer");
     SuperContig super(c);
     if ((rc = super.make(R.total))) return rc;
-    uint8_t *const d_in = super.g->d_in;
+    uint8_t *const d_in = super.g->d_in.p();
     rc = beside([&] { R.ingest(d_in); }, [&] { return R.plan(); });
     if (rc) return rc;
     if (R.ingest_err != hipSuccess) { super.drop(); return hip_fail(c, R.ingest_err, "batch input upload"); }

@@ -178,7 +178,7 @@ int msim_gather_to_root(msim_ctx *p, int n, const int *contig_ids, const int *ow
     if (m && rank == root && m->recv.size() < (size_t)3 * n) { m->recv.resize((size_t)3 * n, nullptr); m->cap.resize((size_t)3 * n, 0); }
     bool any_remote = false;
     auto local_ptr = [&](Contig &g, int part) -> uint8_t * {
-        return part == 0 ? g.d_out : part == 1 ? reinterpret_cast<uint8_t *>(g.d_recs) : g.d_pool + PAD;
+        return part == 0 ? g.d_out.p() : part == 1 ? reinterpret_cast<uint8_t *>(g.d_recs.p()) : g.d_pool.p() + PAD;
     };
     for (int k = 0; k < n_ops; k++) {                      // buffers first: no allocation inside the group
         const int kind = (int)ops[5 * k], slot = (int)ops[5 * k + 1], part = (int)ops[5 * k + 2];
@@ -250,7 +250,7 @@ int msim_dbg_comm_loopback(msim_ctx *p, int contig, uint64_t *sum) {
     MSIM_HIP(c, hipMalloc(&buf, g.out_len + PAD));
     MSIM_HIP(c, hipMemset(buf, 0, g.out_len + PAD));
     int nrc = g_rccl.GroupStart();
-    if (!nrc) nrc = g_rccl.Send(g.d_out, g.out_len, NCCL_UINT8, m->rank, m->comm, c->emit_stream);
+    if (!nrc) nrc = g_rccl.Send(g.d_out.p(), g.out_len, NCCL_UINT8, m->rank, m->comm, c->emit_stream);
     if (!nrc) nrc = g_rccl.Recv(buf, g.out_len, NCCL_UINT8, m->rank, m->comm, c->emit_stream);
     const int erc = g_rccl.GroupEnd();
     if (!nrc) nrc = erc;

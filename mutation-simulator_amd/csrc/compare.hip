@@ -19,19 +19,18 @@ namespace msim {
 
 struct Held {                                  // msim_cmp_hold's copy of one contig's table
     bool have = false;
-    msim_record *d_recs = nullptr;
-    uint8_t *d_pool = nullptr;
+    Scratch<msim_record> d_recs;
+    Scratch<uint8_t> d_pool;
     uint64_t n_rec = 0, pool_len = 0;
-    uint8_t *d_flag_a = nullptr, *d_flag_b = nullptr;      // one byte per held / per current record (the last msim_cmp_counts)
-    size_t cap_flag_b = 0;
+    Scratch<uint8_t> d_flag_a, d_flag_b;                   // one byte per held / per current record (the last msim_cmp_counts)
     uint64_t n_flag_b = 0;
     bool counted = false;
 };
 
 struct CompareState {
     std::vector<Held> held;                    // by contig index
-    unsigned long long *d_out = nullptr;       // HIST_SLOTS x (A's counters, B's counters)
-    unsigned long long *h_out = nullptr;       // pinned copy of them
+    Scratch<unsigned long long> d_out;         // HIST_SLOTS x (A's counters, B's counters)
+    Pinned<unsigned long long> h_out;          // pinned copy of them
     EventPair tm;
     double kernel_ms = 0;
 };
@@ -106,18 +105,12 @@ int state_of(Ctx *c, CompareState **out) {
     if (!c->compare) {
         CompareState *S = new CompareState;
         c->compare = S;
-        MSIM_HIP(c, hipMalloc((void **)&S->d_out, OUT_WORDS * sizeof(unsigned long long)));
-        MSIM_HIP(c, hipHostMalloc((void **)&S->h_out, OUT_WORDS * sizeof(unsigned long long), hipHostMallocDefault));
+        MSIM_HIP(c, dev_alloc(S->d_out, OUT_WORDS * sizeof(unsigned long long)));
+        MSIM_HIP(c, pin_alloc(S->h_out, OUT_WORDS * sizeof(unsigned long long)));
         MSIM_HIP(c, S->tm.create());
     }
     *out = c->compare;
     return MSIM_OK;
-}
-
-void held_free(Held &h) {
-    void *bufs[] = {h.d_recs, h.d_pool, h.d_flag_a, h.d_flag_b};
-    for (void *p : bufs) if (p) (void)hipFree(p);
-    h = Held{};
 }
 
 Held *held_of(Ctx *c, int contig) {
@@ -128,36 +121,35 @@ Held *held_of(Ctx *c, int contig) {
 
 int counts_device(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32_t flags, uint64_t *counts, uint64_t tallies[2]) {
     h.counted = false;
-    if (g.n_rec > h.cap_flag_b) {
-        if (h.d_flag_b) { MSIM_HIP(c, hipFree(h.d_flag_b)); h.d_flag_b = nullptr; h.cap_flag_b = 0; }
-        MSIM_HIP(c, hipMalloc((void **)&h.d_flag_b, (size_t)g.n_rec));
-        h.cap_flag_b = (size_t)g.n_rec;
+    if (g.n_rec > h.d_flag_b.cap) {                        // exactly a byte per record
+        MSIM_HIP(c, h.d_flag_b.release());
+        MSIM_HIP(c, dev_alloc(h.d_flag_b, (size_t)g.n_rec));
     }
     h.n_flag_b = g.n_rec;
     if (h.n_rec || g.n_rec) {
-        const cmp::Table A{h.d_recs, h.n_rec, h.d_pool, h.pool_len};
-        const cmp::Table B{g.d_recs, g.n_rec, g.pool_len ? g.d_pool + PAD : nullptr, g.pool_len};
+        const cmp::Table A{h.d_recs.p(), h.n_rec, h.d_pool.p(), h.pool_len};
+        const cmp::Table B{g.d_recs.p(), g.n_rec, g.pool_len ? g.d_pool.p() + PAD : nullptr, g.pool_len};
         const uint64_t pass_a = (h.n_rec + CMP_PASS - 1) / CMP_PASS, pass_b = (g.n_rec + CMP_PASS - 1) / CMP_PASS;
-        MSIM_HIP(c, hipMemsetAsync(S->d_out, 0, OUT_WORDS * sizeof(unsigned long long), c->stream));
+        MSIM_HIP(c, hipMemsetAsync(S->d_out.p(), 0, OUT_WORDS * sizeof(unsigned long long), c->stream));
         MSIM_HIP(c, S->tm.begin(c->stream));
-        if (g.n_rec) MSIM_HIP(c, hipMemsetAsync(h.d_flag_b, 0, (size_t)g.n_rec, c->stream));
+        if (g.n_rec) MSIM_HIP(c, hipMemsetAsync(h.d_flag_b.p(), 0, (size_t)g.n_rec, c->stream));
         if (h.n_rec) {
             hipLaunchKernelGGL(k_cmp_match, dim3((unsigned)std::min<uint64_t>(pass_a, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
-                               g.d_in + PAD, g.len, A, B, flags & MSIM_CMP_EXACT, pass_a, h.d_flag_a, h.d_flag_b, S->d_out);
+                               g.d_in.p() + PAD, g.len, A, B, flags & MSIM_CMP_EXACT, pass_a, h.d_flag_a.p(), h.d_flag_b.p(), S->d_out.p());
             MSIM_HIP(c, hipGetLastError());
         }
         if (g.n_rec) {
             hipLaunchKernelGGL(k_cmp_tally, dim3((unsigned)std::min<uint64_t>(pass_b, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
-                               (const msim_record *)g.d_recs, g.n_rec, pass_b, (const uint8_t *)h.d_flag_b, S->d_out + CMP_BINS);
+                               (const msim_record *)g.d_recs.p(), g.n_rec, pass_b, (const uint8_t *)h.d_flag_b.p(), S->d_out.p() + CMP_BINS);
             MSIM_HIP(c, hipGetLastError());
         }
         MSIM_HIP(c, S->tm.end(c->stream));                  // (in front of the copy: the kernels alone)
-        MSIM_HIP(c, hipMemcpyAsync(S->h_out, S->d_out, OUT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        MSIM_HIP(c, hipMemcpyAsync(S->h_out.p(), S->d_out.p(), OUT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
         MSIM_HIP(c, wait_stream(c->stream));
         const int rc = S->tm.add_elapsed(c, &S->kernel_ms);
         if (rc) return rc;
         unsigned long long bins[2 * CMP_BINS];
-        hist_sum_slots(S->h_out, 2 * CMP_BINS, bins, 2 * CMP_BINS);
+        hist_sum_slots(S->h_out.p(), 2 * CMP_BINS, bins, 2 * CMP_BINS);
         cmp_finish(bins, bins + CMP_BINS, counts, tallies);
     }
     h.counted = true;
@@ -168,7 +160,6 @@ int counts_device(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32_t fl
 
 void compare_drop_all(Ctx *c) {
     if (!c->compare) return;
-    for (Held &h : c->compare->held) held_free(h);
     c->compare->held.clear();
 }
 
@@ -176,8 +167,6 @@ void compare_state_destroy(Ctx *c) {
     CompareState *S = c->compare;
     if (!S) return;
     compare_drop_all(c);
-    if (S->d_out) (void)hipFree(S->d_out);
-    if (S->h_out) (void)hipHostFree(S->h_out);
     S->tm.destroy();
     delete S;
     c->compare = nullptr;
@@ -204,16 +193,15 @@ int msim_cmp_hold(msim_ctx *p, int contig) {
     CompareState *S;
     if ((rc = state_of(c, &S))) return rc;
     if (S->held.size() <= (size_t)contig) S->held.resize((size_t)contig + 1);
-    Held &h = S->held[(size_t)contig];
-    held_free(h);
+    Held &h = S->held[(size_t)contig] = Held{};
     if (g->n_rec) {
-        MSIM_HIP(c, hipMalloc((void **)&h.d_recs, (size_t)g->n_rec * sizeof(msim_record)));
-        MSIM_HIP(c, hipMalloc((void **)&h.d_flag_a, (size_t)g->n_rec));
-        MSIM_HIP(c, hipMemcpyAsync(h.d_recs, g->d_recs, (size_t)g->n_rec * sizeof(msim_record), hipMemcpyDeviceToDevice, c->stream));
+        MSIM_HIP(c, dev_alloc(h.d_recs, (size_t)g->n_rec * sizeof(msim_record)));
+        MSIM_HIP(c, dev_alloc(h.d_flag_a, (size_t)g->n_rec));
+        MSIM_HIP(c, hipMemcpyAsync(h.d_recs.p(), g->d_recs.p(), (size_t)g->n_rec * sizeof(msim_record), hipMemcpyDeviceToDevice, c->stream));
     }
     if (g->pool_len) {
-        MSIM_HIP(c, hipMalloc((void **)&h.d_pool, (size_t)g->pool_len));
-        MSIM_HIP(c, hipMemcpyAsync(h.d_pool, g->d_pool + PAD, (size_t)g->pool_len, hipMemcpyDeviceToDevice, c->stream));
+        MSIM_HIP(c, dev_alloc(h.d_pool, (size_t)g->pool_len));
+        MSIM_HIP(c, hipMemcpyAsync(h.d_pool.p(), g->d_pool.p() + PAD, (size_t)g->pool_len, hipMemcpyDeviceToDevice, c->stream));
     }
     MSIM_HIP(c, wait_stream(c->stream));
     h.n_rec = g->n_rec;
@@ -228,7 +216,7 @@ int msim_cmp_release(msim_ctx *p, int contig) {
     if (c->host_only || !c->compare) return MSIM_OK;
     MSIM_HIP(c, wait_stream(c->stream));
     if (contig < 0) { compare_drop_all(c); return MSIM_OK; }
-    if (Held *h = held_of(c, contig)) held_free(*h);
+    if (Held *h = held_of(c, contig)) *h = Held{};
     return MSIM_OK;
 }
 
@@ -263,10 +251,10 @@ int msim_cmp_fetch(msim_ctx *p, int contig, uint64_t *n_held, uint64_t *held_poo
         if (!h->counted || !g.planned || g.n_rec != h->n_flag_b)
             return fail(c, MSIM_ERR_ARG, "the flags are those of the contig's last msim_cmp_counts: call it first");
     }
-    if (held && h->n_rec) MSIM_HIP(c, hipMemcpyAsync(held, h->d_recs, (size_t)h->n_rec * sizeof(msim_record), hipMemcpyDeviceToHost, c->stream));
-    if (held_pool && h->pool_len) MSIM_HIP(c, hipMemcpyAsync(held_pool, h->d_pool, (size_t)h->pool_len, hipMemcpyDeviceToHost, c->stream));
-    if (held_flags && h->n_rec) MSIM_HIP(c, hipMemcpyAsync(held_flags, h->d_flag_a, (size_t)h->n_rec, hipMemcpyDeviceToHost, c->stream));
-    if (current_flags && h->n_flag_b) MSIM_HIP(c, hipMemcpyAsync(current_flags, h->d_flag_b, (size_t)h->n_flag_b, hipMemcpyDeviceToHost, c->stream));
+    if (held && h->n_rec) MSIM_HIP(c, hipMemcpyAsync(held, h->d_recs.p(), (size_t)h->n_rec * sizeof(msim_record), hipMemcpyDeviceToHost, c->stream));
+    if (held_pool && h->pool_len) MSIM_HIP(c, hipMemcpyAsync(held_pool, h->d_pool.p(), (size_t)h->pool_len, hipMemcpyDeviceToHost, c->stream));
+    if (held_flags && h->n_rec) MSIM_HIP(c, hipMemcpyAsync(held_flags, h->d_flag_a.p(), (size_t)h->n_rec, hipMemcpyDeviceToHost, c->stream));
+    if (current_flags && h->n_flag_b) MSIM_HIP(c, hipMemcpyAsync(current_flags, h->d_flag_b.p(), (size_t)h->n_flag_b, hipMemcpyDeviceToHost, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
     return MSIM_OK;
 }
@@ -290,7 +278,7 @@ int msim_dbg_cmp_copy_floor(msim_ctx *p, int contig, double *ms) {
     if (!h) return fail(c, MSIM_ERR_ARG, "contig has no held table (msim_cmp_hold)");
     CompareState *S;
     if ((rc = state_of(c, &S))) return rc;
-    const CopySource tables[2] = {{h->d_recs, (size_t)h->n_rec * sizeof(msim_record)}, {g->d_recs, (size_t)g->n_rec * sizeof(msim_record)}};
+    const CopySource tables[2] = {{h->d_recs.p(), (size_t)h->n_rec * sizeof(msim_record)}, {g->d_recs.p(), (size_t)g->n_rec * sizeof(msim_record)}};
     return copy_floor(c, S->tm, tables, 2, ms);
 }
 

@@ -7,13 +7,15 @@
 #include <vector>
 
 #include "../../include/msim.h"
+#include "dev_block.h"
 #include "mt19937.h"
 
 namespace msim {
 
+// Its device buffers are blocks that own themselves (dev_block.h): a Contig is move-only.
 struct Contig {
     uint64_t len = 0;
-    uint8_t *d_in = nullptr;          // allocation; the bases (uint8, upper-cased) start at d_in + PAD
+    Scratch<uint8_t> d_in;            // allocation; the bases (uint8, upper-cased) start at d_in + PAD
     // plan result
     bool planned = false;
     bool plan_empty = true;
@@ -30,21 +32,19 @@ struct Contig {
     uint64_t out_cap_len = 0;         // 16-sigma bound of the mutated length: d_out's allocation and the APPLY grid
     uint64_t n_struct_est = 0;        // expected non-SNP candidates (selects the rewrite kernel's window)
     hipStream_t apply_stream = nullptr;   // the stream its PLAN ran on: its APPLY follows there (null: the context's emit stream)
-    int32_t *d_first = nullptr;       // tile index of its own (contigs on different streams cannot share the context's scratch)
-    size_t cap_first = 0;
+    Scratch<int32_t> d_first;         // tile index of its own (contigs on different streams cannot share the context's scratch)
     bool tile_index_done = false;     // (transient) apply_batch_device has already launched this contig's tile index
     bool tile_index_by_plan = false;  // (one shot) the SNP sampler's expansion is writing d_first on the contig's stream
                                       // (apply_prepare_tile_index): apply_batch_device launches no tile-index job for it
     bool timing_shared = false;       // its rewrite ran inside another contig's batched launch: that contig's events time it
     uint64_t n_rec = 0, pool_len = 0;
-    msim_record *d_recs = nullptr;    // sorted, visited-only records
-    uint8_t *d_pool = nullptr;        // allocation; insert bases start at d_pool + PAD
-    size_t cap_recs = 0, cap_pool = 0, cap_out = 0, cap_off = 0;   // bytes kept allocated across plans
+    Scratch<msim_record> d_recs;      // sorted, visited-only records
+    Scratch<uint8_t> d_pool;          // allocation; insert bases start at d_pool + PAD
     // apply result
     bool applied = false;
     uint64_t out_len = 0;
-    uint8_t *d_out = nullptr;
-    uint32_t *d_off = nullptr;        // output offset of every record
+    Scratch<uint8_t> d_out;           // (these four are kept allocated across plans)
+    Scratch<uint32_t> d_off;          // output offset of every record
     uint8_t key_base = 0;             // KeyError report
     uint64_t key_pos = 0;
     bool key_error = false;
@@ -64,15 +64,12 @@ struct Contig {
     // all_snp ... above describe that haplotype's compacted table (the ACTIVE table: what APPLY, the chain and the fetches read)
     // and `full` keeps the planner's; the VCF text always reads the full one (haplotype.hip: vcf_table).
     bool have_gt = false;
-    uint8_t *d_gt = nullptr;
-    size_t cap_gt = 0;
+    Scratch<uint8_t> d_gt;
     std::vector<uint8_t> h_gt;        // (host-only context)
     int hap = 0;                      // 0: the active table is the full one
-    msim_record *d_recs_hap = nullptr;    // hap == 0: the compacted tables' buffer (kept across selections); else: unused
-    size_t cap_recs_hap = 0;
+    Scratch<msim_record> d_recs_hap;      // hap == 0: the compacted tables' buffer (kept across selections); else: unused
     struct FullTable {                // hap != 0: the planner's table and what it had told APPLY about it
-        msim_record *d_recs = nullptr;
-        size_t cap_recs = 0;
+        Scratch<msim_record> d_recs;
         uint64_t n_rec = 0;
         bool all_snp = false, delta_known = false;
         long long known_delta = 0;
@@ -122,24 +119,20 @@ struct Ctx {
     FastPlan *fast = nullptr;             //   ... and the engine's streams + scratch (plan_fast.hip)
     msim_timing t{};
     // device scratch
-    void *d_scratch = nullptr;
-    size_t scratch_bytes = 0;
-    unsigned long long *h_mail = nullptr;   // pinned, device-visible mailbox for small results
-    unsigned long long *d_errs = nullptr;   // one KeyError word per contig
-    unsigned long long *h_errs = nullptr;   // pinned copy of them (apply_finish)
-    size_t cap_h_errs = 0;
+    DevBlock d_scratch;
+    Pinned<unsigned long long> h_mail;      // pinned, device-visible mailbox for small results
+    Scratch<unsigned long long> d_errs;     // one KeyError word per contig
+    Pinned<unsigned long long> h_errs;      // pinned copy of them (apply_finish)
     std::vector<int> pending_apply;
     // text on the device (text_gpu.hip): rendered VCF lines / framed FASTA body / raw FASTA body staging
-    uint8_t *d_text = nullptr;
-    size_t cap_text = 0;
+    Scratch<uint8_t> d_text;
     uint64_t text_len = 0;
     int text_contig = -1, text_kind = 0;  // what d_text currently holds: 1 VCF lines, 2 framed FASTA body, 3 liftover chain
     uint32_t text_bpl = 0;
     uint64_t text_chain_id = 0;           // kind 3: the chain id and the names (tName '\n' qName) the text was rendered with
     std::string text_chain_names;
     double chain_kernel_ms = -1.0;        // >= 0: msim_dbg_chain_ms asked for the chain kernels' time; that of the last rendering
-    uint8_t *d_text_scratch = nullptr;
-    size_t cap_text_scratch = 0;
+    Scratch<uint8_t> d_text_scratch;
 };
 
 // roctx range (rocprofv3 --marker-trace shows PLAN / APPLY / text / gather per contig).  The marker library is
@@ -421,12 +414,12 @@ bool fast_lane_joined_at_collect(const Ctx *c, hipStream_t s);
 int fast_plan_emulated(Ctx *c, uint64_t L, const msim_range *ranges, int n_ranges, uint64_t key, uint32_t seq, HostPlan &out);
 
 // text_gpu.hip
-// (buf / cap: render there instead of into the context's text buffer -- an output channel's; text_len is then left alone)
-int vcf_render_device(Ctx *c, Contig &g, const char *seq_name, uint64_t *bytes, uint8_t **buf = nullptr, size_t *cap = nullptr);
+// (into: render there instead of into the context's text buffer -- an output channel's; text_len is then left alone)
+int vcf_render_device(Ctx *c, Contig &g, const char *seq_name, uint64_t *bytes, DevBlock *into = nullptr);
 // liftover chain of one planned contig into c->d_text / c->text_len (kernel_ms: optional, the kernels' time by HIP events)
 int chain_render_device(Ctx *c, Contig &g, const char *t_name, const char *q_name, uint64_t id, double *kernel_ms = nullptr);
 uint32_t chain_tile();                 // records / gaps of a workgroup of the chain kernels (CH_TILE), for the tests' edge cases
-int fasta_frame_device(Ctx *c, Contig &g, uint32_t bpl, uint64_t *bytes, uint8_t **buf = nullptr, size_t *cap = nullptr);
+int fasta_frame_device(Ctx *c, Contig &g, uint32_t bpl, uint64_t *bytes, DevBlock *into = nullptr);
 int splice_device(Ctx *c, const Contig &a, const Contig *b, const uint32_t *seg_out, const uint32_t *seg_src, uint32_t n_seg,
                   Contig &dst);
 int fasta_gather_device(Ctx *c, const uint8_t *body, uint64_t body_bytes, uint64_t n_bases, uint32_t lenc,
@@ -434,7 +427,7 @@ int fasta_gather_device(Ctx *c, const uint8_t *body, uint64_t body_bytes, uint64
 
 // file_io.hip: device text -> output files on the channels' own threads (0 the Fasta, 1 the VCF)
 int file_check(Ctx *c, int fd);
-int file_text_buffer(Ctx *c, int ch, int *slot, uint8_t ***buf, size_t **cap);
+int file_text_buffer(Ctx *c, int ch, int *slot, DevBlock **buf);
 int file_enqueue(Ctx *c, int ch, int slot, uint64_t n, int fd, uint64_t offset);
 int file_enqueue_host(Ctx *c, int ch, const uint8_t *src, uint64_t n, int fd, uint64_t offset);
 void file_channel_idle(Ctx *c, int ch);
@@ -478,6 +471,6 @@ int synth_contig_device(Ctx *c, uint8_t *d_dst, uint64_t len, uint64_t seed);
 int checksum_device(Ctx *c, const uint8_t *d_src, uint64_t len, uint64_t *sum);
 int ensure_scratch(Ctx *c, size_t bytes);
 // grow-only device buffer (contents are NOT preserved)
-int dev_reserve(Ctx *c, void **p, size_t *cap, size_t want_bytes);
+int dev_reserve(Ctx *c, DevBlock &b, size_t want_bytes);
 
 }  // namespace msim

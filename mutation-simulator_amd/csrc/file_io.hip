@@ -66,8 +66,7 @@ struct FileChannel {
     uint8_t *pin = nullptr;
     hipEvent_t ev[FILE_SLOTS] = {};
     // text buffers (device), filled by the calling thread on the context's stream
-    uint8_t *d_buf[2] = {nullptr, nullptr};
-    size_t cap[2] = {0, 0};
+    Scratch<uint8_t> d_buf[2];
     bool in_flight[2] = {false, false};
     hipEvent_t ready[2] = {nullptr, nullptr};
     // BGZF mode (bgzf.hip).  The calling thread's view: on, the file, the uncompressed bytes queued so far.
@@ -435,11 +434,12 @@ uint64_t bgzf_bound(uint64_t n) { return (n + BGZF_BLOCK - 1) / BGZF_BLOCK * (BG
 int bgzf_compress_host(Ctx *c, const uint8_t *src, uint64_t n, uint8_t *out, uint64_t cap, uint64_t *written, float *device_ms) {
     if (cap < bgzf_bound(n)) return fail(c, MSIM_ERR_ARG, "BGZF output buffer smaller than msim_bgzf_bound");
     BgzfWork w;
-    uint8_t *d_in = nullptr;
+    Scratch<uint8_t> in;                                   // (whatever ends the call frees it)
     uint64_t done = 0, pos = 0;
     hipEvent_t ev[2] = {nullptr, nullptr};
     float total_ms = 0;
-    hipError_t e = hipMalloc((void **)&d_in, BZ_STAGE + PAD);
+    hipError_t e = dev_alloc(in, BZ_STAGE + PAD);
+    uint8_t *const d_in = in.p();
     for (int i = 0; i < 2 && e == hipSuccess && device_ms; i++) e = hipEventCreate(&ev[i]);
     while (e == hipSuccess && pos < n) {
         const uint64_t take = n - pos < BZ_STAGE ? n - pos : BZ_STAGE;
@@ -454,7 +454,7 @@ int bgzf_compress_host(Ctx *c, const uint8_t *src, uint64_t n, uint8_t *out, uin
         pos += take;
     }
     bgzf_work_free(w);
-    if (d_in) (void)hipFree(d_in);
+    (void)in.release();
     for (auto x : ev) if (x) (void)hipEventDestroy(x);
     if (device_ms) *device_ms = total_ms;
     if (e != hipSuccess) return fail(c, MSIM_ERR_HIP, std::string("BGZF compression: ") + hipGetErrorString(e));
@@ -582,15 +582,14 @@ int file_check(Ctx *c, int fd) {
 }
 
 // A device buffer of channel `ch` that no queued job reads (waits for the older of the two jobs when both are queued).
-// *buf / *cap: the buffer's pointer and capacity (grow it with dev_reserve); *slot: for file_enqueue.
-int file_text_buffer(Ctx *c, int ch_id, int *slot, uint8_t ***buf, size_t **cap) {
+// *buf: the buffer's block (grow it with dev_reserve); *slot: for file_enqueue.
+int file_text_buffer(Ctx *c, int ch_id, int *slot, DevBlock **buf) {
     FileChannel &ch = io_get(c)->ch[ch_id];
     std::unique_lock<std::mutex> lk(ch.mu);
     ch.cv_done.wait(lk, [&] { return !ch.in_flight[0] || !ch.in_flight[1]; });
     const int s = !ch.in_flight[0] ? 0 : 1;
     *slot = s;
     *buf = &ch.d_buf[s];
-    *cap = &ch.cap[s];
     return MSIM_OK;
 }
 
@@ -603,7 +602,7 @@ int file_enqueue(Ctx *c, int ch_id, int slot, uint64_t n, int fd, uint64_t offse
     if (ch.bz) {                                            // BGZF mode: `offset` is the uncompressed stream's length
         if (offset != ch.bz_queued) return fail(c, MSIM_ERR_ARG, "BGZF channel: offset is not the end of the stream");
         MSIM_HIP(c, hipEventRecord(ch.ready[slot], c->stream));
-        FileJob job{ch.d_buf[slot], nullptr, slot, n, -1, offset, false, false, nullptr};
+        FileJob job{ch.d_buf[slot].p(), nullptr, slot, n, -1, offset, false, false, nullptr};
         job.bgzf = true;
         return bz_push(c, ch, job);
     }
@@ -622,7 +621,7 @@ int file_enqueue(Ctx *c, int ch_id, int slot, uint64_t n, int fd, uint64_t offse
             ch.started = true;
         }
         ch.in_flight[slot] = true;
-        ch.q.push_back(FileJob{ch.d_buf[slot], nullptr, slot, n, own, offset, false, false, nullptr});
+        ch.q.push_back(FileJob{ch.d_buf[slot].p(), nullptr, slot, n, own, offset, false, false, nullptr});
     }
     ch.cv_job.notify_one();
     return MSIM_OK;
@@ -696,7 +695,7 @@ void file_io_destroy(Ctx *c) {
         if (ch.bz_fd >= 0) (void)close(ch.bz_fd);
         for (int s = 0; s < 2; s++) {
             if (ch.ready[s]) (void)hipEventDestroy(ch.ready[s]);
-            if (ch.d_buf[s]) (void)hipFree(ch.d_buf[s]);
+            (void)ch.d_buf[s].release();
         }
     }
     delete io;

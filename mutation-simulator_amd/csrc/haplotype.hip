@@ -124,9 +124,8 @@ uint32_t hap_block() { return (uint32_t)HAP_BLOCK; }
 
 void hap_restore_full(Contig &g) {
     if (!g.hap) return;
-    g.d_recs_hap = g.d_recs; g.cap_recs_hap = g.cap_recs;
-    g.d_recs = g.full.d_recs; g.cap_recs = g.full.cap_recs;
-    g.full.d_recs = nullptr; g.full.cap_recs = 0;
+    g.d_recs_hap = std::move(g.d_recs);
+    g.d_recs = std::move(g.full.d_recs);
     g.n_rec = g.full.n_rec;
     g.all_snp = g.full.all_snp;
     g.delta_known = g.full.delta_known;
@@ -146,18 +145,17 @@ void hap_forget(Contig &g) {
 
 int hap_free(Ctx *c, Contig &g) {
     hap_forget(g);
-    if (g.d_recs_hap) { MSIM_HIP(c, hipFree(g.d_recs_hap)); g.d_recs_hap = nullptr; }
-    if (g.d_gt) { MSIM_HIP(c, hipFree(g.d_gt)); g.d_gt = nullptr; }
-    g.cap_recs_hap = g.cap_gt = 0;
+    MSIM_HIP(c, g.d_recs_hap.release());
+    MSIM_HIP(c, g.d_gt.release());
     return MSIM_OK;
 }
 
 TableView vcf_table(const Contig &g) {
     TableView v;
-    v.d_recs = g.hap ? g.full.d_recs : g.d_recs;
+    v.d_recs = g.hap ? g.full.d_recs.p() : g.d_recs.p();
     v.n_rec = g.hap ? g.full.n_rec : g.n_rec;
     v.all_snp = g.hap ? g.full.all_snp : g.all_snp;
-    v.d_gt = g.have_gt ? g.d_gt : nullptr;
+    v.d_gt = g.have_gt ? g.d_gt.p() : nullptr;
     return v;
 }
 
@@ -172,11 +170,11 @@ int hap_genotype(Ctx *c, Contig &g, uint64_t key, uint32_t seq, uint64_t het_thr
         g.have_gt = true;
         return MSIM_OK;
     }
-    const int rc = dev_reserve(c, (void **)&g.d_gt, &g.cap_gt, (size_t)n + PAD);
+    const int rc = dev_reserve(c, g.d_gt, (size_t)n + PAD);
     if (rc) return rc;
     if (n) {
-        hipLaunchKernelGGL(k_gt_draw, dim3((n + HAP_THREADS - 1) / HAP_THREADS), dim3(HAP_THREADS), 0, c->stream, g.d_recs, n,
-                           k.k0, k.k1, k.seq, (unsigned long long)het_thr, g.d_gt);
+        hipLaunchKernelGGL(k_gt_draw, dim3((n + HAP_THREADS - 1) / HAP_THREADS), dim3(HAP_THREADS), 0, c->stream, g.d_recs.p(), n,
+                           k.k0, k.k1, k.seq, (unsigned long long)het_thr, g.d_gt.p());
         MSIM_HIP(c, hipGetLastError());
         MSIM_HIP(c, wait_stream(c->stream));
     }
@@ -194,9 +192,9 @@ int hap_set_genotypes(Ctx *c, Contig &g, const uint8_t *gt) {
         g.have_gt = true;
         return MSIM_OK;
     }
-    const int rc = dev_reserve(c, (void **)&g.d_gt, &g.cap_gt, n + PAD);
+    const int rc = dev_reserve(c, g.d_gt, n + PAD);
     if (rc) return rc;
-    if (n) MSIM_HIP(c, hipMemcpyAsync(g.d_gt, gt, n, hipMemcpyHostToDevice, c->stream));
+    if (n) MSIM_HIP(c, hipMemcpyAsync(g.d_gt.p(), gt, n, hipMemcpyHostToDevice, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
     g.have_gt = true;
     return MSIM_OK;
@@ -206,7 +204,7 @@ int hap_fetch_genotypes(Ctx *c, Contig &g, uint8_t *dst) {
     const size_t n = (size_t)(g.hap ? g.full.n_rec : g.n_rec);
     if (!n) return MSIM_OK;
     if (c->host_only) { memcpy(dst, g.h_gt.data(), n); return MSIM_OK; }
-    MSIM_HIP(c, hipMemcpyAsync(dst, g.d_gt, n, hipMemcpyDeviceToHost, c->stream));
+    MSIM_HIP(c, hipMemcpyAsync(dst, g.d_gt.p(), n, hipMemcpyDeviceToHost, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
     return MSIM_OK;
 }
@@ -232,25 +230,24 @@ int hap_select(Ctx *c, Contig &g, int hap) {
         if (n) {
             int rc = ensure_scratch(c, (size_t)(nb + 1) * sizeof(uint32_t));
             if (rc) return rc;
-            uint32_t *d_cnt = reinterpret_cast<uint32_t *>(c->d_scratch);
-            hipLaunchKernelGGL(k_hap_count, dim3(nb), dim3(HAP_THREADS), 0, c->stream, g.d_gt, n, (uint32_t)hap, d_cnt);
+            uint32_t *d_cnt = reinterpret_cast<uint32_t *>(c->d_scratch.raw);
+            hipLaunchKernelGGL(k_hap_count, dim3(nb), dim3(HAP_THREADS), 0, c->stream, g.d_gt.p(), n, (uint32_t)hap, d_cnt);
             hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, d_cnt, nb);
             MSIM_HIP(c, hipGetLastError());
             MSIM_HIP(c, hipMemcpyAsync(&kept, d_cnt + nb, sizeof kept, hipMemcpyDeviceToHost, c->stream));
             MSIM_HIP(c, wait_stream(c->stream));
             if (kept > n) return fail(c, MSIM_ERR_HIP, "internal: haplotype selection counted more records than the table holds");
             if (kept) {
-                rc = dev_reserve(c, (void **)&g.d_recs_hap, &g.cap_recs_hap, (size_t)kept * sizeof(msim_record));
+                rc = dev_reserve(c, g.d_recs_hap, (size_t)kept * sizeof(msim_record));
                 if (rc) return rc;
-                hipLaunchKernelGGL(k_hap_compact, dim3(nb), dim3(HAP_THREADS), 0, c->stream, g.d_recs, g.d_gt, n, (uint32_t)hap, d_cnt,
-                                   g.d_recs_hap);
+                hipLaunchKernelGGL(k_hap_compact, dim3(nb), dim3(HAP_THREADS), 0, c->stream, g.d_recs.p(), g.d_gt.p(), n, (uint32_t)hap, d_cnt,
+                                   g.d_recs_hap.p());
                 MSIM_HIP(c, hipGetLastError());
                 MSIM_HIP(c, wait_stream(c->stream));
             }
         }
-        f.d_recs = g.d_recs; f.cap_recs = g.cap_recs;
-        g.d_recs = g.d_recs_hap; g.cap_recs = g.cap_recs_hap;
-        g.d_recs_hap = nullptr; g.cap_recs_hap = 0;
+        f.d_recs = std::move(g.d_recs);
+        g.d_recs = std::move(g.d_recs_hap);
     }
     g.full = std::move(f);
     g.hap = hap;

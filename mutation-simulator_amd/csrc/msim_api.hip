@@ -81,10 +81,10 @@ hipError_t wait_stream(hipStream_t s) { return wait_poll([s]() { return hipStrea
 hipError_t wait_event(hipEvent_t ev) { return wait_poll([ev]() { return hipEventQuery(ev); }); }
 
 struct CtxDev {            // small device-side constants owned by the ctx
-    uint8_t *d_lut = nullptr;
+    Scratch<uint8_t> d_lut;
 };
 static CtxDev *dev_of(Ctx *c);
-uint8_t *ctx_lut(Ctx *c) { return dev_of(c)->d_lut; }
+uint8_t *ctx_lut(Ctx *c) { return dev_of(c)->d_lut.p(); }
 
 // Everything enqueued has completed and its deferred results are collected: sampler flags + exact
 // stream position, APPLY timings + KeyError words.  Returns the sampler's error, if any.
@@ -158,7 +158,7 @@ int copy_floor(Ctx *c, const EventPair &tm, const CopySource *srcs, int n_srcs, 
     const int rc = ensure_scratch(c, total);
     if (rc) return rc;
     MSIM_HIP(c, tm.begin(c->stream));
-    uint8_t *dst = (uint8_t *)c->d_scratch;
+    uint8_t *dst = (uint8_t *)c->d_scratch.raw;
     for (int i = 0; i < n_srcs; dst += srcs[i++].bytes)
         if (srcs[i].bytes) MSIM_HIP(c, hipMemcpyAsync(dst, srcs[i].src, srcs[i].bytes, hipMemcpyDeviceToDevice, c->stream));
     MSIM_HIP(c, tm.end(c->stream));
@@ -226,17 +226,16 @@ int free_contig(Ctx *c, Contig &g, bool keep_input) {
         const int rc = hap_free(c, g);
         if (rc) return rc;
     }
-    if (g.d_recs) { MSIM_HIP(c, hipFree(g.d_recs)); g.d_recs = nullptr; }
-    if (g.d_pool) { MSIM_HIP(c, hipFree(g.d_pool)); g.d_pool = nullptr; }
-    if (g.d_out) { MSIM_HIP(c, hipFree(g.d_out)); g.d_out = nullptr; }
-    if (g.d_off) { MSIM_HIP(c, hipFree(g.d_off)); g.d_off = nullptr; }
-    if (g.d_first) { MSIM_HIP(c, hipFree(g.d_first)); g.d_first = nullptr; }
-    g.cap_recs = g.cap_pool = g.cap_out = g.cap_off = g.cap_first = 0;
+    MSIM_HIP(c, g.d_recs.release());
+    MSIM_HIP(c, g.d_pool.release());
+    MSIM_HIP(c, g.d_out.release());
+    MSIM_HIP(c, g.d_off.release());
+    MSIM_HIP(c, g.d_first.release());
     if (g.ea0) { (void)hipEventDestroy(g.ea0); (void)hipEventDestroy(g.ea1); (void)hipEventDestroy(g.ea2); g.ea0 = g.ea1 = g.ea2 = nullptr; }
     g.apply_pending = false;
     g.key_error = false;
     reset_contig(g);
-    if (!keep_input && g.d_in) { MSIM_HIP(c, hipFree(g.d_in)); g.d_in = nullptr; }
+    if (!keep_input) MSIM_HIP(c, g.d_in.release());
     return MSIM_OK;
 }
 
@@ -253,11 +252,11 @@ int new_contig(Ctx *c, uint64_t len, Contig **out) {
     g.index = (int)c->contigs.size();
     if (!c->host_only) {
         // PAD bytes of zero slack on BOTH sides: shifted 16-B reads may start before / end after the data
-        MSIM_HIP(c, hipMalloc(&g.d_in, len + 2 * PAD));
-        MSIM_HIP(c, hipMemsetAsync(g.d_in, 0, PAD, c->stream));
-        MSIM_HIP(c, hipMemsetAsync(g.d_in + PAD + len, 0, PAD, c->stream));
+        MSIM_HIP(c, dev_alloc(g.d_in, len + 2 * PAD));
+        MSIM_HIP(c, hipMemsetAsync(g.d_in.p(), 0, PAD, c->stream));
+        MSIM_HIP(c, hipMemsetAsync(g.d_in.p() + PAD + len, 0, PAD, c->stream));
     }
-    c->contigs.push_back(g);
+    c->contigs.push_back(std::move(g));
     *out = &c->contigs.back();
     return MSIM_OK;
 }
@@ -266,13 +265,13 @@ int new_contig(Ctx *c, uint64_t len, Contig **out) {
 int upload_table(Ctx *c, Contig *g, const msim_record *recs, const uint8_t *pool) {
     int rc = MSIM_OK;
     if (g->n_rec) {
-        rc = dev_reserve(c, (void **)&g->d_recs, &g->cap_recs, g->n_rec * sizeof(msim_record));
+        rc = dev_reserve(c, g->d_recs, g->n_rec * sizeof(msim_record));
         if (rc) return rc;
-        MSIM_HIP(c, hipMemcpyAsync(g->d_recs, recs, g->n_rec * sizeof(msim_record), hipMemcpyHostToDevice, c->stream));
+        MSIM_HIP(c, hipMemcpyAsync(g->d_recs.p(), recs, g->n_rec * sizeof(msim_record), hipMemcpyHostToDevice, c->stream));
     }
-    rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, g->pool_len + 2 * PAD);
+    rc = dev_reserve(c, g->d_pool, g->pool_len + 2 * PAD);
     if (rc) return rc;
-    if (g->pool_len) MSIM_HIP(c, hipMemcpyAsync(g->d_pool + PAD, pool, g->pool_len, hipMemcpyHostToDevice, c->stream));
+    if (g->pool_len) MSIM_HIP(c, hipMemcpyAsync(g->d_pool.p() + PAD, pool, g->pool_len, hipMemcpyHostToDevice, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));          // (the uploads read pageable vectors; APPLY runs on the emit stream)
     g->planned = true;
     return MSIM_OK;
@@ -359,10 +358,10 @@ int msim_create(int device_id, uint32_t flags, msim_ctx **out) {
         if ((e = hipEventCreate(ev)) != hipSuccess) return bail(e, "hipEventCreate");
     uint8_t lut[1280];
     build_lut(lut);
-    if ((e = hipMalloc(&c->dev.d_lut, sizeof lut)) != hipSuccess) return bail(e, "hipMalloc(lut)");
-    if ((e = hipMemcpy(c->dev.d_lut, lut, sizeof lut, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(lut)");
-    if ((e = hipMalloc(&c->d_errs, (size_t)2 * MAX_CONTIGS * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc(errs)");   // KeyError words + length-check words
-    if ((e = hipHostMalloc(&c->h_mail, 64, hipHostMallocMapped)) != hipSuccess) return bail(e, "hipHostMalloc(mailbox)");
+    if ((e = dev_alloc(c->dev.d_lut, sizeof lut)) != hipSuccess) return bail(e, "hipMalloc(lut)");
+    if ((e = hipMemcpy(c->dev.d_lut.p(), lut, sizeof lut, hipMemcpyHostToDevice)) != hipSuccess) return bail(e, "hipMemcpy(lut)");
+    if ((e = dev_alloc(c->d_errs, (size_t)2 * MAX_CONTIGS * sizeof(unsigned long long))) != hipSuccess) return bail(e, "hipMalloc(errs)");   // KeyError words + length-check words
+    if ((e = pin_alloc(c->h_mail, 64, hipHostMallocMapped)) != hipSuccess) return bail(e, "hipHostMalloc(mailbox)");
     c->gpu = gpu_plan_create();
     *out = reinterpret_cast<msim_ctx *>(static_cast<Ctx *>(c));
     return MSIM_OK;
@@ -388,12 +387,12 @@ void msim_destroy(msim_ctx *p) {
     (void)wait_stream(c->emit_stream);
     lap(0);
     for (auto &g : c->contigs) (void)free_contig(c, g, false);
-    if (c->d_scratch) (void)hipFree(c->d_scratch);
-    if (c->dev.d_lut) (void)hipFree(c->dev.d_lut);
-    if (c->d_errs) (void)hipFree(c->d_errs);
-    if (c->h_errs) (void)hipHostFree(c->h_errs);
-    if (c->d_text) (void)hipFree(c->d_text);
-    if (c->d_text_scratch) (void)hipFree(c->d_text_scratch);
+    (void)c->d_scratch.release();
+    (void)c->dev.d_lut.release();
+    (void)c->d_errs.release();
+    (void)c->h_errs.release();
+    (void)c->d_text.release();
+    (void)c->d_text_scratch.release();
     lap(1);
     batch_free(c);
     lap(2);
@@ -403,7 +402,7 @@ void msim_destroy(msim_ctx *p) {
     fast_plan_destroy(c);
     gpu_plan_destroy(c->gpu);
     lap(3);
-    if (c->h_mail) (void)hipHostFree(c->h_mail);
+    (void)c->h_mail.release();
     hipEvent_t evs[4] = {c->ev0, c->ev1, c->ev2, c->ev3};
     for (auto ev : evs) if (ev) (void)hipEventDestroy(ev);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -492,7 +491,7 @@ int msim_add_contig(msim_ctx *p, const uint8_t *bases, uint64_t len, int *contig
     int rc = new_contig(c, len, &g);
     if (rc) return rc;
     if (!c->host_only) {
-        if (len) MSIM_HIP(c, hipMemcpyAsync(g->d_in + PAD, bases, len, hipMemcpyHostToDevice, c->stream));
+        if (len) MSIM_HIP(c, hipMemcpyAsync(g->d_in.p() + PAD, bases, len, hipMemcpyHostToDevice, c->stream));
         MSIM_HIP(c, wait_stream(c->stream));
     }
     *contig = (int)c->contigs.size() - 1;
@@ -506,7 +505,7 @@ int msim_add_contig_synthetic(msim_ctx *p, uint64_t len, uint64_t seed, int *con
     Contig *g;
     int rc = new_contig(c, len, &g);
     if (rc) return rc;
-    rc = synth_contig_device(c, g->d_in + PAD, len, seed);
+    rc = synth_contig_device(c, g->d_in.p() + PAD, len, seed);
     if (rc) return rc;
     MSIM_HIP(c, wait_stream(c->stream));
     *contig = (int)c->contigs.size() - 1;
@@ -529,7 +528,7 @@ int msim_read_contig(msim_ctx *p, int contig, uint64_t offset, uint64_t n, uint8
     Contig *g = get_contig(c, contig);
     if (!g) return MSIM_ERR_ARG;
     if (offset > g->len || n > g->len - offset) return fail(c, MSIM_ERR_ARG, "read beyond contig end");
-    if (n) MSIM_HIP(c, hipMemcpyAsync(dst, g->d_in + PAD + offset, n, hipMemcpyDeviceToHost, c->stream));
+    if (n) MSIM_HIP(c, hipMemcpyAsync(dst, g->d_in.p() + PAD + offset, n, hipMemcpyDeviceToHost, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
     return MSIM_OK;
 }
@@ -793,7 +792,7 @@ int msim_fetch_sequence(msim_ctx *p, int contig, uint64_t offset, uint64_t n, ui
         if (g->key_error) return key_error_of(c, *g);
     }
     if (offset > g->out_len || n > g->out_len - offset) return fail(c, MSIM_ERR_ARG, "fetch beyond mutated contig end");
-    if (n) MSIM_HIP(c, hipMemcpyAsync(dst, g->d_out + offset, n, hipMemcpyDeviceToHost, c->stream));
+    if (n) MSIM_HIP(c, hipMemcpyAsync(dst, g->d_out.p() + offset, n, hipMemcpyDeviceToHost, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
     return MSIM_OK;
 }
@@ -814,9 +813,9 @@ int msim_fetch_records(msim_ctx *p, int contig, msim_record *dst, uint8_t *pool_
         if (rc) return rc;
     }
     if (dst && g->n_rec)
-        MSIM_HIP(c, hipMemcpyAsync(dst, g->d_recs, g->n_rec * sizeof(msim_record), hipMemcpyDeviceToHost, c->stream));
+        MSIM_HIP(c, hipMemcpyAsync(dst, g->d_recs.p(), g->n_rec * sizeof(msim_record), hipMemcpyDeviceToHost, c->stream));
     if (pool_dst && g->pool_len)
-        MSIM_HIP(c, hipMemcpyAsync(pool_dst, g->d_pool + PAD, g->pool_len, hipMemcpyDeviceToHost, c->stream));
+        MSIM_HIP(c, hipMemcpyAsync(pool_dst, g->d_pool.p() + PAD, g->pool_len, hipMemcpyDeviceToHost, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
     return MSIM_OK;
 }
@@ -832,7 +831,7 @@ int msim_result_checksum(msim_ctx *p, int contig, uint64_t *sum) {
         if (rc) return rc;
         if (g->key_error) return key_error_of(c, *g);
     }
-    return checksum_device(c, g->d_out, g->out_len, sum);
+    return checksum_device(c, g->d_out.p(), g->out_len, sum);
 }
 
 int msim_result_device_ptr(msim_ctx *p, int contig, uint64_t *device_address, uint64_t *len) {
@@ -845,7 +844,7 @@ int msim_result_device_ptr(msim_ctx *p, int contig, uint64_t *device_address, ui
     int rc = drain(c);
     if (rc) return rc;
     if (g->key_error) return key_error_of(c, *g);
-    *device_address = (uint64_t)(uintptr_t)g->d_out;
+    *device_address = (uint64_t)(uintptr_t)g->d_out.p();
     *len = g->out_len;
     return MSIM_OK;
 }
@@ -948,7 +947,7 @@ static int text_copy_out(Ctx *c, uint8_t *out, uint64_t cap, uint64_t *needed) {
     *needed = c->text_len;
     if (!out) return MSIM_OK;
     if (cap < c->text_len) return fail(c, MSIM_ERR_ARG, "text buffer too small (see *needed)");
-    if (c->text_len) MSIM_HIP(c, hipMemcpyAsync(out, c->d_text, c->text_len, hipMemcpyDeviceToHost, c->stream));
+    if (c->text_len) MSIM_HIP(c, hipMemcpyAsync(out, c->d_text.p(), c->text_len, hipMemcpyDeviceToHost, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
     return MSIM_OK;
 }
@@ -1062,12 +1061,11 @@ int msim_render_vcf_device_file(msim_ctx *p, int contig, const char *seq_name, i
     rc = drain(c);                                                       // record aux bytes come from the emit stream
     if (rc) return rc;
     int slot;
-    uint8_t **buf;
-    size_t *cap;
-    rc = file_text_buffer(c, 1, &slot, &buf, &cap);
+    DevBlock *buf;
+    rc = file_text_buffer(c, 1, &slot, &buf);
     if (rc) return rc;
     uint64_t bytes = 0;
-    rc = vcf_render_device(c, *g, seq_name, &bytes, buf, cap);
+    rc = vcf_render_device(c, *g, seq_name, &bytes, buf);
     if (rc) return rc;
     *written = bytes;
     return file_enqueue(c, 1, slot, bytes, fd, offset);
@@ -1087,12 +1085,11 @@ int msim_fetch_sequence_framed_file(msim_ctx *p, int contig, uint32_t bpl, int f
     if (rc) return rc;
     if (g->key_error) return key_error_of(c, *g);
     int slot;
-    uint8_t **buf;
-    size_t *cap;
-    rc = file_text_buffer(c, 0, &slot, &buf, &cap);
+    DevBlock *buf;
+    rc = file_text_buffer(c, 0, &slot, &buf);
     if (rc) return rc;
     uint64_t bytes = 0;
-    rc = fasta_frame_device(c, *g, bpl, &bytes, buf, cap);
+    rc = fasta_frame_device(c, *g, bpl, &bytes, buf);
     if (rc) return rc;
     *written = bytes;
     return file_enqueue(c, 0, slot, bytes, fd, offset);
@@ -1167,7 +1164,7 @@ int msim_add_contig_text(msim_ctx *p, const uint8_t *body, uint64_t body_bytes, 
     int rc = new_contig(c, n_bases, &g);
     if (rc) return rc;
     c->text_kind = 0;                                                    // the staging buffer is about to be reused
-    rc = fasta_gather_device(c, body, body_bytes, n_bases, lenc, lenb, g->d_in + PAD);
+    rc = fasta_gather_device(c, body, body_bytes, n_bases, lenc, lenb, g->d_in.p() + PAD);
     if (rc) return rc;
     *contig = (int)c->contigs.size() - 1;
     return MSIM_OK;
@@ -1428,9 +1425,9 @@ int msim_dbg_set_records(msim_ctx *p, int contig, const msim_record *recs, uint6
     g->delta_known = true;
     g->known_delta = delta;
     if (c->host_only || g->all_snp || !n_records) return MSIM_OK;      // (SNP-only: offset == position, no table)
-    rc = dev_reserve(c, (void **)&g->d_off, &g->cap_off, (size_t)n_records * sizeof(uint32_t));
+    rc = dev_reserve(c, g->d_off, (size_t)n_records * sizeof(uint32_t));
     if (rc) return rc;
-    MSIM_HIP(c, hipMemcpyAsync(g->d_off, off.data(), (size_t)n_records * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+    MSIM_HIP(c, hipMemcpyAsync(g->d_off.p(), off.data(), (size_t)n_records * sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
     g->off_ready = true;
     return MSIM_OK;

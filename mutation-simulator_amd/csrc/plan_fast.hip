@@ -24,27 +24,16 @@ namespace {
 
 constexpr int F_SETS = 3;                                  // batches in flight (one stream + one scratch set each)
 
-template <class T>
-struct DevBuf {
-    T *p = nullptr;
-    size_t cap = 0;                                        // elements
-};
-template <class T>
-struct PinBuf {
-    T *p = nullptr;
-    size_t cap = 0;
-};
-
 struct FastSet {
-    DevBuf<uint8_t> tab;                                   // FRange | Settings | SubDesc | big-range list: ONE copy per contig
-    PinBuf<uint8_t> h_tab;                                 // its pinned source
-    DevBuf<LeafDesc> leaves;
-    DevBuf<uint32_t> sub_k, sub_c0;                        // per subtree of 64 leaves: its points, its first candidate
-    DevBuf<uint32_t> cand_pos, cand_stop, cand_bend, cand_end2, blk_out, off_dummy;
-    DevBuf<uint32_t> kept;                                 // per contig of the batch: [0] kept any, [1] / [2] pass 1 / 2 handed over
-    DevBuf<uint8_t> cand_meta;
-    DevBuf<uint32_t> blk_u32;                              // S | indep | in | nrec | pool  (5 arrays of nb + 1)
-    DevBuf<long long> blk_delta;
+    Scratch<uint8_t> tab;                                   // FRange | Settings | SubDesc | big-range list: ONE copy per contig
+    Pinned<uint8_t> h_tab;                                 // its pinned source
+    Scratch<LeafDesc> leaves;
+    Scratch<uint32_t> sub_k, sub_c0;                        // per subtree of 64 leaves: its points, its first candidate
+    Scratch<uint32_t> cand_pos, cand_stop, cand_bend, cand_end2, blk_out, off_dummy;
+    Scratch<uint32_t> kept;                                 // per contig of the batch: [0] kept any, [1] / [2] pass 1 / 2 handed over
+    Scratch<uint8_t> cand_meta;
+    Scratch<uint32_t> blk_u32;                              // S | indep | in | nrec | pool  (5 arrays of nb + 1)
+    Scratch<long long> blk_delta;
     hipEvent_t done = nullptr;
     bool pending = false;
 };
@@ -96,9 +85,9 @@ struct FastPlan {
     HostProf prof;                                         // (per context: two contexts may plan from two threads)
     hipStream_t lane[F_SETS] = {};
     FastSet set[F_SETS];
-    uint32_t *d_flags = nullptr;                           // sticky FF_* flags of everything since the last collection
-    DynSizes *d_dyn = nullptr;                             // one per contig of the context
-    DynSizes *h_dyn = nullptr;                             // pinned copy (collection)
+    Scratch<uint32_t> d_flags;                             // sticky FF_* flags of everything since the last collection
+    Scratch<DynSizes> d_dyn;                               // one per contig of the context
+    Pinned<DynSizes> h_dyn;                                // pinned copy (collection)
     hipEvent_t t0 = nullptr, t1[F_SETS] = {};
     bool pending = false;                                  // work enqueued since the last collection
     std::vector<int> sized;                                // contigs whose sizes are still on the device only
@@ -127,15 +116,12 @@ struct FastPlan {
 namespace {
 
 template <class T>
-int dev_grow(Ctx *c, FastPlan *f, DevBuf<T> &b, size_t want) {
-    if (b.cap >= want) return MSIM_OK;
+int dev_grow(Ctx *c, FastPlan *f, Scratch<T> &b, size_t want) {     // want: elements
+    if (b.cap >= want * sizeof(T)) return MSIM_OK;
     // a buffer is replaced: nothing that may still use the old one can be in flight
     for (auto st : f->lane) if (st) MSIM_HIP(c, wait_stream(st));
-    if (b.p) MSIM_HIP(c, hipFree(b.p));
-    b.p = nullptr; b.cap = 0;
-    const size_t n = want + want / 4 + 1024;
-    MSIM_HIP(c, hipMalloc(&b.p, n * sizeof(T)));
-    b.cap = n;
+    MSIM_HIP(c, b.release());
+    MSIM_HIP(c, dev_alloc(b, (want + want / 4 + 1024) * sizeof(T)));
     return MSIM_OK;
 }
 
@@ -276,12 +262,12 @@ int ensure_plan(Ctx *c) {
     for (auto &s : f->set) {
         MSIM_HIP(c, hipEventCreateWithFlags(&s.done, hipEventDisableTiming));
     }
-    MSIM_HIP(c, hipMalloc(&f->d_flags, 64));
-    MSIM_HIP(c, hipMemset(f->d_flags, 0, 64));
-    MSIM_HIP(c, hipMalloc(&f->d_dyn, sizeof(DynSizes) * MAX_CONTIGS));
-    MSIM_HIP(c, hipHostMalloc(&f->h_dyn, sizeof(DynSizes) * MAX_CONTIGS * F_SETS + 256, hipHostMallocDefault));
-    for (int i = 0; i < F_SETS; i++) f->h_dyn_lane[i] = f->h_dyn + (size_t)i * MAX_CONTIGS;
-    f->h_flags = reinterpret_cast<uint32_t *>(f->h_dyn + (size_t)F_SETS * MAX_CONTIGS);
+    MSIM_HIP(c, dev_alloc(f->d_flags, 64));
+    MSIM_HIP(c, hipMemset(f->d_flags.p(), 0, 64));
+    MSIM_HIP(c, dev_alloc(f->d_dyn, sizeof(DynSizes) * MAX_CONTIGS));
+    MSIM_HIP(c, pin_alloc(f->h_dyn, sizeof(DynSizes) * MAX_CONTIGS * F_SETS + 256));
+    for (int i = 0; i < F_SETS; i++) f->h_dyn_lane[i] = f->h_dyn.p() + (size_t)i * MAX_CONTIGS;
+    f->h_flags = reinterpret_cast<uint32_t *>(f->h_dyn.p() + (size_t)F_SETS * MAX_CONTIGS);
     MSIM_HIP(c, hipEventCreate(&f->t0));
     for (auto &e : f->t1) MSIM_HIP(c, hipEventCreate(&e));
     return MSIM_OK;
@@ -294,15 +280,8 @@ void fast_plan_destroy(Ctx *c) {
     if (!f) return;
     for (auto st : f->lane) if (st) { (void)wait_stream(st); (void)hipStreamDestroy(st); }
     for (auto &s : f->set) {
-        void *bufs[] = {s.tab.p, s.leaves.p, s.sub_k.p, s.sub_c0.p, s.cand_pos.p, s.cand_stop.p, s.cand_bend.p, s.cand_end2.p, s.blk_out.p, s.off_dummy.p, s.kept.p,
-                        s.cand_meta.p, s.blk_u32.p, s.blk_delta.p};
-        for (void *p : bufs) if (p) (void)hipFree(p);
-        if (s.h_tab.p) (void)hipHostFree(s.h_tab.p);
         if (s.done) (void)hipEventDestroy(s.done);
     }
-    if (f->d_flags) (void)hipFree(f->d_flags);
-    if (f->d_dyn) (void)hipFree(f->d_dyn);
-    if (f->h_dyn) (void)hipHostFree(f->h_dyn);
     if (f->t0) (void)hipEventDestroy(f->t0);
     for (auto e : f->t1) if (e) (void)hipEventDestroy(e);
     delete f;
@@ -354,9 +333,9 @@ int fast_plan_collect(Ctx *c, int (*behind)(Ctx *), int *behind_state) {
         for (int i = 0; i < F_SETS; i++) {
             if (!f->set[i].pending) { f->h_flags[i] = 0; continue; }
             if (hi_idx[i] >= 0)
-                MSIM_HIP(c, hipMemcpyAsync(f->h_dyn_lane[i] + lo_idx[i], f->d_dyn + lo_idx[i], sizeof(DynSizes) * (size_t)(hi_idx[i] - lo_idx[i] + 1),
+                MSIM_HIP(c, hipMemcpyAsync(f->h_dyn_lane[i] + lo_idx[i], f->d_dyn.p() + lo_idx[i], sizeof(DynSizes) * (size_t)(hi_idx[i] - lo_idx[i] + 1),
                                            hipMemcpyDeviceToHost, f->lane[i]));
-            MSIM_HIP(c, hipMemcpyAsync(f->h_flags + i, f->d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, f->lane[i]));
+            MSIM_HIP(c, hipMemcpyAsync(f->h_flags + i, f->d_flags.p(), sizeof(uint32_t), hipMemcpyDeviceToHost, f->lane[i]));
             MSIM_HIP(c, hipEventRecord(f->t1[i], f->lane[i]));
         }
         // one host wait: the emit stream joins the lanes (their t1 events), takes the caller's copies, and is waited for --
@@ -404,7 +383,7 @@ int fast_plan_collect(Ctx *c, int (*behind)(Ctx *), int *behind_state) {
             }
         }
         if (flags) {
-            MSIM_HIP(c, hipMemset(f->d_flags, 0, 64));
+            MSIM_HIP(c, hipMemset(f->d_flags.p(), 0, 64));
             if (flags & (FF_POOL_OVERFLOW | FF_OUT_OVERFLOW))
                 return fail(c, MSIM_ERR_HIP, "fast RNG sampler: the mutated length or the insert pool overflowed its 16-sigma allocation (results discarded)");
             return fail(c, MSIM_ERR_HIP, "fast RNG sampler: internal error (flags " + std::to_string(flags) + "; results discarded)");
@@ -480,10 +459,8 @@ static int enqueue_batch(Ctx *c, std::vector<Pending> &items, bool orbit_only) {
                  off_bslot = up16(off_slots + (size_t)n_slots * sizeof(FSlot));
     const size_t tab_bytes = up16(off_bslot + (snp_only ? 0 : (size_t)nb_total * sizeof(uint32_t)));
     if (S.h_tab.cap < tab_bytes) {
-        if (S.h_tab.p) MSIM_HIP(c, hipHostFree(S.h_tab.p));
-        S.h_tab.p = nullptr; S.h_tab.cap = 0;
-        MSIM_HIP(c, hipHostMalloc(&S.h_tab.p, tab_bytes * 2 + 4096, hipHostMallocDefault));
-        S.h_tab.cap = tab_bytes * 2 + 4096;
+        MSIM_HIP(c, S.h_tab.release());
+        MSIM_HIP(c, pin_alloc(S.h_tab, tab_bytes * 2 + 4096));
     }
     if ((rc = dev_grow(c, f, S.tab, tab_bytes))) return rc;
     if ((rc = dev_grow(c, f, S.leaves, n_leaves))) return rc;
@@ -501,12 +478,12 @@ static int enqueue_batch(Ctx *c, std::vector<Pending> &items, bool orbit_only) {
         if ((rc = dev_grow(c, f, S.blk_u32, (size_t)7 * (nb_total + 1)))) return rc;
         if ((rc = dev_grow(c, f, S.blk_delta, nb_total + 1))) return rc;
     }
-    FRange *h_fr = reinterpret_cast<FRange *>(S.h_tab.p);
-    Settings *h_sets = reinterpret_cast<Settings *>(S.h_tab.p + off_sets);
-    SubDesc *h_subs = reinterpret_cast<SubDesc *>(S.h_tab.p + off_subs);
-    uint32_t *h_big = reinterpret_cast<uint32_t *>(S.h_tab.p + off_big);
-    FSlot *h_slots = reinterpret_cast<FSlot *>(S.h_tab.p + off_slots);
-    uint32_t *h_bslot = reinterpret_cast<uint32_t *>(S.h_tab.p + off_bslot);
+    FRange *h_fr = reinterpret_cast<FRange *>(S.h_tab.p());
+    Settings *h_sets = reinterpret_cast<Settings *>(S.h_tab.p() + off_sets);
+    SubDesc *h_subs = reinterpret_cast<SubDesc *>(S.h_tab.p() + off_subs);
+    uint32_t *h_big = reinterpret_cast<uint32_t *>(S.h_tab.p() + off_big);
+    FSlot *h_slots = reinterpret_cast<FSlot *>(S.h_tab.p() + off_slots);
+    uint32_t *h_bslot = reinterpret_cast<uint32_t *>(S.h_tab.p() + off_bslot);
     {
         uint32_t r0 = 0, s0 = 0, sub0 = 0, big0 = 0, leaf0 = 0, cand0 = 0, blk0 = 0;
         for (uint32_t si = 0; si < n_slots; si++) {
@@ -516,16 +493,16 @@ static int enqueue_batch(Ctx *c, std::vector<Pending> &items, bool orbit_only) {
             {   // the record table (and what APPLY reads beside it) may still be in use by an earlier APPLY of this contig
                 const size_t want = (size_t)P.K * sizeof(msim_record);
                 const size_t want_pool = (size_t)P.pool_cap + 2 * PAD, want_off = P.all_sn ? 0 : (size_t)P.K * sizeof(uint32_t);
-                if (ct.cap_recs < want || ct.cap_pool < want_pool || ct.cap_off < want_off) {
+                if (ct.d_recs.cap < want || ct.d_pool.cap < want_pool || ct.d_off.cap < want_off) {
                     MSIM_HIP(c, wait_stream(c->stream));
                     MSIM_HIP(c, wait_stream(c->emit_stream));
                     if (ct.apply_stream) MSIM_HIP(c, wait_stream(ct.apply_stream));
                 } else if (ct.apply_pending && ct.ea2) {
                     MSIM_HIP(c, hipStreamWaitEvent(st, ct.ea2, 0));
                 }
-                if ((rc = dev_reserve(c, (void **)&ct.d_recs, &ct.cap_recs, want))) return rc;
-                if ((rc = dev_reserve(c, (void **)&ct.d_pool, &ct.cap_pool, want_pool))) return rc;
-                if (want_off && (rc = dev_reserve(c, (void **)&ct.d_off, &ct.cap_off, want_off))) return rc;
+                if ((rc = dev_reserve(c, ct.d_recs, want))) return rc;
+                if ((rc = dev_reserve(c, ct.d_pool, want_pool))) return rc;
+                if (want_off && (rc = dev_reserve(c, ct.d_off, want_off))) return rc;
             }
             const uint32_t nb = (uint32_t)((P.K + OB_BLOCK - 1) / OB_BLOCK);
             for (size_t q = 0; q < P.fr.size(); q++) {
@@ -540,10 +517,10 @@ static int enqueue_batch(Ctx *c, std::vector<Pending> &items, bool orbit_only) {
             FSlot sl;
             memset(&sl, 0, sizeof sl);
             sl.L = ct.len; sl.out_cap = P.out_cap; sl.pool_cap = P.pool_cap;
-            sl.recs = ct.d_recs;
-            sl.rec_off = P.all_sn ? (snp_only ? nullptr : S.off_dummy.p + cand0) : ct.d_off;
-            sl.pool = ct.d_pool + PAD;
-            sl.dyn = f->d_dyn + ct.index;
+            sl.recs = ct.d_recs.p();
+            sl.rec_off = P.all_sn ? (snp_only ? nullptr : S.off_dummy.p() + cand0) : ct.d_off.p();
+            sl.pool = ct.d_pool.p() + PAD;
+            sl.dyn = f->d_dyn.p() + ct.index;
             sl.seq = it.seq; sl.K = (uint32_t)P.K; sl.cand_off = cand0; sl.blk_off = blk0; sl.nb = nb;
             sl.range_off = r0; sl.leaf_off = leaf0; sl.sub_off = sub0;
             h_slots[si] = sl;
@@ -553,24 +530,24 @@ static int enqueue_batch(Ctx *c, std::vector<Pending> &items, bool orbit_only) {
         }
     }
     c->fast->prof.lap(2);
-    MSIM_HIP(c, hipMemcpyAsync(S.tab.p, S.h_tab.p, tab_bytes, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemcpyAsync(S.tab.p(), S.h_tab.p(), tab_bytes, hipMemcpyHostToDevice, st));
     c->fast->prof.lap(3);
-    const FRange *d_ranges = reinterpret_cast<const FRange *>(S.tab.p);
-    const Settings *d_sets = reinterpret_cast<const Settings *>(S.tab.p + off_sets);
-    const SubDesc *d_subs = reinterpret_cast<const SubDesc *>(S.tab.p + off_subs);
-    const uint32_t *d_big = reinterpret_cast<const uint32_t *>(S.tab.p + off_big);
-    const FSlot *d_slots = reinterpret_cast<const FSlot *>(S.tab.p + off_slots);
-    const uint32_t *d_bslot = reinterpret_cast<const uint32_t *>(S.tab.p + off_bslot);
+    const FRange *d_ranges = reinterpret_cast<const FRange *>(S.tab.p());
+    const Settings *d_sets = reinterpret_cast<const Settings *>(S.tab.p() + off_sets);
+    const SubDesc *d_subs = reinterpret_cast<const SubDesc *>(S.tab.p() + off_subs);
+    const uint32_t *d_big = reinterpret_cast<const uint32_t *>(S.tab.p() + off_big);
+    const FSlot *d_slots = reinterpret_cast<const FSlot *>(S.tab.p() + off_slots);
+    const uint32_t *d_bslot = reinterpret_cast<const uint32_t *>(S.tab.p() + off_bslot);
     const uint32_t nbt = (uint32_t)nb_total;
-    uint32_t *blk_S = S.blk_u32.p, *blk_indep = blk_S + (nbt + 1), *blk_in = blk_indep + (nbt + 1), *blk_nrec = blk_in + (nbt + 1),
+    uint32_t *blk_S = S.blk_u32.p(), *blk_indep = blk_S + (nbt + 1), *blk_in = blk_indep + (nbt + 1), *blk_nrec = blk_in + (nbt + 1),
              *blk_pool = blk_nrec + (nbt + 1), *blk_max1 = blk_pool + (nbt + 1), *blk_max2 = blk_max1 + (nbt + 1);
     // ---- positions
     if (n_big)
-        hipLaunchKernelGGL(k_fsplit_top, dim3((uint32_t)n_big), dim3(1024), 0, st, d_ranges, d_big, d_slots, key2, S.sub_k.p, S.sub_c0.p,
-                           f->d_flags);
+        hipLaunchKernelGGL(k_fsplit_top, dim3((uint32_t)n_big), dim3(1024), 0, st, d_ranges, d_big, d_slots, key2, S.sub_k.p(), S.sub_c0.p(),
+                           f->d_flags.p());
     hipLaunchKernelGGL(k_fsplit_sub, dim3(((uint32_t)n_subs + 3) / 4), dim3(256), 0, st, d_ranges, d_subs, (uint32_t)n_subs, d_slots, key2,
-                       S.sub_k.p, S.sub_c0.p, S.leaves.p, f->d_flags, snp_only ? (uint32_t *)nullptr : blk_max1,
-                       snp_only ? 0u : 2 * (nbt + 1), S.kept.p, 4 * n_slots, (uint32_t)items[0].P.d);
+                       S.sub_k.p(), S.sub_c0.p(), S.leaves.p(), f->d_flags.p(), snp_only ? (uint32_t *)nullptr : blk_max1,
+                       snp_only ? 0u : 2 * (nbt + 1), S.kept.p(), 4 * n_slots, (uint32_t)items[0].P.d);
     c->fast->prof.lap(4);
     const uint32_t bm_words = (1u << lgB_max) / 32 + 2;
     const size_t lds = (size_t)4 * (bm_words + LEAF_LIST / 2) * sizeof(uint32_t);
@@ -579,32 +556,32 @@ static int enqueue_batch(Ctx *c, std::vector<Pending> &items, bool orbit_only) {
     const Block1 block1 = items[0].P.block1;
     const unsigned long long ti_lim = (unsigned long long)c->params.ti_lim;
     if (snp_only) {
-        hipLaunchKernelGGL(k_fleaf<false>, dim3(leaf_blocks), dim3(256), lds, st, d_ranges, S.leaves.p, (uint32_t)n_leaves, bm_words, d_slots,
+        hipLaunchKernelGGL(k_fleaf<false>, dim3(leaf_blocks), dim3(256), lds, st, d_ranges, S.leaves.p(), (uint32_t)n_leaves, bm_words, d_slots,
                            key2, d, (const Settings *)nullptr, block1, ti_lim, (uint32_t *)nullptr, (uint32_t *)nullptr, (uint32_t *)nullptr,
-                           (uint8_t *)nullptr, (uint32_t *)nullptr, f->d_flags);
+                           (uint8_t *)nullptr, (uint32_t *)nullptr, f->d_flags.p());
         MSIM_HIP(c, hipGetLastError());
         c->fast->prof.lap(5);
     } else {
-        hipLaunchKernelGGL(k_fleaf<true>, dim3(leaf_blocks), dim3(256), lds, st, d_ranges, S.leaves.p, (uint32_t)n_leaves, bm_words, d_slots,
-                           key2, d, d_sets, block1, ti_lim, S.cand_pos.p, S.cand_stop.p, S.cand_bend.p, S.cand_meta.p, blk_max1, f->d_flags);
+        hipLaunchKernelGGL(k_fleaf<true>, dim3(leaf_blocks), dim3(256), lds, st, d_ranges, S.leaves.p(), (uint32_t)n_leaves, bm_words, d_slots,
+                           key2, d, d_sets, block1, ti_lim, S.cand_pos.p(), S.cand_stop.p(), S.cand_bend.p(), S.cand_meta.p(), blk_max1, f->d_flags.p());
         c->fast->prof.lap(5);
         // One pass = k_fkeep (block-local: free candidates + short cluster walks).  Where everything in front of a block is
         // inside somebody's blocked range it raises the contig's hand-over word and that plan is replayed with the three orbit
         // kernels when the sizes are collected (fast_plan_collect): nothing of the common path pays for them.
         const Prep &P0 = items[0].P;
         auto pass = [&](bool visit, bool final, const uint32_t *end_in, uint32_t *end2, uint32_t maxspan) {
-#define MSIM_FK(V, F) hipLaunchKernelGGL((k_fkeep<V, F>), dim3(nbt), dim3(OB_THREADS), 0, st, S.cand_pos.p, end_in, \
-                                         (const uint32_t *)(visit ? blk_max2 : blk_max1), end2, blk_max2, S.cand_stop.p, \
-                                         S.cand_meta.p, 0u, blk_nrec, blk_pool, S.blk_delta.p, S.kept.p, d_slots, d_bslot)
-#define MSIM_FM(V, F) hipLaunchKernelGGL((k_forbit_mark<V, F>), dim3(nbt), dim3(OB_THREADS), 0, st, S.cand_pos.p, end_in, end2, S.cand_stop.p, \
-                                         S.cand_meta.p, (uint32_t)P0.K, blk_in, blk_nrec, blk_pool, S.blk_delta.p, S.kept.p, \
+#define MSIM_FK(V, F) hipLaunchKernelGGL((k_fkeep<V, F>), dim3(nbt), dim3(OB_THREADS), 0, st, S.cand_pos.p(), end_in, \
+                                         (const uint32_t *)(visit ? blk_max2 : blk_max1), end2, blk_max2, S.cand_stop.p(), \
+                                         S.cand_meta.p(), 0u, blk_nrec, blk_pool, S.blk_delta.p(), S.kept.p(), d_slots, d_bslot)
+#define MSIM_FM(V, F) hipLaunchKernelGGL((k_forbit_mark<V, F>), dim3(nbt), dim3(OB_THREADS), 0, st, S.cand_pos.p(), end_in, end2, S.cand_stop.p(), \
+                                         S.cand_meta.p(), (uint32_t)P0.K, blk_in, blk_nrec, blk_pool, S.blk_delta.p(), S.kept.p(), \
                                          (const uint32_t *)nullptr)
             if (!orbit_only) {
                 if (!visit && final) MSIM_FK(false, true); else if (!visit) MSIM_FK(false, false); else MSIM_FK(true, true);
             } else {                                       // (one contig: offsets are zero)
-                hipLaunchKernelGGL(k_forbit_local, dim3(nbt), dim3(OB_THREADS), 0, st, S.cand_pos.p, end_in, (uint32_t)P0.K, maxspan,
-                                   S.blk_out.p, blk_S, blk_indep, (const uint32_t *)nullptr);
-                hipLaunchKernelGGL(k_forbit_resolve, dim3(1), dim3(1024), 0, st, S.cand_pos.p, S.blk_out.p, blk_S, blk_indep, (uint32_t)P0.K,
+                hipLaunchKernelGGL(k_forbit_local, dim3(nbt), dim3(OB_THREADS), 0, st, S.cand_pos.p(), end_in, (uint32_t)P0.K, maxspan,
+                                   S.blk_out.p(), blk_S, blk_indep, (const uint32_t *)nullptr);
+                hipLaunchKernelGGL(k_forbit_resolve, dim3(1), dim3(1024), 0, st, S.cand_pos.p(), S.blk_out.p(), blk_S, blk_indep, (uint32_t)P0.K,
                                    nbt, blk_in, (const uint32_t *)nullptr);
                 if (!visit && final) MSIM_FM(false, true); else if (!visit) MSIM_FM(false, false); else MSIM_FM(true, true);
             }
@@ -616,20 +593,20 @@ static int enqueue_batch(Ctx *c, std::vector<Pending> &items, bool orbit_only) {
         uint32_t maxspan = 1, maxspan_visit = 1;
         for (auto &it : items) { maxspan = std::max(maxspan, it.P.maxspan); maxspan_visit = std::max(maxspan_visit, it.P.maxspan_visit); }
         if (!need_visit) {
-            pass(false, true, S.cand_bend.p, nullptr, maxspan);
+            pass(false, true, S.cand_bend.p(), nullptr, maxspan);
         } else {
-            pass(false, false, S.cand_bend.p, S.cand_end2.p, maxspan);
+            pass(false, false, S.cand_bend.p(), S.cand_end2.p(), maxspan);
             // ---- visit filter (mutator.py:376,386,398): the same pass over what the kept records consume
-            pass(true, true, S.cand_end2.p, nullptr, maxspan_visit);
+            pass(true, true, S.cand_end2.p(), nullptr, maxspan_visit);
         }
         if (!orbit_only || nbt <= 4096) {
-            hipLaunchKernelGGL(k_femit<true>, dim3(nbt), dim3(OB_THREADS), 0, st, S.cand_pos.p, S.cand_stop.p, S.cand_meta.p, blk_nrec, blk_pool,
-                               S.blk_delta.p, S.kept.p, f->d_flags, d_slots, d_bslot, key2);
+            hipLaunchKernelGGL(k_femit<true>, dim3(nbt), dim3(OB_THREADS), 0, st, S.cand_pos.p(), S.cand_stop.p(), S.cand_meta.p(), blk_nrec, blk_pool,
+                               S.blk_delta.p(), S.kept.p(), f->d_flags.p(), d_slots, d_bslot, key2);
         } else {
-            hipLaunchKernelGGL(k_fscan, dim3(1), dim3(1024), 0, st, blk_nrec, blk_pool, S.blk_delta.p, nbt, c->contigs[(size_t)items[0].contig].len,
-                               P0.out_cap, P0.pool_cap, S.kept.p, f->d_flags, f->d_dyn + items[0].contig);
-            hipLaunchKernelGGL(k_femit<false>, dim3(nbt), dim3(OB_THREADS), 0, st, S.cand_pos.p, S.cand_stop.p, S.cand_meta.p, blk_nrec, blk_pool,
-                               S.blk_delta.p, S.kept.p, f->d_flags, d_slots, d_bslot, key2);
+            hipLaunchKernelGGL(k_fscan, dim3(1), dim3(1024), 0, st, blk_nrec, blk_pool, S.blk_delta.p(), nbt, c->contigs[(size_t)items[0].contig].len,
+                               P0.out_cap, P0.pool_cap, S.kept.p(), f->d_flags.p(), f->d_dyn.p() + items[0].contig);
+            hipLaunchKernelGGL(k_femit<false>, dim3(nbt), dim3(OB_THREADS), 0, st, S.cand_pos.p(), S.cand_stop.p(), S.cand_meta.p(), blk_nrec, blk_pool,
+                               S.blk_delta.p(), S.kept.p(), f->d_flags.p(), d_slots, d_bslot, key2);
         }
         MSIM_HIP(c, hipGetLastError());
     }
@@ -642,7 +619,7 @@ static int enqueue_batch(Ctx *c, std::vector<Pending> &items, bool orbit_only) {
         Contig &ct = c->contigs[(size_t)it.contig];
         ct.apply_stream = st;
         if (!it.P.snp_only) {
-            ct.d_dyn = reinterpret_cast<const uint32_t *>(f->d_dyn + ct.index);
+            ct.d_dyn = reinterpret_cast<const uint32_t *>(f->d_dyn.p() + ct.index);
             ct.sizes_pending = true;
             ct.off_ready = !it.P.all_sn;
             f->sized.push_back(ct.index);

@@ -67,19 +67,10 @@ struct GpuStream {
     uint32_t waited_chunks = 0;         // the plan stream already waited for chunks below this
 };
 
-// A scratch block that owns its memory: capacity in BYTES, move-only, frees itself.  Scratch: device memory; Staging: pinned
-// host memory (host_stage_alloc below).  They are grown through Grow alone, which has one rule per kind of block.
-static void dev_free(void *p) { if (p) (void)hipFree(p); }
-static void host_stage_free(void *p);
-template <void (*Free)(void *)> struct Block {
-    void *raw = nullptr; size_t cap = 0;
-    Block() = default;
-    Block(Block &&o) noexcept : raw(o.raw), cap(o.cap) { o.raw = nullptr; o.cap = 0; }
-    ~Block() { Free(raw); }
-};
-using DevBlock = Block<dev_free>;
+// The scratch blocks own their memory (dev_block.h).  Scratch: device memory; Staging: pinned host memory (host_stage_alloc
+// below).  They are grown through Grow alone, which has one rule per kind of block.
+static hipError_t host_stage_free(void *p);
 using PinBlock = Block<host_stage_free>;
-template <class T> struct Scratch : DevBlock { T *p() const { return static_cast<T *>(raw); } };
 template <class T> struct Staging : PinBlock { T *p() const { return static_cast<T *>(raw); } };
 
 constexpr int N_SETS = 32;               // scratch sets: one per in-flight contig, so the plan stream does not have to
@@ -270,12 +261,12 @@ static void *host_stage_alloc(size_t sz, hipError_t *err) {
     if (*err != hipSuccess) { munmap(raw, total); return nullptr; }
     return q;
 }
-static void host_stage_free(void *p) {
-    if (!p) return;
+static hipError_t host_stage_free(void *p) {               // p: a block host_stage_alloc gave, never null (Block::release checks)
     (void)hipDeviceSynchronize();                          // (what hipHostFree does by itself: no copy may still use the block)
-    (void)hipHostUnregister(p);
+    const hipError_t e = hipHostUnregister(p);
     const size_t *hdr = reinterpret_cast<const size_t *>(static_cast<uint8_t *>(p) - 4096);
     munmap(reinterpret_cast<void *>((uintptr_t)hdr[0]), hdr[1]);
+    return e;
 }
 
 // How the scratch blocks grow, one rule per kind; none keeps a block's contents.  One Grow per contig being planned.
@@ -291,8 +282,7 @@ struct Grow {
             MSIM_HIP(c, wait_stream(c->emit_stream));
             grew = true;
         }
-        if (b.raw) MSIM_HIP(c, hipFree(b.raw));
-        b.raw = nullptr; b.cap = 0;
+        MSIM_HIP(c, b.release());
         const size_t sz = want_bytes + want_bytes / 4 + 4096;
         MSIM_HIP(c, hipMalloc(&b.raw, sz));
         b.cap = sz;
@@ -302,8 +292,7 @@ struct Grow {
     // (also how shared() replaces a block, behind its wait)
     int own(PinBlock &b, size_t want_bytes) {
         if (b.cap >= want_bytes) return MSIM_OK;
-        host_stage_free(b.raw);
-        b.raw = nullptr; b.cap = 0;
+        (void)b.release();
         const size_t sz = (want_bytes + want_bytes / 4 + STAGE_HUGE) & ~(STAGE_HUGE - 1);
         hipError_t e;
         void *q = host_stage_alloc(sz, &e);
@@ -1144,7 +1133,7 @@ static int enqueue_snp_stage(Ctx *c, GpuPlan *g, Contig &ct, uint64_t K, const u
         MSIM_HIP(c, hipEventRecord(ce, c->stream));
         MSIM_HIP(c, hipStreamWaitEvent(c->emit_stream, ce, 0));
         hipLaunchKernelGGL(k_snp_emit_abs, dim3(nb2), dim3(SNP_THREADS), 0, c->emit_stream, py.d_lanes, T.base, W2,
-                           T.maps.p(), nb2, ct.d_recs, (uint32_t)K, sn_index, aux8_out ? T.aux8.p() : (uint8_t *)nullptr);
+                           T.maps.p(), nb2, ct.d_recs.p(), (uint32_t)K, sn_index, aux8_out ? T.aux8.p() : (uint8_t *)nullptr);
         MSIM_HIP(c, hipGetLastError());
         if (!aux8_out) {                                  // (else: the caller records it behind the expansion that reads aux8)
             MSIM_HIP(c, hipEventRecord(T.emit_done, c->emit_stream));
@@ -1386,12 +1375,12 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
     Grow grow{c};
     if (!c->chain_only) {   // the record table may still be read by an earlier apply of this contig
         const size_t want = std::max<uint64_t>(K, 1) * sizeof(msim_record);
-        if (ct.cap_recs < want || ct.cap_pool < 2 * PAD) {
+        if (ct.d_recs.cap < want || ct.d_pool.cap < 2 * PAD) {
             MSIM_HIP(c, wait_stream(c->stream));
             MSIM_HIP(c, wait_stream(c->emit_stream));
         }
-        if ((rc = dev_reserve(c, (void **)&ct.d_recs, &ct.cap_recs, want))) return rc;
-        if ((rc = dev_reserve(c, (void **)&ct.d_pool, &ct.cap_pool, 2 * PAD))) return rc;
+        if ((rc = dev_reserve(c, ct.d_recs, want))) return rc;
+        if ((rc = dev_reserve(c, ct.d_pool, 2 * PAD))) return rc;
     }
     ct.n_rec = K;
     ct.pool_len = 0;
@@ -1489,7 +1478,7 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
             } else {
                 hipLaunchKernelGGL(k_bitmap_expand, dim3(bnb), dim3(BM_THREADS), 0, c->emit_stream,
                                    reinterpret_cast<const uint64_t *>(S.bitmap.p()), bmw, S.cnt2.p(), (uint32_t)r.start, (uint32_t)d,
-                                   ct.d_recs + rec_base, (const uint8_t *)nullptr);
+                                   ct.d_recs.p() + rec_base, (const uint8_t *)nullptr);
                 MSIM_HIP(c, hipGetLastError());
                 MSIM_HIP(c, hipEventRecord(S.emit_done, c->emit_stream));
                 S.wait_ev = S.emit_done;
@@ -1515,14 +1504,14 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
         if (grouped) {
             g->emit_d = (uint32_t)d;
             g->emit_items.push_back(EmitItem{ct.index, late.S, df.T, late.bmw, late.bnb, late.start, (uint32_t)K, df.W2, df.nb2,
-                                             ct.d_recs, false});
+                                             ct.d_recs.p(), false});
             if (g->emit_items.size() >= (size_t)EMIT_G && (rc = gpu_emit_flush(c))) return rc;   // (the launch's job table is full)
         } else if (late.S) {
             SampleSet &S = *late.S;
             SnpSet &T = g->snp[(g->snp_unit - 1) % N_SETS];        // (the set enqueue_snp_stage just took)
             hipLaunchKernelGGL(k_bitmap_expand, dim3(late.bnb), dim3(BM_THREADS), 0, c->emit_stream,
                                reinterpret_cast<const uint64_t *>(S.bitmap.p()), late.bmw, S.cnt2.p(), late.start, (uint32_t)d,
-                               ct.d_recs, (const uint8_t *)aux8);
+                               ct.d_recs.p(), (const uint8_t *)aux8);
             MSIM_HIP(c, hipGetLastError());
             MSIM_HIP(c, hipEventRecord(S.emit_done, c->emit_stream));
             S.wait_ev = S.emit_done;
@@ -1880,13 +1869,13 @@ static int mixed_emit(Ctx *c, GpuPlan *g, Contig &ct, MixedSet &M, uint32_t k, u
     // ---- 4. records, insert pool, SNP draws
     if (!c->chain_only) {   // the record table / pool may still be read by an earlier apply of this contig
         const size_t want = std::max<uint64_t>(n_rec, 1) * sizeof(msim_record);
-        if (ct.cap_recs < want || ct.cap_pool < pool_len + 2 * PAD) {
+        if (ct.d_recs.cap < want || ct.d_pool.cap < pool_len + 2 * PAD) {
             MSIM_HIP(c, wait_stream(c->stream));
             MSIM_HIP(c, wait_stream(c->emit_stream));
         }
-        if ((rc = dev_reserve(c, (void **)&ct.d_recs, &ct.cap_recs, want))) return rc;
-        if ((rc = dev_reserve(c, (void **)&ct.d_pool, &ct.cap_pool, pool_len + 2 * PAD))) return rc;
-        if ((rc = dev_reserve(c, (void **)&ct.d_off, &ct.cap_off, std::max<uint64_t>(n_rec, 1) * sizeof(uint32_t)))) return rc;
+        if ((rc = dev_reserve(c, ct.d_recs, want))) return rc;
+        if ((rc = dev_reserve(c, ct.d_pool, pool_len + 2 * PAD))) return rc;
+        if ((rc = dev_reserve(c, ct.d_off, std::max<uint64_t>(n_rec, 1) * sizeof(uint32_t)))) return rc;
     }
     ct.n_rec = n_rec;
     ct.pool_len = pool_len;
@@ -1901,7 +1890,7 @@ static int mixed_emit(Ctx *c, GpuPlan *g, Contig &ct, MixedSet &M, uint32_t k, u
     MSIM_HIP(c, hipEventRecord(ce, c->stream));
     MSIM_HIP(c, hipStreamWaitEvent(c->emit_stream, ce, 0));
     if (!c->chain_only) {
-        emit_records_launch(c->emit_stream, mt, ct.d_recs, ct.d_off, np.d_raw, (unsigned long long)np.pos, pool_len, ct.d_pool + PAD);
+        emit_records_launch(c->emit_stream, mt, ct.d_recs.p(), ct.d_off.p(), np.d_raw, (unsigned long long)np.pos, pool_len, ct.d_pool.p() + PAD);
         MSIM_HIP(c, hipGetLastError());
     }
     np.pos += pool_len;
@@ -2261,12 +2250,12 @@ int plan_contig_gpu_hostsample(Ctx *c, GpuPlan *g, Contig &ct, const msim_range 
     if ((rc = grow(M.wcnt, (size_t)(bnb + 2) * sizeof(uint32_t)))) return rc;
     if (!c->chain_only) {   // the record table may still be read by an earlier apply of this contig
         const size_t want = (size_t)K * sizeof(msim_record);
-        if (ct.cap_recs < want || ct.cap_pool < 2 * PAD) {
+        if (ct.d_recs.cap < want || ct.d_pool.cap < 2 * PAD) {
             MSIM_HIP(c, wait_stream(c->stream));
             MSIM_HIP(c, wait_stream(c->emit_stream));
         }
-        if ((rc = dev_reserve(c, (void **)&ct.d_recs, &ct.cap_recs, want))) return rc;
-        if ((rc = dev_reserve(c, (void **)&ct.d_pool, &ct.cap_pool, 2 * PAD))) return rc;
+        if ((rc = dev_reserve(c, ct.d_recs, want))) return rc;
+        if ((rc = dev_reserve(c, ct.d_pool, 2 * PAD))) return rc;
     }
     {
         uint32_t at = 0, base = 0;
@@ -2328,7 +2317,7 @@ int plan_contig_gpu_hostsample(Ctx *c, GpuPlan *g, Contig &ct, const msim_range 
                            reinterpret_cast<const uint64_t *>(M.wbits.p()), bmw, M.wcnt.p());
         hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->emit_stream, M.wcnt.p(), bnb);
         hipLaunchKernelGGL(k_walk_expand, dim3(bnb), dim3(BM_THREADS), 0, c->emit_stream,
-                           reinterpret_cast<uint64_t *>(M.wbits.p()), bmw, M.wcnt.p(), M.walk_d.p(), n_draw, (uint32_t)d, ct.d_recs);
+                           reinterpret_cast<uint64_t *>(M.wbits.p()), bmw, M.wcnt.p(), M.walk_d.p(), n_draw, (uint32_t)d, ct.d_recs.p());
         MSIM_HIP(c, hipGetLastError());
     }
     ct.n_rec = K;

@@ -30,14 +30,13 @@ using fastrng::Key;
 using fastrng::U4;
 
 struct SpectrumState {
-    unsigned long long *d_counts = nullptr;   // 64 census bins
-    unsigned long long *d_sbs = nullptr;      // HIST_SLOTS x 104 profile bins (spectrum::SBS_BINS)
-    unsigned long long *h_sbs = nullptr;      // pinned copy of them
-    uint64_t *d_thr = nullptr;                // 192 thresholds
-    uint32_t *d_words = nullptr;              // one outcome word per lane of every tile
-    uint32_t *d_tile = nullptr;               // hits per tile, then their exclusive scan; [n_tiles]: the total
-    size_t cap_words = 0, cap_tile = 0;
-    unsigned long long *h_pin = nullptr;      // pinned: [0..63] census bins / [0..191] thresholds on their way up, [192] the total
+    Scratch<unsigned long long> d_counts;     // 64 census bins
+    Scratch<unsigned long long> d_sbs;        // HIST_SLOTS x 104 profile bins (spectrum::SBS_BINS)
+    Pinned<unsigned long long> h_sbs;         // pinned copy of them
+    Scratch<uint64_t> d_thr;                  // 192 thresholds
+    Scratch<uint32_t> d_words;                // one outcome word per lane of every tile (dev_reserve)
+    Scratch<uint32_t> d_tile;                 // hits per tile, then their exclusive scan; [n_tiles]: the total (dev_reserve)
+    Pinned<unsigned long long> h_pin;         // pinned: [0..63] census bins / [0..191] thresholds on their way up, [192] the total
     EventPair tm;
     double census_ms = 0, plan_ms = 0, sbs_ms = 0;
 };
@@ -246,11 +245,11 @@ int state_of(Ctx *c, SpectrumState **out) {
     if (!c->spectrum) {
         SpectrumState *S = new SpectrumState;
         c->spectrum = S;
-        MSIM_HIP(c, hipMalloc((void **)&S->d_counts, 64 * sizeof(unsigned long long)));
-        MSIM_HIP(c, hipMalloc((void **)&S->d_sbs, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long)));
-        MSIM_HIP(c, hipHostMalloc((void **)&S->h_sbs, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long), hipHostMallocDefault));
-        MSIM_HIP(c, hipMalloc((void **)&S->d_thr, 192 * sizeof(uint64_t)));
-        MSIM_HIP(c, hipHostMalloc((void **)&S->h_pin, 193 * sizeof(unsigned long long), hipHostMallocDefault));
+        MSIM_HIP(c, dev_alloc(S->d_counts, 64 * sizeof(unsigned long long)));
+        MSIM_HIP(c, dev_alloc(S->d_sbs, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long)));
+        MSIM_HIP(c, pin_alloc(S->h_sbs, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long)));
+        MSIM_HIP(c, dev_alloc(S->d_thr, 192 * sizeof(uint64_t)));
+        MSIM_HIP(c, pin_alloc(S->h_pin, 193 * sizeof(unsigned long long)));
         MSIM_HIP(c, S->tm.create());
     }
     *out = c->spectrum;
@@ -267,15 +266,15 @@ int stretch_end(Ctx *c, SpectrumState *S, double *acc) {
 int census_device(Ctx *c, SpectrumState *S, const Contig &g, uint64_t counts[64]) {
     const uint64_t n_tiles = tiles_of(g.len);
     if (!n_tiles) { memset(counts, 0, 64 * sizeof(uint64_t)); return MSIM_OK; }
-    MSIM_HIP(c, hipMemsetAsync(S->d_counts, 0, 64 * sizeof(unsigned long long), c->stream));
+    MSIM_HIP(c, hipMemsetAsync(S->d_counts.p(), 0, 64 * sizeof(unsigned long long), c->stream));
     MSIM_HIP(c, S->tm.begin(c->stream));
     const unsigned blocks = (unsigned)std::min<uint64_t>(n_tiles, CENSUS_MAX_BLOCKS);
-    hipLaunchKernelGGL(k_ctx_census, dim3(blocks), dim3(LANES), 0, c->stream, g.d_in + PAD, g.len, n_tiles, S->d_counts);
+    hipLaunchKernelGGL(k_ctx_census, dim3(blocks), dim3(LANES), 0, c->stream, g.d_in.p() + PAD, g.len, n_tiles, S->d_counts.p());
     MSIM_HIP(c, hipGetLastError());
     MSIM_HIP(c, S->tm.end(c->stream));                      // (in front of the copy: the kernel alone)
-    MSIM_HIP(c, hipMemcpyAsync(S->h_pin, S->d_counts, 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    MSIM_HIP(c, hipMemcpyAsync(S->h_pin.p(), S->d_counts.p(), 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
-    for (int i = 0; i < 64; i++) counts[i] = S->h_pin[i];
+    for (int i = 0; i < 64; i++) counts[i] = S->h_pin.p()[i];
     return S->tm.add_elapsed(c, &S->census_ms);
 }
 
@@ -285,16 +284,16 @@ int sbs_device(Ctx *c, SpectrumState *S, const Contig &g, uint64_t channels[96],
     memset(tallies, 0, 8 * sizeof(uint64_t));
     if (!g.n_rec) return MSIM_OK;
     const uint64_t n_pass = (g.n_rec + SBS_PASS - 1) / SBS_PASS;
-    MSIM_HIP(c, hipMemsetAsync(S->d_sbs, 0, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long), c->stream));
+    MSIM_HIP(c, hipMemsetAsync(S->d_sbs.p(), 0, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long), c->stream));
     MSIM_HIP(c, S->tm.begin(c->stream));
     const unsigned blocks = (unsigned)std::min<uint64_t>(n_pass, SBS_MAX_BLOCKS);
-    hipLaunchKernelGGL(k_sbs_count, dim3(blocks), dim3(LANES), 0, c->stream, g.d_in + PAD, g.len,
-                       reinterpret_cast<const uint4 *>(g.d_recs), g.n_rec, n_pass, S->d_sbs);
+    hipLaunchKernelGGL(k_sbs_count, dim3(blocks), dim3(LANES), 0, c->stream, g.d_in.p() + PAD, g.len,
+                       reinterpret_cast<const uint4 *>(g.d_recs.p()), g.n_rec, n_pass, S->d_sbs.p());
     MSIM_HIP(c, hipGetLastError());
     MSIM_HIP(c, S->tm.end(c->stream));                      // (in front of the copy: the kernel alone)
-    MSIM_HIP(c, hipMemcpyAsync(S->h_sbs, S->d_sbs, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    MSIM_HIP(c, hipMemcpyAsync(S->h_sbs.p(), S->d_sbs.p(), HIST_SLOTS * SBS_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
-    sbs_finish(S->h_sbs, channels, tallies);
+    sbs_finish(S->h_sbs.p(), channels, tallies);
     return S->tm.add_elapsed(c, &S->sbs_ms);
 }
 
@@ -308,31 +307,31 @@ int plan_device(Ctx *c, SpectrumState *S, Contig *g, const uint64_t thr[192], ui
     const uint64_t n_tiles = tiles_of(g->len);
     uint64_t n_rec = 0;
     if (n_tiles) {
-        rc = dev_reserve(c, (void **)&S->d_words, &S->cap_words, (size_t)n_tiles * LANES * sizeof(uint32_t));
-        if (!rc) rc = dev_reserve(c, (void **)&S->d_tile, &S->cap_tile, (size_t)(n_tiles + 1) * sizeof(uint32_t));
+        rc = dev_reserve(c, S->d_words, (size_t)n_tiles * LANES * sizeof(uint32_t));
+        if (!rc) rc = dev_reserve(c, S->d_tile, (size_t)(n_tiles + 1) * sizeof(uint32_t));
         if (rc) return rc;
-        memcpy(S->h_pin, thr, 192 * sizeof(uint64_t));
-        MSIM_HIP(c, hipMemcpyAsync(S->d_thr, S->h_pin, 192 * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        memcpy(S->h_pin.p(), thr, 192 * sizeof(uint64_t));
+        MSIM_HIP(c, hipMemcpyAsync(S->d_thr.p(), S->h_pin.p(), 192 * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
         const Key key{(uint32_t)key64, (uint32_t)(key64 >> 32), seq};
         MSIM_HIP(c, S->tm.begin(c->stream));
-        hipLaunchKernelGGL(k_spectrum_draw, dim3((unsigned)n_tiles), dim3(LANES), 0, c->stream, g->d_in + PAD, g->len, S->d_thr, key,
-                           S->d_words, S->d_tile);
-        hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, S->d_tile, (uint32_t)n_tiles);
+        hipLaunchKernelGGL(k_spectrum_draw, dim3((unsigned)n_tiles), dim3(LANES), 0, c->stream, g->d_in.p() + PAD, g->len, S->d_thr.p(), key,
+                           S->d_words.p(), S->d_tile.p());
+        hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, S->d_tile.p(), (uint32_t)n_tiles);
         MSIM_HIP(c, hipGetLastError());
-        MSIM_HIP(c, hipMemcpyAsync(S->h_pin + 192, S->d_tile + n_tiles, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+        MSIM_HIP(c, hipMemcpyAsync(S->h_pin.p() + 192, S->d_tile.p() + n_tiles, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
         if ((rc = stretch_end(c, S, &S->plan_ms))) return rc;
-        n_rec = *reinterpret_cast<const uint32_t *>(S->h_pin + 192);
+        n_rec = *reinterpret_cast<const uint32_t *>(S->h_pin.p() + 192);
         if (n_rec >= (1ull << 31)) return fail(c, MSIM_ERR_UNSUPPORTED, "2^31 or more mutations on one contig");
     }
     if (n_rec) {
-        rc = dev_reserve(c, (void **)&g->d_recs, &g->cap_recs, (size_t)n_rec * sizeof(msim_record));
+        rc = dev_reserve(c, g->d_recs, (size_t)n_rec * sizeof(msim_record));
         if (rc) return rc;
         MSIM_HIP(c, S->tm.begin(c->stream));
-        hipLaunchKernelGGL(k_spectrum_emit, dim3((unsigned)n_tiles), dim3(LANES), 0, c->stream, S->d_words, S->d_tile, g->d_recs);
+        hipLaunchKernelGGL(k_spectrum_emit, dim3((unsigned)n_tiles), dim3(LANES), 0, c->stream, S->d_words.p(), S->d_tile.p(), g->d_recs.p());
         MSIM_HIP(c, hipGetLastError());
         if ((rc = stretch_end(c, S, &S->plan_ms))) return rc;
     }
-    rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, 2 * PAD);
+    rc = dev_reserve(c, g->d_pool, 2 * PAD);
     if (rc) return rc;
     g->n_rec = n_rec;
     g->pool_len = 0;
@@ -353,10 +352,6 @@ bool thresholds_ordered(const uint64_t thr[192], int *bad_ctx) {
 void spectrum_state_destroy(Ctx *c) {
     SpectrumState *S = c->spectrum;
     if (!S) return;
-    void *bufs[] = {S->d_counts, S->d_sbs, S->d_thr, S->d_words, S->d_tile};
-    for (void *p : bufs) if (p) (void)hipFree(p);
-    if (S->h_pin) (void)hipHostFree(S->h_pin);
-    if (S->h_sbs) (void)hipHostFree(S->h_sbs);
     S->tm.destroy();
     delete S;
     c->spectrum = nullptr;
@@ -442,7 +437,7 @@ int msim_dbg_sbs_copy_floor(msim_ctx *p, int contig, double *ms) {
     if (rc) return rc;
     SpectrumState *S;
     if ((rc = state_of(c, &S))) return rc;
-    const CopySource table{g->d_recs, (size_t)g->n_rec * sizeof(msim_record)};
+    const CopySource table{g->d_recs.p(), (size_t)g->n_rec * sizeof(msim_record)};
     return copy_floor(c, S->tm, &table, 1, ms);
 }
 

@@ -1054,13 +1054,13 @@ __global__ __launch_bounds__(TX_THREADS) void k_gather(const uint8_t *__restrict
 }  // namespace
 
 // VCF text of one contig into the context's text buffer; returns its size.
-int vcf_render_device(Ctx *c, Contig &g, const char *seq_name, uint64_t *bytes, uint8_t **buf, size_t *cap) {
+int vcf_render_device(Ctx *c, Contig &g, const char *seq_name, uint64_t *bytes, DevBlock *into) {
     // (diploid runs: the text is the FULL table's whichever haplotype is selected, its sample column the records' genotypes)
     const TableView tv = vcf_table(g);
     const uint32_t n = (uint32_t)tv.n_rec;
     *bytes = 0;
-    const bool own = buf == nullptr;
-    if (own) { buf = &c->d_text; cap = &c->cap_text; }
+    const bool own = into == nullptr;
+    if (own) into = &c->d_text;
     if (!n) { if (own) c->text_len = 0; return MSIM_OK; }
     hipStream_t st = c->stream;
     const size_t name_len = strlen(seq_name);
@@ -1070,17 +1070,17 @@ int vcf_render_device(Ctx *c, Contig &g, const char *seq_name, uint64_t *bytes, 
     const size_t o_sums = o_len + (((size_t)n * 4 + 255) & ~(size_t)255);
     const size_t o_off = o_sums + (((size_t)(nb + 1) * 8 + 255) & ~(size_t)255);
     const size_t o_ra = o_off + (((size_t)n * 8 + 255) & ~(size_t)255);
-    int rc = dev_reserve(c, (void **)&c->d_text_scratch, &c->cap_text_scratch, o_ra + (size_t)n * 2);
+    int rc = dev_reserve(c, c->d_text_scratch, o_ra + (size_t)n * 2);
     if (rc) return rc;
-    uint8_t *base = c->d_text_scratch;
+    uint8_t *base = c->d_text_scratch.p();
     uint8_t *d_name = base;
     uint32_t *d_len = reinterpret_cast<uint32_t *>(base + o_len);
     unsigned long long *d_sums = reinterpret_cast<unsigned long long *>(base + o_sums);
     unsigned long long *d_off = reinterpret_cast<unsigned long long *>(base + o_off);
     uint16_t *d_ra = reinterpret_cast<uint16_t *>(base + o_ra);
     MSIM_HIP(c, hipMemcpyAsync(d_name, seq_name, name_len, hipMemcpyHostToDevice, st));
-    const uint8_t *in = g.d_in + PAD;
-    const uint8_t *pool = g.d_pool ? g.d_pool + PAD : nullptr;
+    const uint8_t *in = g.d_in.p() + PAD;
+    const uint8_t *pool = g.d_pool.p() ? g.d_pool.p() + PAD : nullptr;
     const dim3 grid((n + 64 * TX_WAVES - 1) / (64 * TX_WAVES));           // a wave takes 64 consecutive records
 #define MSIM_VCF_LINES(W, ...) do { if (tv.d_gt) { if (tv.all_snp) hipLaunchKernelGGL((k_vcf_lines<W, true, true>), __VA_ARGS__); \
                                                    else hipLaunchKernelGGL((k_vcf_lines<W, false, true>), __VA_ARGS__); } \
@@ -1089,16 +1089,16 @@ int vcf_render_device(Ctx *c, Contig &g, const char *seq_name, uint64_t *bytes, 
     MSIM_VCF_LINES(false, grid, dim3(TX_THREADS), 0, st, tv.d_recs, n, pool, in, (unsigned long long)g.len,
                    d_name, (uint32_t)name_len, ctx_lut(c), d_len, d_ra, (const unsigned long long *)nullptr, (char *)nullptr, 0u, tv.d_gt);
     hipLaunchKernelGGL(k_len_reduce, dim3(nb), dim3(TX_THREADS), 0, st, d_len, n, d_sums);
-    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, d_sums, nb, c->h_mail);
+    hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, d_sums, nb, c->h_mail.p());
     hipLaunchKernelGGL(k_len_offsets, dim3(nb), dim3(TX_THREADS), 0, st, d_len, n, d_sums, d_off);
     MSIM_HIP(c, hipGetLastError());
     MSIM_HIP(c, wait_stream(st));
-    const uint64_t total = *c->h_mail;
-    rc = dev_reserve(c, (void **)buf, cap, total + 64);
+    const uint64_t total = *c->h_mail.p();
+    rc = dev_reserve(c, *into, total + 64);
     if (rc) return rc;
     if (total) {
         MSIM_VCF_LINES(true, grid, dim3(TX_THREADS), 0, st, tv.d_recs, n, pool, in, (unsigned long long)g.len,
-                       d_name, (uint32_t)name_len, ctx_lut(c), d_len, d_ra, d_off, reinterpret_cast<char *>(*buf),
+                       d_name, (uint32_t)name_len, ctx_lut(c), d_len, d_ra, d_off, static_cast<char *>(into->raw),
                        (getenv("MSIM_DBG_VCF_PLAIN") || name_len > VCF_MAX_NAME) ? 1u : 0u, tv.d_gt);      // (the plain path: test hook, huge names)
 #undef MSIM_VCF_LINES
         // waves the stage scheme cannot describe (vcf_wave_is_plain): only a text of 4 GiB and more can hold one
@@ -1107,10 +1107,10 @@ int vcf_render_device(Ctx *c, Contig &g, const char *seq_name, uint64_t *bytes, 
         if (!tv.all_snp && (plain || far || total >= (1ull << 32) - 16)) {
             if (tv.d_gt)
                 hipLaunchKernelGGL(k_vcf_plain<true>, grid, dim3(TX_THREADS), 0, st, tv.d_recs, n, pool, in, (unsigned long long)g.len, d_name,
-                                   (uint32_t)name_len, ctx_lut(c), d_len, d_ra, d_off, reinterpret_cast<char *>(*buf), plain, tv.d_gt);
+                                   (uint32_t)name_len, ctx_lut(c), d_len, d_ra, d_off, static_cast<char *>(into->raw), plain, tv.d_gt);
             else
                 hipLaunchKernelGGL(k_vcf_plain<false>, grid, dim3(TX_THREADS), 0, st, tv.d_recs, n, pool, in, (unsigned long long)g.len, d_name,
-                                   (uint32_t)name_len, ctx_lut(c), d_len, d_ra, d_off, reinterpret_cast<char *>(*buf), plain, (const uint8_t *)nullptr);
+                                   (uint32_t)name_len, ctx_lut(c), d_len, d_ra, d_off, static_cast<char *>(into->raw), plain, (const uint8_t *)nullptr);
         }
         MSIM_HIP(c, hipGetLastError());
     }
@@ -1157,16 +1157,16 @@ int chain_render_device(Ctx *c, Contig &g, const char *t_name, const char *q_nam
     uint64_t m = 0;
     const uint32_t nb = (n + CH_TILE - 1) / CH_TILE;
     if (n && !g.all_snp) {
-        int rc = dev_reserve(c, (void **)&c->d_text, &c->cap_text, ((size_t)nb + 1) * 8 + 64);
+        int rc = dev_reserve(c, c->d_text, ((size_t)nb + 1) * 8 + 64);
         if (rc) return rc;
-        unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->d_text);
+        unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(c->d_text.p());
         MSIM_HIP(c, mark());
-        hipLaunchKernelGGL(k_chain_count, dim3(nb), dim3(TX_THREADS), 0, st, g.d_recs, n, d_cnt);
-        hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, d_cnt, nb, c->h_mail);
+        hipLaunchKernelGGL(k_chain_count, dim3(nb), dim3(TX_THREADS), 0, st, g.d_recs.p(), n, d_cnt);
+        hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, d_cnt, nb, c->h_mail.p());
         MSIM_HIP(c, hipGetLastError());
         MSIM_HIP(c, mark());
         MSIM_HIP(c, wait_stream(st));
-        m = *c->h_mail;
+        m = *c->h_mail.p();
     }
     uint64_t sum_dt = 0, sum_dq = 0, t_start = 0, q_start = 0, t_trail = 0, q_trail = 0, last_size = L, n_lines = 0, body = 0;
     uint32_t *d_hsize = nullptr;
@@ -1180,9 +1180,9 @@ int chain_render_device(Ctx *c, Contig &g, const char *t_name, const char *q_nam
         const size_t o_hpdt = o_hsize + up(((size_t)mm + 1) * 4), o_hpdq = o_hpdt + up(((size_t)mm + 1) * 8);
         const size_t o_tot = o_hpdq + up(((size_t)mm + 1) * 8), o_len = o_tot + 256, o_lsums = o_len + up((size_t)mm * 4);
         const size_t o_off = o_lsums + up(((size_t)nbl + 1) * 8), end = o_off + up((size_t)mm * 8);
-        int rc = dev_reserve(c, (void **)&c->d_text_scratch, &c->cap_text_scratch, end);
+        int rc = dev_reserve(c, c->d_text_scratch, end);
         if (rc) return rc;
-        uint8_t *base = c->d_text_scratch;
+        uint8_t *base = c->d_text_scratch.p();
         uint4 *d_gaps = reinterpret_cast<uint4 *>(base);
         unsigned long long *d_tiles = reinterpret_cast<unsigned long long *>(base + o_tiles);
         d_hsize = reinterpret_cast<uint32_t *>(base + o_hsize);
@@ -1193,11 +1193,11 @@ int chain_render_device(Ctx *c, Contig &g, const char *t_name, const char *q_nam
         unsigned long long *d_lsums = reinterpret_cast<unsigned long long *>(base + o_lsums);
         d_off = reinterpret_cast<unsigned long long *>(base + o_off);
         MSIM_HIP(c, mark());
-        hipLaunchKernelGGL(k_chain_compact, dim3(nb), dim3(TX_THREADS), 0, st, g.d_recs, n,
-                           reinterpret_cast<const unsigned long long *>(c->d_text), d_gaps);
+        hipLaunchKernelGGL(k_chain_compact, dim3(nb), dim3(TX_THREADS), 0, st, g.d_recs.p(), n,
+                           reinterpret_cast<const unsigned long long *>(c->d_text.p()), d_gaps);
         hipLaunchKernelGGL(k_chain_tiles, dim3(nb2), dim3(TX_THREADS), 0, st, d_gaps, mm, stride, d_tiles);
         for (int q = 0; q < 3; q++)
-            hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, d_tiles + (size_t)q * stride, nb2, c->h_mail);
+            hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, d_tiles + (size_t)q * stride, nb2, c->h_mail.p());
         hipLaunchKernelGGL(k_chain_heads, dim3(nb2), dim3(TX_THREADS), 0, st, d_gaps, mm, stride, d_tiles, d_hsize, d_hp_dt, d_hp_dq,
                            d_tot);
         MSIM_HIP(c, hipGetLastError());
@@ -1228,13 +1228,13 @@ int chain_render_device(Ctx *c, Contig &g, const char *t_name, const char *q_nam
                 hipLaunchKernelGGL((k_chain_lines<false>), dim3((nl + TX_THREADS - 1) / TX_THREADS), dim3(TX_THREADS), 0, st, d_hsize,
                                    d_hp_dt, d_hp_dq, nl, d_len, (const unsigned long long *)nullptr, (char *)nullptr);
                 hipLaunchKernelGGL(k_len_reduce, dim3(nbk), dim3(TX_THREADS), 0, st, d_len, nl, d_lsums);
-                hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, d_lsums, nbk, c->h_mail);
+                hipLaunchKernelGGL(k_scan_u64, dim3(1), dim3(1024), 0, st, d_lsums, nbk, c->h_mail.p());
                 hipLaunchKernelGGL(k_len_offsets, dim3(nbk), dim3(TX_THREADS), 0, st, d_len, nl, d_lsums, d_off);
                 MSIM_HIP(c, hipGetLastError());
                 MSIM_HIP(c, mark());
             }
             MSIM_HIP(c, wait_stream(st));
-            if (n_lines) body = *c->h_mail;
+            if (n_lines) body = *c->h_mail.p();
             t_start = lead[0]; q_start = lead[1];
             if (final_block) last_size = final_block;
             else { last_size = tail_size; t_trail = sum_dt - trail[0]; q_trail = sum_dq - trail[1]; }
@@ -1252,18 +1252,18 @@ int chain_render_device(Ctx *c, Contig &g, const char *t_name, const char *q_nam
     chain_header(&edge[0], &at, L, sum_dt, sum_dq, t_start, q_start, t_trail, q_trail, t_name, q_name, id);
     edge += std::to_string(last_size) + "\n\n";
     const uint64_t total = edge.size() + body;
-    int rc = dev_reserve(c, (void **)&c->d_text, &c->cap_text, total + 64);
+    int rc = dev_reserve(c, c->d_text, total + 64);
     if (rc) return rc;
-    MSIM_HIP(c, hipMemcpyAsync(c->d_text, edge.data(), hdr, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemcpyAsync(c->d_text.p(), edge.data(), hdr, hipMemcpyHostToDevice, st));
     if (n_lines) {
         const uint32_t nl = (uint32_t)n_lines;
         MSIM_HIP(c, mark());
         hipLaunchKernelGGL((k_chain_lines<true>), dim3((nl + TX_THREADS - 1) / TX_THREADS), dim3(TX_THREADS), 0, st, d_hsize, d_hp_dt,
-                           d_hp_dq, nl, (uint32_t *)nullptr, d_off, reinterpret_cast<char *>(c->d_text) + hdr);
+                           d_hp_dq, nl, (uint32_t *)nullptr, d_off, reinterpret_cast<char *>(c->d_text.p()) + hdr);
         MSIM_HIP(c, hipGetLastError());
         MSIM_HIP(c, mark());
     }
-    MSIM_HIP(c, hipMemcpyAsync(c->d_text + hdr + body, edge.data() + hdr, edge.size() - hdr, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemcpyAsync(c->d_text.p() + hdr + body, edge.data() + hdr, edge.size() - hdr, hipMemcpyHostToDevice, st));
     MSIM_HIP(c, wait_stream(st));                                        // (`edge` is read until here)
     MSIM_HIP(c, sum_events());
     c->text_len = total;
@@ -1271,17 +1271,17 @@ int chain_render_device(Ctx *c, Contig &g, const char *t_name, const char *q_nam
 }
 
 // Mutated stream of one contig as FASTA body text into the context's text buffer.
-int fasta_frame_device(Ctx *c, Contig &g, uint32_t bpl, uint64_t *bytes, uint8_t **buf, size_t *cap) {
+int fasta_frame_device(Ctx *c, Contig &g, uint32_t bpl, uint64_t *bytes, DevBlock *into) {
     const uint64_t L = g.out_len;
     const uint64_t total = L + L / bpl;
     *bytes = total;
-    if (!buf) { buf = &c->d_text; cap = &c->cap_text; c->text_len = total; }
+    if (!into) { into = &c->d_text; c->text_len = total; }
     if (!total) return MSIM_OK;
-    int rc = dev_reserve(c, (void **)buf, cap, total + 64);
+    int rc = dev_reserve(c, *into, total + 64);
     if (rc) return rc;
     const uint64_t groups = (total + 15) / 16;
     hipLaunchKernelGGL(k_frame, dim3((uint32_t)((groups + TX_THREADS - 1) / TX_THREADS)), dim3(TX_THREADS), 0, c->stream,
-                       g.d_out, (unsigned long long)L, bpl, (unsigned long long)total, *buf);
+                       g.d_out.p(), (unsigned long long)L, bpl, (unsigned long long)total, static_cast<uint8_t *>(into->raw));
     MSIM_HIP(c, hipGetLastError());
     return MSIM_OK;
 }
@@ -1290,12 +1290,12 @@ int fasta_frame_device(Ctx *c, Contig &g, uint32_t bpl, uint64_t *bytes, uint8_t
 int fasta_gather_device(Ctx *c, const uint8_t *body, uint64_t body_bytes, uint64_t n_bases, uint32_t lenc,
                         uint32_t lenb, uint8_t *d_dst) {
     if (!n_bases) return MSIM_OK;
-    int rc = dev_reserve(c, (void **)&c->d_text, &c->cap_text, body_bytes + 64);
+    int rc = dev_reserve(c, c->d_text, body_bytes + 64);
     if (rc) return rc;
-    MSIM_HIP(c, hipMemcpyAsync(c->d_text, body, body_bytes, hipMemcpyHostToDevice, c->stream));
+    MSIM_HIP(c, hipMemcpyAsync(c->d_text.p(), body, body_bytes, hipMemcpyHostToDevice, c->stream));
     const uint64_t groups = (n_bases + 15) / 16;
     hipLaunchKernelGGL(k_gather, dim3((uint32_t)((groups + TX_THREADS - 1) / TX_THREADS)), dim3(TX_THREADS), 0, c->stream,
-                       c->d_text, (unsigned long long)n_bases, lenc, lenb, d_dst);
+                       c->d_text.p(), (unsigned long long)n_bases, lenc, lenb, d_dst);
     MSIM_HIP(c, hipGetLastError());
     MSIM_HIP(c, wait_stream(c->stream));
     c->text_len = 0;
@@ -1307,24 +1307,23 @@ int fasta_gather_device(Ctx *c, const uint8_t *body, uint64_t body_bytes, uint64
 int splice_device(Ctx *c, const Contig &a, const Contig *b, const uint32_t *seg_out, const uint32_t *seg_src, uint32_t n_seg,
                   Contig &dst) {
     const uint64_t out_len = seg_out[n_seg];
-    int rc = dev_reserve(c, (void **)&dst.d_out, &dst.cap_out, out_len + PAD);
+    int rc = dev_reserve(c, dst.d_out, out_len + PAD);
     if (rc) return rc;
     dst.out_len = out_len;
     if (!out_len) return MSIM_OK;
-    uint32_t *d_tab = nullptr;
-    const size_t tab_bytes = ((size_t)2 * n_seg + 1) * sizeof(uint32_t);
-    MSIM_HIP(c, hipMalloc(&d_tab, tab_bytes));
+    Scratch<uint32_t> tab;                                 // (freed when this returns)
+    MSIM_HIP(c, dev_alloc(tab, ((size_t)2 * n_seg + 1) * sizeof(uint32_t)));
+    uint32_t *d_tab = tab.p();
     hipError_t e = hipMemcpyAsync(d_tab, seg_out, ((size_t)n_seg + 1) * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(d_tab + n_seg + 1, seg_src, (size_t)n_seg * 4, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         const uint64_t groups = (out_len + 15) / 16;
         hipLaunchKernelGGL(k_splice, dim3((uint32_t)((groups + TX_THREADS - 1) / TX_THREADS)), dim3(TX_THREADS), 0, c->stream,
-                           a.d_in + PAD, b ? b->d_in + PAD : a.d_in + PAD, d_tab, d_tab + n_seg + 1, n_seg,
-                           (unsigned long long)out_len, dst.d_out);
+                           a.d_in.p() + PAD, b ? b->d_in.p() + PAD : a.d_in.p() + PAD, d_tab, d_tab + n_seg + 1, n_seg,
+                           (unsigned long long)out_len, dst.d_out.p());
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = wait_stream(c->stream);
-    (void)hipFree(d_tab);
     if (e != hipSuccess) return hip_fail(c, e, "splice");
     return MSIM_OK;
 }

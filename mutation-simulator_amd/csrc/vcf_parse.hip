@@ -46,20 +46,20 @@ struct VcfState {
     std::vector<uint64_t> h_ls;            // n_lines + 1 line starts (the last: one past the text's terminator)
     std::vector<uint32_t> h_tabcum;
     // device
-    uint8_t *d_text = nullptr;             // allocation; the text starts at d_text + PAD
-    uint64_t *d_ls = nullptr;
-    uint32_t *d_tabcum = nullptr;
-    uint32_t *d_a = nullptr, *d_b = nullptr, *d_c = nullptr;   // one word per line each: flags / name lengths, then meta / insert lengths / pool offsets
-    uint64_t *d_tile = nullptr;            // 3 x n_tiles: packed sums, the two channels' offsets
-    size_t cap_tile = 0;
-    unsigned long long *d_mb = nullptr, *h_mb = nullptr;       // 8 words: results of a pass (h_mb pinned)
+    Scratch<uint8_t> d_text;               // allocation; the text starts at d_text + PAD
+    Scratch<uint64_t> d_ls;
+    Scratch<uint32_t> d_tabcum;
+    Scratch<uint32_t> d_a, d_b, d_c;       // one word per line each: flags / name lengths, then meta / insert lengths / pool offsets
+    Scratch<uint64_t> d_tile;              // 3 x n_tiles: packed sums, the two channels' offsets (dev_reserve)
+    Scratch<unsigned long long> d_mb;      // 8 words: results of a pass
+    Pinned<unsigned long long> h_mb;       //   ... and their pinned copy
     EventPair tm;
     double load_ms = 0, plan_ms = 0;
     // msim_vcf_select
     uint32_t grammar = 0, sample = 0, hap = 1;
     uint32_t nf0 = 0;                      // fields of the first data line
-    VcfCons *d_cons = nullptr;             // consensus grammar: one per line
-    uint32_t *d_recline = nullptr;         // the line (index within its group) of every compacted record
+    Scratch<VcfCons> d_cons;               // consensus grammar: one per line
+    Scratch<uint32_t> d_recline;           // the line (index within its group) of every compacted record
 };
 
 namespace {
@@ -444,28 +444,21 @@ int wait_ctx(Ctx *c, bool caller_memory) {
 }
 
 int fetch_mailbox(Ctx *c, VcfState *S) {
-    MSIM_HIP(c, hipMemcpyAsync(S->h_mb, S->d_mb, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    MSIM_HIP(c, hipMemcpyAsync(S->h_mb.p(), S->d_mb.p(), 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
     return wait_ctx(c, false);
 }
 
 template <class F>
 int run_scan(Ctx *c, VcfState *S, F f, uint64_t n_items, unsigned long long *d_totals) {
     const uint64_t n_tiles = std::max<uint64_t>(1, (n_items + TILE - 1) / TILE);
-    int rc = dev_reserve(c, (void **)&S->d_tile, &S->cap_tile, (size_t)n_tiles * 3 * sizeof(uint64_t));
+    int rc = dev_reserve(c, S->d_tile, (size_t)n_tiles * 3 * sizeof(uint64_t));
     if (rc) return rc;
-    uint64_t *sum = S->d_tile, *off_lo = sum + n_tiles, *off_hi = off_lo + n_tiles;
+    uint64_t *sum = S->d_tile.p(), *off_lo = sum + n_tiles, *off_hi = off_lo + n_tiles;
     hipLaunchKernelGGL(k_tile_reduce<F>, dim3((unsigned)n_tiles), dim3(ST), 0, c->stream, f, n_items, sum);
     hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(ST), 0, c->stream, sum, n_tiles, off_lo, off_hi, d_totals);
     hipLaunchKernelGGL(k_tile_apply<F>, dim3((unsigned)n_tiles), dim3(ST), 0, c->stream, f, n_items, off_lo, off_hi);
     MSIM_HIP(c, hipGetLastError());
     return MSIM_OK;
-}
-
-void free_device(VcfState *S) {
-    void *bufs[] = {S->d_text, S->d_ls, S->d_tabcum, S->d_a, S->d_b, S->d_c, S->d_tile, S->d_mb, S->d_cons, S->d_recline};
-    for (void *p : bufs) if (p) (void)hipFree(p);
-    if (S->h_mb) (void)hipHostFree(S->h_mb);
-    S->tm.destroy();
 }
 
 // end of a timed stretch of the load (begun by tm.begin): results back, kernel time added
@@ -638,77 +631,76 @@ int plan_host_cons(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) {
 
 // ---- device parser ---------------------------------------------------------------------------------------------------------
 int load_device(Ctx *c, VcfState *S, const uint8_t *text, uint64_t n) {
-    MSIM_HIP(c, hipHostMalloc((void **)&S->h_mb, 8 * sizeof(unsigned long long), hipHostMallocDefault));
-    MSIM_HIP(c, hipMalloc((void **)&S->d_mb, 8 * sizeof(unsigned long long)));
+    MSIM_HIP(c, pin_alloc(S->h_mb, 8 * sizeof(unsigned long long)));
+    MSIM_HIP(c, dev_alloc(S->d_mb, 8 * sizeof(unsigned long long)));
     MSIM_HIP(c, S->tm.create());
-    MSIM_HIP(c, hipMalloc((void **)&S->d_text, n + 2 * PAD));
-    MSIM_HIP(c, hipMemsetAsync(S->d_text, 0, PAD, c->stream));
-    MSIM_HIP(c, hipMemsetAsync(S->d_text + PAD + n, 0, PAD, c->stream));
-    if (n) MSIM_HIP(c, hipMemcpyAsync(S->d_text + PAD, text, n, hipMemcpyHostToDevice, c->stream));
+    MSIM_HIP(c, dev_alloc(S->d_text, n + 2 * PAD));
+    MSIM_HIP(c, hipMemsetAsync(S->d_text.p(), 0, PAD, c->stream));
+    MSIM_HIP(c, hipMemsetAsync(S->d_text.p() + PAD + n, 0, PAD, c->stream));
+    if (n) MSIM_HIP(c, hipMemcpyAsync(S->d_text.p() + PAD, text, n, hipMemcpyHostToDevice, c->stream));
     int rc = wait_ctx(c, true);                            // (the caller's text is free again)
     if (rc) return rc;
-    const uint8_t *t = S->d_text + PAD;
+    const uint8_t *t = S->d_text.p() + PAD;
     // pass 1: how many lines
     const uint64_t n_pieces = (n + 15) / 16;
     LineStartF lf{t, n, nullptr, nullptr};
     const uint64_t n_tiles = std::max<uint64_t>(1, (n_pieces + TILE - 1) / TILE);
-    rc = dev_reserve(c, (void **)&S->d_tile, &S->cap_tile, (size_t)n_tiles * 3 * sizeof(uint64_t));
+    rc = dev_reserve(c, S->d_tile, (size_t)n_tiles * 3 * sizeof(uint64_t));
     if (rc) return rc;
-    uint64_t *sum = S->d_tile, *off_lo = sum + n_tiles, *off_hi = off_lo + n_tiles;
-    MSIM_HIP(c, hipMemsetAsync(S->d_mb, 0, 8 * sizeof(unsigned long long), c->stream));
+    uint64_t *sum = S->d_tile.p(), *off_lo = sum + n_tiles, *off_hi = off_lo + n_tiles;
+    MSIM_HIP(c, hipMemsetAsync(S->d_mb.p(), 0, 8 * sizeof(unsigned long long), c->stream));
     MSIM_HIP(c, S->tm.begin(c->stream));
     hipLaunchKernelGGL(k_tile_reduce<LineStartF>, dim3((unsigned)n_tiles), dim3(ST), 0, c->stream, lf, n_pieces, sum);
-    hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(ST), 0, c->stream, sum, n_tiles, off_lo, off_hi, S->d_mb + 4);
+    hipLaunchKernelGGL(k_tile_scan, dim3(1), dim3(ST), 0, c->stream, sum, n_tiles, off_lo, off_hi, S->d_mb.p() + 4);
     MSIM_HIP(c, hipGetLastError());
     if ((rc = phase_end(c, S))) return rc;
-    const uint64_t newlines = S->h_mb[4];
-    S->n_tabs = S->h_mb[5];
+    const uint64_t newlines = S->h_mb.p()[4];
+    S->n_tabs = S->h_mb.p()[5];
     const bool open_end = n && text[n - 1] != '\n';
     S->n_lines = newlines + (open_end ? 1 : 0);
     if (S->n_lines >= (1ull << 31)) return fail(c, MSIM_ERR_UNSUPPORTED, "VCF of 2^31 lines or more");
     // pass 2: where they start
-    MSIM_HIP(c, hipMalloc((void **)&S->d_ls, (S->n_lines + 2) * sizeof(uint64_t)));
-    MSIM_HIP(c, hipMalloc((void **)&S->d_tabcum, (S->n_lines + 2) * sizeof(uint32_t)));
-    MSIM_HIP(c, hipMalloc((void **)&S->d_a, (S->n_lines + 1) * sizeof(uint32_t)));
-    MSIM_HIP(c, hipMalloc((void **)&S->d_b, (S->n_lines + 1) * sizeof(uint32_t)));
-    MSIM_HIP(c, hipMalloc((void **)&S->d_c, (S->n_lines + 1) * sizeof(uint32_t)));
-    MSIM_HIP(c, hipMemsetAsync(S->d_ls, 0, sizeof(uint64_t), c->stream));
-    MSIM_HIP(c, hipMemsetAsync(S->d_tabcum, 0, sizeof(uint32_t), c->stream));
-    lf.ls = S->d_ls; lf.tabcum = S->d_tabcum;
+    MSIM_HIP(c, dev_alloc(S->d_ls, (S->n_lines + 2) * sizeof(uint64_t)));
+    MSIM_HIP(c, dev_alloc(S->d_tabcum, (S->n_lines + 2) * sizeof(uint32_t)));
+    MSIM_HIP(c, dev_alloc(S->d_a, (S->n_lines + 1) * sizeof(uint32_t)));
+    MSIM_HIP(c, dev_alloc(S->d_b, (S->n_lines + 1) * sizeof(uint32_t)));
+    MSIM_HIP(c, dev_alloc(S->d_c, (S->n_lines + 1) * sizeof(uint32_t)));
+    MSIM_HIP(c, hipMemsetAsync(S->d_ls.p(), 0, sizeof(uint64_t), c->stream));
+    MSIM_HIP(c, hipMemsetAsync(S->d_tabcum.p(), 0, sizeof(uint32_t), c->stream));
+    lf.ls = S->d_ls.p(); lf.tabcum = S->d_tabcum.p();
     MSIM_HIP(c, S->tm.begin(c->stream));
     hipLaunchKernelGGL(k_tile_apply<LineStartF>, dim3((unsigned)n_tiles), dim3(ST), 0, c->stream, lf, n_pieces, off_lo, off_hi);
     MSIM_HIP(c, hipGetLastError());
     if (open_end) {                                        // the last line has no terminator: it ends where one would stand
-        uint32_t *tabs = reinterpret_cast<uint32_t *>(&S->h_mb[7]);       // (staged in the pinned mailbox: no copy out of this frame)
-        S->h_mb[6] = n + 1;
+        uint32_t *tabs = reinterpret_cast<uint32_t *>(&S->h_mb.p()[7]);       // (staged in the pinned mailbox: no copy out of this frame)
+        S->h_mb.p()[6] = n + 1;
         *tabs = (uint32_t)S->n_tabs;
-        MSIM_HIP(c, hipMemcpyAsync(S->d_ls + S->n_lines, &S->h_mb[6], sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-        MSIM_HIP(c, hipMemcpyAsync(S->d_tabcum + S->n_lines, tabs, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
+        MSIM_HIP(c, hipMemcpyAsync(S->d_ls.p() + S->n_lines, &S->h_mb.p()[6], sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+        MSIM_HIP(c, hipMemcpyAsync(S->d_tabcum.p() + S->n_lines, tabs, sizeof(uint32_t), hipMemcpyHostToDevice, c->stream));
     }
     // header lines, groups
-    S->h_mb[0] = S->n_lines;
-    MSIM_HIP(c, hipMemcpyAsync(S->d_mb, S->h_mb, sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+    S->h_mb.p()[0] = S->n_lines;
+    MSIM_HIP(c, hipMemcpyAsync(S->d_mb.p(), S->h_mb.p(), sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
     if (S->n_lines)
-        hipLaunchKernelGGL(k_first_data, dim3(blocks_for(S->n_lines, 256)), dim3(256), 0, c->stream, t, S->d_ls, S->n_lines, S->d_mb);
+        hipLaunchKernelGGL(k_first_data, dim3(blocks_for(S->n_lines, 256)), dim3(256), 0, c->stream, t, S->d_ls.p(), S->n_lines, S->d_mb.p());
     MSIM_HIP(c, hipGetLastError());
     if ((rc = phase_end(c, S))) return rc;
-    S->n_header = S->h_mb[0];
+    S->n_header = S->h_mb.p()[0];
     const uint64_t n_data = S->n_lines - S->n_header;
     if (n_data) {
         const uint64_t cap = std::min<uint64_t>(n_data, VCF_MAX_GROUPS);
-        uint64_t *g_first = nullptr, *g_off = nullptr;
-        uint32_t *g_len = nullptr;
-        MSIM_HIP(c, hipMalloc((void **)&g_first, cap * 20));
-        g_off = g_first + cap;
-        g_len = reinterpret_cast<uint32_t *>(g_off + cap);
+        Scratch<uint64_t> found;                           // (freed however this block is left)
+        MSIM_HIP(c, dev_alloc(found, cap * 20));
+        uint64_t *const g_first = found.p(), *const g_off = g_first + cap;
+        uint32_t *const g_len = reinterpret_cast<uint32_t *>(g_off + cap);
         MSIM_HIP(c, S->tm.begin(c->stream));
-        hipLaunchKernelGGL(k_group_flags, dim3(blocks_for(n_data, 256)), dim3(256), 0, c->stream, t, S->d_ls, S->n_header, n_data, S->d_a, S->d_b);
-        GroupF gf{S->d_a, S->d_b, S->d_ls, S->n_header, cap, g_first, g_off, g_len};
-        rc = run_scan(c, S, gf, n_data, S->d_mb + 4);
+        hipLaunchKernelGGL(k_group_flags, dim3(blocks_for(n_data, 256)), dim3(256), 0, c->stream, t, S->d_ls.p(), S->n_header, n_data, S->d_a.p(), S->d_b.p());
+        GroupF gf{S->d_a.p(), S->d_b.p(), S->d_ls.p(), S->n_header, cap, g_first, g_off, g_len};
+        rc = run_scan(c, S, gf, n_data, S->d_mb.p() + 4);
         if (!rc) rc = phase_end(c, S);
         std::vector<uint8_t> host;
         if (!rc) {
-            S->n_groups = S->h_mb[4];
+            S->n_groups = S->h_mb.p()[4];
             const uint64_t k = std::min<uint64_t>(S->n_groups, cap);
             host.resize((size_t)cap * 20);
             const hipError_t e = hipMemcpyAsync(host.data(), g_first, (size_t)cap * 20, hipMemcpyDeviceToHost, c->stream);
@@ -724,7 +716,6 @@ int load_device(Ctx *c, VcfState *S, const uint8_t *text, uint64_t n) {
                 }
             }
         }
-        (void)hipFree(g_first);
         if (rc) return rc;
     }
     return MSIM_OK;
@@ -740,19 +731,19 @@ int plan_device(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) {
     uint64_t pool_len = 0;
     bool any_sv = false, too_long = false, check_only = false;
     if (cnt) {
-        const uint8_t *t = S->d_text + PAD, *in = g->d_in + PAD;
+        const uint8_t *t = S->d_text.p() + PAD, *in = g->d_in.p() + PAD;
         const uint64_t first = grp->first_line;
-        rc = dev_reserve(c, (void **)&g->d_recs, &g->cap_recs, (size_t)cnt * sizeof(msim_record));
+        rc = dev_reserve(c, g->d_recs, (size_t)cnt * sizeof(msim_record));
         if (rc) return rc;
-        S->h_mb[0] = ~0ull; S->h_mb[1] = S->h_mb[2] = S->h_mb[3] = 0;
-        MSIM_HIP(c, hipMemcpyAsync(S->d_mb, S->h_mb, 4 * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+        S->h_mb.p()[0] = ~0ull; S->h_mb.p()[1] = S->h_mb.p()[2] = S->h_mb.p()[3] = 0;
+        MSIM_HIP(c, hipMemcpyAsync(S->d_mb.p(), S->h_mb.p(), 4 * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
         MSIM_HIP(c, S->tm.begin(c->stream));
-        uint32_t *meta = S->d_a, *ilen = S->d_b, *poff = S->d_c;
-        hipLaunchKernelGGL(k_vcf_lines, dim3(blocks_for(cnt, 256)), dim3(256), 0, c->stream, t, S->d_ls, S->d_tabcum, first, cnt, grp->name_len, in,
-                           g->len, g->d_recs, meta, ilen, S->d_mb);
-        rc = run_scan(c, S, ArrayScanF{ilen, poff}, cnt, S->d_mb + 4);
+        uint32_t *meta = S->d_a.p(), *ilen = S->d_b.p(), *poff = S->d_c.p();
+        hipLaunchKernelGGL(k_vcf_lines, dim3(blocks_for(cnt, 256)), dim3(256), 0, c->stream, t, S->d_ls.p(), S->d_tabcum.p(), first, cnt, grp->name_len, in,
+                           g->len, g->d_recs.p(), meta, ilen, S->d_mb.p());
+        rc = run_scan(c, S, ArrayScanF{ilen, poff}, cnt, S->d_mb.p() + 4);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_vcf_neigh, dim3(blocks_for(cnt, 256)), dim3(256), 0, c->stream, g->d_recs, meta, poff, first, cnt, S->d_mb);
+        hipLaunchKernelGGL(k_vcf_neigh, dim3(blocks_for(cnt, 256)), dim3(256), 0, c->stream, g->d_recs.p(), meta, poff, first, cnt, S->d_mb.p());
         MSIM_HIP(c, hipGetLastError());
         MSIM_HIP(c, S->tm.end(c->stream));
         if ((rc = fetch_mailbox(c, S))) return rc;
@@ -760,26 +751,26 @@ int plan_device(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) {
         // A refusal found so far does not end the pass: an earlier line may still fail in its long part, and the first
         // offending line is the one to name.  Refused lines add nothing to either sum.  With a refusal pending, or with sums
         // of 2^32 or more (where the 32-bit pool offsets have wrapped), the long pass checks only and writes no pool byte.
-        too_long = g->len + S->h_mb[1] >= (1ull << 32);
-        check_only = too_long || S->h_mb[0] != ~0ull;
-        pool_len = check_only ? 0 : S->h_mb[4];            // (below 2^32 with the bound above: the 32-bit offsets are exact)
-        any_sv = S->h_mb[3] & 1;
+        too_long = g->len + S->h_mb.p()[1] >= (1ull << 32);
+        check_only = too_long || S->h_mb.p()[0] != ~0ull;
+        pool_len = check_only ? 0 : S->h_mb.p()[4];            // (below 2^32 with the bound above: the 32-bit offsets are exact)
+        any_sv = S->h_mb.p()[3] & 1;
     }
-    rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, (size_t)pool_len + 2 * PAD);
+    rc = dev_reserve(c, g->d_pool, (size_t)pool_len + 2 * PAD);
     if (rc) return rc;
     if (any_sv) {
         const uint64_t first = grp->first_line;
         // the group's text: from its first line's start to the start of the line behind its last one
         const uint64_t bytes = S->group_end[(size_t)(grp - S->groups.data())] - grp->name_off + (grp->name_off & 15);
         MSIM_HIP(c, S->tm.begin(c->stream));
-        hipLaunchKernelGGL(k_vcf_long, dim3(blocks_for((bytes + 15) / 16, 256)), dim3(256), 0, c->stream, S->d_text + PAD, S->d_ls, first, cnt,
-                           g->d_recs, S->d_a, g->d_in + PAD, g->d_pool + PAD, pool_len, S->d_mb);
+        hipLaunchKernelGGL(k_vcf_long, dim3(blocks_for((bytes + 15) / 16, 256)), dim3(256), 0, c->stream, S->d_text.p() + PAD, S->d_ls.p(), first, cnt,
+                           g->d_recs.p(), S->d_a.p(), g->d_in.p() + PAD, g->d_pool.p() + PAD, pool_len, S->d_mb.p());
         MSIM_HIP(c, hipGetLastError());
         MSIM_HIP(c, S->tm.end(c->stream));
         if ((rc = fetch_mailbox(c, S))) return rc;
         if ((rc = S->tm.add_elapsed(c, &S->plan_ms))) return rc;
     }
-    if (cnt && S->h_mb[0] != ~0ull) return vcf_fail(c, S->h_mb[0] >> 4, (uint32_t)(S->h_mb[0] & 15));
+    if (cnt && S->h_mb.p()[0] != ~0ull) return vcf_fail(c, S->h_mb.p()[0] >> 4, (uint32_t)(S->h_mb.p()[0] & 15));
     if (too_long) return vcf_fail(c, grp->first_line + 1, VCF_R_LENGTH);
     g->n_rec = cnt;
     g->pool_len = pool_len;
@@ -799,47 +790,47 @@ int plan_device_cons(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) 
     uint64_t pool_len = 0, n_rec = 0;
     bool any_sv = false, too_long = false;
     if (cnt) {
-        const uint8_t *t = S->d_text + PAD, *in = g->d_in + PAD;
+        const uint8_t *t = S->d_text.p() + PAD, *in = g->d_in.p() + PAD;
         const uint64_t first = grp->first_line;
-        rc = dev_reserve(c, (void **)&g->d_recs, &g->cap_recs, (size_t)cnt * 2 * sizeof(msim_record));
+        rc = dev_reserve(c, g->d_recs, (size_t)cnt * 2 * sizeof(msim_record));
         if (rc) return rc;
         // the group's text: from its first line's start to the start of the line behind its last one, in 16-byte pieces
         const uint64_t bytes = S->group_end[(size_t)(grp - S->groups.data())] - grp->name_off + (grp->name_off & 15);
         const unsigned piece_blocks = blocks_for((bytes + 15) / 16, 256), line_blocks = blocks_for(cnt, 256);
-        S->h_mb[0] = ~0ull; S->h_mb[1] = S->h_mb[2] = S->h_mb[3] = 0;
-        MSIM_HIP(c, hipMemcpyAsync(S->d_mb, S->h_mb, 4 * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
+        S->h_mb.p()[0] = ~0ull; S->h_mb.p()[1] = S->h_mb.p()[2] = S->h_mb.p()[3] = 0;
+        MSIM_HIP(c, hipMemcpyAsync(S->d_mb.p(), S->h_mb.p(), 4 * sizeof(unsigned long long), hipMemcpyHostToDevice, c->stream));
         MSIM_HIP(c, S->tm.begin(c->stream));
-        hipLaunchKernelGGL(k_cons_ends, dim3(line_blocks), dim3(256), 0, c->stream, t, S->d_ls, S->d_tabcum, first, cnt, grp->name_len, S->nf0,
-                           S->sample, S->hap, g->len, S->d_cons, S->d_mb);
-        hipLaunchKernelGGL(k_cons_sep, dim3(piece_blocks), dim3(256), 0, c->stream, t, S->d_ls, first, cnt, S->d_cons);
-        hipLaunchKernelGGL(k_cons_lines, dim3(line_blocks), dim3(256), 0, c->stream, t, first, cnt, in, g->len, S->d_cons, S->d_mb);
-        rc = run_scan(c, S, ConsEmitF{S->d_cons, g->d_recs, S->d_recline}, cnt, S->d_mb + 4);
+        hipLaunchKernelGGL(k_cons_ends, dim3(line_blocks), dim3(256), 0, c->stream, t, S->d_ls.p(), S->d_tabcum.p(), first, cnt, grp->name_len, S->nf0,
+                           S->sample, S->hap, g->len, S->d_cons.p(), S->d_mb.p());
+        hipLaunchKernelGGL(k_cons_sep, dim3(piece_blocks), dim3(256), 0, c->stream, t, S->d_ls.p(), first, cnt, S->d_cons.p());
+        hipLaunchKernelGGL(k_cons_lines, dim3(line_blocks), dim3(256), 0, c->stream, t, first, cnt, in, g->len, S->d_cons.p(), S->d_mb.p());
+        rc = run_scan(c, S, ConsEmitF{S->d_cons.p(), g->d_recs.p(), S->d_recline.p()}, cnt, S->d_mb.p() + 4);
         if (rc) return rc;
-        hipLaunchKernelGGL(k_cons_neigh, dim3(blocks_for(2 * cnt, 256)), dim3(256), 0, c->stream, g->d_recs, S->d_recline, S->d_mb + 4, first, S->d_mb);
+        hipLaunchKernelGGL(k_cons_neigh, dim3(blocks_for(2 * cnt, 256)), dim3(256), 0, c->stream, g->d_recs.p(), S->d_recline.p(), S->d_mb.p() + 4, first, S->d_mb.p());
         MSIM_HIP(c, hipGetLastError());
         MSIM_HIP(c, S->tm.end(c->stream));
         if ((rc = fetch_mailbox(c, S))) return rc;
         if ((rc = S->tm.add_elapsed(c, &S->plan_ms))) return rc;
         // as plan_device: a refusal found so far does not end the pass, and with one pending, or with sums of 2^32 or more,
         // the per-byte pass checks only and writes no pool byte
-        too_long = g->len + S->h_mb[1] >= (1ull << 32);
-        const bool check_only = too_long || S->h_mb[0] != ~0ull;
-        n_rec = S->h_mb[4];
-        pool_len = check_only ? 0 : S->h_mb[5];
-        any_sv = S->h_mb[3] & 1;
-        rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, (size_t)pool_len + 2 * PAD);
+        too_long = g->len + S->h_mb.p()[1] >= (1ull << 32);
+        const bool check_only = too_long || S->h_mb.p()[0] != ~0ull;
+        n_rec = S->h_mb.p()[4];
+        pool_len = check_only ? 0 : S->h_mb.p()[5];
+        any_sv = S->h_mb.p()[3] & 1;
+        rc = dev_reserve(c, g->d_pool, (size_t)pool_len + 2 * PAD);
         if (rc) return rc;
         MSIM_HIP(c, S->tm.begin(c->stream));
-        hipLaunchKernelGGL(k_cons_long, dim3(piece_blocks), dim3(256), 0, c->stream, t, S->d_ls, first, cnt, S->d_cons, in, g->d_pool + PAD, pool_len,
-                           S->d_mb);
+        hipLaunchKernelGGL(k_cons_long, dim3(piece_blocks), dim3(256), 0, c->stream, t, S->d_ls.p(), first, cnt, S->d_cons.p(), in, g->d_pool.p() + PAD, pool_len,
+                           S->d_mb.p());
         MSIM_HIP(c, hipGetLastError());
         MSIM_HIP(c, S->tm.end(c->stream));
         if ((rc = fetch_mailbox(c, S))) return rc;
         if ((rc = S->tm.add_elapsed(c, &S->plan_ms))) return rc;
-        if (S->h_mb[0] != ~0ull) return vcf_fail(c, S->h_mb[0] >> 4, (uint32_t)(S->h_mb[0] & 15));
+        if (S->h_mb.p()[0] != ~0ull) return vcf_fail(c, S->h_mb.p()[0] >> 4, (uint32_t)(S->h_mb.p()[0] & 15));
         if (too_long) return vcf_fail(c, grp->first_line + 1, VCF_R_LENGTH);
     } else {
-        rc = dev_reserve(c, (void **)&g->d_pool, &g->cap_pool, 2 * PAD);
+        rc = dev_reserve(c, g->d_pool, 2 * PAD);
         if (rc) return rc;
     }
     g->n_rec = n_rec;
@@ -857,7 +848,7 @@ void vcf_state_destroy(Ctx *c) {
     if (!c->host_only) {
         (void)hipSetDevice(c->device);
         (void)wait_stream(c->stream);
-        free_device(c->vcf);
+        c->vcf->tm.destroy();
     }
     delete c->vcf;
     c->vcf = nullptr;
@@ -936,8 +927,8 @@ int msim_vcf_select(msim_ctx *p, uint32_t grammar, uint32_t sample_index, uint32
     if (S->n_lines > S->n_header) {                        // the first data line's fields: every line must have as many
         if (c->host_only) nf0 = S->h_tabcum[S->n_header + 1] - S->h_tabcum[S->n_header] + 1;
         else {
-            uint32_t *two = reinterpret_cast<uint32_t *>(&S->h_mb[6]);       // (staged in the pinned mailbox)
-            MSIM_HIP(c, hipMemcpyAsync(two, S->d_tabcum + S->n_header, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+            uint32_t *two = reinterpret_cast<uint32_t *>(&S->h_mb.p()[6]);       // (staged in the pinned mailbox)
+            MSIM_HIP(c, hipMemcpyAsync(two, S->d_tabcum.p() + S->n_header, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
             if ((rc = wait_ctx(c, false))) return rc;
             nf0 = two[1] - two[0] + 1;
         }
@@ -947,8 +938,8 @@ int msim_vcf_select(msim_ctx *p, uint32_t grammar, uint32_t sample_index, uint32
     if (!c->host_only) {                                   // per-line state for the largest group: 88 + 8 bytes a line
         uint64_t most = 0;
         for (const msim_vcf_group &g : S->groups) most = std::max<uint64_t>(most, g.n_lines);
-        if (!S->d_cons) MSIM_HIP(c, hipMalloc((void **)&S->d_cons, (most + 1) * sizeof(VcfCons)));
-        if (!S->d_recline) MSIM_HIP(c, hipMalloc((void **)&S->d_recline, 2 * (most + 1) * sizeof(uint32_t)));
+        if (!S->d_cons) MSIM_HIP(c, dev_alloc(S->d_cons, (most + 1) * sizeof(VcfCons)));
+        if (!S->d_recline) MSIM_HIP(c, dev_alloc(S->d_recline, 2 * (most + 1) * sizeof(uint32_t)));
     }
     S->grammar = 1; S->sample = sample_index; S->hap = haplotype; S->nf0 = nf0;
     return MSIM_OK;
