@@ -658,6 +658,62 @@ int msim_dbg_cmp_counts(const uint8_t *bases, uint64_t L, const msim_record *tru
                         uint64_t calls_pool_len, uint32_t flags, uint64_t *counts, uint64_t tallies[2], uint8_t *truth_flags,
                         uint8_t *calls_flags);
 
+/* ---- compare --diploid: genotypes scored against a diploid truth (csrc/compare.hip, compare.h) ------------------------------------ */
+/* A side's (the truth's, the calls') two haplotype tables of one contig are JOINED into one diploid table U of distinct variants with
+ * a genotype byte each, and the truth's U is matched against the calls' U; a pair's DOSAGES are then compared.  Phase is ignored on
+ * both sides: 0|1, 1|0, 0/1 and 1/0 are one het, 1|1 and 1/1 hom, and a haploid 1 -- which serves both haplotypes, as in the
+ * consensus grammar -- counts as hom.
+ * Join.  H1, H2: position-sorted tables (pos strictly increasing), each with its own insert pool.  U carries one genotype byte per
+ *   record, bit 0: on haplotype 1, bit 1: on haplotype 2 (the byte of msim_set_genotypes).  A record of H2 is the same variant as a
+ *   record of H1 iff they have the same pos and are one variant at distance 0: every type the same type and pos; SN, DU, IV, TL and
+ *   TLI the same aux; IN, DE, DU, IV, TL and TLI the same length (stop); IN the same insert bytes, compared as bytes, not as pool
+ *   offsets; TLI the same extra.  Such a pair is written once, as H1's copy, with genotype 3; every other record with genotype 1
+ *   (from H1) or 2 (from H2).  U is sorted by pos, at equal pos the record from H1 first: at most two records of U share a pos,
+ *   and never two of one class (identical pairs were merged), which is why the matching's rank and scan stay correct on U.  U's pool
+ *   is H1's pool followed by H2's: the extra of an IN record that came from H2 is rebased by H1's pool length, no other type's
+ *   extra is touched.  MSIM_ERR_UNSUPPORTED when the two tables hold 2^31 records or more, or the two pools 2^32 bytes or more.
+ * Match.  Every record of the truth's U finds its record in the calls' U by the rules above, window, stops and MSIM_CMP_EXACT
+ *   unchanged.  A pair whose dosages (the set bits of the two genotype bytes) are equal is a true positive, flag byte 1 on both
+ *   records; a pair whose dosages differ is a genotype mismatch, flag byte 2 on both; no partner: flag byte 0.
+ *   counts[type][bin][6]   truth matched, truth genotype-mismatched, truth missed, calls matched, calls genotype-mismatched, calls
+ *                          extra.  In every cell truth matched == calls matched and truth mismatched == calls mismatched (a pair is
+ *                          one type and one length).  tallies[2] as msim_cmp_counts'.
+ * Limits.  Two records on different haplotypes that are shifted placements of one another stay two het records (only identical
+ *   records merge); phase is not compared; each haplotype goes through its grammar on its own.
+ *   msim_cmp_join             the contig's HELD table is haplotype 1, its current table haplotype 2; the result becomes the contig's
+ *                             diploid table of `side`, kept in the context.  The held table is consumed; the current table is not
+ *                             changed.  The diploid table survives a new plan of the contig and is consumed by msim_cmp_release
+ *                             (of the contig, or -1), msim_clear, msim_destroy and a new join on the same contig and side.  Two
+ *                             empty inputs: an empty diploid table, nothing launched.  MSIM_ERR_ARG without a held table, on an
+ *                             unplanned contig or an unknown side, MSIM_ERR_HIP on a host-only context.
+ *   msim_cmp_counts_diploid   the truth's diploid table against the calls'; MSIM_ERR_ARG before both sides exist.  It neither
+ *                             reads nor changes the contig's tables or msim_cmp_counts' state.  Its kernels' time adds to
+ *                             msim_cmp_timing.
+ *   msim_cmp_fetch_diploid    one side's sizes and, into whichever destination is not NULL, its records, pool, genotype bytes and
+ *                             the flag bytes of the last msim_cmp_counts_diploid (MSIM_ERR_ARG before both sides exist, or when
+ *                             the flags are asked for before such a call).
+ *   msim_cmp_join_timing      the join's kernels and pool copies on the device (HIP events) since the context was made or
+ *                             msim_reset_stats.
+ * MSIM_CMP_JOIN_TILE: the records one workgroup of the join's scan takes -- where its edge cases lie.
+ * msim_dbg_cmp_join / msim_dbg_cmp_counts_diploid: the same by sequential host loops, no context, no GPU.  The join writes
+ * out[n1 + n2], out_gt[n1 + n2] and out_pool[pool1_len + pool2_len] and the number of records to *n_out; the counts take a
+ * genotype byte per record and give the flag bytes (either array may be NULL).  MSIM_ERR_ARG for a record of unknown type, a
+ * table out of order, a genotype byte outside 1..3, a NULL table with a count; the join's two MSIM_ERR_UNSUPPORTED cases.           */
+#define MSIM_CMP_TRUTH 0
+#define MSIM_CMP_CALLS 1
+#define MSIM_CMP_JOIN_TILE 1024
+int msim_cmp_join(msim_ctx *ctx, int contig, int side);
+int msim_cmp_counts_diploid(msim_ctx *ctx, int contig, uint32_t flags, uint64_t *counts, uint64_t tallies[2]);
+int msim_cmp_fetch_diploid(msim_ctx *ctx, int contig, int side, uint64_t *n, uint64_t *pool_len, msim_record *recs, uint8_t *pool,
+                           uint8_t *gt, uint8_t *flags);
+int msim_cmp_join_timing(msim_ctx *ctx, double *kernel_ms);
+int msim_dbg_cmp_join(const msim_record *h1, uint64_t n1, const uint8_t *pool1, uint64_t pool1_len, const msim_record *h2, uint64_t n2,
+                      const uint8_t *pool2, uint64_t pool2_len, msim_record *out, uint8_t *out_pool, uint8_t *out_gt, uint64_t *n_out);
+int msim_dbg_cmp_counts_diploid(const uint8_t *bases, uint64_t L, const msim_record *truth, uint64_t n_truth, const uint8_t *truth_pool,
+                                uint64_t truth_pool_len, const uint8_t *truth_gt, const msim_record *calls, uint64_t n_calls,
+                                const uint8_t *calls_pool, uint64_t calls_pool_len, const uint8_t *calls_gt, uint32_t flags,
+                                uint64_t *counts, uint64_t tallies[2], uint8_t *truth_flags, uint8_t *calls_flags);
+
 /* ---- test support: the SNP ti/tv transducer on the caller's words -------------------------------------------------- */
 /* Runs the three passes that turn CPython-stream words into SNP outcomes -- the map pass over whole blocks of
  * MSIM_SNP_BLOCK_WORDS words, the scan that finds where the K-th SNP's draws end, the outcome pass -- over `words` (raw,

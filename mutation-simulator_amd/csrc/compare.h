@@ -8,7 +8,13 @@
 //              that), an insert's bytes up to the rotation by the distance; every other type field by field
 //   partner    the rank of record i in its class among A's records to the left, the record of that rank in B's scan of
 //              [lo, hi]
-// A, B: position-sorted tables (pos strictly increasing, what every planner and msim_dbg_set_records guarantee).
+//   join       a side's two haplotype tables as one diploid table U with a genotype byte per record (compare --diploid): where a
+//              record of either table lands in U, which records of haplotype 2 are haplotype 1's again (join_dup)
+// A, B: position-sorted tables.  A planner's table and msim_dbg_set_records' have pos strictly increasing; a diploid table U has
+// pos NON-DECREASING with at most two records at one pos, haplotype 1's first, and never two of one class there: `same` at
+// distance 0 means identical, and the join wrote every identical pair once.  partner's rank (a scan to the left while pos >= lo)
+// and its scan of B (from the first record at or behind lo) count records of the class, whatever shares their pos, so both stay
+// correct on U.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,6 +30,8 @@ constexpr uint32_t WINDOW_SHIFT = 16;                      // MSIM_CMP_WINDOW = 
 constexpr uint32_t STOP_WINDOW = 1u, STOP_BASE = 2u;       // why a walk ended (Span::stops): msim_cmp_counts' two tallies
 constexpr uint32_t CELLS = 15;                             // (type, bin) pairs that exist: 7 types in bin 0, IN and DE in bins 1..4
 constexpr uint32_t COUNTERS = 2 * CELLS + 2;               // per cell matched / unmatched, then the two tallies
+constexpr uint32_t DIP_COUNTERS = 3 * CELLS + 2;           // diploid: per cell matched / genotype-mismatched / unmatched, the tallies
+constexpr uint32_t DIP_BINS = 48;                          // ... rounded up to an even number of lane-private bins
 static_assert(MSIM_CMP_BINS == 5, "the cells are laid out for five length bins");
 
 struct Rec { uint32_t pos, stop, extra, type, aux; };
@@ -145,6 +153,42 @@ MSIM_FHD inline int64_t partner(const uint8_t *g, uint64_t L, const Table &A, ui
         }
     }
     return -1;
+}
+
+// ---- the diploid join (msim_cmp_join, msim_dbg_cmp_join) -------------------------------------------------------------------------
+// a genotype byte's dosage: the haplotypes that carry the record (bit 0: haplotype 1, bit 1: haplotype 2)
+MSIM_FHD inline uint32_t dosage(uint32_t gt) { return (gt & 1u) + ((gt >> 1) & 1u); }
+// the flag byte of a matched pair: 1 the same dosage, 2 a genotype mismatch (0: no partner)
+MSIM_FHD inline uint8_t pair_flag(uint32_t gt_a, uint32_t gt_b) { return dosage(gt_a) == dosage(gt_b) ? (uint8_t)1 : (uint8_t)2; }
+
+// the records of t in front of pos: the index of the first record at or behind it (t.n: none)
+MSIM_FHD inline uint64_t first_at(const Table &t, uint32_t pos) {
+    uint64_t lo = 0, hi = t.n;
+    while (lo < hi) {
+        const uint64_t mid = lo + ((hi - lo) >> 1);
+        if (rec_at(t.recs, mid).pos < pos) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+// what `same` asks of its first record in place of walkable(): a length, an insert inside its pool.  (The join compares at
+// distance 0 and walks nowhere, so the contig's length does not come into it.)
+MSIM_FHD inline bool comparable(const Rec &r, uint64_t pool_len) {
+    if (!indel(r.type)) return true;
+    if (r.stop < r.pos) return false;
+    const uint64_t n = (uint64_t)r.stop - r.pos + 1;
+    return r.type == (uint32_t)MSIM_DE || (r.extra <= pool_len && n <= pool_len - r.extra);
+}
+// Is H2's record j a record of H1 again?  *in_front: H1's records at or in front of its pos -- where it lands among them, H1's
+// record coming first at equal pos.
+MSIM_FHD inline bool join_dup(const Table &H1, const Table &H2, uint64_t j, uint64_t *in_front) {
+    const Rec b = rec_at(H2.recs, j);
+    const uint64_t i = first_at(H1, b.pos);
+    *in_front = i;
+    if (i >= H1.n) return false;
+    const Rec a = rec_at(H1.recs, i);
+    if (a.pos != b.pos) return false;
+    *in_front = i + 1;
+    return same(a, H1.pool, comparable(a, H1.pool_len), b, H2.pool, H2.pool_len);
 }
 
 }  // namespace cmp

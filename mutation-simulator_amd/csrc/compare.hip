@@ -6,6 +6,9 @@
 //            the lane stores its own flag byte and its partner's (no two lanes share a partner) and counts the record
 //   tally    k_cmp_tally: one lane per B record, counted by its flag byte
 // Both kernels count into 32 lane-private bins (15 cells x matched / unmatched, two tallies: lane_hist.h).
+// compare --diploid (msim_cmp_join, msim_cmp_counts_diploid): a side's two haplotype tables are JOINED into one diploid table with a
+// genotype byte per record (k_join_flag, k_scan_u32, k_join_put2, k_join_put1), and the truth's diploid table is scored against
+// the calls' by genotype-aware siblings of the two kernels (k_dip_match, k_dip_tally: 48 bins).
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -14,6 +17,7 @@
 #include "compare.h"
 #include "ctx.h"
 #include "lane_hist.h"
+#include "scan_kernels.h"
 
 namespace msim {
 
@@ -27,12 +31,30 @@ struct Held {                                  // msim_cmp_hold's copy of one co
     bool counted = false;
 };
 
+struct Dip {                                   // msim_cmp_join's result: one side's diploid table of one contig
+    bool have = false;
+    Scratch<msim_record> d_recs;               // n records (allocated for n1 + n2)
+    Scratch<uint8_t> d_pool;                   // haplotype 1's pool, then haplotype 2's
+    Scratch<uint8_t> d_gt;                     // a genotype byte per record
+    Scratch<uint8_t> d_flag;                   // a flag byte per record (the last msim_cmp_counts_diploid)
+    uint64_t n = 0, pool_len = 0;
+};
+struct DipPair {
+    Dip side[2];                               // MSIM_CMP_TRUTH, MSIM_CMP_CALLS
+    bool counted = false;
+};
+
 struct CompareState {
     std::vector<Held> held;                    // by contig index
+    std::vector<DipPair> dip;                  // by contig index (a sibling of `held`: msim_cmp_hold replaces a Held whole)
     Scratch<unsigned long long> d_out;         // HIST_SLOTS x (A's counters, B's counters)
     Pinned<unsigned long long> h_out;          // pinned copy of them
+    Scratch<uint32_t> d_front;                 // the join's scratch, per haplotype-2 record: haplotype 1's records at or in front
+                                               //   of its pos, bit 31: it is a duplicate of the last of them;
+    Scratch<uint32_t> d_excl;                  //   the duplicates in front of it;
+    Scratch<uint32_t> d_tile;                  //   per scan tile its duplicates (then their exclusive scan, the total last)
     EventPair tm;
-    double kernel_ms = 0;
+    double kernel_ms = 0, join_ms = 0;
 };
 
 namespace {
@@ -88,6 +110,154 @@ __global__ __launch_bounds__(LANES) void k_cmp_tally(const msim_record *__restri
     hist.flush(slot_of(out));
 }
 
+// ---- diploid: the same two launches over two diploid tables, a genotype byte beside every record --------------------------------
+// 48 lane-private bins (15 cells x matched / genotype-mismatched / unmatched, two tallies, one spare): 24 KB of LDS a workgroup,
+// six workgroups a CU.  The 16-bit argument is CmpHist's: the same grid cap, at most 4096 passes a workgroup, one add per
+// counter, lane and pass.
+constexpr int DIP_BINS = (int)cmp::DIP_BINS;
+static_assert(DIP_BINS % 2 == 0 && DIP_BINS >= (int)cmp::DIP_COUNTERS, "every diploid counter has a bin");
+constexpr size_t DIP_OUT_WORDS = (size_t)HIST_SLOTS * 2 * DIP_BINS;
+using DipHist = LaneHist<DIP_BINS, LANES, 2>;
+__device__ __forceinline__ unsigned long long *dip_slot_of(unsigned long long *out) { return out + (blockIdx.x & (HIST_SLOTS - 1)) * 2 * DIP_BINS; }
+__device__ __forceinline__ uint32_t dip_counter(const cmp::Rec &r, uint32_t flag) { return 3 * cmp::cell_of(r) + (flag == 1 ? 0u : flag == 2 ? 1u : 2u); }
+
+// flag_b was zeroed before the launch.  Indices and reads are checked as in k_cmp_match; a genotype byte is read at an index
+// its table's size has been checked against.
+__global__ __launch_bounds__(LANES) void k_dip_match(const uint8_t *__restrict__ g, uint64_t L, cmp::Table A, cmp::Table B,
+                                                     const uint8_t *__restrict__ gt_a, const uint8_t *__restrict__ gt_b, uint32_t exact,
+                                                     uint64_t n_pass, uint8_t *__restrict__ flag_a, uint8_t *__restrict__ flag_b,
+                                                     unsigned long long *__restrict__ out) {
+    __shared__ DipHist hist;
+    hist.zero();
+    for (uint64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
+        const uint64_t i = pass * CMP_PASS + threadIdx.x;
+        if (i >= A.n) continue;
+        const cmp::Rec a = cmp::rec_at(A.recs, i);
+        if (!cmp::known_type(a.type)) { flag_a[i] = 0; continue; }
+        cmp::Span s;
+        const int64_t j = cmp::partner(g, L, A, i, B, exact != 0, &s);
+        const uint8_t f = (j >= 0 && (uint64_t)j < B.n) ? cmp::pair_flag(gt_a[i], gt_b[j]) : (uint8_t)0;
+        flag_a[i] = f;
+        if (f) flag_b[j] = f;                              // a plain byte store: this lane is the only one with this partner
+        hist.add(dip_counter(a, f), 1u);
+        if (s.stops & cmp::STOP_WINDOW) hist.add(3 * cmp::CELLS, 1u);
+        if (s.stops & cmp::STOP_BASE) hist.add(3 * cmp::CELLS + 1, 1u);
+    }
+    hist.flush(dip_slot_of(out));
+}
+
+__global__ __launch_bounds__(LANES) void k_dip_tally(const msim_record *__restrict__ recs, uint64_t n_rec, uint64_t n_pass,
+                                                     const uint8_t *__restrict__ flag, unsigned long long *__restrict__ out) {
+    __shared__ DipHist hist;
+    hist.zero();
+    for (uint64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
+        const uint64_t i = pass * CMP_PASS + threadIdx.x;
+        if (i >= n_rec) continue;
+        const cmp::Rec b = cmp::rec_at(recs, i);
+        if (cmp::known_type(b.type)) hist.add(dip_counter(b, flag[i]), 1u);
+    }
+    hist.flush(dip_slot_of(out));
+}
+
+// ---- the join: haplotype 1's table (H1) and haplotype 2's (H2) into one diploid table U ------------------------------------------
+// One lane per record of either table.  A scan tile is JOIN_TILE records of H2; k_join_put2 takes them in runs of 64 (run s = round *
+// JOIN_WAVES + wave), one ballot a run -- haplotype.hip's compaction pattern:
+//   flag      k_join_flag: an H2 record binary-searches H1 for its pos, tests the record there with cmp::same and stores what it
+//             found in one word -- H1's records at or in front of its pos (fewer than 2^31), bit 31: it is a duplicate -- so
+//             that nobody searches H1 again; the tile's duplicates are counted
+//   scan      k_scan_u32 over the tiles' counts (scan_kernels.h), the total behind them
+//   put 2     k_join_put2: the duplicates in front of every H2 record (stored: H1's lanes need them), and every H2 record that is
+//             no duplicate to  own index - duplicates in front + H1's records at or in front of its pos,  genotype 2, an
+//             insertion's extra rebased by H1's pool length
+//   put 1     k_join_put1: every H1 record to  own index + H2's records in front of its pos - the duplicates among those,
+//             genotype 3 where H2's record at its pos is a duplicate, else 1
+// Every index is checked against its table's size and every write against U's allocation (n1 + n2 records).
+constexpr int JOIN_WAVES = LANES / 64;
+constexpr int JOIN_ROUNDS = 4;
+constexpr int JOIN_SLOTS = JOIN_WAVES * JOIN_ROUNDS;
+constexpr uint32_t JOIN_TILE = 64u * JOIN_SLOTS;
+static_assert(JOIN_TILE == MSIM_CMP_JOIN_TILE, "msim.h and compare.hip must agree on the join's scan tile");
+constexpr uint32_t JOIN_DUP = 1u << 31;
+
+// (one record a lane, the tile's 1024 lanes one workgroup: a lane's search is a chain of dependent loads, and four of them one
+// behind the other in a lane of a 256-lane workgroup took three times as long, NOTES 27)
+__global__ __launch_bounds__(JOIN_TILE) void k_join_flag(cmp::Table H1, cmp::Table H2, uint32_t *__restrict__ front, uint32_t *__restrict__ tile_cnt) {
+    __shared__ uint32_t wcnt[JOIN_SLOTS];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t j = (uint64_t)blockIdx.x * JOIN_TILE + threadIdx.x;
+    bool d = false;
+    if (j < H2.n) {
+        uint64_t in_front;
+        d = cmp::join_dup(H1, H2, j, &in_front);
+        front[j] = (uint32_t)in_front | (d ? JOIN_DUP : 0u);
+    }
+    const uint32_t cnt = (uint32_t)__popcll(__ballot(d));
+    if (lane == 0) wcnt[wave] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t t = 0;
+#pragma unroll
+        for (int w = 0; w < JOIN_SLOTS; w++) t += wcnt[w];
+        tile_cnt[blockIdx.x] = t;
+    }
+}
+
+__device__ __forceinline__ void join_store(msim_record *__restrict__ U, uint8_t *__restrict__ gt, uint64_t cap, uint64_t at, uint4 v, uint8_t g) {
+    if (at >= cap) return;
+    reinterpret_cast<uint4 *>(U)[at] = v;
+    gt[at] = g;
+}
+
+// tile_off: the exclusive scan of k_join_flag's counts
+__global__ __launch_bounds__(LANES) void k_join_put2(cmp::Table H1, cmp::Table H2, const uint32_t *__restrict__ front,
+                                                     const uint32_t *__restrict__ tile_off, uint32_t *__restrict__ excl,
+                                                     msim_record *__restrict__ U, uint8_t *__restrict__ gt, uint64_t cap) {
+    __shared__ uint32_t scnt[JOIN_SLOTS];
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t base = (uint64_t)blockIdx.x * JOIN_TILE;
+    unsigned long long b[JOIN_ROUNDS];
+    uint32_t found[JOIN_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < JOIN_ROUNDS; r++) {
+        const uint64_t j = base + (uint64_t)(r * JOIN_WAVES + (int)wave) * 64 + lane;
+        found[r] = j < H2.n ? front[j] : 0u;
+        b[r] = __ballot((found[r] & JOIN_DUP) != 0);
+        if (lane == 0) scnt[r * JOIN_WAVES + (int)wave] = (uint32_t)__popcll(b[r]);
+    }
+    __syncthreads();
+    const uint32_t off0 = tile_off[blockIdx.x];
+    const unsigned long long below = (1ull << lane) - 1;
+#pragma unroll
+    for (int r = 0; r < JOIN_ROUNDS; r++) {
+        const int slot = r * JOIN_WAVES + (int)wave;
+        uint32_t pre = 0;
+#pragma unroll
+        for (int s = 0; s < JOIN_SLOTS; s++) pre += s < slot ? scnt[s] : 0u;
+        const uint64_t j = base + (uint64_t)slot * 64 + lane;
+        if (j >= H2.n) continue;
+        const uint32_t before = off0 + pre + (uint32_t)__popcll(b[r] & below);
+        excl[j] = before;
+        if ((b[r] >> lane) & 1ull) continue;               // H1's copy is the one written
+        uint4 v = reinterpret_cast<const uint4 *>(H2.recs)[j];
+        const uint64_t in_front = found[r];                // H1's records at or in front of this pos: at equal pos H1's comes first
+        if ((v.w & 0xffu) == (uint32_t)MSIM_IN) v.z += (uint32_t)H1.pool_len;   // (the two pool lengths sum to less than 2^32)
+        join_store(U, gt, cap, j - before + in_front, v, 2);
+    }
+}
+
+// total: the duplicates of all of H2 (the word behind the tiles' scan)
+__global__ __launch_bounds__(LANES) void k_join_put1(cmp::Table H1, cmp::Table H2, const uint32_t *__restrict__ front,
+                                                     const uint32_t *__restrict__ excl, const uint32_t *__restrict__ total,
+                                                     msim_record *__restrict__ U, uint8_t *__restrict__ gt, uint64_t cap) {
+    const uint64_t i = (uint64_t)blockIdx.x * LANES + threadIdx.x;
+    if (i >= H1.n) return;
+    const uint4 v = reinterpret_cast<const uint4 *>(H1.recs)[i];
+    const uint64_t k = cmp::first_at(H2, v.x);             // H2's records in front of this pos
+    const uint32_t before = k < H2.n ? excl[k] : *total;
+    const bool both = k < H2.n && (front[k] & JOIN_DUP) != 0 && cmp::rec_at(H2.recs, k).pos == v.x;
+    join_store(U, gt, cap, i + k - before, v, both ? 3 : 1);
+}
+
 // counters[0]: A's (matched / missed per cell, the two tallies), counters[1]: B's (matched / extra per cell)
 void cmp_finish(const unsigned long long *a, const unsigned long long *b, uint64_t *counts, uint64_t tallies[2]) {
     for (uint32_t cell = 0; cell < cmp::CELLS; cell++) {
@@ -105,8 +275,8 @@ int state_of(Ctx *c, CompareState **out) {
     if (!c->compare) {
         CompareState *S = new CompareState;
         c->compare = S;
-        MSIM_HIP(c, dev_alloc(S->d_out, OUT_WORDS * sizeof(unsigned long long)));
-        MSIM_HIP(c, pin_alloc(S->h_out, OUT_WORDS * sizeof(unsigned long long)));
+        MSIM_HIP(c, dev_alloc(S->d_out, DIP_OUT_WORDS * sizeof(unsigned long long)));   // (the larger of the two layouts)
+        MSIM_HIP(c, pin_alloc(S->h_out, DIP_OUT_WORDS * sizeof(unsigned long long)));
         MSIM_HIP(c, S->tm.create());
     }
     *out = c->compare;
@@ -156,11 +326,141 @@ int counts_device(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32_t fl
     return MSIM_OK;
 }
 
+// a[]: the truth's counters (matched / genotype-mismatched / missed per cell, the two tallies), b[]: the calls'
+void dip_finish(const unsigned long long *a, const unsigned long long *b, uint64_t *counts, uint64_t tallies[2]) {
+    for (uint32_t cell = 0; cell < cmp::CELLS; cell++) {
+        uint32_t type, bin;
+        cmp::cell_index(cell, &type, &bin);
+        uint64_t *dst = counts + ((size_t)type * MSIM_CMP_BINS + bin) * 6;
+        for (int k = 0; k < 3; k++) { dst[k] += a[3 * cell + k]; dst[3 + k] += b[3 * cell + k]; }
+    }
+    tallies[0] += a[3 * cmp::CELLS];
+    tallies[1] += a[3 * cmp::CELLS + 1];
+}
+
+// exactly `bytes`, whatever the block held (contents are not kept)
+hipError_t dev_exact(DevBlock &b, size_t bytes) {
+    const hipError_t e = b.release();
+    return e != hipSuccess || !bytes ? e : dev_alloc(b, bytes);
+}
+// at least `bytes` (contents are not kept)
+hipError_t dev_at_least(DevBlock &b, size_t bytes) { return bytes <= b.cap ? hipSuccess : dev_exact(b, bytes); }
+
+DipPair *dip_of(Ctx *c, int contig) {
+    CompareState *S = c->compare;
+    if (!S || contig < 0 || (size_t)contig >= S->dip.size()) return nullptr;
+    DipPair &p = S->dip[(size_t)contig];
+    return p.side[0].have && p.side[1].have ? &p : nullptr;
+}
+
+// H1 = the held table h, H2 = the contig's active table: the launches of the join into d (sizes checked by the caller)
+int join_device(Ctx *c, CompareState *S, const Contig &g, const Held &h, Dip &d) {
+    const uint64_t n1 = h.n_rec, n2 = g.n_rec, cap = n1 + n2;
+    d.pool_len = h.pool_len + g.pool_len;
+    d.n = 0;
+    MSIM_HIP(c, dev_exact(d.d_recs, (size_t)cap * sizeof(msim_record)));
+    MSIM_HIP(c, dev_exact(d.d_gt, (size_t)cap));
+    MSIM_HIP(c, dev_exact(d.d_flag, (size_t)cap));
+    MSIM_HIP(c, dev_exact(d.d_pool, (size_t)d.pool_len));
+    if (!cap) return MSIM_OK;                              // two empty tables (and so two empty pools): nothing launched
+    const uint32_t tiles = (uint32_t)((n2 + JOIN_TILE - 1) / JOIN_TILE);
+    MSIM_HIP(c, dev_at_least(S->d_front, (size_t)std::max<uint64_t>(n2, 1) * sizeof(uint32_t)));
+    MSIM_HIP(c, dev_at_least(S->d_excl, (size_t)std::max<uint64_t>(n2, 1) * sizeof(uint32_t)));
+    MSIM_HIP(c, dev_at_least(S->d_tile, ((size_t)tiles + 1) * sizeof(uint32_t)));
+    const cmp::Table H1{h.d_recs.p(), n1, h.d_pool.p(), h.pool_len};
+    const cmp::Table H2{g.d_recs.p(), n2, g.pool_len ? g.d_pool.p() + PAD : nullptr, g.pool_len};
+    uint32_t dups = 0;
+    MSIM_HIP(c, S->tm.begin(c->stream));
+    if (n2) {
+        hipLaunchKernelGGL(k_join_flag, dim3(tiles), dim3(JOIN_TILE), 0, c->stream, H1, H2, S->d_front.p(), S->d_tile.p());
+        hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, S->d_tile.p(), tiles);
+        hipLaunchKernelGGL(k_join_put2, dim3(tiles), dim3(LANES), 0, c->stream, H1, H2, (const uint32_t *)S->d_front.p(),
+                           (const uint32_t *)S->d_tile.p(), S->d_excl.p(), d.d_recs.p(), d.d_gt.p(), cap);
+        MSIM_HIP(c, hipGetLastError());
+    } else {
+        MSIM_HIP(c, hipMemsetAsync(S->d_tile.p(), 0, sizeof(uint32_t), c->stream));   // the total: no duplicates
+    }
+    if (n1) {
+        hipLaunchKernelGGL(k_join_put1, dim3((unsigned)((n1 + LANES - 1) / LANES)), dim3(LANES), 0, c->stream, H1, H2,
+                           (const uint32_t *)S->d_front.p(), (const uint32_t *)S->d_excl.p(), (const uint32_t *)S->d_tile.p() + tiles,
+                           d.d_recs.p(), d.d_gt.p(), cap);
+        MSIM_HIP(c, hipGetLastError());
+    }
+    if (h.pool_len) MSIM_HIP(c, hipMemcpyAsync(d.d_pool.p(), h.d_pool.p(), (size_t)h.pool_len, hipMemcpyDeviceToDevice, c->stream));
+    if (g.pool_len)
+        MSIM_HIP(c, hipMemcpyAsync(d.d_pool.p() + h.pool_len, g.d_pool.p() + PAD, (size_t)g.pool_len, hipMemcpyDeviceToDevice, c->stream));
+    MSIM_HIP(c, S->tm.end(c->stream));                      // (the kernels and the two pool copies)
+    MSIM_HIP(c, hipMemcpyAsync(&dups, S->d_tile.p() + tiles, sizeof dups, hipMemcpyDeviceToHost, c->stream));
+    MSIM_HIP(c, wait_stream(c->stream));
+    const int rc = S->tm.add_elapsed(c, &S->join_ms);
+    if (rc) return rc;
+    if (dups > n1 || dups > n2) return fail(c, MSIM_ERR_HIP, "internal: the join counted more duplicates than a table holds");
+    d.n = cap - dups;
+    return MSIM_OK;
+}
+
+int counts_diploid_device(Ctx *c, CompareState *S, const Contig &g, DipPair &p, uint32_t flags, uint64_t *counts, uint64_t tallies[2]) {
+    Dip &a = p.side[MSIM_CMP_TRUTH], &b = p.side[MSIM_CMP_CALLS];
+    p.counted = false;
+    if (a.n || b.n) {
+        const cmp::Table A{a.d_recs.p(), a.n, a.d_pool.p(), a.pool_len}, B{b.d_recs.p(), b.n, b.d_pool.p(), b.pool_len};
+        const uint64_t pass_a = (a.n + CMP_PASS - 1) / CMP_PASS, pass_b = (b.n + CMP_PASS - 1) / CMP_PASS;
+        MSIM_HIP(c, hipMemsetAsync(S->d_out.p(), 0, DIP_OUT_WORDS * sizeof(unsigned long long), c->stream));
+        MSIM_HIP(c, S->tm.begin(c->stream));
+        if (b.n) MSIM_HIP(c, hipMemsetAsync(b.d_flag.p(), 0, (size_t)b.n, c->stream));
+        if (a.n) {
+            hipLaunchKernelGGL(k_dip_match, dim3((unsigned)std::min<uint64_t>(pass_a, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
+                               g.d_in.p() + PAD, g.len, A, B, (const uint8_t *)a.d_gt.p(), (const uint8_t *)b.d_gt.p(),
+                               flags & MSIM_CMP_EXACT, pass_a, a.d_flag.p(), b.d_flag.p(), S->d_out.p());
+            MSIM_HIP(c, hipGetLastError());
+        }
+        if (b.n) {
+            hipLaunchKernelGGL(k_dip_tally, dim3((unsigned)std::min<uint64_t>(pass_b, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
+                               (const msim_record *)b.d_recs.p(), b.n, pass_b, (const uint8_t *)b.d_flag.p(), S->d_out.p() + DIP_BINS);
+            MSIM_HIP(c, hipGetLastError());
+        }
+        MSIM_HIP(c, S->tm.end(c->stream));
+        MSIM_HIP(c, hipMemcpyAsync(S->h_out.p(), S->d_out.p(), DIP_OUT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+        MSIM_HIP(c, wait_stream(c->stream));
+        const int rc = S->tm.add_elapsed(c, &S->kernel_ms);
+        if (rc) return rc;
+        unsigned long long bins[2 * DIP_BINS];
+        hist_sum_slots(S->h_out.p(), 2 * DIP_BINS, bins, 2 * DIP_BINS);
+        dip_finish(bins, bins + DIP_BINS, counts, tallies);
+    }
+    p.counted = true;
+    return MSIM_OK;
+}
+
+// (host restatements) a table the rules are written for: known types, pos non-decreasing (strict: strictly increasing)
+int dbg_table_ok(const char *name, const msim_record *t, uint64_t n, bool strict) {
+    for (uint64_t i = 0; i < n; i++) {
+        if (!cmp::known_type(t[i].type)) return fail(nullptr, MSIM_ERR_ARG, std::string(name) + " record " + std::to_string(i) + ": unknown type");
+        if (i && (strict ? t[i].pos <= t[i - 1].pos : t[i].pos < t[i - 1].pos))
+            return fail(nullptr, MSIM_ERR_ARG, std::string(name) + " record " + std::to_string(i) + ": the table is not sorted by pos");
+    }
+    return MSIM_OK;
+}
+int dbg_gt_ok(const char *name, const uint8_t *gt, uint64_t n) {
+    for (uint64_t i = 0; i < n; i++)
+        if (gt[i] < 1 || gt[i] > 3) return fail(nullptr, MSIM_ERR_ARG, std::string(name) + " record " + std::to_string(i) + ": genotype byte outside 1..3");
+    return MSIM_OK;
+}
+// the join's two refusals
+int join_sizes_ok(Ctx *c, uint64_t n1, uint64_t n2, uint64_t pool1, uint64_t pool2) {
+    if (n1 >= (1ull << 31) || n2 >= (1ull << 31) || n1 + n2 >= (1ull << 31))
+        return fail(c, MSIM_ERR_UNSUPPORTED, "the two haplotype tables hold 2^31 records or more");
+    if (pool1 >= (1ull << 32) || pool2 >= (1ull << 32) || pool1 + pool2 >= (1ull << 32))
+        return fail(c, MSIM_ERR_UNSUPPORTED, "the two insert pools hold 4 GiB or more");
+    return MSIM_OK;
+}
+
 }  // namespace
 
 void compare_drop_all(Ctx *c) {
     if (!c->compare) return;
     c->compare->held.clear();
+    c->compare->dip.clear();
 }
 
 void compare_state_destroy(Ctx *c) {
@@ -173,7 +473,7 @@ void compare_state_destroy(Ctx *c) {
 }
 
 void compare_reset_timing(Ctx *c) {
-    if (c->compare) c->compare->kernel_ms = 0;
+    if (c->compare) c->compare->kernel_ms = c->compare->join_ms = 0;
 }
 
 }  // namespace msim
@@ -217,6 +517,7 @@ int msim_cmp_release(msim_ctx *p, int contig) {
     MSIM_HIP(c, wait_stream(c->stream));
     if (contig < 0) { compare_drop_all(c); return MSIM_OK; }
     if (Held *h = held_of(c, contig)) *h = Held{};
+    if (contig >= 0 && (size_t)contig < c->compare->dip.size()) c->compare->dip[(size_t)contig] = DipPair{};
     return MSIM_OK;
 }
 
@@ -266,6 +567,95 @@ int msim_cmp_timing(msim_ctx *p, double *kernel_ms) {
     return MSIM_OK;
 }
 
+// ---- compare --diploid ----------------------------------------------------------------------------------------------------------
+// The contig's held table (haplotype 1) and its active table (haplotype 2) become its diploid table of `side`; the held table
+// is consumed, the active one untouched.
+int msim_cmp_join(msim_ctx *p, int contig, int side) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c) return MSIM_ERR_ARG;
+    Contig *g;
+    int rc = ctx_device_contig(c, contig, true, &g);
+    if (rc) return rc;
+    if (side != MSIM_CMP_TRUTH && side != MSIM_CMP_CALLS) return fail(c, MSIM_ERR_ARG, "unknown side (MSIM_CMP_TRUTH, MSIM_CMP_CALLS)");
+    Held *h = held_of(c, contig);
+    if (!h) return fail(c, MSIM_ERR_ARG, "contig has no held table (msim_cmp_hold)");
+    if ((rc = join_sizes_ok(c, h->n_rec, g->n_rec, h->pool_len, g->pool_len))) return rc;
+    CompareState *S;
+    if ((rc = state_of(c, &S))) return rc;
+    if (S->dip.size() <= (size_t)contig) S->dip.resize((size_t)contig + 1);
+    DipPair &pair = S->dip[(size_t)contig];
+    pair.counted = false;
+    Dip &d = pair.side[side] = Dip{};
+    TraceRange tr("msim compare join");
+    rc = join_device(c, S, *g, *h, d);
+    if (rc) { d = Dip{}; return rc; }
+    d.have = true;
+    *h = Held{};
+    return MSIM_OK;
+}
+
+int msim_cmp_counts_diploid(msim_ctx *p, int contig, uint32_t flags, uint64_t *counts, uint64_t tallies[2]) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c || !counts || !tallies) return MSIM_ERR_ARG;
+    if (flags & ~(uint32_t)MSIM_CMP_EXACT) return fail(c, MSIM_ERR_ARG, "unknown compare flag");
+    Contig *g;
+    int rc = ctx_device_contig(c, contig, false, &g);
+    if (rc) return rc;
+    DipPair *pair = dip_of(c, contig);
+    if (!pair) return fail(c, MSIM_ERR_ARG, "contig has no diploid table of both sides (msim_cmp_join)");
+    CompareState *S;
+    if ((rc = state_of(c, &S))) return rc;
+    memset(counts, 0, (size_t)8 * MSIM_CMP_BINS * 6 * sizeof(uint64_t));
+    memset(tallies, 0, 2 * sizeof(uint64_t));
+    TraceRange tr("msim compare diploid");
+    return counts_diploid_device(c, S, *g, *pair, flags, counts, tallies);
+}
+
+int msim_cmp_fetch_diploid(msim_ctx *p, int contig, int side, uint64_t *n, uint64_t *pool_len, msim_record *recs, uint8_t *pool,
+                           uint8_t *gt, uint8_t *flags) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c) return MSIM_ERR_ARG;
+    if (c->host_only) return fail(c, MSIM_ERR_HIP, "host-only context: this call needs the GPU");
+    if (side != MSIM_CMP_TRUTH && side != MSIM_CMP_CALLS) return fail(c, MSIM_ERR_ARG, "unknown side (MSIM_CMP_TRUTH, MSIM_CMP_CALLS)");
+    DipPair *pair = dip_of(c, contig);
+    if (!pair) return fail(c, MSIM_ERR_ARG, "contig has no diploid table of both sides (msim_cmp_join)");
+    const Dip &d = pair->side[side];
+    if (n) *n = d.n;
+    if (pool_len) *pool_len = d.pool_len;
+    if (flags && !pair->counted) return fail(c, MSIM_ERR_ARG, "the flags are those of the contig's last msim_cmp_counts_diploid: call it first");
+    if (recs && d.n) MSIM_HIP(c, hipMemcpyAsync(recs, d.d_recs.p(), (size_t)d.n * sizeof(msim_record), hipMemcpyDeviceToHost, c->stream));
+    if (pool && d.pool_len) MSIM_HIP(c, hipMemcpyAsync(pool, d.d_pool.p(), (size_t)d.pool_len, hipMemcpyDeviceToHost, c->stream));
+    if (gt && d.n) MSIM_HIP(c, hipMemcpyAsync(gt, d.d_gt.p(), (size_t)d.n, hipMemcpyDeviceToHost, c->stream));
+    if (flags && d.n) MSIM_HIP(c, hipMemcpyAsync(flags, d.d_flag.p(), (size_t)d.n, hipMemcpyDeviceToHost, c->stream));
+    MSIM_HIP(c, wait_stream(c->stream));
+    return MSIM_OK;
+}
+
+int msim_cmp_join_timing(msim_ctx *p, double *kernel_ms) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c) return MSIM_ERR_ARG;
+    if (kernel_ms) *kernel_ms = c->compare ? c->compare->join_ms : 0.0;
+    return MSIM_OK;
+}
+
+// measurement support (tools/compare_bench.py --diploid; exported, not part of msim.h): a device-to-device copy of the bytes the
+// join of the contig's held and current table reads and writes once -- both tables' records and pools read, as many bytes
+// written (an upper bound: a merged pair is written once) -- timed by HIP events: the join's streaming floor
+int msim_dbg_cmp_join_copy_floor(msim_ctx *p, int contig, double *ms) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c || !ms) return MSIM_ERR_ARG;
+    Contig *g;
+    int rc = ctx_device_contig(c, contig, true, &g);
+    if (rc) return rc;
+    Held *h = held_of(c, contig);
+    if (!h) return fail(c, MSIM_ERR_ARG, "contig has no held table (msim_cmp_hold)");
+    CompareState *S;
+    if ((rc = state_of(c, &S))) return rc;
+    const CopySource one[4] = {{h->d_recs.p(), (size_t)h->n_rec * sizeof(msim_record)}, {g->d_recs.p(), (size_t)g->n_rec * sizeof(msim_record)},
+                               {h->d_pool.p(), (size_t)h->pool_len}, {g->pool_len ? g->d_pool.p() + PAD : nullptr, (size_t)g->pool_len}};
+    return copy_floor(c, S->tm, one, 4, ms);
+}
+
 // measurement support (tools/compare_bench.py; exported, not part of msim.h): a device-to-device copy of the held and the current
 // table's record bytes into the context's scratch, timed by HIP events -- the streaming floor the compare kernels are held against
 int msim_dbg_cmp_copy_floor(msim_ctx *p, int contig, double *ms) {
@@ -313,6 +703,70 @@ int msim_dbg_cmp_counts(const uint8_t *bases, uint64_t L, const msim_record *tru
         if (calls_flags) calls_flags[i] = fb[(size_t)i];
     }
     cmp_finish(a, b, counts, tallies);
+    return MSIM_OK;
+}
+
+// The join as a sequential merge of the two tables: out[n1 + n2], out_gt[n1 + n2], out_pool[pool1_len + pool2_len], *n_out.
+int msim_dbg_cmp_join(const msim_record *h1, uint64_t n1, const uint8_t *pool1, uint64_t pool1_len, const msim_record *h2, uint64_t n2,
+                      const uint8_t *pool2, uint64_t pool2_len, msim_record *out, uint8_t *out_pool, uint8_t *out_gt, uint64_t *n_out) {
+    if ((!h1 && n1) || (!h2 && n2) || (!pool1 && pool1_len) || (!pool2 && pool2_len) || !n_out || ((n1 || n2) && (!out || !out_gt)) ||
+        ((pool1_len || pool2_len) && !out_pool))
+        return MSIM_ERR_ARG;
+    int rc = join_sizes_ok(nullptr, n1, n2, pool1_len, pool2_len);
+    if (rc || (rc = dbg_table_ok("haplotype 1", h1, n1, true)) || (rc = dbg_table_ok("haplotype 2", h2, n2, true))) return rc;
+    uint64_t i = 0, j = 0, k = 0;
+    while (i < n1 || j < n2) {
+        if (j == n2 || (i < n1 && h1[i].pos <= h2[j].pos)) {               // at equal pos haplotype 1's record first
+            const cmp::Rec a = cmp::rec_at(h1, i);
+            const bool both = j < n2 && h2[j].pos == a.pos &&
+                              cmp::same(a, pool1, cmp::comparable(a, pool1_len), cmp::rec_at(h2, j), pool2, pool2_len);
+            out[k] = h1[i++];
+            out_gt[k++] = both ? 3 : 1;
+            if (both) j++;
+        } else {
+            out[k] = h2[j++];
+            if (out[k].type == MSIM_IN) out[k].extra += (uint32_t)pool1_len;
+            out_gt[k++] = 2;
+        }
+    }
+    if (pool1_len) memcpy(out_pool, pool1, (size_t)pool1_len);
+    if (pool2_len) memcpy(out_pool + pool1_len, pool2, (size_t)pool2_len);
+    *n_out = k;
+    return MSIM_OK;
+}
+
+int msim_dbg_cmp_counts_diploid(const uint8_t *bases, uint64_t L, const msim_record *truth, uint64_t n_truth, const uint8_t *truth_pool,
+                                uint64_t truth_pool_len, const uint8_t *truth_gt, const msim_record *calls, uint64_t n_calls,
+                                const uint8_t *calls_pool, uint64_t calls_pool_len, const uint8_t *calls_gt, uint32_t flags,
+                                uint64_t *counts, uint64_t tallies[2], uint8_t *truth_flags, uint8_t *calls_flags) {
+    if ((!bases && L) || ((!truth || !truth_gt) && n_truth) || ((!calls || !calls_gt) && n_calls) || (!truth_pool && truth_pool_len) ||
+        (!calls_pool && calls_pool_len) || !counts || !tallies || (flags & ~(uint32_t)MSIM_CMP_EXACT))
+        return MSIM_ERR_ARG;
+    int rc;
+    if ((rc = dbg_table_ok("truth", truth, n_truth, false)) || (rc = dbg_table_ok("calls", calls, n_calls, false)) ||
+        (rc = dbg_gt_ok("truth", truth_gt, n_truth)) || (rc = dbg_gt_ok("calls", calls_gt, n_calls)))
+        return rc;
+    memset(counts, 0, (size_t)8 * MSIM_CMP_BINS * 6 * sizeof(uint64_t));
+    memset(tallies, 0, 2 * sizeof(uint64_t));
+    std::vector<uint8_t> fb((size_t)n_calls, 0);
+    unsigned long long a[cmp::DIP_COUNTERS] = {}, b[cmp::DIP_COUNTERS] = {};
+    const cmp::Table A{truth, n_truth, truth_pool, truth_pool_len}, B{calls, n_calls, calls_pool, calls_pool_len};
+    for (uint64_t i = 0; i < n_truth; i++) {
+        cmp::Span s;
+        const int64_t j = cmp::partner(bases, L, A, i, B, (flags & MSIM_CMP_EXACT) != 0, &s);
+        const uint8_t f = j >= 0 ? cmp::pair_flag(truth_gt[i], calls_gt[(size_t)j]) : (uint8_t)0;
+        if (truth_flags) truth_flags[i] = f;
+        if (j >= 0) fb[(size_t)j] = f;
+        a[3 * cmp::cell_of(cmp::rec_at(truth, i)) + (f == 1 ? 0 : f == 2 ? 1 : 2)]++;
+        if (s.stops & cmp::STOP_WINDOW) a[3 * cmp::CELLS]++;
+        if (s.stops & cmp::STOP_BASE) a[3 * cmp::CELLS + 1]++;
+    }
+    for (uint64_t i = 0; i < n_calls; i++) {
+        const uint8_t f = fb[(size_t)i];
+        b[3 * cmp::cell_of(cmp::rec_at(calls, i)) + (f == 1 ? 0 : f == 2 ? 1 : 2)]++;
+        if (calls_flags) calls_flags[i] = f;
+    }
+    dip_finish(a, b, counts, tallies);
     return MSIM_OK;
 }
 

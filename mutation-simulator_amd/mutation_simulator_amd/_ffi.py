@@ -185,6 +185,13 @@ SYMBOLS = [
     ("msim_cmp_timing", C.c_int, [_VP, C.POINTER(C.c_double)]),
     ("msim_dbg_cmp_counts", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64,
                                       C.c_uint32, _VP, _VP, _VP, _VP]),
+    ("msim_cmp_join", C.c_int, [_VP, C.c_int, C.c_int]),
+    ("msim_cmp_counts_diploid", C.c_int, [_VP, C.c_int, C.c_uint32, _VP, _VP]),
+    ("msim_cmp_fetch_diploid", C.c_int, [_VP, C.c_int, C.c_int, _U64P, _U64P, _VP, _VP, _VP, _VP]),
+    ("msim_cmp_join_timing", C.c_int, [_VP, C.POINTER(C.c_double)]),
+    ("msim_dbg_cmp_join", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, _VP, _U64P]),
+    ("msim_dbg_cmp_counts_diploid", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, C.c_uint64, _VP,
+                                              C.c_uint64, _VP, C.c_uint32, _VP, _VP, _VP, _VP]),
     ("msim_stats", C.c_int, [_VP, C.POINTER(Timing)]),
     ("msim_reset_stats", C.c_int, [_VP]),
 ]
@@ -192,6 +199,8 @@ CMP_EXACT = 1            # msim.h: MSIM_CMP_EXACT, the literal comparison
 CMP_BINS = 5             # msim.h: MSIM_CMP_BINS, the length bins of IN and DE (1, 2-5, 6-20, 21-50, 51 and above)
 CMP_PASS = 256           # msim.h: MSIM_CMP_PASS, the records one workgroup of the compare kernels takes per pass
 CMP_WINDOW = 65536       # msim.h: MSIM_CMP_WINDOW, the bases an indel's placements stay inside
+CMP_TRUTH, CMP_CALLS = 0, 1          # msim.h: MSIM_CMP_TRUTH, MSIM_CMP_CALLS, the sides of a diploid comparison
+CMP_JOIN_TILE = 1024     # msim.h: MSIM_CMP_JOIN_TILE, the records one workgroup of the diploid join's scan takes
 SPECTRUM_TILE = 4096     # msim.h: MSIM_SPECTRUM_TILE, the bases one workgroup of the spectrum sampler takes
 SBS_CHANNELS, SBS_TALLIES = 96, 8    # msim.h: MSIM_SBS_CHANNELS, MSIM_SBS_TALLIES
 SBS_PASS = 1024          # msim.h: MSIM_SBS_PASS, the records one workgroup of the profile kernel takes per pass
@@ -680,6 +689,40 @@ class Engine:
         """The compare kernels' milliseconds since ``reset_stats`` (HIP events)."""
         a = C.c_double()
         self._check(self.lib.msim_cmp_timing(self.h, C.byref(a)))
+        return a.value
+
+    def cmp_join(self, contig: int, side: int):
+        """The contig's held table (haplotype 1) and its current table (haplotype 2) joined into its diploid table of ``side``
+        (``CMP_TRUTH`` / ``CMP_CALLS``): distinct variants with a genotype byte each.  The held table is consumed."""
+        self._check(self.lib.msim_cmp_join(self.h, int(contig), int(side)), contig)
+
+    def cmp_counts_diploid(self, contig: int, exact: bool = False) -> tuple:
+        """The contig's truth diploid table scored against its calls one: (uint64[8, CMP_BINS, 6] -- truth matched, truth
+        genotype-mismatched, truth missed, calls matched, calls genotype-mismatched, calls extra; uint64[2] as ``cmp_counts``)."""
+        counts = np.zeros((8, CMP_BINS, 6), dtype=np.uint64)
+        tallies = np.zeros(2, dtype=np.uint64)
+        self._check(self.lib.msim_cmp_counts_diploid(self.h, int(contig), CMP_EXACT if exact else 0, _ptr(counts), _ptr(tallies)),
+                    contig)
+        return counts, tallies
+
+    def cmp_fetch_diploid(self, contig: int, side: int, flags: bool = True) -> tuple:
+        """(records, pool, genotype bytes, flag bytes) of one side's diploid table; the flags are those of the contig's last
+        ``cmp_counts_diploid`` (0 no partner, 1 matched, 2 matched with another dosage; None with ``flags=False``)."""
+        n, m = C.c_uint64(), C.c_uint64()
+        self._check(self.lib.msim_cmp_fetch_diploid(self.h, int(contig), int(side), C.byref(n), C.byref(m), None, None, None, None),
+                    contig)
+        recs = np.zeros(n.value, dtype=RECORD_DTYPE)
+        pool = np.zeros(m.value, dtype=np.uint8)
+        gt = np.zeros(n.value, dtype=np.uint8)
+        fl = np.zeros(n.value, dtype=np.uint8) if flags else None
+        self._check(self.lib.msim_cmp_fetch_diploid(self.h, int(contig), int(side), None, None, _ptr(recs), _ptr(pool), _ptr(gt),
+                                                    _ptr(fl) if flags else None), contig)
+        return recs, pool, gt, fl
+
+    def cmp_join_timing(self) -> float:
+        """The diploid join's milliseconds on the device since ``reset_stats`` (HIP events)."""
+        a = C.c_double()
+        self._check(self.lib.msim_cmp_join_timing(self.h, C.byref(a)))
         return a.value
 
     # test hooks (msim_dbg_*: exported, not part of include/msim.h)
@@ -1277,6 +1320,55 @@ def cmp_counts_host(bases, truth, truth_pool, calls, calls_pool, exact: bool = F
     rc = lib.msim_dbg_cmp_counts(ptr(bases), len(bases), ptr(truth), len(truth), ptr(truth_pool), len(truth_pool), ptr(calls),
                                  len(calls), ptr(calls_pool), len(calls_pool), CMP_EXACT if exact else 0, _ptr(counts),
                                  _ptr(tallies), ptr(fa), ptr(fb))
+    if rc != OK:
+        raise _host_error(rc)
+    return counts, tallies, fa, fb
+
+
+def _opt_ptr(a):
+    return C.c_void_p(a.ctypes.data) if len(a) else None
+
+
+def cmp_join_host(h1, pool1, h2, pool2) -> tuple:
+    """``msim_dbg_cmp_join``: the diploid table ``Engine.cmp_join`` makes of two haplotype tables -- (records, pool, genotype
+    bytes) -- by a sequential host merge.  No context, no GPU."""
+    lib = load()
+    h1 = np.ascontiguousarray(h1, dtype=RECORD_DTYPE)
+    h2 = np.ascontiguousarray(h2, dtype=RECORD_DTYPE)
+    pool1 = np.ascontiguousarray(pool1, dtype=np.uint8)
+    pool2 = np.ascontiguousarray(pool2, dtype=np.uint8)
+    out = np.zeros(len(h1) + len(h2), dtype=RECORD_DTYPE)
+    gt = np.zeros(len(h1) + len(h2), dtype=np.uint8)
+    pool = np.zeros(len(pool1) + len(pool2), dtype=np.uint8)
+    n = C.c_uint64()
+    rc = lib.msim_dbg_cmp_join(_opt_ptr(h1), len(h1), _opt_ptr(pool1), len(pool1), _opt_ptr(h2), len(h2), _opt_ptr(pool2), len(pool2),
+                               _opt_ptr(out), _opt_ptr(pool), _opt_ptr(gt), C.byref(n))
+    if rc != OK:
+        raise _host_error(rc)
+    return out[:n.value].copy(), pool, gt[:n.value].copy()
+
+
+def cmp_counts_diploid_host(bases, truth, truth_pool, truth_gt, calls, calls_pool, calls_gt, exact: bool = False) -> tuple:
+    """``msim_dbg_cmp_counts_diploid``: what ``Engine.cmp_counts_diploid`` returns and the two flag arrays of
+    ``Engine.cmp_fetch_diploid`` -- (counts, tallies, truth flags, calls flags) -- by a sequential host loop over two diploid
+    tables with a genotype byte per record.  No context, no GPU."""
+    lib = load()
+    bases = _as_u8(bases)
+    truth = np.ascontiguousarray(truth, dtype=RECORD_DTYPE)
+    calls = np.ascontiguousarray(calls, dtype=RECORD_DTYPE)
+    truth_pool = np.ascontiguousarray(truth_pool, dtype=np.uint8)
+    calls_pool = np.ascontiguousarray(calls_pool, dtype=np.uint8)
+    truth_gt = np.ascontiguousarray(truth_gt, dtype=np.uint8)
+    calls_gt = np.ascontiguousarray(calls_gt, dtype=np.uint8)
+    assert len(truth_gt) == len(truth) and len(calls_gt) == len(calls)
+    counts = np.zeros((8, CMP_BINS, 6), dtype=np.uint64)
+    tallies = np.zeros(2, dtype=np.uint64)
+    fa = np.zeros(len(truth), dtype=np.uint8)
+    fb = np.zeros(len(calls), dtype=np.uint8)
+    rc = lib.msim_dbg_cmp_counts_diploid(_opt_ptr(bases), len(bases), _opt_ptr(truth), len(truth), _opt_ptr(truth_pool),
+                                         len(truth_pool), _opt_ptr(truth_gt), _opt_ptr(calls), len(calls), _opt_ptr(calls_pool),
+                                         len(calls_pool), _opt_ptr(calls_gt), CMP_EXACT if exact else 0, _ptr(counts), _ptr(tallies),
+                                         _opt_ptr(fa), _opt_ptr(fb))
     if rc != OK:
         raise _host_error(rc)
     return counts, tallies, fa, fb

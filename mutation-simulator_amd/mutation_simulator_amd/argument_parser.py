@@ -7,8 +7,9 @@ a default: ``--seed``, ``--device``, ``--gpus``, ``--rng``, ``--bgzip``, ``--cha
 the SBS-96 spectrum of a VCF's SNPs against the reference, counted on the GPU; it writes ``<outbase>_ms.sbs96.tsv``, a file
 ``--spectrum`` reads; ``profile_refusal`` words what it does not cover), and the ``compare`` sub-command (``compare.py``: a calls
 VCF scored against a truth VCF on the GPU, indels matched up to their placement inside a repeat; it writes
-``<outbase>_ms.compare.tsv`` and, with ``--list``, ``<outbase>_ms.compare.records.tsv``; ``compare_refusal`` words what it does
-not cover).
+``<outbase>_ms.compare.tsv`` and, with ``--list``, ``<outbase>_ms.compare.records.tsv``; ``--diploid`` joins both haplotypes of each
+side and scores genotypes by dosage -- a ``GT`` column, ``GT`` lines in the records file; it is a usage error together with
+``--haplotype`` or ``--truth-haplotype``; ``compare_refusal`` words what it does not cover).
 
 ``--ploidy 2 [--het F]`` (``args`` / ``rmt``) writes two haplotype Fastas, ``<outbase>_ms_h1<suffix>`` and ``<outbase>_ms_h2<suffix>``
 (``args.outfasta_h1`` / ``outfasta_h2``; ``<outbase>_ms<suffix>`` is not written), one phased ``<outbase>_ms.vcf`` and, with ``--chain``,
@@ -206,6 +207,10 @@ def build_parser() -> ArgumentParser:
                        help="The sample column of the calls VCF to follow. Default = the first one")
     p_cmp.add_argument("--haplotype", type=int, default=None, metavar="N",
                        help="Which allele of the calls genotype to score, counted from 1. Default = 1")
+    p_cmp.add_argument("--diploid", action="store_true", default=False,
+                       help="Score genotypes against a diploid truth: both haplotypes of each side are joined into distinct "
+                            "variants with a dosage (0/1 or 1/1, phase ignored; a haploid 1 counts as 1/1); a variant found with "
+                            "the wrong dosage is reported as GT. Cannot be combined with --truth-haplotype or --haplotype")
     p_cmp.add_argument("--exact", action="store_true", default=False,
                        help="Compare positions literally: an indel placed elsewhere in its repeat counts as missed and as extra")
     p_cmp.add_argument("--per-contig", action="store_true", default=False, dest="per_contig",
@@ -317,6 +322,8 @@ def get_args(argv=None) -> Namespace:
     if args.mode == "compare":
         if any(h is not None and h < 1 for h in (args.haplotype, args.truth_haplotype)):
             parser.error("--haplotype and --truth-haplotype count from 1")
+        if args.diploid and (args.haplotype is not None or args.truth_haplotype is not None):
+            parser.error("--diploid scores both haplotypes of each side: --haplotype and --truth-haplotype do not apply")
     if args.quiet:
         args.ignore_warnings = True
         args.no_progress = True

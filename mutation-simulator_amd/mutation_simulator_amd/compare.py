@@ -12,13 +12,19 @@ record of the same type and length that is a shifted placement of it -- anywhere
 stands in, an insertion's bytes rotating with it -- as long as both lie in the same window of 65 536 bases and no base outside
 A, C, G, T is stepped over; ``--exact`` compares positions literally.  Inside one class of equivalent records the i-th of the
 truth matches the i-th of the calls.  Counts come per record type and, for insertions and deletions, per length bin.
+
+``--diploid`` scores genotypes: per side haplotype 1 is planned and held, haplotype 2 is planned from the same loaded text, and
+``msim_cmp_join`` joins the two tables per contig into one table of distinct variants with a dosage each (``0/1`` or ``1/1``; phase
+is ignored, a haploid ``1`` counts as ``1/1``).  ``msim_cmp_counts_diploid`` matches the truth's table against the calls' by the
+same rules and compares the dosages: the table gains a ``GT`` column -- pairs found with the wrong genotype, which count in ``FN``
+and in ``FP`` as hap.py reports them.  The renderers of the haploid files are untouched; the diploid ones stand beside them.
 """
 from __future__ import annotations
 
 import numpy as np
 
 from . import _ffi
-from .vcf_replay import VcfReplayError, load_vcf_text, plan_all, resident_genome
+from .vcf_replay import VcfReplayError, load_vcf_text, plan_all, plan_loaded, resident_genome
 
 TYPE_NAMES = (None, "SN", "IN", "DE", "DU", "IV", "TL", "TLI")            # msim.h: MSIM_SN .. MSIM_TLI
 BIN_NAMES = ("1", "2-5", "6-20", "21-50", "51+")                          # msim_cmp_counts: the length bins of IN and DE
@@ -71,6 +77,60 @@ def record_rows(kind: str, contig: str, recs, flags) -> list:
     return out
 
 
+# ---- --diploid: counts[..., 6] = truth matched / genotype-mismatched / missed, calls matched / genotype-mismatched / extra -------
+HEADER_DIPLOID = ("type", "length", "truth", "calls", "TP", "FN", "FP", "GT", "recall", "precision")
+GT_NAMES = (".", "0/1", "1/1")                                            # by dosage
+
+
+def row_cells_diploid(kind: str, length: str, v) -> list:
+    """One row from the six values of a cell: a genotype mismatch counts in FN and in FP, and once in GT."""
+    tm, tg, miss, cm, cg, extra = (int(x) for x in v)
+    fn, fp = tg + miss, cg + extra
+    return [kind, length, str(tm + fn), str(cm + fp), str(tm), str(fn), str(fp), str(tg), ratio(tm, tm + fn), ratio(cm, cm + fp)]
+
+
+def render_block_diploid(counts) -> list:
+    """The rows of one ``counts[8][CMP_BINS][6]``: a row per type and length bin, then ALL."""
+    counts = np.asarray(counts, dtype=np.uint64)
+    lines = ["\t".join(HEADER_DIPLOID)]
+    for t, b in ROWS:
+        lines.append("\t".join(row_cells_diploid(TYPE_NAMES[t], BIN_NAMES[b] if t in (2, 3) else ".", counts[t, b])))
+    lines.append("\t".join(row_cells_diploid("ALL", ".", counts.reshape(-1, 6).sum(axis=0, dtype=np.uint64))))
+    return lines
+
+
+def render_diploid(notes, counts, names=None) -> str:
+    """``render`` for ``counts[contigs][8][CMP_BINS][6]``."""
+    counts = np.asarray(counts, dtype=np.uint64)
+    lines = [f"# {note}" for note in notes]
+    lines += render_block_diploid(counts.sum(axis=0, dtype=np.uint64))
+    for i, name in enumerate(names or ()):
+        lines.append(f"# contig {name}")
+        lines += render_block_diploid(counts[i])
+    return "\n".join(lines) + "\n"
+
+
+def dosage(gt) -> int:
+    return (int(gt) & 1) + ((int(gt) >> 1) & 1)
+
+
+def record_rows_diploid(contig: str, truth, truth_gt, truth_flags, calls, calls_gt, calls_flags) -> list:
+    """The lines of ``--list`` for one contig's two diploid tables: kind, contig, 1-based position, type, length, truth genotype,
+    calls genotype (``.`` where that side has no record).  The truth's records in table order -- ``FN`` where the flag byte is 0,
+    ``GT`` where it is 2, written once, at the truth record's position: its partner's dosage is the other one --, then the calls'
+    ``FP`` (flag byte 0)."""
+    def line(kind, r, a, b):
+        return "\t".join([kind, contig, str(int(r["pos"]) + 1), TYPE_NAMES[int(r["type"])], str(int(r["stop"]) - int(r["pos"]) + 1),
+                          GT_NAMES[a], GT_NAMES[b]])
+    out = []
+    for k in np.flatnonzero(np.asarray(truth_flags) != 1):
+        d = dosage(truth_gt[k])
+        out.append(line("FN", truth[k], d, 0) if truth_flags[k] == 0 else line("GT", truth[k], d, 3 - d))
+    for k in np.flatnonzero(np.asarray(calls_flags) == 0):
+        out.append(line("FP", calls[k], 0, dosage(calls_gt[k])))
+    return out
+
+
 class Compare:
     """Scores one calls VCF against one truth VCF on the GPU and writes ``*_ms.compare.tsv``."""
 
@@ -81,7 +141,7 @@ class Compare:
         self._engine = engine
         self._own_engine = engine is None
         self.stats: dict = {}
-        self.counts = None           # uint64[contigs, 8, CMP_BINS, 4] of the last run
+        self.counts = None           # uint64[contigs, 8, CMP_BINS, 4] of the last run ([..., 6] with --diploid)
         self.tallies = None          # uint64[contigs, 2]
 
     def _plan(self, eng, side: str, path, names, cids, sample, haplotype):
@@ -95,12 +155,59 @@ class Compare:
         load_ms, plan_ms = eng.vcf_timing()
         return int(text.shape[0]), load_ms, plan_ms
 
+    def _plan_diploid(self, eng, side: str, side_id: int, path, names, cids, sample):
+        """One file's two haplotypes onto the contigs, joined into the side's diploid tables: haplotype 1 planned and held,
+        haplotype 2 planned from the same loaded text, every contig joined."""
+        text = load_vcf_text(path, eng)
+        try:
+            plan_all(eng, text, names, cids, (sample, 1))
+            for cid in cids:
+                eng.cmp_hold(cid)
+            plan_loaded(eng, text, names, cids, (sample, 2))
+        except (VcfReplayError, ValueError) as e:
+            msg = str(e)
+            raise CompareError(f"{side} {msg}" if msg.startswith("VCF line") else f"{side} VCF: {msg}") from None
+        for cid in cids:
+            eng.cmp_join(cid, side_id)
+        load_ms, plan_ms = eng.vcf_timing()
+        eng.vcf_release()
+        return int(text.shape[0]), load_ms, plan_ms
+
+    def _run_diploid(self, eng, names, cids):
+        args = self._args
+        join0 = eng.cmp_join_timing()
+        truth = self._plan_diploid(eng, "truth", _ffi.CMP_TRUTH, args.truthfile, names, cids, getattr(args, "truth_sample", None))
+        calls = self._plan_diploid(eng, "calls", _ffi.CMP_CALLS, args.callsfile, names, cids, getattr(args, "sample", None))
+        exact = bool(getattr(args, "exact", False))
+        cmp0 = eng.cmp_timing()
+        n = len(cids)
+        self.counts = np.zeros((n, 8, _ffi.CMP_BINS, 6), dtype=np.uint64)
+        self.tallies = np.zeros((n, 2), dtype=np.uint64)
+        listed = []
+        for i, cid in enumerate(cids):
+            self.counts[i], self.tallies[i] = eng.cmp_counts_diploid(cid, exact)
+            if getattr(args, "list_records", False):
+                a, _, ga, fa_flags = eng.cmp_fetch_diploid(cid, _ffi.CMP_TRUTH)
+                b, _, gb, fb_flags = eng.cmp_fetch_diploid(cid, _ffi.CMP_CALLS)
+                listed += record_rows_diploid(names[i], a, ga, fa_flags, b, gb, fb_flags)
+        self.stats = {"truth_vcf_bytes": truth[0], "calls_vcf_bytes": calls[0], "vcf_load_kernel_ms": truth[1] + calls[1],
+                      "vcf_plan_kernel_ms": truth[2] + calls[2], "cmp_kernel_ms": round(eng.cmp_timing() - cmp0, 4),
+                      "cmp_join_kernel_ms": round(eng.cmp_join_timing() - join0, 4)}
+        eng.cmp_release()
+        return listed
+
     def run(self):
         fa, args = self._fasta, self._args
         if self._engine is None:
             self._engine = _ffi.Engine(self._device)
         eng = self._engine
         _, names, cids = resident_genome(eng, fa, "compare")
+        if getattr(args, "diploid", False):
+            listed = self._run_diploid(eng, names, cids)
+            args.outcompare.write_text(self.render(names))
+            if getattr(args, "list_records", False):
+                args.outcompare_records.write_text("".join(line + "\n" for line in listed))
+            return
         truth = self._plan(eng, "truth", args.truthfile, names, cids, getattr(args, "truth_sample", None),
                            getattr(args, "truth_haplotype", None))
         for cid in cids:
@@ -132,8 +239,10 @@ class Compare:
         args = self._args
         tallies = self.tallies.sum(axis=0, dtype=np.uint64)
 
+        diploid = bool(getattr(args, "diploid", False))
+
         def followed(sample, haplotype):
-            return f"sample {sample if sample is not None else '(first)'} haplotype {haplotype or 1}"
+            return f"sample {sample if sample is not None else '(first)'} " + ("both haplotypes" if diploid else f"haplotype {haplotype or 1}")
         notes = [f"compare: calls {args.callsfile.name} against truth {args.truthfile.name} on "
                  f"{getattr(args, 'genome_name', args.infile.name)} ({len(names)} contigs)",
                  f"truth: {followed(getattr(args, 'truth_sample', None), getattr(args, 'truth_haplotype', None))}",
@@ -142,6 +251,9 @@ class Compare:
                                  else "normalised (an indel matches any placement inside its repeat)"),
                  f"truth indels whose placements end at a window edge: {int(tallies[0])}",
                  f"truth indels whose placements end at a base outside ACGT: {int(tallies[1])}"]
+        if diploid:
+            notes.insert(3, "genotypes: diploid, unphased (dosage compared; a haploid 1 counts as 1/1)")
+            return render_diploid(notes, self.counts, names if getattr(args, "per_contig", False) else None)
         return render(notes, self.counts, names if getattr(args, "per_contig", False) else None)
 
     def close(self):

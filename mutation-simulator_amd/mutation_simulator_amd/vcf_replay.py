@@ -84,6 +84,12 @@ def plan_all(engine, text: np.ndarray, names, contig_ids, consensus=None) -> Non
     VcfReplayError, "VCF line N: ...").  Contigs without lines get an empty table.  Nothing has been rewritten when this raises.
     ``consensus``: None for the simulator's dialect, or (sample name or None, haplotype) for the general grammar."""
     engine.vcf_load(text)
+    plan_loaded(engine, text, names, contig_ids, consensus)
+
+
+def plan_loaded(engine, text: np.ndarray, names, contig_ids, consensus=None) -> None:
+    """``plan_all`` behind its ``vcf_load``: plan every contig from the text the context already holds, under the grammar and
+    haplotype selected here -- so one loaded file can be planned once per haplotype (``compare --diploid``)."""
     groups = engine.vcf_groups()
     if consensus is not None:
         sample, haplotype = consensus
