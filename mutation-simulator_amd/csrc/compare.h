@@ -29,10 +29,18 @@ namespace cmp {
 constexpr uint32_t WINDOW_SHIFT = 16;                      // MSIM_CMP_WINDOW = 1 << 16
 constexpr uint32_t STOP_WINDOW = 1u, STOP_BASE = 2u;       // why a walk ended (Span::stops): msim_cmp_counts' two tallies
 constexpr uint32_t CELLS = 15;                             // (type, bin) pairs that exist: 7 types in bin 0, IN and DE in bins 1..4
-constexpr uint32_t COUNTERS = 2 * CELLS + 2;               // per cell matched / unmatched, then the two tallies
-constexpr uint32_t DIP_COUNTERS = 3 * CELLS + 2;           // diploid: per cell matched / genotype-mismatched / unmatched, the tallies
-constexpr uint32_t DIP_BINS = 48;                          // ... rounded up to an even number of lane-private bins
 static_assert(MSIM_CMP_BINS == 5, "the cells are laid out for five length bins");
+
+// A comparison's counters, by the OUTCOMES a record of a cell can have: 2 (haploid: matched / unmatched) or 3 (diploid: matched /
+// genotype-mismatched / unmatched).  A record's flag byte names its outcome: 1 matched, 2 (diploid only) matched with another
+// dosage, 0 no partner -- the last outcome.
+template <int OUTCOMES>
+struct Score {
+    static_assert(OUTCOMES == 2 || OUTCOMES == 3, "haploid or diploid");
+    static constexpr uint32_t TALLIES = OUTCOMES * CELLS;  // behind the cells' counters: the two tallies
+    static constexpr uint32_t COUNTERS = TALLIES + 2;
+    static constexpr uint32_t BINS = (COUNTERS + 1) & ~1u; // ... rounded up to an even number of lane-private bins: 32, 48
+};
 
 struct Rec { uint32_t pos, stop, extra, type, aux; };
 struct Table { const msim_record *recs; uint64_t n; const uint8_t *pool; uint64_t pool_len; };
@@ -62,6 +70,9 @@ MSIM_FHD inline void cell_index(uint32_t cell, uint32_t *type, uint32_t *bin) {
     else if (cell < 11) { *type = MSIM_IN; *bin = cell - 6; }
     else { *type = MSIM_DE; *bin = cell - 10; }
 }
+// the counter of a record with that flag byte
+template <int OUTCOMES>
+MSIM_FHD inline uint32_t counter_of(const Rec &r, uint32_t flag) { return OUTCOMES * cell_of(r) + (flag ? flag - 1u : OUTCOMES - 1u); }
 
 // an indel the walk is written for: inside the contig, an insert inside its pool (what table_check guarantees, checked again
 // because nothing else keeps a read inside its buffer)

@@ -5,10 +5,12 @@
 //            scan of A to the left, a binary search of B for the interval's start, a scan of B for the record of that rank;
 //            the lane stores its own flag byte and its partner's (no two lanes share a partner) and counts the record
 //   tally    k_cmp_tally: one lane per B record, counted by its flag byte
-// Both kernels count into 32 lane-private bins (15 cells x matched / unmatched, two tallies: lane_hist.h).
+// Both kernels are templates over the outcomes a record of a cell can have (compare.h: Score) and count into lane-private bins
+// (lane_hist.h): 2, a haploid comparison -- 15 cells x matched / unmatched, two tallies: 32 bins; 3, a diploid one -- 15 cells x
+// matched / genotype-mismatched / unmatched, two tallies, one spare: 48 bins.
 // compare --diploid (msim_cmp_join, msim_cmp_counts_diploid): a side's two haplotype tables are JOINED into one diploid table with a
 // genotype byte per record (k_join_flag, k_scan_u32, k_join_put2, k_join_put1), and the truth's diploid table is scored against
-// the calls' by genotype-aware siblings of the two kernels (k_dip_match, k_dip_tally: 48 bins).
+// the calls' by the same two kernels, a matched pair's flag byte saying whether the two dosages agree.
 #include <algorithm>
 #include <cstring>
 #include <string>
@@ -64,22 +66,31 @@ constexpr uint32_t CMP_PASS = LANES;                       // records of a workg
 static_assert(CMP_PASS == MSIM_CMP_PASS, "msim.h and compare.hip must agree on the pass");
 static_assert((1u << cmp::WINDOW_SHIFT) == MSIM_CMP_WINDOW, "msim.h and compare.h must agree on the window");
 constexpr unsigned CMP_MAX_BLOCKS = 2048;                  // more passes than that stride: eight workgroups a CU (16 KB of LDS each)
-constexpr int CMP_BINS = (int)cmp::COUNTERS;
-constexpr size_t OUT_WORDS = (size_t)HIST_SLOTS * 2 * CMP_BINS;
 static_assert(sizeof(msim_record) == sizeof(uint4), "a record is one 16-byte load");
 
-// 32 lane-private bins, summed in two halves into the workgroup's slot of `out`: 2 x CMP_BINS words a slot, A's counters in
-// front of B's (lane_hist.h).  A table has fewer than 2^31 records, so fewer than 2^23 passes; beyond CMP_MAX_BLOCKS passes the
-// grid strides, a workgroup takes at most 4096 of them and a lane adds at most once per counter and pass: 16 bits hold it.
-using CmpHist = LaneHist<CMP_BINS, LANES, 2>;
-__device__ __forceinline__ unsigned long long *slot_of(unsigned long long *out) { return out + (blockIdx.x & (HIST_SLOTS - 1)) * 2 * CMP_BINS; }
+// Lane-private bins, summed in two halves into the workgroup's slot of `out`: 2 x BINS words a slot, A's counters in front of
+// B's (lane_hist.h) -- 16 KB of LDS a workgroup and eight workgroups a CU with two outcomes, 24 KB and six with three.  A table
+// has fewer than 2^31 records, so fewer than 2^23 passes; beyond CMP_MAX_BLOCKS passes the grid strides, a workgroup takes at
+// most 4096 of them and a lane adds at most once per counter and pass: 16 bits hold it, in either instantiation.
+template <int OUTCOMES> using CmpHist = LaneHist<(int)cmp::Score<OUTCOMES>::BINS, LANES, 2>;
+template <int OUTCOMES> constexpr size_t OUT_WORDS = (size_t)HIST_SLOTS * 2 * cmp::Score<OUTCOMES>::BINS;
+template <int OUTCOMES>
+__device__ __forceinline__ unsigned long long *slot_of(unsigned long long *out) {
+    return out + (blockIdx.x & (HIST_SLOTS - 1)) * 2 * cmp::Score<OUTCOMES>::BINS;
+}
 
-// flag_b was zeroed before the launch.  Every index below is checked against its table's size; the bases are read inside
-// [0, L) only, the pools inside their lengths (compare.h: walkable, same).
+// the two tables' genotype bytes, which a haploid comparison neither has nor passes to its kernel
+template <int OUTCOMES> struct Gt { const uint8_t *a, *b; };
+template <> struct Gt<2> { Gt(const uint8_t *, const uint8_t *) {} };
+
+// flag_b was zeroed before the launch.  Every index below is checked against its table's size -- a genotype byte is read at
+// such an index --; the bases are read inside [0, L) only, the pools inside their lengths (compare.h: walkable, same).
+template <int OUTCOMES>
 __global__ __launch_bounds__(LANES) void k_cmp_match(const uint8_t *__restrict__ g, uint64_t L, cmp::Table A, cmp::Table B, uint32_t exact,
                                                      uint64_t n_pass, uint8_t *__restrict__ flag_a, uint8_t *__restrict__ flag_b,
-                                                     unsigned long long *__restrict__ out) {
-    __shared__ CmpHist hist;
+                                                     unsigned long long *__restrict__ out, Gt<OUTCOMES> gt) {
+    using S = cmp::Score<OUTCOMES>;
+    __shared__ CmpHist<OUTCOMES> hist;
     hist.zero();
     for (uint64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
         const uint64_t i = pass * CMP_PASS + threadIdx.x;
@@ -88,75 +99,32 @@ __global__ __launch_bounds__(LANES) void k_cmp_match(const uint8_t *__restrict__
         if (!cmp::known_type(a.type)) { flag_a[i] = 0; continue; }
         cmp::Span s;
         const int64_t j = cmp::partner(g, L, A, i, B, exact != 0, &s);
-        flag_a[i] = j >= 0 ? 1 : 0;
-        if (j >= 0 && (uint64_t)j < B.n) flag_b[j] = 1;    // a plain byte store: this lane is the only one with this partner
-        hist.add(2 * cmp::cell_of(a) + (j >= 0 ? 0u : 1u), 1u);
-        if (s.stops & cmp::STOP_WINDOW) hist.add(2 * cmp::CELLS, 1u);
-        if (s.stops & cmp::STOP_BASE) hist.add(2 * cmp::CELLS + 1, 1u);
+        uint8_t f = 0;
+        if (j >= 0 && (uint64_t)j < B.n) {
+            if constexpr (OUTCOMES == 3) f = cmp::pair_flag(gt.a[i], gt.b[j]);
+            else f = 1;
+            flag_b[j] = f;                                 // a plain byte store: this lane is the only one with this partner
+        }
+        flag_a[i] = f;
+        hist.add(cmp::counter_of<OUTCOMES>(a, f), 1u);
+        if (s.stops & cmp::STOP_WINDOW) hist.add(S::TALLIES, 1u);
+        if (s.stops & cmp::STOP_BASE) hist.add(S::TALLIES + 1, 1u);
     }
-    hist.flush(slot_of(out));
+    hist.flush(slot_of<OUTCOMES>(out));
 }
 
+template <int OUTCOMES>
 __global__ __launch_bounds__(LANES) void k_cmp_tally(const msim_record *__restrict__ recs, uint64_t n_rec, uint64_t n_pass,
                                                      const uint8_t *__restrict__ flag, unsigned long long *__restrict__ out) {
-    __shared__ CmpHist hist;
+    __shared__ CmpHist<OUTCOMES> hist;
     hist.zero();
     for (uint64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
         const uint64_t i = pass * CMP_PASS + threadIdx.x;
         if (i >= n_rec) continue;
         const cmp::Rec b = cmp::rec_at(recs, i);
-        if (cmp::known_type(b.type)) hist.add(2 * cmp::cell_of(b) + (flag[i] ? 0u : 1u), 1u);
+        if (cmp::known_type(b.type)) hist.add(cmp::counter_of<OUTCOMES>(b, flag[i]), 1u);
     }
-    hist.flush(slot_of(out));
-}
-
-// ---- diploid: the same two launches over two diploid tables, a genotype byte beside every record --------------------------------
-// 48 lane-private bins (15 cells x matched / genotype-mismatched / unmatched, two tallies, one spare): 24 KB of LDS a workgroup,
-// six workgroups a CU.  The 16-bit argument is CmpHist's: the same grid cap, at most 4096 passes a workgroup, one add per
-// counter, lane and pass.
-constexpr int DIP_BINS = (int)cmp::DIP_BINS;
-static_assert(DIP_BINS % 2 == 0 && DIP_BINS >= (int)cmp::DIP_COUNTERS, "every diploid counter has a bin");
-constexpr size_t DIP_OUT_WORDS = (size_t)HIST_SLOTS * 2 * DIP_BINS;
-using DipHist = LaneHist<DIP_BINS, LANES, 2>;
-__device__ __forceinline__ unsigned long long *dip_slot_of(unsigned long long *out) { return out + (blockIdx.x & (HIST_SLOTS - 1)) * 2 * DIP_BINS; }
-__device__ __forceinline__ uint32_t dip_counter(const cmp::Rec &r, uint32_t flag) { return 3 * cmp::cell_of(r) + (flag == 1 ? 0u : flag == 2 ? 1u : 2u); }
-
-// flag_b was zeroed before the launch.  Indices and reads are checked as in k_cmp_match; a genotype byte is read at an index
-// its table's size has been checked against.
-__global__ __launch_bounds__(LANES) void k_dip_match(const uint8_t *__restrict__ g, uint64_t L, cmp::Table A, cmp::Table B,
-                                                     const uint8_t *__restrict__ gt_a, const uint8_t *__restrict__ gt_b, uint32_t exact,
-                                                     uint64_t n_pass, uint8_t *__restrict__ flag_a, uint8_t *__restrict__ flag_b,
-                                                     unsigned long long *__restrict__ out) {
-    __shared__ DipHist hist;
-    hist.zero();
-    for (uint64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
-        const uint64_t i = pass * CMP_PASS + threadIdx.x;
-        if (i >= A.n) continue;
-        const cmp::Rec a = cmp::rec_at(A.recs, i);
-        if (!cmp::known_type(a.type)) { flag_a[i] = 0; continue; }
-        cmp::Span s;
-        const int64_t j = cmp::partner(g, L, A, i, B, exact != 0, &s);
-        const uint8_t f = (j >= 0 && (uint64_t)j < B.n) ? cmp::pair_flag(gt_a[i], gt_b[j]) : (uint8_t)0;
-        flag_a[i] = f;
-        if (f) flag_b[j] = f;                              // a plain byte store: this lane is the only one with this partner
-        hist.add(dip_counter(a, f), 1u);
-        if (s.stops & cmp::STOP_WINDOW) hist.add(3 * cmp::CELLS, 1u);
-        if (s.stops & cmp::STOP_BASE) hist.add(3 * cmp::CELLS + 1, 1u);
-    }
-    hist.flush(dip_slot_of(out));
-}
-
-__global__ __launch_bounds__(LANES) void k_dip_tally(const msim_record *__restrict__ recs, uint64_t n_rec, uint64_t n_pass,
-                                                     const uint8_t *__restrict__ flag, unsigned long long *__restrict__ out) {
-    __shared__ DipHist hist;
-    hist.zero();
-    for (uint64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
-        const uint64_t i = pass * CMP_PASS + threadIdx.x;
-        if (i >= n_rec) continue;
-        const cmp::Rec b = cmp::rec_at(recs, i);
-        if (cmp::known_type(b.type)) hist.add(dip_counter(b, flag[i]), 1u);
-    }
-    hist.flush(dip_slot_of(out));
+    hist.flush(slot_of<OUTCOMES>(out));
 }
 
 // ---- the join: haplotype 1's table (H1) and haplotype 2's (H2) into one diploid table U ------------------------------------------
@@ -258,25 +226,26 @@ __global__ __launch_bounds__(LANES) void k_join_put1(cmp::Table H1, cmp::Table H
     join_store(U, gt, cap, i + k - before, v, both ? 3 : 1);
 }
 
-// counters[0]: A's (matched / missed per cell, the two tallies), counters[1]: B's (matched / extra per cell)
-void cmp_finish(const unsigned long long *a, const unsigned long long *b, uint64_t *counts, uint64_t tallies[2]) {
+// a[]: the truth's counters (per cell its outcomes -- matched / missed, or matched / genotype-mismatched / missed --, the two
+// tallies), b[]: the calls' (the last outcome: extra)
+template <int OUTCOMES>
+void finish(const unsigned long long *a, const unsigned long long *b, uint64_t *counts, uint64_t tallies[2]) {
     for (uint32_t cell = 0; cell < cmp::CELLS; cell++) {
         uint32_t type, bin;
         cmp::cell_index(cell, &type, &bin);
-        uint64_t *dst = counts + ((size_t)type * MSIM_CMP_BINS + bin) * 4;
-        dst[0] += a[2 * cell]; dst[1] += a[2 * cell + 1];
-        dst[2] += b[2 * cell]; dst[3] += b[2 * cell + 1];
+        uint64_t *dst = counts + ((size_t)type * MSIM_CMP_BINS + bin) * 2 * OUTCOMES;
+        for (int k = 0; k < OUTCOMES; k++) { dst[k] += a[OUTCOMES * cell + k]; dst[OUTCOMES + k] += b[OUTCOMES * cell + k]; }
     }
-    tallies[0] += a[2 * cmp::CELLS];
-    tallies[1] += a[2 * cmp::CELLS + 1];
+    tallies[0] += a[cmp::Score<OUTCOMES>::TALLIES];
+    tallies[1] += a[cmp::Score<OUTCOMES>::TALLIES + 1];
 }
 
 int state_of(Ctx *c, CompareState **out) {
     if (!c->compare) {
         CompareState *S = new CompareState;
         c->compare = S;
-        MSIM_HIP(c, dev_alloc(S->d_out, DIP_OUT_WORDS * sizeof(unsigned long long)));   // (the larger of the two layouts)
-        MSIM_HIP(c, pin_alloc(S->h_out, DIP_OUT_WORDS * sizeof(unsigned long long)));
+        MSIM_HIP(c, dev_alloc(S->d_out, OUT_WORDS<3> * sizeof(unsigned long long)));   // (the larger of the two layouts)
+        MSIM_HIP(c, pin_alloc(S->h_out, OUT_WORDS<3> * sizeof(unsigned long long)));
         MSIM_HIP(c, S->tm.create());
     }
     *out = c->compare;
@@ -289,53 +258,73 @@ Held *held_of(Ctx *c, int contig) {
     return &S->held[(size_t)contig];
 }
 
-int counts_device(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32_t flags, uint64_t *counts, uint64_t tallies[2]) {
+// What a call on a contig's held table begins with: the planned contig on the device, the held table, the state -- refused in
+// this order.  own_refusal: what the caller found wrong with an argument of its own, judged behind the contig.
+int held_contig(Ctx *c, int contig, Contig **g, Held **h, CompareState **S, const char *own_refusal = nullptr) {
+    const int rc = ctx_device_contig(c, contig, true, g);
+    if (rc) return rc;
+    if (own_refusal) return fail(c, MSIM_ERR_ARG, own_refusal);
+    if (!(*h = held_of(c, contig))) return fail(c, MSIM_ERR_ARG, "contig has no held table (msim_cmp_hold)");
+    return state_of(c, S);
+}
+
+// one side of a comparison: its table, its genotype bytes (a haploid side: none), its flag bytes (one per record)
+struct Side { cmp::Table t; const uint8_t *gt; uint8_t *flag; };
+
+// The two launches of a comparison on contig g, A against B: b's flags zeroed, a's records matched, b's tallied, the counters
+// fetched and summed into counts and tallies.
+template <int OUTCOMES>
+int counts_device(Ctx *c, CompareState *S, const Contig &g, const Side &a, const Side &b, uint32_t flags, uint64_t *counts, uint64_t tallies[2]) {
+    constexpr size_t BINS = cmp::Score<OUTCOMES>::BINS, OUT_BYTES = OUT_WORDS<OUTCOMES> * sizeof(unsigned long long);
+    if (!a.t.n && !b.t.n) return MSIM_OK;
+    const uint64_t pass_a = (a.t.n + CMP_PASS - 1) / CMP_PASS, pass_b = (b.t.n + CMP_PASS - 1) / CMP_PASS;
+    MSIM_HIP(c, hipMemsetAsync(S->d_out.p(), 0, OUT_BYTES, c->stream));
+    MSIM_HIP(c, S->tm.begin(c->stream));
+    if (b.t.n) MSIM_HIP(c, hipMemsetAsync(b.flag, 0, (size_t)b.t.n, c->stream));
+    if (a.t.n) {
+        hipLaunchKernelGGL(k_cmp_match<OUTCOMES>, dim3((unsigned)std::min<uint64_t>(pass_a, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
+                           g.d_in.p() + PAD, g.len, a.t, b.t, flags & MSIM_CMP_EXACT, pass_a, a.flag, b.flag, S->d_out.p(),
+                           Gt<OUTCOMES>{a.gt, b.gt});
+        MSIM_HIP(c, hipGetLastError());
+    }
+    if (b.t.n) {
+        hipLaunchKernelGGL(k_cmp_tally<OUTCOMES>, dim3((unsigned)std::min<uint64_t>(pass_b, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
+                           b.t.recs, b.t.n, pass_b, (const uint8_t *)b.flag, S->d_out.p() + BINS);
+        MSIM_HIP(c, hipGetLastError());
+    }
+    MSIM_HIP(c, S->tm.end(c->stream));                      // (in front of the copy: the kernels alone)
+    MSIM_HIP(c, hipMemcpyAsync(S->h_out.p(), S->d_out.p(), OUT_BYTES, hipMemcpyDeviceToHost, c->stream));
+    MSIM_HIP(c, wait_stream(c->stream));
+    const int rc = S->tm.add_elapsed(c, &S->kernel_ms);
+    if (rc) return rc;
+    unsigned long long bins[2 * BINS];
+    hist_sum_slots(S->h_out.p(), 2 * BINS, bins, 2 * BINS);
+    finish<OUTCOMES>(bins, bins + BINS, counts, tallies);
+    return MSIM_OK;
+}
+
+// the held table against the contig's current one
+int counts_held(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32_t flags, uint64_t *counts, uint64_t tallies[2]) {
     h.counted = false;
     if (g.n_rec > h.d_flag_b.cap) {                        // exactly a byte per record
         MSIM_HIP(c, h.d_flag_b.release());
         MSIM_HIP(c, dev_alloc(h.d_flag_b, (size_t)g.n_rec));
     }
     h.n_flag_b = g.n_rec;
-    if (h.n_rec || g.n_rec) {
-        const cmp::Table A{h.d_recs.p(), h.n_rec, h.d_pool.p(), h.pool_len};
-        const cmp::Table B{g.d_recs.p(), g.n_rec, g.pool_len ? g.d_pool.p() + PAD : nullptr, g.pool_len};
-        const uint64_t pass_a = (h.n_rec + CMP_PASS - 1) / CMP_PASS, pass_b = (g.n_rec + CMP_PASS - 1) / CMP_PASS;
-        MSIM_HIP(c, hipMemsetAsync(S->d_out.p(), 0, OUT_WORDS * sizeof(unsigned long long), c->stream));
-        MSIM_HIP(c, S->tm.begin(c->stream));
-        if (g.n_rec) MSIM_HIP(c, hipMemsetAsync(h.d_flag_b.p(), 0, (size_t)g.n_rec, c->stream));
-        if (h.n_rec) {
-            hipLaunchKernelGGL(k_cmp_match, dim3((unsigned)std::min<uint64_t>(pass_a, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
-                               g.d_in.p() + PAD, g.len, A, B, flags & MSIM_CMP_EXACT, pass_a, h.d_flag_a.p(), h.d_flag_b.p(), S->d_out.p());
-            MSIM_HIP(c, hipGetLastError());
-        }
-        if (g.n_rec) {
-            hipLaunchKernelGGL(k_cmp_tally, dim3((unsigned)std::min<uint64_t>(pass_b, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
-                               (const msim_record *)g.d_recs.p(), g.n_rec, pass_b, (const uint8_t *)h.d_flag_b.p(), S->d_out.p() + CMP_BINS);
-            MSIM_HIP(c, hipGetLastError());
-        }
-        MSIM_HIP(c, S->tm.end(c->stream));                  // (in front of the copy: the kernels alone)
-        MSIM_HIP(c, hipMemcpyAsync(S->h_out.p(), S->d_out.p(), OUT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        MSIM_HIP(c, wait_stream(c->stream));
-        const int rc = S->tm.add_elapsed(c, &S->kernel_ms);
-        if (rc) return rc;
-        unsigned long long bins[2 * CMP_BINS];
-        hist_sum_slots(S->h_out.p(), 2 * CMP_BINS, bins, 2 * CMP_BINS);
-        cmp_finish(bins, bins + CMP_BINS, counts, tallies);
-    }
-    h.counted = true;
-    return MSIM_OK;
+    const Side a{{h.d_recs.p(), h.n_rec, h.d_pool.p(), h.pool_len}, nullptr, h.d_flag_a.p()};
+    const Side b{{g.d_recs.p(), g.n_rec, g.pool_len ? g.d_pool.p() + PAD : nullptr, g.pool_len}, nullptr, h.d_flag_b.p()};
+    const int rc = counts_device<2>(c, S, g, a, b, flags, counts, tallies);
+    h.counted = !rc;
+    return rc;
 }
 
-// a[]: the truth's counters (matched / genotype-mismatched / missed per cell, the two tallies), b[]: the calls'
-void dip_finish(const unsigned long long *a, const unsigned long long *b, uint64_t *counts, uint64_t tallies[2]) {
-    for (uint32_t cell = 0; cell < cmp::CELLS; cell++) {
-        uint32_t type, bin;
-        cmp::cell_index(cell, &type, &bin);
-        uint64_t *dst = counts + ((size_t)type * MSIM_CMP_BINS + bin) * 6;
-        for (int k = 0; k < 3; k++) { dst[k] += a[3 * cell + k]; dst[3 + k] += b[3 * cell + k]; }
-    }
-    tallies[0] += a[3 * cmp::CELLS];
-    tallies[1] += a[3 * cmp::CELLS + 1];
+// the truth's diploid table against the calls'
+int counts_joined(Ctx *c, CompareState *S, const Contig &g, DipPair &p, uint32_t flags, uint64_t *counts, uint64_t tallies[2]) {
+    const auto side = [](Dip &d) { return Side{{d.d_recs.p(), d.n, d.d_pool.p(), d.pool_len}, d.d_gt.p(), d.d_flag.p()}; };
+    p.counted = false;
+    const int rc = counts_device<3>(c, S, g, side(p.side[MSIM_CMP_TRUTH]), side(p.side[MSIM_CMP_CALLS]), flags, counts, tallies);
+    p.counted = !rc;
+    return rc;
 }
 
 // exactly `bytes`, whatever the block held (contents are not kept)
@@ -399,39 +388,6 @@ int join_device(Ctx *c, CompareState *S, const Contig &g, const Held &h, Dip &d)
     return MSIM_OK;
 }
 
-int counts_diploid_device(Ctx *c, CompareState *S, const Contig &g, DipPair &p, uint32_t flags, uint64_t *counts, uint64_t tallies[2]) {
-    Dip &a = p.side[MSIM_CMP_TRUTH], &b = p.side[MSIM_CMP_CALLS];
-    p.counted = false;
-    if (a.n || b.n) {
-        const cmp::Table A{a.d_recs.p(), a.n, a.d_pool.p(), a.pool_len}, B{b.d_recs.p(), b.n, b.d_pool.p(), b.pool_len};
-        const uint64_t pass_a = (a.n + CMP_PASS - 1) / CMP_PASS, pass_b = (b.n + CMP_PASS - 1) / CMP_PASS;
-        MSIM_HIP(c, hipMemsetAsync(S->d_out.p(), 0, DIP_OUT_WORDS * sizeof(unsigned long long), c->stream));
-        MSIM_HIP(c, S->tm.begin(c->stream));
-        if (b.n) MSIM_HIP(c, hipMemsetAsync(b.d_flag.p(), 0, (size_t)b.n, c->stream));
-        if (a.n) {
-            hipLaunchKernelGGL(k_dip_match, dim3((unsigned)std::min<uint64_t>(pass_a, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
-                               g.d_in.p() + PAD, g.len, A, B, (const uint8_t *)a.d_gt.p(), (const uint8_t *)b.d_gt.p(),
-                               flags & MSIM_CMP_EXACT, pass_a, a.d_flag.p(), b.d_flag.p(), S->d_out.p());
-            MSIM_HIP(c, hipGetLastError());
-        }
-        if (b.n) {
-            hipLaunchKernelGGL(k_dip_tally, dim3((unsigned)std::min<uint64_t>(pass_b, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
-                               (const msim_record *)b.d_recs.p(), b.n, pass_b, (const uint8_t *)b.d_flag.p(), S->d_out.p() + DIP_BINS);
-            MSIM_HIP(c, hipGetLastError());
-        }
-        MSIM_HIP(c, S->tm.end(c->stream));
-        MSIM_HIP(c, hipMemcpyAsync(S->h_out.p(), S->d_out.p(), DIP_OUT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-        MSIM_HIP(c, wait_stream(c->stream));
-        const int rc = S->tm.add_elapsed(c, &S->kernel_ms);
-        if (rc) return rc;
-        unsigned long long bins[2 * DIP_BINS];
-        hist_sum_slots(S->h_out.p(), 2 * DIP_BINS, bins, 2 * DIP_BINS);
-        dip_finish(bins, bins + DIP_BINS, counts, tallies);
-    }
-    p.counted = true;
-    return MSIM_OK;
-}
-
 // (host restatements) a table the rules are written for: known types, pos non-decreasing (strict: strictly increasing)
 int dbg_table_ok(const char *name, const msim_record *t, uint64_t n, bool strict) {
     for (uint64_t i = 0; i < n; i++) {
@@ -446,6 +402,35 @@ int dbg_gt_ok(const char *name, const uint8_t *gt, uint64_t n) {
         if (gt[i] < 1 || gt[i] > 3) return fail(nullptr, MSIM_ERR_ARG, std::string(name) + " record " + std::to_string(i) + ": genotype byte outside 1..3");
     return MSIM_OK;
 }
+// The comparison as one sequential loop over two host tables the caller has judged (a side's flag bytes: wanted or NULL).
+template <int OUTCOMES>
+void dbg_counts(const uint8_t *bases, uint64_t L, const Side &a, const Side &b, uint32_t flags, uint64_t *counts, uint64_t tallies[2]) {
+    using S = cmp::Score<OUTCOMES>;
+    memset(counts, 0, (size_t)8 * MSIM_CMP_BINS * 2 * OUTCOMES * sizeof(uint64_t));
+    memset(tallies, 0, 2 * sizeof(uint64_t));
+    std::vector<uint8_t> fb((size_t)b.t.n, 0);
+    unsigned long long ca[S::COUNTERS] = {}, cb[S::COUNTERS] = {};
+    for (uint64_t i = 0; i < a.t.n; i++) {
+        cmp::Span s;
+        const int64_t j = cmp::partner(bases, L, a.t, i, b.t, (flags & MSIM_CMP_EXACT) != 0, &s);
+        uint8_t f = 0;
+        if (j >= 0 && (uint64_t)j < b.t.n) {
+            if constexpr (OUTCOMES == 3) f = cmp::pair_flag(a.gt[i], b.gt[(size_t)j]);
+            else f = 1;
+            fb[(size_t)j] = f;
+        }
+        if (a.flag) a.flag[i] = f;
+        ca[cmp::counter_of<OUTCOMES>(cmp::rec_at(a.t.recs, i), f)]++;
+        if (s.stops & cmp::STOP_WINDOW) ca[S::TALLIES]++;
+        if (s.stops & cmp::STOP_BASE) ca[S::TALLIES + 1]++;
+    }
+    for (uint64_t i = 0; i < b.t.n; i++) {
+        cb[cmp::counter_of<OUTCOMES>(cmp::rec_at(b.t.recs, i), fb[(size_t)i])]++;
+        if (b.flag) b.flag[i] = fb[(size_t)i];
+    }
+    finish<OUTCOMES>(ca, cb, counts, tallies);
+}
+
 // the join's two refusals
 int join_sizes_ok(Ctx *c, uint64_t n1, uint64_t n2, uint64_t pool1, uint64_t pool2) {
     if (n1 >= (1ull << 31) || n2 >= (1ull << 31) || n1 + n2 >= (1ull << 31))
@@ -526,16 +511,14 @@ int msim_cmp_counts(msim_ctx *p, int contig, uint32_t flags, uint64_t *counts, u
     if (!c || !counts || !tallies) return MSIM_ERR_ARG;
     if (flags & ~(uint32_t)MSIM_CMP_EXACT) return fail(c, MSIM_ERR_ARG, "unknown compare flag");
     Contig *g;
-    int rc = ctx_device_contig(c, contig, true, &g);
-    if (rc) return rc;
-    Held *h = held_of(c, contig);
-    if (!h) return fail(c, MSIM_ERR_ARG, "contig has no held table (msim_cmp_hold)");
+    Held *h;
     CompareState *S;
-    if ((rc = state_of(c, &S))) return rc;
+    const int rc = held_contig(c, contig, &g, &h, &S);
+    if (rc) return rc;
     memset(counts, 0, (size_t)8 * MSIM_CMP_BINS * 4 * sizeof(uint64_t));
     memset(tallies, 0, 2 * sizeof(uint64_t));
     TraceRange tr("msim compare");
-    return counts_device(c, S, *g, *h, flags, counts, tallies);
+    return counts_held(c, S, *g, *h, flags, counts, tallies);
 }
 
 int msim_cmp_fetch(msim_ctx *p, int contig, uint64_t *n_held, uint64_t *held_pool_len, msim_record *held, uint8_t *held_pool,
@@ -574,14 +557,11 @@ int msim_cmp_join(msim_ctx *p, int contig, int side) {
     Ctx *c = reinterpret_cast<Ctx *>(p);
     if (!c) return MSIM_ERR_ARG;
     Contig *g;
-    int rc = ctx_device_contig(c, contig, true, &g);
-    if (rc) return rc;
-    if (side != MSIM_CMP_TRUTH && side != MSIM_CMP_CALLS) return fail(c, MSIM_ERR_ARG, "unknown side (MSIM_CMP_TRUTH, MSIM_CMP_CALLS)");
-    Held *h = held_of(c, contig);
-    if (!h) return fail(c, MSIM_ERR_ARG, "contig has no held table (msim_cmp_hold)");
-    if ((rc = join_sizes_ok(c, h->n_rec, g->n_rec, h->pool_len, g->pool_len))) return rc;
+    Held *h;
     CompareState *S;
-    if ((rc = state_of(c, &S))) return rc;
+    int rc = held_contig(c, contig, &g, &h, &S,
+                         side != MSIM_CMP_TRUTH && side != MSIM_CMP_CALLS ? "unknown side (MSIM_CMP_TRUTH, MSIM_CMP_CALLS)" : nullptr);
+    if (rc || (rc = join_sizes_ok(c, h->n_rec, g->n_rec, h->pool_len, g->pool_len))) return rc;
     if (S->dip.size() <= (size_t)contig) S->dip.resize((size_t)contig + 1);
     DipPair &pair = S->dip[(size_t)contig];
     pair.counted = false;
@@ -608,7 +588,7 @@ int msim_cmp_counts_diploid(msim_ctx *p, int contig, uint32_t flags, uint64_t *c
     memset(counts, 0, (size_t)8 * MSIM_CMP_BINS * 6 * sizeof(uint64_t));
     memset(tallies, 0, 2 * sizeof(uint64_t));
     TraceRange tr("msim compare diploid");
-    return counts_diploid_device(c, S, *g, *pair, flags, counts, tallies);
+    return counts_joined(c, S, *g, *pair, flags, counts, tallies);
 }
 
 int msim_cmp_fetch_diploid(msim_ctx *p, int contig, int side, uint64_t *n, uint64_t *pool_len, msim_record *recs, uint8_t *pool,
@@ -645,12 +625,10 @@ int msim_dbg_cmp_join_copy_floor(msim_ctx *p, int contig, double *ms) {
     Ctx *c = reinterpret_cast<Ctx *>(p);
     if (!c || !ms) return MSIM_ERR_ARG;
     Contig *g;
-    int rc = ctx_device_contig(c, contig, true, &g);
-    if (rc) return rc;
-    Held *h = held_of(c, contig);
-    if (!h) return fail(c, MSIM_ERR_ARG, "contig has no held table (msim_cmp_hold)");
+    Held *h;
     CompareState *S;
-    if ((rc = state_of(c, &S))) return rc;
+    const int rc = held_contig(c, contig, &g, &h, &S);
+    if (rc) return rc;
     const CopySource one[4] = {{h->d_recs.p(), (size_t)h->n_rec * sizeof(msim_record)}, {g->d_recs.p(), (size_t)g->n_rec * sizeof(msim_record)},
                                {h->d_pool.p(), (size_t)h->pool_len}, {g->pool_len ? g->d_pool.p() + PAD : nullptr, (size_t)g->pool_len}};
     return copy_floor(c, S->tm, one, 4, ms);
@@ -662,12 +640,10 @@ int msim_dbg_cmp_copy_floor(msim_ctx *p, int contig, double *ms) {
     Ctx *c = reinterpret_cast<Ctx *>(p);
     if (!c || !ms) return MSIM_ERR_ARG;
     Contig *g;
-    int rc = ctx_device_contig(c, contig, true, &g);
-    if (rc) return rc;
-    Held *h = held_of(c, contig);
-    if (!h) return fail(c, MSIM_ERR_ARG, "contig has no held table (msim_cmp_hold)");
+    Held *h;
     CompareState *S;
-    if ((rc = state_of(c, &S))) return rc;
+    const int rc = held_contig(c, contig, &g, &h, &S);
+    if (rc) return rc;
     const CopySource tables[2] = {{h->d_recs.p(), (size_t)h->n_rec * sizeof(msim_record)}, {g->d_recs.p(), (size_t)g->n_rec * sizeof(msim_record)}};
     return copy_floor(c, S->tm, tables, 2, ms);
 }
@@ -684,25 +660,8 @@ int msim_dbg_cmp_counts(const uint8_t *bases, uint64_t L, const msim_record *tru
         if (!cmp::known_type(truth[i].type)) return fail(nullptr, MSIM_ERR_ARG, "truth record " + std::to_string(i) + ": unknown type");
     for (uint64_t i = 0; i < n_calls; i++)
         if (!cmp::known_type(calls[i].type)) return fail(nullptr, MSIM_ERR_ARG, "calls record " + std::to_string(i) + ": unknown type");
-    memset(counts, 0, (size_t)8 * MSIM_CMP_BINS * 4 * sizeof(uint64_t));
-    memset(tallies, 0, 2 * sizeof(uint64_t));
-    std::vector<uint8_t> fb((size_t)n_calls, 0);
-    unsigned long long a[cmp::COUNTERS] = {}, b[cmp::COUNTERS] = {};
-    const cmp::Table A{truth, n_truth, truth_pool, truth_pool_len}, B{calls, n_calls, calls_pool, calls_pool_len};
-    for (uint64_t i = 0; i < n_truth; i++) {
-        cmp::Span s;
-        const int64_t j = cmp::partner(bases, L, A, i, B, (flags & MSIM_CMP_EXACT) != 0, &s);
-        if (truth_flags) truth_flags[i] = j >= 0 ? 1 : 0;
-        if (j >= 0) fb[(size_t)j] = 1;
-        a[2 * cmp::cell_of(cmp::rec_at(truth, i)) + (j >= 0 ? 0 : 1)]++;
-        if (s.stops & cmp::STOP_WINDOW) a[2 * cmp::CELLS]++;
-        if (s.stops & cmp::STOP_BASE) a[2 * cmp::CELLS + 1]++;
-    }
-    for (uint64_t i = 0; i < n_calls; i++) {
-        b[2 * cmp::cell_of(cmp::rec_at(calls, i)) + (fb[(size_t)i] ? 0 : 1)]++;
-        if (calls_flags) calls_flags[i] = fb[(size_t)i];
-    }
-    cmp_finish(a, b, counts, tallies);
+    dbg_counts<2>(bases, L, Side{{truth, n_truth, truth_pool, truth_pool_len}, nullptr, truth_flags},
+                  Side{{calls, n_calls, calls_pool, calls_pool_len}, nullptr, calls_flags}, flags, counts, tallies);
     return MSIM_OK;
 }
 
@@ -746,27 +705,8 @@ int msim_dbg_cmp_counts_diploid(const uint8_t *bases, uint64_t L, const msim_rec
     if ((rc = dbg_table_ok("truth", truth, n_truth, false)) || (rc = dbg_table_ok("calls", calls, n_calls, false)) ||
         (rc = dbg_gt_ok("truth", truth_gt, n_truth)) || (rc = dbg_gt_ok("calls", calls_gt, n_calls)))
         return rc;
-    memset(counts, 0, (size_t)8 * MSIM_CMP_BINS * 6 * sizeof(uint64_t));
-    memset(tallies, 0, 2 * sizeof(uint64_t));
-    std::vector<uint8_t> fb((size_t)n_calls, 0);
-    unsigned long long a[cmp::DIP_COUNTERS] = {}, b[cmp::DIP_COUNTERS] = {};
-    const cmp::Table A{truth, n_truth, truth_pool, truth_pool_len}, B{calls, n_calls, calls_pool, calls_pool_len};
-    for (uint64_t i = 0; i < n_truth; i++) {
-        cmp::Span s;
-        const int64_t j = cmp::partner(bases, L, A, i, B, (flags & MSIM_CMP_EXACT) != 0, &s);
-        const uint8_t f = j >= 0 ? cmp::pair_flag(truth_gt[i], calls_gt[(size_t)j]) : (uint8_t)0;
-        if (truth_flags) truth_flags[i] = f;
-        if (j >= 0) fb[(size_t)j] = f;
-        a[3 * cmp::cell_of(cmp::rec_at(truth, i)) + (f == 1 ? 0 : f == 2 ? 1 : 2)]++;
-        if (s.stops & cmp::STOP_WINDOW) a[3 * cmp::CELLS]++;
-        if (s.stops & cmp::STOP_BASE) a[3 * cmp::CELLS + 1]++;
-    }
-    for (uint64_t i = 0; i < n_calls; i++) {
-        const uint8_t f = fb[(size_t)i];
-        b[3 * cmp::cell_of(cmp::rec_at(calls, i)) + (f == 1 ? 0 : f == 2 ? 1 : 2)]++;
-        if (calls_flags) calls_flags[i] = f;
-    }
-    dip_finish(a, b, counts, tallies);
+    dbg_counts<3>(bases, L, Side{{truth, n_truth, truth_pool, truth_pool_len}, truth_gt, truth_flags},
+                  Side{{calls, n_calls, calls_pool, calls_pool_len}, calls_gt, calls_flags}, flags, counts, tallies);
     return MSIM_OK;
 }
 

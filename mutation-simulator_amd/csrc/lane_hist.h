@@ -1,4 +1,4 @@
-// The counting kernels' histogram (k_ctx_census, k_sbs_count, k_cmp_match, k_cmp_tally): BINS 16-bit counters per LANE in LDS.
+// The counting kernels' histogram (k_ctx_census, k_sbs_count, k_cmp_match<>, k_cmp_tally<>): BINS 16-bit counters per LANE in LDS.
 //   columns   every lane owns column threadIdx.x of `cnt`, two bins to a 32-bit word: no two lanes share a word and a wave's 64
 //             adds go to 64 different banks, so an add is one conflict-free ds_add whatever the data holds -- a homopolymer
 //             run or a one-channel table costs what random input costs.  A lane zeroes its own column: no barrier before its adds.

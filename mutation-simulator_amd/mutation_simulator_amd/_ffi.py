@@ -661,14 +661,17 @@ class Engine:
         """Drop the contig's held table (-1: every contig's)."""
         self._check(self.lib.msim_cmp_release(self.h, int(contig)))
 
+    def _cmp_counts(self, fn, width: int, contig: int, exact: bool) -> tuple:
+        counts = np.zeros((8, CMP_BINS, width), dtype=np.uint64)
+        tallies = np.zeros(2, dtype=np.uint64)
+        self._check(fn(self.h, int(contig), CMP_EXACT if exact else 0, _ptr(counts), _ptr(tallies)), contig)
+        return counts, tallies
+
     def cmp_counts(self, contig: int, exact: bool = False) -> tuple:
         """The contig's held table (truth) scored against its current one (calls): (uint64[8, CMP_BINS, 4] by record type and
         length bin -- truth matched, truth missed, calls matched, calls extra; uint64[2]: truth indels whose walk a window edge
         stopped, ... a byte outside ACGT stopped).  ``exact``: the literal comparison, no shifting."""
-        counts = np.zeros((8, CMP_BINS, 4), dtype=np.uint64)
-        tallies = np.zeros(2, dtype=np.uint64)
-        self._check(self.lib.msim_cmp_counts(self.h, int(contig), CMP_EXACT if exact else 0, _ptr(counts), _ptr(tallies)), contig)
-        return counts, tallies
+        return self._cmp_counts(self.lib.msim_cmp_counts, 4, contig, exact)
 
     def cmp_fetch(self, contig: int, flags: bool = True) -> tuple:
         """(held records, held pool, a flag byte per held record, a flag byte per current record) of the contig's last
@@ -699,11 +702,7 @@ class Engine:
     def cmp_counts_diploid(self, contig: int, exact: bool = False) -> tuple:
         """The contig's truth diploid table scored against its calls one: (uint64[8, CMP_BINS, 6] -- truth matched, truth
         genotype-mismatched, truth missed, calls matched, calls genotype-mismatched, calls extra; uint64[2] as ``cmp_counts``)."""
-        counts = np.zeros((8, CMP_BINS, 6), dtype=np.uint64)
-        tallies = np.zeros(2, dtype=np.uint64)
-        self._check(self.lib.msim_cmp_counts_diploid(self.h, int(contig), CMP_EXACT if exact else 0, _ptr(counts), _ptr(tallies)),
-                    contig)
-        return counts, tallies
+        return self._cmp_counts(self.lib.msim_cmp_counts_diploid, 6, contig, exact)
 
     def cmp_fetch_diploid(self, contig: int, side: int, flags: bool = True) -> tuple:
         """(records, pool, genotype bytes, flag bytes) of one side's diploid table; the flags are those of the contig's last
@@ -1300,33 +1299,40 @@ def sbs_counts_host(bases, recs) -> tuple:
     return channels, tallies
 
 
-def cmp_counts_host(bases, truth, truth_pool, calls, calls_pool, exact: bool = False) -> tuple:
-    """``msim_dbg_cmp_counts``: what ``Engine.cmp_counts`` returns and the two flag arrays of ``Engine.cmp_fetch`` -- (counts,
-    tallies, truth flags, calls flags) -- by a sequential host loop over ``bases`` (uint8, upper-cased) and two tables
-    (RECORD_DTYPE, insert pools uint8).  No context, no GPU."""
+def _opt_ptr(a):
+    return C.c_void_p(a.ctypes.data) if len(a) else None
+
+
+def _cmp_counts_host(bases, truth, calls, exact: bool) -> tuple:
+    """The two sequential restatements' call: ``truth`` and ``calls`` are (records, pool) -- ``msim_dbg_cmp_counts`` -- or
+    (records, pool, genotype bytes) -- ``msim_dbg_cmp_counts_diploid``."""
     lib = load()
     bases = _as_u8(bases)
-    truth = np.ascontiguousarray(truth, dtype=RECORD_DTYPE)
-    calls = np.ascontiguousarray(calls, dtype=RECORD_DTYPE)
-    truth_pool = np.ascontiguousarray(truth_pool, dtype=np.uint8)
-    calls_pool = np.ascontiguousarray(calls_pool, dtype=np.uint8)
-    counts = np.zeros((8, CMP_BINS, 4), dtype=np.uint64)
+    diploid = len(truth) == 3
+    sides = []
+    for recs, *rest in (truth, calls):
+        side = [np.ascontiguousarray(recs, dtype=RECORD_DTYPE)] + [np.ascontiguousarray(a, dtype=np.uint8) for a in rest]
+        assert all(len(gt) == len(side[0]) for gt in side[2:])
+        sides.append(side)
+    counts = np.zeros((8, CMP_BINS, 6 if diploid else 4), dtype=np.uint64)
     tallies = np.zeros(2, dtype=np.uint64)
-    fa = np.zeros(len(truth), dtype=np.uint8)
-    fb = np.zeros(len(calls), dtype=np.uint8)
-
-    def ptr(a):
-        return C.c_void_p(a.ctypes.data) if len(a) else None
-    rc = lib.msim_dbg_cmp_counts(ptr(bases), len(bases), ptr(truth), len(truth), ptr(truth_pool), len(truth_pool), ptr(calls),
-                                 len(calls), ptr(calls_pool), len(calls_pool), CMP_EXACT if exact else 0, _ptr(counts),
-                                 _ptr(tallies), ptr(fa), ptr(fb))
+    fa = np.zeros(len(sides[0][0]), dtype=np.uint8)
+    fb = np.zeros(len(sides[1][0]), dtype=np.uint8)
+    args = [_opt_ptr(bases), len(bases)]
+    for recs, pool, *gt in sides:
+        args += [_opt_ptr(recs), len(recs), _opt_ptr(pool), len(pool)] + [_opt_ptr(a) for a in gt]
+    rc = (lib.msim_dbg_cmp_counts_diploid if diploid else lib.msim_dbg_cmp_counts)(
+        *args, CMP_EXACT if exact else 0, _ptr(counts), _ptr(tallies), _opt_ptr(fa), _opt_ptr(fb))
     if rc != OK:
         raise _host_error(rc)
     return counts, tallies, fa, fb
 
 
-def _opt_ptr(a):
-    return C.c_void_p(a.ctypes.data) if len(a) else None
+def cmp_counts_host(bases, truth, truth_pool, calls, calls_pool, exact: bool = False) -> tuple:
+    """``msim_dbg_cmp_counts``: what ``Engine.cmp_counts`` returns and the two flag arrays of ``Engine.cmp_fetch`` -- (counts,
+    tallies, truth flags, calls flags) -- by a sequential host loop over ``bases`` (uint8, upper-cased) and two tables
+    (RECORD_DTYPE, insert pools uint8).  No context, no GPU."""
+    return _cmp_counts_host(bases, (truth, truth_pool), (calls, calls_pool), exact)
 
 
 def cmp_join_host(h1, pool1, h2, pool2) -> tuple:
@@ -1352,26 +1358,7 @@ def cmp_counts_diploid_host(bases, truth, truth_pool, truth_gt, calls, calls_poo
     """``msim_dbg_cmp_counts_diploid``: what ``Engine.cmp_counts_diploid`` returns and the two flag arrays of
     ``Engine.cmp_fetch_diploid`` -- (counts, tallies, truth flags, calls flags) -- by a sequential host loop over two diploid
     tables with a genotype byte per record.  No context, no GPU."""
-    lib = load()
-    bases = _as_u8(bases)
-    truth = np.ascontiguousarray(truth, dtype=RECORD_DTYPE)
-    calls = np.ascontiguousarray(calls, dtype=RECORD_DTYPE)
-    truth_pool = np.ascontiguousarray(truth_pool, dtype=np.uint8)
-    calls_pool = np.ascontiguousarray(calls_pool, dtype=np.uint8)
-    truth_gt = np.ascontiguousarray(truth_gt, dtype=np.uint8)
-    calls_gt = np.ascontiguousarray(calls_gt, dtype=np.uint8)
-    assert len(truth_gt) == len(truth) and len(calls_gt) == len(calls)
-    counts = np.zeros((8, CMP_BINS, 6), dtype=np.uint64)
-    tallies = np.zeros(2, dtype=np.uint64)
-    fa = np.zeros(len(truth), dtype=np.uint8)
-    fb = np.zeros(len(calls), dtype=np.uint8)
-    rc = lib.msim_dbg_cmp_counts_diploid(_opt_ptr(bases), len(bases), _opt_ptr(truth), len(truth), _opt_ptr(truth_pool),
-                                         len(truth_pool), _opt_ptr(truth_gt), _opt_ptr(calls), len(calls), _opt_ptr(calls_pool),
-                                         len(calls_pool), _opt_ptr(calls_gt), CMP_EXACT if exact else 0, _ptr(counts), _ptr(tallies),
-                                         _opt_ptr(fa), _opt_ptr(fb))
-    if rc != OK:
-        raise _host_error(rc)
-    return counts, tallies, fa, fb
+    return _cmp_counts_host(bases, (truth, truth_pool, truth_gt), (calls, calls_pool, calls_gt), exact)
 
 
 VCF_GROUP_DTYPE = np.dtype([("name_off", "<u8"), ("first_line", "<u8"), ("n_lines", "<u8"), ("name_len", "<u4"), ("rsv", "<u4")])   # msim_vcf_group

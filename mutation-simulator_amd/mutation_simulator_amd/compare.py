@@ -17,9 +17,11 @@ truth matches the i-th of the calls.  Counts come per record type and, for inser
 ``msim_cmp_join`` joins the two tables per contig into one table of distinct variants with a dosage each (``0/1`` or ``1/1``; phase
 is ignored, a haploid ``1`` counts as ``1/1``).  ``msim_cmp_counts_diploid`` matches the truth's table against the calls' by the
 same rules and compares the dosages: the table gains a ``GT`` column -- pairs found with the wrong genotype, which count in ``FN``
-and in ``FP`` as hap.py reports them.  The renderers of the haploid files are untouched; the diploid ones stand beside them.
+and in ``FP`` as hap.py reports them.  One renderer writes both tables: the counts' last axis (4 or 6) says which.
 """
 from __future__ import annotations
+
+import contextlib
 
 import numpy as np
 
@@ -30,10 +32,21 @@ TYPE_NAMES = (None, "SN", "IN", "DE", "DU", "IV", "TL", "TLI")            # msim
 BIN_NAMES = ("1", "2-5", "6-20", "21-50", "51+")                          # msim_cmp_counts: the length bins of IN and DE
 ROWS = [(t, b) for t in range(1, 8) for b in (range(_ffi.CMP_BINS) if t in (2, 3) else (0,))]
 HEADER = ("type", "length", "truth", "calls", "TP", "FN", "FP", "recall", "precision")
+HEADER_DIPLOID = HEADER[:7] + ("GT",) + HEADER[7:]                        # --diploid: counts[..., 6]
 
 
 class CompareError(Exception):
     """The comparison cannot be made as asked (the message says why)."""
+
+
+@contextlib.contextmanager
+def refusals_of(side: str):
+    """What the loader's grammar refuses inside the block, raised as a CompareError that names the side (``truth``, ``calls``)."""
+    try:
+        yield
+    except (VcfReplayError, ValueError) as e:
+        msg = str(e)
+        raise CompareError(f"{side} {msg}" if msg.startswith("VCF line") else f"{side} VCF: {msg}") from None
 
 
 def ratio(n: int, d: int) -> str:
@@ -41,18 +54,25 @@ def ratio(n: int, d: int) -> str:
 
 
 def row_cells(kind: str, length: str, v) -> list:
-    """One row of the table from (truth matched, truth missed, calls matched, calls extra)."""
-    tm, fn, cm, fp = (int(x) for x in v)
-    return [kind, length, str(tm + fn), str(cm + fp), str(tm), str(fn), str(fp), ratio(tm, tm + fn), ratio(cm, cm + fp)]
+    """One row of the table from a cell's values: (truth matched, truth missed, calls matched, calls extra) or, with genotypes,
+    (truth matched, genotype-mismatched, missed, calls matched, genotype-mismatched, extra) -- a genotype mismatch counts in FN
+    and in FP, and once in the ``GT`` column."""
+    v = [int(x) for x in v]
+    half = len(v) // 2
+    tm, cm = v[0], v[half]
+    fn, fp = sum(v[1:half]), sum(v[half + 1:])
+    gt = [str(v[1])] if half == 3 else []
+    return [kind, length, str(tm + fn), str(cm + fp), str(tm), str(fn), str(fp)] + gt + [ratio(tm, tm + fn), ratio(cm, cm + fp)]
 
 
 def render_block(counts) -> list:
-    """The rows of one ``counts[8][CMP_BINS][4]``: a row per type and length bin, then ALL."""
+    """The rows of one ``counts[8][CMP_BINS][4]`` (``[6]``: with the ``GT`` column): a row per type and length bin, then ALL."""
     counts = np.asarray(counts, dtype=np.uint64)
-    lines = ["\t".join(HEADER)]
+    width = counts.shape[-1]
+    lines = ["\t".join(HEADER_DIPLOID if width == 6 else HEADER)]
     for t, b in ROWS:
         lines.append("\t".join(row_cells(TYPE_NAMES[t], BIN_NAMES[b] if t in (2, 3) else ".", counts[t, b])))
-    lines.append("\t".join(row_cells("ALL", ".", counts.reshape(-1, 4).sum(axis=0, dtype=np.uint64))))
+    lines.append("\t".join(row_cells("ALL", ".", counts.reshape(-1, width).sum(axis=0, dtype=np.uint64))))
     return lines
 
 
@@ -77,37 +97,8 @@ def record_rows(kind: str, contig: str, recs, flags) -> list:
     return out
 
 
-# ---- --diploid: counts[..., 6] = truth matched / genotype-mismatched / missed, calls matched / genotype-mismatched / extra -------
-HEADER_DIPLOID = ("type", "length", "truth", "calls", "TP", "FN", "FP", "GT", "recall", "precision")
+# ---- --diploid: --list names genotypes ---------------------------------------------------------------------------------------
 GT_NAMES = (".", "0/1", "1/1")                                            # by dosage
-
-
-def row_cells_diploid(kind: str, length: str, v) -> list:
-    """One row from the six values of a cell: a genotype mismatch counts in FN and in FP, and once in GT."""
-    tm, tg, miss, cm, cg, extra = (int(x) for x in v)
-    fn, fp = tg + miss, cg + extra
-    return [kind, length, str(tm + fn), str(cm + fp), str(tm), str(fn), str(fp), str(tg), ratio(tm, tm + fn), ratio(cm, cm + fp)]
-
-
-def render_block_diploid(counts) -> list:
-    """The rows of one ``counts[8][CMP_BINS][6]``: a row per type and length bin, then ALL."""
-    counts = np.asarray(counts, dtype=np.uint64)
-    lines = ["\t".join(HEADER_DIPLOID)]
-    for t, b in ROWS:
-        lines.append("\t".join(row_cells_diploid(TYPE_NAMES[t], BIN_NAMES[b] if t in (2, 3) else ".", counts[t, b])))
-    lines.append("\t".join(row_cells_diploid("ALL", ".", counts.reshape(-1, 6).sum(axis=0, dtype=np.uint64))))
-    return lines
-
-
-def render_diploid(notes, counts, names=None) -> str:
-    """``render`` for ``counts[contigs][8][CMP_BINS][6]``."""
-    counts = np.asarray(counts, dtype=np.uint64)
-    lines = [f"# {note}" for note in notes]
-    lines += render_block_diploid(counts.sum(axis=0, dtype=np.uint64))
-    for i, name in enumerate(names or ()):
-        lines.append(f"# contig {name}")
-        lines += render_block_diploid(counts[i])
-    return "\n".join(lines) + "\n"
 
 
 def dosage(gt) -> int:
@@ -147,11 +138,8 @@ class Compare:
     def _plan(self, eng, side: str, path, names, cids, sample, haplotype):
         """One file's tables onto the contigs; (bytes of its text, load kernel ms, plan kernel ms)."""
         text = load_vcf_text(path, eng)
-        try:
+        with refusals_of(side):
             plan_all(eng, text, names, cids, (sample, haplotype or 1))
-        except (VcfReplayError, ValueError) as e:
-            msg = str(e)
-            raise CompareError(f"{side} {msg}" if msg.startswith("VCF line") else f"{side} VCF: {msg}") from None
         load_ms, plan_ms = eng.vcf_timing()
         return int(text.shape[0]), load_ms, plan_ms
 
@@ -159,42 +147,16 @@ class Compare:
         """One file's two haplotypes onto the contigs, joined into the side's diploid tables: haplotype 1 planned and held,
         haplotype 2 planned from the same loaded text, every contig joined."""
         text = load_vcf_text(path, eng)
-        try:
+        with refusals_of(side):
             plan_all(eng, text, names, cids, (sample, 1))
             for cid in cids:
                 eng.cmp_hold(cid)
             plan_loaded(eng, text, names, cids, (sample, 2))
-        except (VcfReplayError, ValueError) as e:
-            msg = str(e)
-            raise CompareError(f"{side} {msg}" if msg.startswith("VCF line") else f"{side} VCF: {msg}") from None
         for cid in cids:
             eng.cmp_join(cid, side_id)
         load_ms, plan_ms = eng.vcf_timing()
         eng.vcf_release()
         return int(text.shape[0]), load_ms, plan_ms
-
-    def _run_diploid(self, eng, names, cids):
-        args = self._args
-        join0 = eng.cmp_join_timing()
-        truth = self._plan_diploid(eng, "truth", _ffi.CMP_TRUTH, args.truthfile, names, cids, getattr(args, "truth_sample", None))
-        calls = self._plan_diploid(eng, "calls", _ffi.CMP_CALLS, args.callsfile, names, cids, getattr(args, "sample", None))
-        exact = bool(getattr(args, "exact", False))
-        cmp0 = eng.cmp_timing()
-        n = len(cids)
-        self.counts = np.zeros((n, 8, _ffi.CMP_BINS, 6), dtype=np.uint64)
-        self.tallies = np.zeros((n, 2), dtype=np.uint64)
-        listed = []
-        for i, cid in enumerate(cids):
-            self.counts[i], self.tallies[i] = eng.cmp_counts_diploid(cid, exact)
-            if getattr(args, "list_records", False):
-                a, _, ga, fa_flags = eng.cmp_fetch_diploid(cid, _ffi.CMP_TRUTH)
-                b, _, gb, fb_flags = eng.cmp_fetch_diploid(cid, _ffi.CMP_CALLS)
-                listed += record_rows_diploid(names[i], a, ga, fa_flags, b, gb, fb_flags)
-        self.stats = {"truth_vcf_bytes": truth[0], "calls_vcf_bytes": calls[0], "vcf_load_kernel_ms": truth[1] + calls[1],
-                      "vcf_plan_kernel_ms": truth[2] + calls[2], "cmp_kernel_ms": round(eng.cmp_timing() - cmp0, 4),
-                      "cmp_join_kernel_ms": round(eng.cmp_join_timing() - join0, 4)}
-        eng.cmp_release()
-        return listed
 
     def run(self):
         fa, args = self._fasta, self._args
@@ -202,37 +164,44 @@ class Compare:
             self._engine = _ffi.Engine(self._device)
         eng = self._engine
         _, names, cids = resident_genome(eng, fa, "compare")
-        if getattr(args, "diploid", False):
-            listed = self._run_diploid(eng, names, cids)
-            args.outcompare.write_text(self.render(names))
-            if getattr(args, "list_records", False):
-                args.outcompare_records.write_text("".join(line + "\n" for line in listed))
-            return
-        truth = self._plan(eng, "truth", args.truthfile, names, cids, getattr(args, "truth_sample", None),
-                           getattr(args, "truth_haplotype", None))
-        for cid in cids:
-            eng.cmp_hold(cid)
-        eng.vcf_release()
-        calls = self._plan(eng, "calls", args.callsfile, names, cids, getattr(args, "sample", None), getattr(args, "haplotype", None))
+        diploid, listing = bool(getattr(args, "diploid", False)), bool(getattr(args, "list_records", False))
+        truth_sample, sample = getattr(args, "truth_sample", None), getattr(args, "sample", None)
+        if diploid:
+            join0 = eng.cmp_join_timing()
+            truth = self._plan_diploid(eng, "truth", _ffi.CMP_TRUTH, args.truthfile, names, cids, truth_sample)
+            calls = self._plan_diploid(eng, "calls", _ffi.CMP_CALLS, args.callsfile, names, cids, sample)
+        else:
+            truth = self._plan(eng, "truth", args.truthfile, names, cids, truth_sample, getattr(args, "truth_haplotype", None))
+            for cid in cids:
+                eng.cmp_hold(cid)
+            eng.vcf_release()
+            calls = self._plan(eng, "calls", args.callsfile, names, cids, sample, getattr(args, "haplotype", None))
         # every line of both files is accepted: count, contig by contig
         exact = bool(getattr(args, "exact", False))
         cmp0 = eng.cmp_timing()                        # (a caller's engine may have compared before)
         n = len(cids)
-        self.counts = np.zeros((n, 8, _ffi.CMP_BINS, 4), dtype=np.uint64)
+        self.counts = np.zeros((n, 8, _ffi.CMP_BINS, 6 if diploid else 4), dtype=np.uint64)
         self.tallies = np.zeros((n, 2), dtype=np.uint64)
         listed = []
         for i, cid in enumerate(cids):
-            self.counts[i], self.tallies[i] = eng.cmp_counts(cid, exact)
-            if getattr(args, "list_records", False):
+            self.counts[i], self.tallies[i] = eng.cmp_counts_diploid(cid, exact) if diploid else eng.cmp_counts(cid, exact)
+            if listing and diploid:
+                a, _, ga, fa_flags = eng.cmp_fetch_diploid(cid, _ffi.CMP_TRUTH)
+                b, _, gb, fb_flags = eng.cmp_fetch_diploid(cid, _ffi.CMP_CALLS)
+                listed += record_rows_diploid(names[i], a, ga, fa_flags, b, gb, fb_flags)
+            elif listing:
                 held, _, fa_flags, fb_flags = eng.cmp_fetch(cid)
                 listed += record_rows("FN", names[i], held, fa_flags)
                 listed += record_rows("FP", names[i], eng.fetch_records(cid)[0], fb_flags)
         self.stats = {"truth_vcf_bytes": truth[0], "calls_vcf_bytes": calls[0], "vcf_load_kernel_ms": truth[1] + calls[1],
                       "vcf_plan_kernel_ms": truth[2] + calls[2], "cmp_kernel_ms": round(eng.cmp_timing() - cmp0, 4)}
-        eng.vcf_release()
+        if diploid:
+            self.stats["cmp_join_kernel_ms"] = round(eng.cmp_join_timing() - join0, 4)
+        else:
+            eng.vcf_release()                          # (a diploid side released its text behind its joins)
         eng.cmp_release()
         args.outcompare.write_text(self.render(names))
-        if getattr(args, "list_records", False):
+        if listing:
             args.outcompare_records.write_text("".join(line + "\n" for line in listed))
 
     def render(self, names) -> str:
@@ -253,7 +222,6 @@ class Compare:
                  f"truth indels whose placements end at a base outside ACGT: {int(tallies[1])}"]
         if diploid:
             notes.insert(3, "genotypes: diploid, unphased (dosage compared; a haploid 1 counts as 1/1)")
-            return render_diploid(notes, self.counts, names if getattr(args, "per_contig", False) else None)
         return render(notes, self.counts, names if getattr(args, "per_contig", False) else None)
 
     def close(self):

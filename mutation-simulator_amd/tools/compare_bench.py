@@ -15,7 +15,7 @@ and each side goes the way of `compare --diploid`: haplotype 1 selected and held
 above, which are taken first in the same process on the same full tables (the join's held table replaces the haploid run's):
   cmp_join_kernel_ms        the join of the calls' two haplotype tables (msim_cmp_join_timing: its kernels and two pool copies)
   join_copy_floor_ms        a device-to-device copy of the bytes that join reads and writes (msim_dbg_cmp_join_copy_floor)
-  cmp_diploid_kernel_ms     k_dip_match + k_dip_tally, to hold against cmp_kernel_ms"""
+  cmp_diploid_kernel_ms     k_cmp_match<3> + k_cmp_tally<3>, to hold against cmp_kernel_ms"""
 import ctypes as C
 import json
 import statistics

@@ -1,6 +1,7 @@
 """``compare --diploid`` without a GPU: the library's sequential restatements (``msim_dbg_cmp_join``,
-``msim_dbg_cmp_counts_diploid``) against ``dip_twin`` on every shape the GPU tier runs, the file writer's diploid counterparts, and
-the command line's names and usage errors.  All comparisons are exact integers and bytes."""
+``msim_dbg_cmp_counts_diploid``) against ``dip_twin`` on every shape the GPU tier runs, the haploid restatement as the diploid
+one with equal dosages, the file writer with the ``GT`` column, and the command line's names and usage errors.  All comparisons
+are exact integers and bytes."""
 from __future__ import annotations
 
 import contextlib
@@ -68,6 +69,26 @@ def test_constants_are_the_headers():
 @pytest.mark.parametrize("case", sorted(CASES))
 def test_host_restatements_equal_the_twin(case):
     check_host(CASES[case])
+
+
+HAPLOID_CASES = tw.small_cases(PASS)
+HAPLOID_OF_DIPLOID = (0, 2, 3, 5)          # truth matched, missed, calls matched, extra among the six values of a diploid cell
+
+
+@pytest.mark.parametrize("exact", (False, True), ids=("normalised", "exact"))
+@pytest.mark.parametrize("case", sorted(HAPLOID_CASES))
+def test_a_haploid_comparison_is_the_diploid_one_with_every_dosage_equal(case, exact):
+    """Both restatements run one loop (csrc/compare.hip: ``dbg_counts``): with every genotype byte 3 on both sides no pair can
+    differ in dosage, and the diploid counts are the haploid ones with two empty columns.  The diploid entry point refuses what
+    the haploid one counts as nothing (an unknown type, an unsorted table); none of the haploid cases is such a table, so no
+    case is left out and a refusal fails the test."""
+    bases, a, pa, b, pb, _ = HAPLOID_CASES[case]
+    hom = lambda t: np.full(len(t), 3, dtype=np.uint8)                                     # noqa: E731
+    want = _ffi.cmp_counts_host(bases, a, pa, b, pb, exact)
+    got = _ffi.cmp_counts_diploid_host(bases, a, pa, hom(a), b, pb, hom(b), exact)
+    assert np.array_equal(got[0][..., HAPLOID_OF_DIPLOID], want[0]) and not got[0][..., (1, 4)].any()
+    for name, g, w in zip(("tallies", "truth flags", "calls flags"), got[1:], want[1:]):
+        assert g.dtype == w.dtype and np.array_equal(g, w), name
 
 
 def test_what_the_named_cases_are_about():
@@ -164,7 +185,7 @@ def test_rendering_with_the_gt_column_and_na_cells():
     counts[0, tw.DE, 1] = (0, 0, 4, 0, 0, 0)               # truth only: precision has no denominator
     counts[1, tw.IN, 4] = (0, 0, 0, 0, 0, 2)               # calls only: recall has none
     counts[1, tw.IN, 0] = (0, 3, 0, 0, 3, 0)               # found, every one with the wrong genotype
-    text = compare.render_diploid(["a note", "another"], counts, ["chr1", "chr 2"])
+    text = compare.render(["a note", "another"], counts, ["chr1", "chr 2"])
     lines = text.splitlines()
     assert compare.HEADER_DIPLOID == ("type", "length", "truth", "calls", "TP", "FN", "FP", "GT", "recall", "precision")
     assert lines[:2] == ["# a note", "# another"] and lines[2] == "\t".join(compare.HEADER_DIPLOID)
@@ -182,7 +203,7 @@ def test_rendering_with_the_gt_column_and_na_cells():
     assert lines[19] == "# contig chr1" and lines[37] == "# contig chr 2"
     assert lines[21].split("\t") == ["SN", ".", "100", "120", "80", "20", "40", "10", "0.800000", "0.666667"]
     assert lines[39].split("\t") == ["SN", ".", "10", "10", "10", "0", "0", "0", "1.000000", "1.000000"]
-    assert compare.render_diploid([], counts).count("\n") == 17
+    assert compare.render([], counts).count("\n") == 17
     # the haploid renderers are what they were
     assert compare.HEADER == ("type", "length", "truth", "calls", "TP", "FN", "FP", "recall", "precision")
     assert compare.render([], np.zeros((1, 8, _ffi.CMP_BINS, 4), np.uint64)).splitlines()[0] == "\t".join(compare.HEADER)

@@ -1,5 +1,5 @@
 """``compare --diploid`` on the device: ``msim_cmp_join`` (csrc/compare.hip: ``k_join_flag``, ``k_join_put2``, ``k_join_put1``) and
-``msim_cmp_counts_diploid`` (``k_dip_match``, ``k_dip_tally``) on hand-built and planned record tables, and the command line.
+``msim_cmp_counts_diploid`` (``k_cmp_match<3>``, ``k_cmp_tally<3>``) on hand-built and planned record tables, and the command line.
 Every result is held against ``dip_twin`` (the rules in Python) AND against the library's sequential restatements
 (``_ffi.cmp_join_host``, ``_ffi.cmp_counts_diploid_host``) through ``cmp_fetch_diploid``; all comparisons are exact.
 """
@@ -255,7 +255,61 @@ def test_planned_table_of_2_17_plus_1_records(eng):
     eng.clear()
 
 
-# ------------------------------------------------------------------------------ 4. the command line
+# ------------------------------------------------------------------------------ 4. one scoring path for both comparisons
+HAPLOID_CASES = tw.small_cases(PASS)
+HAPLOID_OF_DIPLOID = (0, 2, 3, 5)          # truth matched, missed, calls matched, extra among the six values of a diploid cell
+
+
+def check_haploid_is_diploid(eng, bases, a, pa, b, pb, exact=False):
+    """``cmp_counts`` of ``a`` against ``b``, then each table joined with itself -- installed, held, left current, joined: every
+    record of haplotype 2 is haplotype 1's again -- and ``cmp_counts_diploid``: the same records with every genotype byte 3 and
+    the pool twice, the haploid counts with two empty columns, the same tallies and flags.  Returns the haploid result."""
+    eng.clear()
+    cid = eng.add_contig(bases)
+    eng.set_records(cid, a, pa)
+    eng.cmp_hold(cid)
+    eng.set_records(cid, b, pb)
+    want = eng.cmp_counts(cid, exact) + eng.cmp_fetch(cid)[2:]
+    for side, recs, pool in ((TRUTH, a, pa), (CALLS, b, pb)):
+        eng.set_records(cid, recs, pool)
+        eng.cmp_hold(cid)
+        eng.cmp_join(cid, side)
+    counts, tallies = eng.cmp_counts_diploid(cid, exact)
+    flags = []
+    for side, recs, pool in ((TRUTH, a, pa), (CALLS, b, pb)):
+        u, upool, gt, fl = eng.cmp_fetch_diploid(cid, side)
+        assert u.tobytes() == np.ascontiguousarray(recs).tobytes() and upool.tobytes() == np.ascontiguousarray(pool).tobytes() * 2
+        assert gt.shape == (len(recs),) and (gt == 3).all()
+        flags.append(fl)
+    assert np.array_equal(counts[..., HAPLOID_OF_DIPLOID], want[0]) and not counts[..., (1, 4)].any()
+    same((tallies, *flags), want[1:], ("tallies", "truth flags", "calls flags"), "haploid")
+    eng.clear()
+    return want
+
+
+@pytest.mark.parametrize("case", sorted(HAPLOID_CASES))
+def test_haploid_small_shapes_as_diploid(eng, case):
+    check_haploid_is_diploid(eng, *HAPLOID_CASES[case])
+
+
+def test_sn_table_past_the_grid_cap_as_diploid(eng):
+    """``2048 * PASS + 1`` SN records a side (``test_gpu_compare``'s table past the grid cap): the first size at which a workgroup
+    of the diploid instantiation takes a second pass.  The closed form: 524 changed records, each missed once and extra once."""
+    n = 2048 * PASS + 1
+    bases = np.frombuffer(b"ACGT", dtype=np.uint8)[np.random.RandomState(5).randint(0, 4, n)]
+    a = np.zeros(n, dtype=_ffi.RECORD_DTYPE)
+    a["pos"] = a["stop"] = np.arange(n, dtype=np.uint32)
+    a["type"] = tw.SN
+    a["aux"] = np.arange(n) % 3
+    changed = np.arange(999, n, 1000)
+    b = a.copy()
+    b["aux"][changed] = (b["aux"][changed] + 1) % 3
+    counts, tallies, fa, fb = check_haploid_is_diploid(eng, bases, a, tw.NO_POOL, b, tw.NO_POOL)
+    assert len(changed) == 524 and counts[tw.SN, 0].tolist() == [n - 524, 524, n - 524, 524] and not tallies.any()
+    assert np.array_equal(np.flatnonzero(fa == 0), changed) and np.array_equal(fa, fb)
+
+
+# ------------------------------------------------------------------------------ 5. the command line
 def haplotype_tables(seqs, vcf_path, names=NAMES):
     """The two record tables the consensus parser makes of a VCF's first sample, per contig: [(H1, pool, H2, pool)]."""
     e = _ffi.Engine(0)
@@ -448,7 +502,7 @@ def test_cli_multi_allelic_and_overlapping_haplotypes(tmp_path):
     assert [len(t) for t in truth[0][::2]] == [3, 3]       # each haplotype: its allele of the 1|2, the deletion or the SNP, the 1|1
     (a, _, ga), (b, _, gb), (counts, _, fa_, fb_) = twin_of(seqs, truth, calls)[0]
     assert a["pos"].tolist() == [9, 9, 20, 21, 39] and ga.tolist() == [1, 2, 1, 2, 3]
-    assert body_of(tmp_path / "o_ms.compare.tsv") == compare.render_block_diploid(counts)
+    assert body_of(tmp_path / "o_ms.compare.tsv") == compare.render_block(counts)
     _, rows = table_rows(tmp_path / "o_ms.compare.tsv")
     assert rows[("SN", ".")][:6] == ["4", "4", "3", "1", "1", "1"] and rows[("DE", "2-5")][:6] == ["1", "1", "1", "0", "0", "0"]
     assert (tmp_path / "o_ms.compare.records.tsv").read_text() == "GT\tc\t40\tSN\t1\t1/1\t0/1\n"
