@@ -658,6 +658,51 @@ int msim_dbg_cmp_counts(const uint8_t *bases, uint64_t L, const msim_record *tru
                         uint64_t calls_pool_len, uint32_t flags, uint64_t *counts, uint64_t tallies[2], uint8_t *truth_flags,
                         uint8_t *calls_flags);
 
+/* ---- compare --blocks: unmatched records rescued by replaying blocks (csrc/cmp_blocks.hip, cmp_blocks.h) ---------------------------- */
+/* The match above scores every record on its own: an MNP written as one line against two SNPs, or a duplication reported as the
+ * insertion it also is, counts once as missed and once as extra although both files describe the same sequence.  This pass, haploid
+ * only, runs behind the match (flag bytes 0 or 1 on both tables) and rescues such records; it never takes a match away.
+ * Blocks.  A record's FOOTPRINT END is its stop for DE, DU, IV and TL and its pos for SN, IN and TLI.  In merged position order (the
+ *   truth's record first at equal pos) a record belongs to the block of its predecessors iff pos - end <= gap, `end` the largest
+ *   footprint end of the records in front of it in either table; otherwise it starts a block.  A table's records do not overlap, so
+ *   the record in front of it in its own table and the one in front of it in the other table (a binary search) decide.
+ * Candidates.  A block that holds a record with flag byte 0, on either side, is a candidate.  It is walked in merged order, and the
+ *   walk ends at the first record that
+ *     - is a TL or a TLI (its bytes come from elsewhere on the contig): the block HOLDS A TRANSLOCATION and is not replayed; or
+ *     - is the block's record number MSIM_CMP_BLOCK_RECORDS + 1 (both sides together), or has a footprint end more than
+ *       MSIM_CMP_BLOCK_SPAN bases behind the block's first pos: the block is OVER A LIMIT and is not replayed.
+ *   A record that meets both is a translocation.
+ * Replay.  Every other candidate is replayed over its input bases [lo, hi], its first pos to its largest footprint end: the bytes the
+ *   rewrite (msim_apply_contig) writes there with the truth's records of the block alone, and the bytes it writes with the calls'
+ *   alone -- an SN's outcome on the de-ambiguated base, an IN's bytes in front of the base it stands at, a DU's span twice, an IV's
+ *   reverse complement.  The two streams are compared byte for byte, lengths included; a stream with an SN the rewrite has no outcome
+ *   for (MSIM_ERR_KEY) equals nothing.  On equality every flag-0 record of the block, on both sides, gets flag byte 2, "matched as
+ *   part of a block"; flag-1 records keep their byte; on inequality nothing changes.  So a shifted pair of indels the match paired
+ *   stays matched even with an SNP between the two placements, where a replay of that neighbourhood alone would differ.
+ *   counts[type][bin][6]   truth matched, truth block-matched, truth missed, calls matched, calls block-matched, calls extra.
+ *   tallies[2]             as msim_cmp_counts'.
+ *   block_tallies[5]       candidates, replayed, equal, over a limit, holding a translocation; candidates = replayed + over a limit +
+ *                          holding a translocation.
+ *   msim_cmp_counts_blocks   held against current, as msim_cmp_counts and with its errors; MSIM_CMP_EXACT is allowed (the match is
+ *                            then literal and the replay rescues the shifted indels inside a gap); MSIM_ERR_ARG for gap >
+ *                            MSIM_CMP_BLOCK_SPAN.  msim_cmp_fetch then returns flag bytes 0, 1 or 2.  The match's and the final
+ *                            tally's time adds to msim_cmp_timing.
+ *   msim_cmp_blocks_timing   the block pass's two kernels on the device (HIP events) since the context was made or msim_reset_stats.
+ * Limits.  A block is compared as a whole: one unmatched record that stands alone among matched ones is not rescued by dropping a
+ *   neighbour; blocks holding a translocation or over a limit stay as the match left them; genotypes are not considered.
+ * msim_dbg_cmp_counts_blocks: the same counts, tallies, block tallies and flags (either flag array may be NULL) by sequential host
+ * loops -- no context, no GPU (MSIM_ERR_ARG for a record of unknown type, a table not strictly increasing in pos, gap > MSIM_CMP_BLOCK_SPAN). */
+#define MSIM_CMP_BLOCK_GAP     50
+#define MSIM_CMP_BLOCK_RECORDS 64
+#define MSIM_CMP_BLOCK_SPAN    4096
+int msim_cmp_counts_blocks(msim_ctx *ctx, int contig, uint32_t flags, uint32_t gap, uint64_t *counts, uint64_t tallies[2],
+                           uint64_t block_tallies[5]);
+int msim_cmp_blocks_timing(msim_ctx *ctx, double *kernel_ms);
+int msim_dbg_cmp_counts_blocks(const uint8_t *bases, uint64_t L, const msim_record *truth, uint64_t n_truth, const uint8_t *truth_pool,
+                               uint64_t truth_pool_len, const msim_record *calls, uint64_t n_calls, const uint8_t *calls_pool,
+                               uint64_t calls_pool_len, uint32_t flags, uint32_t gap, uint64_t *counts, uint64_t tallies[2],
+                               uint64_t block_tallies[5], uint8_t *truth_flags, uint8_t *calls_flags);
+
 /* ---- compare --diploid: genotypes scored against a diploid truth (csrc/compare.hip, compare.h) ------------------------------------ */
 /* A side's (the truth's, the calls') two haplotype tables of one contig are JOINED into one diploid table U of distinct variants with
  * a genotype byte each, and the truth's U is matched against the calls' U; a pair's DOSAGES are then compared.  Phase is ignored on

@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "cmp_blocks.h"
 #include "compare.h"
 #include "ctx.h"
 #include "lane_hist.h"
@@ -57,6 +58,14 @@ struct CompareState {
     Scratch<uint32_t> d_tile;                  //   per scan tile its duplicates (then their exclusive scan, the total last)
     EventPair tm;
     double kernel_ms = 0, join_ms = 0;
+    // compare --blocks (msim_cmp_counts_blocks; kernels in cmp_blocks.hip)
+    Scratch<unsigned long long> d_blk_out;     // the match's counters (two outcomes), the final tally's (three), the block pass's
+    Pinned<unsigned long long> h_blk_out;      // pinned copy of them
+    Scratch<blk::Desc> d_desc;                 // the blocks to replay
+    EventPair tm_blk, tm_tally;
+    hipEvent_t ev_blk_mid = nullptr;           // between k_blk_scan and k_blk_replay
+    double blocks_ms = 0, scan_ms = 0, replay_ms = 0;
+    uint64_t replay_steps = 0, replay_wave_steps = 0;      // msim_dbg_cmp_blocks_split
 };
 
 namespace {
@@ -318,6 +327,97 @@ int counts_held(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32_t flag
     return rc;
 }
 
+// exactly `bytes`, whatever the block held (contents are not kept)
+hipError_t dev_exact(DevBlock &b, size_t bytes) {
+    const hipError_t e = b.release();
+    return e != hipSuccess || !bytes ? e : dev_alloc(b, bytes);
+}
+// at least `bytes` (contents are not kept)
+hipError_t dev_at_least(DevBlock &b, size_t bytes) { return bytes <= b.cap ? hipSuccess : dev_exact(b, bytes); }
+
+// ---- compare --blocks: the held table against the current one, unmatched records rescued block by block ---------------------------
+// The words of d_blk_out: k_cmp_match<2>'s counters (its two walk tallies are used, its cells are not), k_cmp_tally<3>'s over both
+// tables with the final flag bytes, the block pass's (cmp_blocks.h).
+constexpr size_t BLK_MATCH_AT = 0, BLK_TALLY_AT = OUT_WORDS<2>, BLK_PASS_AT = BLK_TALLY_AT + OUT_WORDS<3>,
+                 BLK_OUT_WORDS = BLK_PASS_AT + blk::PASS_WORDS;
+
+void finish_blocks(const unsigned long long *words, uint64_t *counts, uint64_t tallies[2], uint64_t block_tallies[5]) {
+    constexpr size_t B2 = cmp::Score<2>::BINS, B3 = cmp::Score<3>::BINS;
+    unsigned long long m[2 * B2], t[2 * B3], p[blk::PASS_BINS];
+    hist_sum_slots(words + BLK_MATCH_AT, 2 * B2, m, 2 * B2);
+    hist_sum_slots(words + BLK_TALLY_AT, 2 * B3, t, 2 * B3);
+    hist_sum_slots(words + BLK_PASS_AT, blk::PASS_BINS, p, blk::PASS_BINS);
+    uint64_t none[2] = {0, 0};
+    finish<3>(t, t + B3, counts, none);
+    tallies[0] += m[cmp::Score<2>::TALLIES];
+    tallies[1] += m[cmp::Score<2>::TALLIES + 1];
+    for (uint32_t k = 0; k < blk::TALLIES; k++) block_tallies[k] += p[k];
+}
+
+int counts_held_blocks(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32_t flags, uint32_t gap, uint64_t *counts, uint64_t tallies[2],
+                       uint64_t block_tallies[5]) {
+    h.counted = false;
+    if (!S->d_blk_out) MSIM_HIP(c, dev_alloc(S->d_blk_out, BLK_OUT_WORDS * sizeof(unsigned long long)));   // (made on first use)
+    if (!S->h_blk_out) MSIM_HIP(c, pin_alloc(S->h_blk_out, BLK_OUT_WORDS * sizeof(unsigned long long)));
+    if (!S->tm_blk.e1) { S->tm_blk.destroy(); MSIM_HIP(c, S->tm_blk.create()); }
+    if (!S->tm_tally.e1) { S->tm_tally.destroy(); MSIM_HIP(c, S->tm_tally.create()); }
+    if (!S->ev_blk_mid) MSIM_HIP(c, hipEventCreate(&S->ev_blk_mid));
+    if (g.n_rec > h.d_flag_b.cap) {                        // exactly a byte per record
+        MSIM_HIP(c, h.d_flag_b.release());
+        MSIM_HIP(c, dev_alloc(h.d_flag_b, (size_t)g.n_rec));
+    }
+    h.n_flag_b = g.n_rec;
+    const Side a{{h.d_recs.p(), h.n_rec, h.d_pool.p(), h.pool_len}, nullptr, h.d_flag_a.p()};
+    const Side b{{g.d_recs.p(), g.n_rec, g.pool_len ? g.d_pool.p() + PAD : nullptr, g.pool_len}, nullptr, h.d_flag_b.p()};
+    const uint64_t total = a.t.n + b.t.n;
+    if (!total) { h.counted = true; return MSIM_OK; }
+    MSIM_HIP(c, dev_at_least(S->d_desc, (size_t)total * sizeof(blk::Desc)));
+    unsigned long long *out = S->d_blk_out.p();
+    const uint64_t pass_a = (a.t.n + CMP_PASS - 1) / CMP_PASS, pass_b = (b.t.n + CMP_PASS - 1) / CMP_PASS;
+    MSIM_HIP(c, hipMemsetAsync(out, 0, BLK_OUT_WORDS * sizeof(unsigned long long), c->stream));
+    MSIM_HIP(c, S->tm.begin(c->stream));
+    if (b.t.n) MSIM_HIP(c, hipMemsetAsync(b.flag, 0, (size_t)b.t.n, c->stream));
+    if (a.t.n) {
+        hipLaunchKernelGGL(k_cmp_match<2>, dim3((unsigned)std::min<uint64_t>(pass_a, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
+                           g.d_in.p() + PAD, g.len, a.t, b.t, flags & MSIM_CMP_EXACT, pass_a, a.flag, b.flag, out + BLK_MATCH_AT, Gt<2>{nullptr, nullptr});
+        MSIM_HIP(c, hipGetLastError());
+    }
+    MSIM_HIP(c, S->tm.end(c->stream));
+    MSIM_HIP(c, S->tm_blk.begin(c->stream));
+    const int rc_blk = blocks_enqueue(c, c->stream, g.d_in.p() + PAD, g.len, a.t, b.t, a.flag, b.flag, gap, S->d_desc.p(), total, out + BLK_PASS_AT,
+                                      S->ev_blk_mid);
+    if (rc_blk) return rc_blk;
+    MSIM_HIP(c, S->tm_blk.end(c->stream));
+    MSIM_HIP(c, S->tm_tally.begin(c->stream));
+    const Side *sides[2] = {&a, &b};
+    for (int s = 0; s < 2; s++) {
+        const Side &x = *sides[s];
+        if (!x.t.n) continue;
+        hipLaunchKernelGGL(k_cmp_tally<3>, dim3((unsigned)std::min<uint64_t>(s ? pass_b : pass_a, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
+                           x.t.recs, x.t.n, s ? pass_b : pass_a, (const uint8_t *)x.flag, out + BLK_TALLY_AT + (s ? cmp::Score<3>::BINS : 0));
+        MSIM_HIP(c, hipGetLastError());
+    }
+    MSIM_HIP(c, S->tm_tally.end(c->stream));
+    MSIM_HIP(c, hipMemcpyAsync(S->h_blk_out.p(), out, BLK_OUT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+    MSIM_HIP(c, wait_stream(c->stream));
+    int rc;
+    if ((rc = S->tm.add_elapsed(c, &S->kernel_ms)) || (rc = S->tm_tally.add_elapsed(c, &S->kernel_ms)) ||
+        (rc = S->tm_blk.add_elapsed(c, &S->blocks_ms)))
+        return rc;
+    const unsigned long long *pass = S->h_blk_out.p() + BLK_PASS_AT;
+    if (pass[blk::PASS_COUNT_AT] > total) return fail(c, MSIM_ERR_HIP, "internal: more blocks to replay than the two tables hold records");
+    float scan = 0, replay = 0;
+    MSIM_HIP(c, hipEventElapsedTime(&scan, S->tm_blk.e0, S->ev_blk_mid));
+    MSIM_HIP(c, hipEventElapsedTime(&replay, S->ev_blk_mid, S->tm_blk.e1));
+    S->scan_ms += scan;
+    S->replay_ms += replay;
+    S->replay_steps += pass[blk::PASS_STEPS_AT];
+    S->replay_wave_steps += pass[blk::PASS_WAVE_STEPS_AT];
+    finish_blocks(S->h_blk_out.p(), counts, tallies, block_tallies);
+    h.counted = true;
+    return MSIM_OK;
+}
+
 // the truth's diploid table against the calls'
 int counts_joined(Ctx *c, CompareState *S, const Contig &g, DipPair &p, uint32_t flags, uint64_t *counts, uint64_t tallies[2]) {
     const auto side = [](Dip &d) { return Side{{d.d_recs.p(), d.n, d.d_pool.p(), d.pool_len}, d.d_gt.p(), d.d_flag.p()}; };
@@ -326,14 +426,6 @@ int counts_joined(Ctx *c, CompareState *S, const Contig &g, DipPair &p, uint32_t
     p.counted = !rc;
     return rc;
 }
-
-// exactly `bytes`, whatever the block held (contents are not kept)
-hipError_t dev_exact(DevBlock &b, size_t bytes) {
-    const hipError_t e = b.release();
-    return e != hipSuccess || !bytes ? e : dev_alloc(b, bytes);
-}
-// at least `bytes` (contents are not kept)
-hipError_t dev_at_least(DevBlock &b, size_t bytes) { return bytes <= b.cap ? hipSuccess : dev_exact(b, bytes); }
 
 DipPair *dip_of(Ctx *c, int contig) {
     CompareState *S = c->compare;
@@ -453,12 +545,18 @@ void compare_state_destroy(Ctx *c) {
     if (!S) return;
     compare_drop_all(c);
     S->tm.destroy();
+    S->tm_blk.destroy();
+    S->tm_tally.destroy();
+    if (S->ev_blk_mid) (void)hipEventDestroy(S->ev_blk_mid);
     delete S;
     c->compare = nullptr;
 }
 
 void compare_reset_timing(Ctx *c) {
-    if (c->compare) c->compare->kernel_ms = c->compare->join_ms = 0;
+    if (!c->compare) return;
+    CompareState &S = *c->compare;
+    S.kernel_ms = S.join_ms = S.blocks_ms = S.scan_ms = S.replay_ms = 0;
+    S.replay_steps = S.replay_wave_steps = 0;
 }
 
 }  // namespace msim
@@ -519,6 +617,43 @@ int msim_cmp_counts(msim_ctx *p, int contig, uint32_t flags, uint64_t *counts, u
     memset(tallies, 0, 2 * sizeof(uint64_t));
     TraceRange tr("msim compare");
     return counts_held(c, S, *g, *h, flags, counts, tallies);
+}
+
+int msim_cmp_counts_blocks(msim_ctx *p, int contig, uint32_t flags, uint32_t gap, uint64_t *counts, uint64_t tallies[2], uint64_t block_tallies[5]) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c || !counts || !tallies || !block_tallies) return MSIM_ERR_ARG;
+    if (flags & ~(uint32_t)MSIM_CMP_EXACT) return fail(c, MSIM_ERR_ARG, "unknown compare flag");
+    Contig *g;
+    Held *h;
+    CompareState *S;
+    const int rc = held_contig(c, contig, &g, &h, &S, gap > MSIM_CMP_BLOCK_SPAN ? "the block gap is larger than MSIM_CMP_BLOCK_SPAN" : nullptr);
+    if (rc) return rc;
+    memset(counts, 0, (size_t)8 * MSIM_CMP_BINS * 6 * sizeof(uint64_t));
+    memset(tallies, 0, 2 * sizeof(uint64_t));
+    memset(block_tallies, 0, 5 * sizeof(uint64_t));
+    TraceRange tr("msim compare blocks");
+    return counts_held_blocks(c, S, *g, *h, flags, gap, counts, tallies, block_tallies);
+}
+
+int msim_cmp_blocks_timing(msim_ctx *p, double *kernel_ms) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c) return MSIM_ERR_ARG;
+    if (kernel_ms) *kernel_ms = c->compare ? c->compare->blocks_ms : 0.0;
+    return MSIM_OK;
+}
+
+// measurement support (tools/compare_bench.py --blocks; exported, not part of msim.h): msim_cmp_blocks_timing by kernel -- ms[0]
+// k_blk_scan, ms[1] k_blk_replay -- and the replay's lane-steps since msim_reset_stats: steps[0] the bytes its lanes compared,
+// steps[1] 64 x the longest lane of every wave, summed (what the waves occupied)
+int msim_dbg_cmp_blocks_split(msim_ctx *p, double ms[2], uint64_t steps[2]) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c || !ms || !steps) return MSIM_ERR_ARG;
+    const CompareState *S = c->compare;
+    ms[0] = S ? S->scan_ms : 0.0;
+    ms[1] = S ? S->replay_ms : 0.0;
+    steps[0] = S ? S->replay_steps : 0;
+    steps[1] = S ? S->replay_wave_steps : 0;
+    return MSIM_OK;
 }
 
 int msim_cmp_fetch(msim_ctx *p, int contig, uint64_t *n_held, uint64_t *held_pool_len, msim_record *held, uint8_t *held_pool,
@@ -662,6 +797,49 @@ int msim_dbg_cmp_counts(const uint8_t *bases, uint64_t L, const msim_record *tru
         if (!cmp::known_type(calls[i].type)) return fail(nullptr, MSIM_ERR_ARG, "calls record " + std::to_string(i) + ": unknown type");
     dbg_counts<2>(bases, L, Side{{truth, n_truth, truth_pool, truth_pool_len}, nullptr, truth_flags},
                   Side{{calls, n_calls, calls_pool, calls_pool_len}, nullptr, calls_flags}, flags, counts, tallies);
+    return MSIM_OK;
+}
+
+// msim_cmp_counts_blocks as sequential loops: the match (dbg_counts), then every record of either table in turn -- head test, walk,
+// replay, rescue (cmp_blocks.h) --, then the counters from the final flag bytes.
+int msim_dbg_cmp_counts_blocks(const uint8_t *bases, uint64_t L, const msim_record *truth, uint64_t n_truth, const uint8_t *truth_pool,
+                               uint64_t truth_pool_len, const msim_record *calls, uint64_t n_calls, const uint8_t *calls_pool,
+                               uint64_t calls_pool_len, uint32_t flags, uint32_t gap, uint64_t *counts, uint64_t tallies[2],
+                               uint64_t block_tallies[5], uint8_t *truth_flags, uint8_t *calls_flags) {
+    if ((!bases && L) || (!truth && n_truth) || (!calls && n_calls) || (!truth_pool && truth_pool_len) ||
+        (!calls_pool && calls_pool_len) || !counts || !tallies || !block_tallies || (flags & ~(uint32_t)MSIM_CMP_EXACT))
+        return MSIM_ERR_ARG;
+    if (gap > MSIM_CMP_BLOCK_SPAN) return fail(nullptr, MSIM_ERR_ARG, "the block gap is larger than MSIM_CMP_BLOCK_SPAN");
+    if (n_truth >= (1ull << 31) || n_calls >= (1ull << 31)) return fail(nullptr, MSIM_ERR_ARG, "more than 2^31 records");
+    int rc;
+    if ((rc = dbg_table_ok("truth", truth, n_truth, true)) || (rc = dbg_table_ok("calls", calls, n_calls, true))) return rc;
+    std::vector<uint8_t> fa((size_t)n_truth, 0), fb((size_t)n_calls, 0);
+    std::vector<uint64_t> haploid((size_t)8 * MSIM_CMP_BINS * 4);
+    const cmp::Table A{truth, n_truth, truth_pool, truth_pool_len}, B{calls, n_calls, calls_pool, calls_pool_len};
+    dbg_counts<2>(bases, L, Side{A, nullptr, fa.data()}, Side{B, nullptr, fb.data()}, flags, haploid.data(), tallies);
+    memset(block_tallies, 0, 5 * sizeof(uint64_t));
+    for (uint64_t i = 0; i < n_truth + n_calls; i++) {
+        const bool own_is_truth = i < n_truth;
+        const uint64_t own = own_is_truth ? i : i - n_truth;
+        uint64_t other;
+        if (!blk::is_head(own_is_truth ? A : B, own, own_is_truth ? B : A, own_is_truth, gap, &other)) continue;
+        blk::Desc d{};
+        const uint32_t what = blk::walk(A, B, fa.data(), fb.data(), own_is_truth ? own : other, own_is_truth ? other : own, gap, &d);
+        if (what == blk::NOT_A_CANDIDATE) continue;
+        block_tallies[blk::T_CANDIDATE]++;
+        block_tallies[what == blk::REPLAY ? blk::T_REPLAYED : what == blk::OVER_LIMIT ? blk::T_LIMIT : blk::T_TRANSLOCATION]++;
+        if (what != blk::REPLAY || !blk::replay_equal(bases, L, A, B, d)) continue;
+        blk::rescue(fa.data(), fb.data(), d);
+        block_tallies[blk::T_EQUAL]++;
+    }
+    unsigned long long ca[cmp::Score<3>::COUNTERS] = {}, cb[cmp::Score<3>::COUNTERS] = {};
+    for (uint64_t i = 0; i < n_truth; i++) ca[cmp::counter_of<3>(cmp::rec_at(truth, i), fa[(size_t)i])]++;
+    for (uint64_t i = 0; i < n_calls; i++) cb[cmp::counter_of<3>(cmp::rec_at(calls, i), fb[(size_t)i])]++;
+    memset(counts, 0, (size_t)8 * MSIM_CMP_BINS * 6 * sizeof(uint64_t));
+    uint64_t none[2] = {0, 0};
+    finish<3>(ca, cb, counts, none);
+    if (truth_flags && n_truth) memcpy(truth_flags, fa.data(), (size_t)n_truth);
+    if (calls_flags && n_calls) memcpy(calls_flags, fb.data(), (size_t)n_calls);
     return MSIM_OK;
 }
 

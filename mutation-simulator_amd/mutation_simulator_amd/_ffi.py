@@ -185,6 +185,10 @@ SYMBOLS = [
     ("msim_cmp_timing", C.c_int, [_VP, C.POINTER(C.c_double)]),
     ("msim_dbg_cmp_counts", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64,
                                       C.c_uint32, _VP, _VP, _VP, _VP]),
+    ("msim_cmp_counts_blocks", C.c_int, [_VP, C.c_int, C.c_uint32, C.c_uint32, _VP, _VP, _VP]),
+    ("msim_cmp_blocks_timing", C.c_int, [_VP, C.POINTER(C.c_double)]),
+    ("msim_dbg_cmp_counts_blocks", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64,
+                                             C.c_uint32, C.c_uint32, _VP, _VP, _VP, _VP, _VP]),
     ("msim_cmp_join", C.c_int, [_VP, C.c_int, C.c_int]),
     ("msim_cmp_counts_diploid", C.c_int, [_VP, C.c_int, C.c_uint32, _VP, _VP]),
     ("msim_cmp_fetch_diploid", C.c_int, [_VP, C.c_int, C.c_int, _U64P, _U64P, _VP, _VP, _VP, _VP]),
@@ -199,6 +203,8 @@ CMP_EXACT = 1            # msim.h: MSIM_CMP_EXACT, the literal comparison
 CMP_BINS = 5             # msim.h: MSIM_CMP_BINS, the length bins of IN and DE (1, 2-5, 6-20, 21-50, 51 and above)
 CMP_PASS = 256           # msim.h: MSIM_CMP_PASS, the records one workgroup of the compare kernels takes per pass
 CMP_WINDOW = 65536       # msim.h: MSIM_CMP_WINDOW, the bases an indel's placements stay inside
+CMP_BLOCK_GAP = 50       # msim.h: MSIM_CMP_BLOCK_GAP, the default gap of compare --blocks (hap.py's superlocus window)
+CMP_BLOCK_RECORDS, CMP_BLOCK_SPAN = 64, 4096     # msim.h: the records / the bases a block may hold and still be replayed
 CMP_TRUTH, CMP_CALLS = 0, 1          # msim.h: MSIM_CMP_TRUTH, MSIM_CMP_CALLS, the sides of a diploid comparison
 CMP_JOIN_TILE = 1024     # msim.h: MSIM_CMP_JOIN_TILE, the records one workgroup of the diploid join's scan takes
 SPECTRUM_TILE = 4096     # msim.h: MSIM_SPECTRUM_TILE, the bases one workgroup of the spectrum sampler takes
@@ -692,6 +698,24 @@ class Engine:
         """The compare kernels' milliseconds since ``reset_stats`` (HIP events)."""
         a = C.c_double()
         self._check(self.lib.msim_cmp_timing(self.h, C.byref(a)))
+        return a.value
+
+    def cmp_counts_blocks(self, contig: int, exact: bool = False, gap: int = CMP_BLOCK_GAP) -> tuple:
+        """``cmp_counts`` with the unmatched records rescued block by block (msim.h: compare --blocks): (uint64[8, CMP_BINS, 6] --
+        truth matched, truth block-matched, truth missed, calls matched, calls block-matched, calls extra; uint64[2] as
+        ``cmp_counts``; uint64[5]: candidates, replayed, equal, over a limit, holding a translocation).  ``cmp_fetch`` then
+        gives flag bytes 0, 1 or 2 (matched as part of a block)."""
+        counts = np.zeros((8, CMP_BINS, 6), dtype=np.uint64)
+        tallies = np.zeros(2, dtype=np.uint64)
+        blocks = np.zeros(5, dtype=np.uint64)
+        self._check(self.lib.msim_cmp_counts_blocks(self.h, int(contig), CMP_EXACT if exact else 0, int(gap), _ptr(counts),
+                                                    _ptr(tallies), _ptr(blocks)), contig)
+        return counts, tallies, blocks
+
+    def cmp_blocks_timing(self) -> float:
+        """The block pass's milliseconds on the device since ``reset_stats`` (HIP events)."""
+        a = C.c_double()
+        self._check(self.lib.msim_cmp_blocks_timing(self.h, C.byref(a)))
         return a.value
 
     def cmp_join(self, contig: int, side: int):
@@ -1333,6 +1357,26 @@ def cmp_counts_host(bases, truth, truth_pool, calls, calls_pool, exact: bool = F
     tallies, truth flags, calls flags) -- by a sequential host loop over ``bases`` (uint8, upper-cased) and two tables
     (RECORD_DTYPE, insert pools uint8).  No context, no GPU."""
     return _cmp_counts_host(bases, (truth, truth_pool), (calls, calls_pool), exact)
+
+
+def cmp_counts_blocks_host(bases, truth, truth_pool, calls, calls_pool, exact: bool = False, gap: int = CMP_BLOCK_GAP) -> tuple:
+    """``msim_dbg_cmp_counts_blocks``: what ``Engine.cmp_counts_blocks`` returns and the two flag arrays of ``Engine.cmp_fetch``
+    behind it -- (counts, tallies, block tallies, truth flags, calls flags) -- by sequential host loops.  No context, no GPU."""
+    lib = load()
+    bases = _as_u8(bases)
+    truth, calls = (np.ascontiguousarray(t, dtype=RECORD_DTYPE) for t in (truth, calls))
+    truth_pool, calls_pool = (np.ascontiguousarray(p, dtype=np.uint8) for p in (truth_pool, calls_pool))
+    counts = np.zeros((8, CMP_BINS, 6), dtype=np.uint64)
+    tallies = np.zeros(2, dtype=np.uint64)
+    blocks = np.zeros(5, dtype=np.uint64)
+    fa = np.zeros(len(truth), dtype=np.uint8)
+    fb = np.zeros(len(calls), dtype=np.uint8)
+    rc = lib.msim_dbg_cmp_counts_blocks(_opt_ptr(bases), len(bases), _opt_ptr(truth), len(truth), _opt_ptr(truth_pool), len(truth_pool),
+                                        _opt_ptr(calls), len(calls), _opt_ptr(calls_pool), len(calls_pool), CMP_EXACT if exact else 0,
+                                        int(gap), _ptr(counts), _ptr(tallies), _ptr(blocks), _opt_ptr(fa), _opt_ptr(fb))
+    if rc != OK:
+        raise _host_error(rc)
+    return counts, tallies, blocks, fa, fb
 
 
 def cmp_join_host(h1, pool1, h2, pool2) -> tuple:

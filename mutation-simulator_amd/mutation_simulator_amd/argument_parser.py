@@ -9,7 +9,9 @@ the SBS-96 spectrum of a VCF's SNPs against the reference, counted on the GPU; i
 VCF scored against a truth VCF on the GPU, indels matched up to their placement inside a repeat; it writes
 ``<outbase>_ms.compare.tsv`` and, with ``--list``, ``<outbase>_ms.compare.records.tsv``; ``--diploid`` joins both haplotypes of each
 side and scores genotypes by dosage -- a ``GT`` column, ``GT`` lines in the records file; it is a usage error together with
-``--haplotype`` or ``--truth-haplotype``; ``compare_refusal`` words what it does not cover).
+``--haplotype`` or ``--truth-haplotype``; ``--blocks [--block-gap N]`` rescues unmatched records whose block of neighbours writes
+the same bases on both sides -- ``BLK`` columns and lines; a usage error together with ``--diploid``, as is ``--block-gap`` without
+``--blocks``; ``compare_refusal`` words what it does not cover).
 
 ``--ploidy 2 [--het F]`` (``args`` / ``rmt``) writes two haplotype Fastas, ``<outbase>_ms_h1<suffix>`` and ``<outbase>_ms_h2<suffix>``
 (``args.outfasta_h1`` / ``outfasta_h2``; ``<outbase>_ms<suffix>`` is not written), one phased ``<outbase>_ms.vcf`` and, with ``--chain``,
@@ -213,6 +215,14 @@ def build_parser() -> ArgumentParser:
                             "the wrong dosage is reported as GT. Cannot be combined with --truth-haplotype or --haplotype")
     p_cmp.add_argument("--exact", action="store_true", default=False,
                        help="Compare positions literally: an indel placed elsewhere in its repeat counts as missed and as extra")
+    p_cmp.add_argument("--blocks", action="store_true", default=False,
+                       help="Rescue unmatched records block by block: neighbouring records of both files are replayed onto the "
+                            "reference, and where the truth's and the calls' records of a block write the same bases (an MNP "
+                            "against two SNPs, a duplication against the insertion it is) they count as matched (BLK columns). "
+                            "Cannot be combined with --diploid")
+    p_cmp.add_argument("--block-gap", type=int, default=None, metavar="N", dest="block_gap",
+                       help="With --blocks: a record joins the block in front of it when it stands at most N bases behind it "
+                            "(0 to 4096). Default = 50")
     p_cmp.add_argument("--per-contig", action="store_true", default=False, dest="per_contig",
                        help="Repeat the table per contig behind the genome-wide one")
     p_cmp.add_argument("--list", action="store_true", default=False, dest="list_records",
@@ -324,6 +334,12 @@ def get_args(argv=None) -> Namespace:
             parser.error("--haplotype and --truth-haplotype count from 1")
         if args.diploid and (args.haplotype is not None or args.truth_haplotype is not None):
             parser.error("--diploid scores both haplotypes of each side: --haplotype and --truth-haplotype do not apply")
+        if args.block_gap is not None and not args.blocks:
+            parser.error("--block-gap needs --blocks")
+        if args.blocks and args.diploid:
+            parser.error("--blocks compares one haplotype against one: it cannot be combined with --diploid")
+        if args.block_gap is not None and not 0 <= args.block_gap <= 4096:
+            parser.error("--block-gap must lie in 0..4096")
     if args.quiet:
         args.ignore_warnings = True
         args.no_progress = True

@@ -18,6 +18,12 @@ truth matches the i-th of the calls.  Counts come per record type and, for inser
 is ignored, a haploid ``1`` counts as ``1/1``).  ``msim_cmp_counts_diploid`` matches the truth's table against the calls' by the
 same rules and compares the dosages: the table gains a ``GT`` column -- pairs found with the wrong genotype, which count in ``FN``
 and in ``FP`` as hap.py reports them.  One renderer writes both tables: the counts' last axis (4 or 6) says which.
+
+``--blocks [--block-gap N]`` (haploid only) rescues records the match leaves unmatched although both files describe the same
+sequence: ``msim_cmp_counts_blocks`` cuts both tables into blocks of neighbouring records, replays every block that holds an
+unmatched record -- the bytes the rewrite writes with the truth's records of the block alone against the bytes it writes with the
+calls' alone (csrc/cmp_blocks.hip) -- and marks the unmatched records of an equal block as matched as part of a block.  The table
+gains ``TP.calls``, ``BLK`` and ``BLK.calls``, the comment lines a ``blocks:`` line, the records file ``BLK`` lines.
 """
 from __future__ import annotations
 
@@ -33,6 +39,7 @@ BIN_NAMES = ("1", "2-5", "6-20", "21-50", "51+")                          # msim
 ROWS = [(t, b) for t in range(1, 8) for b in (range(_ffi.CMP_BINS) if t in (2, 3) else (0,))]
 HEADER = ("type", "length", "truth", "calls", "TP", "FN", "FP", "recall", "precision")
 HEADER_DIPLOID = HEADER[:7] + ("GT",) + HEADER[7:]                        # --diploid: counts[..., 6]
+HEADER_BLOCKS = HEADER[:7] + ("TP.calls", "BLK", "BLK.calls") + HEADER[7:]  # --blocks: counts[..., 6], the middle outcome block-matched
 
 
 class CompareError(Exception):
@@ -65,35 +72,47 @@ def row_cells(kind: str, length: str, v) -> list:
     return [kind, length, str(tm + fn), str(cm + fp), str(tm), str(fn), str(fp)] + gt + [ratio(tm, tm + fn), ratio(cm, cm + fp)]
 
 
-def render_block(counts) -> list:
-    """The rows of one ``counts[8][CMP_BINS][4]`` (``[6]``: with the ``GT`` column): a row per type and length bin, then ALL."""
+def row_cells_blocks(kind: str, length: str, v) -> list:
+    """One row of the ``--blocks`` table from (truth matched, block-matched, missed, calls matched, block-matched, extra): a
+    block-matched record is a true positive on its side -- ``TP`` and ``TP.calls`` hold both kinds, ``BLK`` and ``BLK.calls`` the
+    block-matched part (a block pairs records, not one with one: the two sides' counts differ)."""
+    tm, tb, fn, cm, cb, fp = (int(x) for x in v)
+    return [kind, length, str(tm + tb + fn), str(cm + cb + fp), str(tm + tb), str(fn), str(fp), str(cm + cb), str(tb), str(cb),
+            ratio(tm + tb, tm + tb + fn), ratio(cm + cb, cm + cb + fp)]
+
+
+def render_block(counts, blocks: bool = False) -> list:
+    """The rows of one ``counts[8][CMP_BINS][4]`` (``[6]``: with the ``GT`` column or, with ``blocks``, the ``BLK`` columns): a row
+    per type and length bin, then ALL."""
     counts = np.asarray(counts, dtype=np.uint64)
     width = counts.shape[-1]
-    lines = ["\t".join(HEADER_DIPLOID if width == 6 else HEADER)]
+    cells = row_cells_blocks if blocks else row_cells
+    lines = ["\t".join(HEADER_BLOCKS if blocks else HEADER_DIPLOID if width == 6 else HEADER)]
     for t, b in ROWS:
-        lines.append("\t".join(row_cells(TYPE_NAMES[t], BIN_NAMES[b] if t in (2, 3) else ".", counts[t, b])))
-    lines.append("\t".join(row_cells("ALL", ".", counts.reshape(-1, width).sum(axis=0, dtype=np.uint64))))
+        lines.append("\t".join(cells(TYPE_NAMES[t], BIN_NAMES[b] if t in (2, 3) else ".", counts[t, b])))
+    lines.append("\t".join(cells("ALL", ".", counts.reshape(-1, width).sum(axis=0, dtype=np.uint64))))
     return lines
 
 
-def render(notes, counts, names=None) -> str:
+def render(notes, counts, names=None, blocks: bool = False) -> str:
     """The text of ``*_ms.compare.tsv``: ``#`` comment lines (``notes``), the genome-wide block (the sum of ``counts`` over
     its first axis, the contigs) and, with ``names``, a ``# contig NAME`` line and a block per contig."""
     counts = np.asarray(counts, dtype=np.uint64)
     lines = [f"# {note}" for note in notes]
-    lines += render_block(counts.sum(axis=0, dtype=np.uint64))
+    lines += render_block(counts.sum(axis=0, dtype=np.uint64), blocks)
     for i, name in enumerate(names or ()):
         lines.append(f"# contig {name}")
-        lines += render_block(counts[i])
+        lines += render_block(counts[i], blocks)
     return "\n".join(lines) + "\n"
 
 
-def record_rows(kind: str, contig: str, recs, flags) -> list:
-    """The lines of ``--list`` for one table: every record whose flag byte is 0."""
+def record_rows(kind: str, contig: str, recs, flags, flag: int = 0, side=None) -> list:
+    """The lines of ``--list`` for one table: every record whose flag byte is ``flag`` (0: unmatched; 2, with ``--blocks``:
+    matched as part of a block -- ``BLK`` lines, which name their ``side``, ``truth`` or ``calls``, in a sixth field)."""
     out = []
-    for r in recs[np.asarray(flags) == 0]:
+    for r in recs[np.asarray(flags) == flag]:
         out.append("\t".join([kind, contig, str(int(r["pos"]) + 1), TYPE_NAMES[int(r["type"])],
-                              str(int(r["stop"]) - int(r["pos"]) + 1)]))
+                              str(int(r["stop"]) - int(r["pos"]) + 1)] + ([side] if side else [])))
     return out
 
 
@@ -134,6 +153,7 @@ class Compare:
         self.stats: dict = {}
         self.counts = None           # uint64[contigs, 8, CMP_BINS, 4] of the last run ([..., 6] with --diploid)
         self.tallies = None          # uint64[contigs, 2]
+        self.block_tallies = None    # uint64[contigs, 5] (--blocks)
 
     def _plan(self, eng, side: str, path, names, cids, sample, haplotype):
         """One file's tables onto the contigs; (bytes of its text, load kernel ms, plan kernel ms)."""
@@ -165,6 +185,11 @@ class Compare:
         eng = self._engine
         _, names, cids = resident_genome(eng, fa, "compare")
         diploid, listing = bool(getattr(args, "diploid", False)), bool(getattr(args, "list_records", False))
+        blocks = bool(getattr(args, "blocks", False))
+        gap = getattr(args, "block_gap", None)
+        gap = _ffi.CMP_BLOCK_GAP if gap is None else int(gap)
+        if blocks and diploid:
+            raise CompareError("--blocks compares one haplotype against one: it cannot be combined with --diploid")
         truth_sample, sample = getattr(args, "truth_sample", None), getattr(args, "sample", None)
         if diploid:
             join0 = eng.cmp_join_timing()
@@ -179,22 +204,33 @@ class Compare:
         # every line of both files is accepted: count, contig by contig
         exact = bool(getattr(args, "exact", False))
         cmp0 = eng.cmp_timing()                        # (a caller's engine may have compared before)
+        blk0 = eng.cmp_blocks_timing() if blocks else 0.0
         n = len(cids)
-        self.counts = np.zeros((n, 8, _ffi.CMP_BINS, 6 if diploid else 4), dtype=np.uint64)
+        self.counts = np.zeros((n, 8, _ffi.CMP_BINS, 6 if diploid or blocks else 4), dtype=np.uint64)
         self.tallies = np.zeros((n, 2), dtype=np.uint64)
+        self.block_tallies = np.zeros((n, 5), dtype=np.uint64)
         listed = []
         for i, cid in enumerate(cids):
-            self.counts[i], self.tallies[i] = eng.cmp_counts_diploid(cid, exact) if diploid else eng.cmp_counts(cid, exact)
+            if blocks:
+                self.counts[i], self.tallies[i], self.block_tallies[i] = eng.cmp_counts_blocks(cid, exact, gap)
+            else:
+                self.counts[i], self.tallies[i] = eng.cmp_counts_diploid(cid, exact) if diploid else eng.cmp_counts(cid, exact)
             if listing and diploid:
                 a, _, ga, fa_flags = eng.cmp_fetch_diploid(cid, _ffi.CMP_TRUTH)
                 b, _, gb, fb_flags = eng.cmp_fetch_diploid(cid, _ffi.CMP_CALLS)
                 listed += record_rows_diploid(names[i], a, ga, fa_flags, b, gb, fb_flags)
             elif listing:
                 held, _, fa_flags, fb_flags = eng.cmp_fetch(cid)
+                current = eng.fetch_records(cid)[0]
                 listed += record_rows("FN", names[i], held, fa_flags)
-                listed += record_rows("FP", names[i], eng.fetch_records(cid)[0], fb_flags)
+                listed += record_rows("FP", names[i], current, fb_flags)
+                if blocks:
+                    listed += record_rows("BLK", names[i], held, fa_flags, 2, "truth")
+                    listed += record_rows("BLK", names[i], current, fb_flags, 2, "calls")
         self.stats = {"truth_vcf_bytes": truth[0], "calls_vcf_bytes": calls[0], "vcf_load_kernel_ms": truth[1] + calls[1],
                       "vcf_plan_kernel_ms": truth[2] + calls[2], "cmp_kernel_ms": round(eng.cmp_timing() - cmp0, 4)}
+        if blocks:
+            self.stats["cmp_block_kernel_ms"] = round(eng.cmp_blocks_timing() - blk0, 4)
         if diploid:
             self.stats["cmp_join_kernel_ms"] = round(eng.cmp_join_timing() - join0, 4)
         else:
@@ -222,7 +258,13 @@ class Compare:
                  f"truth indels whose placements end at a base outside ACGT: {int(tallies[1])}"]
         if diploid:
             notes.insert(3, "genotypes: diploid, unphased (dosage compared; a haploid 1 counts as 1/1)")
-        return render(notes, self.counts, names if getattr(args, "per_contig", False) else None)
+        blocks = bool(getattr(args, "blocks", False))
+        if blocks:
+            gap = getattr(args, "block_gap", None)
+            t = [int(x) for x in self.block_tallies.sum(axis=0, dtype=np.uint64)]
+            notes.append(f"blocks: gap {_ffi.CMP_BLOCK_GAP if gap is None else int(gap)}; {t[0]} candidates, {t[1]} replayed, {t[2]} equal, "
+                         f"{t[3]} over a limit ({_ffi.CMP_BLOCK_RECORDS} records, {_ffi.CMP_BLOCK_SPAN} bases), {t[4]} holding a translocation")
+        return render(notes, self.counts, names if getattr(args, "per_contig", False) else None, blocks)
 
     def close(self):
         eng = self._engine

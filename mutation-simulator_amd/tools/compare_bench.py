@@ -15,7 +15,18 @@ and each side goes the way of `compare --diploid`: haplotype 1 selected and held
 above, which are taken first in the same process on the same full tables (the join's held table replaces the haploid run's):
   cmp_join_kernel_ms        the join of the calls' two haplotype tables (msim_cmp_join_timing: its kernels and two pool copies)
   join_copy_floor_ms        a device-to-device copy of the bytes that join reads and writes (msim_dbg_cmp_join_copy_floor)
-  cmp_diploid_kernel_ms     k_cmp_match<3> + k_cmp_tally<3>, to hold against cmp_kernel_ms"""
+  cmp_diploid_kernel_ms     k_cmp_match<3> + k_cmp_tally<3>, to hold against cmp_kernel_ms
+
+With --blocks (anywhere on the line) the same two tables -- where nearly every block is a candidate: the worst case -- go through
+`compare --blocks` (msim_cmp_counts_blocks) as well, and then a second calls table DERIVED from the truth (the realistic case): about
+1 % of its records picked and re-represented -- an SN with room behind it as a deletion and an insertion (an MNP line), a deletion of
+two bases or more in two pieces, a duplication as the insertion it is; a picked record with no other form (IN, IV, a one-base DE) is
+dropped one time in four and kept otherwise -- and installed with msim_dbg_set_records.  Per table pair, medians of `runs` with min and max:
+  cmp_block_kernel_ms       k_blk_scan + k_blk_replay (msim_cmp_blocks_timing)
+  cmp_kernel_ms_in_blocks   k_cmp_match<2> + k_cmp_tally<3> of the same calls (msim_cmp_timing)
+  blk_scan_ms, blk_replay_ms   the two kernels apart, and replay_lane_use: the bytes the replay's lanes compared over 64 x the
+                            longest lane of every wave -- what blocks of different lengths leave of a wave (msim_dbg_cmp_blocks_split)
+the derived pair's figures under derived_*, with its own cmp_kernel_ms (no blocks) and copy floor."""
 import ctypes as C
 import json
 import statistics
@@ -25,6 +36,8 @@ from pathlib import Path
 ROOT = Path(__file__).resolve().parents[2]
 for p in (ROOT, ROOT / "mutation-simulator_amd", ROOT / "tests"):
     sys.path.insert(0, str(p))
+
+import numpy as np  # noqa: E402
 
 import bench  # noqa: E402
 from mutation_simulator_amd import _ffi  # noqa: E402
@@ -48,10 +61,66 @@ def join_pass_one(eng, cid, side, before_join=None):
     eng.cmp_join(cid, side)
 
 
+def snp_alt_table():
+    """alt[aux, base]: the byte an SN writes (tests/apply_ref.py's tables; 0: the reference has none)."""
+    import apply_ref
+    conv = apply_ref.NON_AMBIGUOUS
+    alt = np.zeros((3, 256), dtype=np.uint8)
+    alt[0] = apply_ref.TRANSITIONS[conv]
+    for x in range(256):
+        pair = apply_ref.TRANSVERSIONS.get(chr(int(conv[x])))
+        if pair:
+            alt[1, x], alt[2, x] = ord(pair[0]), ord(pair[1])
+    return alt
+
+
+def derived_calls(eng, cid, share=0.01):
+    """The contig's held table with `share` of its records picked and re-represented (see above): (records, pool)."""
+    a, pa, _, _ = eng.cmp_fetch(cid, flags=False)
+    g = eng.read_contig(cid)
+    n = len(a)
+    rs = np.random.RandomState(cid)
+    pick = rs.random_sample(n) < share
+    pos = a["pos"].astype(np.int64)
+    length = a["stop"].astype(np.int64) - pos + 1
+    nxt = np.append(pos[1:], len(g))
+    alt = snp_alt_table()[a["aux"] % 3, g[pos]]
+    as_mnp = pick & (a["type"] == 1) & (pos + 3 <= nxt) & (alt != 0)       # an SN as a DE and an IN behind it
+    split = pick & (a["type"] == 3) & (length >= 2)                        # a DE in two pieces
+    to_in = pick & (a["type"] == 4)                                        # a DU as the IN it is
+    drop = pick & ~as_mnp & ~split & ~to_in & (rs.random_sample(n) < 0.25)
+    reps = np.ones(n, dtype=np.int64)
+    reps[split | as_mnp] = 2
+    reps[drop] = 0
+    b = np.repeat(a, reps)
+    first = np.cumsum(reps) - reps
+    i1 = first[split]
+    b["stop"][i1] = b["pos"][i1]
+    b["pos"][i1 + 1] += 1
+    j1 = first[as_mnp]
+    b["type"][j1], b["aux"][j1] = 3, 0
+    b["type"][j1 + 1], b["aux"][j1 + 1] = 2, 0
+    b["pos"][j1 + 1] += 1
+    b["stop"][j1 + 1] = b["pos"][j1 + 1]
+    b["extra"][j1 + 1] = len(pa) + np.arange(len(j1))
+    inserts, off = [pa, alt[as_mnp]], len(pa) + len(j1)
+    for k in np.flatnonzero(to_in):
+        b["type"][first[k]] = 2
+        b["extra"][first[k]] = off
+        inserts.append(g[pos[k]:pos[k] + length[k]])
+        off += int(length[k])
+    return b, np.concatenate(inserts)
+
+
 def main():
     diploid = "--diploid" in sys.argv
     if diploid:
         sys.argv.remove("--diploid")
+    blocks = "--blocks" in sys.argv
+    if blocks:
+        sys.argv.remove("--blocks")
+    if blocks and diploid:
+        sys.exit("--blocks replaces the calls' tables: run it without --diploid")
     runs = max(7, int(sys.argv[1])) if len(sys.argv) > 1 else 7
     total = int(float(sys.argv[2])) if len(sys.argv) > 2 else 3_000_000_000
     out_path = Path(sys.argv[3]) if len(sys.argv) > 3 else None
@@ -62,6 +131,8 @@ def main():
     copy_floor.restype, copy_floor.argtypes = C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
     join_floor = _ffi.load().msim_dbg_cmp_join_copy_floor
     join_floor.restype, join_floor.argtypes = C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+    split = _ffi.load().msim_dbg_cmp_blocks_split
+    split.restype, split.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     eng = _ffi.Engine(0, _ffi.RNG_FAST)
     res = {"bases": sum(lengths), "contigs": len(lengths), "runs": runs, "device": eng.device_name()}
     try:
@@ -125,6 +196,45 @@ def main():
         for _ in range(runs):
             rows.append(kernel_pass()[0])
             floors.append(copy_pass())
+
+        def blocks_pass():
+            eng.reset_stats()
+            got = [eng.cmp_counts_blocks(cid) for cid in cids]
+            counts, tallies = sum(g[0] for g in got), sum(g[2] for g in got)
+            assert int(counts[..., :3].sum()) == records[0] and int(counts[..., 3:].sum()) == records[1]
+            assert int(tallies[0]) == int(tallies[1]) + int(tallies[3]) + int(tallies[4])
+            ms, steps = (C.c_double * 2)(), (C.c_uint64 * 2)()
+            eng._check(split(eng.h, ms, steps))
+            return eng.cmp_blocks_timing(), eng.cmp_timing(), counts, tallies, ms[0], ms[1], steps[0] / max(1, steps[1])
+
+        def blocks_runs(prefix):
+            _, _, counts, tallies, *_ = blocks_pass()      # warm-up: code objects, the descriptors' allocation
+            res[prefix + "block_matched"] = [int(counts[..., 1].sum()), int(counts[..., 4].sum())]
+            res[prefix + "block_tallies"] = [int(t) for t in tallies]
+            got = [blocks_pass() for _ in range(runs)]
+            res[prefix + "replay_lane_use"] = got[0][6]
+            for name, col in (("cmp_block_kernel_ms", 0), ("cmp_kernel_ms_in_blocks", 1), ("blk_scan_ms", 4), ("blk_replay_ms", 5)):
+                res[prefix + name] = statistics.median(g[col] for g in got)
+                res[prefix + name + "_min_max"] = [min(g[col] for g in got), max(g[col] for g in got)]
+
+        if blocks:                                     # (in front of the joins: they consume the held tables)
+            blocks_runs("")
+            for cid in cids:
+                eng.set_records(cid, *derived_calls(eng, cid))
+            records[1] = sum(eng.result_sizes(cid, applied=False)[1] for cid in cids)
+            res["derived_calls_records"] = records[1]
+            _, counts, _ = kernel_pass()
+            res["derived_matched"] = int(counts[..., 0].sum())
+            plain, plain_floor = [], []
+            for _ in range(runs):
+                plain.append(kernel_pass()[0])
+                plain_floor.append(copy_pass())
+            res["derived_cmp_kernel_ms"] = statistics.median(plain)
+            res["derived_cmp_kernel_ms_min_max"] = [min(plain), max(plain)]
+            res["derived_copy_floor_ms"] = statistics.median(plain_floor)
+            res["derived_copy_floor_ms_min_max"] = [min(plain_floor), max(plain_floor)]
+            blocks_runs("derived_")
+            records[1] = res["calls_records"]              # (the figures below are the independent pair's)
         if diploid:                                    # (behind the haploid runs: the joins' held tables replace theirs)
             join_pass()
             _, dcounts = diploid_pass()
