@@ -775,6 +775,26 @@ int msim_dbg_cmp_counts_diploid(const uint8_t *bases, uint64_t L, const msim_rec
 int msim_dbg_snp_draws(msim_ctx *ctx, const uint32_t *words, uint64_t n_words, uint64_t ti_lim, uint64_t start, uint32_t K,
                        uint32_t aux_off, uint32_t *lanes, uint32_t *maps, uint64_t *end_pos, uint32_t *flags, uint8_t *aux);
 
+/* ---- test support: the sampler's tail rounds and stream cut on the caller's tables -------------------------------- */
+/* One launch of the kernel that ends a random.sample() on the device -- the tail rounds (every duplicate costs one more accepted
+ * draw, first occurrences win) and the exact stream cut (one past the word that holds the last accepted draw consumed) -- over
+ * tables the caller made, in buffers of the call's own: synchronous, no contig, no stream session.
+ *   words:  raw (untempered) CPython-stream words; the sample's window is words[p0, p0 + W), p0 = state->pos or, anchored,
+ *           win_pos; a draw is accepted when temper(word) >> shift < n
+ *   acc:    the accepted draws of the window in order from accepted index acc_first on (n_acc of them; all < n)
+ *   blocks: raw_counts 1: the accepted draws per block of 2048 window words (n_blocks = ceil(W / 2048) <= 8192 entries);
+ *           raw_counts 0: their exclusive prefix sums, n_blocks + 1 entries
+ *   k:      accepted draws already consumed in front of the rounds (anchored: + need0); the rounds start with state->dups
+ *           duplicates to replace (anchored: d1)
+ *   bitmap: bm_guard guard words, ceil(n / 32) words, bm_guard guard words -- in and out, guards included
+ *   state:  in and out; flags bit 0 = the window does not hold enough accepted draws, or the cut lay beyond pos_limit
+ *           (then clamped to it)                                                                                         */
+typedef struct msim_dbg_tail_state { uint64_t pos, snp_base; uint32_t flags, dups, accepted_used, rsv; } msim_dbg_tail_state;
+int msim_dbg_sample_tail(msim_ctx *ctx, const uint32_t *words, uint64_t n_words, const uint32_t *acc, uint64_t n_acc,
+                         uint32_t acc_first, const uint32_t *blocks, uint32_t n_blocks, uint32_t raw_counts, uint32_t W,
+                         uint32_t shift, uint32_t n, uint32_t k, uint32_t *bitmap, uint32_t bm_guard, msim_dbg_tail_state *state,
+                         int anchored, uint64_t win_pos, uint32_t need0, uint32_t d1, uint64_t pos_limit);
+
 /* ---- stats -------------------------------------------------------------------------------------- */
 int msim_stats(msim_ctx *ctx, msim_timing *out);
 int msim_reset_stats(msim_ctx *ctx);

@@ -973,8 +973,22 @@ static int enqueue_err_copies(Ctx *c) {
     return MSIM_OK;
 }
 
+int apply_ride_err_copies(Ctx *c) {
+    if (c->fast || c->pending_apply.empty() || c->errs_riding) return MSIM_OK;
+    for (int idx : c->pending_apply) {
+        if (idx < 0 || (size_t)idx >= c->contigs.size()) continue;
+        const hipStream_t s = c->contigs[(size_t)idx].apply_stream;
+        if (s && s != c->emit_stream) return MSIM_OK;      // (an APPLY elsewhere: apply_finish waits for it first, as before)
+    }
+    const int rc = enqueue_err_copies(c);
+    if (rc) return rc;
+    c->errs_riding = true;
+    return MSIM_OK;
+}
+
 int apply_finish(Ctx *c) {
-    bool have_errs = false;
+    bool have_errs = c->errs_riding;                       // (enqueued behind every pending APPLY, in front of the pass's host wait)
+    c->errs_riding = false;
     {   // sizes the counter-based engine left on the device (synchronises its streams; no-op when nothing is pending).  The
         // KeyError words ride behind its lanes' work, under the same host wait.
         int state = 0;
@@ -999,7 +1013,7 @@ int apply_finish(Ctx *c) {
         }
         const int rc = fast_plan_collect(c, ride ? enqueue_err_copies : nullptr, &state);
         if (rc) { c->pending_apply.clear(); for (auto &g : c->contigs) g.apply_pending = g.dyn_applied = false; return rc; }
-        have_errs = state == 1;
+        have_errs = have_errs || state == 1;
     }
     if (c->pending_apply.empty()) return MSIM_OK;
     {   // APPLYs that ran on a stream of their own (counter-based engine)
@@ -1014,8 +1028,8 @@ int apply_finish(Ctx *c) {
     if (!have_errs) {                                      // (two blocking hipMemcpy cost ~40 us each at every step boundary)
         const int rc = enqueue_err_copies(c);
         if (rc) return rc;
-        MSIM_HIP(c, wait_stream(c->emit_stream));
     }
+    MSIM_HIP(c, wait_stream(c->emit_stream));
     unsigned long long *errs = c->h_errs.p(), *deltas = c->h_errs.p() + nc;
     bool delta_mismatch = false;
     hipEvent_t origin = nullptr;

@@ -123,6 +123,7 @@ struct Ctx {
     Pinned<unsigned long long> h_mail;      // pinned, device-visible mailbox for small results
     Scratch<unsigned long long> d_errs;     // one KeyError word per contig
     Pinned<unsigned long long> h_errs;      // pinned copy of them (apply_finish)
+    bool errs_riding = false;               //   ... already on its way behind the pending APPLYs (apply_ride_err_copies)
     std::vector<int> pending_apply;
     // text on the device (text_gpu.hip): rendered VCF lines / framed FASTA body / raw FASTA body staging
     Scratch<uint8_t> d_text;
@@ -461,6 +462,9 @@ int apply_contig_device(Ctx *c, Contig &g);
 // and the three-contig rewrite kernel runs at 0.76 of the HBM peak inside the pipeline instead of 0.67 -- fewer ramps and tails)
 int apply_batch_device(Ctx *c, const std::vector<int> &ids, bool batch_rewrites);
 int apply_finish(Ctx *c);             // collect results of asynchronous APPLYs (timing, KeyError words)
+// Before the host waits for a pass (gpu_plan_finish): where every pending APPLY ran on the emit stream, the copies apply_finish
+// will read are enqueued behind them now and Ctx::errs_riding says so; the apply_finish that follows only waits.
+int apply_ride_err_copies(Ctx *c);
 // SNP sampler (plan_gpu.hip: gpu_emit_flush): the expansion kernel writes an SNP-only contig's tile index itself -- room for it,
 // its geometry (tile = 1 << *tile_shift output bytes, *n_tiles of them; n_tiles + 1 entries) and the contig's KeyError word
 uint32_t apply_tile_shift();              // log2 of the rewrite kernels' tile

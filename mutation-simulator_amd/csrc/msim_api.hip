@@ -93,7 +93,7 @@ int ctx_drain(Ctx *c) { return drain(c); }
 static int drain(Ctx *c) {
     if (c->host_only) return MSIM_OK;
     TraceRange tr("msim drain (collect deferred results)");
-    int rc = c->gpu ? gpu_plan_finish(c, c->gpu) : MSIM_OK;
+    int rc = c->gpu ? gpu_plan_finish(c, c->gpu, true) : MSIM_OK;
     int rc2 = apply_finish(c);                             // (collects the counter-based engine's flags and sizes too)
     if (rc) return rc;
     if (rc2) return rc2;
@@ -1481,6 +1481,21 @@ int msim_dbg_snp_draws(msim_ctx *p, const uint32_t *words, uint64_t n_words, uin
     int rc = drain(c);
     if (rc) return rc;
     return gpu_dbg_snp_draws(c, words, n_words, ti_lim, start, K, aux_off, lanes, maps, end_pos, flags, aux);
+}
+
+// The sampler's tail rounds and stream cut (plan_kernels.h: k_sample_tail) over tables the caller made (include/msim.h).
+// Synchronous; touches no contig and no stream session.
+int msim_dbg_sample_tail(msim_ctx *p, const uint32_t *words, uint64_t n_words, const uint32_t *acc, uint64_t n_acc, uint32_t acc_first,
+                         const uint32_t *blocks, uint32_t n_blocks, uint32_t raw_counts, uint32_t W, uint32_t shift, uint32_t n,
+                         uint32_t k, uint32_t *bitmap, uint32_t bm_guard, msim_dbg_tail_state *state, int anchored, uint64_t win_pos,
+                         uint32_t need0, uint32_t d1, uint64_t pos_limit) {
+    CTX_FLUSHED(c, p)
+    if (!c) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    int rc = drain(c);
+    if (rc) return rc;
+    return gpu_dbg_sample_tail(c, words, n_words, acc, n_acc, acc_first, blocks, n_blocks, raw_counts, W, shift, n, k, bitmap, bm_guard,
+                               state, anchored, win_pos, need0, d1, pos_limit);
 }
 
 // The device halves of the SV-mix and host-chain engines over tables the caller made (plan_gpu.hip: gpu_dbg_*): the engines' own

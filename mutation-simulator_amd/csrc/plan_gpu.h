@@ -16,7 +16,9 @@ int gpu_plan_sync_to_host(Ctx *c, GpuPlan *g);
 // optional sizing hint: generate at least this many words ahead on the first extension
 void gpu_plan_reserve(GpuPlan *g, uint64_t py_words, uint64_t np_words);
 // wait for everything enqueued, collect flags + exact stream position (no-op if nothing is pending)
-int gpu_plan_finish(Ctx *c, GpuPlan *g);
+// ride_errs (the context's drain): what apply_finish reads next -- every contig's KeyError and length words -- is copied on the
+// emit stream BEFORE the host waits here, so that the device's last operation is that copy and the host blocks once
+int gpu_plan_finish(Ctx *c, GpuPlan *g, bool ride_errs = false);
 bool gpu_plan_eligible(const Ctx *c, const msim_range *ranges, int n_ranges);
 int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, int n_ranges);
 // SV mixes (SNPs + IN/DE/DU/IV on one large range): sample, type draw, filter, records, insert pool and SNP
@@ -44,6 +46,11 @@ int gpu_dbg_emit_train(Ctx *c, int n_jobs, const uint64_t *const *bm, const uint
 // test support (msim_dbg_snp_draws): the SNP transducer's map, scan and outcome passes over the caller's words
 int gpu_dbg_snp_draws(Ctx *c, const uint32_t *words, uint64_t n_words, uint64_t ti_lim, uint64_t start, uint32_t K, uint32_t aux_off,
                       uint32_t *lanes, uint32_t *maps, uint64_t *end_pos, uint32_t *flags, uint8_t *aux);
+// test support (msim_dbg_sample_tail): one launch of the sampler's tail rounds + cut over the caller's tables
+int gpu_dbg_sample_tail(Ctx *c, const uint32_t *words, uint64_t n_words, const uint32_t *acc, uint64_t n_acc, uint32_t acc_first,
+                        const uint32_t *blocks, uint32_t n_blocks, uint32_t raw_counts, uint32_t W, uint32_t shift, uint32_t n,
+                        uint32_t k, uint32_t *bitmap, uint32_t bm_guard, msim_dbg_tail_state *state, int anchored, uint64_t win_pos,
+                        uint32_t need0, uint32_t d1, uint64_t pos_limit);
 // test support (msim_dbg_candidates / msim_dbg_accept_tables / msim_dbg_mixed_emit): the device halves of the SV-mix and host-chain
 // engines -- the engines' own launch helpers -- over tables the caller made (plan_gpu.hip);
 // rt: MixRangeDev[n_draw], sets: TypeTable[n_sets] (plan_kernels.h)

@@ -150,8 +150,7 @@ struct GpuPlan {
     Staging<uint8_t> h_naux;
     MixSets mm_sets;                                       //   what gpu_plan_multimix_eligible derived for the contig being planned
     const msim_range *mm_for = nullptr; int mm_n = 0;
-    uint32_t *h_seed = nullptr;         // pinned staging of the two host generator states (reseed without a stream sync)
-    hipEvent_t seed_ev[2] = {nullptr, nullptr};   //   recorded behind the copies that read a slot
+    hipEvent_t seed_ev = nullptr;       // recorded behind the launches that start a session's streams (streams_to_device)
     hipStream_t gen_stream = nullptr;   // chunk generation (latency-bound, ~300 us per batch)
     hipStream_t jump_stream = nullptr;  // jump cascade: never waits for a generation batch
     std::vector<hipEvent_t> ev_pool;
@@ -365,8 +364,7 @@ void gpu_plan_destroy(GpuPlan *g) {
     for (auto e : g->grp_ev) if (e) (void)hipEventDestroy(e);
     if (g->t0) (void)hipEventDestroy(g->t0);
     if (g->t1) (void)hipEventDestroy(g->t1);
-    if (g->h_seed) (void)hipHostFree(g->h_seed);
-    for (auto e : g->seed_ev) if (e) (void)hipEventDestroy(e);
+    if (g->seed_ev) (void)hipEventDestroy(g->seed_ev);
     if (g->d_poly) (void)hipFree(g->d_poly);
     if (g->d_ps) (void)hipFree(g->d_ps);
     if (g->h_mail) (void)hipHostFree(g->h_mail);
@@ -396,7 +394,7 @@ static inline uint64_t span_words(const GpuPlan *g) { return (uint64_t)MT_N + (u
 // lasts; util.py:104), the jump tables have: 8192 chunks = 1.31 G words from a session's origin (-sn 0.01: ~20 Gb of genome).
 // Before a contig is handed to a device engine: will its windows fit into what is left of the span?  If not, the session is
 // RE-BASED -- everything in flight is finished, the 624-word window at each stream's exact position goes to the host generators
-// (gpu_plan_sync_to_host: any such window is a valid state) and the engine's stream_to_device makes it the origin of a new
+// (gpu_plan_sync_to_host: any such window is a valid state) and the engine's streams_to_device makes it the origin of a new
 // session; a synchronisation and a fresh cascade every 1.3 G words.  *fits = false: not even an empty span holds this contig
 // (hundreds of millions of candidates on one contig) -- AUTO plans it on the host, which has no such limit.
 // The need is an upper bound built from the engines' own window formulas (plan_windows.h: the very functions enqueue_sample_chain,
@@ -695,19 +693,27 @@ static int ensure_words(Ctx *c, GpuPlan *g, int si, uint64_t upto, bool maps = t
     return MSIM_OK;
 }
 
-// host generator -> device stream
-static int stream_to_device(Ctx *c, GpuPlan *g, int si) {
-    GpuStream &s = g->s[si];
-    HostMT &h = si ? c->np : c->py;
-    if (s.live) return MSIM_OK;
-    if (!s.d_states) {
-        MSIM_HIP(c, hipMalloc(&s.d_states, (size_t)MT_N * sizeof(uint32_t)));
-        s.states_cap = 1;
+// host generators -> device streams, both in one go.  The order matters at a step boundary (a pass reseeds, a cohort run reseeds
+// per genome, a long genome re-bases every 1.3 G words): every host wait comes FIRST, while the side streams are idle and a
+// query of them returns at once; then the device work, one launch per stream with the state in its arguments (k_reseed: h.mt may
+// change right after, the arguments were copied at the launch); then ONE event the side streams are ordered behind.  No host wait
+// depends on anything enqueued here.  (Stream by stream it was: two copies from a pinned slot, an event, barrier packets on the
+// side queues -- and the second stream's routine began by waiting for exactly those queues.)
+static int streams_to_device(Ctx *c, GpuPlan *g) {
+    if (g->s[0].live && g->s[1].live) return MSIM_OK;
+    for (int si = 0; si < 2; si++) {
+        GpuStream &s = g->s[si];
+        if (s.live) continue;
+        if (!s.d_states) {
+            MSIM_HIP(c, hipMalloc(&s.d_states, (size_t)MT_N * sizeof(uint32_t)));
+            s.states_cap = 1;
+        }
+        if (!s.d_raw) {
+            MSIM_HIP(c, hipMalloc(&s.d_raw, (size_t)MT_N * sizeof(uint32_t)));
+            s.cap = MT_N;
+        }
     }
-    if (!s.d_raw) {
-        MSIM_HIP(c, hipMalloc(&s.d_raw, (size_t)MT_N * sizeof(uint32_t)));
-        s.cap = MT_N;
-    }
+    if (!g->d_ps) MSIM_HIP(c, hipMalloc(&g->d_ps, sizeof(PlanState)));
     {
         int rc0 = ensure_side_streams(c, g);
         if (rc0) return rc0;
@@ -715,39 +721,46 @@ static int stream_to_device(Ctx *c, GpuPlan *g, int si) {
     MSIM_HIP(c, wait_stream(g->jump_stream));     // nothing of the old session in flight
     MSIM_HIP(c, wait_stream(g->gen_stream));
     for (auto st : g->prep_streams) if (st) MSIM_HIP(c, wait_stream(st));
-    // the state goes through a pinned staging slot (one per stream), so the copies need no host synchronisation:
-    // h.mt may change right after; the slot is rewritten only once the copies that read it are known to be done,
-    // and the side streams are ordered behind the copies by the same event
-    if (!g->h_seed) MSIM_HIP(c, hipHostMalloc(&g->h_seed, 2 * sizeof h.mt, hipHostMallocDefault));
-    if (!g->seed_ev[si]) MSIM_HIP(c, hipEventCreateWithFlags(&g->seed_ev[si], hipEventDisableTiming));
-    else MSIM_HIP(c, wait_event(g->seed_ev[si]));
-    uint32_t *slot = g->h_seed + (size_t)si * MT_N;
-    memcpy(slot, h.mt, sizeof h.mt);
-    MSIM_HIP(c, hipMemcpyAsync(s.d_states, slot, sizeof h.mt, hipMemcpyHostToDevice, c->stream));
-    MSIM_HIP(c, hipMemcpyAsync(s.d_raw, slot, sizeof h.mt, hipMemcpyHostToDevice, c->stream));
-    MSIM_HIP(c, hipEventRecord(g->seed_ev[si], c->stream));
-    MSIM_HIP(c, hipStreamWaitEvent(g->jump_stream, g->seed_ev[si], 0));
-    MSIM_HIP(c, hipStreamWaitEvent(g->gen_stream, g->seed_ev[si], 0));
-    if (si == 0) for (auto st : g->prep_streams) if (st) MSIM_HIP(c, hipStreamWaitEvent(st, g->seed_ev[si], 0));
-    for (auto e : s.ready_ev) g->ev_pool.push_back(e);
-    s.ready_ev.clear();
-    s.ready_hi.clear();
-    for (auto e : s.words_ev) if (e) g->ev_pool.push_back(e);
-    s.words_ev.clear();
-    s.waited_chunks = 0;
-    s.waited_words = 0;
-    if (si == 0) for (auto &w : g->prep_waited) w = 0;
-    s.casc_pending = false;
-    s.n_states = 1;
-    s.lvl = 0; s.n_src = 1; s.m_done = 0;
-    s.z_lvl = -1;
-    s.n_chunks = 0;
-    s.mapped_blocks = 0;
-    s.maps_ti_lim = c->params.ti_lim;
-    s.pos = (uint64_t)h.idx;
-    s.max_upto = 0;
-    s.live = true;
-    if (si == 0) { g->ps_valid = false; g->verified_pos = s.pos; }
+    if (!g->seed_ev) MSIM_HIP(c, hipEventCreateWithFlags(&g->seed_ev, hipEventDisableTiming));
+    static_assert(sizeof(SeedWords) == sizeof(HostMT::mt), "k_reseed carries a host generator's state words");
+    for (int si = 0; si < 2; si++) {
+        GpuStream &s = g->s[si];
+        if (s.live) continue;
+        HostMT &h = si ? c->np : c->py;
+        SeedWords sw;
+        memcpy(sw.w, h.mt, sizeof sw.w);
+        hipLaunchKernelGGL(k_reseed, dim3(1), dim3(256), 0, c->stream, sw, s.d_states, s.d_raw, si == 0 ? g->d_ps : (PlanState *)nullptr,
+                           (unsigned long long)h.idx);
+        MSIM_HIP(c, hipGetLastError());
+    }
+    MSIM_HIP(c, hipEventRecord(g->seed_ev, c->stream));
+    MSIM_HIP(c, hipStreamWaitEvent(g->jump_stream, g->seed_ev, 0));
+    MSIM_HIP(c, hipStreamWaitEvent(g->gen_stream, g->seed_ev, 0));
+    for (auto st : g->prep_streams) if (st) MSIM_HIP(c, hipStreamWaitEvent(st, g->seed_ev, 0));
+    for (int si = 0; si < 2; si++) {
+        GpuStream &s = g->s[si];
+        if (s.live) continue;
+        HostMT &h = si ? c->np : c->py;
+        for (auto e : s.ready_ev) g->ev_pool.push_back(e);
+        s.ready_ev.clear();
+        s.ready_hi.clear();
+        for (auto e : s.words_ev) if (e) g->ev_pool.push_back(e);
+        s.words_ev.clear();
+        s.waited_chunks = 0;
+        s.waited_words = 0;
+        if (si == 0) for (auto &w : g->prep_waited) w = 0;
+        s.casc_pending = false;
+        s.n_states = 1;
+        s.lvl = 0; s.n_src = 1; s.m_done = 0;
+        s.z_lvl = -1;
+        s.n_chunks = 0;
+        s.mapped_blocks = 0;
+        s.maps_ti_lim = c->params.ti_lim;
+        s.pos = (uint64_t)h.idx;
+        s.max_upto = 0;
+        s.live = true;
+        if (si == 0) { g->ps_valid = true; g->verified_pos = s.pos; }      // (k_reseed started the bookkeeping block at s.pos)
+    }
     return MSIM_OK;
 }
 
@@ -755,9 +768,7 @@ static int stream_to_device(Ctx *c, GpuPlan *g, int si) {
 // session_open: both host generators are device streams (nothing to do inside a session); the device PlanState and its mailbox exist.
 static int session_open(Ctx *c, GpuPlan *g) {
     int rc;
-    if ((rc = stream_to_device(c, g, 0))) return rc;
-    if ((rc = stream_to_device(c, g, 1))) return rc;
-    if (!g->d_ps) MSIM_HIP(c, hipMalloc(&g->d_ps, sizeof(PlanState)));
+    if ((rc = streams_to_device(c, g))) return rc;
     if (!g->h_mail) MSIM_HIP(c, hipHostMalloc(&g->h_mail, sizeof(PlanState), hipHostMallocMapped));
     return MSIM_OK;
 }
@@ -823,7 +834,7 @@ bool gpu_plan_eligible(const Ctx *c, const msim_range *ranges, int n_ranges) {
 }
 
 // Everything enqueued so far has completed: collect the sticky flags and the exact stream position.
-int gpu_plan_finish(Ctx *c, GpuPlan *g) {
+int gpu_plan_finish(Ctx *c, GpuPlan *g, bool ride_errs) {
     {
         const int rc = gpu_emit_flush(c);                  // (a group that is still waiting goes out now)
         if (rc) return rc;
@@ -832,6 +843,10 @@ int gpu_plan_finish(Ctx *c, GpuPlan *g) {
     hipLaunchKernelGGL(k_publish, dim3(1), dim3(1), 0, c->stream, g->d_ps, g->h_mail);
     MSIM_HIP(c, hipGetLastError());
     MSIM_HIP(c, hipEventRecord(g->t1, c->stream));
+    if (ride_errs) {                                       // (the counter-based engine does the same behind its lanes: apply_finish)
+        const int rc = apply_ride_err_copies(c);
+        if (rc) return rc;
+    }
     MSIM_HIP(c, wait_stream(c->stream));
     MSIM_HIP(c, wait_stream(c->emit_stream));
     float ms = 0;
@@ -958,7 +973,7 @@ static int enqueue_sample_chain(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
                            ps, raw_counts);
         hipLaunchKernelGGL(k_bin_dedupe, dim3(n_bins), dim3(512), 0, c->stream, S.bins.p(), S.cursors.p(), bin_cap, S.bitmap.p(),
                            ps);
-        hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(1024), 0, c->stream, raw, S.acc.p(), k, S.cnt.p(), nb, W,
+        hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(TAIL_THREADS), 0, c->stream, raw, S.acc.p(), k, S.cnt.p(), nb, W,
                            (uint32_t)(32 - bits), (uint32_t)n, k, S.bitmap.p(), ps, raw_counts, (const PlanState *)nullptr,
                            (const SpecHdr *)nullptr, (unsigned long long)pos_limit);
     } else {
@@ -966,7 +981,7 @@ static int enqueue_sample_chain(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
         hipLaunchKernelGGL(k_accept_scatter, dim3(nb), dim3(ACC_THREADS), 0, c->stream, raw, ps, W,
                            (uint32_t)(32 - bits), (uint32_t)n, S.cnt.p(), S.acc.p());
         hipLaunchKernelGGL(k_bitmap_insert, dim3((k + 1023) / 1024), dim3(256), 0, c->stream, S.acc.p(), k, S.bitmap.p(), ps);
-        hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(1024), 0, c->stream, raw, S.acc.p(), 0u, S.cnt.p(), nb, W,
+        hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(TAIL_THREADS), 0, c->stream, raw, S.acc.p(), 0u, S.cnt.p(), nb, W,
                            (uint32_t)(32 - bits), (uint32_t)n, k, S.bitmap.p(), ps, 0u, (const PlanState *)nullptr,
                            (const SpecHdr *)nullptr, (unsigned long long)pos_limit);
     }
@@ -1020,7 +1035,7 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
         MSIM_HIP(c, hipDeviceGetStreamPriorityRange(&plo, &phi));
         const int prio = g->prep_i >= g->n_prep - g->n_prep_low ? plo : g->prep_prio > 0 ? plo : g->prep_prio < 0 ? phi : 0;
         MSIM_HIP(c, hipStreamCreateWithPriority(&g->prep_streams[g->prep_i], hipStreamNonBlocking, prio));
-        if (g->seed_ev[0]) MSIM_HIP(c, hipStreamWaitEvent(g->prep_streams[g->prep_i], g->seed_ev[0], 0));   // (the session's first 624 words are a copy)
+        if (g->seed_ev) MSIM_HIP(c, hipStreamWaitEvent(g->prep_streams[g->prep_i], g->seed_ev, 0));   // (the session's first 624 words come from k_reseed)
     }
     g->prep_stream = g->prep_streams[g->prep_i];
     hipStream_t ps_ = g->prep_stream;
@@ -1078,7 +1093,7 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
     hipLaunchKernelGGL(k_ahead_fringe, dim3(G), dim3(ACC_THREADS), 0, c->stream, raw, g->d_ps, ps_core, ps_head, hdr,
                        (unsigned long long)lo, F, S.hcnt.p(), nbh, S.hacc.p(), S.acc.p(), K, k_core, shift, (uint32_t)n, S.bitmap.p(),
                        (unsigned long long)expect, soft_half);
-    hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(1024), 0, c->stream, raw, S.acc.p(), k_core, S.cnt.p(), nb, W, shift, (uint32_t)n,
+    hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(TAIL_THREADS), 0, c->stream, raw, S.acc.p(), k_core, S.cnt.p(), nb, W, shift, (uint32_t)n,
                        k_core, S.bitmap.p(), g->d_ps, 1u, ps_core, hdr, (unsigned long long)e_limit);
     MSIM_HIP(c, hipGetLastError());
     if (!grouped) MSIM_HIP(c, hipEventRecord(S.chain_done, c->stream));
@@ -1338,6 +1353,57 @@ int gpu_dbg_snp_draws(Ctx *c, const uint32_t *words, uint64_t n_words, uint64_t 
     MSIM_HIP(c, wait_stream(st));
     *end_pos = ps.pos;
     *flags = ps.flags;
+    return MSIM_OK;
+}
+
+// test support (msim_dbg_sample_tail): one launch of k_sample_tail over tables the caller made, in buffers of its own, synchronous.
+// Everything the kernel can index with is checked here first (include/msim.h lists what a caller has to hand in): the window lies
+// inside `words`, the list covers every accepted index the rounds can reach, every list entry is a bit of the bitmap.
+int gpu_dbg_sample_tail(Ctx *c, const uint32_t *words, uint64_t n_words, const uint32_t *acc, uint64_t n_acc, uint32_t acc_first,
+                        const uint32_t *blocks, uint32_t n_blocks, uint32_t raw_counts, uint32_t W, uint32_t shift, uint32_t n,
+                        uint32_t k, uint32_t *bitmap, uint32_t bm_guard, msim_dbg_tail_state *state, int anchored, uint64_t win_pos,
+                        uint32_t need0, uint32_t d1, uint64_t pos_limit) {
+    if (!words || !acc || !blocks || !bitmap || !state || !n_blocks || !W || !n || shift >= 32 || n_words >= (1ull << 31) ||
+        n_blocks != (W + ACC_BLOCK - 1) / ACC_BLOCK || (raw_counts && n_blocks > (uint32_t)TAIL_LDS_OFFS) || raw_counts > 1)
+        return fail(c, MSIM_ERR_ARG, "msim_dbg_sample_tail: bad argument");
+    const uint64_t p0 = anchored ? win_pos : state->pos;
+    uint64_t total = 0;
+    if (raw_counts) for (uint32_t i = 0; i < n_blocks; i++) total += blocks[i];
+    else total = blocks[n_blocks];
+    const uint64_t first_pos = (uint64_t)k + (anchored ? need0 : 0u);
+    if (p0 > n_words || W > n_words - p0 || total >= (1ull << 32) || acc_first > first_pos || total > (uint64_t)acc_first + n_acc)
+        return fail(c, MSIM_ERR_ARG, "msim_dbg_sample_tail: the window or the list does not cover what the kernel may read");
+    for (uint64_t i = 0; i < n_acc; i++)
+        if (acc[i] >= n) return fail(c, MSIM_ERR_ARG, "msim_dbg_sample_tail: a list entry beyond the population");
+    const size_t bm_words = ((size_t)n + 31) / 32, sz_bm = (bm_words + 2 * (size_t)bm_guard) * 4;
+    const size_t sz_raw = std::max<size_t>((size_t)n_words * 4, 4), sz_acc = std::max<size_t>((size_t)n_acc * 4, 4);
+    const size_t sz_blk = ((size_t)n_blocks + 1) * 4;
+    DbgDev dev;
+    uint32_t *d_raw, *d_acc, *d_blk, *d_bm; PlanState *d_ps; SpecHdr *d_hdr;
+    MSIM_HIP(c, dev.bytes(&d_raw, sz_raw)); MSIM_HIP(c, dev.bytes(&d_acc, sz_acc)); MSIM_HIP(c, dev.bytes(&d_blk, sz_blk));
+    MSIM_HIP(c, dev.bytes(&d_bm, sz_bm)); MSIM_HIP(c, dev.bytes(&d_ps, 2 * sizeof(PlanState))); MSIM_HIP(c, dev.bytes(&d_hdr, sizeof(SpecHdr)));
+    hipStream_t st = c->stream;
+    PlanState ps[2];
+    memset(ps, 0, sizeof ps);
+    ps[0].pos = state->pos; ps[0].snp_base = state->snp_base; ps[0].flags = state->flags; ps[0].dups = state->dups;
+    ps[0].accepted_used = state->accepted_used;
+    ps[1].pos = ps[1].snp_base = win_pos;
+    SpecHdr hdr{need0, d1, 0, 0};
+    MSIM_HIP(c, hipMemcpyAsync(d_raw, words, (size_t)n_words * 4, hipMemcpyHostToDevice, st));
+    if (n_acc) MSIM_HIP(c, hipMemcpyAsync(d_acc, acc, (size_t)n_acc * 4, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemcpyAsync(d_blk, blocks, ((size_t)n_blocks + (raw_counts ? 0 : 1)) * 4, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemcpyAsync(d_bm, bitmap, sz_bm, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemcpyAsync(d_ps, ps, sizeof ps, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemcpyAsync(d_hdr, &hdr, sizeof hdr, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(TAIL_THREADS), 0, st, d_raw, d_acc, acc_first, d_blk, n_blocks, W, shift, n, k,
+                       d_bm + bm_guard, d_ps, raw_counts, anchored ? (const PlanState *)(d_ps + 1) : (const PlanState *)nullptr,
+                       anchored ? (const SpecHdr *)d_hdr : (const SpecHdr *)nullptr, (unsigned long long)pos_limit);
+    MSIM_HIP(c, hipGetLastError());
+    MSIM_HIP(c, hipMemcpyAsync(bitmap, d_bm, sz_bm, hipMemcpyDeviceToHost, st));
+    MSIM_HIP(c, hipMemcpyAsync(ps, d_ps, sizeof(PlanState), hipMemcpyDeviceToHost, st));
+    MSIM_HIP(c, wait_stream(st));
+    state->pos = ps[0].pos; state->snp_base = ps[0].snp_base; state->flags = ps[0].flags; state->dups = ps[0].dups;
+    state->accepted_used = ps[0].accepted_used;
     return MSIM_OK;
 }
 

@@ -603,7 +603,8 @@ __global__ __launch_bounds__(ACC_THREADS) void k_ahead_fringe(const uint32_t *__
 // Tail rounds + exact cut.  One workgroup.  `total_acc` = accepted draws available in the window.
 // `acc` holds the accepted draws from accepted-index `acc_first` on (0: the whole list, k: tail only).
 constexpr int TAIL_LDS_OFFS = 8192;
-__global__ __launch_bounds__(1024) void k_sample_tail(const uint32_t *__restrict__ raw, const uint32_t *__restrict__ acc,
+constexpr int TAIL_THREADS = 1024;                       // (its three launch sites and the test hook: plan_gpu.hip)
+__global__ __launch_bounds__(TAIL_THREADS) void k_sample_tail(const uint32_t *__restrict__ raw, const uint32_t *__restrict__ acc,
                                                       uint32_t acc_first,
                                                       const uint32_t *__restrict__ block_off, uint32_t n_blocks,
                                                       uint32_t W, uint32_t shift, uint32_t n, uint32_t k,
@@ -2017,11 +2018,22 @@ __global__ void k_publish_seq(const PlanState *__restrict__ ps, PlanState *__res
 
 __global__ void k_raise_flag(PlanState *ps, uint32_t flag) { ps->flags |= flag; }
 
-__global__ void k_state_init(PlanState *ps, unsigned long long pos) {
+__device__ __forceinline__ void state_init(PlanState *ps, unsigned long long pos) {
     ps->pos = pos; ps->snp_base = pos; ps->flags = 0; ps->dups = 0; ps->accepted_used = 0;
     ps->n_nsn = ps->n_rec = ps->n_sn = ps->pool_len = 0;
     ps->len_delta = 0;
     ps->ahead_margin_used = 0; ps->rsv = 0;
+}
+__global__ void k_state_init(PlanState *ps, unsigned long long pos) { state_init(ps, pos); }
+
+// A host generator becomes a device stream: its 624 state words travel BY VALUE in the kernel arguments (2496 bytes: no staging
+// slot to guard, no copy engine, nothing of the host's to wait for) and land where the session starts from -- the cascade's
+// first state and words [0, 624) of the stream.  ps given (the CPython stream): the bookkeeping block starts at `pos` too.
+struct SeedWords { uint32_t w[MT_N]; };
+__global__ __launch_bounds__(256) void k_reseed(SeedWords sw, uint32_t *__restrict__ states, uint32_t *__restrict__ raw,
+                                                PlanState *ps, unsigned long long pos) {
+    for (int i = threadIdx.x; i < MT_N; i += 256) { const uint32_t v = sw.w[i]; states[i] = v; raw[i] = v; }
+    if (ps && threadIdx.x == 0) state_init(ps, pos);
 }
 
 }  // namespace

@@ -170,6 +170,9 @@ SYMBOLS = [
     ("msim_gather_fetch", C.c_int, [_VP, C.c_uint64, C.c_uint64, _VP]),
     ("msim_dbg_snp_draws", C.c_int, [_VP, _VP, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _VP, _VP, _U64P,
                                      _U32P, _VP]),
+    ("msim_dbg_sample_tail", C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint64, C.c_uint32, _VP, C.c_uint32, C.c_uint32, C.c_uint32,
+                                       C.c_uint32, C.c_uint32, C.c_uint32, _VP, C.c_uint32, _VP, C.c_int, C.c_uint64, C.c_uint32,
+                                       C.c_uint32, C.c_uint64]),
     ("msim_context_counts", C.c_int, [_VP, C.c_int, _VP, _U64P]),
     ("msim_plan_contig_spectrum", C.c_int, [_VP, C.c_int, _VP, C.c_uint64, C.c_uint32]),
     ("msim_spectrum_timing", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -262,6 +265,8 @@ def render_chain(recs: np.ndarray, length: int, t_name: str, q_name: str, chain_
 # the device tables of the SV-mix / host-chain test hooks (csrc/plan_kernels.h: TypeTable, MixRangeDev)
 TYPE_TABLE_DTYPE = np.dtype([("thr", "<u8", (8,)), ("n", "<u4"), ("type", "u1", (8,)), ("_pad", "u1", (4,))])
 MIX_RANGE_DTYPE = np.dtype([("rec_base", "<u4"), ("clip", "<u4"), ("set_id", "<u4"), ("rsv", "<u4")])
+TAIL_STATE_DTYPE = np.dtype([("pos", "<u8"), ("snp_base", "<u8"), ("flags", "<u4"), ("dups", "<u4"), ("accepted_used", "<u4"),
+                             ("rsv", "<u4")])      # msim_dbg_tail_state
 CHAIN_DROPPED = 0xFFFFFFFF           # ctx.h: a chain candidate that is blocked / dropped
 CHAIN_TOMBSTONE = 0x80               # ctx.h: ch_aux flag of an entry __fix_tl_amount deleted
 
@@ -810,6 +815,30 @@ class Engine:
         self._check(self.lib.msim_dbg_snp_draws(self.h, _ptr(words), words.shape[0], int(ti_lim), int(start), int(K), int(aux_off),
                                                 _ptr(lanes), _ptr(maps), C.byref(end_pos), C.byref(flags), _ptr(aux)))
         return {"lanes": lanes, "maps": maps, "end_pos": int(end_pos.value), "flags": int(flags.value), "aux": aux}
+
+    def sample_tail(self, words, acc, acc_first: int, blocks, raw_counts: bool, W: int, shift: int, n: int, k: int, bitmap,
+                    state: dict, win=None, pos_limit: int = 2 ** 64 - 1, guard: int = 4):
+        """One launch of the sampler's tail rounds and stream cut over the caller's tables (msim_dbg_sample_tail): RAW
+        CPython-stream ``words``, the accepted draws ``acc`` from accepted index ``acc_first`` on, ``blocks`` = the accepted
+        draws per 2048-word block (``raw_counts``) or their exclusive prefix sums, the initial ``bitmap`` of ceil(n / 32) uint32
+        and the initial ``state`` (pos, snp_base, flags, dups, accepted_used).  ``win`` = (pos, need0, d1): the anchored form.
+        Returns (state, bitmap) -- the bitmap between ``guard`` words of 0xee bytes on either side, as they came back."""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        acc = np.ascontiguousarray(acc, dtype=np.uint32)
+        blocks = np.ascontiguousarray(blocks, dtype=np.uint32)
+        bm = np.concatenate([np.full(guard, 0xEEEEEEEE, dtype=np.uint32), np.ascontiguousarray(bitmap, dtype=np.uint32),
+                             np.full(guard, 0xEEEEEEEE, dtype=np.uint32)])
+        assert bm.shape[0] == 2 * guard + (int(n) + 31) // 32, "bitmap: ceil(n / 32) words"
+        n_blocks = blocks.shape[0] - (0 if raw_counts else 1)
+        st = np.zeros(1, dtype=TAIL_STATE_DTYPE)
+        for f in ("pos", "snp_base", "flags", "dups", "accepted_used"):
+            st[f] = int(state.get(f, 0))
+        wpos, need0, d1 = win if win is not None else (0, 0, 0)
+        self._check(self.lib.msim_dbg_sample_tail(self.h, _ptr(words), words.shape[0], _ptr(acc), acc.shape[0], int(acc_first),
+                                                  _ptr(blocks), int(n_blocks), 1 if raw_counts else 0, int(W), int(shift), int(n),
+                                                  int(k), _ptr(bm), int(guard), _ptr(st), 0 if win is None else 1, int(wpos),
+                                                  int(need0), int(d1), int(pos_limit)))
+        return {f: int(st[f][0]) for f in ("pos", "snp_base", "flags", "dups", "accepted_used")}, bm
 
     def candidates(self, np_words, sets, bitmap=None, start: int = 0, d: int = 1, K: int = 0, ranges=None, all: bool = False):
         """The candidate front of the SV-mix (``bitmap`` given: one range, ``sets`` one TYPE_TABLE_DTYPE entry) or host-chain
