@@ -217,6 +217,37 @@ int msim_plan_contig(msim_ctx *ctx, int contig, const msim_range *ranges, int n_
  * both streams advance exactly as msim_plan_contig on a contig of `len` bases would leave them -- the chain across
  * contigs stays intact -- but no record table, insert pool or SNP outcome is produced and no contig is created.   */
 int msim_plan_chain(msim_ctx *ctx, uint64_t len, const msim_range *ranges, int n_ranges);
+/* A whole pass in one call: item by item exactly what the same sequence of msim_plan_contig / msim_plan_chain /
+ * msim_apply_contig calls does, in item order -- records, insert pools, mutated streams, KeyError words, both stream positions,
+ * msim_timing and the error codes come out the same, errors stay sticky and asynchronous, and the call returns at the first item
+ * that fails (the items behind it are not planned).  What the call adds is knowledge of the contigs to come: for a run of
+ * consecutive items that the SNP sampler plans from ONE drawing range with an anchored window (msim_timing.snp_samples_ahead),
+ * the samples' count / scatter / de-dup -- which need only the host's bound of where each sample starts -- are enqueued for the
+ * whole run first, eight samples a launch, and the contigs' stream-position chains follow as before.  A -sn 0.01 pass over a
+ * 3 Gb genome then has no LDS-heavy kernel left to run beside its rewrite launches (NOTES section 31).
+ * Such a run ends in front of an item of any other engine (SV mix, host cut, host chain, host planner, MSIM_RNG_FAST, a host-only
+ * context), a sample that stays on the chain, an item in front of which the device streams' session would be re-based, and
+ * after 24 items; everything else takes the per-contig path in its place in the order.  Always correct, faster only where it
+ * can hoist.  MSIM_NO_PASS_HOIST=1: nothing is hoisted.  MSIM_PASS_BATCH / MSIM_PASS_FIRST: samples per prep launch (8) and in
+ * a run's first one (1: the run's first chain waits for that launch alone).  MSIM_PASS_STREAMS / MSIM_PASS_GATE: schedule
+ * experiments (NOTES section 31).                                                                                          */
+#define MSIM_PASS_APPLY 1u             /* msim_apply_contig(contig) right behind the item's plan (contig >= 0)              */
+typedef struct msim_pass_item {
+    int32_t  contig;                   /* contig id, or -1: walk only (msim_plan_chain)                                    */
+    uint32_t flags;                    /* MSIM_PASS_APPLY                                                                  */
+    uint64_t len;                      /* contig == -1: its length                                                        */
+    const msim_range *ranges;          /* as msim_plan_contig                                                              */
+    int32_t  n_ranges;
+    int32_t  rsv;
+} msim_pass_item;
+int msim_plan_pass(msim_ctx *ctx, const msim_pass_item *items, int n_items);
+/* Test support: the rule that cuts a pass into those runs ("segments"), the very function msim_plan_pass calls, over an item list
+ * alone -- pure host code, no context.  The streams are taken to stand exactly at py_pos / np_pos of a session that spans
+ * max_chunks chunks (0: the jump tables' 8192); ahead: MSIM_AHEAD's value (2 = every context plans ahead).  seg[i] = 0: item i
+ * takes the per-contig path; s >= 1: it belongs to the pass's s-th segment.  An item the SNP sampler does not take, and a re-base,
+ * count as a synchronisation: the position behind them is exact.                                                            */
+int msim_dbg_pass_segments(const msim_params *params, const msim_pass_item *items, int n_items, uint64_t py_pos, uint64_t np_pos,
+                           uint32_t max_chunks, int ahead, int32_t *seg);
 /* 1 if the last plan of this contig left `muts` empty (warning at mutator.py:125-129).             */
 int msim_plan_was_empty(msim_ctx *ctx, int contig, int *empty);
 

@@ -696,6 +696,38 @@ int msim_plan_chain(msim_ctx *p, uint64_t len, const msim_range *ranges, int n_r
     return rc;
 }
 
+// A pass in one call.  Every item goes through the per-contig entry points' own code, in order; in front of an item at which no
+// hoisted sample is waiting, the sampler looks at the items from there on and sends ahead what it can (gpu_plan_pass_prep).
+int msim_plan_pass(msim_ctx *p, const msim_pass_item *items, int n_items) {
+    Ctx *c = C(p);
+    if (!c || n_items < 0 || (n_items && !items)) return MSIM_ERR_ARG;
+    const bool dev = !c->host_only && c->gpu && !(c->flags & (MSIM_PLAN_HOST | MSIM_RNG_FAST)) && c->have_params;
+    for (int i = 0; i < n_items; i++) {
+        const msim_pass_item &it = items[i];
+        int rc = MSIM_OK;
+        if (dev && !gpu_plan_pass_hoisting(c->gpu)) {
+            // (contigs the context does not know end a segment like any item the sampler would not take: by failing at their turn)
+            int n = 0;
+            while (i + n < n_items && (items[i + n].contig < 0 || (size_t)items[i + n].contig < c->contigs.size())) n++;
+            rc = gpu_plan_pass_prep(c, c->gpu, items + i, n);
+        }
+        if (!rc) rc = it.contig < 0 ? msim_plan_chain(p, it.len, it.ranges, it.n_ranges) : msim_plan_contig(p, it.contig, it.ranges, it.n_ranges);
+        if (!rc && it.contig >= 0 && (it.flags & MSIM_PASS_APPLY)) rc = msim_apply_contig(p, it.contig);
+        if (rc) {
+            if (dev) gpu_plan_pass_abort(c, c->gpu);
+            return rc;
+        }
+    }
+    if (dev) gpu_plan_pass_abort(c, c->gpu);                // (nothing is left waiting behind a pass that ran through)
+    return MSIM_OK;
+}
+
+int msim_dbg_pass_segments(const msim_params *params, const msim_pass_item *items, int n_items, uint64_t py_pos, uint64_t np_pos,
+                           uint32_t max_chunks, int ahead, int32_t *seg) {
+    if (!params || n_items < 0 || (n_items && (!items || !seg))) return MSIM_ERR_ARG;
+    return gpu_dbg_pass_segments(params, items, n_items, py_pos, np_pos, max_chunks, ahead, seg);
+}
+
 int msim_plan_was_empty(msim_ctx *p, int contig, int *empty) {
     CTX_FLUSHED(c, p)
     if (!c || !empty) return MSIM_ERR_ARG;

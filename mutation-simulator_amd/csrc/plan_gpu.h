@@ -75,6 +75,17 @@ int gpu_plan_make_room(Ctx *c, GpuPlan *g, const msim_range *ranges, int n_range
 struct StreamNeed { double py, np; bool bad; };
 StreamNeed stream_need(const msim_params &P, const msim_range *ranges, int n_ranges);
 
+// msim_plan_pass: the leading items of items[0 .. n) whose samples' off-chain parts can go out ahead of their chains (the
+// segmenting rule: plan_gpu.hip, pass_segment) get them enqueued, batched; plan_contig_gpu then finds them waiting when each
+// contig's turn comes.  Nothing to hoist: nothing happens.  gpu_plan_pass_abort: the pass ended early -- what is still waiting
+// is dropped, behind a wait for the prep streams.
+int gpu_plan_pass_prep(Ctx *c, GpuPlan *g, const msim_pass_item *items, int n);
+void gpu_plan_pass_abort(Ctx *c, GpuPlan *g);
+bool gpu_plan_pass_hoisting(const GpuPlan *g);            // some hoisted sample still waits for its contig's turn
+// test support (msim_dbg_pass_segments): the segmenting rule over an item list, pure host code
+int gpu_dbg_pass_segments(const msim_params *P, const msim_pass_item *items, int n, uint64_t py_pos, uint64_t np_pos,
+                          uint32_t max_chunks, int ahead, int32_t *seg);
+
 void gpu_plan_stream_status(Ctx *c, GpuPlan *g, int out[8]);
 
 // Mean and variance of the CPython stream's words one stage consumes -- what the SNP sampler's anchored windows lay out the

@@ -23,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <vector>
 #include <sys/mman.h>
 
@@ -136,6 +137,39 @@ struct MixedSet {                        // scratch of one SV-mix range (section
     bool pending = false;
 };
 
+// The CPython stream's position as the host knows it between two exact readings (anchored windows): mean and variance of the
+// words consumed since, and a hard lower bound.
+struct ChainEst {
+    bool ok = false;
+    double e = 0, v = 0;
+    uint64_t lo = 0;
+    // mean + 16 sigma of the position, never beyond `bound` (the sum of the windows)
+    uint64_t hi(uint64_t bound) const {
+        if (!ok) return bound;
+        const double m = v > 0.0 ? 16.0 * std::sqrt(1.1 * v) + 256.0 : 0.0;
+        return std::min<uint64_t>(bound, (uint64_t)std::ceil(e + m));
+    }
+    void add(const StreamMoments &m, uint64_t least) { if (ok) { e += m.e; v += m.v; lo += least; } }
+};
+// What the host decides about one sampled range before anything is launched (sample_step): the window, whether its heavy part
+// runs off the chain and then on which interval [lo, H] of possible starts, the bounds handed to the kernels.
+struct SampleStep {
+    bool bad = false;                    // window beyond 2^32 words
+    bool ahead = false;                  // anchored window (count / scatter / de-dup off the chain)
+    uint64_t lo = 0, H = 0, expect = 0;
+    uint32_t soft_half = 0, W = 0;
+    uint64_t pos_in = 0;                 // bound of the start (the chain path's window origin)
+    uint64_t e_lim = ~0ull;              // bound of the end
+};
+struct SnpStep { bool bad = false; uint32_t W2 = 0; uint64_t pos_in = 0, e_lim = ~0ull; };
+struct SampleSet;
+struct Hoisted {                         // a sample whose off-chain part is enqueued (msim_plan_pass)
+    SampleStep st; int64_t start, k;     //   what it was laid out for: must be what the contig's own turn arrives at
+    SampleSet *S;
+    hipEvent_t batch_done;               //   behind the launches of its batch; wait_it: the chain has not waited for it yet
+    bool wait_it;
+};
+
 struct GpuPlan {
     GpuStream s[2];
     MixedSet mixed[N_SETS];
@@ -216,9 +250,15 @@ struct GpuPlan {
     int ahead = 2;                      //   0 never (MSIM_NO_AHEAD), 1 sharded ranks only (round 5's default), 2 always
     uint32_t pass_chain_only = 0;       //   msim_plan_chain calls in this pass
     bool sharded_rank = false;          //   ... there were some in this pass or in the one before
-    bool est_ok = false;
-    double est_e = 0, est_v = 0;
-    uint64_t est_lo = 0;
+    ChainEst est;
+    // msim_plan_pass: samples whose off-chain part went out ahead of their contigs' turn, in item order; plan_contig_gpu takes
+    // the front one when it reaches the sample (gpu_plan_pass_prep)
+    std::deque<Hoisted> hoisted;
+    int pass_batch = PREP_G, pass_first = 1;   //   jobs per prep launch / in a segment's first one (MSIM_PASS_BATCH, MSIM_PASS_FIRST):
+                                               //   the first chain of a segment waits for the first launch alone (NOTES section 31)
+    bool pass_hoist = true;                    //   MSIM_NO_PASS_HOIST: msim_plan_pass issues every prep at its contig's turn
+    int pass_streams = 0;                      //   MSIM_PASS_STREAMS: a segment's prep launches rotate over the first so many prep streams (0: all)
+    bool pass_gate = false;                    //   MSIM_PASS_GATE: a segment's prep starts behind the SNP maps of the words it reads
 };
 
 GpuPlan *gpu_plan_create() {
@@ -234,6 +274,11 @@ GpuPlan *gpu_plan_create() {
     if (const char *e = getenv("MSIM_PREP_LOW")) g->n_prep_low = std::min(g->n_prep, std::max(0, atoi(e)));
     if (const char *e = getenv("MSIM_PREP_PRIO")) g->prep_prio = atoi(e);
     if (const char *e = getenv("MSIM_AHEAD_SIGMA")) g->ahead_sigma = std::min(16.0, std::max(0.0, atof(e)));
+    if (const char *e = getenv("MSIM_PASS_BATCH")) g->pass_batch = std::min(PREP_G, std::max(1, atoi(e)));
+    if (const char *e = getenv("MSIM_PASS_FIRST")) g->pass_first = std::min(PREP_G, std::max(1, atoi(e)));
+    if (getenv("MSIM_NO_PASS_HOIST")) g->pass_hoist = false;
+    if (const char *e = getenv("MSIM_PASS_GATE")) g->pass_gate = atoi(e) != 0;
+    if (const char *e = getenv("MSIM_PASS_STREAMS")) g->pass_streams = std::min(8, std::max(0, atoi(e)));
     return g;
 }
 
@@ -442,15 +487,24 @@ StreamNeed stream_need(const msim_params &P, const msim_range *ranges, int n_ran
     return StreamNeed{py, 2.0 * K + pool_mean + 16.0 * std::sqrt(pool_var) + 4096.0, bad};
 }
 
+static bool sampler_eligible(const msim_params &P, const msim_range *ranges, int n_ranges);
+// The rule itself, on positions the caller names (gpu_plan_make_room: where the streams stand; pass_segment: where they will).
+struct RoomVerdict { bool fits, rebase; };
+static RoomVerdict room_for(const StreamNeed &need, uint64_t span_w, bool live0, uint64_t pos0, bool live1, uint64_t pos1) {
+    const double py = need.py, np = need.np, span = (double)(span_w - MT_N);
+    RoomVerdict v;
+    v.fits = need.bad || (std::isfinite(py) && py < span && np < span);   // (bad: the engines' eligibility refuses these themselves)
+    v.rebase = false;
+    if (need.bad || !v.fits) return v;
+    const double at0 = live0 ? (double)pos0 : (double)MT_N, at1 = live1 ? (double)pos1 : (double)MT_N;
+    v.rebase = (live0 || live1) && (at0 + py > (double)span_w || at1 + np > (double)span_w);
+    return v;
+}
 int gpu_plan_make_room(Ctx *c, GpuPlan *g, const msim_range *ranges, int n_ranges, bool *fits) {
-    const StreamNeed need = stream_need(c->params, ranges, n_ranges);
-    const double py = need.py, np = need.np, span = (double)(span_words(g) - MT_N);
-    *fits = need.bad || (std::isfinite(py) && py < span && np < span);   // (bad: the engines' eligibility refuses these themselves)
-    if (need.bad || !*fits) return MSIM_OK;
     const GpuStream &s0 = g->s[0], &s1 = g->s[1];
-    const bool live = s0.live || s1.live;
-    const double at0 = s0.live ? (double)s0.pos : (double)MT_N, at1 = s1.live ? (double)s1.pos : (double)MT_N;
-    if (live && (at0 + py > (double)span_words(g) || at1 + np > (double)span_words(g))) {
+    const RoomVerdict v = room_for(stream_need(c->params, ranges, n_ranges), span_words(g), s0.live, s0.pos, s1.live, s1.pos);
+    *fits = v.fits;
+    if (v.rebase) {
         const int rc = gpu_plan_sync_to_host(c, g);          // both streams: exact positions -> host states; the next engine reseeds
         if (rc) return rc;
         g->rebases++;
@@ -482,7 +536,7 @@ static int ensure_side_streams(Ctx *c, GpuPlan *g) {
 // contigs instead of preceding it.
 // maps = false: the caller reads the words only (a sample's chain) -- it need not wait for the batch's SNP maps, which the first
 // batch of a step delivers ~110 us behind its words
-static int ensure_words(Ctx *c, GpuPlan *g, int si, uint64_t upto, bool maps = true) {
+static int ensure_words(Ctx *c, GpuPlan *g, int si, uint64_t upto, bool maps = true, bool wait_plan = true) {
     GpuStream &s = g->s[si];
     {
         int rc0 = ensure_side_streams(c, g);
@@ -676,7 +730,7 @@ static int ensure_words(Ctx *c, GpuPlan *g, int si, uint64_t upto, bool maps = t
         }
     }
     // the plan stream waits for the batch that covers `upto`
-    if (upto > MT_N) {
+    if (wait_plan && upto > MT_N) {
         const uint32_t need = (uint32_t)((upto - MT_N + MT_CHUNK_WORDS - 1) / MT_CHUNK_WORDS);
         if (need > (maps ? s.waited_chunks : s.waited_words)) {
             for (size_t b = 0; b < s.ready_hi.size(); b++) {
@@ -781,7 +835,7 @@ static int chain_open(Ctx *c, GpuPlan *g, bool sampler) {
         hipLaunchKernelGGL(k_state_init, dim3(1), dim3(1), 0, c->stream, g->d_ps, (unsigned long long)g->s[0].pos);
         g->ps_valid = true;
     }
-    if (!sampler) { g->unverified = true; g->est_ok = false; }
+    if (!sampler) { g->unverified = true; g->est.ok = false; }
     return MSIM_OK;
 }
 
@@ -811,8 +865,8 @@ int gpu_plan_sync_to_host(Ctx *c, GpuPlan *g) {
     return MSIM_OK;
 }
 
-bool gpu_plan_eligible(const Ctx *c, const msim_range *ranges, int n_ranges) {
-    const msim_params &P = c->params;
+bool gpu_plan_eligible(const Ctx *c, const msim_range *ranges, int n_ranges) { return sampler_eligible(c->params, ranges, n_ranges); }
+static bool sampler_eligible(const msim_params &P, const msim_range *ranges, int n_ranges) {
     const int64_t d = min_block(P);
     if (P.block[MSIM_SN] != d) return false;              // an SNP could block its successor
     int64_t prev_stop = -1;
@@ -874,10 +928,11 @@ int gpu_plan_finish(Ctx *c, GpuPlan *g, bool ride_errs) {
 // streams' session holds is no longer a position the host knows.  The session ends here -- the next plan starts from the host
 // generators, which the caller sets (msim_seed / msim_set_mt_state: mutator.py restores them before it re-plans).
 void gpu_plan_abandon(GpuPlan *g) {
+    g->hoisted.clear();
     g->s[0].live = g->s[1].live = false;
     g->unverified = false;
     g->ps_valid = false;
-    g->est_ok = false;
+    g->est.ok = false;
 }
 
 int gpu_plan_force_overflow(Ctx *c, GpuPlan *g) {
@@ -995,15 +1050,17 @@ static int enqueue_sample_chain(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
 // the compaction of the accepted draws of [lo, H) run on the prep stream as soon as the words exist; the chain keeps the
 // fringe pass (needs the exact start), the tail rounds and the cut.  e_limit: the cut may not lie beyond it (what the caller
 // will have made sure exists for the stage that follows).
-static int prep_wait_words(Ctx *c, GpuPlan *g, uint64_t upto) {
+// maps: wait for the batch's SNP maps too (not for their sake: a pass's prep that starts behind them leaves the device to the map
+// pass, which the first contig's chain waits for -- MSIM_PASS_GATE)
+static int prep_wait_words(Ctx *c, GpuPlan *g, uint64_t upto, bool maps = false) {
     GpuStream &s = g->s[0];
     if (upto <= MT_N) return MSIM_OK;
     const uint32_t need = (uint32_t)((upto - MT_N + MT_CHUNK_WORDS - 1) / MT_CHUNK_WORDS);
     uint32_t &waited = g->prep_waited[g->prep_i];
-    if (need <= waited) return MSIM_OK;
+    if (need <= waited && !maps) return MSIM_OK;
     for (size_t b = 0; b < s.ready_hi.size(); b++) {
         if (s.ready_hi[b] >= need) {
-            MSIM_HIP(c, hipStreamWaitEvent(g->prep_stream, s.words_ev[b] ? s.words_ev[b] : s.ready_ev[b], 0));
+            MSIM_HIP(c, hipStreamWaitEvent(g->prep_stream, s.words_ev[b] && !maps ? s.words_ev[b] : s.ready_ev[b], 0));
             waited = s.ready_hi[b];
             break;
         }
@@ -1011,25 +1068,31 @@ static int prep_wait_words(Ctx *c, GpuPlan *g, uint64_t upto) {
     return MSIM_OK;
 }
 
-// grouped: the contig's emission goes out with a group (gpu_emit_flush) -- the group's event, behind its rewrite launch, then also
-// covers the chain kernels enqueued here (the emit stream waited for the plan stream's position at the flush), so no event of the
-// set's own is recorded behind them: one packet less per contig on the chain's queue
-static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t d, uint64_t lo, uint64_t H, uint64_t e_limit,
-                                Grow &grow, SampleLaunch &out, bool &took, bool grouped, uint64_t expect, uint32_t soft_half) {
-    int rc;
-    const uint32_t K = (uint32_t)r.k;
+// The launch geometry of an anchored window: a pure function of the range and of [lo, H].  took = false: counts beyond what the
+// chain's kernels hold in LDS (the sample stays on the chain).  W is sized for all K draws from H: the core needs fewer.
+struct AheadGeom { uint32_t K, n, shift, W, F, nb, nbh, a_max, k_core, bmw, bnb, n_bins, bin_cap; bool took; };
+static AheadGeom ahead_geometry(const msim_range &r, int64_t d, uint64_t lo, uint64_t H, uint32_t W) {
+    AheadGeom a{};
+    a.K = (uint32_t)r.k;
     const uint64_t n = (uint64_t)range_population(r, d);
-    const int bits = bit_length64(n);
     const double p_acc = randbelow_acceptance((double)n);
-    const double wd = big_sample_window((double)n, set_path_need((double)n, (double)K));
-    if (wd >= 4.0e9) return fail(c, MSIM_ERR_UNSUPPORTED, "sample window beyond 2^32 words");
-    const uint32_t W = (uint32_t)wd;                       // (sized for all K draws from H: the core needs fewer)
-    const uint32_t F = (uint32_t)(H - lo);
-    took = (W + ACC_BLOCK - 1) / ACC_BLOCK < (uint32_t)TAIL_LDS_OFFS && (F + ACC_BLOCK - 1) / ACC_BLOCK <= (uint32_t)AHEAD_MAX_HEAD_BLOCKS;
-    if (!took) return MSIM_OK;                             // (counts beyond what the chain's kernels hold in LDS: the caller's other path)
-    const uint32_t a_max = F ? (uint32_t)std::min<double>((double)F, (double)F * p_acc + 16.0 * std::sqrt((double)F * p_acc * (1.0 - p_acc)) + 64.0) : 0u;
-    const uint32_t k_core = K - a_max;
-    g->prep_i = (g->prep_i + 1) % g->n_prep;
+    a.n = (uint32_t)n; a.shift = (uint32_t)(32 - bit_length64(n)); a.W = W; a.F = (uint32_t)(H - lo);
+    a.nb = (W + ACC_BLOCK - 1) / ACC_BLOCK;
+    a.nbh = (a.F + ACC_BLOCK - 1) / ACC_BLOCK;
+    a.took = a.nb < (uint32_t)TAIL_LDS_OFFS && a.nbh <= (uint32_t)AHEAD_MAX_HEAD_BLOCKS;
+    const double F = (double)a.F;
+    a.a_max = a.F ? (uint32_t)std::min<double>(F, F * p_acc + 16.0 * std::sqrt(F * p_acc * (1.0 - p_acc)) + 64.0) : 0u;
+    a.k_core = a.K - a.a_max;
+    a.bmw = (uint32_t)((n + 63) / 64);
+    a.bnb = (a.bmw + BM_THREADS - 1) / BM_THREADS;
+    a.n_bins = (uint32_t)((n + BIN_VALUES - 1) >> BIN_SHIFT);
+    a.bin_cap = sample_bin_cap(n, a.K, p_acc);
+    return a;
+}
+
+// The next prep stream in turn becomes g->prep_stream (created on first use).
+static int next_prep_stream(Ctx *c, GpuPlan *g, int among = 0) {      // among: only the first so many of them (0: all)
+    g->prep_i = (g->prep_i + 1) % (among > 0 ? std::min(among, g->n_prep) : g->n_prep);
     if (!g->prep_streams[g->prep_i]) {
         int plo = 0, phi = 0;
         MSIM_HIP(c, hipDeviceGetStreamPriorityRange(&plo, &phi));
@@ -1038,31 +1101,30 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
         if (g->seed_ev) MSIM_HIP(c, hipStreamWaitEvent(g->prep_streams[g->prep_i], g->seed_ev, 0));   // (the session's first 624 words come from k_reseed)
     }
     g->prep_stream = g->prep_streams[g->prep_i];
+    return MSIM_OK;
+}
+
+// An anchored window's scratch set: the next one in turn, grown to the window, ordered on g->prep_stream behind whatever may
+// still read it.
+// grouped: the contig's emission goes out with a group (gpu_emit_flush) -- the group's event, behind its rewrite launch, then also
+// covers the chain kernels enqueued for it (the emit stream waited for the plan stream's position at the flush), so no event of the
+// set's own is recorded behind them: one packet less per contig on the chain's queue
+static int ahead_take_set(Ctx *c, GpuPlan *g, const AheadGeom &a, Grow &grow, bool grouped, SampleSet *&out) {
+    int rc;
     hipStream_t ps_ = g->prep_stream;
     SampleSet &S = g->sample[g->unit++ % N_SETS];
-    const uint32_t nb = (W + ACC_BLOCK - 1) / ACC_BLOCK;
-    const uint32_t nbh = (F + ACC_BLOCK - 1) / ACC_BLOCK;
-    const size_t bm_words64 = (size_t)((n + 63) / 64);
-    const uint32_t bmw = (uint32_t)bm_words64;
-    const uint32_t bnb = (bmw + BM_THREADS - 1) / BM_THREADS;
-    const uint32_t n_bins = (uint32_t)((n + BIN_VALUES - 1) >> BIN_SHIFT);
-    const uint32_t bin_cap = sample_bin_cap(n, K, p_acc);
-    if ((rc = grow(S.cnt, (size_t)(nb + 2) * sizeof(uint32_t)))) return rc;
-    if ((rc = grow(S.cnt2, emit_cnt2_words(bmw) * sizeof(uint32_t)))) return rc;   // (either train's layout: plan_kernels.h)
-    if ((rc = grow(S.acc, (size_t)W * sizeof(uint32_t)))) return rc;
-    if ((rc = grow(S.bins, (size_t)n_bins * BIN_SUBS * bin_cap * sizeof(uint32_t)))) return rc;
+    const size_t bm_words64 = (size_t)a.bmw;
+    if ((rc = grow(S.cnt, (size_t)(a.nb + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = grow(S.cnt2, emit_cnt2_words(a.bmw) * sizeof(uint32_t)))) return rc;   // (either train's layout: plan_kernels.h)
+    if ((rc = grow(S.acc, (size_t)a.W * sizeof(uint32_t)))) return rc;
+    if ((rc = grow(S.bins, (size_t)a.n_bins * BIN_SUBS * a.bin_cap * sizeof(uint32_t)))) return rc;
     if ((rc = grow(S.cursors, (size_t)MAX_BINS * BIN_SUBS * sizeof(uint32_t)))) return rc;
-    if ((rc = grow(S.bitmap, std::max(bm_words64 * 8, (size_t)n_bins * BIN_WORDS * 4)))) return rc;
-    if ((rc = grow(S.hcnt, (size_t)(nbh + 2) * sizeof(uint32_t)))) return rc;
-    if ((rc = grow(S.hacc, ((size_t)nbh * ACC_BLOCK + 64) * sizeof(uint32_t)))) return rc;
+    if ((rc = grow(S.bitmap, std::max(bm_words64 * 8, (size_t)a.n_bins * BIN_WORDS * 4)))) return rc;
+    if ((rc = grow(S.hcnt, (size_t)(a.nbh + 2) * sizeof(uint32_t)))) return rc;
+    if ((rc = grow(S.hacc, ((size_t)a.nbh * ACC_BLOCK + 64) * sizeof(uint32_t)))) return rc;
     if (!S.ahead) MSIM_HIP(c, hipMalloc(&S.ahead, 2 * sizeof(PlanState) + sizeof(SpecHdr)));
     if (!S.emit_done) MSIM_HIP(c, hipEventCreateWithFlags(&S.emit_done, hipEventDisableTiming));
     if (!S.prep_done) MSIM_HIP(c, hipEventCreateWithFlags(&S.prep_done, hipEventDisableTiming));
-    PlanState *ps_core = reinterpret_cast<PlanState *>(S.ahead), *ps_head = ps_core + 1;
-    SpecHdr *hdr = reinterpret_cast<SpecHdr *>(ps_head + 1);
-    if ((rc = ensure_words(c, g, 0, H + W + 1, false))) return rc;
-    const uint32_t *raw = g->s[0].d_raw;
-    if ((rc = prep_wait_words(c, g, H + W + 1))) return rc;
     if (S.pending) {                                       // the set's last emission may still read it
         if (hipEventQuery(S.wait_ev) == hipSuccess) S.pending = false;
         else { (void)hipGetLastError(); MSIM_HIP(c, hipStreamWaitEvent(ps_, S.wait_ev, 0)); }
@@ -1076,32 +1138,103 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
         MSIM_HIP(c, hipStreamWaitEvent(ps_, S.chain_done, 0));
     }
     S.last_user = grouped ? 3 : 2;                         // (3: its group's event -- S.wait_ev, checked above -- stands for chain_done)
-    // ---- off the chain
-    const uint32_t shift = (uint32_t)(32 - bits);
-    hipLaunchKernelGGL(k_ahead_count, dim3(nb + nbh), dim3(ACC_THREADS), 0, ps_, raw, ps_core, ps_head, hdr, (unsigned long long)H,
-                       (unsigned long long)lo, W, F, nb, shift, (uint32_t)n, S.cnt.p(), S.cursors.p(), n_bins * BIN_SUBS, S.hcnt.p(), S.hacc.p());
-    hipLaunchKernelGGL(k_bin_scatter, dim3((W + SPL_BLOCK - 1) / SPL_BLOCK), dim3(ACC_THREADS), 0, ps_, raw, ps_core, W, shift,
-                       (uint32_t)n, k_core, S.cnt.p(), n_bins, bin_cap, S.cursors.p(), S.bins.p(), S.acc.p(), ps_core, 1u);
-    hipLaunchKernelGGL(k_bin_dedupe, dim3(n_bins), dim3(512), 0, ps_, S.bins.p(), S.cursors.p(), bin_cap, S.bitmap.p(), ps_core);
+    out = &S;
+    return MSIM_OK;
+}
+
+static PrepJob prep_job(const SampleSet &S, const AheadGeom &a, uint64_t lo, uint64_t H) {
+    PrepJob T{};
+    T.ps_core = reinterpret_cast<PlanState *>(S.ahead); T.ps_head = T.ps_core + 1; T.hdr = reinterpret_cast<SpecHdr *>(T.ps_head + 1);
+    T.cnt = S.cnt.p(); T.cursors = S.cursors.p(); T.hcnt = S.hcnt.p(); T.hacc = S.hacc.p(); T.bins = S.bins.p(); T.acc = S.acc.p();
+    T.bitmap = S.bitmap.p();
+    T.H = H; T.lo = lo;
+    T.W = a.W; T.F = a.F; T.nb = a.nb; T.nbh = a.nbh; T.shift = a.shift; T.n = a.n; T.k_core = a.k_core; T.n_bins = a.n_bins;
+    T.bin_cap = a.bin_cap;
+    return T;
+}
+
+// ---- off the chain: count, scatter, de-dup of J.n samples on g->prep_stream, `done` recorded behind them.  One sample: the
+// single-job kernels; several: one launch per stage for all of them (plan_kernels.h: PrepJobs).
+static int prep_launch(Ctx *c, GpuPlan *g, PrepJobs &J, hipEvent_t done) {
+    hipStream_t ps_ = g->prep_stream;
+    const uint32_t *raw = g->s[0].d_raw;
+    if (J.n == 1) {
+        const PrepJob &T = J.j[0];
+        hipLaunchKernelGGL(k_ahead_count, dim3(T.nb + T.nbh), dim3(ACC_THREADS), 0, ps_, raw, T.ps_core, T.ps_head, T.hdr,
+                           T.H, T.lo, T.W, T.F, T.nb, T.shift, T.n, T.cnt, T.cursors, T.n_bins * BIN_SUBS, T.hcnt, T.hacc);
+        hipLaunchKernelGGL(k_bin_scatter, dim3((T.W + SPL_BLOCK - 1) / SPL_BLOCK), dim3(ACC_THREADS), 0, ps_, raw, T.ps_core, T.W, T.shift,
+                           T.n, T.k_core, T.cnt, T.n_bins, T.bin_cap, T.cursors, T.bins, T.acc, T.ps_core, 1u);
+        hipLaunchKernelGGL(k_bin_dedupe, dim3(T.n_bins), dim3(512), 0, ps_, T.bins, T.cursors, T.bin_cap, T.bitmap, T.ps_core);
+    } else {
+        uint32_t cblk = 0, sblk = 0, dblk = 0;
+        for (uint32_t i = 0; i < J.n; i++) {
+            PrepJob &T = J.j[i];
+            T.cblk0 = cblk; T.sblk0 = sblk; T.dblk0 = dblk;
+            cblk += T.nb + T.nbh; sblk += (T.W + SPL_BLOCK - 1) / SPL_BLOCK; dblk += T.n_bins;
+        }
+        hipLaunchKernelGGL(k_ahead_count_b, dim3(cblk), dim3(ACC_THREADS), 0, ps_, raw, J);
+        hipLaunchKernelGGL(k_bin_scatter_b, dim3(sblk), dim3(ACC_THREADS), 0, ps_, raw, J);
+        hipLaunchKernelGGL(k_bin_dedupe_b, dim3(dblk), dim3(512), 0, ps_, J);
+    }
     MSIM_HIP(c, hipGetLastError());
-    MSIM_HIP(c, hipEventRecord(S.prep_done, ps_));
-    // ---- on the chain: fringe (exact start), tail rounds, cut
-    MSIM_HIP(c, hipStreamWaitEvent(c->stream, S.prep_done, 0));
-    const double dups_est = (double)K * (double)K / (2.0 * (double)n);
-    const uint32_t items_est = a_max + (uint32_t)(dups_est + 16.0 * std::sqrt(dups_est) + 64.0);
+    MSIM_HIP(c, hipEventRecord(done, ps_));
+    return MSIM_OK;
+}
+
+// ---- on the chain: fringe (exact start), tail rounds, cut.  wait_for: the event behind the sample's off-chain part (nullptr:
+// the plan stream has waited for it already -- an earlier sample of the same batch).
+static int ahead_chain(Ctx *c, GpuPlan *g, SampleSet &S, const msim_range &r, const AheadGeom &a, const SampleStep &st, hipEvent_t wait_for,
+                       bool grouped, SampleLaunch &out) {
+    int rc;
+    // (the plan stream waits for the words here, as a sample on the chain would; a set laid out ahead of its turn had them
+    //  generated then, on the side streams alone)
+    if ((rc = ensure_words(c, g, 0, st.H + a.W + 1, false))) return rc;
+    const uint32_t *raw = g->s[0].d_raw;
+    PlanState *ps_core = reinterpret_cast<PlanState *>(S.ahead), *ps_head = ps_core + 1;
+    SpecHdr *hdr = reinterpret_cast<SpecHdr *>(ps_head + 1);
+    if (wait_for) MSIM_HIP(c, hipStreamWaitEvent(c->stream, wait_for, 0));
+    const double dups_est = (double)a.K * (double)a.K / (2.0 * (double)a.n);
+    const uint32_t items_est = a.a_max + (uint32_t)(dups_est + 16.0 * std::sqrt(dups_est) + 64.0);
     const uint32_t G = std::max(1u, std::min(256u, (items_est + ACC_THREADS * FRINGE_ITEMS - 1) / (ACC_THREADS * FRINGE_ITEMS)));
     hipLaunchKernelGGL(k_ahead_fringe, dim3(G), dim3(ACC_THREADS), 0, c->stream, raw, g->d_ps, ps_core, ps_head, hdr,
-                       (unsigned long long)lo, F, S.hcnt.p(), nbh, S.hacc.p(), S.acc.p(), K, k_core, shift, (uint32_t)n, S.bitmap.p(),
-                       (unsigned long long)expect, soft_half);
-    hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(TAIL_THREADS), 0, c->stream, raw, S.acc.p(), k_core, S.cnt.p(), nb, W, shift, (uint32_t)n,
-                       k_core, S.bitmap.p(), g->d_ps, 1u, ps_core, hdr, (unsigned long long)e_limit);
+                       (unsigned long long)st.lo, a.F, S.hcnt.p(), a.nbh, S.hacc.p(), S.acc.p(), a.K, a.k_core, a.shift, a.n, S.bitmap.p(),
+                       (unsigned long long)st.expect, st.soft_half);
+    hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(TAIL_THREADS), 0, c->stream, raw, S.acc.p(), a.k_core, S.cnt.p(), a.nb, a.W, a.shift, a.n,
+                       a.k_core, S.bitmap.p(), g->d_ps, 1u, ps_core, hdr, (unsigned long long)st.e_lim);
     MSIM_HIP(c, hipGetLastError());
     if (!grouped) MSIM_HIP(c, hipEventRecord(S.chain_done, c->stream));
-    out.S = &S; out.W = W; out.bmw = bmw; out.bnb = bnb;
+    out.S = &S; out.W = a.W; out.bmw = a.bmw; out.bnb = a.bnb;
     c->t.snp_samples_ahead++;
     static const bool log_ahead = getenv("MSIM_DBG_AHEAD_LOG") != nullptr;
-    if (log_ahead) fprintf(stderr, "msim: sample ahead of the chain: K %u, start in [%llu, %llu], core %u draws\n", K, (unsigned long long)lo, (unsigned long long)H, k_core);
+    if (log_ahead) fprintf(stderr, "msim: sample ahead of the chain: K %u, start in [%llu, %llu], core %u draws\n", a.K, (unsigned long long)st.lo, (unsigned long long)st.H, a.k_core);
+    (void)r;
     return MSIM_OK;
+}
+
+// An anchored window at its contig's own turn: set, off-chain launches and chain in one go -- or, where msim_plan_pass sent the
+// off-chain part ahead (g->hoisted), the chain alone.
+static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t d, const SampleStep &st, Grow &grow, SampleLaunch &out,
+                                bool grouped) {
+    int rc;
+    const AheadGeom a = ahead_geometry(r, d, st.lo, st.H, st.W);
+    if (!g->hoisted.empty()) {
+        const Hoisted h = g->hoisted.front();
+        g->hoisted.pop_front();
+        if (h.start != r.start || h.k != r.k || h.st.lo != st.lo || h.st.H != st.H || h.st.W != st.W || h.st.e_lim != st.e_lim ||
+            h.st.expect != st.expect || h.st.soft_half != st.soft_half)
+            return fail(c, MSIM_ERR_HIP, "GPU sampler: a sample laid out ahead of its pass does not match its contig's turn (results discarded)");
+        return ahead_chain(c, g, *h.S, r, a, st, h.wait_it ? h.batch_done : (hipEvent_t) nullptr, grouped, out);
+    }
+    if ((rc = next_prep_stream(c, g))) return rc;
+    SampleSet *S = nullptr;
+    if ((rc = ahead_take_set(c, g, a, grow, grouped, S))) return rc;
+    if ((rc = ensure_words(c, g, 0, st.H + a.W + 1, false))) return rc;
+    if ((rc = prep_wait_words(c, g, st.H + a.W + 1))) return rc;
+    PrepJobs J;
+    J.n = 1;
+    J.j[0] = prep_job(*S, a, st.lo, st.H);
+    if ((rc = prep_launch(c, g, J, S->prep_done))) return rc;
+    return ahead_chain(c, g, *S, r, a, st, S->prep_done, grouped, out);
 }
 
 // SNP draws of a contig's K (kept) SNPs in position order, starting at the device position (ps->snp_base): the chain
@@ -1427,6 +1560,64 @@ StreamMoments snp_words_moments(uint64_t K, unsigned long long ti_lim) {
     return StreamMoments{(double)K * (2.0 + 2.0 * p_tv), (double)K * (2.0 * p_tv + 4.0 * p_tv * (1.0 - p_tv))};
 }
 
+// ---- part (a) of a contig's plan: the host's arithmetic, nothing launched.  plan_contig_gpu runs these steps at the contig's
+// turn; msim_plan_pass runs them over the contigs to come (pass_segment), on a copy of the estimate, to send their samples'
+// off-chain parts ahead -- the same functions, so both arrive at the same windows.
+static bool no_aux_fold() { static const bool v = getenv("MSIM_NO_AUX_FOLD") != nullptr; return v; }
+// one drawing range and a record table to write: the contig's emission goes out with a group (gpu_emit_flush)
+static bool contig_is_grouped(int n_draw, bool chain_only) {
+    static const bool no_group = getenv("MSIM_NO_EMIT_GROUP") != nullptr;
+    return n_draw == 1 && !chain_only && !no_aux_fold() && !no_group;
+}
+// One sampled range: its window, whether its heavy part leaves the chain, and est / pos_hi (the bound of the device position)
+// behind it.  can_ahead: the context plans ahead and the contig's shape allows it.
+static SampleStep sample_step(double ahead_sigma, ChainEst &est, uint64_t &pos_hi, const msim_range &r, int64_t d, bool can_ahead) {
+    SampleStep st;
+    const uint32_t k = (uint32_t)r.k;
+    // moments of the words this sample consumes: A accepted draws until k distinct values (duplicates: a coupon collector's
+    // first k), each after a geometric number of rejected words (_randbelow)
+    const double n_d = (double)range_population(r, d);
+    const StreamMoments ms = sample_words_moments((uint64_t)n_d, (uint64_t)k);
+    const double wd = big_sample_window(n_d, set_path_need(n_d, (double)k));
+    if (wd >= 4.0e9) { st.bad = true; return st; }
+    st.W = (uint32_t)wd;
+    if (can_ahead && est.ok && (uint64_t)n_d <= ((uint64_t)MAX_BINS << BIN_SHIFT) && 4.0 * (double)k <= n_d) {
+        // the interval costs what it holds (its accepted draws go through the fringe pass on the chain): ahead_sigma
+        // (8) standard deviations instead of the windows' 16 -- a start outside it is reported like an overflowed window
+        const double m = est.v > 0.0 ? ahead_sigma * std::sqrt(1.1 * est.v) + 256.0 : 0.0;
+        st.expect = (uint64_t)std::max(0.0, est.e);
+        st.soft_half = (uint32_t)std::min(4.0e9, m);
+        st.lo = std::max<uint64_t>(est.lo, (uint64_t)std::max(0.0, std::floor(est.e - m)));
+        st.H = std::max<uint64_t>(st.lo, std::min<uint64_t>(pos_hi, (uint64_t)std::ceil(est.e + m)));
+        // (a sample smaller than the uncertainty of its start stays on the chain; so does one whose start is known exactly --
+        //  behind a synchronisation the chain is empty and nothing is gained by making it wait for the prep stream)
+        static const bool ahead_first = getenv("MSIM_AHEAD_FIRST") != nullptr;
+        st.ahead = 2 * (st.H - st.lo) <= (uint64_t)k && (est.v > 0.0 || ahead_first) && ahead_geometry(r, d, st.lo, st.H, st.W).took;
+    }
+    est.add(ms, k);
+    // the sample ends at or in front of e_lim (and inside its window): what the SNP stage's windows are laid out from
+    st.e_lim = est.hi(~0ull);
+    if (st.ahead) pos_hi = std::min<uint64_t>(st.H + st.W, st.e_lim) - st.W;
+    st.pos_in = pos_hi;
+    pos_hi += st.W;
+    if (!st.ahead) pos_hi = est.hi(pos_hi);
+    return st;
+}
+// The SNP draws of a contig's K SNPs: a uniform() = 2 words, a transversion's randbelow(2) = a geometric(1/2) loop.
+static SnpStep snp_step(ChainEst &est, uint64_t &pos_hi, uint64_t K, const msim_params &P) {
+    SnpStep sn;
+    est.add(snp_words_moments(K, P.ti_lim), 2 * K);
+    sn.e_lim = est.hi(~0ull);
+    sn.pos_in = pos_hi;
+    const double p_tv = 1.0 - std::min(1.0, (double)P.ti_lim / 9007199254740992.0);
+    const double w2 = (double)K * (2.0 + 2.0 * p_tv) + 16.0 * std::sqrt(4.0 * (double)K) + 16384.0;
+    if (w2 >= 4.0e9) { sn.bad = true; return sn; }
+    sn.W2 = (uint32_t)w2;
+    pos_hi += sn.W2;
+    pos_hi = est.hi(pos_hi);
+    return sn;
+}
+
 // Asynchronous: enqueues the contig's chain (stream positions) on the plan stream and its emit work
 // (records) on the emit stream; nothing is waited for.  Flags and the exact position are collected
 // by gpu_plan_finish at the next synchronising call.
@@ -1458,26 +1649,15 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
     uint64_t pos_hi = py.pos;                             // upper bound of the device position
     uint64_t rec_base = 0;
     if (c->chain_only) { g->pass_chain_only++; g->sharded_rank = true; }
-    if (!g->unverified) {                                 // py.pos is exact: the estimate of the position starts here
-        g->est_ok = true;
-        g->est_e = (double)py.pos; g->est_v = 0.0; g->est_lo = py.pos;
-    }
-    // mean + 16 sigma of the position (est_*), never beyond the sum of the windows
-    auto est_hi = [&](uint64_t bound) -> uint64_t {
-        if (!g->est_ok) return bound;
-        const double m = g->est_v > 0.0 ? 16.0 * std::sqrt(1.1 * g->est_v) + 256.0 : 0.0;
-        return std::min<uint64_t>(bound, (uint64_t)std::ceil(g->est_e + m));
-    };
+    if (!g->unverified) g->est = ChainEst{true, (double)py.pos, 0.0, py.pos};   // py.pos is exact: the estimate of the position starts here
     // One drawing range (ARGS mode): the SNP outcomes are folded into the records by the expansion, which then runs behind
     // the SNP stage.  Several ranges keep the order expansion -> outcomes patched in (their bitmaps rotate through N_SETS
     // scratch sets and cannot all wait for the contig's one SNP stage).
     int n_draw = 0;
     for (int i = 0; i < n_ranges; i++) n_draw += ranges[i].k != 0;
-    static const bool no_fold = getenv("MSIM_NO_AUX_FOLD") != nullptr;
-    const bool fold_aux = n_draw == 1 && !c->chain_only && !no_fold;
+    const bool fold_aux = n_draw == 1 && !c->chain_only && !no_aux_fold();
     // ... and such contigs go through the emission stages in groups of EMIT_G (gpu_emit_flush), one launch per stage
-    static const bool no_group = getenv("MSIM_NO_EMIT_GROUP") != nullptr;
-    const bool grouped = fold_aux && !no_group;
+    const bool grouped = contig_is_grouped(n_draw, c->chain_only);
     // A full group goes out when the NEXT contig is planned, in front of its chain: by then msim_apply_contig has marked the
     // group's last contig too, so all of its APPLYs share the group's tile-index launch.
     // (pairs.  Measured with the calling thread on the GPU's NUMA node, where runs repeat within 0.05 ms: pairs 4.10-4.21 ms per
@@ -1498,37 +1678,14 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
         if (r.k == 0) continue;
         const uint32_t k = (uint32_t)r.k;
         SampleLaunch sl;
-        // moments of the words this sample consumes: A accepted draws until k distinct values (duplicates: a coupon collector's
-        // first k), each after a geometric number of rejected words (_randbelow)
-        const double n_d = (double)range_population(r, d);
-        const StreamMoments ms = sample_words_moments((uint64_t)n_d, (uint64_t)k);
-        const double e_samp = ms.e, v_samp = ms.v;
-        bool ahead = false;
-        uint64_t lo = 0, H = 0, expect = 0;
-        uint32_t soft_half = 0;
-        if ((g->ahead == 2 || (g->ahead == 1 && g->sharded_rank)) && (grouped || (c->chain_only && n_draw == 1)) && g->est_ok && (uint64_t)n_d <= ((uint64_t)MAX_BINS << BIN_SHIFT) && 4.0 * (double)k <= n_d) {
-            // the interval costs what it holds (its accepted draws go through the fringe pass on the chain): g->ahead_sigma
-            // (8) standard deviations instead of the windows' 16 -- a start outside it is reported like an overflowed window
-            const double m = g->est_v > 0.0 ? g->ahead_sigma * std::sqrt(1.1 * g->est_v) + 256.0 : 0.0;
-            expect = (uint64_t)std::max(0.0, g->est_e);
-            soft_half = (uint32_t)std::min(4.0e9, m);
-            lo = std::max<uint64_t>(g->est_lo, (uint64_t)std::max(0.0, std::floor(g->est_e - m)));
-            H = std::max<uint64_t>(lo, std::min<uint64_t>(pos_hi, (uint64_t)std::ceil(g->est_e + m)));
-            // (a sample smaller than the uncertainty of its start stays on the chain; so does one whose start is known exactly --
-            //  behind a synchronisation the chain is empty and nothing is gained by making it wait for the prep stream)
-            static const bool ahead_first = getenv("MSIM_AHEAD_FIRST") != nullptr;
-            ahead = 2 * (H - lo) <= (uint64_t)k && (g->est_v > 0.0 || ahead_first);
-        }
-        if (g->est_ok) { g->est_e += e_samp; g->est_v += v_samp; g->est_lo += k; }
-        if (ahead) {
-            // the sample ends at or in front of e_lim (and inside its window): what the SNP stage's windows are laid out from
-            const uint64_t e_lim = est_hi(~0ull);
-            if ((rc = enqueue_sample_ahead(c, g, r, d, lo, H, e_lim, grow, sl, ahead, grouped, expect, soft_half))) return rc;
-            if (ahead) pos_hi = std::min<uint64_t>(H + sl.W, e_lim) - sl.W;      // (+ W below)
-        }
-        if (!ahead && (rc = enqueue_sample_chain(c, g, r, d, pos_hi, grow, sl, nullptr, nullptr, est_hi(~0ull)))) return rc;
+        const bool can_ahead = ahead_role && (grouped || (c->chain_only && n_draw == 1));
+        const SampleStep st = sample_step(g->ahead_sigma, g->est, pos_hi, r, d, can_ahead);
+        if (st.bad) return fail(c, MSIM_ERR_UNSUPPORTED, "sample window beyond 2^32 words");
+        const bool ahead = st.ahead;
+        if (ahead && (rc = enqueue_sample_ahead(c, g, r, d, st, grow, sl, grouped))) return rc;
+        if (!ahead && (rc = enqueue_sample_chain(c, g, r, d, st.pos_in, grow, sl, nullptr, nullptr, st.e_lim))) return rc;
         SampleSet &S = *sl.S;
-        const uint32_t W = sl.W, bmw = sl.bmw, bnb = sl.bnb;
+        const uint32_t bmw = sl.bmw, bnb = sl.bnb;
         if (grouped) {
             late = {&S, bmw, bnb, (uint32_t)r.start};
         } else if (!c->chain_only) {
@@ -1551,22 +1708,15 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
                 S.pending = true;
             }
         }
-        pos_hi += W;
-        if (!ahead) pos_hi = est_hi(pos_hi);
         rec_base += k;
     }
     if (K) {                                          // SNP draws in position order (chain: scan + cut; aux off the chain)
         uint8_t *aux8 = nullptr;
         SnpDefer df{nullptr, 0, 0};
-        if (g->est_ok) {                              // a uniform() = 2 words, a transversion's randbelow(2) = a geometric(1/2) loop
-            const StreamMoments mv = snp_words_moments(K, P.ti_lim);
-            g->est_e += mv.e;
-            g->est_v += mv.v;
-            g->est_lo += 2 * K;
-        }
-        // (est_hi(~0): the bound the position is tightened to behind this stage -- the kernel flags a cut beyond it)
-        if ((rc = enqueue_snp_stage(c, g, ct, K, nullptr, pos_hi, grow, late.S ? &aux8 : nullptr, grouped ? &df : nullptr, est_hi(~0ull)))) return rc;
-        pos_hi = est_hi(pos_hi);
+        // (e_lim: the bound the position is tightened to behind this stage -- the kernel flags a cut beyond it)
+        const SnpStep sn = snp_step(g->est, pos_hi, K, P);
+        uint64_t snp_pos = sn.pos_in;
+        if ((rc = enqueue_snp_stage(c, g, ct, K, nullptr, snp_pos, grow, late.S ? &aux8 : nullptr, grouped ? &df : nullptr, sn.e_lim))) return rc;
         if (grouped) {
             g->emit_d = (uint32_t)d;
             g->emit_items.push_back(EmitItem{ct.index, late.S, df.T, late.bmw, late.bnb, late.start, (uint32_t)K, df.W2, df.nb2,
@@ -1592,6 +1742,152 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
     c->t.np_words += 2 * K;
     g->unverified = true;
     ct.planned = true;
+    return MSIM_OK;
+}
+
+// ---- msim_plan_pass: the samples' off-chain parts of a whole segment of contigs, ahead of their chains.
+// Where the pass stands as the host knows it: what plan_contig_gpu reads of the plan's state before it launches anything.
+struct PassCursor { ChainEst est; uint64_t py_pos, np_pos; bool unverified, live, sharded_rank; };
+struct PassRules { int ahead; double ahead_sigma; uint64_t span_w; int max_sets; };
+struct PassStep { SampleStep st; const msim_range *r; bool chain_only; };
+// One item that the SNP sampler takes, walked on the cursor as plan_contig_gpu walks it on the plan.  Returns false (cursor
+// untouched) where the sampler would not get it as it stands: another engine's, a re-base in front of it, no room at all.
+// *hoist: exactly one drawing range, and its sample is an anchored window (out->st: laid out how).
+static bool pass_walk_item(const msim_params &P, const PassRules &R, PassCursor &cur, const msim_pass_item &it, bool *hoist, PassStep *out) {
+    *hoist = false;
+    const bool chain_only = it.contig < 0;
+    if (it.n_ranges < 0 || (it.n_ranges && !it.ranges) || (chain_only && it.len >= (1ull << 32))) return false;
+    if (!sampler_eligible(P, it.ranges, it.n_ranges)) return false;
+    const RoomVerdict room = room_for(stream_need(P, it.ranges, it.n_ranges), R.span_w, cur.live, cur.py_pos, cur.live, cur.np_pos);
+    if (!room.fits || room.rebase) return false;
+    uint64_t K = 0;
+    int n_draw = 0;
+    for (int i = 0; i < it.n_ranges; i++) { K += (uint64_t)it.ranges[i].k; n_draw += it.ranges[i].k != 0; }
+    if (K >= (1ull << 31)) return false;
+    const int64_t d = min_block(P);
+    PassCursor w = cur;
+    w.sharded_rank = cur.sharded_rank || chain_only;
+    if (!w.unverified) w.est = ChainEst{true, (double)w.py_pos, 0.0, w.py_pos};
+    const bool ahead_role = R.ahead == 2 || (R.ahead == 1 && w.sharded_rank);
+    const bool can_ahead = ahead_role && (contig_is_grouped(n_draw, chain_only) || (chain_only && n_draw == 1));
+    uint64_t pos_hi = w.py_pos;
+    bool any_ahead = false;
+    for (int i = 0; i < it.n_ranges; i++) {
+        if (it.ranges[i].k == 0) continue;
+        const SampleStep st = sample_step(R.ahead_sigma, w.est, pos_hi, it.ranges[i], d, can_ahead);
+        if (st.bad) return false;
+        if (st.ahead) { any_ahead = true; if (out) *out = PassStep{st, &it.ranges[i], chain_only}; }
+    }
+    if (K && snp_step(w.est, pos_hi, K, P).bad) return false;
+    w.py_pos = pos_hi;
+    w.np_pos += 2 * K;
+    w.unverified = true;
+    *hoist = w.live && n_draw == 1 && any_ahead;
+    cur = w;
+    return true;
+}
+// THE SEGMENTING RULE: how many of items[0 .. n) form a segment whose prep goes out in front of the first one's chain -- the
+// leading items the SNP sampler takes with one anchored window each, up to the first one that is another engine's or stays on the
+// chain (it changes the estimate as it always did: at its own turn), that would re-base the session (judged on the bound of
+// the position the items before it leave), or that would need a scratch set too many (R.max_sets: a set whose previous user
+// has not been through its emission group yet is never handed out).  The cursor ends behind the segment.
+static int pass_segment(const msim_params &P, const PassRules &R, PassCursor &cur, const msim_pass_item *items, int n, std::vector<PassStep> *steps) {
+    int m = 0;
+    while (m < n && m < R.max_sets) {
+        PassCursor w = cur;
+        PassStep ps{};
+        bool hoist = false;
+        if (!pass_walk_item(P, R, w, items[m], &hoist, &ps) || !hoist) break;
+        cur = w;
+        if (steps) steps->push_back(ps);
+        m++;
+    }
+    return m;
+}
+// N_SETS sets in turn; the EMIT_G contigs planned last may still wait for their emission group, which is what marks their sets
+// as in use (SampleSet::wait_ev) -- so a segment takes at most N_SETS - EMIT_G sets in front of its first chain.
+constexpr int PASS_MAX_SETS = N_SETS - EMIT_G;
+
+int gpu_plan_pass_prep(Ctx *c, GpuPlan *g, const msim_pass_item *items, int n) {
+    if (!g->pass_hoist || !g->hoisted.empty() || n < 1) return MSIM_OK;
+    const PassRules R{g->ahead, g->ahead_sigma, span_words(g), PASS_MAX_SETS};
+    PassCursor cur{g->est, g->s[0].pos, g->s[1].pos, g->unverified, g->s[0].live && g->s[1].live && g->ps_valid, g->sharded_rank};
+    std::vector<PassStep> steps;
+    const int m = pass_segment(c->params, R, cur, items, n, &steps);
+    if (m < 1) return MSIM_OK;
+    int rc;
+    const int64_t d = min_block(c->params);
+    uint64_t upto = 0;
+    for (const PassStep &ps : steps) upto = std::max<uint64_t>(upto, ps.st.H + ps.st.W + 1);
+    if ((rc = ensure_words(c, g, 0, upto, false, false))) return rc;      // (generated on the side streams; the chain waits at its turn)
+    for (int at = 0; at < m;) {
+        const int nj = std::min(m - at, at == 0 ? g->pass_first : g->pass_batch);
+        if ((rc = next_prep_stream(c, g, g->pass_streams))) return rc;
+        AheadGeom geo[PREP_G];
+        SampleSet *sets[PREP_G];
+        uint64_t b_upto = 0;
+        for (int q = 0; q < nj; q++) {
+            const PassStep &ps = steps[(size_t)(at + q)];
+            geo[q] = ahead_geometry(*ps.r, d, ps.st.lo, ps.st.H, ps.st.W);
+            Grow grow{c};
+            if ((rc = ahead_take_set(c, g, geo[q], grow, contig_is_grouped(1, ps.chain_only), sets[q]))) return rc;
+            b_upto = std::max<uint64_t>(b_upto, ps.st.H + ps.st.W + 1);
+        }
+        if ((rc = prep_wait_words(c, g, b_upto, g->pass_gate))) return rc;
+        PrepJobs J;
+        J.n = (uint32_t)nj;
+        for (int q = 0; q < nj; q++) J.j[q] = prep_job(*sets[q], geo[q], steps[(size_t)(at + q)].st.lo, steps[(size_t)(at + q)].st.H);
+        if ((rc = prep_launch(c, g, J, sets[0]->prep_done))) return rc;     // ONE event per batch: its first set's
+        for (int q = 0; q < nj; q++) {
+            const PassStep &ps = steps[(size_t)(at + q)];
+            g->hoisted.push_back(Hoisted{ps.st, ps.r->start, ps.r->k, sets[q], sets[0]->prep_done, q == 0});
+        }
+        at += nj;
+    }
+    return MSIM_OK;
+}
+// A pass ended in the middle of a segment (an error at some contig's turn): the prep of the contigs behind it is in flight on sets
+// nobody will chain on -- wait for it, so that the sets' next users find them idle.
+void gpu_plan_pass_abort(Ctx *c, GpuPlan *g) {
+    if (g->hoisted.empty()) return;
+    g->hoisted.clear();
+    for (auto st : g->prep_streams) if (st) (void)wait_stream(st);
+    (void)c;
+}
+bool gpu_plan_pass_hoisting(const GpuPlan *g) { return !g->hoisted.empty(); }
+
+// test support (msim_dbg_pass_segments): pass_segment over a whole item list, from streams that stand exactly at py_pos / np_pos.
+// seg[i]: 0 = the item takes the per-contig path, s >= 1 = it is in the pass's s-th segment.  An item of another engine is stepped
+// over by the bound of its windows, with the estimate dropped (the engines with a host chain leave an exact position behind).
+int gpu_dbg_pass_segments(const msim_params *P, const msim_pass_item *items, int n, uint64_t py_pos, uint64_t np_pos,
+                          uint32_t max_chunks, int ahead, int32_t *seg) {
+    const uint64_t span_w = (uint64_t)MT_N + (uint64_t)(max_chunks ? std::min<uint32_t>(MT_JUMP_MAX_CHUNKS, std::max<uint32_t>(2, max_chunks)) : (uint32_t)MT_JUMP_MAX_CHUNKS) * MT_CHUNK_WORDS;
+    const PassRules R{ahead, 8.0, span_w, PASS_MAX_SETS};
+    PassCursor cur{ChainEst{}, py_pos, np_pos, false, true, false};
+    int32_t id = 0;
+    for (int i = 0; i < n;) {
+        const int m = pass_segment(*P, R, cur, items + i, n - i, nullptr);
+        if (m) {
+            id++;
+            for (int q = 0; q < m; q++) seg[i + q] = id;
+            i += m;
+            continue;
+        }
+        bool hoist = false;
+        if (!pass_walk_item(*P, R, cur, items[i], &hoist, nullptr)) {
+            // a re-base, or an item the sampler does not take: either way a synchronisation, an exact position behind it
+            cur.unverified = false;
+            cur.est.ok = false;
+            const bool ok_args = items[i].n_ranges >= 0 && (!items[i].n_ranges || items[i].ranges);
+            const StreamNeed need = ok_args ? stream_need(*P, items[i].ranges, items[i].n_ranges) : StreamNeed{0, 0, true};
+            if (ok_args && room_for(need, span_w, true, cur.py_pos, true, cur.np_pos).rebase) cur.py_pos = cur.np_pos = MT_N;
+            if (!pass_walk_item(*P, R, cur, items[i], &hoist, nullptr) && !need.bad && std::isfinite(need.py)) {
+                cur.py_pos += (uint64_t)need.py;           // (another engine's: stepped over by the bound of its windows)
+                cur.np_pos += (uint64_t)need.np;
+            }
+        }
+        seg[i++] = 0;
+    }
     return MSIM_OK;
 }
 
@@ -1968,7 +2264,7 @@ static int mixed_emit(Ctx *c, GpuPlan *g, Contig &ct, MixedSet &M, uint32_t k, u
     M.pending = true;
     py.pos = pos_hi;                                       // bound until the next sync reads the exact value
     g->unverified = true;
-    g->est_ok = false;                                    // (the SNP sampler's estimate of the position ends here)
+    g->est.ok = false;                                    // (the SNP sampler's estimate of the position ends here)
     ct.planned = true;
     return MSIM_OK;
 }

@@ -293,12 +293,14 @@ constexpr int SPL_LDS = SPL_BLOCK + SPL_BLOCK / 32;
 // list.  A workgroup stages its 8192 words through row-padded LDS (coalesced loads, conflict-free
 // per-lane runs), counting-sorts its accepted values by bin in LDS, reserves bin space with one
 // atomicAdd per non-empty bin and writes every bin's run out contiguously.
-__global__ __launch_bounds__(ACC_THREADS) void k_bin_scatter(const uint32_t *__restrict__ raw, const PlanState *ps,
-                                                             uint32_t W, uint32_t shift, uint32_t n, uint32_t k,
-                                                             const uint32_t *__restrict__ block_off, uint32_t n_bins,
-                                                             uint32_t bin_cap, uint32_t *__restrict__ cursors,
-                                                             uint32_t *__restrict__ bins, uint32_t *__restrict__ tail,
-                                                             PlanState *ps_rw, uint32_t raw_counts) {
+// (blk: the workgroup's index among the sample's scatter blocks -- blk, or the block's place in its job of a batched launch;
+//  p0: where the window starts)
+__device__ __forceinline__ void bin_scatter_body(const uint32_t blk, const uint32_t *__restrict__ raw, const unsigned long long p0,
+                                                 uint32_t W, uint32_t shift, uint32_t n, uint32_t k,
+                                                 const uint32_t *__restrict__ block_off, uint32_t n_bins,
+                                                 uint32_t bin_cap, uint32_t *__restrict__ cursors,
+                                                 uint32_t *__restrict__ bins, uint32_t *__restrict__ tail,
+                                                 PlanState *ps_rw, uint32_t raw_counts) {
     // raw_counts: block_off holds k_accept_count's COUNTS, not their prefix sums -- every workgroup adds up the counts in front
     // of its first block itself (a few loads per lane), which takes the scan kernel and its launch off the chain
     __shared__ uint32_t stage[SPL_LDS];
@@ -308,8 +310,7 @@ __global__ __launch_bounds__(ACC_THREADS) void k_bin_scatter(const uint32_t *__r
     __shared__ uint32_t lbase[MAX_BINS + 1];
     __shared__ uint32_t gbase[MAX_BINS];
     for (uint32_t b = threadIdx.x; b < n_bins; b += ACC_THREADS) lhist[b] = 0;
-    const unsigned long long p0 = ps->pos;
-    const uint32_t base = blockIdx.x * SPL_BLOCK;
+    const uint32_t base = blk * SPL_BLOCK;
     {
         uint32_t w[SPL_ITEMS];
 #pragma unroll
@@ -336,13 +337,13 @@ __global__ __launch_bounds__(ACC_THREADS) void k_bin_scatter(const uint32_t *__r
     uint32_t before;                                      // accepted draws in front of this workgroup's words
     if (raw_counts) {
         uint32_t t = 0;
-        for (uint32_t i = threadIdx.x; i < blockIdx.x * (SPL_BLOCK / ACC_BLOCK); i += ACC_THREADS) t += block_off[i];
+        for (uint32_t i = threadIdx.x; i < blk * (SPL_BLOCK / ACC_BLOCK); i += ACC_THREADS) t += block_off[i];
         const uint32_t incl = wg_scan_incl(t, wsum3);
         if (threadIdx.x == ACC_THREADS - 1) s_total = incl;
         __syncthreads();
         before = s_total;
     } else {
-        before = block_off[blockIdx.x * (SPL_BLOCK / ACC_BLOCK)];
+        before = block_off[blk * (SPL_BLOCK / ACC_BLOCK)];
     }
     uint32_t a = before + wg_scan_incl(c, wsum) - c;      // accepted index
     uint32_t slot[SPL_ITEMS];
@@ -372,7 +373,7 @@ __global__ __launch_bounds__(ACC_THREADS) void k_bin_scatter(const uint32_t *__r
             const uint32_t b = threadIdx.x * 4 + q;
             if (b < n_bins) {
                 lbase[b] = run;
-                gbase[b] = h[q] ? atomicAdd(&cursors[b * BIN_SUBS + (blockIdx.x & (BIN_SUBS - 1))], h[q]) : 0;
+                gbase[b] = h[q] ? atomicAdd(&cursors[b * BIN_SUBS + (blk & (BIN_SUBS - 1))], h[q]) : 0;
             }
             run += h[q];
         }
@@ -389,20 +390,28 @@ __global__ __launch_bounds__(ACC_THREADS) void k_bin_scatter(const uint32_t *__r
         const uint32_t v = stage[i];
         const uint32_t b = v >> BIN_SHIFT;
         const uint32_t at = gbase[b] + (i - lbase[b]);
-        if (at < bin_cap) bins[((size_t)b * BIN_SUBS + (blockIdx.x & (BIN_SUBS - 1))) * bin_cap + at] = v;
+        if (at < bin_cap) bins[((size_t)b * BIN_SUBS + (blk & (BIN_SUBS - 1))) * bin_cap + at] = v;
         else over = true;
     }
     if (over) atomicOr(&ps_rw->flags, FLAG_SAMPLE_OVERFLOW);
 }
 
+__global__ __launch_bounds__(ACC_THREADS) void k_bin_scatter(const uint32_t *__restrict__ raw, const PlanState *ps,
+                                                             uint32_t W, uint32_t shift, uint32_t n, uint32_t k,
+                                                             const uint32_t *__restrict__ block_off, uint32_t n_bins,
+                                                             uint32_t bin_cap, uint32_t *__restrict__ cursors,
+                                                             uint32_t *__restrict__ bins, uint32_t *__restrict__ tail,
+                                                             PlanState *ps_rw, uint32_t raw_counts) {
+    bin_scatter_body(blockIdx.x, raw, ps->pos, W, shift, n, k, block_off, n_bins, bin_cap, cursors, bins, tail, ps_rw, raw_counts);
+}
+
 // One workgroup per bin: LDS bitmap, LDS atomics, duplicate count, then the bitmap slice is written
 // out with coalesced 16-B stores (so the global bitmap needs no memset).
-__global__ __launch_bounds__(512) void k_bin_dedupe(const uint32_t *__restrict__ bins, const uint32_t *__restrict__ cursors,
-                                                    uint32_t bin_cap, uint32_t *__restrict__ bitmap,
-                                                    PlanState *__restrict__ ps) {
+__device__ __forceinline__ void bin_dedupe_body(const uint32_t b, const uint32_t *__restrict__ bins,
+                                                const uint32_t *__restrict__ cursors, uint32_t bin_cap,
+                                                uint32_t *__restrict__ bitmap, PlanState *__restrict__ ps) {
     __shared__ __attribute__((aligned(16))) uint32_t lbm[BIN_WORDS];
     __shared__ uint32_t red[8];
-    const uint32_t b = blockIdx.x;
     uint4 *l4 = reinterpret_cast<uint4 *>(lbm);
     for (int i = threadIdx.x; i < BIN_WORDS / 4; i += 512) l4[i] = uint4{0, 0, 0, 0};
     __syncthreads();
@@ -428,6 +437,11 @@ __global__ __launch_bounds__(512) void k_bin_dedupe(const uint32_t *__restrict__
     uint4 *g4 = reinterpret_cast<uint4 *>(bitmap + (size_t)b * BIN_WORDS);
     for (int i = threadIdx.x; i < BIN_WORDS / 4; i += 512) g4[i] = l4[i];
 }
+__global__ __launch_bounds__(512) void k_bin_dedupe(const uint32_t *__restrict__ bins, const uint32_t *__restrict__ cursors,
+                                                    uint32_t bin_cap, uint32_t *__restrict__ bitmap,
+                                                    PlanState *__restrict__ ps) {
+    bin_dedupe_body(blockIdx.x, bins, cursors, bin_cap, bitmap, ps);
+}
 
 // ---- anchored windows (plan_gpu.hip: enqueue_sample_ahead).  Where a contig's sample STARTS is known exactly only when the
 // chain of the contig before it has ended -- but the host knows it to within a few standard deviations of the words consumed
@@ -442,22 +456,21 @@ constexpr int AHEAD_MAX_HEAD_BLOCKS = 1024;              // [lo, H) of at most 2
 // Off the chain, launch 1 of 3 (then k_bin_scatter with raw counts, k_bin_dedupe): blocks [0, nb) count the accepted draws of the
 // core window's 2048-word blocks (k_accept_count, the window's origin as an argument); blocks [nb, nb + nbh) compact the accepted
 // draws of the head interval's blocks, in order, each into its own 2048-entry segment.  Block 0 also resets the bookkeeping.
-__global__ __launch_bounds__(ACC_THREADS) void k_ahead_count(const uint32_t *__restrict__ raw, PlanState *ps_core, PlanState *ps_head,
-                                                             SpecHdr *hdr, unsigned long long H, unsigned long long lo, uint32_t W,
-                                                             uint32_t F, uint32_t nb, uint32_t shift, uint32_t n,
-                                                             uint32_t *__restrict__ block_cnt, uint32_t *__restrict__ cursors,
-                                                             uint32_t n_cursors, uint32_t *__restrict__ hcnt,
-                                                             uint32_t *__restrict__ hacc) {
+__device__ __forceinline__ void ahead_count_body(const uint32_t blk, const uint32_t *__restrict__ raw, PlanState *ps_core,
+                                                 PlanState *ps_head, SpecHdr *hdr, unsigned long long H, unsigned long long lo,
+                                                 uint32_t W, uint32_t F, uint32_t nb, uint32_t shift, uint32_t n,
+                                                 uint32_t *__restrict__ block_cnt, uint32_t *__restrict__ cursors,
+                                                 uint32_t n_cursors, uint32_t *__restrict__ hcnt, uint32_t *__restrict__ hacc) {
     __shared__ uint32_t red[ACC_THREADS / 64];
     __shared__ uint32_t part[ACC_THREADS];
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
+    if (blk == 0 && threadIdx.x == 0) {
         ps_core->pos = H; ps_core->snp_base = H; ps_core->flags = 0; ps_core->dups = 0; ps_core->accepted_used = 0;
         ps_head->pos = lo; ps_head->snp_base = lo; ps_head->flags = 0; ps_head->dups = 0; ps_head->accepted_used = 0;
         hdr->need0 = 0; hdr->d1 = 0;
     }
-    if (blockIdx.x < nb) {
-        for (uint32_t i = blockIdx.x * ACC_THREADS + threadIdx.x; i < n_cursors; i += nb * ACC_THREADS) cursors[i] = 0;
-        const uint32_t i0 = blockIdx.x * ACC_BLOCK + threadIdx.x * ACC_ITEMS;
+    if (blk < nb) {
+        for (uint32_t i = blk * ACC_THREADS + threadIdx.x; i < n_cursors; i += nb * ACC_THREADS) cursors[i] = 0;
+        const uint32_t i0 = blk * ACC_BLOCK + threadIdx.x * ACC_ITEMS;
         uint32_t c = 0;
 #pragma unroll
         for (int q = 0; q < ACC_ITEMS; q++) {
@@ -467,10 +480,10 @@ __global__ __launch_bounds__(ACC_THREADS) void k_ahead_count(const uint32_t *__r
         for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
         __syncthreads();
-        if (threadIdx.x == 0) block_cnt[blockIdx.x] = red[0] + red[1] + red[2] + red[3];
+        if (threadIdx.x == 0) block_cnt[blk] = red[0] + red[1] + red[2] + red[3];
         return;
     }
-    const uint32_t hb = blockIdx.x - nb;
+    const uint32_t hb = blk - nb;
     const uint32_t i0 = hb * ACC_BLOCK + threadIdx.x * ACC_ITEMS;
     uint32_t vals[ACC_ITEMS];
     uint32_t mask = 0, c = 0;
@@ -494,6 +507,49 @@ __global__ __launch_bounds__(ACC_THREADS) void k_ahead_count(const uint32_t *__r
     for (int q = 0; q < ACC_ITEMS; q++)
         if (mask & (1u << q)) hacc[w++] = vals[q];
     if (threadIdx.x == ACC_THREADS - 1) hcnt[hb] = part[threadIdx.x];
+}
+__global__ __launch_bounds__(ACC_THREADS) void k_ahead_count(const uint32_t *__restrict__ raw, PlanState *ps_core, PlanState *ps_head,
+                                                             SpecHdr *hdr, unsigned long long H, unsigned long long lo, uint32_t W,
+                                                             uint32_t F, uint32_t nb, uint32_t shift, uint32_t n,
+                                                             uint32_t *__restrict__ block_cnt, uint32_t *__restrict__ cursors,
+                                                             uint32_t n_cursors, uint32_t *__restrict__ hcnt,
+                                                             uint32_t *__restrict__ hacc) {
+    ahead_count_body(blockIdx.x, raw, ps_core, ps_head, hdr, H, lo, W, F, nb, shift, n, block_cnt, cursors, n_cursors, hcnt, hacc);
+}
+
+// The same three launches for up to PREP_G samples at once (msim_plan_pass: the prep of a whole segment of contigs goes out in
+// front of their chains).  The jobs travel as kernel arguments, as the emission train's do (EmitJobs below); a workgroup finds
+// its job from the jobs' first blocks in the launch's grid -- cblk0 in the count grid (nb + nbh blocks a job), sblk0 in the
+// scatter grid (ceil(W / SPL_BLOCK)), dblk0 in the de-dup grid (n_bins) -- and runs the single-job body with its block index
+// inside the job.  Each job has buffers of its own (its scratch set), so the jobs of a launch share nothing.
+constexpr int PREP_G = 8;
+struct PrepJob {
+    PlanState *ps_core, *ps_head; SpecHdr *hdr;
+    uint32_t *cnt, *cursors, *hcnt, *hacc, *bins, *acc, *bitmap;
+    unsigned long long H, lo;
+    uint32_t W, F, nb, nbh, shift, n, k_core, n_bins, bin_cap;
+    uint32_t cblk0, sblk0, dblk0;
+};
+struct PrepJobs { PrepJob j[PREP_G]; uint32_t n; };
+__device__ __forceinline__ uint32_t prep_job_of(const PrepJobs &J, uint32_t blk, int grid) {      // grid: 0 count, 1 scatter, 2 de-dup
+    uint32_t k = 0;
+    for (uint32_t q = 1; q < J.n; q++) if ((grid == 0 ? J.j[q].cblk0 : grid == 1 ? J.j[q].sblk0 : J.j[q].dblk0) <= blk) k = q;
+    return k;
+}
+__global__ __launch_bounds__(ACC_THREADS) void k_ahead_count_b(const uint32_t *__restrict__ raw, PrepJobs J) {
+    const PrepJob &T = J.j[prep_job_of(J, blockIdx.x, 0)];
+    ahead_count_body(blockIdx.x - T.cblk0, raw, T.ps_core, T.ps_head, T.hdr, T.H, T.lo, T.W, T.F, T.nb, T.shift, T.n, T.cnt, T.cursors,
+                     T.n_bins * BIN_SUBS, T.hcnt, T.hacc);
+}
+// (the window's origin is the job's H: what k_ahead_count wrote to ps_core->pos in the launch before)
+__global__ __launch_bounds__(ACC_THREADS) void k_bin_scatter_b(const uint32_t *__restrict__ raw, PrepJobs J) {
+    const PrepJob &T = J.j[prep_job_of(J, blockIdx.x, 1)];
+    bin_scatter_body(blockIdx.x - T.sblk0, raw, T.H, T.W, T.shift, T.n, T.k_core, T.cnt, T.n_bins, T.bin_cap, T.cursors, T.bins, T.acc,
+                     T.ps_core, 1u);
+}
+__global__ __launch_bounds__(512) void k_bin_dedupe_b(PrepJobs J) {
+    const PrepJob &T = J.j[prep_job_of(J, blockIdx.x, 2)];
+    bin_dedupe_body(blockIdx.x - T.dblk0, T.bins, T.cursors, T.bin_cap, T.bitmap, T.ps_core);
 }
 
 constexpr int FRINGE_ITEMS = 4;

@@ -51,6 +51,14 @@ class Params(C.Structure):           # msim_params
     _fields_ = [("block", C.c_int64 * 8), ("ti_lim", C.c_uint64)]
 
 
+class PassItem(C.Structure):         # msim_pass_item
+    _fields_ = [("contig", C.c_int32), ("flags", C.c_uint32), ("len", C.c_uint64), ("ranges", C.POINTER(Range)),
+                ("n_ranges", C.c_int32), ("rsv", C.c_int32)]
+
+
+PASS_APPLY = 1
+
+
 class BatchContig(C.Structure):      # msim_batch_contig
     _fields_ = [("body", C.c_void_p), ("body_bytes", C.c_uint64), ("n_bases", C.c_uint64),
                 ("lenc", C.c_uint32), ("lenb", C.c_uint32), ("ranges", C.POINTER(Range)),
@@ -109,6 +117,9 @@ SYMBOLS = [
     ("msim_set_params", C.c_int, [_VP, C.POINTER(Params)]),
     ("msim_plan_contig", C.c_int, [_VP, C.c_int, C.POINTER(Range), C.c_int]),
     ("msim_plan_chain", C.c_int, [_VP, C.c_uint64, C.POINTER(Range), C.c_int]),
+    ("msim_plan_pass", C.c_int, [_VP, C.POINTER(PassItem), C.c_int]),
+    ("msim_dbg_pass_segments", C.c_int, [C.POINTER(Params), C.POINTER(PassItem), C.c_int, C.c_uint64, C.c_uint64, C.c_uint32,
+                                         C.c_int, C.POINTER(C.c_int32)]),
     ("msim_plan_was_empty", C.c_int, [_VP, C.c_int, _IP]),
     ("msim_apply_contig", C.c_int, [_VP, C.c_int]),
     ("msim_key_error", C.c_int, [_VP, C.c_int, _U8P, _U64P]),
@@ -527,6 +538,31 @@ class Engine:
         """Advance both streams over a contig this process does not mutate (multi-GPU: a rank that does not own it)."""
         ptr, n, keep = self._ranges_arg(ranges)
         self._check(self.lib.msim_plan_chain(self.h, length, ptr, n))
+        del keep
+
+    @staticmethod
+    def pass_items(items):
+        """The ctypes table ``plan_pass`` hands on, from ``(contig, ranges, apply)`` triples in pass order -- ``contig`` a libmsim
+        id, or ``None`` with ``length`` given as a fourth element for a contig that is only walked (``msim_plan_chain``).  Returns
+        (table, keep-alive)."""
+        arr = (PassItem * max(len(items), 1))()
+        keep = []
+        for slot, it in zip(arr, items):
+            contig, ranges, apply = it[0], it[1], it[2]
+            ptr, n, k = Engine._ranges_arg(ranges)
+            keep.append(k)
+            slot.contig = -1 if contig is None else int(contig)
+            slot.flags = PASS_APPLY if (apply and contig is not None) else 0
+            slot.len = int(it[3]) if contig is None else 0
+            slot.ranges = C.cast(ptr, C.POINTER(Range))
+            slot.n_ranges = n
+        return arr, keep
+
+    def plan_pass(self, items):
+        """A whole pass in one call (``msim_plan_pass``): item by item what ``plan_contig`` / ``plan_chain`` / ``apply_contig``
+        would do in the same order, with the SNP sampler's off-chain work of the contigs to come enqueued up front."""
+        arr, keep = self.pass_items(items)
+        self._check(self.lib.msim_plan_pass(self.h, arr, len(items)))
         del keep
 
     def set_plan_mode(self, mode: int):

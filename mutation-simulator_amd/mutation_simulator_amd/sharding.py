@@ -34,13 +34,21 @@ def run_sharded_pass(engine, sim, contig_ids, owned, plan_descriptors, apply: bo
     """One PLAN + APPLY pass of a rank over contigs resident in HBM: every contig in index order (the streams chain
     across contigs) -- the owned ones planned with emission and applied, the others only walked (``msim_plan_chain``:
     stream positions, no records / SNP outcomes / insert pool) when their ``lengths`` are given, else planned in full.
+    The pass goes to libmsim as ``msim_plan_pass`` calls -- the first contig, then all the others in one: the same work in the
+    same order, and the library sees the contigs to come (the SNP sampler sends their samples' off-chain parts ahead of the chain).
     ``engine`` is an ``_ffi.Engine``; ``contig_ids[i]`` the libmsim id of contig i."""
     mine = set(owned)
-    for chrom in sim.chromosomes:
+
+    def item(chrom):                                       # (the descriptors are made anew in every pass)
         i = chrom.number
         if i in mine or lengths is None:
-            engine.plan_contig(contig_ids[i], plan_descriptors(chrom))
-            if apply and i in mine:
-                engine.apply_contig(contig_ids[i])
-        else:
-            engine.plan_chain(lengths[i], plan_descriptors(chrom))
+            return (contig_ids[i], plan_descriptors(chrom), apply and i in mine)
+        return (None, plan_descriptors(chrom), False, lengths[i])
+    chroms = list(sim.chromosomes)
+    if not chroms:
+        return
+    # The first contig goes out by itself: it starts the streams' session (reseed, jump cascade, word generation: 0.4 ms of device
+    # work at 3 Gb), and the other contigs' descriptors are made beside that instead of in front of it.  A pass's first contig
+    # starts at an exact position and is never hoisted, so the library sees the same segments either way.
+    engine.plan_pass([item(chroms[0])])
+    engine.plan_pass([item(ch) for ch in chroms[1:]])
