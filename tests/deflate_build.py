@@ -323,6 +323,7 @@ def _scan_block(r, blk, state):
         _check_set(cl, "code-length", False)
         ctab = _code_table(cl)
         blk["cl_defined"], blk["cl_used"] = sorted({l for l in cl if l}), set()
+        blk["cl_lengths"], blk["cl_syms"] = list(cl), []
         blk["cross"], blk["ends_on_boundary"], blk["starts_on_boundary"], blk["rep_after_zero_run"] = [], [], [], []
         lens, before = [], None
         state["stage"] = "code lengths"
@@ -332,15 +333,19 @@ def _scan_block(r, blk, state):
             at = len(lens)
             if s < 16:
                 lens.append(s)
+                blk["cl_syms"].append((s, 0))
             else:
                 if s == 16:
                     if not lens:
                         raise ScanError("invalid code lengths", "repeat without a length before it")
                     if before in (17, 18):
                         blk["rep_after_zero_run"].append(before)
-                    lens += [lens[-1]] * (3 + r.field(2))
+                    ext = r.field(2)
+                    lens += [lens[-1]] * (3 + ext)
                 else:
-                    lens += [0] * (3 + r.field(3) if s == 17 else 11 + r.field(7))
+                    ext = r.field(3) if s == 17 else r.field(7)
+                    lens += [0] * (3 + ext if s == 17 else 11 + ext)
+                blk["cl_syms"].append((s, ext))
                 if at < hlit < len(lens):
                     blk["cross"].append(s)
                 if len(lens) == hlit:
@@ -351,6 +356,7 @@ def _scan_block(r, blk, state):
         if len(lens) > hlit + hdist:
             raise ScanError("invalid code lengths", "a run passes HLIT + HDIST")
         ll, dl = lens[:hlit], lens[hlit:]
+        blk["ll_lengths"], blk["d_lengths"] = list(ll), list(dl)
         if not ll[256]:
             raise ScanError("invalid code lengths", "no end-of-block code")
         _check_set(ll, "literal/length", True)
@@ -396,7 +402,8 @@ def _scan_block(r, blk, state):
 
 def scan(payload: bytes, strict: bool = True, limit: int = 1 << 30) -> dict:
     """What a deflate stream holds: {'blocks': [per-block dicts], 'out_len', 'end_bit', 'trailing_bytes', 'error', 'past_bit'}.
-    Per block: type, bit phase of its header, final; stored_len; hlit / hdist / hclen; the code lengths defined and used per
+    Per block: type, bit phase of its header, final; stored_len; hlit / hdist / hclen; of a dynamic block the three tables as
+    sent (ll_lengths, d_lengths, cl_lengths) and their spelling, cl_syms: [(code-length symbol, extra value)]; the code lengths defined and used per
     alphabet (cl_ / ll_ / d_ + defined / used); the run symbols that cross the HLIT boundary, end on it or start on it;
     which zero run (17 / 18) a 16 directly followed; n_dist_codes; the matches as (length, distance, bytes produced before);
     the (symbol, extra value) pairs of both alphabets; the symbols length 258 was coded with; the bit after the
