@@ -790,6 +790,64 @@ int msim_dbg_cmp_counts_diploid(const uint8_t *bases, uint64_t L, const msim_rec
                                 const uint8_t *calls_pool, uint64_t calls_pool_len, const uint8_t *calls_gt, uint32_t flags,
                                 uint64_t *counts, uint64_t tallies[2], uint8_t *truth_flags, uint8_t *calls_flags);
 
+/* ---- compare --diploid --phased: switch and flip errors against a phased truth (csrc/cmp_phase.hip, cmp_phase.h) ------------------- */
+/* Every record of a side's diploid table U carries a PHASE WORD: 0 not phased; MSIM_PHASE_CONTIG phased with no phase set named (the
+ * contig is the set); 1 .. 0xFFFFFFFE phased in the set its PS names.  The word of a VCF line (vcf_cons_phase, csrc/vcf_parse.h): the
+ * sample column and FORMAT are found from the back as the consensus grammar finds them; the GT subfield is phased iff it holds at
+ * least one '|' and no '/' (a haploid GT, a VCF of 8 fields, a GT with '/': word 0); FORMAT's keys are split at ':' and the key that
+ * is exactly PS selects the sample subfield of the same index -- one to ten decimal digits with a value in 1 .. 0xFFFFFFFE give that
+ * value; no PS key, a sample with fewer subfields, an empty subfield or '.' give MSIM_PHASE_CONTIG; anything else (a sign, a letter,
+ * 0, a value too large) gives word 0 and the record is tallied as UNREADABLE -- the run is not refused.
+ * Pairs.  A truth record is INFORMATIVE iff its flag byte (msim_cmp_counts_diploid) is 1, its genotype byte is 1 or 2, its word is
+ *   nonzero and the word of its partner -- the calls' record the match paired it with -- is nonzero.  Such a pair has the key (truth
+ *   word, calls word) and the orientation o: 1 when the two genotype bytes differ, 0 when they are equal.  The informative pairs are
+ *   taken in the truth table's order (pos non-decreasing, haplotype 1's record first at equal pos); every other record is transparent.
+ * Tally.  A BLOCK is a maximal run of consecutive pairs with equal key.  A pair carries a RAW SWITCH BIT iff its predecessor is in
+ *   the same block and has the other orientation.  Inside a block a maximal run of r consecutive raw switch bits counts as r / 2
+ *   FLIPS and r % 2 SWITCHES (the greedy left-to-right pairing of whatshap compare).  A block's HAMMING distance is min(its pairs
+ *   with o = 0, its pairs with o = 1).
+ *   out[MSIM_CMP_PHASE_COUNTS]: truth phased hets (genotype 1 or 2, word nonzero), calls phased hets, pairs, blocks, blocks of one
+ *   pair, assessed adjacencies (pairs - blocks), raw switch bits, switches, flips, Hamming, pairs in blocks of two or more.
+ * Limits.  Interleaved or nested phase sets are cut into more blocks than a per-set sort would give; a line that yields a DE and an
+ *   IN counts as two pairs; a het whose partner is a genotype mismatch is not assessed; one sample per side.
+ *   msim_cmp_phase_mark     directly behind a consensus-grammar msim_vcf_plan_contig of `contig`, while its text is loaded: the
+ *                           (pos, word) of every record of the table just planned are kept as the MARKS of (contig, side,
+ *                           haplotype 1 or 2); tally[3]: phased, unphased, unreadable records.  An empty table: empty marks, nothing
+ *                           launched.  MSIM_ERR_ARG where the contig's last call was no such plan, for an unknown side or haplotype.
+ *   msim_cmp_phase_join     behind msim_cmp_join of that side: U's records get their words -- genotype 1 or 3 from haplotype 1's
+ *                           marks, genotype 2 from haplotype 2's, found by pos -- and the marks are consumed.  MSIM_ERR_ARG without
+ *                           both haplotypes' marks or without the side's diploid table.
+ *   msim_cmp_phase_set      the words of U directly (as msim_set_genotypes sets genotype bytes); MSIM_ERR_ARG without the side's
+ *                           diploid table or when n is not its record count.
+ *   msim_cmp_phase_counts   behind msim_cmp_counts_diploid with the same flags (MSIM_ERR_ARG before that call, with other flags, or
+ *                           before both sides have words).  It changes neither the tables nor the flag bytes nor any count of
+ *                           msim_cmp_counts_diploid.
+ *   msim_cmp_fetch_phase    a side's words and, for the truth (MSIM_ERR_ARG for the calls, or before msim_cmp_phase_counts), a
+ *                           state byte per record: 0 not informative, 1 informative, 2 added with a raw switch bit, 4 added with
+ *                           orientation 1.  Either destination may be NULL.
+ *   msim_cmp_phase_timing   the phase kernels' time on the device (HIP events) since the context was made or msim_reset_stats.
+ * Words, marks and state bytes are consumed where the diploid tables are: msim_cmp_release, msim_clear, msim_destroy; a new
+ * msim_cmp_join of a contig and side consumes that side's words.  MSIM_ERR_HIP on a host-only context.
+ * MSIM_CMP_PHASE_TILE: the records (and the pairs) one workgroup of the passes takes -- where their edge cases lie.
+ * msim_dbg_cmp_phase: out[] and the truth's state bytes (may be NULL) by sequential host loops over two diploid tables with their
+ * genotype bytes and words -- no context, no GPU; the refusals of msim_dbg_cmp_counts_diploid.  msim_dbg_vcf_phase_word: the word of
+ * one VCF line (n bytes, no terminator) of a file with nf0 fields a line, sample column `sample` (0-based); *unreadable (may be
+ * NULL): the line's PS was present and not a readable value.                                                                         */
+#define MSIM_PHASE_CONTIG     0xFFFFFFFFu
+#define MSIM_CMP_PHASE_TILE   256
+#define MSIM_CMP_PHASE_COUNTS 11
+int msim_cmp_phase_mark(msim_ctx *ctx, int contig, int side, int haplotype, uint64_t tally[3]);
+int msim_cmp_phase_join(msim_ctx *ctx, int contig, int side);
+int msim_cmp_phase_set(msim_ctx *ctx, int contig, int side, const uint32_t *words, uint64_t n);
+int msim_cmp_phase_counts(msim_ctx *ctx, int contig, uint32_t flags, uint64_t out[MSIM_CMP_PHASE_COUNTS]);
+int msim_cmp_fetch_phase(msim_ctx *ctx, int contig, int side, uint32_t *words, uint8_t *state);
+int msim_cmp_phase_timing(msim_ctx *ctx, double *kernel_ms);
+int msim_dbg_cmp_phase(const uint8_t *bases, uint64_t L, const msim_record *truth, uint64_t n_truth, const uint8_t *truth_pool,
+                       uint64_t truth_pool_len, const uint8_t *truth_gt, const uint32_t *truth_words, const msim_record *calls,
+                       uint64_t n_calls, const uint8_t *calls_pool, uint64_t calls_pool_len, const uint8_t *calls_gt,
+                       const uint32_t *calls_words, uint32_t flags, uint64_t out[MSIM_CMP_PHASE_COUNTS], uint8_t *truth_state);
+int msim_dbg_vcf_phase_word(const uint8_t *line, uint64_t n, uint32_t nf0, uint32_t sample, uint32_t *word, uint32_t *unreadable);
+
 /* ---- test support: the SNP ti/tv transducer on the caller's words -------------------------------------------------- */
 /* Runs the three passes that turn CPython-stream words into SNP outcomes -- the map pass over whole blocks of
  * MSIM_SNP_BLOCK_WORDS words, the scan that finds where the K-th SNP's draws end, the outcome pass -- over `words` (raw,

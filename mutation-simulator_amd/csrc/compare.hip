@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "cmp_blocks.h"
+#include "cmp_phase.h"
 #include "compare.h"
 #include "ctx.h"
 #include "lane_hist.h"
@@ -45,6 +46,7 @@ struct Dip {                                   // msim_cmp_join's result: one si
 struct DipPair {
     Dip side[2];                               // MSIM_CMP_TRUTH, MSIM_CMP_CALLS
     bool counted = false;
+    uint32_t counted_flags = 0;                // the flags of that msim_cmp_counts_diploid
 };
 
 struct CompareState {
@@ -66,6 +68,7 @@ struct CompareState {
     hipEvent_t ev_blk_mid = nullptr;           // between k_blk_scan and k_blk_replay
     double blocks_ms = 0, scan_ms = 0, replay_ms = 0;
     uint64_t replay_steps = 0, replay_wave_steps = 0;      // msim_dbg_cmp_blocks_split
+    PhaseState *phase = nullptr;               // compare --phased (cmp_phase.hip; made on first use)
 };
 
 namespace {
@@ -424,6 +427,7 @@ int counts_joined(Ctx *c, CompareState *S, const Contig &g, DipPair &p, uint32_t
     p.counted = false;
     const int rc = counts_device<3>(c, S, g, side(p.side[MSIM_CMP_TRUTH]), side(p.side[MSIM_CMP_CALLS]), flags, counts, tallies);
     p.counted = !rc;
+    p.counted_flags = flags;
     return rc;
 }
 
@@ -538,12 +542,38 @@ void compare_drop_all(Ctx *c) {
     if (!c->compare) return;
     c->compare->held.clear();
     c->compare->dip.clear();
+    phase_drop(c->compare->phase, -1);
+}
+
+bool compare_dip_view(Ctx *c, int contig, int side, DipView *v, bool *counted, uint32_t *counted_flags) {
+    CompareState *S = c->compare;
+    *v = DipView{};
+    *counted = false;
+    *counted_flags = 0;
+    if (!S || contig < 0 || (size_t)contig >= S->dip.size() || (side != MSIM_CMP_TRUTH && side != MSIM_CMP_CALLS)) return false;
+    const DipPair &p = S->dip[(size_t)contig];
+    const Dip &d = p.side[side];
+    if (!d.have) return false;
+    *v = DipView{true, {d.d_recs.p(), d.n, d.d_pool.p(), d.pool_len}, d.d_gt.p(), d.d_flag.p()};
+    *counted = p.counted && p.side[0].have && p.side[1].have;
+    *counted_flags = p.counted_flags;
+    return true;
+}
+
+int compare_phase_slot(Ctx *c, PhaseState ***slot) {
+    CompareState *S;
+    const int rc = state_of(c, &S);
+    if (rc) return rc;
+    *slot = &S->phase;
+    return MSIM_OK;
 }
 
 void compare_state_destroy(Ctx *c) {
     CompareState *S = c->compare;
     if (!S) return;
     compare_drop_all(c);
+    phase_state_destroy(S->phase);
+    S->phase = nullptr;
     S->tm.destroy();
     S->tm_blk.destroy();
     S->tm_tally.destroy();
@@ -557,6 +587,7 @@ void compare_reset_timing(Ctx *c) {
     CompareState &S = *c->compare;
     S.kernel_ms = S.join_ms = S.blocks_ms = S.scan_ms = S.replay_ms = 0;
     S.replay_steps = S.replay_wave_steps = 0;
+    phase_reset_timing(S.phase);
 }
 
 }  // namespace msim
@@ -601,6 +632,7 @@ int msim_cmp_release(msim_ctx *p, int contig) {
     if (contig < 0) { compare_drop_all(c); return MSIM_OK; }
     if (Held *h = held_of(c, contig)) *h = Held{};
     if (contig >= 0 && (size_t)contig < c->compare->dip.size()) c->compare->dip[(size_t)contig] = DipPair{};
+    phase_drop(c->compare->phase, contig);
     return MSIM_OK;
 }
 
@@ -701,6 +733,7 @@ int msim_cmp_join(msim_ctx *p, int contig, int side) {
     DipPair &pair = S->dip[(size_t)contig];
     pair.counted = false;
     Dip &d = pair.side[side] = Dip{};
+    phase_drop_side(S->phase, contig, side);
     TraceRange tr("msim compare join");
     rc = join_device(c, S, *g, *h, d);
     if (rc) { d = Dip{}; return rc; }

@@ -18,6 +18,7 @@ struct Contig {
     Scratch<uint8_t> d_in;            // allocation; the bases (uint8, upper-cased) start at d_in + PAD
     // plan result
     bool planned = false;
+    uint64_t table_gen = 0;           // counts the times the plan was forgotten (contig_reset): a table made since is another one
     bool plan_empty = true;
     bool all_snp = false;             // record table holds SNPs only: no length change, offset == pos
     bool delta_known = false;         // the planner already knows out_len - len (SV mixes planned on the device):

@@ -207,6 +207,7 @@ static void reset_contig(Contig &g);
 void contig_reset(Contig &g) { reset_contig(g); }
 static void reset_contig(Contig &g) {   // (callers also drop the context's text cache: see text_kind)
     hap_forget(g);                                         // (a selected haplotype's table, the genotypes: gone with the plan)
+    g.table_gen++;
     g.planned = g.applied = false;
     g.defer_apply = false;
     g.tile_index_by_plan = false;

@@ -370,6 +370,54 @@ VCF_HD uint32_t vcf_cons_ends(const uint8_t *t, uint64_t b, uint64_t e, uint32_t
     return VCF_OK;
 }
 
+// The line's phase word (msim.h: compare --diploid --phased): 0 not phased, MSIM_PHASE_CONTIG phased without a phase set, else its
+// PS.  The sample column and FORMAT are found from the back as vcf_cons_ends finds them; only bytes of [b, e) are read.
+// *unreadable: the GT is phased and its PS is neither absent, empty, '.' nor a value in 1 .. 0xFFFFFFFE (the word is then 0).
+VCF_HD uint32_t vcf_cons_phase(const uint8_t *t, uint64_t b, uint64_t e, uint32_t tabs, uint32_t nf0, uint32_t sample, bool *unreadable) {
+    *unreadable = false;
+    if (tabs + 1 != nf0 || nf0 < 10 || sample >= nf0 - 9) return 0;
+    uint64_t q = e, gt0 = 0, gt1 = 0, fm0 = 0, fm1 = 0;
+    for (uint32_t f = nf0 - 1; f >= 8; f--) {
+        const uint64_t end = q;
+        while (q > b && t[q - 1] != '\t') q--;
+        if (q <= b) return 0;                              // (cannot happen with the tabs counted; keeps every read inside the line)
+        if (f == 9 + sample) { gt0 = q; gt1 = end; }
+        if (f == 8) { fm0 = q; fm1 = end; }
+        q--;
+    }
+    if (fm1 - fm0 < 2 || t[fm0] != 'G' || t[fm0 + 1] != 'T' || (fm1 - fm0 > 2 && t[fm0 + 2] != ':')) return 0;
+    uint64_t g1 = gt0;
+    uint32_t bars = 0, slashes = 0;
+    for (; g1 < gt1 && t[g1] != ':'; g1++) { bars += t[g1] == '|'; slashes += t[g1] == '/'; }
+    if (bars == 0 || slashes != 0) return 0;
+    // the index of the key that is exactly PS (the first such key)
+    constexpr uint32_t NONE = 0xffffffffu;
+    uint32_t key = 0, ps = NONE;
+    uint64_t k0 = fm0;
+    for (uint64_t x = fm0; x <= fm1; x++) {
+        if (x < fm1 && t[x] != ':') continue;
+        if (ps == NONE && x - k0 == 2 && t[k0] == 'P' && t[k0 + 1] == 'S') ps = key;
+        key++;
+        k0 = x + 1;
+    }
+    if (ps == NONE) return MSIM_PHASE_CONTIG;
+    uint32_t cur = 0;
+    uint64_t s0 = gt0;
+    for (uint64_t x = gt0; x < gt1 && cur < ps; x++) if (t[x] == ':') { cur++; s0 = x + 1; }
+    if (cur < ps) return MSIM_PHASE_CONTIG;                // the sample has fewer subfields
+    uint64_t s1 = s0;
+    while (s1 < gt1 && t[s1] != ':') s1++;
+    if (s1 == s0 || (s1 - s0 == 1 && t[s0] == '.')) return MSIM_PHASE_CONTIG;
+    uint64_t v = 0;
+    bool bad = s1 - s0 > 10;
+    for (uint64_t x = s0; x < s1 && !bad; x++) {
+        if (t[x] < '0' || t[x] > '9') bad = true;
+        else v = v * 10 + (uint64_t)(t[x] - '0');
+    }
+    if (bad || v < 1 || v > 0xFFFFFFFEull) { *unreadable = true; return 0; }
+    return (uint32_t)v;
+}
+
 // o.sep is known.  Returns the reason the line is refused for (o.flags still says which bytes the per-byte pass checks: a smaller
 // reason found there wins), or VCF_OK with the line's records described in o.
 VCF_HD uint32_t vcf_cons_line(const uint8_t *t, const uint8_t *in, uint64_t L, VcfCons &o) {

@@ -28,6 +28,7 @@
 #include <cstring>
 #include <string>
 
+#include "cmp_phase.h"
 #include "ctx.h"
 #include "plan_gpu.h"
 #include "vcf_parse.h"
@@ -60,6 +61,10 @@ struct VcfState {
     uint32_t nf0 = 0;                      // fields of the first data line
     Scratch<VcfCons> d_cons;               // consensus grammar: one per line
     Scratch<uint32_t> d_recline;           // the line (index within its group) of every compacted record
+    // the last msim_vcf_plan_contig, where it was a consensus-grammar plan on the device (msim_cmp_phase_mark reads d_recline)
+    int last_contig = -1;                  // -1: none
+    uint64_t last_first = 0, last_lines = 0, last_recs = 0;    // the group's first line and line count, the records it gave
+    uint64_t last_gen = 0;                 // the contig's table_gen behind that plan: a table installed since is not the parser's
 };
 
 namespace {
@@ -843,6 +848,15 @@ int plan_device_cons(Ctx *c, VcfState *S, Contig *g, const msim_vcf_group *grp) 
 
 }  // namespace
 
+bool vcf_last_plan(const Ctx *c, int contig, VcfPlanView *v) {
+    const VcfState *S = c->vcf;
+    if (!S || c->host_only || S->grammar != 1 || S->last_contig != contig || contig < 0 || (size_t)contig >= c->contigs.size()) return false;
+    const Contig &g = c->contigs[(size_t)contig];
+    if (!g.planned || g.hap != 0 || g.table_gen != S->last_gen || g.n_rec != S->last_recs || S->last_first + S->last_lines > S->n_lines) return false;
+    *v = VcfPlanView{S->d_text.p() + PAD, S->d_ls.p(), S->d_tabcum.p(), S->d_recline.p(), S->last_first, S->last_lines, S->last_recs, S->nf0, S->sample};
+    return true;
+}
+
 void vcf_state_destroy(Ctx *c) {
     if (!c->vcf) return;
     if (!c->host_only) {
@@ -906,7 +920,17 @@ int msim_vcf_plan_contig(msim_ctx *p, int contig, int64_t group) {
         return S->grammar ? plan_host_cons(c, S, g, grp) : plan_host(c, S, g, grp);
     }
     TraceRange tr("msim VCF plan contig");
-    return S->grammar ? plan_device_cons(c, S, g, grp) : plan_device(c, S, g, grp);
+    S->last_contig = -1;
+    if (!S->grammar) return plan_device(c, S, g, grp);
+    rc = plan_device_cons(c, S, g, grp);
+    if (!rc) {
+        S->last_contig = contig;
+        S->last_first = grp ? grp->first_line : 0;
+        S->last_lines = grp ? grp->n_lines : 0;
+        S->last_recs = g->n_rec;
+        S->last_gen = g->table_gen;
+    }
+    return rc;
 }
 
 int msim_vcf_select(msim_ctx *p, uint32_t grammar, uint32_t sample_index, uint32_t haplotype) {
@@ -942,6 +966,7 @@ int msim_vcf_select(msim_ctx *p, uint32_t grammar, uint32_t sample_index, uint32
         if (!S->d_recline) MSIM_HIP(c, dev_alloc(S->d_recline, 2 * (most + 1) * sizeof(uint32_t)));
     }
     S->grammar = 1; S->sample = sample_index; S->hap = haplotype; S->nf0 = nf0;
+    S->last_contig = -1;
     return MSIM_OK;
 }
 

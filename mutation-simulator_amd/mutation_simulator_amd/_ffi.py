@@ -207,6 +207,15 @@ SYMBOLS = [
     ("msim_cmp_counts_diploid", C.c_int, [_VP, C.c_int, C.c_uint32, _VP, _VP]),
     ("msim_cmp_fetch_diploid", C.c_int, [_VP, C.c_int, C.c_int, _U64P, _U64P, _VP, _VP, _VP, _VP]),
     ("msim_cmp_join_timing", C.c_int, [_VP, C.POINTER(C.c_double)]),
+    ("msim_cmp_phase_mark", C.c_int, [_VP, C.c_int, C.c_int, C.c_int, _VP]),
+    ("msim_cmp_phase_join", C.c_int, [_VP, C.c_int, C.c_int]),
+    ("msim_cmp_phase_set", C.c_int, [_VP, C.c_int, C.c_int, _VP, C.c_uint64]),
+    ("msim_cmp_phase_counts", C.c_int, [_VP, C.c_int, C.c_uint32, _VP]),
+    ("msim_cmp_fetch_phase", C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP]),
+    ("msim_cmp_phase_timing", C.c_int, [_VP, C.POINTER(C.c_double)]),
+    ("msim_dbg_cmp_phase", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP,
+                                     C.c_uint32, _VP, _VP]),
+    ("msim_dbg_vcf_phase_word", C.c_int, [_VP, C.c_uint64, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     ("msim_dbg_cmp_join", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, _VP, _U64P]),
     ("msim_dbg_cmp_counts_diploid", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, C.c_uint64, _VP,
                                               C.c_uint64, _VP, C.c_uint32, _VP, _VP, _VP, _VP]),
@@ -221,6 +230,9 @@ CMP_BLOCK_GAP = 50       # msim.h: MSIM_CMP_BLOCK_GAP, the default gap of compar
 CMP_BLOCK_RECORDS, CMP_BLOCK_SPAN = 64, 4096     # msim.h: the records / the bases a block may hold and still be replayed
 CMP_TRUTH, CMP_CALLS = 0, 1          # msim.h: MSIM_CMP_TRUTH, MSIM_CMP_CALLS, the sides of a diploid comparison
 CMP_JOIN_TILE = 1024     # msim.h: MSIM_CMP_JOIN_TILE, the records one workgroup of the diploid join's scan takes
+PHASE_CONTIG = 0xFFFFFFFF            # msim.h: MSIM_PHASE_CONTIG, the phase word of a record phased without a phase set
+CMP_PHASE_TILE = 256     # msim.h: MSIM_CMP_PHASE_TILE, the records (and pairs) one workgroup of the phase passes takes
+CMP_PHASE_COUNTS = 11    # msim.h: MSIM_CMP_PHASE_COUNTS, the values of msim_cmp_phase_counts
 SPECTRUM_TILE = 4096     # msim.h: MSIM_SPECTRUM_TILE, the bases one workgroup of the spectrum sampler takes
 SBS_CHANNELS, SBS_TALLIES = 96, 8    # msim.h: MSIM_SBS_CHANNELS, MSIM_SBS_TALLIES
 SBS_PASS = 1024          # msim.h: MSIM_SBS_PASS, the records one workgroup of the profile kernel takes per pass
@@ -787,6 +799,47 @@ class Engine:
         """The diploid join's milliseconds on the device since ``reset_stats`` (HIP events)."""
         a = C.c_double()
         self._check(self.lib.msim_cmp_join_timing(self.h, C.byref(a)))
+        return a.value
+
+    def cmp_phase_mark(self, contig: int, side: int, haplotype: int) -> np.ndarray:
+        """Directly behind a consensus-grammar ``vcf_plan_contig`` of the contig: the phase word of every record of the table just
+        planned, kept as the marks of (contig, side, haplotype); uint64[3]: phased, unphased, unreadable-PS records."""
+        tally = np.zeros(3, dtype=np.uint64)
+        self._check(self.lib.msim_cmp_phase_mark(self.h, int(contig), int(side), int(haplotype), _ptr(tally)), contig)
+        return tally
+
+    def cmp_phase_join(self, contig: int, side: int):
+        """Behind ``cmp_join`` of that side: the diploid table's records get their phase words from the two haplotypes' marks,
+        which are consumed."""
+        self._check(self.lib.msim_cmp_phase_join(self.h, int(contig), int(side)), contig)
+
+    def cmp_phase_set(self, contig: int, side: int, words):
+        """The phase words of the side's diploid table, given directly (uint32, one per record)."""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        self._check(self.lib.msim_cmp_phase_set(self.h, int(contig), int(side), _opt_ptr(words), len(words)), contig)
+
+    def cmp_phase_counts(self, contig: int, exact: bool = False) -> np.ndarray:
+        """Behind ``cmp_counts_diploid`` with the same ``exact``: uint64[CMP_PHASE_COUNTS] -- truth phased hets, calls phased
+        hets, pairs, blocks, blocks of one pair, assessed adjacencies, raw switch bits, switches, flips, Hamming, pairs in blocks
+        of two or more."""
+        out = np.zeros(CMP_PHASE_COUNTS, dtype=np.uint64)
+        self._check(self.lib.msim_cmp_phase_counts(self.h, int(contig), CMP_EXACT if exact else 0, _ptr(out)), contig)
+        return out
+
+    def cmp_fetch_phase(self, contig: int, side: int, state: bool = True) -> tuple:
+        """(phase words, state bytes) of one side's diploid table, both sides joined; the state bytes are the truth's, of the contig's last
+        ``cmp_phase_counts`` (0 not informative, 1 informative, +2 a raw switch bit, +4 orientation 1; None with ``state=False``)."""
+        n = C.c_uint64()
+        self._check(self.lib.msim_cmp_fetch_diploid(self.h, int(contig), int(side), C.byref(n), None, None, None, None, None), contig)
+        words = np.zeros(n.value, dtype=np.uint32)
+        st = np.zeros(n.value, dtype=np.uint8) if state else None
+        self._check(self.lib.msim_cmp_fetch_phase(self.h, int(contig), int(side), _ptr(words), _ptr(st) if state else None), contig)
+        return words, st
+
+    def cmp_phase_timing(self) -> float:
+        """The phase kernels' milliseconds on the device since ``reset_stats`` (HIP events)."""
+        a = C.c_double()
+        self._check(self.lib.msim_cmp_phase_timing(self.h, C.byref(a)))
         return a.value
 
     # test hooks (msim_dbg_*: exported, not part of include/msim.h)
@@ -1474,6 +1527,40 @@ VCF_GROUP_DTYPE = np.dtype([("name_off", "<u8"), ("first_line", "<u8"), ("n_line
 FASTA_RECORD_DTYPE = np.dtype([("h0", "<u8"), ("h1", "<u8"), ("b0", "<u8"), ("b1", "<u8"), ("n_bases", "<u8"),
                                ("lenc", "<u4"), ("lenb", "<u4"), ("flags", "<u4"), ("rsv", "<u4")])   # msim_fasta_record
 FASTA_HAS_BODY, FASTA_BAD_LINES, FASTA_NONUNIFORM = 1, 2, 4
+
+
+def cmp_phase_host(bases, truth, truth_pool, truth_gt, truth_words, calls, calls_pool, calls_gt, calls_words, exact: bool = False) -> tuple:
+    """``msim_dbg_cmp_phase``: what ``Engine.cmp_phase_counts`` returns and the truth's state bytes of ``Engine.cmp_fetch_phase``
+    by sequential host loops over two diploid tables with their genotype bytes and phase words.  No context, no GPU."""
+    lib = load()
+    bases = _as_u8(bases)
+    args = [_opt_ptr(bases), len(bases)]
+    n = []
+    for recs, pool, gt, words in ((truth, truth_pool, truth_gt, truth_words), (calls, calls_pool, calls_gt, calls_words)):
+        recs = np.ascontiguousarray(recs, dtype=RECORD_DTYPE)
+        pool, gt = np.ascontiguousarray(pool, dtype=np.uint8), np.ascontiguousarray(gt, dtype=np.uint8)
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        assert len(gt) == len(recs) == len(words)
+        args += [_opt_ptr(recs), len(recs), _opt_ptr(pool), len(pool), _opt_ptr(gt), _opt_ptr(words)]
+        n.append((recs, pool, gt, words))                  # (kept alive over the call)
+    out = np.zeros(CMP_PHASE_COUNTS, dtype=np.uint64)
+    state = np.zeros(len(n[0][0]), dtype=np.uint8)
+    rc = lib.msim_dbg_cmp_phase(*args, CMP_EXACT if exact else 0, _ptr(out), _opt_ptr(state))
+    if rc != OK:
+        raise _host_error(rc)
+    return out, state
+
+
+def vcf_phase_word(line: bytes, nf0: int, sample: int = 0) -> tuple:
+    """``msim_dbg_vcf_phase_word``: (the phase word of one VCF line of a file with ``nf0`` fields a line, sample column ``sample``;
+    whether its PS was unreadable)."""
+    lib = load()
+    buf = np.frombuffer(bytes(line), dtype=np.uint8)
+    word, bad = C.c_uint32(), C.c_uint32()
+    rc = lib.msim_dbg_vcf_phase_word(_opt_ptr(buf), len(buf), int(nf0), int(sample), C.byref(word), C.byref(bad))
+    if rc != OK:
+        raise _host_error(rc)
+    return word.value, bool(bad.value)
 
 
 def _as_u8(data) -> np.ndarray:

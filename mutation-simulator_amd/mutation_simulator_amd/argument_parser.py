@@ -11,7 +11,8 @@ VCF scored against a truth VCF on the GPU, indels matched up to their placement 
 side and scores genotypes by dosage -- a ``GT`` column, ``GT`` lines in the records file; it is a usage error together with
 ``--haplotype`` or ``--truth-haplotype``; ``--blocks [--block-gap N]`` rescues unmatched records whose block of neighbours writes
 the same bases on both sides -- ``BLK`` columns and lines; a usage error together with ``--diploid``, as is ``--block-gap`` without
-``--blocks``; ``compare_refusal`` words what it does not cover).
+``--blocks``; ``--diploid --phased`` also compares the phasing and writes ``<outbase>_ms.compare.phase.tsv`` (``outcompare_phase``),
+a usage error without ``--diploid`` or with ``--blocks``; ``compare_refusal`` words what it does not cover).
 
 ``--ploidy 2 [--het F]`` (``args`` / ``rmt``) writes two haplotype Fastas, ``<outbase>_ms_h1<suffix>`` and ``<outbase>_ms_h2<suffix>``
 (``args.outfasta_h1`` / ``outfasta_h2``; ``<outbase>_ms<suffix>`` is not written), one phased ``<outbase>_ms.vcf`` and, with ``--chain``,
@@ -59,6 +60,7 @@ def add_outfile_names(args: Namespace) -> Namespace:
     if getattr(args, "mode", None) == "compare":
         args.outcompare = args.outfasta.with_suffix(".compare.tsv")
         args.outcompare_records = args.outfasta.with_suffix(".compare.records.tsv")
+        args.outcompare_phase = args.outfasta.with_suffix(".compare.phase.tsv")
     if getattr(args, "ploidy", 1) == 2:           # a diploid run: a Fasta (and a chain) per haplotype, ONE phased VCF
         for h in ("h1", "h2"):
             fa = args.outfasta.with_stem(f"{args.outfasta.stem}_{h}")
@@ -213,6 +215,10 @@ def build_parser() -> ArgumentParser:
                        help="Score genotypes against a diploid truth: both haplotypes of each side are joined into distinct "
                             "variants with a dosage (0/1 or 1/1, phase ignored; a haploid 1 counts as 1/1); a variant found with "
                             "the wrong dosage is reported as GT. Cannot be combined with --truth-haplotype or --haplotype")
+    p_cmp.add_argument("--phased", action="store_true", default=False,
+                       help="With --diploid: also compare the phasing of the matched heterozygous variants against the truth's "
+                            "(GT written with |, PS naming the phase set) and write <outbase>_ms.compare.phase.tsv: switch errors, "
+                            "switches and flips, blockwise Hamming distance. Cannot be combined with --blocks")
     p_cmp.add_argument("--exact", action="store_true", default=False,
                        help="Compare positions literally: an indel placed elsewhere in its repeat counts as missed and as extra")
     p_cmp.add_argument("--blocks", action="store_true", default=False,
@@ -338,6 +344,10 @@ def get_args(argv=None) -> Namespace:
             parser.error("--block-gap needs --blocks")
         if args.blocks and args.diploid:
             parser.error("--blocks compares one haplotype against one: it cannot be combined with --diploid")
+        if args.phased and args.blocks:
+            parser.error("--phased compares the phasing of a diploid comparison: it cannot be combined with --blocks")
+        if args.phased and not args.diploid:
+            parser.error("--phased needs --diploid")
         if args.block_gap is not None and not 0 <= args.block_gap <= 4096:
             parser.error("--block-gap must lie in 0..4096")
     if args.quiet:

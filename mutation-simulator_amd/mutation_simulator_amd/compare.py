@@ -24,6 +24,12 @@ sequence: ``msim_cmp_counts_blocks`` cuts both tables into blocks of neighbourin
 unmatched record -- the bytes the rewrite writes with the truth's records of the block alone against the bytes it writes with the
 calls' alone (csrc/cmp_blocks.hip) -- and marks the unmatched records of an equal block as matched as part of a block.  The table
 gains ``TP.calls``, ``BLK`` and ``BLK.calls``, the comment lines a ``blocks:`` line, the records file ``BLK`` lines.
+
+``--diploid --phased`` compares the phasing as well: behind each haplotype's plan ``msim_cmp_phase_mark`` reads every record's
+phase word off its line (``GT`` written with ``|``, ``PS``), behind each join ``msim_cmp_phase_join`` hands the words to the
+diploid table, and behind each contig's counts ``msim_cmp_phase_counts`` takes the matched hets that are phased on both sides in
+position order (csrc/cmp_phase.hip): blocks, raw switch bits, switches and flips, Hamming distance.  ``*_ms.compare.phase.tsv``
+holds them, the comment lines of the table a ``phasing:`` line, the records file ``SW`` lines.
 """
 from __future__ import annotations
 
@@ -106,6 +112,41 @@ def render(notes, counts, names=None, blocks: bool = False) -> str:
     return "\n".join(lines) + "\n"
 
 
+# ---- --diploid --phased: the phase table and the SW lines of --list -----------------------------------------------------------
+PHASE_HEADER = ("contig", "truth.het.phased", "calls.het.phased", "pairs", "blocks", "singletons", "assessed", "switch.raw", "switch.rate",
+                "switches", "flips", "switchflip.rate", "hamming", "hamming.rate")
+PHASED_GT = {1: "1|0", 2: "0|1"}                                          # a het's genotype byte, phased
+
+
+def phase_row(label: str, out) -> str:
+    """One row of ``*_ms.compare.phase.tsv`` from the values of ``msim_cmp_phase_counts``: ``switch.rate`` = raw switch bits /
+    assessed adjacencies, ``switchflip.rate`` = (switches + flips) / assessed, ``hamming.rate`` = Hamming / pairs in blocks of two
+    or more."""
+    th, ch, pairs, blocks, single, assessed, raw, sw, fl, ham, blocked = (int(x) for x in out)
+    return "\t".join([label, str(th), str(ch), str(pairs), str(blocks), str(single), str(assessed), str(raw), ratio(raw, assessed),
+                      str(sw), str(fl), ratio(sw + fl, assessed), str(ham), ratio(ham, blocked)])
+
+
+def render_phase(notes, phase, names=None) -> str:
+    """The text of ``*_ms.compare.phase.tsv``: ``#`` comment lines, the header, the ``ALL`` row (the sum of ``phase`` over the
+    contigs) and, with ``names``, a row per contig."""
+    phase = np.asarray(phase, dtype=np.uint64).reshape(-1, _ffi.CMP_PHASE_COUNTS)
+    lines = [f"# {note}" for note in notes] + ["\t".join(PHASE_HEADER), phase_row("ALL", phase.sum(axis=0, dtype=np.uint64))]
+    lines += [phase_row(name, phase[i]) for i, name in enumerate(names or ())]
+    return "\n".join(lines) + "\n"
+
+
+def switch_rows(contig: str, truth, truth_gt, state) -> list:
+    """The ``SW`` lines of ``--list`` for one contig: every pair with a raw switch bit -- kind, contig, 1-based position, type,
+    length, the truth's and the calls' genotype as ``1|0`` / ``0|1`` (state bit 2: the calls' is the other one)."""
+    out = []
+    for k in np.flatnonzero(np.asarray(state) & 2):
+        r, g = truth[k], int(truth_gt[k])
+        out.append("\t".join(["SW", contig, str(int(r["pos"]) + 1), TYPE_NAMES[int(r["type"])], str(int(r["stop"]) - int(r["pos"]) + 1),
+                              PHASED_GT[g], PHASED_GT[3 - g if int(state[k]) & 4 else g]]))
+    return out
+
+
 def record_rows(kind: str, contig: str, recs, flags, flag: int = 0, side=None) -> list:
     """The lines of ``--list`` for one table: every record whose flag byte is ``flag`` (0: unmatched; 2, with ``--blocks``:
     matched as part of a block -- ``BLK`` lines, which name their ``side``, ``truth`` or ``calls``, in a sixth field)."""
@@ -154,6 +195,8 @@ class Compare:
         self.counts = None           # uint64[contigs, 8, CMP_BINS, 4] of the last run ([..., 6] with --diploid)
         self.tallies = None          # uint64[contigs, 2]
         self.block_tallies = None    # uint64[contigs, 5] (--blocks)
+        self.phase = None            # uint64[contigs, CMP_PHASE_COUNTS] (--phased)
+        self.phase_marks = None      # uint64[2, 3] (--phased): per side the phased, unphased, unreadable-PS records
 
     def _plan(self, eng, side: str, path, names, cids, sample, haplotype):
         """One file's tables onto the contigs; (bytes of its text, load kernel ms, plan kernel ms)."""
@@ -167,13 +210,21 @@ class Compare:
         """One file's two haplotypes onto the contigs, joined into the side's diploid tables: haplotype 1 planned and held,
         haplotype 2 planned from the same loaded text, every contig joined."""
         text = load_vcf_text(path, eng)
+        phased = bool(getattr(self._args, "phased", False))
+
+        def marker(haplotype):
+            def mark(cid):
+                self.phase_marks[side_id] += eng.cmp_phase_mark(cid, side_id, haplotype)
+            return mark if phased else None
         with refusals_of(side):
-            plan_all(eng, text, names, cids, (sample, 1))
+            plan_all(eng, text, names, cids, (sample, 1), marker(1))
             for cid in cids:
                 eng.cmp_hold(cid)
-            plan_loaded(eng, text, names, cids, (sample, 2))
+            plan_loaded(eng, text, names, cids, (sample, 2), marker(2))
         for cid in cids:
             eng.cmp_join(cid, side_id)
+            if phased:
+                eng.cmp_phase_join(cid, side_id)
         load_ms, plan_ms = eng.vcf_timing()
         eng.vcf_release()
         return int(text.shape[0]), load_ms, plan_ms
@@ -186,10 +237,14 @@ class Compare:
         _, names, cids = resident_genome(eng, fa, "compare")
         diploid, listing = bool(getattr(args, "diploid", False)), bool(getattr(args, "list_records", False))
         blocks = bool(getattr(args, "blocks", False))
+        phased = bool(getattr(args, "phased", False))
         gap = getattr(args, "block_gap", None)
         gap = _ffi.CMP_BLOCK_GAP if gap is None else int(gap)
         if blocks and diploid:
             raise CompareError("--blocks compares one haplotype against one: it cannot be combined with --diploid")
+        if phased and not diploid:
+            raise CompareError("--phased needs --diploid")
+        self.phase_marks = np.zeros((2, 3), dtype=np.uint64)
         truth_sample, sample = getattr(args, "truth_sample", None), getattr(args, "sample", None)
         if diploid:
             join0 = eng.cmp_join_timing()
@@ -205,20 +260,26 @@ class Compare:
         exact = bool(getattr(args, "exact", False))
         cmp0 = eng.cmp_timing()                        # (a caller's engine may have compared before)
         blk0 = eng.cmp_blocks_timing() if blocks else 0.0
+        phase0 = eng.cmp_phase_timing() if phased else 0.0
         n = len(cids)
         self.counts = np.zeros((n, 8, _ffi.CMP_BINS, 6 if diploid or blocks else 4), dtype=np.uint64)
         self.tallies = np.zeros((n, 2), dtype=np.uint64)
         self.block_tallies = np.zeros((n, 5), dtype=np.uint64)
+        self.phase = np.zeros((n, _ffi.CMP_PHASE_COUNTS), dtype=np.uint64)
         listed = []
         for i, cid in enumerate(cids):
             if blocks:
                 self.counts[i], self.tallies[i], self.block_tallies[i] = eng.cmp_counts_blocks(cid, exact, gap)
             else:
                 self.counts[i], self.tallies[i] = eng.cmp_counts_diploid(cid, exact) if diploid else eng.cmp_counts(cid, exact)
+            if phased:
+                self.phase[i] = eng.cmp_phase_counts(cid, exact)
             if listing and diploid:
                 a, _, ga, fa_flags = eng.cmp_fetch_diploid(cid, _ffi.CMP_TRUTH)
                 b, _, gb, fb_flags = eng.cmp_fetch_diploid(cid, _ffi.CMP_CALLS)
                 listed += record_rows_diploid(names[i], a, ga, fa_flags, b, gb, fb_flags)
+                if phased:
+                    listed += switch_rows(names[i], a, ga, eng.cmp_fetch_phase(cid, _ffi.CMP_TRUTH)[1])
             elif listing:
                 held, _, fa_flags, fb_flags = eng.cmp_fetch(cid)
                 current = eng.fetch_records(cid)[0]
@@ -235,8 +296,12 @@ class Compare:
             self.stats["cmp_join_kernel_ms"] = round(eng.cmp_join_timing() - join0, 4)
         else:
             eng.vcf_release()                          # (a diploid side released its text behind its joins)
+        if phased:
+            self.stats["cmp_phase_kernel_ms"] = round(eng.cmp_phase_timing() - phase0, 4)
         eng.cmp_release()
         args.outcompare.write_text(self.render(names))
+        if phased:
+            args.outcompare_phase.write_text(self.render_phase(names))
         if listing:
             args.outcompare_records.write_text("".join(line + "\n" for line in listed))
 
@@ -258,6 +323,9 @@ class Compare:
                  f"truth indels whose placements end at a base outside ACGT: {int(tallies[1])}"]
         if diploid:
             notes.insert(3, "genotypes: diploid, unphased (dosage compared; a haploid 1 counts as 1/1)")
+        if diploid and getattr(args, "phased", False):
+            total = self.phase.sum(axis=0, dtype=np.uint64)
+            notes.insert(4, f"phasing: {int(total[2])} pairs in {int(total[3])} blocks, {int(total[6])} raw switches (see {args.outcompare_phase.name})")
         blocks = bool(getattr(args, "blocks", False))
         if blocks:
             gap = getattr(args, "block_gap", None)
@@ -265,6 +333,23 @@ class Compare:
             notes.append(f"blocks: gap {_ffi.CMP_BLOCK_GAP if gap is None else int(gap)}; {t[0]} candidates, {t[1]} replayed, {t[2]} equal, "
                          f"{t[3]} over a limit ({_ffi.CMP_BLOCK_RECORDS} records, {_ffi.CMP_BLOCK_SPAN} bases), {t[4]} holding a translocation")
         return render(notes, self.counts, names if getattr(args, "per_contig", False) else None, blocks)
+
+    def render_phase(self, names) -> str:
+        """The text of ``*_ms.compare.phase.tsv``."""
+        args = self._args
+
+        def side(k, sample):
+            p, u, bad = (int(x) for x in self.phase_marks[k])
+            return (f"sample {sample if sample is not None else '(first)'}; records of both haplotype tables: {p} phased, {u} unphased, "
+                    f"{bad} with an unreadable PS")
+        notes = [f"compare --phased: calls {args.callsfile.name} against truth {args.truthfile.name} on "
+                 f"{getattr(args, 'genome_name', args.infile.name)} ({len(names)} contigs)",
+                 f"truth: {side(_ffi.CMP_TRUTH, getattr(args, 'truth_sample', None))}",
+                 f"calls: {side(_ffi.CMP_CALLS, getattr(args, 'sample', None))}",
+                 "pairs: matched heterozygous variants phased on both sides; blocks: runs of pairs in one truth and one calls phase set",
+                 "switch.rate = switch.raw / assessed; switchflip.rate = (switches + flips) / assessed; "
+                 "hamming.rate = hamming / pairs in blocks of two or more"]
+        return render_phase(notes, self.phase, names if getattr(args, "per_contig", False) else None)
 
     def close(self):
         eng = self._engine

@@ -78,16 +78,17 @@ def resident_genome(engine, fasta, mode_name: str):
     return recs, [r.name for r in recs], [put_contig(engine, r) for r in recs]
 
 
-def plan_all(engine, text: np.ndarray, names, contig_ids, consensus=None) -> None:
+def plan_all(engine, text: np.ndarray, names, contig_ids, consensus=None, after_plan=None) -> None:
     """Load ``text`` and plan every contig (``contig_ids[i]`` is the context's id of the contig called ``names[i]``) from the
     lines that name it, in FILE order, so that the first offending line of the file is the one reported (ValueError /
     VcfReplayError, "VCF line N: ...").  Contigs without lines get an empty table.  Nothing has been rewritten when this raises.
-    ``consensus``: None for the simulator's dialect, or (sample name or None, haplotype) for the general grammar."""
+    ``consensus``: None for the simulator's dialect, or (sample name or None, haplotype) for the general grammar.
+    ``after_plan``: None, or a hook called as ``after_plan(contig id)`` directly behind each contig's plan."""
     engine.vcf_load(text)
-    plan_loaded(engine, text, names, contig_ids, consensus)
+    plan_loaded(engine, text, names, contig_ids, consensus, after_plan)
 
 
-def plan_loaded(engine, text: np.ndarray, names, contig_ids, consensus=None) -> None:
+def plan_loaded(engine, text: np.ndarray, names, contig_ids, consensus=None, after_plan=None) -> None:
     """``plan_all`` behind its ``vcf_load``: plan every contig from the text the context already holds, under the grammar and
     haplotype selected here -- so one loaded file can be planned once per haplotype (``compare --diploid``)."""
     groups = engine.vcf_groups()
@@ -116,9 +117,13 @@ def plan_loaded(engine, text: np.ndarray, names, contig_ids, consensus=None) -> 
             engine.vcf_plan_contig(contig_ids[i], k)
         except ValueError as e:
             raise VcfReplayError(str(e)) from None
+        if after_plan is not None:
+            after_plan(contig_ids[i])
     for i, cid in enumerate(contig_ids):
         if i not in seen:
             engine.vcf_plan_contig(cid, -1)
+            if after_plan is not None:
+                after_plan(cid)
 
 
 class VcfReplay:

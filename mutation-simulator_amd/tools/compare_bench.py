@@ -26,7 +26,15 @@ dropped one time in four and kept otherwise -- and installed with msim_dbg_set_r
   cmp_kernel_ms_in_blocks   k_cmp_match<2> + k_cmp_tally<3> of the same calls (msim_cmp_timing)
   blk_scan_ms, blk_replay_ms   the two kernels apart, and replay_lane_use: the bytes the replay's lanes compared over 64 x the
                             longest lane of every wave -- what blocks of different lengths leave of a wave (msim_dbg_cmp_blocks_split)
-the derived pair's figures under derived_*, with its own cmp_kernel_ms (no blocks) and copy floor."""
+the derived pair's figures under derived_*, with its own cmp_kernel_ms (no blocks) and copy floor.
+
+With --phased (with --diploid) a third section follows: the calls become the truth's own tables again (the truth's key planned and
+genotyped once more) with 1 % of the heterozygous records on the other haplotype, joined; the truth's words are one phase set per
+contig, the calls' sets of 4096 records (msim_cmp_phase_set).  Every record then has a partner and half of them are pairs.  Per
+genome, medians of `runs` with min and max, all from this process:
+  cmp_phase_kernel_ms           msim_cmp_phase_counts (msim_cmp_phase_timing: its six kernels)
+  phased_cmp_diploid_kernel_ms  k_cmp_match<3> + k_cmp_tally<3> on the same tables (msim_cmp_counts_diploid, which the pass follows)
+  phase_copy_floor_ms           a device-to-device copy of the bytes the phase pass reads and writes (msim_dbg_cmp_phase_copy_floor)"""
 import ctypes as C
 import json
 import statistics
@@ -121,6 +129,11 @@ def main():
         sys.argv.remove("--blocks")
     if blocks and diploid:
         sys.exit("--blocks replaces the calls' tables: run it without --diploid")
+    phased = "--phased" in sys.argv
+    if phased:
+        sys.argv.remove("--phased")
+    if phased and not diploid:
+        sys.exit("--phased measures the pass behind the diploid comparison: run it with --diploid")
     runs = max(7, int(sys.argv[1])) if len(sys.argv) > 1 else 7
     total = int(float(sys.argv[2])) if len(sys.argv) > 2 else 3_000_000_000
     out_path = Path(sys.argv[3]) if len(sys.argv) > 3 else None
@@ -131,6 +144,8 @@ def main():
     copy_floor.restype, copy_floor.argtypes = C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
     join_floor = _ffi.load().msim_dbg_cmp_join_copy_floor
     join_floor.restype, join_floor.argtypes = C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+    phase_floor = _ffi.load().msim_dbg_cmp_phase_copy_floor
+    phase_floor.restype, phase_floor.argtypes = C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
     split = _ffi.load().msim_dbg_cmp_blocks_split
     split.restype, split.argtypes = C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]
     eng = _ffi.Engine(0, _ffi.RNG_FAST)
@@ -245,6 +260,43 @@ def main():
                 joins.append(j)
                 join_floors.append(f)
                 dips.append(diploid_pass()[0])
+        if phased:                                     # (last: the calls' tables are replaced)
+            rs = np.random.RandomState(7)
+            eng.set_fast_key(KEYS[0])
+            swapped = 0
+            for i, (cid, ch) in enumerate(zip(cids, sim.chromosomes)):
+                eng.plan_contig(cid, mm.plan_table(ch))
+                eng.genotype_contig(cid, KEYS[0], i, HET_THR)
+                gt = eng.fetch_genotypes(cid, eng.result_sizes(cid, applied=False)[1])
+                flip = (gt != 3) & (rs.random_sample(len(gt)) < 0.01)
+                gt[flip] = 3 - gt[flip]
+                swapped += int(flip.sum())
+                eng.set_genotypes(cid, gt)
+                join_pass_one(eng, cid, _ffi.CMP_CALLS)
+                for side in (_ffi.CMP_TRUTH, _ffi.CMP_CALLS):
+                    n = C.c_uint64()
+                    eng._check(eng.lib.msim_cmp_fetch_diploid(eng.h, cid, side, C.byref(n), None, None, None, None, None), cid)
+                    words = np.ones(n.value, dtype=np.uint32) if side == _ffi.CMP_TRUTH else 1 + (np.arange(n.value, dtype=np.uint32) >> 12)
+                    eng.cmp_phase_set(cid, side, words)
+            res["phased_swapped_hets"] = swapped
+
+            def phased_pass():
+                """(phase ms, the diploid comparison's ms on the same tables, copy floor ms, the summed counts)"""
+                eng.reset_stats()
+                out, floor_ms = np.zeros(_ffi.CMP_PHASE_COUNTS, dtype=np.uint64), 0.0
+                for cid in cids:
+                    eng.cmp_counts_diploid(cid)
+                    out += eng.cmp_phase_counts(cid)
+                dip_ms, phase_ms = eng.cmp_timing(), eng.cmp_phase_timing()
+                for cid in cids:
+                    ms = C.c_double()
+                    eng._check(phase_floor(eng.h, cid, C.byref(ms)), cid)
+                    floor_ms += ms.value
+                return phase_ms, dip_ms, floor_ms, out
+
+            out = phased_pass()[3]                         # warm-up: code objects, the pass's scratch
+            res["phase_counts"] = [int(x) for x in out]
+            phases = [phased_pass()[:3] for _ in range(runs)]
     finally:
         eng.close()
     med = statistics.median
@@ -265,6 +317,12 @@ def main():
         res["cmp_diploid_kernel_ms_min_max"] = [min(dips), max(dips)]
         res["diploid_over_haploid"] = med(dips) / med(rows)
         res["join_over_diploid_counts"] = med(joins) / med(dips)
+    if phased:
+        for name, col in (("cmp_phase_kernel_ms", 0), ("phased_cmp_diploid_kernel_ms", 1), ("phase_copy_floor_ms", 2)):
+            res[name] = med(p[col] for p in phases)
+            res[name + "_min_max"] = [min(p[col] for p in phases), max(p[col] for p in phases)]
+        res["phase_over_floor"] = res["cmp_phase_kernel_ms"] / res["phase_copy_floor_ms"]
+        res["phase_over_diploid_counts"] = res["cmp_phase_kernel_ms"] / res["phased_cmp_diploid_kernel_ms"]
     for k, v in res.items():
         print(f"{k}: {v:.4g}" if isinstance(v, float) else f"{k}: {v}")
     if out_path:
