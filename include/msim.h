@@ -848,6 +848,67 @@ int msim_dbg_cmp_phase(const uint8_t *bases, uint64_t L, const msim_record *trut
                        const uint32_t *calls_words, uint32_t flags, uint64_t out[MSIM_CMP_PHASE_COUNTS], uint8_t *truth_state);
 int msim_dbg_vcf_phase_word(const uint8_t *line, uint64_t n, uint32_t nf0, uint32_t sample, uint32_t *word, uint32_t *unreadable);
 
+/* ---- compare --regions / --stratify: records scored inside BED intervals (csrc/cmp_regions.hip, cmp_regions.h, bed.cpp) ------------ */
+/* A REGION SET of a contig of L bases is a list of n half-open 0-based intervals [start, end) in normal form: start < end <= L and
+ * start[i] > end[i-1] -- overlapping and abutting intervals have been merged.  n == 0 is the empty set: nothing is inside it.
+ * Anchor.  A record's ANCHOR is, for IN and DE, the leftmost of its placements -- lo of the interval the match gives it (rules
+ *   above: walk, window and base stops unchanged) --; with MSIM_CMP_EXACT, and for every other type, its pos.  A record is INSIDE a
+ *   set iff some interval holds its anchor: an upper-bound binary search over the starts, then anchor < end of the interval in front.
+ *   Matched partners are of one class and one window and so share lo: both records of a pair fall on the same side of every region
+ *   edge however the two files placed the indel, and truth matched == calls matched holds in every cell of every restriction.
+ * Limit.  Only the anchor counts: a DE, DU, IV or TL that reaches out of an interval is inside if its anchor is, and one that reaches
+ *   into an interval from an anchor in front of it is outside.
+ * A contig keeps up to MSIM_CMP_REGION_SETS resident sets.  The MARK of a record is one byte, bit s set iff the record is inside set
+ * s (bits of sets that are not resident: 0; a record of unknown type: 0).  `flags`: MSIM_CMP_EXACT, and MSIM_CMP_DIPLOID for the
+ * contig's two diploid tables (msim_cmp_join) in place of its held and current table.
+ *   msim_cmp_regions_set      set `set` (0 .. MSIM_CMP_REGION_SETS - 1) of the contig, replacing one set before; the contig's marks are
+ *                             forgotten.  MSIM_ERR_ARG for a set index out of range, a list not in normal form or an end beyond the
+ *                             contig's length.
+ *   msim_cmp_regions_drop     one set (set -1: all of the contig's; contig -1: every contig's) and the contig's marks.  Sets and marks
+ *                             also go where held tables go: msim_cmp_release, msim_clear, msim_destroy.
+ *   msim_cmp_regions_mark     the mark bytes of both tables -- held and current (the contig planned), or the two diploid tables --
+ *                             with one walk per record and one search per record and resident set.  MSIM_ERR_ARG without the tables
+ *                             the flags name.  Two empty tables: nothing launched.
+ *   msim_cmp_counts_regions   behind msim_cmp_regions_mark AND behind the count call whose flag bytes it tallies again --
+ *                             msim_cmp_counts or msim_cmp_counts_blocks; with MSIM_CMP_DIPLOID msim_cmp_counts_diploid --, all three
+ *                             with the same MSIM_CMP_EXACT bit.  counts: the layout and width of that count call ([..][4]; [..][6]
+ *                             behind the blocks and the diploid call), holding only the records inside EVERY set of `mask`;
+ *                             outside[2]: the truth's and the calls' records that are not.  mask == 0: the count call's own counts,
+ *                             outside 0.  MSIM_ERR_ARG before either call, with another exact bit, after a set of the contig changed
+ *                             since the mark, after a new hold, join or current table since the mark, for a mask bit whose set is
+ *                             not resident.
+ *   msim_cmp_fetch_regions    the mark bytes of the last msim_cmp_regions_mark with these flags' tables: one per truth record, one per
+ *                             calls record (either destination may be NULL); the refusals of msim_cmp_counts_regions' mark.
+ *   msim_cmp_regions_timing   the two kernels' time on the device (HIP events) since the context was made or msim_reset_stats.
+ * All of them: MSIM_ERR_HIP on a host-only context.
+ * msim_dbg_cmp_counts_regions: the same counts, outside[2] and both mark arrays (either may be NULL) by sequential host loops over
+ * the caller's bases, two tables with their flag bytes (those of the count call with `outcomes` 2 or 3 outcomes) and n_sets <=
+ * MSIM_CMP_REGION_SETS sets -- set s is starts / ends [set_off[s], set_off[s + 1]) --, no context, no GPU.  MSIM_ERR_ARG for a record
+ * of unknown type, a set not in normal form or beyond L, outcomes other than 2 or 3, a mask bit at or above n_sets.
+ * msim_bed_scan: one sequential pass over BED text, no context.  Lines end at '\n' (a '\r' in front of it is dropped; the last line
+ * needs none); empty lines and lines beginning with '#', "track" or "browser" are skipped; fields are split on runs of tab or blank;
+ * the first three are the name, start and end, both decimal digits only and at most 4294967295; a line with start == end is valid
+ * and dropped.  Per kept interval: starts[], ends[], lines[] (its 1-based line); per RUN of consecutive kept lines with one name:
+ * run_name_off[], run_name_len[] (into the text), run_first[] (its first interval), run_count[].  Two calls: with the arrays NULL
+ * *n_intervals and *n_runs are the sizes; then they are the capacities (MSIM_ERR_ARG when too small) and become the sizes.
+ * MSIM_ERR_VALUE with "BED line N: fewer than three fields | start is no number | end is no number | end in front of start" for the
+ * first offending line (msim_last_error with a NULL context).                                                                      */
+#define MSIM_CMP_REGION_SETS 8
+#define MSIM_CMP_DIPLOID     2u
+int msim_cmp_regions_set(msim_ctx *ctx, int contig, int set, const uint32_t *starts, const uint32_t *ends, uint64_t n);
+int msim_cmp_regions_drop(msim_ctx *ctx, int contig, int set);
+int msim_cmp_regions_mark(msim_ctx *ctx, int contig, uint32_t flags);
+int msim_cmp_counts_regions(msim_ctx *ctx, int contig, uint32_t flags, uint32_t mask, uint64_t *counts, uint64_t outside[2]);
+int msim_cmp_fetch_regions(msim_ctx *ctx, int contig, uint32_t flags, uint8_t *truth_marks, uint8_t *calls_marks);
+int msim_cmp_regions_timing(msim_ctx *ctx, double *kernel_ms);
+int msim_dbg_cmp_counts_regions(const uint8_t *bases, uint64_t L, const msim_record *truth, uint64_t n_truth, const uint8_t *truth_pool,
+                                uint64_t truth_pool_len, const uint8_t *truth_flags, const msim_record *calls, uint64_t n_calls,
+                                const uint8_t *calls_pool, uint64_t calls_pool_len, const uint8_t *calls_flags, int outcomes,
+                                uint32_t flags, uint32_t n_sets, const uint32_t *starts, const uint32_t *ends, const uint64_t *set_off,
+                                uint32_t mask, uint64_t *counts, uint64_t outside[2], uint8_t *truth_marks, uint8_t *calls_marks);
+int msim_bed_scan(const uint8_t *text, uint64_t n_text, uint32_t *starts, uint32_t *ends, uint64_t *lines, uint64_t *n_intervals,
+                  uint64_t *run_name_off, uint32_t *run_name_len, uint64_t *run_first, uint64_t *run_count, uint64_t *n_runs);
+
 /* ---- test support: the SNP ti/tv transducer on the caller's words -------------------------------------------------- */
 /* Runs the three passes that turn CPython-stream words into SNP outcomes -- the map pass over whole blocks of
  * MSIM_SNP_BLOCK_WORDS words, the scan that finds where the K-th SNP's draws end, the outcome pass -- over `words` (raw,

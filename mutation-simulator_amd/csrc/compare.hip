@@ -18,6 +18,7 @@
 
 #include "cmp_blocks.h"
 #include "cmp_phase.h"
+#include "cmp_regions.h"
 #include "compare.h"
 #include "ctx.h"
 #include "lane_hist.h"
@@ -33,6 +34,9 @@ struct Held {                                  // msim_cmp_hold's copy of one co
     Scratch<uint8_t> d_flag_a, d_flag_b;                   // one byte per held / per current record (the last msim_cmp_counts)
     uint64_t n_flag_b = 0;
     bool counted = false;
+    int counted_outcomes = 0;                              // of that count: 2 (msim_cmp_counts), 3 (msim_cmp_counts_blocks)
+    uint32_t counted_flags = 0;                            // its flags
+    uint64_t counted_gen = 0;                              // the contig's table generation it saw
 };
 
 struct Dip {                                   // msim_cmp_join's result: one side's diploid table of one contig
@@ -69,6 +73,7 @@ struct CompareState {
     double blocks_ms = 0, scan_ms = 0, replay_ms = 0;
     uint64_t replay_steps = 0, replay_wave_steps = 0;      // msim_dbg_cmp_blocks_split
     PhaseState *phase = nullptr;               // compare --phased (cmp_phase.hip; made on first use)
+    RegionState *regions = nullptr;            // compare --regions / --stratify (cmp_regions.hip; made on first use)
 };
 
 namespace {
@@ -327,6 +332,9 @@ int counts_held(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32_t flag
     const Side b{{g.d_recs.p(), g.n_rec, g.pool_len ? g.d_pool.p() + PAD : nullptr, g.pool_len}, nullptr, h.d_flag_b.p()};
     const int rc = counts_device<2>(c, S, g, a, b, flags, counts, tallies);
     h.counted = !rc;
+    h.counted_outcomes = 2;
+    h.counted_flags = flags;
+    h.counted_gen = g.table_gen;
     return rc;
 }
 
@@ -370,6 +378,9 @@ int counts_held_blocks(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32
         MSIM_HIP(c, dev_alloc(h.d_flag_b, (size_t)g.n_rec));
     }
     h.n_flag_b = g.n_rec;
+    h.counted_outcomes = 3;
+    h.counted_flags = flags;
+    h.counted_gen = g.table_gen;
     const Side a{{h.d_recs.p(), h.n_rec, h.d_pool.p(), h.pool_len}, nullptr, h.d_flag_a.p()};
     const Side b{{g.d_recs.p(), g.n_rec, g.pool_len ? g.d_pool.p() + PAD : nullptr, g.pool_len}, nullptr, h.d_flag_b.p()};
     const uint64_t total = a.t.n + b.t.n;
@@ -543,6 +554,7 @@ void compare_drop_all(Ctx *c) {
     c->compare->held.clear();
     c->compare->dip.clear();
     phase_drop(c->compare->phase, -1);
+    regions_drop(c->compare->regions, -1);
 }
 
 bool compare_dip_view(Ctx *c, int contig, int side, DipView *v, bool *counted, uint32_t *counted_flags) {
@@ -560,6 +572,44 @@ bool compare_dip_view(Ctx *c, int contig, int side, DipView *v, bool *counted, u
     return true;
 }
 
+bool compare_region_tables(Ctx *c, int contig, bool diploid, RegionTables *v, const char **why) {
+    *v = RegionTables{};
+    if (diploid) {
+        DipPair *p = dip_of(c, contig);
+        if (!p) { *why = "contig has no diploid table of both sides (msim_cmp_join)"; return false; }
+        for (int s = 0; s < 2; s++) {
+            const Dip &d = p->side[s];
+            v->t[s] = cmp::Table{d.d_recs.p(), d.n, d.d_pool.p(), d.pool_len};
+            v->flag[s] = d.d_flag.p();
+        }
+        v->counted = p->counted;
+        v->outcomes = 3;
+        v->counted_flags = p->counted_flags;
+        return true;
+    }
+    Held *h = held_of(c, contig);
+    if (!h) { *why = "contig has no held table (msim_cmp_hold)"; return false; }
+    const Contig &g = c->contigs[(size_t)contig];
+    if (!g.planned) { *why = "contig has no current table: plan it first"; return false; }
+    v->t[MSIM_CMP_TRUTH] = cmp::Table{h->d_recs.p(), h->n_rec, h->d_pool.p(), h->pool_len};
+    v->t[MSIM_CMP_CALLS] = cmp::Table{g.d_recs.p(), g.n_rec, g.pool_len ? g.d_pool.p() + PAD : nullptr, g.pool_len};
+    v->flag[MSIM_CMP_TRUTH] = h->d_flag_a.p();
+    v->flag[MSIM_CMP_CALLS] = h->d_flag_b.p();
+    v->counted = h->counted && g.n_rec == h->n_flag_b && g.table_gen == h->counted_gen;   // (msim_cmp_fetch's test, and the generation)
+    v->outcomes = h->counted_outcomes;
+    v->counted_flags = h->counted_flags;
+    v->table_gen = g.table_gen;
+    return true;
+}
+
+int compare_region_slot(Ctx *c, RegionState ***slot) {
+    CompareState *S;
+    const int rc = state_of(c, &S);
+    if (rc) return rc;
+    *slot = &S->regions;
+    return MSIM_OK;
+}
+
 int compare_phase_slot(Ctx *c, PhaseState ***slot) {
     CompareState *S;
     const int rc = state_of(c, &S);
@@ -574,6 +624,8 @@ void compare_state_destroy(Ctx *c) {
     compare_drop_all(c);
     phase_state_destroy(S->phase);
     S->phase = nullptr;
+    regions_state_destroy(S->regions);
+    S->regions = nullptr;
     S->tm.destroy();
     S->tm_blk.destroy();
     S->tm_tally.destroy();
@@ -588,6 +640,7 @@ void compare_reset_timing(Ctx *c) {
     S.kernel_ms = S.join_ms = S.blocks_ms = S.scan_ms = S.replay_ms = 0;
     S.replay_steps = S.replay_wave_steps = 0;
     phase_reset_timing(S.phase);
+    regions_reset_timing(S.regions);
 }
 
 }  // namespace msim
@@ -608,6 +661,7 @@ int msim_cmp_hold(msim_ctx *p, int contig) {
     if ((rc = state_of(c, &S))) return rc;
     if (S->held.size() <= (size_t)contig) S->held.resize((size_t)contig + 1);
     Held &h = S->held[(size_t)contig] = Held{};
+    regions_unmark(S->regions, contig);
     if (g->n_rec) {
         MSIM_HIP(c, dev_alloc(h.d_recs, (size_t)g->n_rec * sizeof(msim_record)));
         MSIM_HIP(c, dev_alloc(h.d_flag_a, (size_t)g->n_rec));
@@ -633,6 +687,7 @@ int msim_cmp_release(msim_ctx *p, int contig) {
     if (Held *h = held_of(c, contig)) *h = Held{};
     if (contig >= 0 && (size_t)contig < c->compare->dip.size()) c->compare->dip[(size_t)contig] = DipPair{};
     phase_drop(c->compare->phase, contig);
+    regions_drop(c->compare->regions, contig);
     return MSIM_OK;
 }
 
@@ -734,6 +789,7 @@ int msim_cmp_join(msim_ctx *p, int contig, int side) {
     pair.counted = false;
     Dip &d = pair.side[side] = Dip{};
     phase_drop_side(S->phase, contig, side);
+    regions_unmark(S->regions, contig);
     TraceRange tr("msim compare join");
     rc = join_device(c, S, *g, *h, d);
     if (rc) { d = Dip{}; return rc; }

@@ -219,9 +219,20 @@ SYMBOLS = [
     ("msim_dbg_cmp_join", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, _VP, _U64P]),
     ("msim_dbg_cmp_counts_diploid", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, C.c_uint64, _VP,
                                               C.c_uint64, _VP, C.c_uint32, _VP, _VP, _VP, _VP]),
+    ("msim_cmp_regions_set", C.c_int, [_VP, C.c_int, C.c_int, _VP, _VP, C.c_uint64]),
+    ("msim_cmp_regions_drop", C.c_int, [_VP, C.c_int, C.c_int]),
+    ("msim_cmp_regions_mark", C.c_int, [_VP, C.c_int, C.c_uint32]),
+    ("msim_cmp_counts_regions", C.c_int, [_VP, C.c_int, C.c_uint32, C.c_uint32, _VP, _VP]),
+    ("msim_cmp_fetch_regions", C.c_int, [_VP, C.c_int, C.c_uint32, _VP, _VP]),
+    ("msim_cmp_regions_timing", C.c_int, [_VP, C.POINTER(C.c_double)]),
+    ("msim_dbg_cmp_counts_regions", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, C.c_uint64, _VP, C.c_uint64, _VP,
+                                              C.c_int, C.c_uint32, C.c_uint32, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP]),
+    ("msim_bed_scan", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, _U64P, _VP, _VP, _VP, _VP, _U64P]),
     ("msim_stats", C.c_int, [_VP, C.POINTER(Timing)]),
     ("msim_reset_stats", C.c_int, [_VP]),
 ]
+CMP_REGION_SETS = 8      # msim.h: MSIM_CMP_REGION_SETS, the region sets a contig keeps resident (a mark byte's bits)
+CMP_DIPLOID = 2          # msim.h: MSIM_CMP_DIPLOID, the region calls' flag for the two diploid tables
 CMP_EXACT = 1            # msim.h: MSIM_CMP_EXACT, the literal comparison
 CMP_BINS = 5             # msim.h: MSIM_CMP_BINS, the length bins of IN and DE (1, 2-5, 6-20, 21-50, 51 and above)
 CMP_PASS = 256           # msim.h: MSIM_CMP_PASS, the records one workgroup of the compare kernels takes per pass
@@ -840,6 +851,60 @@ class Engine:
         """The phase kernels' milliseconds on the device since ``reset_stats`` (HIP events)."""
         a = C.c_double()
         self._check(self.lib.msim_cmp_phase_timing(self.h, C.byref(a)))
+        return a.value
+
+    @staticmethod
+    def _region_flags(exact: bool, diploid: bool) -> int:
+        return (CMP_EXACT if exact else 0) | (CMP_DIPLOID if diploid else 0)
+
+    def cmp_regions_set(self, contig: int, set_index: int, starts, ends):
+        """Region set ``set_index`` (0 .. CMP_REGION_SETS - 1) of the contig: half-open 0-based intervals in normal form (sorted,
+        merged, inside the contig); an empty list is the empty set.  The contig's marks are forgotten."""
+        starts, ends = np.ascontiguousarray(starts, dtype=np.uint32), np.ascontiguousarray(ends, dtype=np.uint32)
+        if len(starts) != len(ends):
+            raise ValueError("cmp_regions_set: as many starts as ends")
+        self._check(self.lib.msim_cmp_regions_set(self.h, int(contig), int(set_index), _opt_ptr(starts), _opt_ptr(ends), len(starts)), contig)
+
+    def cmp_regions_drop(self, contig: int = -1, set_index: int = -1):
+        """Drops one region set (``set_index`` -1: all of the contig's; ``contig`` -1: every contig's) and the marks."""
+        self._check(self.lib.msim_cmp_regions_drop(self.h, int(contig), int(set_index)))
+
+    def cmp_regions_mark(self, contig: int, exact: bool = False, diploid: bool = False):
+        """A mark byte per record of the contig's held and current table (``diploid``: its two diploid tables): bit s set iff the
+        record's anchor -- an indel's leftmost placement, else its pos -- lies inside resident set s."""
+        self._check(self.lib.msim_cmp_regions_mark(self.h, int(contig), self._region_flags(exact, diploid)), contig)
+
+    def cmp_counts_regions(self, contig: int, mask: int, exact: bool = False, diploid: bool = False, width: int | None = None) -> tuple:
+        """Behind ``cmp_regions_mark`` and the count call whose flag bytes it tallies again, both with the same ``exact``: (that
+        call's counts over the records inside every set of ``mask`` only, uint64[2]: the truth's and the calls' records outside).
+        ``width``: the last axis of that call's counts, 4 (``cmp_counts``) or 6 (``cmp_counts_blocks``, ``cmp_counts_diploid``;
+        the default with ``diploid``) -- the rows beyond a haploid count's 4 stay zero."""
+        counts = np.zeros((8, CMP_BINS, 6), dtype=np.uint64)
+        outside = np.zeros(2, dtype=np.uint64)
+        self._check(self.lib.msim_cmp_counts_regions(self.h, int(contig), self._region_flags(exact, diploid), int(mask), _ptr(counts),
+                                                     _ptr(outside)), contig)
+        width = (6 if diploid else 4) if width is None else int(width)
+        if width == 4:                                     # (written as [8][CMP_BINS][4] into the front of the buffer)
+            counts = counts.reshape(-1)[:8 * CMP_BINS * 4].reshape(8, CMP_BINS, 4).copy()
+        return counts, outside
+
+    def cmp_fetch_regions(self, contig: int, exact: bool = False, diploid: bool = False) -> tuple:
+        """(the truth's mark bytes, the calls') of the last ``cmp_regions_mark`` of these tables: one per record."""
+        n = [C.c_uint64(), C.c_uint64()]
+        if diploid:
+            for side in (CMP_TRUTH, CMP_CALLS):
+                self._check(self.lib.msim_cmp_fetch_diploid(self.h, int(contig), side, C.byref(n[side]), None, None, None, None, None), contig)
+        else:
+            self._check(self.lib.msim_cmp_fetch(self.h, int(contig), C.byref(n[0]), None, None, None, None, None), contig)
+            n[1] = C.c_uint64(self.result_sizes(contig, applied=False)[1])
+        a, b = np.zeros(n[0].value, dtype=np.uint8), np.zeros(n[1].value, dtype=np.uint8)
+        self._check(self.lib.msim_cmp_fetch_regions(self.h, int(contig), self._region_flags(exact, diploid), _opt_ptr(a), _opt_ptr(b)), contig)
+        return a, b
+
+    def cmp_regions_timing(self) -> float:
+        """The region kernels' milliseconds on the device since ``reset_stats`` (HIP events)."""
+        a = C.c_double()
+        self._check(self.lib.msim_cmp_regions_timing(self.h, C.byref(a)))
         return a.value
 
     # test hooks (msim_dbg_*: exported, not part of include/msim.h)
@@ -1549,6 +1614,57 @@ def cmp_phase_host(bases, truth, truth_pool, truth_gt, truth_words, calls, calls
     if rc != OK:
         raise _host_error(rc)
     return out, state
+
+
+def cmp_counts_regions_host(bases, truth, truth_pool, truth_flags, calls, calls_pool, calls_flags, outcomes: int, sets, mask: int,
+                            exact: bool = False) -> tuple:
+    """``msim_dbg_cmp_counts_regions``: what ``Engine.cmp_counts_regions`` and ``Engine.cmp_fetch_regions`` return -- (counts,
+    outside, truth marks, calls marks) -- by sequential host loops.  The flag bytes are those of the count call with ``outcomes``
+    (2 or 3) outcomes; ``sets``: up to CMP_REGION_SETS pairs (starts, ends).  No context, no GPU."""
+    lib = load()
+    bases = _as_u8(bases)
+    truth, calls = (np.ascontiguousarray(t, dtype=RECORD_DTYPE) for t in (truth, calls))
+    truth_pool, calls_pool, truth_flags, calls_flags = (np.ascontiguousarray(p, dtype=np.uint8)
+                                                        for p in (truth_pool, calls_pool, truth_flags, calls_flags))
+    assert len(truth_flags) == len(truth) and len(calls_flags) == len(calls)
+    sets = [(np.ascontiguousarray(s, dtype=np.uint32), np.ascontiguousarray(e, dtype=np.uint32)) for s, e in sets]
+    assert all(len(s) == len(e) for s, e in sets)
+    starts = np.concatenate([s for s, _ in sets] + [np.zeros(0, dtype=np.uint32)])
+    ends = np.concatenate([e for _, e in sets] + [np.zeros(0, dtype=np.uint32)])
+    off = np.zeros(len(sets) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(s) for s, _ in sets], dtype=np.uint64)
+    counts = np.zeros((8, CMP_BINS, 2 * int(outcomes) if outcomes in (2, 3) else 6), dtype=np.uint64)
+    outside = np.zeros(2, dtype=np.uint64)
+    ma, mb = np.zeros(len(truth), dtype=np.uint8), np.zeros(len(calls), dtype=np.uint8)
+    rc = lib.msim_dbg_cmp_counts_regions(_opt_ptr(bases), len(bases), _opt_ptr(truth), len(truth), _opt_ptr(truth_pool), len(truth_pool),
+                                         _opt_ptr(truth_flags), _opt_ptr(calls), len(calls), _opt_ptr(calls_pool), len(calls_pool),
+                                         _opt_ptr(calls_flags), int(outcomes), CMP_EXACT if exact else 0, len(sets), _opt_ptr(starts),
+                                         _opt_ptr(ends), _ptr(off), int(mask), _ptr(counts), _ptr(outside), _opt_ptr(ma), _opt_ptr(mb))
+    if rc != OK:
+        raise _host_error(rc)
+    return counts, outside, ma, mb
+
+
+def bed_scan(text) -> tuple:
+    """``msim_bed_scan``: BED text (bytes or uint8) in one sequential pass -- (starts uint32, ends uint32, 1-based lines uint64 per
+    kept interval; per run of consecutive kept lines with one name: name offset uint64, name length uint32, first interval uint64,
+    count uint64).  MsimError with code ERR_VALUE and ``BED line N: reason`` for the first offending line."""
+    lib = load()
+    text = _as_u8(text)
+    n_iv, n_run = C.c_uint64(0), C.c_uint64(0)
+    rc = lib.msim_bed_scan(_opt_ptr(text), len(text), None, None, None, C.byref(n_iv), None, None, None, None, C.byref(n_run))
+    if rc != OK:
+        raise _host_error(rc)
+    starts, ends = np.zeros(n_iv.value, dtype=np.uint32), np.zeros(n_iv.value, dtype=np.uint32)
+    lines = np.zeros(n_iv.value, dtype=np.uint64)
+    name_off, name_len = np.zeros(n_run.value, dtype=np.uint64), np.zeros(n_run.value, dtype=np.uint32)
+    first, count = np.zeros(n_run.value, dtype=np.uint64), np.zeros(n_run.value, dtype=np.uint64)
+    if n_iv.value:
+        rc = lib.msim_bed_scan(_ptr(text), len(text), _ptr(starts), _ptr(ends), _ptr(lines), C.byref(n_iv), _ptr(name_off), _ptr(name_len),
+                               _ptr(first), _ptr(count), C.byref(n_run))
+        if rc != OK:
+            raise _host_error(rc)
+    return starts, ends, lines, name_off, name_len, first, count
 
 
 def vcf_phase_word(line: bytes, nf0: int, sample: int = 0) -> tuple:

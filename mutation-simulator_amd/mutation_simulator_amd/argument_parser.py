@@ -12,7 +12,11 @@ side and scores genotypes by dosage -- a ``GT`` column, ``GT`` lines in the reco
 ``--haplotype`` or ``--truth-haplotype``; ``--blocks [--block-gap N]`` rescues unmatched records whose block of neighbours writes
 the same bases on both sides -- ``BLK`` columns and lines; a usage error together with ``--diploid``, as is ``--block-gap`` without
 ``--blocks``; ``--diploid --phased`` also compares the phasing and writes ``<outbase>_ms.compare.phase.tsv`` (``outcompare_phase``),
-a usage error without ``--diploid`` or with ``--blocks``; ``compare_refusal`` words what it does not cover).
+a usage error without ``--diploid`` or with ``--blocks``; ``--regions FILE`` scores only the records whose anchor -- an indel's
+leftmost placement, else the position -- lies inside the BED's intervals, and the repeatable ``--stratify NAME=FILE`` adds a
+genome-wide table per BED, inside ``--regions`` where both are given; NAME is non-empty, without tab, blank, ``=`` or ``#``, and
+distinct; both are usage errors together with ``--phased``, whose phase table would silently stay genome-wide, and go with
+``--diploid``, ``--blocks``, ``--exact``, ``--per-contig`` and ``--list``; ``compare_refusal`` words what it does not cover).
 
 ``--ploidy 2 [--het F]`` (``args`` / ``rmt``) writes two haplotype Fastas, ``<outbase>_ms_h1<suffix>`` and ``<outbase>_ms_h2<suffix>``
 (``args.outfasta_h1`` / ``outfasta_h2``; ``<outbase>_ms<suffix>`` is not written), one phased ``<outbase>_ms.vcf`` and, with ``--chain``,
@@ -229,6 +233,13 @@ def build_parser() -> ArgumentParser:
     p_cmp.add_argument("--block-gap", type=int, default=None, metavar="N", dest="block_gap",
                        help="With --blocks: a record joins the block in front of it when it stands at most N bases behind it "
                             "(0 to 4096). Default = 50")
+    p_cmp.add_argument("--regions", type=Path, default=None, metavar="FILE",
+                       help="Score only the records inside the intervals of this BED file (text, .gz or .bgz), the truth set's "
+                            "confident regions: a record counts by its anchor, an indel's leftmost placement, so both records of a "
+                            "matched pair fall on the same side of every edge. Cannot be combined with --phased")
+    p_cmp.add_argument("--stratify", action="append", default=None, metavar="NAME=FILE",
+                       help="Also write a genome-wide table of the records inside this BED file (and inside --regions), headed "
+                            "'# stratum NAME'. May be given several times with distinct names. Cannot be combined with --phased")
     p_cmp.add_argument("--per-contig", action="store_true", default=False, dest="per_contig",
                        help="Repeat the table per contig behind the genome-wide one")
     p_cmp.add_argument("--list", action="store_true", default=False, dest="list_records",
@@ -350,6 +361,18 @@ def get_args(argv=None) -> Namespace:
             parser.error("--phased needs --diploid")
         if args.block_gap is not None and not 0 <= args.block_gap <= 4096:
             parser.error("--block-gap must lie in 0..4096")
+        if args.phased and (args.regions is not None or args.stratify):
+            parser.error("--regions and --stratify restrict the counts table only: the phase table of --phased would silently "
+                         "stay genome-wide, so they cannot be combined with it")
+        strata = []
+        for item in args.stratify or ():
+            name, sep, path = item.partition("=")
+            if not sep or not name or not path or any(ch in name for ch in "\t #"):
+                parser.error(f"--stratify takes NAME=FILE, NAME non-empty and without tab, blank, = or #: {item!r}")
+            if name in (n for n, _ in strata):
+                parser.error(f"--stratify names must be distinct: {name!r} is given twice")
+            strata.append((name, Path(path)))
+        args.stratify = strata
     if args.quiet:
         args.ignore_warnings = True
         args.no_progress = True

@@ -30,6 +30,18 @@ phase word off its line (``GT`` written with ``|``, ``PS``), behind each join ``
 diploid table, and behind each contig's counts ``msim_cmp_phase_counts`` takes the matched hets that are phased on both sides in
 position order (csrc/cmp_phase.hip): blocks, raw switch bits, switches and flips, Hamming distance.  ``*_ms.compare.phase.tsv``
 holds them, the comment lines of the table a ``phasing:`` line, the records file ``SW`` lines.
+
+``--regions FILE`` and ``--stratify NAME=FILE`` (repeatable) score inside BED intervals (``bed.py``; csrc/cmp_regions.hip).  A record
+is judged by its ANCHOR alone -- an insertion's or deletion's leftmost placement, the left end of the interval the match gives it;
+with ``--exact`` and for every other type its position --, so both records of a matched pair fall on the same side of every region
+edge and ``TP == TP.calls`` holds in every table.  Per contig, behind the count call, the sets go onto the contig (set 0: the
+confident regions; the strata on the free bits, seven a batch with ``--regions``, eight without), ``msim_cmp_regions_mark`` gives
+every record of both tables a mark byte once per batch, and ``msim_cmp_counts_regions`` tallies the count call's flag bytes again
+under a mask: the main table holds the records inside ``--regions`` only (``--per-contig`` as before), a ``regions:`` comment line
+says how many records lay outside and were not scored, ``--list`` lists inside records only, and behind the table comes one
+genome-wide block per stratum -- the records inside the stratum and inside ``--regions``.  Limits: only the anchor counts (a long
+deletion that reaches out of an interval is inside if its anchor is); strata are genome-wide, not per contig; not with
+``--phased``, whose phase table would silently stay genome-wide.
 """
 from __future__ import annotations
 
@@ -38,6 +50,7 @@ import contextlib
 import numpy as np
 
 from . import _ffi
+from .bed import BedError, Regions
 from .vcf_replay import VcfReplayError, load_vcf_text, plan_all, plan_loaded, resident_genome
 
 TYPE_NAMES = (None, "SN", "IN", "DE", "DU", "IV", "TL", "TLI")            # msim.h: MSIM_SN .. MSIM_TLI
@@ -197,6 +210,11 @@ class Compare:
         self.block_tallies = None    # uint64[contigs, 5] (--blocks)
         self.phase = None            # uint64[contigs, CMP_PHASE_COUNTS] (--phased)
         self.phase_marks = None      # uint64[2, 3] (--phased): per side the phased, unphased, unreadable-PS records
+        self.regions = None          # bed.Regions of --regions
+        self.outside = None          # uint64[contigs, 2] (--regions): the truth's and the calls' records outside, not scored
+        self.strata = []             # (name, bed.Regions) per --stratify, in command-line order
+        self.strata_counts = None    # uint64[strata, contigs, 8, CMP_BINS, 4 or 6]: the records inside the stratum (and --regions)
+        self.strata_outside = None   # uint64[strata, contigs, 2]
 
     def _plan(self, eng, side: str, path, names, cids, sample, haplotype):
         """One file's tables onto the contigs; (bytes of its text, load kernel ms, plan kernel ms)."""
@@ -229,12 +247,46 @@ class Compare:
         eng.vcf_release()
         return int(text.shape[0]), load_ms, plan_ms
 
+    def _load_beds(self, names, lengths):
+        """The BED files of ``--regions`` and ``--stratify`` on this genome; the seconds their scans took."""
+        args = self._args
+        try:
+            path = getattr(args, "regions", None)
+            self.regions = Regions(path, names, lengths) if path is not None else None
+            self.strata = [(name, Regions(p, names, lengths)) for name, p in (getattr(args, "stratify", None) or ())]
+        except BedError as e:
+            raise CompareError(str(e)) from None
+        return sum(r.scan_s for r in ([self.regions] if self.regions else []) + [r for _, r in self.strata])
+
+    def _score_regions(self, eng, i, cid, exact, diploid, width):
+        """Contig i behind its count call: the main counts restricted to ``--regions`` and every stratum's counts.  Returns the two
+        tables' mark bytes of the batch that holds set 0 (None without ``--regions``)."""
+        base = 1 if self.regions else 0                    # bit 0: the confident set; the strata take the free bits, batch by batch
+        room = _ffi.CMP_REGION_SETS - base
+        if self.regions:
+            eng.cmp_regions_set(cid, 0, *self.regions.sets[i])
+        marks = None
+        for first in range(0, max(len(self.strata), 1), room):
+            batch = self.strata[first:first + room]
+            for j, (_, r) in enumerate(batch):
+                eng.cmp_regions_set(cid, base + j, *r.sets[i])
+            for j in range(len(batch), room if first else 0):
+                eng.cmp_regions_drop(cid, base + j)        # (a set of the batch before: not searched again)
+            eng.cmp_regions_mark(cid, exact, diploid)
+            if self.regions and first == 0:
+                self.counts[i], self.outside[i] = eng.cmp_counts_regions(cid, 1, exact, diploid, width)
+                marks = eng.cmp_fetch_regions(cid, exact, diploid)
+            for j in range(len(batch)):
+                self.strata_counts[first + j, i], self.strata_outside[first + j, i] = eng.cmp_counts_regions(
+                    cid, (1 << (base + j)) | base, exact, diploid, width)
+        return marks
+
     def run(self):
         fa, args = self._fasta, self._args
         if self._engine is None:
             self._engine = _ffi.Engine(self._device)
         eng = self._engine
-        _, names, cids = resident_genome(eng, fa, "compare")
+        recs, names, cids = resident_genome(eng, fa, "compare")
         diploid, listing = bool(getattr(args, "diploid", False)), bool(getattr(args, "list_records", False))
         blocks = bool(getattr(args, "blocks", False))
         phased = bool(getattr(args, "phased", False))
@@ -244,6 +296,10 @@ class Compare:
             raise CompareError("--blocks compares one haplotype against one: it cannot be combined with --diploid")
         if phased and not diploid:
             raise CompareError("--phased needs --diploid")
+        restricted = getattr(args, "regions", None) is not None or bool(getattr(args, "stratify", None))
+        if restricted and phased:
+            raise CompareError("--regions and --stratify restrict the counts table only: they cannot be combined with --phased")
+        bed_scan_s = self._load_beds(names, [len(r) for r in recs]) if restricted else 0.0
         self.phase_marks = np.zeros((2, 3), dtype=np.uint64)
         truth_sample, sample = getattr(args, "truth_sample", None), getattr(args, "sample", None)
         if diploid:
@@ -261,11 +317,15 @@ class Compare:
         cmp0 = eng.cmp_timing()                        # (a caller's engine may have compared before)
         blk0 = eng.cmp_blocks_timing() if blocks else 0.0
         phase0 = eng.cmp_phase_timing() if phased else 0.0
+        region0 = eng.cmp_regions_timing() if restricted else 0.0
         n = len(cids)
         self.counts = np.zeros((n, 8, _ffi.CMP_BINS, 6 if diploid or blocks else 4), dtype=np.uint64)
         self.tallies = np.zeros((n, 2), dtype=np.uint64)
         self.block_tallies = np.zeros((n, 5), dtype=np.uint64)
         self.phase = np.zeros((n, _ffi.CMP_PHASE_COUNTS), dtype=np.uint64)
+        self.outside = np.zeros((n, 2), dtype=np.uint64)
+        self.strata_counts = np.zeros((len(self.strata), n) + self.counts.shape[1:], dtype=np.uint64)
+        self.strata_outside = np.zeros((len(self.strata), n, 2), dtype=np.uint64)
         listed = []
         for i, cid in enumerate(cids):
             if blocks:
@@ -274,15 +334,19 @@ class Compare:
                 self.counts[i], self.tallies[i] = eng.cmp_counts_diploid(cid, exact) if diploid else eng.cmp_counts(cid, exact)
             if phased:
                 self.phase[i] = eng.cmp_phase_counts(cid, exact)
+            marks = self._score_regions(eng, i, cid, exact, diploid, self.counts.shape[-1]) if restricted else None
+            ia, ib = (slice(None), slice(None)) if marks is None else ((marks[0] & 1) != 0, (marks[1] & 1) != 0)   # --list: inside only
             if listing and diploid:
                 a, _, ga, fa_flags = eng.cmp_fetch_diploid(cid, _ffi.CMP_TRUTH)
                 b, _, gb, fb_flags = eng.cmp_fetch_diploid(cid, _ffi.CMP_CALLS)
+                a, ga, fa_flags, b, gb, fb_flags = a[ia], ga[ia], fa_flags[ia], b[ib], gb[ib], fb_flags[ib]
                 listed += record_rows_diploid(names[i], a, ga, fa_flags, b, gb, fb_flags)
                 if phased:
                     listed += switch_rows(names[i], a, ga, eng.cmp_fetch_phase(cid, _ffi.CMP_TRUTH)[1])
             elif listing:
                 held, _, fa_flags, fb_flags = eng.cmp_fetch(cid)
                 current = eng.fetch_records(cid)[0]
+                held, fa_flags, current, fb_flags = held[ia], fa_flags[ia], current[ib], fb_flags[ib]
                 listed += record_rows("FN", names[i], held, fa_flags)
                 listed += record_rows("FP", names[i], current, fb_flags)
                 if blocks:
@@ -298,6 +362,9 @@ class Compare:
             eng.vcf_release()                          # (a diploid side released its text behind its joins)
         if phased:
             self.stats["cmp_phase_kernel_ms"] = round(eng.cmp_phase_timing() - phase0, 4)
+        if restricted:
+            self.stats["cmp_region_kernel_ms"] = round(eng.cmp_regions_timing() - region0, 4)
+            self.stats["bed_scan_s"] = round(bed_scan_s, 6)
         eng.cmp_release()
         args.outcompare.write_text(self.render(names))
         if phased:
@@ -332,7 +399,17 @@ class Compare:
             t = [int(x) for x in self.block_tallies.sum(axis=0, dtype=np.uint64)]
             notes.append(f"blocks: gap {_ffi.CMP_BLOCK_GAP if gap is None else int(gap)}; {t[0]} candidates, {t[1]} replayed, {t[2]} equal, "
                          f"{t[3]} over a limit ({_ffi.CMP_BLOCK_RECORDS} records, {_ffi.CMP_BLOCK_SPAN} bases), {t[4]} holding a translocation")
-        return render(notes, self.counts, names if getattr(args, "per_contig", False) else None, blocks)
+        if self.regions:
+            r, out = self.regions, [int(x) for x in self.outside.sum(axis=0, dtype=np.uint64)]
+            notes.append(f"regions: {r.path.name}: {r.n_intervals} intervals, {r.bases} bases ({r.foreign_lines} lines on names the genome "
+                         f"does not have); outside and not scored: {out[0]} truth records, {out[1]} calls records")
+        text = render(notes, self.counts, names if getattr(args, "per_contig", False) else None, blocks)
+        lines = []
+        for k, (name, r) in enumerate(self.strata):        # genome-wide only: no per-contig blocks per stratum
+            out = [int(x) for x in self.strata_outside[k].sum(axis=0, dtype=np.uint64)]
+            lines.append(f"# stratum {name}: {r.path.name}: {r.n_intervals} intervals, {r.bases} bases; outside: {out[0]} truth, {out[1]} calls")
+            lines += render_block(self.strata_counts[k].sum(axis=0, dtype=np.uint64), blocks)
+        return text + "".join(line + "\n" for line in lines)
 
     def render_phase(self, names) -> str:
         """The text of ``*_ms.compare.phase.tsv``."""

@@ -34,7 +34,15 @@ contig, the calls' sets of 4096 records (msim_cmp_phase_set).  Every record then
 genome, medians of `runs` with min and max, all from this process:
   cmp_phase_kernel_ms           msim_cmp_phase_counts (msim_cmp_phase_timing: its six kernels)
   phased_cmp_diploid_kernel_ms  k_cmp_match<3> + k_cmp_tally<3> on the same tables (msim_cmp_counts_diploid, which the pass follows)
-  phase_copy_floor_ms           a device-to-device copy of the bytes the phase pass reads and writes (msim_dbg_cmp_phase_copy_floor)"""
+  phase_copy_floor_ms           a device-to-device copy of the bytes the phase pass reads and writes (msim_dbg_cmp_phase_copy_floor)
+
+With --regions (anywhere on the line) the same two tables are marked and tallied again inside region sets, behind the plain runs and in
+the same process: `dense` sets of 1000 bases in every 2000 (about 1.5 M intervals a set over the genome) and `sparse` sets of 100 in
+every 100 000, one resident set and eight different ones (set s shifted by s / 8 of the period).  Per configuration
+regions_<dense|sparse>_<1|8>_*, medians of `runs` with min and max:
+  mark_ms             k_region_mark over the 24 contigs, both tables (msim_cmp_regions_timing around msim_cmp_regions_mark)
+  tally_ms            one k_region_tally<2> pass over them, mask = set 0 (msim_cmp_counts_regions)
+  mark_over_match     mark_ms over cmp_kernel_ms of the plain comparison; mark_over_floor: over copy_floor_ms"""
 import ctypes as C
 import json
 import statistics
@@ -134,6 +142,9 @@ def main():
         sys.argv.remove("--phased")
     if phased and not diploid:
         sys.exit("--phased measures the pass behind the diploid comparison: run it with --diploid")
+    regions = "--regions" in sys.argv
+    if regions:
+        sys.argv.remove("--regions")
     runs = max(7, int(sys.argv[1])) if len(sys.argv) > 1 else 7
     total = int(float(sys.argv[2])) if len(sys.argv) > 2 else 3_000_000_000
     out_path = Path(sys.argv[3]) if len(sys.argv) > 3 else None
@@ -232,6 +243,46 @@ def main():
                 res[prefix + name] = statistics.median(g[col] for g in got)
                 res[prefix + name + "_min_max"] = [min(g[col] for g in got), max(g[col] for g in got)]
 
+        def region_sets(L, period, width, n_sets):
+            """n_sets different sets of a contig: `width` bases in every `period`, set s shifted by s * period / 8."""
+            out = []
+            for s in range(n_sets):
+                starts = np.arange(s * (period // 8), L - width, period, dtype=np.int64)
+                out.append((starts.astype(np.uint32), (starts + width).astype(np.uint32)))
+            return out
+
+        def regions_pass(mask):
+            """(k_region_mark ms over the contigs, one k_region_tally<2> pass ms over them, records inside a side, outside a side)"""
+            eng.reset_stats()
+            for cid in cids:
+                eng.cmp_regions_mark(cid)
+            mark_ms = eng.cmp_regions_timing()
+            got = [eng.cmp_counts_regions(cid, mask) for cid in cids]
+            tally_ms = eng.cmp_regions_timing() - mark_ms
+            counts, outside = sum(g[0] for g in got), sum(g[1] for g in got)
+            assert int(counts[..., :2].sum()) + int(outside[0]) == records[0] and int(counts[..., 2:].sum()) + int(outside[1]) == records[1]
+            assert (counts[..., 0] == counts[..., 2]).all()
+            return mark_ms, tally_ms, [int(counts[..., :2].sum()), int(counts[..., 2:].sum())], [int(x) for x in outside]
+
+        if regions:                                    # (behind the plain runs: their flag bytes are the ones tallied again)
+            for tag, period, width in (("dense", 2000, 1000), ("sparse", 100_000, 100)):
+                for n_sets in (1, 8):
+                    eng.cmp_regions_drop()
+                    n_iv = 0
+                    for cid, L in zip(cids, lengths):
+                        for s, (starts, ends) in enumerate(region_sets(L, period, width, n_sets)):
+                            eng.cmp_regions_set(cid, s, starts, ends)
+                            n_iv += len(starts) if s == 0 else 0
+                    name = f"regions_{tag}_{n_sets}"
+                    _, _, inside, outside = regions_pass(1)        # warm-up: code objects, the mark bytes' allocation
+                    res[name + "_intervals_a_set"], res[name + "_inside"], res[name + "_outside"] = n_iv, inside, outside
+                    got = [regions_pass(1)[:2] for _ in range(runs)]
+                    for what, col in (("mark_ms", 0), ("tally_ms", 1)):
+                        res[f"{name}_{what}"] = statistics.median(g[col] for g in got)
+                        res[f"{name}_{what}_min_max"] = [min(g[col] for g in got), max(g[col] for g in got)]
+                    res[name + "_mark_over_match"] = res[name + "_mark_ms"] / statistics.median(rows)
+                    res[name + "_mark_over_floor"] = res[name + "_mark_ms"] / statistics.median(floors)
+            eng.cmp_regions_drop()
         if blocks:                                     # (in front of the joins: they consume the held tables)
             blocks_runs("")
             for cid in cids:
