@@ -945,6 +945,40 @@ int msim_dbg_sample_tail(msim_ctx *ctx, const uint32_t *words, uint64_t n_words,
                          uint32_t shift, uint32_t n, uint32_t k, uint32_t *bitmap, uint32_t bm_guard, msim_dbg_tail_state *state,
                          int anchored, uint64_t win_pos, uint32_t need0, uint32_t d1, uint64_t pos_limit);
 
+/* ---- test support: an anchored contig's whole stream chain on the caller's tables -------------------------------- */
+/* The chain of a contig whose sample is an anchored window with one drawing range -- the fringe pass (the accepted draws of
+ * [start, H) and the first need0 of the tail list go into the bitmap, duplicates counted), the tail rounds, the stream cut, the
+ * scan and cut of the K2 SNPs' draws from there -- over tables the caller made, in buffers of the call's own: synchronous, no
+ * contig, no stream session.  fused = 1: the ONE launch the sampler sends (NOTES section 34); 0: the three
+ * stand-alone launches (MSIM_NO_CHAIN_FUSE=1).  Both must leave the same bytes wherever no overflow flag is raised, and the
+ * same flag where one is.
+ *   words:  raw (untempered) CPython-stream words, fewer than 2^28; the head interval is words[lo, lo + F), H = lo + F, the
+ *           sample's window words[H, H + W); the SNP stage's lanes and maps are made by the map pass over the whole blocks of
+ *           MSIM_SNP_BLOCK_WORDS words, and W2 / MSIM_SNP_BLOCK_WORDS + 2 of them must follow the block of word H + W
+ *   hcnt:   accepted draws per block of 2048 words of the head interval (ceil(F / 2048) <= 1024 entries; checked against words)
+ *   hacc:   those draws in order, block b's from index 2048 b on (n_hacc >= 2048 ceil(F / 2048))
+ *   tail:   the window's accepted draws in order from accepted index k_core on (all < n); n_tail covers K - k_core + core_dups
+ *           entries and everything up to the window's last accepted draw
+ *   cnt:    accepted draws per block of 2048 window words (ceil(W / 2048) <= 8192 entries)
+ *   bitmap: bm_guard guard words, ceil(n / 32) words, bm_guard guard words -- in and out, guards included
+ *   win_maps: out, (W2 / MSIM_SNP_BLOCK_WORDS + 4) * 4 uint32: per SNP window block count and state at its start, the totals
+ *           entry, one guard entry; what no launch writes stays 0xee
+ *   io:     in: the layout (G = workgroups of the fringe grid, 1..256; core_dups / core_flags / head_flags: what the prep left
+ *           behind); in and out: state (rsv = the largest margin used, permille); out: hdr = need0, d1, the ticket word
+ *           (fused: G), 0; base = the saved start of the SNP draws                                                          */
+typedef struct msim_dbg_chain {
+    uint64_t lo, expect, pos_limit, snp_limit, ti_lim;
+    uint32_t F, K, k_core, shift, n, W, W2, K2, soft_half, G, core_dups, core_flags, head_flags, bm_guard, fused, rsv;
+    msim_dbg_tail_state state;
+    uint32_t hdr[4];
+    uint64_t base;
+} msim_dbg_chain;
+int msim_dbg_chain_step(msim_ctx *ctx, const uint32_t *words, uint64_t n_words, const uint32_t *hcnt, const uint32_t *hacc,
+                        uint64_t n_hacc, const uint32_t *tail, uint64_t n_tail, const uint32_t *cnt, uint32_t *bitmap,
+                        uint32_t *win_maps, msim_dbg_chain *io);
+/* Fused chain launches the context's SNP sampler has sent since it was created (0 with MSIM_NO_CHAIN_FUSE=1). */
+int msim_dbg_chains_fused(msim_ctx *ctx, uint64_t *n);
+
 /* ---- stats -------------------------------------------------------------------------------------- */
 int msim_stats(msim_ctx *ctx, msim_timing *out);
 int msim_reset_stats(msim_ctx *ctx);

@@ -1531,6 +1531,25 @@ int msim_dbg_sample_tail(msim_ctx *p, const uint32_t *words, uint64_t n_words, c
                                state, anchored, win_pos, need0, d1, pos_limit);
 }
 
+// An anchored contig's whole chain (plan_kernels.h: k_chain_fused, or k_ahead_fringe / k_sample_tail / k_snp_scan_cut_abs) over
+// tables the caller made (include/msim.h).  Synchronous; touches no contig and no stream session.
+int msim_dbg_chain_step(msim_ctx *p, const uint32_t *words, uint64_t n_words, const uint32_t *hcnt, const uint32_t *hacc, uint64_t n_hacc,
+                        const uint32_t *tail, uint64_t n_tail, const uint32_t *cnt, uint32_t *bitmap, uint32_t *win_maps,
+                        msim_dbg_chain *io) {
+    CTX_FLUSHED(c, p)
+    if (!c) return MSIM_ERR_ARG;
+    NEED_GPU(c);
+    int rc = drain(c);
+    if (rc) return rc;
+    return gpu_dbg_chain_step(c, words, n_words, hcnt, hacc, n_hacc, tail, n_tail, cnt, bitmap, win_maps, io);
+}
+int msim_dbg_chains_fused(msim_ctx *p, uint64_t *n) {
+    Ctx *c = reinterpret_cast<Ctx *>(p);
+    if (!c || !n) return MSIM_ERR_ARG;
+    *n = gpu_plan_chains_fused(c->gpu);
+    return MSIM_OK;
+}
+
 // The device halves of the SV-mix and host-chain engines over tables the caller made (plan_gpu.hip: gpu_dbg_*): the engines' own
 // launch helpers in buffers of the call's own.  Synchronous; no contig, no stream session.  Each refuses with MSIM_ERR_ARG,
 // before anything is launched, whatever the planners cannot produce.

@@ -51,6 +51,12 @@ int gpu_dbg_sample_tail(Ctx *c, const uint32_t *words, uint64_t n_words, const u
                         const uint32_t *blocks, uint32_t n_blocks, uint32_t raw_counts, uint32_t W, uint32_t shift, uint32_t n,
                         uint32_t k, uint32_t *bitmap, uint32_t bm_guard, msim_dbg_tail_state *state, int anchored, uint64_t win_pos,
                         uint32_t need0, uint32_t d1, uint64_t pos_limit);
+// test support (msim_dbg_chain_step): one anchored contig's chain -- fringe, tail, both cuts -- over the caller's tables, as the one
+// fused launch or as the three stand-alone ones; msim_dbg_chains_fused: fused launches the context's sampler has sent
+int gpu_dbg_chain_step(Ctx *c, const uint32_t *words, uint64_t n_words, const uint32_t *hcnt, const uint32_t *hacc, uint64_t n_hacc,
+                       const uint32_t *tail, uint64_t n_tail, const uint32_t *cnt, uint32_t *bitmap, uint32_t *win_maps,
+                       msim_dbg_chain *io);
+uint64_t gpu_plan_chains_fused(const GpuPlan *g);
 // test support (msim_dbg_candidates / msim_dbg_accept_tables / msim_dbg_mixed_emit): the device halves of the SV-mix and host-chain
 // engines -- the engines' own launch helpers -- over tables the caller made (plan_gpu.hip);
 // rt: MixRangeDev[n_draw], sets: TypeTable[n_sets] (plan_kernels.h)

@@ -259,6 +259,11 @@ struct GpuPlan {
     bool pass_hoist = true;                    //   MSIM_NO_PASS_HOIST: msim_plan_pass issues every prep at its contig's turn
     int pass_streams = 0;                      //   MSIM_PASS_STREAMS: a segment's prep launches rotate over the first so many prep streams (0: all)
     bool pass_gate = false;                    //   MSIM_PASS_GATE: a segment's prep starts behind the SNP maps of the words it reads
+    // An anchored contig with one drawing range: fringe, tail and SNP cut go out as ONE launch (k_chain_fused).  ahead_chain fills
+    // in the sample's share and holds it; enqueue_snp_stage adds its own and launches.  MSIM_NO_CHAIN_FUSE: the three launches.
+    bool chain_fuse = true;
+    uint64_t chains_fused = 0;                 //   ... such launches since the context was created (msim_dbg_chains_fused)
+    struct { bool on = false; ChainJob J; uint32_t G = 0; SampleSet *S = nullptr; bool grouped = false; } held;
 };
 
 GpuPlan *gpu_plan_create() {
@@ -279,6 +284,7 @@ GpuPlan *gpu_plan_create() {
     if (getenv("MSIM_NO_PASS_HOIST")) g->pass_hoist = false;
     if (const char *e = getenv("MSIM_PASS_GATE")) g->pass_gate = atoi(e) != 0;
     if (const char *e = getenv("MSIM_PASS_STREAMS")) g->pass_streams = std::min(8, std::max(0, atoi(e)));
+    if (const char *e = getenv("MSIM_NO_CHAIN_FUSE")) g->chain_fuse = atoi(e) == 0;
     return g;
 }
 
@@ -1183,8 +1189,9 @@ static int prep_launch(Ctx *c, GpuPlan *g, PrepJobs &J, hipEvent_t done) {
 
 // ---- on the chain: fringe (exact start), tail rounds, cut.  wait_for: the event behind the sample's off-chain part (nullptr:
 // the plan stream has waited for it already -- an earlier sample of the same batch).
+// fuse: nothing is launched here -- the launch is held (g->held) until enqueue_snp_stage knows the SNP stage's share of it.
 static int ahead_chain(Ctx *c, GpuPlan *g, SampleSet &S, const msim_range &r, const AheadGeom &a, const SampleStep &st, hipEvent_t wait_for,
-                       bool grouped, SampleLaunch &out) {
+                       bool grouped, bool fuse, SampleLaunch &out) {
     int rc;
     // (the plan stream waits for the words here, as a sample on the chain would; a set laid out ahead of its turn had them
     //  generated then, on the side streams alone)
@@ -1196,13 +1203,24 @@ static int ahead_chain(Ctx *c, GpuPlan *g, SampleSet &S, const msim_range &r, co
     const double dups_est = (double)a.K * (double)a.K / (2.0 * (double)a.n);
     const uint32_t items_est = a.a_max + (uint32_t)(dups_est + 16.0 * std::sqrt(dups_est) + 64.0);
     const uint32_t G = std::max(1u, std::min(256u, (items_est + ACC_THREADS * FRINGE_ITEMS - 1) / (ACC_THREADS * FRINGE_ITEMS)));
-    hipLaunchKernelGGL(k_ahead_fringe, dim3(G), dim3(ACC_THREADS), 0, c->stream, raw, g->d_ps, ps_core, ps_head, hdr,
-                       (unsigned long long)st.lo, a.F, S.hcnt.p(), a.nbh, S.hacc.p(), S.acc.p(), a.K, a.k_core, a.shift, a.n, S.bitmap.p(),
-                       (unsigned long long)st.expect, st.soft_half);
-    hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(TAIL_THREADS), 0, c->stream, raw, S.acc.p(), a.k_core, S.cnt.p(), a.nb, a.W, a.shift, a.n,
-                       a.k_core, S.bitmap.p(), g->d_ps, 1u, ps_core, hdr, (unsigned long long)st.e_lim);
-    MSIM_HIP(c, hipGetLastError());
-    if (!grouped) MSIM_HIP(c, hipEventRecord(S.chain_done, c->stream));
+    if (fuse) {
+        ChainJob &J = g->held.J;
+        J = ChainJob{};
+        J.ps = g->d_ps; J.ps_core = ps_core; J.ps_head = ps_head; J.hdr = hdr;      // (raw: the launch takes the array as it is then)
+        J.hcnt = S.hcnt.p(); J.hacc = S.hacc.p(); J.acc = S.acc.p(); J.bitmap = S.bitmap.p();
+        J.lo = st.lo; J.expect = st.expect;
+        J.F = a.F; J.nbh = a.nbh; J.K = a.K; J.k_core = a.k_core; J.shift = a.shift; J.n = a.n; J.soft_half = st.soft_half;
+        J.cnt = S.cnt.p(); J.nb = a.nb; J.W = a.W; J.pos_limit = st.e_lim;
+        g->held.G = G; g->held.S = &S; g->held.grouped = grouped; g->held.on = true;
+    } else {
+        hipLaunchKernelGGL(k_ahead_fringe, dim3(G), dim3(ACC_THREADS), 0, c->stream, raw, g->d_ps, ps_core, ps_head, hdr,
+                           (unsigned long long)st.lo, a.F, S.hcnt.p(), a.nbh, S.hacc.p(), S.acc.p(), a.K, a.k_core, a.shift, a.n, S.bitmap.p(),
+                           (unsigned long long)st.expect, st.soft_half);
+        hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(TAIL_THREADS), 0, c->stream, raw, S.acc.p(), a.k_core, S.cnt.p(), a.nb, a.W, a.shift, a.n,
+                           a.k_core, S.bitmap.p(), g->d_ps, 1u, ps_core, hdr, (unsigned long long)st.e_lim);
+        MSIM_HIP(c, hipGetLastError());
+        if (!grouped) MSIM_HIP(c, hipEventRecord(S.chain_done, c->stream));
+    }
     out.S = &S; out.W = a.W; out.bmw = a.bmw; out.bnb = a.bnb;
     c->t.snp_samples_ahead++;
     static const bool log_ahead = getenv("MSIM_DBG_AHEAD_LOG") != nullptr;
@@ -1214,7 +1232,7 @@ static int ahead_chain(Ctx *c, GpuPlan *g, SampleSet &S, const msim_range &r, co
 // An anchored window at its contig's own turn: set, off-chain launches and chain in one go -- or, where msim_plan_pass sent the
 // off-chain part ahead (g->hoisted), the chain alone.
 static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t d, const SampleStep &st, Grow &grow, SampleLaunch &out,
-                                bool grouped) {
+                                bool grouped, bool fuse) {
     int rc;
     const AheadGeom a = ahead_geometry(r, d, st.lo, st.H, st.W);
     if (!g->hoisted.empty()) {
@@ -1223,7 +1241,7 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
         if (h.start != r.start || h.k != r.k || h.st.lo != st.lo || h.st.H != st.H || h.st.W != st.W || h.st.e_lim != st.e_lim ||
             h.st.expect != st.expect || h.st.soft_half != st.soft_half)
             return fail(c, MSIM_ERR_HIP, "GPU sampler: a sample laid out ahead of its pass does not match its contig's turn (results discarded)");
-        return ahead_chain(c, g, *h.S, r, a, st, h.wait_it ? h.batch_done : (hipEvent_t) nullptr, grouped, out);
+        return ahead_chain(c, g, *h.S, r, a, st, h.wait_it ? h.batch_done : (hipEvent_t) nullptr, grouped, fuse, out);
     }
     if ((rc = next_prep_stream(c, g))) return rc;
     SampleSet *S = nullptr;
@@ -1234,7 +1252,7 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
     J.n = 1;
     J.j[0] = prep_job(*S, a, st.lo, st.H);
     if ((rc = prep_launch(c, g, J, S->prep_done))) return rc;
-    return ahead_chain(c, g, *S, r, a, st, S->prep_done, grouped, out);
+    return ahead_chain(c, g, *S, r, a, st, S->prep_done, grouped, fuse, out);
 }
 
 // SNP draws of a contig's K (kept) SNPs in position order, starting at the device position (ps->snp_base): the chain
@@ -1244,7 +1262,10 @@ static int enqueue_sample_ahead(Ctx *c, GpuPlan *g, const msim_range &r, int64_t
 // caller launches the bitmap expansion behind this stage and hands it that array (*aux8_out).
 // defer (with aux8_out): the emit pass is not launched here at all -- the caller queues it for the contig's emission group.
 static int enqueue_snp_stage(Ctx *c, GpuPlan *g, Contig &ct, uint64_t K, const uint32_t *sn_index, uint64_t &pos_hi, Grow &grow,
-                             uint8_t **aux8_out = nullptr, SnpDefer *defer = nullptr, uint64_t e_limit = ~0ull) {
+                             uint8_t **aux8_out = nullptr, SnpDefer *defer = nullptr, uint64_t e_limit = ~0ull, bool take_held = false) {
+    // take_held: the caller's sample left its launch in g->held (ahead_chain): this stage completes it and sends it
+    const bool fused = take_held && g->held.on;
+    g->held.on = false;
     const msim_params &P = c->params;
     GpuStream &py = g->s[0];
     int rc;
@@ -1271,10 +1292,21 @@ static int enqueue_snp_stage(Ctx *c, GpuPlan *g, Contig &ct, uint64_t K, const u
                                (uint32_t)(MT_N + (uint64_t)py.n_chunks * MT_CHUNK_WORDS), (unsigned long long)P.ti_lim, 0u, py.d_maps, py.d_lanes);
         py.maps_ti_lim = P.ti_lim;
     }
-    hipLaunchKernelGGL(k_snp_scan_cut_abs, dim3(1), dim3(SNP_THREADS), 0, c->stream, py.d_lanes, g->d_ps, W2,
-                       py.d_maps, T.maps.p(), nb2, (uint32_t)K, T.base,
-                       (unsigned long long)(e_limit == ~0ull ? ~0ull : std::min<uint64_t>(pos_hi + W2, e_limit)));
-    MSIM_HIP(c, hipGetLastError());
+    const unsigned long long snp_limit = e_limit == ~0ull ? ~0ull : std::min<uint64_t>(pos_hi + W2, e_limit);
+    if (fused) {                                           // the sample's fringe and tail and this stage's cut: one launch
+        ChainJob &J = g->held.J;
+        J.raw = py.d_raw;
+        J.lanes = py.d_lanes; J.abs_maps = py.d_maps; J.win_maps = T.maps.p(); J.base_out = T.base;
+        J.snp_limit = snp_limit; J.W2 = W2; J.nb2 = nb2; J.K2 = (uint32_t)K;
+        hipLaunchKernelGGL(k_chain_fused, dim3(g->held.G), dim3(ACC_THREADS), 0, c->stream, J);
+        MSIM_HIP(c, hipGetLastError());
+        if (!g->held.grouped) MSIM_HIP(c, hipEventRecord(g->held.S->chain_done, c->stream));
+        g->chains_fused++;
+    } else {
+        hipLaunchKernelGGL(k_snp_scan_cut_abs, dim3(1), dim3(SNP_THREADS), 0, c->stream, py.d_lanes, g->d_ps, W2,
+                           py.d_maps, T.maps.p(), nb2, (uint32_t)K, T.base, snp_limit);
+        MSIM_HIP(c, hipGetLastError());
+    }
     if (defer) { defer->T = &T; defer->W2 = W2; defer->nb2 = nb2; }
     if (!c->chain_only && !defer) {                       // (chain only: where the draws END is all that is wanted)
         hipEvent_t ce = next_chain_event(g);
@@ -1540,6 +1572,110 @@ int gpu_dbg_sample_tail(Ctx *c, const uint32_t *words, uint64_t n_words, const u
     return MSIM_OK;
 }
 
+// test support (msim_dbg_chain_step): the chain of one anchored contig -- fringe, tail rounds, stream cut, SNP scan and cut -- over
+// tables the caller made, as the ONE launch (k_chain_fused) or as the three stand-alone launches, in buffers of its own,
+// synchronous.  The lanes and maps of the SNP stage come from the map pass over the whole blocks of `words`.  Everything the
+// kernels can index with is checked first (include/msim.h lists what a caller hands in).
+int gpu_dbg_chain_step(Ctx *c, const uint32_t *words, uint64_t n_words, const uint32_t *hcnt, const uint32_t *hacc, uint64_t n_hacc,
+                       const uint32_t *tail, uint64_t n_tail, const uint32_t *cnt, uint32_t *bitmap, uint32_t *win_maps,
+                       msim_dbg_chain *io) {
+    if (!words || !hcnt || !hacc || !tail || !cnt || !bitmap || !win_maps || !io)
+        return fail(c, MSIM_ERR_ARG, "msim_dbg_chain_step: bad argument");
+    msim_dbg_chain &d = *io;
+    const uint64_t n_blocks2 = n_words / SNP_BLOCK2;
+    const uint32_t nb = (d.W + ACC_BLOCK - 1) / ACC_BLOCK, nbh = (d.F + ACC_BLOCK - 1) / ACC_BLOCK;
+    const uint64_t H = d.lo + d.F;
+    if (!n_blocks2 || n_words >= (1ull << 28) || !d.W || !d.n || d.shift >= 32 || !d.G || d.G > 256 || !d.W2 || !d.K2 || d.k_core > d.K ||
+        d.K >= (1u << 30) || d.core_dups >= (1u << 30) || nb > (uint32_t)TAIL_LDS_OFFS || nbh > (uint32_t)AHEAD_MAX_HEAD_BLOCKS ||
+        d.bm_guard > 4096 || d.fused > 1)
+        return fail(c, MSIM_ERR_ARG, "msim_dbg_chain_step: bad argument");
+    const uint32_t nb2 = d.W2 / SNP_BLOCK2 + 2;
+    // the head interval and the window lie inside the words; wherever the SNP draws may start (the cut, the clamp, the old base),
+    // their window's blocks are mapped ones
+    if (d.lo > n_words || H > n_words || d.W > n_words - H || d.state.snp_base > H + d.W ||
+        (H + d.W) / SNP_BLOCK2 + nb2 > n_blocks2 || d.K2 > n_words)
+        return fail(c, MSIM_ERR_ARG, "msim_dbg_chain_step: the head interval, the window or the SNP window does not lie inside the words");
+    // the head counts are what the words say (the fringe pass subtracts what it counts itself from them), the head list has a
+    // segment per block, the tail list covers whatever index the fringe and the rounds can reach
+    if (n_hacc < (uint64_t)nbh * ACC_BLOCK) return fail(c, MSIM_ERR_ARG, "msim_dbg_chain_step: head list shorter than its blocks' segments");
+    for (uint32_t b = 0; b < nbh; b++) {
+        uint32_t n_acc = 0;
+        for (uint32_t i = b * ACC_BLOCK; i < std::min<uint32_t>(d.F, (b + 1) * ACC_BLOCK); i++) n_acc += (mt_temper(words[d.lo + i]) >> d.shift) < d.n;
+        if (hcnt[b] != n_acc) return fail(c, MSIM_ERR_ARG, "msim_dbg_chain_step: a head count that is not the words' count");
+    }
+    uint64_t total = 0;
+    for (uint32_t i = 0; i < nb; i++) total += cnt[i];
+    const uint64_t items = (uint64_t)d.K - d.k_core + d.core_dups;
+    if (total >= (1ull << 31) || n_tail < items || (total > d.k_core && n_tail < total - d.k_core))
+        return fail(c, MSIM_ERR_ARG, "msim_dbg_chain_step: the tail list does not cover what the kernels may read");
+    for (uint64_t i = 0; i < n_tail; i++)
+        if (tail[i] >= d.n) return fail(c, MSIM_ERR_ARG, "msim_dbg_chain_step: a list entry beyond the population");
+    static_assert(sizeof(SnpLane) == 16 && sizeof(SnpMap) == 16 && sizeof(SpecHdr) == 16, "msim_dbg_chain_step hands them out as four uint32");
+    const size_t bm_words = ((size_t)d.n + 31) / 32, sz_bm = (bm_words + 2 * (size_t)d.bm_guard) * 4;
+    const size_t sz_raw = (size_t)n_words * 4, sz_lanes = (size_t)n_blocks2 * SNP_THREADS * sizeof(SnpLane), sz_maps = (size_t)n_blocks2 * sizeof(SnpMap);
+    const size_t sz_win = (size_t)(nb2 + 2) * sizeof(SnpMap);                 // nb2 blocks, the totals entry, one guard entry
+    const size_t sz_hcnt = ((size_t)nbh + 2) * 4, sz_hacc = std::max<size_t>((size_t)n_hacc * 4, 4) + 256, sz_tail = std::max<size_t>((size_t)n_tail * 4, 4);
+    const size_t sz_cnt = ((size_t)nb + 2) * 4;
+    DbgDev dev;
+    uint32_t *d_raw, *d_hcnt, *d_hacc, *d_tail, *d_cnt, *d_bm; SnpLane *d_lanes; SnpMap *d_maps, *d_win; PlanState *d_ps; SpecHdr *d_hdr;
+    unsigned long long *d_base;
+    MSIM_HIP(c, dev.bytes(&d_raw, sz_raw)); MSIM_HIP(c, dev.bytes(&d_hcnt, sz_hcnt)); MSIM_HIP(c, dev.bytes(&d_hacc, sz_hacc));
+    MSIM_HIP(c, dev.bytes(&d_tail, sz_tail)); MSIM_HIP(c, dev.bytes(&d_cnt, sz_cnt)); MSIM_HIP(c, dev.bytes(&d_bm, sz_bm));
+    MSIM_HIP(c, dev.bytes(&d_lanes, sz_lanes)); MSIM_HIP(c, dev.bytes(&d_maps, sz_maps)); MSIM_HIP(c, dev.bytes(&d_win, sz_win));
+    MSIM_HIP(c, dev.bytes(&d_ps, 3 * sizeof(PlanState))); MSIM_HIP(c, dev.bytes(&d_hdr, sizeof(SpecHdr))); MSIM_HIP(c, dev.bytes(&d_base, 64));
+    hipStream_t st = c->stream;
+    PlanState ps[3];                                       // the chain's, the core window's, the head interval's
+    memset(ps, 0, sizeof ps);
+    ps[0].pos = d.state.pos; ps[0].snp_base = d.state.snp_base; ps[0].flags = d.state.flags; ps[0].dups = d.state.dups;
+    ps[0].accepted_used = d.state.accepted_used; ps[0].ahead_margin_used = d.state.rsv;
+    ps[1].pos = ps[1].snp_base = H; ps[1].dups = d.core_dups; ps[1].flags = d.core_flags;
+    ps[2].pos = ps[2].snp_base = d.lo; ps[2].flags = d.head_flags;
+    const SpecHdr hdr{0, 0, 0, 0};                         // (as the prep's count body leaves it)
+    MSIM_HIP(c, hipMemcpyAsync(d_raw, words, sz_raw, hipMemcpyHostToDevice, st));
+    if (nbh) MSIM_HIP(c, hipMemcpyAsync(d_hcnt, hcnt, (size_t)nbh * 4, hipMemcpyHostToDevice, st));
+    if (n_hacc) MSIM_HIP(c, hipMemcpyAsync(d_hacc, hacc, (size_t)n_hacc * 4, hipMemcpyHostToDevice, st));
+    if (n_tail) MSIM_HIP(c, hipMemcpyAsync(d_tail, tail, (size_t)n_tail * 4, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemsetAsync(d_cnt, 0, sz_cnt, st));
+    MSIM_HIP(c, hipMemcpyAsync(d_cnt, cnt, (size_t)nb * 4, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemcpyAsync(d_bm, bitmap, sz_bm, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemcpyAsync(d_ps, ps, sizeof ps, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemcpyAsync(d_hdr, &hdr, sizeof hdr, hipMemcpyHostToDevice, st));
+    MSIM_HIP(c, hipMemsetAsync(d_win, 0xee, sz_win, st));
+    MSIM_HIP(c, hipMemsetAsync(d_base, 0xee, 64, st));
+    hipLaunchKernelGGL(k_snp_maps_abs, dim3((uint32_t)n_blocks2), dim3(SNP_THREADS), 0, st, d_raw, (uint32_t)n_words,
+                       (unsigned long long)d.ti_lim, 0u, d_maps, d_lanes);
+    if (d.fused) {
+        ChainJob J{};
+        J.raw = d_raw; J.ps = d_ps; J.ps_core = d_ps + 1; J.ps_head = d_ps + 2; J.hdr = d_hdr;
+        J.hcnt = d_hcnt; J.hacc = d_hacc; J.acc = d_tail; J.bitmap = d_bm + d.bm_guard;
+        J.lo = d.lo; J.expect = d.expect;
+        J.F = d.F; J.nbh = nbh; J.K = d.K; J.k_core = d.k_core; J.shift = d.shift; J.n = d.n; J.soft_half = d.soft_half;
+        J.cnt = d_cnt; J.nb = nb; J.W = d.W; J.pos_limit = d.pos_limit;
+        J.lanes = d_lanes; J.abs_maps = d_maps; J.win_maps = d_win; J.base_out = d_base;
+        J.snp_limit = d.snp_limit; J.W2 = d.W2; J.nb2 = nb2; J.K2 = d.K2;
+        hipLaunchKernelGGL(k_chain_fused, dim3(d.G), dim3(ACC_THREADS), 0, st, J);
+    } else {
+        hipLaunchKernelGGL(k_ahead_fringe, dim3(d.G), dim3(ACC_THREADS), 0, st, d_raw, d_ps, d_ps + 1, d_ps + 2, d_hdr, (unsigned long long)d.lo,
+                           d.F, d_hcnt, nbh, d_hacc, d_tail, d.K, d.k_core, d.shift, d.n, d_bm + d.bm_guard, (unsigned long long)d.expect,
+                           d.soft_half);
+        hipLaunchKernelGGL(k_sample_tail, dim3(1), dim3(TAIL_THREADS), 0, st, d_raw, d_tail, d.k_core, d_cnt, nb, d.W, d.shift, d.n, d.k_core,
+                           d_bm + d.bm_guard, d_ps, 1u, (const PlanState *)(d_ps + 1), (const SpecHdr *)d_hdr, (unsigned long long)d.pos_limit);
+        hipLaunchKernelGGL(k_snp_scan_cut_abs, dim3(1), dim3(SNP_THREADS), 0, st, d_lanes, d_ps, d.W2, d_maps, d_win, nb2, d.K2, d_base,
+                           (unsigned long long)d.snp_limit);
+    }
+    MSIM_HIP(c, hipGetLastError());
+    MSIM_HIP(c, hipMemcpyAsync(bitmap, d_bm, sz_bm, hipMemcpyDeviceToHost, st));
+    MSIM_HIP(c, hipMemcpyAsync(win_maps, d_win, sz_win, hipMemcpyDeviceToHost, st));
+    MSIM_HIP(c, hipMemcpyAsync(ps, d_ps, sizeof(PlanState), hipMemcpyDeviceToHost, st));
+    MSIM_HIP(c, hipMemcpyAsync(d.hdr, d_hdr, sizeof(SpecHdr), hipMemcpyDeviceToHost, st));
+    MSIM_HIP(c, hipMemcpyAsync(&d.base, d_base, 8, hipMemcpyDeviceToHost, st));
+    MSIM_HIP(c, wait_stream(st));
+    d.state.pos = ps[0].pos; d.state.snp_base = ps[0].snp_base; d.state.flags = ps[0].flags; d.state.dups = ps[0].dups;
+    d.state.accepted_used = ps[0].accepted_used; d.state.rsv = ps[0].ahead_margin_used;
+    return MSIM_OK;
+}
+uint64_t gpu_plan_chains_fused(const GpuPlan *g) { return g ? g->chains_fused : 0; }
+
 bool gpu_emit_pending(Ctx *c, int contig, bool mark_apply) {
     GpuPlan *g = c->gpu;
     if (!g) return false;
@@ -1673,6 +1809,7 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
     if (!g->emit_items.empty() && (!grouped || g->emit_d != (uint32_t)d || g->emit_items.size() >= (size_t)group))
         if ((rc = gpu_emit_flush(c))) return rc;
     struct { SampleSet *S; uint32_t bmw, bnb, start; } late = {nullptr, 0, 0, 0};
+    g->held.on = false;
     for (int i = 0; i < n_ranges; i++) {
         const msim_range &r = ranges[i];
         if (r.k == 0) continue;
@@ -1682,13 +1819,16 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
         const SampleStep st = sample_step(g->ahead_sigma, g->est, pos_hi, r, d, can_ahead);
         if (st.bad) return fail(c, MSIM_ERR_UNSUPPORTED, "sample window beyond 2^32 words");
         const bool ahead = st.ahead;
-        if (ahead && (rc = enqueue_sample_ahead(c, g, r, d, st, grow, sl, grouped))) return rc;
+        // (an anchored window implies one drawing range: the whole chain of the contig is then one launch, sent by the SNP stage)
+        if (ahead && (rc = enqueue_sample_ahead(c, g, r, d, st, grow, sl, grouped, g->chain_fuse && n_draw == 1))) return rc;
         if (!ahead && (rc = enqueue_sample_chain(c, g, r, d, st.pos_in, grow, sl, nullptr, nullptr, st.e_lim))) return rc;
         SampleSet &S = *sl.S;
         const uint32_t bmw = sl.bmw, bnb = sl.bnb;
         if (grouped) {
             late = {&S, bmw, bnb, (uint32_t)r.start};
         } else if (!c->chain_only) {
+            // (a held launch belongs to a grouped or walked contig: this event would be recorded in front of the sample's kernels)
+            if (g->held.on) return fail(c, MSIM_ERR_HIP, "GPU sampler: a held chain launch in front of an ungrouped emission");
             hipEvent_t ce = next_chain_event(g);
             MSIM_HIP(c, hipEventRecord(ce, c->stream));
             // ---- emit (emit stream): the bitmap is the sorted sample -> records
@@ -1710,13 +1850,14 @@ int plan_contig_gpu(Ctx *c, GpuPlan *g, Contig &ct, const msim_range *ranges, in
         }
         rec_base += k;
     }
+    if (!K && g->held.on) return fail(c, MSIM_ERR_HIP, "GPU sampler: a held chain launch and no SNP stage to send it");
     if (K) {                                          // SNP draws in position order (chain: scan + cut; aux off the chain)
         uint8_t *aux8 = nullptr;
         SnpDefer df{nullptr, 0, 0};
         // (e_lim: the bound the position is tightened to behind this stage -- the kernel flags a cut beyond it)
         const SnpStep sn = snp_step(g->est, pos_hi, K, P);
         uint64_t snp_pos = sn.pos_in;
-        if ((rc = enqueue_snp_stage(c, g, ct, K, nullptr, snp_pos, grow, late.S ? &aux8 : nullptr, grouped ? &df : nullptr, sn.e_lim))) return rc;
+        if ((rc = enqueue_snp_stage(c, g, ct, K, nullptr, snp_pos, grow, late.S ? &aux8 : nullptr, grouped ? &df : nullptr, sn.e_lim, true))) return rc;
         if (grouped) {
             g->emit_d = (uint32_t)d;
             g->emit_items.push_back(EmitItem{ct.index, late.S, df.T, late.bmw, late.bnb, late.start, (uint32_t)K, df.W2, df.nb2,

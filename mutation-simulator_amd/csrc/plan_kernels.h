@@ -466,7 +466,7 @@ __device__ __forceinline__ void ahead_count_body(const uint32_t blk, const uint3
     if (blk == 0 && threadIdx.x == 0) {
         ps_core->pos = H; ps_core->snp_base = H; ps_core->flags = 0; ps_core->dups = 0; ps_core->accepted_used = 0;
         ps_head->pos = lo; ps_head->snp_base = lo; ps_head->flags = 0; ps_head->dups = 0; ps_head->accepted_used = 0;
-        hdr->need0 = 0; hdr->d1 = 0;
+        hdr->need0 = 0; hdr->d1 = 0; hdr->rsv0 = 0;         // (rsv0: k_chain_fused's ticket word)
     }
     if (blk < nb) {
         for (uint32_t i = blk * ACC_THREADS + threadIdx.x; i < n_cursors; i += nb * ACC_THREADS) cursors[i] = 0;
@@ -553,27 +553,47 @@ __global__ __launch_bounds__(512) void k_bin_dedupe_b(PrepJobs J) {
 }
 
 constexpr int FRINGE_ITEMS = 4;
-__global__ __launch_bounds__(ACC_THREADS) void k_ahead_fringe(const uint32_t *__restrict__ raw, PlanState *__restrict__ ps,
-                                                              const PlanState *__restrict__ ps_core,
-                                                              const PlanState *__restrict__ ps_head, SpecHdr *__restrict__ hdr,
-                                                              unsigned long long lo, uint32_t F,
-                                                              const uint32_t *__restrict__ hcnt, uint32_t nbh,
-                                                              const uint32_t *__restrict__ hacc, const uint32_t *__restrict__ tail,
-                                                              uint32_t K, uint32_t k_core, uint32_t shift, uint32_t n,
-                                                              uint32_t *__restrict__ bitmap, unsigned long long expect,
-                                                              uint32_t soft_half) {
+// What a fringe workgroup reads that nothing in its launch computes (the chain's position, what the prep left behind): loaded
+// by every lane in front of everything else, so that none of it is a round trip of its own behind a barrier.
+struct FringeIn { unsigned long long s; uint32_t core_dups, fl; };
+__device__ __forceinline__ FringeIn fringe_in(const PlanState *ps, const PlanState *ps_core, const PlanState *ps_head) {
+    FringeIn in;
+    in.s = ps->pos; in.core_dups = ps_core->dups; in.fl = ps_core->flags | ps_head->flags;
+    return in;
+}
+// The fringe pass of workgroup `wg` of `n_wg`.  Returns false where the sample is flagged (uniform over the whole launch: every
+// workgroup sees the same start and the same counts); h_acc / items as the tail pass needs them (need0 = items - h_acc).
+// FUSED (k_chain_fused): hdr->need0 is left to the workgroup that goes on, and every wave has the ANSWER of its add to hdr->d1
+// before it returns -- the add has then been performed where the ticket's add and the last arriver's load are performed.
+template <bool FUSED>
+__device__ __forceinline__ bool ahead_fringe_body(const uint32_t wg, const uint32_t n_wg, const FringeIn in,
+                                                  const uint32_t *__restrict__ raw, PlanState *__restrict__ ps, SpecHdr *hdr,
+                                                  unsigned long long lo, uint32_t F,
+                                                  const uint32_t *__restrict__ hcnt, uint32_t nbh,
+                                                  const uint32_t *__restrict__ hacc, const uint32_t *__restrict__ tail,
+                                                  uint32_t K, uint32_t k_core, uint32_t shift, uint32_t n,
+                                                  uint32_t *__restrict__ bitmap, unsigned long long expect,
+                                                  uint32_t soft_half, uint32_t &h_acc_out, uint32_t &items_out) {
     // expect / soft_half: the start the host expected and the half-width 8 sigma + 256 it allowed around it BEFORE the hard
     // bounds clipped the interval to [lo, lo + F] (a start at a hard bound is certain, not lucky): telemetry only
     __shared__ uint32_t red[ACC_THREADS / 64];
     __shared__ uint32_t hoff[AHEAD_MAX_HEAD_BLOCKS + 1];   // accepted draws of [s, H) in front of head block b
     __shared__ uint32_t wsum[ACC_THREADS / 64];
-    const unsigned long long s = ps->pos;
+    h_acc_out = 0; items_out = 0;
+    const unsigned long long s = in.s;
+    // the head blocks' counts depend on nothing either: four consecutive blocks per lane, in flight before the first barrier
+    uint32_t hc[4];
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const uint32_t b = threadIdx.x * 4 + q;
+        hc[q] = b < nbh ? hcnt[b] : 0u;
+    }
     if (s < lo || s > lo + F) {                            // (uniform) the start fell outside the interval the host planned for
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&ps->flags, FLAG_SAMPLE_OVERFLOW);
-        return;
+        if (wg == 0 && threadIdx.x == 0) atomicOr(&ps->flags, FLAG_SAMPLE_OVERFLOW);
+        return false;
     }
     const uint32_t rel = (uint32_t)(s - lo);
-    if (blockIdx.x == 0 && threadIdx.x == 0 && soft_half) {   // telemetry: how much of the allowed deviation this start used
+    if (wg == 0 && threadIdx.x == 0 && soft_half) {   // telemetry: how much of the allowed deviation this start used
         const unsigned long long dev = s > expect ? s - expect : expect - s;
         atomicMax(&ps->ahead_margin_used, (uint32_t)min(1000000ull, 1000ull * dev / soft_half));
     }
@@ -599,7 +619,7 @@ __global__ __launch_bounds__(ACC_THREADS) void k_ahead_fringe(const uint32_t *__
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const uint32_t b = threadIdx.x * 4 + q;
-            v[q] = (b >= blk && b < nbh) ? hcnt[b] - (b == blk ? skip : 0u) : 0u;
+            v[q] = (b >= blk && b < nbh) ? hc[q] - (b == blk ? skip : 0u) : 0u;
             sum += v[q];
         }
         uint32_t run = wg_scan_incl(sum, wsum) - sum;
@@ -613,19 +633,19 @@ __global__ __launch_bounds__(ACC_THREADS) void k_ahead_fringe(const uint32_t *__
         __syncthreads();
         h_acc = hoff[AHEAD_MAX_HEAD_BLOCKS];
     }
-    const uint32_t items = K - k_core + ps_core->dups;     // = h_acc + need0
+    const uint32_t items = K - k_core + in.core_dups;      // = h_acc + need0
+    h_acc_out = h_acc; items_out = items;
     if (h_acc > items) {                                   // (uniform) more accepted draws in front of the anchor than a_max
-        if (blockIdx.x == 0 && threadIdx.x == 0) atomicOr(&ps->flags, FLAG_SAMPLE_OVERFLOW);
-        return;
+        if (wg == 0 && threadIdx.x == 0) atomicOr(&ps->flags, FLAG_SAMPLE_OVERFLOW);
+        return false;
     }
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        hdr->need0 = items - h_acc;
-        const uint32_t fl = ps_core->flags | ps_head->flags;
-        if (fl) atomicOr(&ps->flags, fl);
+    if (wg == 0 && threadIdx.x == 0) {
+        if (!FUSED) hdr->need0 = items - h_acc;
+        if (in.fl) atomicOr(&ps->flags, in.fl);
     }
     uint32_t d = 0;
-    const uint32_t stride = gridDim.x * ACC_THREADS;
-    for (uint32_t base = blockIdx.x * ACC_THREADS + threadIdx.x; base < items; base += FRINGE_ITEMS * stride) {
+    const uint32_t stride = n_wg * ACC_THREADS;
+    for (uint32_t base = wg * ACC_THREADS + threadIdx.x; base < items; base += FRINGE_ITEMS * stride) {
         uint32_t old[FRINGE_ITEMS], bit[FRINGE_ITEMS];
 #pragma unroll
         for (int q = 0; q < FRINGE_ITEMS; q++) {           // the atomics back to back, then their answers
@@ -653,7 +673,28 @@ __global__ __launch_bounds__(ACC_THREADS) void k_ahead_fringe(const uint32_t *__
         for (int q = 0; q < FRINGE_ITEMS; q++) d += (old[q] & bit[q]) ? 1u : 0u;
     }
     for (int o = 32; o > 0; o >>= 1) d += __shfl_down(d, o, 64);
-    if ((threadIdx.x & 63) == 0 && d) atomicAdd(&hdr->d1, d);
+    if ((threadIdx.x & 63) == 0 && d) {
+        if (FUSED) {
+            const uint32_t was = __hip_atomic_fetch_add(&hdr->d1, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            asm volatile("s_waitcnt vmcnt(0)" ::"v"(was) : "memory");
+        } else {
+            atomicAdd(&hdr->d1, d);
+        }
+    }
+    return true;
+}
+__global__ __launch_bounds__(ACC_THREADS) void k_ahead_fringe(const uint32_t *__restrict__ raw, PlanState *__restrict__ ps,
+                                                              const PlanState *__restrict__ ps_core,
+                                                              const PlanState *__restrict__ ps_head, SpecHdr *__restrict__ hdr,
+                                                              unsigned long long lo, uint32_t F,
+                                                              const uint32_t *__restrict__ hcnt, uint32_t nbh,
+                                                              const uint32_t *__restrict__ hacc, const uint32_t *__restrict__ tail,
+                                                              uint32_t K, uint32_t k_core, uint32_t shift, uint32_t n,
+                                                              uint32_t *__restrict__ bitmap, unsigned long long expect,
+                                                              uint32_t soft_half) {
+    uint32_t h_acc, items;
+    (void)ahead_fringe_body<false>(blockIdx.x, gridDim.x, fringe_in(ps, ps_core, ps_head), raw, ps, hdr, lo, F, hcnt, nbh, hacc, tail,
+                                   K, k_core, shift, n, bitmap, expect, soft_half, h_acc, items);
 }
 
 // Tail rounds + exact cut.  One workgroup.  `total_acc` = accepted draws available in the window.
@@ -1257,21 +1298,29 @@ __global__ __launch_bounds__(SNP_THREADS) void k_snp_maps_abs(const uint32_t *__
 // of window block j when the stream starts in state 0 (c[0] = count, e = state) -- what k_snp_emit_abs needs -- and
 // the block in which the K-th SNP completes has been re-walked: the word on which it completes + 1 is the new
 // stream position.  Also saves the start position for the emit pass.
-__global__ __launch_bounds__(SNP_THREADS) void k_snp_scan_cut_abs(const SnpLane *__restrict__ lanes, PlanState *__restrict__ ps,
-                                                                  uint32_t W,
-                                                                  const SnpMap *__restrict__ abs_maps,
-                                                                  SnpMap *__restrict__ win_maps, uint32_t nb_max, uint32_t K,
-                                                                  unsigned long long *__restrict__ base_out,
-                                                                  unsigned long long pos_limit = ~0ull) {
+// (the body: p0 is where the draws start -- ps->snp_base for the kernel of its own, the cut the workgroup has just made for
+//  k_chain_fused, which has it in LDS and need not read it back)
+__device__ __forceinline__ void snp_scan_cut_body(const SnpLane *__restrict__ lanes, PlanState *__restrict__ ps,
+                                                  const unsigned long long p0, uint32_t W,
+                                                  const SnpMap *__restrict__ abs_maps,
+                                                  SnpMap *__restrict__ win_maps, uint32_t nb_max, uint32_t K,
+                                                  unsigned long long *__restrict__ base_out,
+                                                  unsigned long long pos_limit) {
     __shared__ SnpMap wave_tot[SNP_THREADS / 64];
     __shared__ SnpMap s_first;
     __shared__ uint32_t s_blk, s_bs, s_bc;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const unsigned long long p0 = ps->snp_base;
     const uint32_t b0 = (uint32_t)(p0 / SNP_BLOCK2), off = (uint32_t)(p0 % SNP_BLOCK2);
     const uint32_t nb = min(nb_max, (off + W + SNP_BLOCK2 - 1) / SNP_BLOCK2);
     const uint32_t w_end = (uint32_t)min<unsigned long long>(p0 + W, 0xffffffffull);       // words beyond the window are not live
     if (threadIdx.x == 0) { s_blk = 0xffffffffu; *base_out = p0; }
+    SnpMap v[4];                                          // the first chunk's maps: in flight beside the first block's lanes
+#pragma unroll
+    for (int q = 0; q < 4; q++) {
+        const uint32_t i = threadIdx.x * 4 + q;
+        v[q] = snp_identity();
+        if (i && i < nb) v[q] = abs_maps[b0 + i];
+    }
     {   // the partial first block, mapped here
         const SnpLane L0 = lanes[(size_t)b0 * SNP_THREADS + threadIdx.x];
         const SnpBits m0 = snp_bits_of(L0, b0 * SNP_BLOCK2, w_end, off);
@@ -1283,9 +1332,15 @@ __global__ __launch_bounds__(SNP_THREADS) void k_snp_scan_cut_abs(const SnpLane 
     uint32_t c_state = 0, c_count = 0;                    // carried across chunks, identical in every lane
     for (uint32_t base = 0; base < nb; base += 4 * SNP_THREADS) {
         const uint32_t i0 = base + threadIdx.x * 4;
-        SnpMap v[4];
+        if (base) {
 #pragma unroll
-        for (int q = 0; q < 4; q++) v[q] = i0 + q >= nb ? snp_identity() : (i0 + q == 0 ? s_first : abs_maps[b0 + i0 + q]);
+            for (int q = 0; q < 4; q++) {
+                v[q] = snp_identity();
+                if (i0 + q < nb) v[q] = abs_maps[b0 + i0 + q];
+            }
+        } else if (threadIdx.x == 0) {
+            v[0] = s_first;                               // (window block 0: the partial one)
+        }
         SnpMap incl = snp_compose(snp_compose(v[0], v[1]), snp_compose(v[2], v[3]));
 #pragma unroll
         for (int o = 1; o < 64; o <<= 1) {
@@ -1325,7 +1380,7 @@ __global__ __launch_bounds__(SNP_THREADS) void k_snp_scan_cut_abs(const SnpLane 
         win_maps[nb_max].c[0] = c_count;
         win_maps[nb_max].c[1] = nb;
         win_maps[nb_max].e = c_state;
-        if (c_count < K) ps->flags |= FLAG_SNP_OVERFLOW;
+        if (c_count < K) atomicOr(&ps->flags, FLAG_SNP_OVERFLOW);   // (atomic: in k_chain_fused other workgroups raise flags too)
     }
     if (c_count < K) return;                              // uniform
     const uint32_t b = s_blk, bs = s_bs, bc = s_bc;
@@ -1349,6 +1404,167 @@ __global__ __launch_bounds__(SNP_THREADS) void k_snp_scan_cut_abs(const SnpLane 
         // exists).  Beyond it the next stage would read words nobody generated: an overflow, never a silent short read.
         if (cut > pos_limit) atomicOr(&ps->flags, FLAG_SNP_OVERFLOW);
     }
+}
+
+__global__ __launch_bounds__(SNP_THREADS) void k_snp_scan_cut_abs(const SnpLane *__restrict__ lanes, PlanState *__restrict__ ps,
+                                                                  uint32_t W,
+                                                                  const SnpMap *__restrict__ abs_maps,
+                                                                  SnpMap *__restrict__ win_maps, uint32_t nb_max, uint32_t K,
+                                                                  unsigned long long *__restrict__ base_out,
+                                                                  unsigned long long pos_limit = ~0ull) {
+    snp_scan_cut_body(lanes, ps, ps->snp_base, W, abs_maps, win_maps, nb_max, K, base_out, pos_limit);
+}
+
+// ---- the chain of an anchored contig with one drawing range in ONE launch: k_ahead_fringe's grid, and the workgroup that
+// finishes its fringe share last goes on with k_sample_tail's rounds and cut and k_snp_scan_cut_abs's scan and cut (NOTES
+// section 34).  Per contig the three launches cost three start-ups beside a rewrite launch that fills every wave slot, two
+// hand-overs through memory (hdr->need0 / d1, ps->pos / snp_base) and loads that wait behind a kernel boundary for no reason.
+//   * 256 threads, 5 344 B of LDS: a workgroup fits behind any ONE retiring rewrite tile (k_sample_tail needs four of a CU's eight).
+//   * Who goes on: a workgroup that has the ANSWERS of all its atomics (bitmap, hdr->d1) passes a barrier and takes a ticket, a
+//     returning agent-scope add on hdr->rsv0 (zeroed with need0 / d1 by the prep's count body); ticket G - 1 goes on, the others
+//     exit.  Nobody waits for anybody: the launch cannot hang, whatever is resident.
+//   * What crosses workgroups inside the launch is touched by atomics only -- the bitmap's words, d1 (read back by an agent-scope
+//     atomic load behind the ticket), rsv0, ps->flags -- so there is nothing to release and no L1 line to invalidate; everything
+//     else the last workgroup reads was written by earlier launches, and what it plain-stores (ps, need0, win_maps, the base) is
+//     read by later ones.
+//   * The tail stage in its four-wave form (section 30, second form): a lane keeps the counts of 32 consecutive blocks in
+//     registers (256 x 32 = TAIL_LDS_OFFS), one workgroup scan, the cut's block by a look at the per-lane offsets, eight words per
+//     lane of that block.
+//   * A flagged sample skips what follows (the three launches go on over whatever is there; a flagged pass is discarded either
+//     way): same flag, same error.
+struct ChainJob {
+    const uint32_t *raw; PlanState *ps; const PlanState *ps_core, *ps_head; SpecHdr *hdr;       // fringe (k_ahead_fringe's arguments)
+    const uint32_t *hcnt, *hacc, *acc; uint32_t *bitmap;
+    unsigned long long lo, expect;
+    uint32_t F, nbh, K, k_core, shift, n, soft_half;
+    const uint32_t *cnt; uint32_t nb, W; unsigned long long pos_limit;                          // tail (k_sample_tail's)
+    const SnpLane *lanes; const SnpMap *abs_maps; SnpMap *win_maps; unsigned long long *base_out;   // SNP draws (k_snp_scan_cut_abs's)
+    unsigned long long snp_limit;
+    uint32_t W2, nb2, K2;
+};
+constexpr int CHAIN_CPL = TAIL_LDS_OFFS / ACC_THREADS;   // block counts a lane keeps
+static_assert(CHAIN_CPL == 32 && ACC_THREADS == SNP_THREADS, "k_chain_fused: one workgroup shape for all three stages");
+__global__ __launch_bounds__(ACC_THREADS) void k_chain_fused(ChainJob J) {
+    __shared__ uint32_t loff[ACC_THREADS + 1];            // accepted draws in front of a lane's 32 blocks; the total
+    __shared__ uint32_t wsum_a[ACC_THREADS / 64], wsum_b[ACC_THREADS / 64], red[2][ACC_THREADS / 64];
+    __shared__ uint32_t s_last, s_blk, s_want, s_cut_ok;
+    __shared__ unsigned long long s_cut;
+    // ---- everything that depends on nothing computed here, in flight at once
+    const FringeIn in = fringe_in(J.ps, J.ps_core, J.ps_head);
+    const unsigned long long p0 = J.ps_core->pos;         // the anchored window's origin
+    const unsigned long long base_old = J.ps->snp_base;
+    uint32_t bc[CHAIN_CPL];
+    {
+        const uint32_t b0 = threadIdx.x * CHAIN_CPL;
+        if (b0 + CHAIN_CPL <= J.nb) {                      // (a scratch block is a device allocation: 128-byte aligned rows)
+            const uint4 *p = reinterpret_cast<const uint4 *>(J.cnt + b0);
+#pragma unroll
+            for (int q = 0; q < CHAIN_CPL / 4; q++) {
+                const uint4 t = p[q];
+                bc[4 * q] = t.x; bc[4 * q + 1] = t.y; bc[4 * q + 2] = t.z; bc[4 * q + 3] = t.w;
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < CHAIN_CPL; q++) bc[q] = b0 + q < J.nb ? J.cnt[b0 + q] : 0u;
+        }
+    }
+    // ---- fringe: this workgroup's share
+    uint32_t h_acc, items;
+    const bool ok = ahead_fringe_body<true>(blockIdx.x, gridDim.x, in, J.raw, J.ps, J.hdr, J.lo, J.F, J.hcnt, J.nbh, J.hacc, J.acc,
+                                            J.K, J.k_core, J.shift, J.n, J.bitmap, J.expect, J.soft_half, h_acc, items);
+    __syncthreads();                                       // every wave has the answers of its atomics
+    if (threadIdx.x == 0)
+        s_last = __hip_atomic_fetch_add(&J.hdr->rsv0, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == gridDim.x - 1 ? 1u : 0u;
+    __syncthreads();
+    if (!s_last || !ok) return;                            // (uniform)
+    // ---- the last workgroup: tail rounds
+    const uint32_t need0 = items - h_acc;
+    uint32_t need = __hip_atomic_load(&J.hdr->d1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    uint32_t sum = 0;
+#pragma unroll
+    for (int q = 0; q < CHAIN_CPL; q++) sum += bc[q];
+    const uint32_t incl = wg_scan_incl(sum, wsum_a);
+    const uint32_t excl = incl - sum;
+    loff[threadIdx.x] = excl;
+    if (threadIdx.x == ACC_THREADS - 1) loff[ACC_THREADS] = incl;
+    if (threadIdx.x == 0) { J.hdr->need0 = need0; s_blk = 0; s_want = 0; s_cut_ok = 0; }
+    __syncthreads();
+    const uint32_t total_acc = loff[ACC_THREADS];
+    uint32_t pos = J.k_core + need0;
+    bool over = total_acc < pos;                           // window too small even for the core's share and the fringe's
+    for (uint32_t round = 0; !over && need; round++) {
+        if (pos + need > total_acc) { over = true; break; }
+        uint32_t d = 0;
+        for (uint32_t base = threadIdx.x; base < need; base += 8 * ACC_THREADS) {
+            uint32_t old[8], bit[8];
+#pragma unroll
+            for (int q = 0; q < 8; q++) {                  // eight atomics a lane before the first answer
+                const uint32_t i = base + q * ACC_THREADS;
+                old[q] = 0; bit[q] = 0;
+                if (i < need) {
+                    const uint32_t v = J.acc[pos - J.k_core + i];
+                    bit[q] = 1u << (v & 31);
+                    old[q] = atomicOr(&J.bitmap[v >> 5], bit[q]);
+                }
+            }
+#pragma unroll
+            for (int q = 0; q < 8; q++) d += (old[q] & bit[q]) ? 1u : 0u;
+        }
+        for (int o = 32; o > 0; o >>= 1) d += __shfl_down(d, o, 64);
+        if ((threadIdx.x & 63) == 0) red[round & 1][threadIdx.x >> 6] = d;
+        __syncthreads();                                   // (two buffers in turn: one barrier a round)
+        pos += need;
+        need = red[round & 1][0] + red[round & 1][1] + red[round & 1][2] + red[round & 1][3];
+    }
+    if (over) {                                            // (uniform)
+        if (threadIdx.x == 0) atomicOr(&J.ps->flags, FLAG_SAMPLE_OVERFLOW);
+        return;
+    }
+    // ---- stream cut: one past the word holding the A-th accepted draw of the window
+    const uint32_t A = pos;
+    {   // the last block b < nb with fewer than A accepted draws in front of it: in the last lane whose first block is such a one
+        const uint32_t b0 = threadIdx.x * CHAIN_CPL;
+        const bool mine = b0 < J.nb && excl < A;
+        const bool next = threadIdx.x + 1 < ACC_THREADS && b0 + CHAIN_CPL < J.nb && loff[threadIdx.x + 1] < A;
+        if (mine && !next) {
+            uint32_t run = excl, best = b0, best_off = excl;
+#pragma unroll
+            for (int q = 0; q < CHAIN_CPL; q++) {
+                if (b0 + q < J.nb && run < A) { best = b0 + q; best_off = run; }
+                run += bc[q];
+            }
+            s_blk = best; s_want = A - best_off;
+        }
+    }
+    __syncthreads();
+    {
+        const uint32_t b = s_blk, want = s_want;           // 1-based rank inside block b
+        const uint32_t i0 = b * ACC_BLOCK + threadIdx.x * ACC_ITEMS;
+        uint32_t mask = 0;
+#pragma unroll
+        for (int q = 0; q < ACC_ITEMS; q++) {
+            uint32_t v;
+            if (i0 + q < J.W && accepted(J.raw, p0 + i0 + q, J.shift, J.n, v)) mask |= 1u << q;
+        }
+        const uint32_t c = (uint32_t)__popc(mask);
+        const uint32_t incl2 = wg_scan_incl(c, wsum_b);
+        const uint32_t excl2 = incl2 - c;
+        if (excl2 < want && want <= incl2) {
+            for (uint32_t r = excl2 + 1; r < want; r++) mask &= mask - 1;
+            unsigned long long cut = p0 + i0 + (uint32_t)__builtin_ctz(mask) + 1;
+            if (cut > J.pos_limit) { cut = J.pos_limit; atomicOr(&J.ps->flags, FLAG_SAMPLE_OVERFLOW); }   // (beyond what the host made sure exists)
+            // (ps->pos is stored again by the SNP cut's lane, possibly of another wave, behind barriers only: two stores of one
+            //  workgroup to one address reach L2 in issue order -- the workgroup is not split over CUs -- and k_sample_tail's
+            //  value stands where the SNP stage flags and returns, as in the three launches)
+            J.ps->pos = cut;
+            J.ps->snp_base = cut;
+            J.ps->accepted_used = A;
+            s_cut = cut; s_cut_ok = 1;
+        }
+    }
+    __syncthreads();
+    // ---- the SNP draws from there
+    snp_scan_cut_body(J.lanes, J.ps, s_cut_ok ? s_cut : base_old, J.W2, J.abs_maps, J.win_maps, J.nb2, J.K2, J.base_out, J.snp_limit);
 }
 
 // aux of every SNP record (off the critical path; runs on the emit stream).  Window block j = absolute block b0 + j.

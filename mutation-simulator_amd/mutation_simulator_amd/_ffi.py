@@ -184,6 +184,8 @@ SYMBOLS = [
     ("msim_dbg_sample_tail", C.c_int, [_VP, _VP, C.c_uint64, _VP, C.c_uint64, C.c_uint32, _VP, C.c_uint32, C.c_uint32, C.c_uint32,
                                        C.c_uint32, C.c_uint32, C.c_uint32, _VP, C.c_uint32, _VP, C.c_int, C.c_uint64, C.c_uint32,
                                        C.c_uint32, C.c_uint64]),
+    ("msim_dbg_chain_step", C.c_int, [_VP, _VP, C.c_uint64, _VP, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, _VP, _VP]),
+    ("msim_dbg_chains_fused", C.c_int, [_VP, _U64P]),
     ("msim_context_counts", C.c_int, [_VP, C.c_int, _VP, _U64P]),
     ("msim_plan_contig_spectrum", C.c_int, [_VP, C.c_int, _VP, C.c_uint64, C.c_uint32]),
     ("msim_spectrum_timing", C.c_int, [_VP, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
@@ -301,6 +303,10 @@ TYPE_TABLE_DTYPE = np.dtype([("thr", "<u8", (8,)), ("n", "<u4"), ("type", "u1", 
 MIX_RANGE_DTYPE = np.dtype([("rec_base", "<u4"), ("clip", "<u4"), ("set_id", "<u4"), ("rsv", "<u4")])
 TAIL_STATE_DTYPE = np.dtype([("pos", "<u8"), ("snp_base", "<u8"), ("flags", "<u4"), ("dups", "<u4"), ("accepted_used", "<u4"),
                              ("rsv", "<u4")])      # msim_dbg_tail_state
+CHAIN_STEP_DTYPE = np.dtype([("lo", "<u8"), ("expect", "<u8"), ("pos_limit", "<u8"), ("snp_limit", "<u8"), ("ti_lim", "<u8")] +
+                            [(f, "<u4") for f in ("F", "K", "k_core", "shift", "n", "W", "W2", "K2", "soft_half", "G", "core_dups",
+                                                  "core_flags", "head_flags", "bm_guard", "fused", "rsv")] +
+                            [("state", TAIL_STATE_DTYPE), ("hdr", "<u4", (4,)), ("base", "<u8")])      # msim_dbg_chain
 CHAIN_DROPPED = 0xFFFFFFFF           # ctx.h: a chain candidate that is blocked / dropped
 CHAIN_TOMBSTONE = 0x80               # ctx.h: ch_aux flag of an entry __fix_tl_amount deleted
 
@@ -993,6 +999,49 @@ class Engine:
                                                   int(k), _ptr(bm), int(guard), _ptr(st), 0 if win is None else 1, int(wpos),
                                                   int(need0), int(d1), int(pos_limit)))
         return {f: int(st[f][0]) for f in ("pos", "snp_base", "flags", "dups", "accepted_used")}, bm
+
+    def chain_step(self, words, ti_lim: int, lo: int, F: int, hcnt, hacc, tail, cnt, bitmap, state: dict, K: int, k_core: int,
+                   shift: int, n: int, W: int, W2: int, K2: int, G: int, fused: bool, core_dups: int = 0, core_flags: int = 0,
+                   head_flags: int = 0, expect: int = 0, soft_half: int = 0, pos_limit: int = 2 ** 64 - 1,
+                   snp_limit: int = 2 ** 64 - 1, guard: int = 4):
+        """One anchored contig's whole stream chain over the caller's tables (msim_dbg_chain_step): fringe, tail rounds, stream
+        cut, SNP scan and cut -- ``fused``: as the one launch the sampler sends, else as the three stand-alone launches.  RAW
+        CPython-stream ``words``; the head interval is words[lo, lo + F) with its accepted draws per 2048-word block (``hcnt``)
+        and in order, a 2048-entry segment per block (``hacc``); the window is words[lo + F, lo + F + W) with its accepted draws
+        per block (``cnt``) and, from accepted index ``k_core`` on, in order (``tail``); ``bitmap``: ceil(n / 32) uint32.
+        Returns a dict: state (pos, snp_base, flags, dups, accepted_used, margin), hdr (need0, d1, ticket word, 0), bitmap
+        between ``guard`` words of 0xee bytes, win_maps (W2 // 8192 + 4, 4) uint32 with the totals entry at W2 // 8192 + 2 and a
+        guard entry behind it (what no launch wrote: 0xee bytes), base."""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        hcnt = np.ascontiguousarray(hcnt, dtype=np.uint32)
+        hacc = np.ascontiguousarray(hacc, dtype=np.uint32)
+        tail = np.ascontiguousarray(tail, dtype=np.uint32)
+        cnt = np.ascontiguousarray(cnt, dtype=np.uint32)
+        assert hcnt.shape[0] == (int(F) + 2047) // 2048 and cnt.shape[0] == (int(W) + 2047) // 2048, "a count per 2048-word block"
+        bm = np.concatenate([np.full(guard, 0xEEEEEEEE, dtype=np.uint32), np.ascontiguousarray(bitmap, dtype=np.uint32),
+                             np.full(guard, 0xEEEEEEEE, dtype=np.uint32)])
+        assert bm.shape[0] == 2 * guard + (int(n) + 31) // 32, "bitmap: ceil(n / 32) words"
+        win = np.zeros((int(W2) // 8192 + 4, 4), dtype=np.uint32)
+        io = np.zeros(1, dtype=CHAIN_STEP_DTYPE)
+        for f, v in (("lo", lo), ("expect", expect), ("pos_limit", pos_limit), ("snp_limit", snp_limit), ("ti_lim", ti_lim), ("F", F),
+                     ("K", K), ("k_core", k_core), ("shift", shift), ("n", n), ("W", W), ("W2", W2), ("K2", K2), ("soft_half", soft_half),
+                     ("G", G), ("core_dups", core_dups), ("core_flags", core_flags), ("head_flags", head_flags), ("bm_guard", guard),
+                     ("fused", 1 if fused else 0)):
+            io[f] = int(v)
+        for f in ("pos", "snp_base", "flags", "dups", "accepted_used"):
+            io["state"][f] = int(state.get(f, 0))
+        io["state"]["rsv"] = int(state.get("margin", 0))
+        self._check(self.lib.msim_dbg_chain_step(self.h, _ptr(words), words.shape[0], _ptr(hcnt), _ptr(hacc), hacc.shape[0], _ptr(tail),
+                                                 tail.shape[0], _ptr(cnt), _ptr(bm), _ptr(win), _ptr(io)))
+        st = {f: int(io["state"][f][0]) for f in ("pos", "snp_base", "flags", "dups", "accepted_used")}
+        st["margin"] = int(io["state"]["rsv"][0])
+        return {"state": st, "hdr": [int(x) for x in io["hdr"][0]], "bitmap": bm, "win_maps": win, "base": int(io["base"][0])}
+
+    def chains_fused(self) -> int:
+        """Fused chain launches this context's SNP sampler has sent since it was created (msim_dbg_chains_fused)."""
+        n = C.c_uint64(0)
+        self._check(self.lib.msim_dbg_chains_fused(self.h, C.byref(n)))
+        return int(n.value)
 
     def candidates(self, np_words, sets, bitmap=None, start: int = 0, d: int = 1, K: int = 0, ranges=None, all: bool = False):
         """The candidate front of the SV-mix (``bitmap`` given: one range, ``sets`` one TYPE_TABLE_DTYPE entry) or host-chain
