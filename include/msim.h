@@ -909,6 +909,69 @@ int msim_dbg_cmp_counts_regions(const uint8_t *bases, uint64_t L, const msim_rec
 int msim_bed_scan(const uint8_t *text, uint64_t n_text, uint32_t *starts, uint32_t *ends, uint64_t *lines, uint64_t *n_intervals,
                   uint64_t *run_name_off, uint32_t *run_name_len, uint64_t *run_first, uint64_t *run_count, uint64_t *n_runs);
 
+/* ---- reads: FASTQ records drawn from the resident genome (csrc/reads.hip, reads.h) ------------------------------------------ */
+/* A read (pair) is a pure function of (key, read index i): no generator of the mutation engines is touched, nothing chains, and
+ * every record of a run is `stride` bytes long, so read i lies at byte i * stride of its file and any range renders on its own.
+ * The caller passes integer tables only (mutation_simulator_amd/reads.py builds them); the device does no floating point.
+ *
+ * Tables.  frag_min and frag_thr[n_frag], 1 <= n_frag <= 4096: ascending uint64, the last equal to 2^53 -- fragment length
+ * frag_min + k has the mass (frag_thr[k] - frag_thr[k - 1]) / 2^53; frag_min >= len; fmax = frag_min + n_frag - 1.  A single-end
+ * run passes frag_min = len, n_frag = 1.  err_thr[2][len]: ceil(p_j * 2^53), the substitution probability of cycle j of mate 1,
+ * then of mate 2; qual[2][len]: the quality bytes ('!' .. '~').  prefix: letters, digits and ._- only, at most 32 bytes.
+ * n_reads: the run's N, 1 <= N < 2^32 (it fixes the width of the index field).
+ *
+ * Eligible contigs, in context order: those with length >= fmax; weight w_c = length - fmax + 1, P = their sum, prefix_w the
+ * exclusive prefix sums.  Philox4x32-10 under the 64-bit key, counter (x, y, 0, tag):
+ *   placement  v = draw(x = i, y = 0, tag 22); p = mulhi64(low 64 bits of v, P); the contig is the last eligible one with
+ *              prefix_w[c] <= p, the 0-based start s = p - prefix_w[c]; u = (high 64 bits of v) >> 11, f = frag_min + the first k
+ *              with u < frag_thr[k]; strand = bit 0 of the high 64 bits.  The fragment is bases [s, s + f) of the contig and
+ *              always fits: there is no rejection loop.  The price: the last fmax - f starts of a contig are never drawn when
+ *              f < fmax.
+ *   bases      the fragment in its own orientation is those bases (strand 0) or their reverse complement (strand 1); mate 1 is
+ *              its first len bases, mate 2 the reverse complement of its last len.  A genome byte outside A, C, G, T (the
+ *              resident bases are upper-cased) reads 'N', takes no error and gets quality '!'.
+ *   errors     cycle j of mate m (0, 1): w = draw(x = i, y = m << 16 | j >> 1, tag 23), word = the high 64 bits of w for an odd
+ *              j, the low 64 for an even one; substitute iff (word >> 11) < err_thr[m][j]; the new base is index
+ *              (b + 1 + (((word & 0x7FF) * 3) >> 11)) & 3 in the order A, C, G, T, b the index of the read's base -- the three
+ *              alternatives come out 683 : 683 : 682 of 2048.
+ *   record     "@<prefix><i>_<n>_<s + 1>_<f>_<+|->/<1|2>\n<len bases>\n+\n<len quals>\n": n the 1-based number of the contig in
+ *              the context (the Fasta), + for strand 0; the four numbers are zero-padded decimals whose widths are fixed per run
+ *              by the largest values they can take: N - 1, the number of the last eligible contig, the longest eligible contig's
+ *              length, fmax.  stride = bytes of the prefix and the four widths + 2 len + 13.
+ *
+ *   msim_reads_setup        checks the tables (MSIM_ERR_ARG), finds the eligible contigs among the context's (MSIM_ERR_VALUE when
+ *                           there is none, MSIM_ERR_UNSUPPORTED for one of 4 GiB or more) and uploads everything; *stride,
+ *                           *n_eligible and *P describe the run.  The tables are copied.  msim_clear ends the setup.
+ *   msim_reads_render       records [first, first + count) of mate 0 or 1 (1: a paired setup only) into out[cap], count * stride
+ *                           bytes.  first + count may reach 2^32 where the index still fits its field; at most 1 GiB a call.
+ *   msim_reads_render_file  the same text through output channel `mate` to bytes [offset, offset + *written) of `fd`: queued as
+ *                           msim_fetch_sequence_framed_file queues a contig, BGZF mode included (msim_bgzf_open on the channel).
+ *   msim_reads_timing       the render kernel's time on the device (HIP events) since the context was made or msim_reset_stats,
+ *                           and how many reads of mate 1 / mate 2 rendered since the last setup hold only N (either may be NULL);
+ *                           waits for the context's stream.
+ *   msim_reads_release      waits for the channels and frees the run's tables.
+ * All of them: MSIM_ERR_HIP on a host-only context.
+ * msim_dbg_reads_render: the same text by a sequential host loop over the caller's bases -- contig k is
+ * bases[offsets[k], offsets[k + 1]), upper case -- no context, no GPU (error text: msim_last_error with a NULL context).
+ * out == NULL: *stride, *n_eligible and *P only.                                                                              */
+typedef struct msim_reads_params {
+    uint64_t key;
+    uint64_t n_reads;
+    uint32_t len, paired, frag_min, n_frag;
+    const uint64_t *frag_thr;
+    const uint64_t *err_thr;
+    const uint8_t *qual;
+    const char *prefix;
+} msim_reads_params;
+int msim_reads_setup(msim_ctx *ctx, const msim_reads_params *params, uint64_t *stride, uint64_t *n_eligible, uint64_t *P);
+int msim_reads_render(msim_ctx *ctx, int mate, uint64_t first, uint64_t count, uint8_t *out, uint64_t cap);
+int msim_reads_render_file(msim_ctx *ctx, int mate, uint64_t first, uint64_t count, int fd, uint64_t offset, uint64_t *written);
+int msim_reads_timing(msim_ctx *ctx, double *kernel_ms, uint64_t all_n[2]);
+int msim_reads_release(msim_ctx *ctx);
+int msim_dbg_reads_render(const msim_reads_params *params, const uint8_t *bases, const uint64_t *offsets, uint32_t n_contigs, int mate,
+                          uint64_t first, uint64_t count, uint8_t *out, uint64_t cap, uint64_t *stride, uint64_t *n_eligible,
+                          uint64_t *P);
+
 /* ---- test support: the SNP ti/tv transducer on the caller's words -------------------------------------------------- */
 /* Runs the three passes that turn CPython-stream words into SNP outcomes -- the map pass over whole blocks of
  * MSIM_SNP_BLOCK_WORDS words, the scan that finds where the K-th SNP's draws end, the outcome pass -- over `words` (raw,

@@ -88,6 +88,7 @@ struct FileIo;                        // file_io.hip: the output channels (threa
 struct VcfState;                      // vcf_parse.hip: the VCF text of a replay, its line starts and groups
 struct SpectrumState;                 // spectrum.hip: scratch, thresholds and kernel times of the context-dependent SNP engine
 struct CompareState;                  // compare.hip: the held tables of the compare mode, its result buffers and kernel time
+struct ReadsState;                    // reads.hip: the tables of a reads run, its event pairs and kernel time
 
 struct Ctx {
     int device = 0;
@@ -108,6 +109,7 @@ struct Ctx {
     VcfState *vcf = nullptr;          // vcf_parse.hip (msim_vcf_load .. msim_vcf_release)
     SpectrumState *spectrum = nullptr;    // spectrum.hip (made on first use)
     CompareState *compare = nullptr;      // compare.hip (made on first use)
+    ReadsState *reads = nullptr;          // reads.hip (made on first use)
     msim_params params{};
     bool have_params = false;
     std::vector<Contig> contigs;
@@ -266,6 +268,9 @@ void spectrum_reset_timing(Ctx *c);   // msim_reset_stats: msim_spectrum_timing 
 void compare_state_destroy(Ctx *c);   // compare.hip (the caller has waited for the context's streams)
 void compare_drop_all(Ctx *c);        // msim_clear: every held table goes with the contigs
 void compare_reset_timing(Ctx *c);    // msim_reset_stats: msim_cmp_timing counts from here
+void reads_state_destroy(Ctx *c);     // reads.hip (the caller has waited for the context's streams)
+void reads_forget(Ctx *c);            // msim_clear: the tables name contigs that are gone -- msim_reads_setup has to run again
+void reads_reset_timing(Ctx *c);      // msim_reset_stats: msim_reads_timing counts from here
 
 // plan_host.cpp
 struct HostPlan {

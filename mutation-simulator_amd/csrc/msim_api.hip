@@ -400,6 +400,7 @@ void msim_destroy(msim_ctx *p) {
     comm_destroy(c);
     spectrum_state_destroy(c);
     compare_state_destroy(c);
+    reads_state_destroy(c);
     fast_plan_destroy(c);
     gpu_plan_destroy(c->gpu);
     lap(3);
@@ -547,6 +548,7 @@ int msim_clear(msim_ctx *p) {
     }
     c->contigs.clear();
     compare_drop_all(c);                                   // (held tables belong to contigs that are gone)
+    reads_forget(c);
     c->text_kind = 0;
     return MSIM_OK;
 }
@@ -1715,6 +1717,7 @@ int msim_reset_stats(msim_ctx *p) {
     c->t = msim_timing{};
     spectrum_reset_timing(c);
     compare_reset_timing(c);
+    reads_reset_timing(c);
     return MSIM_OK;
 }
 

@@ -1,6 +1,7 @@
 """``mutation-simulator file {args,rmt,it}`` (reference __main__.py:34-111) on an MI355X, plus ``file vcf truth.vcf``
 (``--consensus``: any VCF, one haplotype of one sample), ``file profile calls.vcf`` (the VCF's SBS-96 spectrum, counted
-against the reference) and ``file compare truth.vcf calls.vcf`` (the calls scored against the truth)."""
+against the reference), ``file compare truth.vcf calls.vcf`` (the calls scored against the truth) and ``file reads -n N``
+(FASTQ reads drawn from the genome)."""
 from __future__ import annotations
 
 import json
@@ -10,7 +11,7 @@ from timeit import default_timer as timer
 
 from . import *  # noqa: F401,F403  (same style of namespace as the reference entry point)
 from ._ffi import MsimError, MsimUnsupported
-from .argument_parser import compare_refusal, ploidy_refusal, profile_refusal, spectrum_refusal
+from .argument_parser import compare_refusal, ploidy_refusal, profile_refusal, reads_refusal, spectrum_refusal
 from .spectrum import SpectrumError
 from .fasta_io import is_gzip
 
@@ -52,6 +53,10 @@ class CompareUnsupportedError(Exception):
     """The compare mode together with what it does not cover (argument_parser.compare_refusal)."""
 
 
+class ReadsUnsupportedError(Exception):
+    """The reads mode together with what it does not cover (argument_parser.reads_refusal)."""
+
+
 class CompressedInputUnsupportedError(Exception):
     """A gzip-compressed input together with what does not cover it (a sharded run)."""
 
@@ -74,6 +79,9 @@ def initialize(argv=None):
     refusal = compare_refusal(args)
     if refusal:
         exit_with_error(CompareUnsupportedError(refusal), args.no_color)
+    refusal = reads_refusal(args)
+    if refusal:
+        exit_with_error(ReadsUnsupportedError(refusal), args.no_color)
     refusal = ploidy_refusal(args)
     if refusal:
         exit_with_error(PloidyUnsupportedError(refusal), args.no_color)
@@ -114,7 +122,7 @@ def initialize(argv=None):
         args.genome_name = args.infile.name
         if fasta.compressed and args.infile.suffix.lower() in (".gz", ".bgz") and args.infile.stem:
             args.genome_name = args.infile.stem
-        if args.mode in ("vcf", "profile", "compare"):     # a replay, a profile and a comparison have no settings and draw nothing
+        if args.mode in ("vcf", "profile", "compare", "reads"):    # a replay, a profile, a comparison and the reads have no settings
             return args, fasta, None
         if args.mode == "args":
             sim = SimulationSettings.from_args(args, fasta, args.ignore_warnings)
@@ -204,6 +212,24 @@ def main(argv=None):
                 stats["cli_s"] = {"load_index": round(STAGES.get("load_index", 0.0), 4), "compare": round(timer() - loaded, 4)}
                 args.bench_json.write_text(json.dumps(stats, indent=1) + "\n")
         except (CompareError, VcfReplayError, MsimError, OSError, UnsupportedCompressionFormat, ValueError) as e:
+            exit_with_error(e, args.no_color)
+        if not args.quiet:
+            print_success(f"Mutation-Simulator finished in: {round(timer() - start, 4)}s", args.no_color)
+        return
+    if args.mode == "reads":                           # (--seed is the Philox key; --rng has no effect: no mutation engine runs)
+        from .reads import Reads, ReadsError
+        try:
+            reads = Reads(args, fasta)
+            try:
+                reads.run()
+            finally:
+                reads.close()
+            fasta.close()
+            if args.bench_json:
+                stats = dict(reads.stats)
+                stats["cli_s"] = {"load_index": round(STAGES.get("load_index", 0.0), 4), "reads": round(timer() - loaded, 4)}
+                args.bench_json.write_text(json.dumps(stats, indent=1) + "\n")
+        except (ReadsError, MsimError, OSError, UnsupportedCompressionFormat, ValueError) as e:
             exit_with_error(e, args.no_color)
         if not args.quiet:
             print_success(f"Mutation-Simulator finished in: {round(timer() - start, 4)}s", args.no_color)

@@ -51,6 +51,12 @@ class Params(C.Structure):           # msim_params
     _fields_ = [("block", C.c_int64 * 8), ("ti_lim", C.c_uint64)]
 
 
+class ReadsParams(C.Structure):      # msim_reads_params
+    _fields_ = [("key", C.c_uint64), ("n_reads", C.c_uint64), ("len", C.c_uint32), ("paired", C.c_uint32),
+                ("frag_min", C.c_uint32), ("n_frag", C.c_uint32), ("frag_thr", C.c_void_p), ("err_thr", C.c_void_p),
+                ("qual", C.c_void_p), ("prefix", C.c_char_p)]
+
+
 class PassItem(C.Structure):         # msim_pass_item
     _fields_ = [("contig", C.c_int32), ("flags", C.c_uint32), ("len", C.c_uint64), ("ranges", C.POINTER(Range)),
                 ("n_ranges", C.c_int32), ("rsv", C.c_int32)]
@@ -230,6 +236,13 @@ SYMBOLS = [
     ("msim_dbg_cmp_counts_regions", C.c_int, [_VP, C.c_uint64, _VP, C.c_uint64, _VP, C.c_uint64, _VP, _VP, C.c_uint64, _VP, C.c_uint64, _VP,
                                               C.c_int, C.c_uint32, C.c_uint32, _VP, _VP, _VP, C.c_uint32, _VP, _VP, _VP, _VP]),
     ("msim_bed_scan", C.c_int, [_VP, C.c_uint64, _VP, _VP, _VP, _U64P, _VP, _VP, _VP, _VP, _U64P]),
+    ("msim_reads_setup", C.c_int, [_VP, C.POINTER(ReadsParams), _U64P, _U64P, _U64P]),
+    ("msim_reads_render", C.c_int, [_VP, C.c_int, C.c_uint64, C.c_uint64, _VP, C.c_uint64]),
+    ("msim_reads_render_file", C.c_int, [_VP, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_uint64, _U64P]),
+    ("msim_reads_timing", C.c_int, [_VP, C.POINTER(C.c_double), _VP]),
+    ("msim_reads_release", C.c_int, [_VP]),
+    ("msim_dbg_reads_render", C.c_int, [C.POINTER(ReadsParams), _VP, _VP, C.c_uint32, C.c_int, C.c_uint64, C.c_uint64, _VP, C.c_uint64,
+                                        _U64P, _U64P, _U64P]),
     ("msim_stats", C.c_int, [_VP, C.POINTER(Timing)]),
     ("msim_reset_stats", C.c_int, [_VP]),
 ]
@@ -249,6 +262,8 @@ CMP_PHASE_COUNTS = 11    # msim.h: MSIM_CMP_PHASE_COUNTS, the values of msim_cmp
 SPECTRUM_TILE = 4096     # msim.h: MSIM_SPECTRUM_TILE, the bases one workgroup of the spectrum sampler takes
 SBS_CHANNELS, SBS_TALLIES = 96, 8    # msim.h: MSIM_SBS_CHANNELS, MSIM_SBS_TALLIES
 SBS_PASS = 1024          # msim.h: MSIM_SBS_PASS, the records one workgroup of the profile kernel takes per pass
+
+READS_MAX_LEN, READS_MAX_FRAG, READS_MAX_PREFIX = 512, 4096, 32      # msim.h: the limits of msim_reads_params
 
 _lib = None
 
@@ -341,6 +356,14 @@ def chain_tile() -> int:
     return int(fn())
 
 
+def reads_group(stride: int) -> int:
+    """Reads a workgroup of the render kernel takes at this record stride (reads.hip: reads_per_group): where the edge cases of
+    a chunk split lie (msim_dbg_reads_group: exported, not part of include/msim.h)."""
+    fn = load().msim_dbg_reads_group
+    fn.restype, fn.argtypes = C.c_uint32, [C.c_uint32]
+    return int(fn(int(stride)))
+
+
 def parse_cpulist(text: str) -> set:
     """A Linux cpulist ("0-63,128-191") as a set of ints."""
     out = set()
@@ -382,6 +405,49 @@ def warm_up_async(device: int = 0, pin: bool = False):
 
 def _ptr(a: np.ndarray):
     return C.c_void_p(a.ctypes.data)
+
+
+def reads_params(key: int, n_reads: int, length: int, paired: bool, frag_min: int, frag_thr, err_thr, qual, prefix: str):
+    """``msim_reads_params`` over the caller's tables: (the struct, the arrays it points into -- keep them while it is used)."""
+    frag_thr = np.ascontiguousarray(frag_thr, dtype=np.uint64).reshape(-1)
+    err_thr = np.ascontiguousarray(err_thr, dtype=np.uint64).reshape(-1)
+    qual = np.ascontiguousarray(qual, dtype=np.uint8).reshape(-1)
+    if err_thr.shape[0] != 2 * int(length) or qual.shape[0] != 2 * int(length):
+        raise MsimError("reads: err_thr and qual hold 2 x LEN entries")
+    p = ReadsParams()
+    p.key, p.n_reads, p.len, p.paired = int(key) & (2**64 - 1), int(n_reads), int(length), 1 if paired else 0
+    p.frag_min, p.n_frag = int(frag_min), int(frag_thr.shape[0])
+    p.frag_thr, p.err_thr, p.qual = frag_thr.ctypes.data, err_thr.ctypes.data, qual.ctypes.data
+    p.prefix = prefix.encode("utf-8", "replace")
+    return p, (frag_thr, err_thr, qual)
+
+
+def dbg_reads_render(params, contigs, mate: int, first: int, count: int):
+    """``msim_dbg_reads_render``: records [first, first + count) of ``mate`` by the library's sequential host loop over
+    ``contigs`` (a list of uint8 arrays, upper case): (text as bytes, stride, eligible contigs, P).  No context, no GPU."""
+    lib = load()
+    p, keep = params
+    offsets = np.zeros(len(contigs) + 1, dtype=np.uint64)
+    offsets[1:] = np.cumsum([len(x) for x in contigs], dtype=np.uint64)
+    bases = np.concatenate([np.asarray(x, dtype=np.uint8) for x in contigs]) if contigs else np.zeros(0, np.uint8)
+    bases = np.ascontiguousarray(bases)
+    stride, n_elig, P = C.c_uint64(), C.c_uint64(), C.c_uint64()
+
+    def call(out, cap):
+        rc = lib.msim_dbg_reads_render(C.byref(p), _ptr(bases), _ptr(offsets), len(contigs), int(mate), int(first), int(count), out, cap,
+                                       C.byref(stride), C.byref(n_elig), C.byref(P))
+        if rc != OK:
+            msg = lib.msim_last_error(None).decode()
+            err = ValueError(msg) if rc == ERR_VALUE else MsimUnsupported(msg) if rc == ERR_UNSUPPORTED else MsimError(f"libmsim error {rc}: {msg}")
+            if not isinstance(err, ValueError):
+                err.code = rc
+            raise err
+    call(None, 0)
+    out = np.empty(int(count) * stride.value, dtype=np.uint8)
+    if count:
+        call(_ptr(out), out.shape[0])
+    del keep
+    return out.tobytes(), stride.value, n_elig.value, P.value
 
 
 class Engine:
@@ -726,6 +792,38 @@ class Engine:
         a = C.c_double()
         self._check(self.lib.msim_sbs_timing(self.h, C.byref(a)))
         return a.value
+
+    # ------------------------------------------------------------------ reads (msim.h: FASTQ records from the resident genome)
+    def reads_setup(self, params) -> tuple:
+        """Check and upload the tables of a reads run (``reads_params``) over the context's contigs: (stride, eligible
+        contigs, P)."""
+        p, _keep = params
+        stride, n_elig, P = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.lib.msim_reads_setup(self.h, C.byref(p), C.byref(stride), C.byref(n_elig), C.byref(P)))
+        self._reads_stride = stride.value
+        return stride.value, n_elig.value, P.value
+
+    def reads_render(self, mate: int, first: int, count: int) -> bytes:
+        """Records [first, first + count) of mate 0 / 1 as bytes."""
+        out = np.empty(int(count) * self._reads_stride, dtype=np.uint8)
+        self._check(self.lib.msim_reads_render(self.h, int(mate), int(first), int(count), _ptr(out), out.shape[0]))
+        return out.tobytes()
+
+    def reads_render_to_file(self, mate: int, first: int, count: int, fd: int, offset: int) -> int:
+        """The same records queued for bytes [offset, ...) of ``fd`` on output channel ``mate``; returns their byte count."""
+        n = C.c_uint64()
+        self._check(self.lib.msim_reads_render_file(self.h, int(mate), int(first), int(count), int(fd), int(offset), C.byref(n)))
+        return n.value
+
+    def reads_timing(self) -> tuple:
+        """(render kernel milliseconds since ``reset_stats``, reads of mate 1 / mate 2 that hold only N since the last setup)."""
+        ms = C.c_double()
+        all_n = np.zeros(2, dtype=np.uint64)
+        self._check(self.lib.msim_reads_timing(self.h, C.byref(ms), _ptr(all_n)))
+        return ms.value, (int(all_n[0]), int(all_n[1]))
+
+    def reads_release(self):
+        self._check(self.lib.msim_reads_release(self.h))
 
     # ------------------------------------------------------------------ compare (msim.h: a truth table against a calls table)
     def cmp_hold(self, contig: int):

@@ -16,7 +16,12 @@ a usage error without ``--diploid`` or with ``--blocks``; ``--regions FILE`` sco
 leftmost placement, else the position -- lies inside the BED's intervals, and the repeatable ``--stratify NAME=FILE`` adds a
 genome-wide table per BED, inside ``--regions`` where both are given; NAME is non-empty, without tab, blank, ``=`` or ``#``, and
 distinct; both are usage errors together with ``--phased``, whose phase table would silently stay genome-wide, and go with
-``--diploid``, ``--blocks``, ``--exact``, ``--per-contig`` and ``--list``; ``compare_refusal`` words what it does not cover).
+``--diploid``, ``--blocks``, ``--exact``, ``--per-contig`` and ``--list``; ``compare_refusal`` words what it does not cover), and the
+``reads`` sub-command (``reads.py``: FASTQ reads drawn from the genome on the GPU, ``(-n N | --coverage X) [-l LEN] [--paired
+--frag-mean M --frag-sd SD] [--error-rate A[:B]] [--prefix P]``; it writes ``<outbase>_ms.fq`` (``args.outfastq``) or, with
+``--paired``, ``<outbase>_ms_1.fq`` and ``<outbase>_ms_2.fq`` (``outfastq_1`` / ``outfastq_2``), ``.gz`` appended under ``--bgzip``;
+``--frag-*`` without ``--paired``, ``--paired`` without both, SD > 511 and M + 4 SD < LEN are usage errors; ``reads_refusal`` words
+what it does not cover).
 
 ``--ploidy 2 [--het F]`` (``args`` / ``rmt``) writes two haplotype Fastas, ``<outbase>_ms_h1<suffix>`` and ``<outbase>_ms_h2<suffix>``
 (``args.outfasta_h1`` / ``outfasta_h2``; ``<outbase>_ms<suffix>`` is not written), one phased ``<outbase>_ms.vcf`` and, with ``--chain``,
@@ -65,6 +70,12 @@ def add_outfile_names(args: Namespace) -> Namespace:
         args.outcompare = args.outfasta.with_suffix(".compare.tsv")
         args.outcompare_records = args.outfasta.with_suffix(".compare.records.tsv")
         args.outcompare_phase = args.outfasta.with_suffix(".compare.phase.tsv")
+    if getattr(args, "mode", None) == "reads":
+        gz = ".gz" if getattr(args, "bgzip", False) else ""
+        stem = args.outfasta.stem
+        args.outfastq = args.outfasta.with_name(f"{stem}.fq{gz}")
+        args.outfastq_1 = args.outfasta.with_name(f"{stem}_1.fq{gz}")
+        args.outfastq_2 = args.outfasta.with_name(f"{stem}_2.fq{gz}")
     if getattr(args, "ploidy", 1) == 2:           # a diploid run: a Fasta (and a chain) per haplotype, ONE phased VCF
         for h in ("h1", "h2"):
             fa = args.outfasta.with_stem(f"{args.outfasta.stem}_{h}")
@@ -244,7 +255,44 @@ def build_parser() -> ArgumentParser:
                        help="Repeat the table per contig behind the genome-wide one")
     p_cmp.add_argument("--list", action="store_true", default=False, dest="list_records",
                        help="Also write <outbase>_ms.compare.records.tsv: one line per unmatched record")
+
+    p_reads = sub.add_parser("reads", help="Draw FASTQ reads from the genome on the GPU: single-end, or pairs from fragments of "
+                                           "normally distributed length, with a per-cycle substitution error ramp")
+    p_reads.add_argument("-n", "--reads", type=int, default=None, dest="n_reads", metavar="N",
+                         help="Number of reads (pairs with --paired), 1 to 2^32 - 1. One of -n and --coverage is needed")
+    p_reads.add_argument("--coverage", type=float, default=None, metavar="X",
+                         help="Number of reads from the coverage: N = floor(X * G / (LEN * mates)), G the bases of the contigs "
+                              "long enough to hold the longest fragment")
+    p_reads.add_argument("-l", "--length", type=int, default=150, metavar="LEN", help="Read length, 1 to 512. Default = 150")
+    p_reads.add_argument("--paired", action="store_true", default=False,
+                         help="Draw pairs: mate 1 from the fragment's start, mate 2 from its end off the other strand. Needs "
+                              "--frag-mean and --frag-sd; writes <outbase>_ms_1.fq and <outbase>_ms_2.fq")
+    p_reads.add_argument("--frag-mean", type=int, default=None, dest="frag_mean", metavar="M",
+                         help="With --paired: mean fragment length")
+    p_reads.add_argument("--frag-sd", type=int, default=None, dest="frag_sd", metavar="SD",
+                         help="With --paired: standard deviation of the fragment length, 0 to 511; lengths beyond M +- 4 SD (and "
+                              "below LEN) are not drawn")
+    p_reads.add_argument("--error-rate", default="0.001:0.01", dest="error_rate", metavar="A[:B]",
+                         help="Substitution probability per cycle, linear from A at the first cycle to B at the last; a single "
+                              "value is a flat rate. Default = 0.001:0.01")
+    p_reads.add_argument("--prefix", default="r", metavar="P",
+                         help="Prefix of the read names: letters, digits and ._- only, at most 32 bytes. Default = 'r'")
     return parser
+
+
+def reads_refusal(args: Namespace):
+    """What the ``reads`` mode does not cover, as the message to refuse it with; None: the run can go ahead (or is no reads
+    run).  ``--rng`` has no effect: no generator of the mutation engines is touched."""
+    if args.mode != "reads":
+        return None
+    if getattr(args, "ploidy", 1) == 2:
+        return ("--ploidy 2 does not apply to the reads mode (it samples one genome: run reads on the _h1 and the _h2 Fasta "
+                "with two prefixes)")
+    if getattr(args, "chain", False):
+        return "--chain does not apply to the reads mode (nothing is applied: there is no mutated genome to lift over to)"
+    if (args.gpus or 1) > 1:
+        return "the reads mode needs a single-GPU run (--gpus 1)"
+    return None
 
 
 def compare_refusal(args: Namespace):
@@ -373,6 +421,31 @@ def get_args(argv=None) -> Namespace:
                 parser.error(f"--stratify names must be distinct: {name!r} is given twice")
             strata.append((name, Path(path)))
         args.stratify = strata
+    if args.mode == "reads":
+        from .reads import MAX_LEN, MAX_SD, parse_error_rate, prefix_refusal, ReadsError
+        if (args.n_reads is None) == (args.coverage is None):
+            parser.error("reads needs exactly one of -n N and --coverage X")
+        if args.n_reads is not None and not 1 <= args.n_reads < 2**32:
+            parser.error("-n must lie in 1..2^32 - 1")
+        if args.coverage is not None and not 0.0 < args.coverage < float("inf"):
+            parser.error("--coverage must be a positive number")
+        if not 1 <= args.length <= MAX_LEN:
+            parser.error(f"-l must lie in 1..{MAX_LEN}")
+        if not args.paired and (args.frag_mean is not None or args.frag_sd is not None):
+            parser.error("--frag-mean and --frag-sd need --paired")
+        if args.paired:
+            if args.frag_mean is None or args.frag_sd is None:
+                parser.error("--paired needs --frag-mean and --frag-sd")
+            if not 0 <= args.frag_sd <= MAX_SD:
+                parser.error(f"--frag-sd must lie in 0..{MAX_SD}")
+            if args.frag_mean + 4 * args.frag_sd < args.length:
+                parser.error("--frag-mean + 4 --frag-sd lies below the read length: no fragment holds a read")
+        try:
+            parse_error_rate(args.error_rate)
+        except ReadsError as e:
+            parser.error(str(e))
+        if prefix_refusal(args.prefix):
+            parser.error(prefix_refusal(args.prefix))
     if args.quiet:
         args.ignore_warnings = True
         args.no_progress = True
