@@ -15,7 +15,6 @@
 //            the measure of what blocks of different lengths in one wave cost (msim_dbg_cmp_blocks_split).
 // Both kernels count into lane-private bins (lane_hist.h).  Every index is checked against its table's size, every base read
 // against L, every pool read against the pool (cmp_blocks.h), every descriptor store against the descriptors' allocation.
-#include <algorithm>
 
 #include "cmp_blocks.h"
 #include "ctx.h"
@@ -112,8 +111,7 @@ int blocks_enqueue(Ctx *c, hipStream_t stream, const uint8_t *g, uint64_t L, con
                    uint8_t *fb, uint32_t gap, blk::Desc *desc, uint64_t cap, unsigned long long *out, hipEvent_t between) {
     const uint64_t total = A.n + B.n;
     if (!total) return MSIM_OK;
-    const uint64_t n_pass = (total + LANES - 1) / LANES;
-    const dim3 grid((unsigned)std::min<uint64_t>(n_pass, BLK_MAX_BLOCKS));
+    const auto [n_pass, grid] = pass_grid(total, LANES, BLK_MAX_BLOCKS);
     unsigned long long *n_desc = out + blk::PASS_COUNT_AT;
     hipLaunchKernelGGL(k_blk_scan, grid, dim3(LANES), 0, stream, A, B, (const uint8_t *)fa, (const uint8_t *)fb, gap, n_pass, desc, cap, n_desc, out);
     MSIM_HIP(c, hipGetLastError());

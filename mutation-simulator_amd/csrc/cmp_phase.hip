@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "cmp_phase.h"
+#include "counter_trip.h"
 #include "ctx.h"
 #include "scan_kernels.h"
 #include "vcf_parse.h"
@@ -53,9 +54,7 @@ struct PhaseState {
     Scratch<uint2> d_key;
     Scratch<uint8_t> d_orient;
     Scratch<phase::Scan> d_agg, d_pre;
-    Scratch<unsigned long long> d_out;         // OUT_WORDS counters
-    Pinned<unsigned long long> h_out;
-    EventPair tm;
+    CounterTrip out;                           // PHASE_OUT_WORDS counters; its events time the word join as well
     double kernel_ms = 0;
 };
 
@@ -66,7 +65,7 @@ constexpr uint32_t TILE = MSIM_CMP_PHASE_TILE;
 static_assert(LANES == 256, "the kernels are written for four waves a workgroup");
 static_assert(sizeof(msim_record) == sizeof(uint4), "a record is one 16-byte load");
 // the device's counters: phase::C_* (C_ASSESSED is left to the host), the mark's three tallies behind them
-constexpr uint32_t OUT_MARK = phase::COUNTS, OUT_WORDS = 16;
+constexpr uint32_t OUT_MARK = phase::COUNTS, PHASE_OUT_WORDS = 16;
 
 // the workgroup's sums of K values a lane, in every lane (two barriers)
 template <int K>
@@ -309,32 +308,15 @@ unsigned tiles_of(uint64_t n) { return (unsigned)((n + TILE - 1) / TILE); }
 
 int state_of(Ctx *c, PhaseState **out) {
     PhaseState **slot;
-    const int rc = compare_phase_slot(c, &slot);
-    if (rc) return rc;
-    if (!*slot) {                                          // (the slot is filled once the state is whole)
-        PhaseState *P = new PhaseState;
-        hipError_t e = dev_alloc(P->d_out, OUT_WORDS * sizeof(unsigned long long));
-        if (e == hipSuccess) e = pin_alloc(P->h_out, OUT_WORDS * sizeof(unsigned long long));
-        if (e == hipSuccess) e = P->tm.create();
-        if (e != hipSuccess) {
-            phase_state_destroy(P);
-            return hip_fail(c, e, "the phase pass's result buffers and events");
-        }
-        *slot = P;
-    }
-    *out = *slot;
-    return MSIM_OK;
+    int rc = compare_phase_slot(c, &slot);
+    if (!rc) rc = lazy_state(c, slot, PHASE_OUT_WORDS, "the phase pass's result buffers and events");
+    if (!rc) *out = *slot;
+    return rc;
 }
 
 PhaseContig &contig_of(PhaseState *P, int contig) {
     if (P->contigs.size() <= (size_t)contig) P->contigs.resize((size_t)contig + 1);
     return P->contigs[(size_t)contig];
-}
-
-// exactly `bytes`, whatever the block held (contents are not kept)
-hipError_t dev_exact(DevBlock &b, size_t bytes) {
-    const hipError_t e = b.release();
-    return e != hipSuccess || !bytes ? e : dev_alloc(b, bytes);
 }
 
 const char *side_refusal(int side) { return side != MSIM_CMP_TRUTH && side != MSIM_CMP_CALLS ? "unknown side (MSIM_CMP_TRUTH, MSIM_CMP_CALLS)" : nullptr; }
@@ -345,21 +327,13 @@ int device_contig(Ctx *c, int contig, Contig **g) {
     return ctx_device_contig(c, contig, false, g);
 }
 
-// the counters back on the host (the caller's launches are on the context's stream), the kernels' time added
-int fetch_out(Ctx *c, PhaseState *P) {
-    MSIM_HIP(c, P->tm.end(c->stream));
-    MSIM_HIP(c, hipMemcpyAsync(P->h_out.p(), P->d_out.p(), OUT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    MSIM_HIP(c, wait_stream(c->stream));
-    return P->tm.add_elapsed(c, &P->kernel_ms);
-}
-
 int counts_device(Ctx *c, PhaseState *P, const Contig &g, PhaseContig &pc, const DipView &a, const DipView &b, uint32_t flags, uint64_t *out) {
     const uint64_t na = a.t.n, nb = b.t.n;
     pc.counted = false;
     if (!na && !nb) { pc.n_state = 0; pc.counted = true; return MSIM_OK; }
     const unsigned tiles_a = tiles_of(na);
     int rc;
-    if (na > pc.d_state.cap) MSIM_HIP(c, dev_exact(pc.d_state, (size_t)na));
+    MSIM_HIP(c, dev_at_least(pc.d_state, (size_t)na));
     if ((rc = dev_reserve(c, P->d_pkey, (size_t)std::max<uint64_t>(na, 1) * sizeof(uint32_t))) ||
         (rc = dev_reserve(c, P->d_src, (size_t)std::max<uint64_t>(na, 1) * sizeof(uint32_t))) ||
         (rc = dev_reserve(c, P->d_key, (size_t)std::max<uint64_t>(na, 1) * sizeof(uint2))) ||
@@ -369,10 +343,9 @@ int counts_device(Ctx *c, PhaseState *P, const Contig &g, PhaseContig &pc, const
         (rc = dev_reserve(c, P->d_pre, ((size_t)tiles_a + 1) * sizeof(phase::Scan))))
         return rc;
     const uint32_t *w_a = pc.side[MSIM_CMP_TRUTH].d_words.p(), *w_b = pc.side[MSIM_CMP_CALLS].d_words.p();
-    MSIM_HIP(c, hipMemsetAsync(P->d_out.p(), 0, OUT_WORDS * sizeof(unsigned long long), c->stream));
-    MSIM_HIP(c, P->tm.begin(c->stream));
+    if ((rc = P->out.begin(c, PHASE_OUT_WORDS))) return rc;
     hipLaunchKernelGGL(k_phase_pairs, dim3(tiles_of(std::max(na, nb))), dim3(LANES), 0, c->stream, g.d_in.p() + PAD, g.len, a.t, b.t, a.gt, b.gt, a.flag, w_a,
-                       w_b, flags & MSIM_CMP_EXACT, pc.d_state.p(), P->d_pkey.p(), P->d_tile.p(), tiles_a, P->d_out.p());
+                       w_b, flags & MSIM_CMP_EXACT, pc.d_state.p(), P->d_pkey.p(), P->d_tile.p(), tiles_a, P->out.d.p());
     MSIM_HIP(c, hipGetLastError());
     if (na) {
         const uint32_t *n_pairs = P->d_tile.p() + tiles_a;
@@ -383,11 +356,11 @@ int counts_device(Ctx *c, PhaseState *P, const Contig &g, PhaseContig &pc, const
                            P->d_agg.p());
         hipLaunchKernelGGL(k_phase_tilescan, dim3(1), dim3(LANES), 0, c->stream, (const phase::Scan *)P->d_agg.p(), tiles_a, P->d_pre.p());
         hipLaunchKernelGGL(k_phase_tally, dim3(tiles_a), dim3(LANES), 0, c->stream, (const uint2 *)P->d_key.p(), (const uint8_t *)P->d_orient.p(),
-                           (const uint32_t *)P->d_src.p(), n_pairs, na, (const phase::Scan *)P->d_pre.p(), pc.d_state.p(), na, P->d_out.p());
+                           (const uint32_t *)P->d_src.p(), n_pairs, na, (const phase::Scan *)P->d_pre.p(), pc.d_state.p(), na, P->out.d.p());
         MSIM_HIP(c, hipGetLastError());
     }
-    if ((rc = fetch_out(c, P))) return rc;
-    const unsigned long long *h = P->h_out.p();
+    if ((rc = P->out.finish(c, &P->kernel_ms))) return rc;
+    const unsigned long long *h = P->out.h.p();
     if (h[phase::C_PAIRS] > na || h[phase::C_BLOCKS] > h[phase::C_PAIRS])
         return fail(c, MSIM_ERR_HIP, "internal: the phase pass counted more pairs than the truth holds records");
     for (uint32_t k = 0; k < phase::COUNTS; k++) out[k] = h[k];
@@ -415,11 +388,7 @@ void phase_drop(PhaseState *P, int contig) {
     else if ((size_t)contig < P->contigs.size()) P->contigs[(size_t)contig] = PhaseContig{};
 }
 
-void phase_state_destroy(PhaseState *P) {
-    if (!P) return;
-    P->tm.destroy();
-    delete P;
-}
+void phase_state_destroy(PhaseState *P) { delete P; }
 
 void phase_reset_timing(PhaseState *P) {
     if (P) P->kernel_ms = 0;
@@ -449,13 +418,12 @@ int msim_cmp_phase_mark(msim_ctx *p, int contig, int side, int haplotype, uint64
     m = Marks{};
     if (v.n_rec) {
         MSIM_HIP(c, dev_alloc(m.d, (size_t)v.n_rec * sizeof(Mark)));
-        MSIM_HIP(c, hipMemsetAsync(P->d_out.p(), 0, OUT_WORDS * sizeof(unsigned long long), c->stream));
-        MSIM_HIP(c, P->tm.begin(c->stream));
+        if ((rc = P->out.begin(c, PHASE_OUT_WORDS))) { m = Marks{}; return rc; }
         hipLaunchKernelGGL(k_cons_phase, dim3(tiles_of(v.n_rec)), dim3(LANES), 0, c->stream, v.text, v.ls, v.tabcum, v.recline,
-                           (const msim_record *)g->d_recs.p(), v.n_rec, v.first, v.n_lines, v.nf0, v.sample, m.d.p(), P->d_out.p());
+                           (const msim_record *)g->d_recs.p(), v.n_rec, v.first, v.n_lines, v.nf0, v.sample, m.d.p(), P->out.d.p());
         MSIM_HIP(c, hipGetLastError());
-        if ((rc = fetch_out(c, P))) { m = Marks{}; return rc; }
-        for (int k = 0; k < 3; k++) tally[k] = P->h_out.p()[OUT_MARK + k];
+        if ((rc = P->out.finish(c, &P->kernel_ms))) { m = Marks{}; return rc; }
+        for (int k = 0; k < 3; k++) tally[k] = P->out.h.p()[OUT_MARK + k];
     }
     m.n = v.n_rec;
     m.have = true;
@@ -482,13 +450,13 @@ int msim_cmp_phase_join(msim_ctx *p, int contig, int side) {
     s.have_words = false;
     MSIM_HIP(c, dev_exact(s.d_words, (size_t)d.t.n * sizeof(uint32_t)));
     if (d.t.n) {
-        MSIM_HIP(c, P->tm.begin(c->stream));
+        MSIM_HIP(c, P->out.tm.begin(c->stream));
         hipLaunchKernelGGL(k_phase_join, dim3(tiles_of(d.t.n)), dim3(LANES), 0, c->stream, d.t.recs, d.gt, d.t.n, (const Mark *)s.marks[0].d.p(), s.marks[0].n,
                            (const Mark *)s.marks[1].d.p(), s.marks[1].n, s.d_words.p());
         MSIM_HIP(c, hipGetLastError());
-        MSIM_HIP(c, P->tm.end(c->stream));
+        MSIM_HIP(c, P->out.tm.end(c->stream));
         MSIM_HIP(c, wait_stream(c->stream));
-        if ((rc = P->tm.add_elapsed(c, &P->kernel_ms))) return rc;
+        if ((rc = P->out.tm.add_elapsed(c, &P->kernel_ms))) return rc;
     }
     s.marks[0] = Marks{};
     s.marks[1] = Marks{};
@@ -605,7 +573,7 @@ int msim_dbg_cmp_phase_copy_floor(msim_ctx *p, int contig, double *ms) {
                                 // written and read again: partner words + dense keys + dense records (4 + 8 + 4 bytes a truth record:
                                 // its 16-byte record stands for them), orientation + state bytes (its genotype and flag bytes)
                                 {a.t.recs, na * sizeof(msim_record)}, {a.gt, na}, {a.flag, na}};
-    return copy_floor(c, P->tm, src, 10, ms);
+    return copy_floor(c, P->out.tm, src, 10, ms);
 }
 
 // ---- sequential host restatement: no context, no GPU ----------------------------------------------------------------------------

@@ -9,12 +9,12 @@
 //            match's first walk tally, which a tally never uses).  Lane-private bins and slots as in compare.hip.
 // Both grids are capped and stride over the passes.  The bases are read inside [0, L) only and the pools inside their lengths
 // (compare.h: walkable), starts / ends inside [0, n) (cmp_regions.h: inside); every record index is checked against its table.
-#include <algorithm>
 #include <cstring>
 #include <string>
 #include <vector>
 
 #include "cmp_regions.h"
+#include "counter_trip.h"
 #include "ctx.h"
 #include "lane_hist.h"
 
@@ -38,25 +38,22 @@ struct RegionContig {
 
 struct RegionState {
     std::vector<RegionContig> contigs;         // by contig index
-    Scratch<unsigned long long> d_out;         // HIST_SLOTS x (the truth's counters, the calls' counters)
-    Pinned<unsigned long long> h_out;
-    EventPair tm;
+    CounterTrip out;                           // HIST_SLOTS x (the truth's counters, the calls' counters); its events time the mark too
     double kernel_ms = 0;
 };
 
 namespace {
 
-constexpr int LANES = 256;
+constexpr int LANES = cmp::LANES;
 constexpr uint32_t PASS = LANES;                           // records of a workgroup's pass: one a lane
 static_assert(PASS == MSIM_CMP_PASS, "msim.h and cmp_regions.hip must agree on the pass");
 constexpr unsigned MAX_BLOCKS = 2048;                      // more passes than that stride (compare.hip: CMP_MAX_BLOCKS)
 static_assert(sizeof(msim_record) == sizeof(uint4), "a record is one 16-byte load");
 constexpr uint32_t KNOWN_FLAGS = MSIM_CMP_EXACT | MSIM_CMP_DIPLOID;
 
-// compare.hip's layout: 2 x BINS words a slot, the truth's counters in front of the calls'.  A table has fewer than 2^31 records,
-// the grid strides beyond MAX_BLOCKS passes, a workgroup takes at most 4096 of them and a lane adds once per pass: 16 bits hold it.
-template <int OUTCOMES> using RgnHist = LaneHist<(int)cmp::Score<OUTCOMES>::BINS, LANES, 2>;
-template <int OUTCOMES> constexpr size_t OUT_WORDS = (size_t)HIST_SLOTS * 2 * cmp::Score<OUTCOMES>::BINS;
+// compare.hip's layout (compare.h: Hist, OUT_WORDS, slot_of).  A table has fewer than 2^31 records, the grid strides beyond
+// MAX_BLOCKS passes, a workgroup takes at most 4096 of them and a lane adds once per pass: 16 bits hold it.
+using cmp::OUT_WORDS;
 template <int OUTCOMES> constexpr uint32_t OUTSIDE = cmp::Score<OUTCOMES>::TALLIES;      // the "outside" counter's bin
 
 __global__ __launch_bounds__(LANES) void k_region_mark(const uint8_t *__restrict__ g, uint64_t L, cmp::Table T, uint32_t exact, uint64_t n_pass,
@@ -72,7 +69,7 @@ template <int OUTCOMES>
 __global__ __launch_bounds__(LANES) void k_region_tally(const msim_record *__restrict__ recs, uint64_t n_rec, uint64_t n_pass,
                                                         const uint8_t *__restrict__ flag, const uint8_t *__restrict__ mark, uint32_t mask,
                                                         unsigned long long *__restrict__ out) {
-    __shared__ RgnHist<OUTCOMES> hist;
+    __shared__ cmp::Hist<OUTCOMES> hist;
     hist.zero();
     for (uint64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
         const uint64_t i = pass * PASS + threadIdx.x;
@@ -83,51 +80,29 @@ __global__ __launch_bounds__(LANES) void k_region_tally(const msim_record *__res
         const bool in = (mark[i] & mask) == mask && f < (uint32_t)OUTCOMES;
         hist.add(in ? cmp::counter_of<OUTCOMES>(r, f) : OUTSIDE<OUTCOMES>, 1u);
     }
-    hist.flush(out + (blockIdx.x & (HIST_SLOTS - 1)) * 2 * cmp::Score<OUTCOMES>::BINS);
+    hist.flush(cmp::slot_of<OUTCOMES>(out));
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
 // a[]: the truth's counters of the records inside (per cell its outcomes), b[]: the calls'; each side's outside counter behind them
 template <int OUTCOMES>
 void finish(const unsigned long long *a, const unsigned long long *b, uint64_t *counts, uint64_t outside[2]) {
-    for (uint32_t cell = 0; cell < cmp::CELLS; cell++) {
-        uint32_t type, bin;
-        cmp::cell_index(cell, &type, &bin);
-        uint64_t *dst = counts + ((size_t)type * MSIM_CMP_BINS + bin) * 2 * OUTCOMES;
-        for (int k = 0; k < OUTCOMES; k++) { dst[k] += a[OUTCOMES * cell + k]; dst[OUTCOMES + k] += b[OUTCOMES * cell + k]; }
-    }
+    cmp::fold_cells<OUTCOMES>(a, b, counts);
     outside[0] += a[OUTSIDE<OUTCOMES>];
     outside[1] += b[OUTSIDE<OUTCOMES>];
 }
 
 int state_of(Ctx *c, RegionState **out) {
     RegionState **slot;
-    const int rc = compare_region_slot(c, &slot);
-    if (rc) return rc;
-    if (!*slot) {                                          // (the slot is filled once the state is whole)
-        RegionState *R = new RegionState;
-        hipError_t e = dev_alloc(R->d_out, OUT_WORDS<3> * sizeof(unsigned long long));   // (the larger of the two layouts)
-        if (e == hipSuccess) e = pin_alloc(R->h_out, OUT_WORDS<3> * sizeof(unsigned long long));
-        if (e == hipSuccess) e = R->tm.create();
-        if (e != hipSuccess) {
-            regions_state_destroy(R);
-            return hip_fail(c, e, "the region pass's result buffers and events");
-        }
-        *slot = R;
-    }
-    *out = *slot;
-    return MSIM_OK;
+    int rc = compare_region_slot(c, &slot);
+    if (!rc) rc = lazy_state(c, slot, OUT_WORDS<3>, "the region pass's result buffers and events");   // (the larger of the two layouts)
+    if (!rc) *out = *slot;
+    return rc;
 }
 
 RegionContig &contig_of(RegionState *R, int contig) {
     if (R->contigs.size() <= (size_t)contig) R->contigs.resize((size_t)contig + 1);
     return R->contigs[(size_t)contig];
-}
-
-// exactly `bytes`, whatever the block held (contents are not kept)
-hipError_t dev_exact(DevBlock &b, size_t bytes) {
-    const hipError_t e = b.release();
-    return e != hipSuccess || !bytes ? e : dev_alloc(b, bytes);
 }
 
 // a device call's prologue: a GPU context, known flags, a contig of that index (held / current: planned), its tables
@@ -154,24 +129,21 @@ const char *marks_refusal(const RegionContig &rc, const RegionTables &t, uint32_
 
 template <int OUTCOMES>
 int counts_device(Ctx *c, RegionState *R, const RegionContig &rc, const RegionTables &t, uint32_t mask, uint64_t *counts, uint64_t outside[2]) {
-    constexpr size_t BINS = cmp::Score<OUTCOMES>::BINS, OUT_BYTES = OUT_WORDS<OUTCOMES> * sizeof(unsigned long long);
+    constexpr size_t BINS = cmp::Score<OUTCOMES>::BINS;
     if (!t.t[0].n && !t.t[1].n) return MSIM_OK;
-    MSIM_HIP(c, hipMemsetAsync(R->d_out.p(), 0, OUT_BYTES, c->stream));
-    MSIM_HIP(c, R->tm.begin(c->stream));
+    int rc_trip = R->out.begin(c, OUT_WORDS<OUTCOMES>);
+    if (rc_trip) return rc_trip;
     for (int s = 0; s < 2; s++) {
-        const uint64_t n = t.t[s].n, n_pass = (n + PASS - 1) / PASS;
+        const uint64_t n = t.t[s].n;
         if (!n) continue;
-        hipLaunchKernelGGL(k_region_tally<OUTCOMES>, dim3((unsigned)std::min<uint64_t>(n_pass, MAX_BLOCKS)), dim3(LANES), 0, c->stream, t.t[s].recs, n,
-                           n_pass, t.flag[s], (const uint8_t *)rc.d_mark[s].p(), mask, R->d_out.p() + (s ? BINS : 0));
+        const PassGrid pg = pass_grid(n, PASS, MAX_BLOCKS);
+        hipLaunchKernelGGL(k_region_tally<OUTCOMES>, pg.grid, dim3(LANES), 0, c->stream, t.t[s].recs, n, pg.n_pass, t.flag[s],
+                           (const uint8_t *)rc.d_mark[s].p(), mask, R->out.d.p() + (s ? BINS : 0));
         MSIM_HIP(c, hipGetLastError());
     }
-    MSIM_HIP(c, R->tm.end(c->stream));                      // (in front of the copy: the kernels alone)
-    MSIM_HIP(c, hipMemcpyAsync(R->h_out.p(), R->d_out.p(), OUT_BYTES, hipMemcpyDeviceToHost, c->stream));
-    MSIM_HIP(c, wait_stream(c->stream));
-    const int rc_tm = R->tm.add_elapsed(c, &R->kernel_ms);
-    if (rc_tm) return rc_tm;
+    if ((rc_trip = R->out.finish(c, &R->kernel_ms))) return rc_trip;
     unsigned long long bins[2 * BINS];
-    hist_sum_slots(R->h_out.p(), 2 * BINS, bins, 2 * BINS);
+    hist_sum_slots(R->out.h.p(), 2 * BINS, bins, 2 * BINS);
     finish<OUTCOMES>(bins, bins + BINS, counts, outside);
     return MSIM_OK;
 }
@@ -202,11 +174,7 @@ void regions_drop(RegionState *R, int contig) {
     else if ((size_t)contig < R->contigs.size()) R->contigs[(size_t)contig] = RegionContig{};
 }
 
-void regions_state_destroy(RegionState *R) {
-    if (!R) return;
-    R->tm.destroy();
-    delete R;
-}
+void regions_state_destroy(RegionState *R) { delete R; }
 
 void regions_reset_timing(RegionState *R) {
     if (R) R->kernel_ms = 0;
@@ -281,20 +249,20 @@ int msim_cmp_regions_mark(msim_ctx *p, int contig, uint32_t flags) {
         sets.resident |= 1u << s;
     }
     for (int s = 0; s < 2; s++)
-        if (t.t[s].n > rcg.d_mark[s].cap) MSIM_HIP(c, dev_exact(rcg.d_mark[s], (size_t)t.t[s].n));
+        MSIM_HIP(c, dev_at_least(rcg.d_mark[s], (size_t)t.t[s].n));
     TraceRange tr("msim compare regions mark");
     if (t.t[0].n || t.t[1].n) {
-        MSIM_HIP(c, R->tm.begin(c->stream));
+        MSIM_HIP(c, R->out.tm.begin(c->stream));
         for (int s = 0; s < 2; s++) {
-            const uint64_t n = t.t[s].n, n_pass = (n + PASS - 1) / PASS;
-            if (!n) continue;
-            hipLaunchKernelGGL(k_region_mark, dim3((unsigned)std::min<uint64_t>(n_pass, MAX_BLOCKS)), dim3(LANES), 0, c->stream, g->d_in.p() + PAD, g->len,
-                               t.t[s], flags & MSIM_CMP_EXACT, n_pass, sets, rcg.d_mark[s].p());
+            if (!t.t[s].n) continue;
+            const PassGrid pg = pass_grid(t.t[s].n, PASS, MAX_BLOCKS);
+            hipLaunchKernelGGL(k_region_mark, pg.grid, dim3(LANES), 0, c->stream, g->d_in.p() + PAD, g->len, t.t[s], flags & MSIM_CMP_EXACT, pg.n_pass,
+                               sets, rcg.d_mark[s].p());
             MSIM_HIP(c, hipGetLastError());
         }
-        MSIM_HIP(c, R->tm.end(c->stream));
+        MSIM_HIP(c, R->out.tm.end(c->stream));
         MSIM_HIP(c, wait_stream(c->stream));
-        if ((rc = R->tm.add_elapsed(c, &R->kernel_ms))) return rc;
+        if ((rc = R->out.tm.add_elapsed(c, &R->kernel_ms))) return rc;
     }
     rcg.n_mark[0] = t.t[0].n;
     rcg.n_mark[1] = t.t[1].n;

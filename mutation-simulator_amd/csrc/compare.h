@@ -22,6 +22,7 @@
 
 #include "../../include/msim.h"
 #include "fast_math.h"
+#include "lane_hist.h"
 
 namespace msim {
 namespace cmp {
@@ -41,6 +42,17 @@ struct Score {
     static constexpr uint32_t COUNTERS = TALLIES + 2;
     static constexpr uint32_t BINS = (COUNTERS + 1) & ~1u; // ... rounded up to an even number of lane-private bins: 32, 48
 };
+
+// What the kernels that count a comparison's records share (k_cmp_match<>, k_cmp_tally<>, k_region_tally<>): LANES lanes a
+// workgroup and a record a lane and pass; lane-private bins, summed in two halves into the workgroup's slot of `out` -- OUT_WORDS
+// counters: HIST_SLOTS slots of 2 x BINS words, the truth's counters in front of the calls' (lane_hist.h).
+constexpr int LANES = 256;
+template <int OUTCOMES> using Hist = LaneHist<(int)Score<OUTCOMES>::BINS, LANES, 2>;
+template <int OUTCOMES> constexpr size_t OUT_WORDS = (size_t)HIST_SLOTS * 2 * Score<OUTCOMES>::BINS;
+template <int OUTCOMES>
+__device__ __forceinline__ unsigned long long *slot_of(unsigned long long *out) {
+    return out + (blockIdx.x & (HIST_SLOTS - 1)) * 2 * Score<OUTCOMES>::BINS;
+}
 
 struct Rec { uint32_t pos, stop, extra, type, aux; };
 struct Table { const msim_record *recs; uint64_t n; const uint8_t *pool; uint64_t pool_len; };
@@ -73,6 +85,17 @@ MSIM_FHD inline void cell_index(uint32_t cell, uint32_t *type, uint32_t *bin) {
 // the counter of a record with that flag byte
 template <int OUTCOMES>
 MSIM_FHD inline uint32_t counter_of(const Rec &r, uint32_t flag) { return OUTCOMES * cell_of(r) + (flag ? flag - 1u : OUTCOMES - 1u); }
+
+// host: a[], b[] -- the truth's and the calls' counters, per cell its outcomes -- added to counts[type][bin][side][outcome]
+template <int OUTCOMES>
+inline void fold_cells(const unsigned long long *a, const unsigned long long *b, uint64_t *counts) {
+    for (uint32_t cell = 0; cell < CELLS; cell++) {
+        uint32_t type, bin;
+        cell_index(cell, &type, &bin);
+        uint64_t *dst = counts + ((size_t)type * MSIM_CMP_BINS + bin) * 2 * OUTCOMES;
+        for (int k = 0; k < OUTCOMES; k++) { dst[k] += a[OUTCOMES * cell + k]; dst[OUTCOMES + k] += b[OUTCOMES * cell + k]; }
+    }
+}
 
 // an indel the walk is written for: inside the contig, an insert inside its pool (what table_check guarantees, checked again
 // because nothing else keeps a read inside its buffer)

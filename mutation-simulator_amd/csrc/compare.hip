@@ -20,6 +20,7 @@
 #include "cmp_phase.h"
 #include "cmp_regions.h"
 #include "compare.h"
+#include "counter_trip.h"
 #include "ctx.h"
 #include "lane_hist.h"
 #include "scan_kernels.h"
@@ -56,17 +57,15 @@ struct DipPair {
 struct CompareState {
     std::vector<Held> held;                    // by contig index
     std::vector<DipPair> dip;                  // by contig index (a sibling of `held`: msim_cmp_hold replaces a Held whole)
-    Scratch<unsigned long long> d_out;         // HIST_SLOTS x (A's counters, B's counters)
-    Pinned<unsigned long long> h_out;          // pinned copy of them
-    Scratch<uint32_t> d_front;                 // the join's scratch, per haplotype-2 record: haplotype 1's records at or in front
+    CounterTrip out;                           // HIST_SLOTS x (A's counters, B's counters); its events time the join as well
+    Scratch<uint32_t> d_front;                // the join's scratch, per haplotype-2 record: haplotype 1's records at or in front
                                                //   of its pos, bit 31: it is a duplicate of the last of them;
     Scratch<uint32_t> d_excl;                  //   the duplicates in front of it;
     Scratch<uint32_t> d_tile;                  //   per scan tile its duplicates (then their exclusive scan, the total last)
-    EventPair tm;
     double kernel_ms = 0, join_ms = 0;
     // compare --blocks (msim_cmp_counts_blocks; kernels in cmp_blocks.hip)
-    Scratch<unsigned long long> d_blk_out;     // the match's counters (two outcomes), the final tally's (three), the block pass's
-    Pinned<unsigned long long> h_blk_out;      // pinned copy of them
+    CounterTrip blk_out;                       // the match's counters (two outcomes), the final tally's (three), the block pass's;
+                                               //   its events time the match
     Scratch<blk::Desc> d_desc;                 // the blocks to replay
     EventPair tm_blk, tm_tally;
     hipEvent_t ev_blk_mid = nullptr;           // between k_blk_scan and k_blk_replay
@@ -78,23 +77,18 @@ struct CompareState {
 
 namespace {
 
-constexpr int LANES = 256;
+constexpr int LANES = cmp::LANES;
 constexpr uint32_t CMP_PASS = LANES;                       // records of a workgroup's pass: one a lane (a walk is long enough)
 static_assert(CMP_PASS == MSIM_CMP_PASS, "msim.h and compare.hip must agree on the pass");
 static_assert((1u << cmp::WINDOW_SHIFT) == MSIM_CMP_WINDOW, "msim.h and compare.h must agree on the window");
 constexpr unsigned CMP_MAX_BLOCKS = 2048;                  // more passes than that stride: eight workgroups a CU (16 KB of LDS each)
 static_assert(sizeof(msim_record) == sizeof(uint4), "a record is one 16-byte load");
 
-// Lane-private bins, summed in two halves into the workgroup's slot of `out`: 2 x BINS words a slot, A's counters in front of
-// B's (lane_hist.h) -- 16 KB of LDS a workgroup and eight workgroups a CU with two outcomes, 24 KB and six with three.  A table
-// has fewer than 2^31 records, so fewer than 2^23 passes; beyond CMP_MAX_BLOCKS passes the grid strides, a workgroup takes at
-// most 4096 of them and a lane adds at most once per counter and pass: 16 bits hold it, in either instantiation.
-template <int OUTCOMES> using CmpHist = LaneHist<(int)cmp::Score<OUTCOMES>::BINS, LANES, 2>;
-template <int OUTCOMES> constexpr size_t OUT_WORDS = (size_t)HIST_SLOTS * 2 * cmp::Score<OUTCOMES>::BINS;
-template <int OUTCOMES>
-__device__ __forceinline__ unsigned long long *slot_of(unsigned long long *out) {
-    return out + (blockIdx.x & (HIST_SLOTS - 1)) * 2 * cmp::Score<OUTCOMES>::BINS;
-}
+// Lane-private bins and slots: compare.h (Hist, OUT_WORDS, slot_of) -- 16 KB of LDS a workgroup and eight workgroups a CU with
+// two outcomes, 24 KB and six with three.  A table has fewer than 2^31 records, so fewer than 2^23 passes; beyond CMP_MAX_BLOCKS
+// passes the grid strides, a workgroup takes at most 4096 of them and a lane adds at most once per counter and pass: 16 bits
+// hold it, in either instantiation.
+using cmp::OUT_WORDS;
 
 // the two tables' genotype bytes, which a haploid comparison neither has nor passes to its kernel
 template <int OUTCOMES> struct Gt { const uint8_t *a, *b; };
@@ -107,7 +101,7 @@ __global__ __launch_bounds__(LANES) void k_cmp_match(const uint8_t *__restrict__
                                                      uint64_t n_pass, uint8_t *__restrict__ flag_a, uint8_t *__restrict__ flag_b,
                                                      unsigned long long *__restrict__ out, Gt<OUTCOMES> gt) {
     using S = cmp::Score<OUTCOMES>;
-    __shared__ CmpHist<OUTCOMES> hist;
+    __shared__ cmp::Hist<OUTCOMES> hist;
     hist.zero();
     for (uint64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
         const uint64_t i = pass * CMP_PASS + threadIdx.x;
@@ -127,13 +121,13 @@ __global__ __launch_bounds__(LANES) void k_cmp_match(const uint8_t *__restrict__
         if (s.stops & cmp::STOP_WINDOW) hist.add(S::TALLIES, 1u);
         if (s.stops & cmp::STOP_BASE) hist.add(S::TALLIES + 1, 1u);
     }
-    hist.flush(slot_of<OUTCOMES>(out));
+    hist.flush(cmp::slot_of<OUTCOMES>(out));
 }
 
 template <int OUTCOMES>
 __global__ __launch_bounds__(LANES) void k_cmp_tally(const msim_record *__restrict__ recs, uint64_t n_rec, uint64_t n_pass,
                                                      const uint8_t *__restrict__ flag, unsigned long long *__restrict__ out) {
-    __shared__ CmpHist<OUTCOMES> hist;
+    __shared__ cmp::Hist<OUTCOMES> hist;
     hist.zero();
     for (uint64_t pass = blockIdx.x; pass < n_pass; pass += gridDim.x) {
         const uint64_t i = pass * CMP_PASS + threadIdx.x;
@@ -141,7 +135,7 @@ __global__ __launch_bounds__(LANES) void k_cmp_tally(const msim_record *__restri
         const cmp::Rec b = cmp::rec_at(recs, i);
         if (cmp::known_type(b.type)) hist.add(cmp::counter_of<OUTCOMES>(b, flag[i]), 1u);
     }
-    hist.flush(slot_of<OUTCOMES>(out));
+    hist.flush(cmp::slot_of<OUTCOMES>(out));
 }
 
 // ---- the join: haplotype 1's table (H1) and haplotype 2's (H2) into one diploid table U ------------------------------------------
@@ -247,26 +241,15 @@ __global__ __launch_bounds__(LANES) void k_join_put1(cmp::Table H1, cmp::Table H
 // tallies), b[]: the calls' (the last outcome: extra)
 template <int OUTCOMES>
 void finish(const unsigned long long *a, const unsigned long long *b, uint64_t *counts, uint64_t tallies[2]) {
-    for (uint32_t cell = 0; cell < cmp::CELLS; cell++) {
-        uint32_t type, bin;
-        cmp::cell_index(cell, &type, &bin);
-        uint64_t *dst = counts + ((size_t)type * MSIM_CMP_BINS + bin) * 2 * OUTCOMES;
-        for (int k = 0; k < OUTCOMES; k++) { dst[k] += a[OUTCOMES * cell + k]; dst[OUTCOMES + k] += b[OUTCOMES * cell + k]; }
-    }
+    cmp::fold_cells<OUTCOMES>(a, b, counts);
     tallies[0] += a[cmp::Score<OUTCOMES>::TALLIES];
     tallies[1] += a[cmp::Score<OUTCOMES>::TALLIES + 1];
 }
 
 int state_of(Ctx *c, CompareState **out) {
-    if (!c->compare) {
-        CompareState *S = new CompareState;
-        c->compare = S;
-        MSIM_HIP(c, dev_alloc(S->d_out, OUT_WORDS<3> * sizeof(unsigned long long)));   // (the larger of the two layouts)
-        MSIM_HIP(c, pin_alloc(S->h_out, OUT_WORDS<3> * sizeof(unsigned long long)));
-        MSIM_HIP(c, S->tm.create());
-    }
+    const int rc = lazy_state(c, &c->compare, OUT_WORDS<3>, "the compare mode's result buffers and events");   // (the larger of the two layouts)
     *out = c->compare;
-    return MSIM_OK;
+    return rc;
 }
 
 Held *held_of(Ctx *c, int contig) {
@@ -285,52 +268,66 @@ int held_contig(Ctx *c, int contig, Contig **g, Held **h, CompareState **S, cons
     return state_of(c, S);
 }
 
+// a contig's current table and a held one, as the kernels take them
+cmp::Table table_of(const Contig &g) { return {g.d_recs.p(), g.n_rec, g.pool_len ? g.d_pool.p() + PAD : nullptr, g.pool_len}; }
+cmp::Table table_of(const Held &h) { return {h.d_recs.p(), h.n_rec, h.d_pool.p(), h.pool_len}; }
+
 // one side of a comparison: its table, its genotype bytes (a haploid side: none), its flag bytes (one per record)
 struct Side { cmp::Table t; const uint8_t *gt; uint8_t *flag; };
+
+// What a count of the held table against the contig's current one begins with: a flag byte per current record, the two sides.
+int held_sides(Ctx *c, const Contig &g, Held &h, Side *a, Side *b) {
+    h.counted = false;
+    MSIM_HIP(c, dev_at_least(h.d_flag_b, (size_t)g.n_rec));      // exactly a byte per record
+    h.n_flag_b = g.n_rec;
+    *a = Side{table_of(h), nullptr, h.d_flag_a.p()};
+    *b = Side{table_of(g), nullptr, h.d_flag_b.p()};
+    return MSIM_OK;
+}
+
+// b's flags zeroed and a's records matched against b: every record of a its flag byte and counter, its partner in b the flag
+template <int OUTCOMES>
+int launch_match(Ctx *c, const Contig &g, const Side &a, const Side &b, uint32_t flags, unsigned long long *out) {
+    if (b.t.n) MSIM_HIP(c, hipMemsetAsync(b.flag, 0, (size_t)b.t.n, c->stream));
+    if (!a.t.n) return MSIM_OK;
+    const PassGrid pg = pass_grid(a.t.n, CMP_PASS, CMP_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_cmp_match<OUTCOMES>, pg.grid, dim3(LANES), 0, c->stream, g.d_in.p() + PAD, g.len, a.t, b.t, flags & MSIM_CMP_EXACT,
+                       pg.n_pass, a.flag, b.flag, out, Gt<OUTCOMES>{a.gt, b.gt});
+    MSIM_HIP(c, hipGetLastError());
+    return MSIM_OK;
+}
+// a side's records counted by their flag bytes
+template <int OUTCOMES>
+int launch_tally(Ctx *c, const Side &x, unsigned long long *out) {
+    if (!x.t.n) return MSIM_OK;
+    const PassGrid pg = pass_grid(x.t.n, CMP_PASS, CMP_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_cmp_tally<OUTCOMES>, pg.grid, dim3(LANES), 0, c->stream, x.t.recs, x.t.n, pg.n_pass, (const uint8_t *)x.flag, out);
+    MSIM_HIP(c, hipGetLastError());
+    return MSIM_OK;
+}
 
 // The two launches of a comparison on contig g, A against B: b's flags zeroed, a's records matched, b's tallied, the counters
 // fetched and summed into counts and tallies.
 template <int OUTCOMES>
 int counts_device(Ctx *c, CompareState *S, const Contig &g, const Side &a, const Side &b, uint32_t flags, uint64_t *counts, uint64_t tallies[2]) {
-    constexpr size_t BINS = cmp::Score<OUTCOMES>::BINS, OUT_BYTES = OUT_WORDS<OUTCOMES> * sizeof(unsigned long long);
+    constexpr size_t BINS = cmp::Score<OUTCOMES>::BINS;
     if (!a.t.n && !b.t.n) return MSIM_OK;
-    const uint64_t pass_a = (a.t.n + CMP_PASS - 1) / CMP_PASS, pass_b = (b.t.n + CMP_PASS - 1) / CMP_PASS;
-    MSIM_HIP(c, hipMemsetAsync(S->d_out.p(), 0, OUT_BYTES, c->stream));
-    MSIM_HIP(c, S->tm.begin(c->stream));
-    if (b.t.n) MSIM_HIP(c, hipMemsetAsync(b.flag, 0, (size_t)b.t.n, c->stream));
-    if (a.t.n) {
-        hipLaunchKernelGGL(k_cmp_match<OUTCOMES>, dim3((unsigned)std::min<uint64_t>(pass_a, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
-                           g.d_in.p() + PAD, g.len, a.t, b.t, flags & MSIM_CMP_EXACT, pass_a, a.flag, b.flag, S->d_out.p(),
-                           Gt<OUTCOMES>{a.gt, b.gt});
-        MSIM_HIP(c, hipGetLastError());
-    }
-    if (b.t.n) {
-        hipLaunchKernelGGL(k_cmp_tally<OUTCOMES>, dim3((unsigned)std::min<uint64_t>(pass_b, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
-                           b.t.recs, b.t.n, pass_b, (const uint8_t *)b.flag, S->d_out.p() + BINS);
-        MSIM_HIP(c, hipGetLastError());
-    }
-    MSIM_HIP(c, S->tm.end(c->stream));                      // (in front of the copy: the kernels alone)
-    MSIM_HIP(c, hipMemcpyAsync(S->h_out.p(), S->d_out.p(), OUT_BYTES, hipMemcpyDeviceToHost, c->stream));
-    MSIM_HIP(c, wait_stream(c->stream));
-    const int rc = S->tm.add_elapsed(c, &S->kernel_ms);
-    if (rc) return rc;
+    int rc;
+    if ((rc = S->out.begin(c, OUT_WORDS<OUTCOMES>)) || (rc = launch_match<OUTCOMES>(c, g, a, b, flags, S->out.d.p())) ||
+        (rc = launch_tally<OUTCOMES>(c, b, S->out.d.p() + BINS)) || (rc = S->out.finish(c, &S->kernel_ms)))
+        return rc;
     unsigned long long bins[2 * BINS];
-    hist_sum_slots(S->h_out.p(), 2 * BINS, bins, 2 * BINS);
+    hist_sum_slots(S->out.h.p(), 2 * BINS, bins, 2 * BINS);
     finish<OUTCOMES>(bins, bins + BINS, counts, tallies);
     return MSIM_OK;
 }
 
 // the held table against the contig's current one
 int counts_held(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32_t flags, uint64_t *counts, uint64_t tallies[2]) {
-    h.counted = false;
-    if (g.n_rec > h.d_flag_b.cap) {                        // exactly a byte per record
-        MSIM_HIP(c, h.d_flag_b.release());
-        MSIM_HIP(c, dev_alloc(h.d_flag_b, (size_t)g.n_rec));
-    }
-    h.n_flag_b = g.n_rec;
-    const Side a{{h.d_recs.p(), h.n_rec, h.d_pool.p(), h.pool_len}, nullptr, h.d_flag_a.p()};
-    const Side b{{g.d_recs.p(), g.n_rec, g.pool_len ? g.d_pool.p() + PAD : nullptr, g.pool_len}, nullptr, h.d_flag_b.p()};
-    const int rc = counts_device<2>(c, S, g, a, b, flags, counts, tallies);
+    Side a, b;
+    int rc = held_sides(c, g, h, &a, &b);
+    if (rc) return rc;
+    rc = counts_device<2>(c, S, g, a, b, flags, counts, tallies);
     h.counted = !rc;
     h.counted_outcomes = 2;
     h.counted_flags = flags;
@@ -338,16 +335,8 @@ int counts_held(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32_t flag
     return rc;
 }
 
-// exactly `bytes`, whatever the block held (contents are not kept)
-hipError_t dev_exact(DevBlock &b, size_t bytes) {
-    const hipError_t e = b.release();
-    return e != hipSuccess || !bytes ? e : dev_alloc(b, bytes);
-}
-// at least `bytes` (contents are not kept)
-hipError_t dev_at_least(DevBlock &b, size_t bytes) { return bytes <= b.cap ? hipSuccess : dev_exact(b, bytes); }
-
 // ---- compare --blocks: the held table against the current one, unmatched records rescued block by block ---------------------------
-// The words of d_blk_out: k_cmp_match<2>'s counters (its two walk tallies are used, its cells are not), k_cmp_tally<3>'s over both
+// The words of blk_out: k_cmp_match<2>'s counters (its two walk tallies are used, its cells are not), k_cmp_tally<3>'s over both
 // tables with the final flag bytes, the block pass's (cmp_blocks.h).
 constexpr size_t BLK_MATCH_AT = 0, BLK_TALLY_AT = OUT_WORDS<2>, BLK_PASS_AT = BLK_TALLY_AT + OUT_WORDS<3>,
                  BLK_OUT_WORDS = BLK_PASS_AT + blk::PASS_WORDS;
@@ -358,67 +347,44 @@ void finish_blocks(const unsigned long long *words, uint64_t *counts, uint64_t t
     hist_sum_slots(words + BLK_MATCH_AT, 2 * B2, m, 2 * B2);
     hist_sum_slots(words + BLK_TALLY_AT, 2 * B3, t, 2 * B3);
     hist_sum_slots(words + BLK_PASS_AT, blk::PASS_BINS, p, blk::PASS_BINS);
-    uint64_t none[2] = {0, 0};
-    finish<3>(t, t + B3, counts, none);
+    cmp::fold_cells<3>(t, t + B3, counts);
     tallies[0] += m[cmp::Score<2>::TALLIES];
     tallies[1] += m[cmp::Score<2>::TALLIES + 1];
     for (uint32_t k = 0; k < blk::TALLIES; k++) block_tallies[k] += p[k];
 }
 
+// Three timed stretches on one trip: the match (the trip's own events), the block pass with an event between its two kernels, the
+// final tallies.
 int counts_held_blocks(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32_t flags, uint32_t gap, uint64_t *counts, uint64_t tallies[2],
                        uint64_t block_tallies[5]) {
-    h.counted = false;
-    if (!S->d_blk_out) MSIM_HIP(c, dev_alloc(S->d_blk_out, BLK_OUT_WORDS * sizeof(unsigned long long)));   // (made on first use)
-    if (!S->h_blk_out) MSIM_HIP(c, pin_alloc(S->h_blk_out, BLK_OUT_WORDS * sizeof(unsigned long long)));
+    CounterTrip &trip = S->blk_out;
+    if (!trip) MSIM_HIP(c, trip.create(BLK_OUT_WORDS));     // (made on first use)
     if (!S->tm_blk.e1) { S->tm_blk.destroy(); MSIM_HIP(c, S->tm_blk.create()); }
     if (!S->tm_tally.e1) { S->tm_tally.destroy(); MSIM_HIP(c, S->tm_tally.create()); }
     if (!S->ev_blk_mid) MSIM_HIP(c, hipEventCreate(&S->ev_blk_mid));
-    if (g.n_rec > h.d_flag_b.cap) {                        // exactly a byte per record
-        MSIM_HIP(c, h.d_flag_b.release());
-        MSIM_HIP(c, dev_alloc(h.d_flag_b, (size_t)g.n_rec));
-    }
-    h.n_flag_b = g.n_rec;
+    Side a, b;
+    int rc = held_sides(c, g, h, &a, &b);
+    if (rc) return rc;
     h.counted_outcomes = 3;
     h.counted_flags = flags;
     h.counted_gen = g.table_gen;
-    const Side a{{h.d_recs.p(), h.n_rec, h.d_pool.p(), h.pool_len}, nullptr, h.d_flag_a.p()};
-    const Side b{{g.d_recs.p(), g.n_rec, g.pool_len ? g.d_pool.p() + PAD : nullptr, g.pool_len}, nullptr, h.d_flag_b.p()};
     const uint64_t total = a.t.n + b.t.n;
     if (!total) { h.counted = true; return MSIM_OK; }
     MSIM_HIP(c, dev_at_least(S->d_desc, (size_t)total * sizeof(blk::Desc)));
-    unsigned long long *out = S->d_blk_out.p();
-    const uint64_t pass_a = (a.t.n + CMP_PASS - 1) / CMP_PASS, pass_b = (b.t.n + CMP_PASS - 1) / CMP_PASS;
-    MSIM_HIP(c, hipMemsetAsync(out, 0, BLK_OUT_WORDS * sizeof(unsigned long long), c->stream));
-    MSIM_HIP(c, S->tm.begin(c->stream));
-    if (b.t.n) MSIM_HIP(c, hipMemsetAsync(b.flag, 0, (size_t)b.t.n, c->stream));
-    if (a.t.n) {
-        hipLaunchKernelGGL(k_cmp_match<2>, dim3((unsigned)std::min<uint64_t>(pass_a, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
-                           g.d_in.p() + PAD, g.len, a.t, b.t, flags & MSIM_CMP_EXACT, pass_a, a.flag, b.flag, out + BLK_MATCH_AT, Gt<2>{nullptr, nullptr});
-        MSIM_HIP(c, hipGetLastError());
-    }
-    MSIM_HIP(c, S->tm.end(c->stream));
+    unsigned long long *out = trip.d.p();
+    if ((rc = trip.begin(c, BLK_OUT_WORDS)) || (rc = launch_match<2>(c, g, a, b, flags, out + BLK_MATCH_AT))) return rc;
+    MSIM_HIP(c, trip.tm.end(c->stream));
     MSIM_HIP(c, S->tm_blk.begin(c->stream));
-    const int rc_blk = blocks_enqueue(c, c->stream, g.d_in.p() + PAD, g.len, a.t, b.t, a.flag, b.flag, gap, S->d_desc.p(), total, out + BLK_PASS_AT,
-                                      S->ev_blk_mid);
-    if (rc_blk) return rc_blk;
+    if ((rc = blocks_enqueue(c, c->stream, g.d_in.p() + PAD, g.len, a.t, b.t, a.flag, b.flag, gap, S->d_desc.p(), total, out + BLK_PASS_AT, S->ev_blk_mid)))
+        return rc;
     MSIM_HIP(c, S->tm_blk.end(c->stream));
     MSIM_HIP(c, S->tm_tally.begin(c->stream));
-    const Side *sides[2] = {&a, &b};
-    for (int s = 0; s < 2; s++) {
-        const Side &x = *sides[s];
-        if (!x.t.n) continue;
-        hipLaunchKernelGGL(k_cmp_tally<3>, dim3((unsigned)std::min<uint64_t>(s ? pass_b : pass_a, CMP_MAX_BLOCKS)), dim3(LANES), 0, c->stream,
-                           x.t.recs, x.t.n, s ? pass_b : pass_a, (const uint8_t *)x.flag, out + BLK_TALLY_AT + (s ? cmp::Score<3>::BINS : 0));
-        MSIM_HIP(c, hipGetLastError());
-    }
-    MSIM_HIP(c, S->tm_tally.end(c->stream));
-    MSIM_HIP(c, hipMemcpyAsync(S->h_blk_out.p(), out, BLK_OUT_WORDS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    MSIM_HIP(c, wait_stream(c->stream));
-    int rc;
-    if ((rc = S->tm.add_elapsed(c, &S->kernel_ms)) || (rc = S->tm_tally.add_elapsed(c, &S->kernel_ms)) ||
+    if ((rc = launch_tally<3>(c, a, out + BLK_TALLY_AT)) || (rc = launch_tally<3>(c, b, out + BLK_TALLY_AT + cmp::Score<3>::BINS))) return rc;
+    MSIM_HIP(c, S->tm_tally.end(c->stream));                // (in front of the copy: the kernels alone)
+    if ((rc = trip.copy_wait(c)) || (rc = trip.tm.add_elapsed(c, &S->kernel_ms)) || (rc = S->tm_tally.add_elapsed(c, &S->kernel_ms)) ||
         (rc = S->tm_blk.add_elapsed(c, &S->blocks_ms)))
         return rc;
-    const unsigned long long *pass = S->h_blk_out.p() + BLK_PASS_AT;
+    const unsigned long long *pass = trip.h.p() + BLK_PASS_AT;
     if (pass[blk::PASS_COUNT_AT] > total) return fail(c, MSIM_ERR_HIP, "internal: more blocks to replay than the two tables hold records");
     float scan = 0, replay = 0;
     MSIM_HIP(c, hipEventElapsedTime(&scan, S->tm_blk.e0, S->ev_blk_mid));
@@ -427,7 +393,7 @@ int counts_held_blocks(Ctx *c, CompareState *S, const Contig &g, Held &h, uint32
     S->replay_ms += replay;
     S->replay_steps += pass[blk::PASS_STEPS_AT];
     S->replay_wave_steps += pass[blk::PASS_WAVE_STEPS_AT];
-    finish_blocks(S->h_blk_out.p(), counts, tallies, block_tallies);
+    finish_blocks(trip.h.p(), counts, tallies, block_tallies);
     h.counted = true;
     return MSIM_OK;
 }
@@ -463,10 +429,9 @@ int join_device(Ctx *c, CompareState *S, const Contig &g, const Held &h, Dip &d)
     MSIM_HIP(c, dev_at_least(S->d_front, (size_t)std::max<uint64_t>(n2, 1) * sizeof(uint32_t)));
     MSIM_HIP(c, dev_at_least(S->d_excl, (size_t)std::max<uint64_t>(n2, 1) * sizeof(uint32_t)));
     MSIM_HIP(c, dev_at_least(S->d_tile, ((size_t)tiles + 1) * sizeof(uint32_t)));
-    const cmp::Table H1{h.d_recs.p(), n1, h.d_pool.p(), h.pool_len};
-    const cmp::Table H2{g.d_recs.p(), n2, g.pool_len ? g.d_pool.p() + PAD : nullptr, g.pool_len};
+    const cmp::Table H1 = table_of(h), H2 = table_of(g);
     uint32_t dups = 0;
-    MSIM_HIP(c, S->tm.begin(c->stream));
+    MSIM_HIP(c, S->out.tm.begin(c->stream));
     if (n2) {
         hipLaunchKernelGGL(k_join_flag, dim3(tiles), dim3(JOIN_TILE), 0, c->stream, H1, H2, S->d_front.p(), S->d_tile.p());
         hipLaunchKernelGGL(k_scan_u32, dim3(1), dim3(1024), 0, c->stream, S->d_tile.p(), tiles);
@@ -485,10 +450,10 @@ int join_device(Ctx *c, CompareState *S, const Contig &g, const Held &h, Dip &d)
     if (h.pool_len) MSIM_HIP(c, hipMemcpyAsync(d.d_pool.p(), h.d_pool.p(), (size_t)h.pool_len, hipMemcpyDeviceToDevice, c->stream));
     if (g.pool_len)
         MSIM_HIP(c, hipMemcpyAsync(d.d_pool.p() + h.pool_len, g.d_pool.p() + PAD, (size_t)g.pool_len, hipMemcpyDeviceToDevice, c->stream));
-    MSIM_HIP(c, S->tm.end(c->stream));                      // (the kernels and the two pool copies)
+    MSIM_HIP(c, S->out.tm.end(c->stream));                  // (the kernels and the two pool copies)
     MSIM_HIP(c, hipMemcpyAsync(&dups, S->d_tile.p() + tiles, sizeof dups, hipMemcpyDeviceToHost, c->stream));
     MSIM_HIP(c, wait_stream(c->stream));
-    const int rc = S->tm.add_elapsed(c, &S->join_ms);
+    const int rc = S->out.tm.add_elapsed(c, &S->join_ms);
     if (rc) return rc;
     if (dups > n1 || dups > n2) return fail(c, MSIM_ERR_HIP, "internal: the join counted more duplicates than a table holds");
     d.n = cap - dups;
@@ -591,8 +556,8 @@ bool compare_region_tables(Ctx *c, int contig, bool diploid, RegionTables *v, co
     if (!h) { *why = "contig has no held table (msim_cmp_hold)"; return false; }
     const Contig &g = c->contigs[(size_t)contig];
     if (!g.planned) { *why = "contig has no current table: plan it first"; return false; }
-    v->t[MSIM_CMP_TRUTH] = cmp::Table{h->d_recs.p(), h->n_rec, h->d_pool.p(), h->pool_len};
-    v->t[MSIM_CMP_CALLS] = cmp::Table{g.d_recs.p(), g.n_rec, g.pool_len ? g.d_pool.p() + PAD : nullptr, g.pool_len};
+    v->t[MSIM_CMP_TRUTH] = table_of(*h);
+    v->t[MSIM_CMP_CALLS] = table_of(g);
     v->flag[MSIM_CMP_TRUTH] = h->d_flag_a.p();
     v->flag[MSIM_CMP_CALLS] = h->d_flag_b.p();
     v->counted = h->counted && g.n_rec == h->n_flag_b && g.table_gen == h->counted_gen;   // (msim_cmp_fetch's test, and the generation)
@@ -626,7 +591,6 @@ void compare_state_destroy(Ctx *c) {
     S->phase = nullptr;
     regions_state_destroy(S->regions);
     S->regions = nullptr;
-    S->tm.destroy();
     S->tm_blk.destroy();
     S->tm_tally.destroy();
     if (S->ev_blk_mid) (void)hipEventDestroy(S->ev_blk_mid);
@@ -853,9 +817,10 @@ int msim_dbg_cmp_join_copy_floor(msim_ctx *p, int contig, double *ms) {
     CompareState *S;
     const int rc = held_contig(c, contig, &g, &h, &S);
     if (rc) return rc;
-    const CopySource one[4] = {{h->d_recs.p(), (size_t)h->n_rec * sizeof(msim_record)}, {g->d_recs.p(), (size_t)g->n_rec * sizeof(msim_record)},
-                               {h->d_pool.p(), (size_t)h->pool_len}, {g->pool_len ? g->d_pool.p() + PAD : nullptr, (size_t)g->pool_len}};
-    return copy_floor(c, S->tm, one, 4, ms);
+    const cmp::Table H = table_of(*h), G = table_of(*g);
+    const CopySource one[4] = {{H.recs, (size_t)H.n * sizeof(msim_record)}, {G.recs, (size_t)G.n * sizeof(msim_record)},
+                               {H.pool, (size_t)H.pool_len}, {G.pool, (size_t)G.pool_len}};
+    return copy_floor(c, S->out.tm, one, 4, ms);
 }
 
 // measurement support (tools/compare_bench.py; exported, not part of msim.h): a device-to-device copy of the held and the current
@@ -868,8 +833,9 @@ int msim_dbg_cmp_copy_floor(msim_ctx *p, int contig, double *ms) {
     CompareState *S;
     const int rc = held_contig(c, contig, &g, &h, &S);
     if (rc) return rc;
-    const CopySource tables[2] = {{h->d_recs.p(), (size_t)h->n_rec * sizeof(msim_record)}, {g->d_recs.p(), (size_t)g->n_rec * sizeof(msim_record)}};
-    return copy_floor(c, S->tm, tables, 2, ms);
+    const cmp::Table H = table_of(*h), G = table_of(*g);
+    const CopySource tables[2] = {{H.recs, (size_t)H.n * sizeof(msim_record)}, {G.recs, (size_t)G.n * sizeof(msim_record)}};
+    return copy_floor(c, S->out.tm, tables, 2, ms);
 }
 
 // ---- sequential host restatement: no context, no GPU -------------------------------------------------------------------
@@ -925,8 +891,7 @@ int msim_dbg_cmp_counts_blocks(const uint8_t *bases, uint64_t L, const msim_reco
     for (uint64_t i = 0; i < n_truth; i++) ca[cmp::counter_of<3>(cmp::rec_at(truth, i), fa[(size_t)i])]++;
     for (uint64_t i = 0; i < n_calls; i++) cb[cmp::counter_of<3>(cmp::rec_at(calls, i), fb[(size_t)i])]++;
     memset(counts, 0, (size_t)8 * MSIM_CMP_BINS * 6 * sizeof(uint64_t));
-    uint64_t none[2] = {0, 0};
-    finish<3>(ca, cb, counts, none);
+    cmp::fold_cells<3>(ca, cb, counts);
     if (truth_flags && n_truth) memcpy(truth_flags, fa.data(), (size_t)n_truth);
     if (calls_flags && n_calls) memcpy(calls_flags, fb.data(), (size_t)n_calls);
     return MSIM_OK;

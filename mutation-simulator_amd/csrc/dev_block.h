@@ -1,6 +1,7 @@
 // A block of device or pinned host memory that owns itself: capacity in BYTES, move-only, frees itself.  A move assignment
 // frees what the target held; release() frees now and reports.  Blocks grow through one function per rule, each taking the
-// block: dev_reserve, ensure_scratch (ctx.h), Grow (plan_gpu.hip), dev_grow (plan_fast.hip).
+// block: dev_exact, dev_at_least (below), dev_reserve, ensure_scratch (ctx.h), Grow (plan_gpu.hip), dev_grow
+// (plan_fast.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -37,6 +38,13 @@ inline hipError_t dev_alloc(DevBlock &b, size_t bytes) {
     if (e == hipSuccess) b.cap = bytes;
     return e;
 }
+// exactly `bytes`, whatever the block held (contents are not kept)
+inline hipError_t dev_exact(DevBlock &b, size_t bytes) {
+    const hipError_t e = b.release();
+    return e != hipSuccess || !bytes ? e : dev_alloc(b, bytes);
+}
+// at least `bytes`, allocated at exactly that size (contents are not kept; dev_reserve, ctx.h, adds slack to what it allocates)
+inline hipError_t dev_at_least(DevBlock &b, size_t bytes) { return bytes <= b.cap ? hipSuccess : dev_exact(b, bytes); }
 inline hipError_t pin_alloc(HostPinBlock &b, size_t bytes, unsigned flags = hipHostMallocDefault) {
     const hipError_t e = hipHostMalloc(&b.raw, bytes, flags);
     if (e == hipSuccess) b.cap = bytes;

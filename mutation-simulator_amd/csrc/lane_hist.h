@@ -1,4 +1,5 @@
-// The counting kernels' histogram (k_ctx_census, k_sbs_count, k_cmp_match<>, k_cmp_tally<>): BINS 16-bit counters per LANE in LDS.
+// The counting kernels' histogram (k_ctx_census, k_sbs_count, k_cmp_match<>, k_cmp_tally<>, k_region_tally<>, k_blk_scan,
+// k_blk_replay): BINS 16-bit counters per LANE in LDS.
 //   columns   every lane owns column threadIdx.x of `cnt`, two bins to a 32-bit word: no two lanes share a word and a wave's 64
 //             adds go to 64 different banks, so an add is one conflict-free ds_add whatever the data holds -- a homopolymer
 //             run or a one-channel table costs what random input costs.  A lane zeroes its own column: no barrier before its adds.
@@ -7,7 +8,7 @@
 //   flush     PARTS x BINS threads sum bin b over LANES / PARTS columns each, reading them rotated by the thread index: a wave's
 //             64 reads stay on 64 banks.  Then one device-scope add per non-zero bin and workgroup into `out`.
 //   slots     the caller chooses `out`: HIST_SLOTS copies of the result, workgroup w adding to copy w & 15, and the host sums
-//             them (hist_sum_slots).  On one copy, 96 busy bins cost 96 adds to the same few lines per workgroup and the time
+//             them (hist_sum_slots) once the counters are back (counter_trip.h).  On one copy, 96 busy bins cost 96 adds to the same few lines per workgroup and the time
 //             depended on the data (NOTES 21: 0.873 ms one channel, 1.095 ms a real spectrum).  The census keeps its one copy.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -58,6 +59,13 @@ inline void hist_sum_slots(const unsigned long long *slots, size_t stride, unsig
     for (size_t i = 0; i < n_bins; i++) bins[i] = 0;
     for (int s = 0; s < HIST_SLOTS; s++)
         for (size_t i = 0; i < n_bins; i++) bins[i] += slots[(size_t)s * stride + i];
+}
+
+// host: the grid of a kernel with a pass loop -- n records in passes of `pass`, at most `cap` workgroups, which stride beyond that
+struct PassGrid { uint64_t n_pass; dim3 grid; };
+inline PassGrid pass_grid(uint64_t n, uint32_t pass, unsigned cap) {
+    const uint64_t n_pass = (n + pass - 1) / pass;
+    return PassGrid{n_pass, dim3((unsigned)(n_pass < cap ? n_pass : cap))};
 }
 
 }  // namespace msim

@@ -15,10 +15,10 @@
 //            SN record's position gathered from the resident contig, counted into 104 lane-private bins (96 channels + 8
 //            tallies: lane_hist.h)
 // The host waits once between scan and emit: the record table is allocated at its exact size.
-#include <algorithm>
 #include <cstring>
 #include <string>
 
+#include "counter_trip.h"
 #include "ctx.h"
 #include "lane_hist.h"
 #include "scan_kernels.h"
@@ -30,14 +30,13 @@ using fastrng::Key;
 using fastrng::U4;
 
 struct SpectrumState {
-    Scratch<unsigned long long> d_counts;     // 64 census bins
-    Scratch<unsigned long long> d_sbs;        // HIST_SLOTS x 104 profile bins (spectrum::SBS_BINS)
-    Pinned<unsigned long long> h_sbs;         // pinned copy of them
+    CounterTrip census;                       // 64 census bins
+    CounterTrip sbs;                          // HIST_SLOTS x 104 profile bins (spectrum::SBS_BINS)
     Scratch<uint64_t> d_thr;                  // 192 thresholds
     Scratch<uint32_t> d_words;                // one outcome word per lane of every tile (dev_reserve)
     Scratch<uint32_t> d_tile;                 // hits per tile, then their exclusive scan; [n_tiles]: the total (dev_reserve)
-    Pinned<unsigned long long> h_pin;         // pinned: [0..63] census bins / [0..191] thresholds on their way up, [192] the total
-    EventPair tm;
+    Pinned<unsigned long long> h_pin;         // pinned: [0..191] thresholds on their way up, [192] the plan's total
+    EventPair tm;                             // the plan's stretches
     double census_ms = 0, plan_ms = 0, sbs_ms = 0;
 };
 
@@ -239,15 +238,16 @@ void sbs_finish(const unsigned long long *slots, uint64_t channels[96], uint64_t
     tallies[1] = sn;
 }
 
+constexpr size_t CENSUS_WORDS = 64, SBS_WORDS = (size_t)HIST_SLOTS * SBS_BINS;
+
 inline uint64_t tiles_of(uint64_t L) { return (L + spectrum::TILE - 1) / spectrum::TILE; }
 
 int state_of(Ctx *c, SpectrumState **out) {
     if (!c->spectrum) {
         SpectrumState *S = new SpectrumState;
         c->spectrum = S;
-        MSIM_HIP(c, dev_alloc(S->d_counts, 64 * sizeof(unsigned long long)));
-        MSIM_HIP(c, dev_alloc(S->d_sbs, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long)));
-        MSIM_HIP(c, pin_alloc(S->h_sbs, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long)));
+        MSIM_HIP(c, S->census.create(CENSUS_WORDS));
+        MSIM_HIP(c, S->sbs.create(SBS_WORDS));
         MSIM_HIP(c, dev_alloc(S->d_thr, 192 * sizeof(uint64_t)));
         MSIM_HIP(c, pin_alloc(S->h_pin, 193 * sizeof(unsigned long long)));
         MSIM_HIP(c, S->tm.create());
@@ -264,18 +264,15 @@ int stretch_end(Ctx *c, SpectrumState *S, double *acc) {
 }
 
 int census_device(Ctx *c, SpectrumState *S, const Contig &g, uint64_t counts[64]) {
-    const uint64_t n_tiles = tiles_of(g.len);
-    if (!n_tiles) { memset(counts, 0, 64 * sizeof(uint64_t)); return MSIM_OK; }
-    MSIM_HIP(c, hipMemsetAsync(S->d_counts.p(), 0, 64 * sizeof(unsigned long long), c->stream));
-    MSIM_HIP(c, S->tm.begin(c->stream));
-    const unsigned blocks = (unsigned)std::min<uint64_t>(n_tiles, CENSUS_MAX_BLOCKS);
-    hipLaunchKernelGGL(k_ctx_census, dim3(blocks), dim3(LANES), 0, c->stream, g.d_in.p() + PAD, g.len, n_tiles, S->d_counts.p());
+    if (!g.len) { memset(counts, 0, 64 * sizeof(uint64_t)); return MSIM_OK; }
+    int rc = S->census.begin(c, CENSUS_WORDS);
+    if (rc) return rc;
+    const PassGrid pg = pass_grid(g.len, spectrum::TILE, CENSUS_MAX_BLOCKS);    // (a pass: one tile)
+    hipLaunchKernelGGL(k_ctx_census, pg.grid, dim3(LANES), 0, c->stream, g.d_in.p() + PAD, g.len, pg.n_pass, S->census.d.p());
     MSIM_HIP(c, hipGetLastError());
-    MSIM_HIP(c, S->tm.end(c->stream));                      // (in front of the copy: the kernel alone)
-    MSIM_HIP(c, hipMemcpyAsync(S->h_pin.p(), S->d_counts.p(), 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    MSIM_HIP(c, wait_stream(c->stream));
-    for (int i = 0; i < 64; i++) counts[i] = S->h_pin.p()[i];
-    return S->tm.add_elapsed(c, &S->census_ms);
+    if ((rc = S->census.finish(c, &S->census_ms))) return rc;
+    for (int i = 0; i < 64; i++) counts[i] = S->census.h.p()[i];
+    return MSIM_OK;
 }
 
 // the contig's ACTIVE table (the caller drained the context: the table is complete, its size collected, nothing writes it)
@@ -283,18 +280,15 @@ int sbs_device(Ctx *c, SpectrumState *S, const Contig &g, uint64_t channels[96],
     memset(channels, 0, 96 * sizeof(uint64_t));
     memset(tallies, 0, 8 * sizeof(uint64_t));
     if (!g.n_rec) return MSIM_OK;
-    const uint64_t n_pass = (g.n_rec + SBS_PASS - 1) / SBS_PASS;
-    MSIM_HIP(c, hipMemsetAsync(S->d_sbs.p(), 0, HIST_SLOTS * SBS_BINS * sizeof(unsigned long long), c->stream));
-    MSIM_HIP(c, S->tm.begin(c->stream));
-    const unsigned blocks = (unsigned)std::min<uint64_t>(n_pass, SBS_MAX_BLOCKS);
-    hipLaunchKernelGGL(k_sbs_count, dim3(blocks), dim3(LANES), 0, c->stream, g.d_in.p() + PAD, g.len,
-                       reinterpret_cast<const uint4 *>(g.d_recs.p()), g.n_rec, n_pass, S->d_sbs.p());
+    int rc = S->sbs.begin(c, SBS_WORDS);
+    if (rc) return rc;
+    const PassGrid pg = pass_grid(g.n_rec, SBS_PASS, SBS_MAX_BLOCKS);
+    hipLaunchKernelGGL(k_sbs_count, pg.grid, dim3(LANES), 0, c->stream, g.d_in.p() + PAD, g.len, reinterpret_cast<const uint4 *>(g.d_recs.p()), g.n_rec,
+                       pg.n_pass, S->sbs.d.p());
     MSIM_HIP(c, hipGetLastError());
-    MSIM_HIP(c, S->tm.end(c->stream));                      // (in front of the copy: the kernel alone)
-    MSIM_HIP(c, hipMemcpyAsync(S->h_sbs.p(), S->d_sbs.p(), HIST_SLOTS * SBS_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
-    MSIM_HIP(c, wait_stream(c->stream));
-    sbs_finish(S->h_sbs.p(), channels, tallies);
-    return S->tm.add_elapsed(c, &S->sbs_ms);
+    if ((rc = S->sbs.finish(c, &S->sbs_ms))) return rc;
+    sbs_finish(S->sbs.h.p(), channels, tallies);
+    return MSIM_OK;
 }
 
 // leaves the contig planned as plan_device (vcf_parse.hip) does: an SNP-only table of host-known size, no insert pool
